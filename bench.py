@@ -19,20 +19,24 @@ rank), work per GPU fixed as N grows.  --scaling strong: ONE dataset of `--reads
 contiguous block ranges (cbc_amd.shard.shard_ranges); the container gathered on rank 0 is checked byte
 for byte against a single-GPU encode of the whole dataset.
 
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes what
+the last timed step computed (dump_outputs).  What the headline figure does not need runs only with --full,
+after the headline region (cpu_baseline, e2e, cfg4 below; null or absent otherwise).
+
 Prints ONE JSON line on rank 0 (see the task contract), with extra objects:
   roofline     -- algorithmic bytes (2*L+18 per read) / HIP-event kernel time vs 8 TB/s,
                   plus `issue`: the instruction-issue picture of the committed SQ counter pass (nulled
                   when that pass was taken from other kernel sources than the ones built here)
-  cpu_baseline -- CPU legs timed single-threaded on this host on a bounded sample of the same workload
+  cpu_baseline -- --full: CPU legs timed single-threaded on this host on a bounded sample of the same workload
                   (N=1, rank 0 only): the oracle on SAM text (parse included) and the packed-input CPU
                   port (parse excluded).  The CPU port codes the very blocks the GPU coded and its bytes
                   are compared with the GPU's: `verified_vs_cpu_port` (the run fails on a mismatch)
-  e2e          -- SURVEY 8d's other two timed regions, measured in the run outside the headline region
+  e2e          -- --full: SURVEY 8d's other two timed regions, measured in the run outside the headline region
                   (N=1): the host-buffer entry point (PCIe included) and the `cbc` CLI on SAM text
   rccl         -- N > 1: backend, world size, per-rank device / kernel ms / payload bytes, and the
                   checksum every rank took of its payload on the device before the gather next to the
                   one rank 0 recomputed on what the collective delivered (the run fails on a mismatch)
-  cfg4         -- N > 1: BASELINE config 4 (GRCh38-shaped, chromosome-sharded, strong scaling) run
+  cfg4         -- --full, N > 1: BASELINE config 4 (GRCh38-shaped, chromosome-sharded, strong scaling) run
                   after the headline region through the same exchange, so that one SCALE run reports it
 """
 import argparse
@@ -87,10 +91,16 @@ def parse_args(argv=None):
                          "(the payloads are produced by one untimed encode launch and checked to decode to the packed bases)")
     ap.add_argument("--force-dist", action="store_true",
                     help="N = 1 only: build the one-rank process group anyway and go through every collective of the N > 1 path "
-                         "(gather of the bitstreams, checksum exchange, cfg4 pass) -- how the RCCL call sites are rehearsed on a one-GPU box")
+                         "(gather of the bitstreams, checksum exchange, with --full the cfg4 pass) -- how the RCCL call sites are rehearsed "
+                         "on a one-GPU box")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the real path); gloo = rehearsal of the N>1 host logic when "
                          "several ranks must share one GPU (payloads take a detour through host memory)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the headline region: the CPU legs and the check "
+                         "of the GPU's bytes against the CPU port (N = 1), the PCIe-inclusive and CLI legs (N = 1), the cfg4 pass (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy in float32 / float64")
     a = ap.parse_args(argv)
     if a.workload == "cfg5":                                  # one 100 Mb contig, 1 M x 10 kb, 5 % edits
         if a.reads == 10_000_000:
@@ -214,6 +224,39 @@ def issue_picture(root, which, kernel_ms, n_recs):
                     if sq.get(key):
                         issue[name] = round(sq[key] / sq["SQ_WAVE_CYCLES"], 3)
     return pm.get("hbm_bytes_per_launch"), src, issue
+
+
+DUMP_SAMPLE_BYTES = 1 << 22     # --dump-outputs: bytes kept of a larger byte output (as float32: 16 MB per output)
+DUMP_CRC_CHUNK = 1 << 20        # --dump-outputs: a byte output's CRC-32 is taken per chunk of this many bytes
+
+
+def dump_outputs(dirname, byte_outputs, tables):
+    """--dump-outputs: what the timed path returned in its last step, as DIR/<name>.npy, so that two builds can be compared
+    output for output.  A byte output (bitstreams, decoded bases / records; a tensor on any device) is written as
+    <name>.npy, float32: all of it up to DUMP_SAMPLE_BYTES bytes, else the bytes at DUMP_SAMPLE_BYTES positions drawn with
+    a fixed seed (sorted; the same positions for the same size), and as <name>_crc32.npy, float64: the CRC-32 of every
+    DUMP_CRC_CHUNK bytes of the whole output, so that a change anywhere shows.  A table (per-block results, offsets) is
+    written field by field as <name>[_<field>].npy, float64 (integers exact up to 2**53)."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in byte_outputs.items():
+        n = t.numel()
+        if n <= DUMP_SAMPLE_BYTES:
+            sample = t.cpu().numpy()
+        else:
+            idx = np.sort(np.random.default_rng(0xCBC0D).integers(0, n, DUMP_SAMPLE_BYTES))
+            sample = t[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), sample.astype(np.float32))
+        crcs, piece = [], 256 * DUMP_CRC_CHUNK                   # copied to the host a piece at a time
+        for p in range(0, n, piece):
+            h = t[p:p + piece].cpu().numpy()
+            crcs += [zlib.crc32(h[c:c + DUMP_CRC_CHUNK]) for c in range(0, h.size, DUMP_CRC_CHUNK)]
+        np.save(os.path.join(dirname, name + "_crc32.npy"), np.array(crcs, dtype=np.float64))
+    for name, a in tables.items():
+        for f in a.dtype.names or [None]:
+            np.save(os.path.join(dirname, name + ("_" + f if f else "") + ".npy"), (a if f is None else a[f]).astype(np.float64))
 
 
 class Rank:
@@ -541,10 +584,18 @@ def run_rank(args, R):
     if default_shape:
         traffic, traffic_src, issue = issue_picture(ROOT, ("long_" if long_fmt else "") + args.mode + "_pmc", k_ms, n_recs)
 
+    if args.dump_outputs and rank == 0:
+        if args.mode == "encode":
+            dump_outputs(args.dump_outputs, {"payload": d_packed[:payload_bytes]},
+                         {"payload_offsets": d_offs[:my_blocks + 1].cpu().numpy(), "block_results": d_res.cpu().numpy().view(host.RESULT_DTYPE)[b0:b1]})
+        else:
+            dump_outputs(args.dump_outputs, {"decoded_bases": dec["seq"], "decoded_records": dec["recs"]},
+                         {"block_results": dec["res"].cpu().numpy().view(host.RESULT_DTYPE)})
+
     cpu = None
     whole_file_bits = None
     verified = None
-    if rank == 0 and world == 1 and not multi and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not multi and not args.no_cpu_baseline:
         from oracle import oracle                            # the checker, also timed as the reported baseline
         # parse excluded + verification: the CPU port codes the VERY blocks the GPU coded (same packed batch), bounded by
         # --cpu-sample-reads; its bytes must equal the GPU's compacted payload over those blocks
@@ -588,11 +639,11 @@ def run_rank(args, R):
             spb.close()
 
     e2e = None
-    if rank == 0 and world == 1 and not multi and not args.no_e2e and not long_fmt and args.mode == "encode":
+    if args.full and rank == 0 and world == 1 and not multi and not args.no_e2e and not long_fmt and args.mode == "encode":
         e2e = e2e_legs(args, enc, pb, first_payload, offs_first)
 
     cfg4 = None
-    if multi and not args.no_cfg4 and not long_fmt and args.mode == "encode":
+    if args.full and multi and not args.no_cfg4 and not long_fmt and args.mode == "encode":
         del d_recs, d_seq, d_tok, d_out, d_packed, first_payload
         torch.cuda.empty_cache()
         cfg4 = cfg4_pass(args, R, args.scale if args.scale is not None else 0.1)
@@ -848,6 +899,10 @@ def cfg4_pass(args, R, scale):
     elapsed = time.perf_counter() - t_start
     if not torch.equal(flat[:payload], first_flat):
         raise SystemExit("bench.py (cfg4): the timed launches did not reproduce the first launch's bitstreams")
+    if args.dump_outputs and rank == 0 and args.workload == "cfg4":
+        dump_outputs(args.dump_outputs, {"payload": flat[:payload]},
+                     {"contig_payload_bytes": np.array([C["bytes"] for C in res_list]),
+                      "block_results": np.concatenate([C["res"].cpu().numpy().view(host.RESULT_DTYPE) for C in res_list])})
     tot = torch.tensor([float(n_bases), float(n_recs), float(n_blocks), float(payload), elapsed], dtype=torch.float64, device=cdev)
     table = None
     if multi:

@@ -453,12 +453,12 @@ def test_blocks_at_the_cap_limits(enc, built):
 def test_bench_launched_bare_with_two_ranks(built, scaling):
     """`python bench.py --gpus 2` exactly as the driver starts it (no torch.distributed.run): the parent spawns
     its own ranks.  Two ranks share the one GPU of this box, so the collectives go over gloo; strong scaling
-    checks the gathered container against the single-GPU container inside the run."""
+    checks the gathered container against the single-GPU container inside the run; --full adds the cfg4 pass."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--reads", "300000",
-                        "--contig-len", "8000000", "--steps", "2", "--warmup", "1", "--scaling", scaling, "--no-cpu-baseline"],
+                        "--contig-len", "8000000", "--steps", "2", "--warmup", "1", "--scaling", scaling, "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -467,6 +467,61 @@ def test_bench_launched_bare_with_two_ranks(built, scaling):
     assert j["n_gpus"] == 2 and j["scaling"] == scaling and j["value"] > 0
     if scaling == "strong":
         assert j["config"]["gathered_equals_single_gpu"] is True
+
+
+def test_bench_plain_full_and_dump_outputs(built, tmp_path):
+    """A plain `bench.py --gpus 1` run times its steps and nothing else (no CPU legs, no e2e legs); --dump-outputs writes
+    the last step's bitstreams and per-block results, float32 / float64, identical from run to run; --full adds the CPU
+    legs, whose check of the GPU's bytes against the CPU port must pass."""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--reads", "300000", "--contig-len", "8000000",
+            "--steps", "3", "--warmup", "1"]
+    runs = []
+    for extra in (["--dump-outputs", str(tmp_path / "a")], ["--dump-outputs", str(tmp_path / "b"), "--full", "--cpu-sample-reads", "50000"]):
+        r = subprocess.run(base + extra, capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        runs.append(json.loads(lines[0]))
+    plain, full = runs
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert plain["cpu_baseline"] is None and plain["verified_vs_cpu_port"] is None and "e2e" not in plain
+    assert full["cpu_baseline"] is not None and full["verified_vs_cpu_port"] is True and "e2e" in full
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"payload.npy", "payload_crc32.npy", "payload_offsets.npy", "block_results_status.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    offs = np.load(tmp_path / "a" / "payload_offsets.npy")
+    assert offs[-1] == plain["config"]["payload_bytes_rank0"] and len(offs) == plain["config"]["blocks_rank0"] + 1
+    assert (np.load(tmp_path / "a" / "block_results_status.npy") == 0).all()
+
+
+@pytest.mark.parametrize("extra,expect", [
+    (["--mode", "decode", "--reads", "300000", "--contig-len", "8000000"], ["decoded_bases.npy", "decoded_bases_crc32.npy", "decoded_records.npy", "block_results_status.npy"]),
+    (["--workload", "cfg5", "--reads", "2000", "--contig-len", "2000000"], ["payload.npy", "payload_crc32.npy", "block_results_status.npy"]),
+    (["--workload", "cfg4", "--scale", "0.001"], ["payload.npy", "payload_crc32.npy", "contig_payload_bytes.npy", "block_results_status.npy"]),
+])
+def test_bench_dump_outputs_other_paths(built, tmp_path, extra, expect):
+    """--dump-outputs on the decode path, the long-read path and the cfg4 workload: every block reports success and the
+    arrays are float32 / float64 within 64 MB."""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)] + extra, capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    names = os.listdir(tmp_path)
+    assert set(expect) <= set(names), names
+    arrays = [np.load(tmp_path / n) for n in names]
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays) and sum(a.nbytes for a in arrays) <= 64 << 20
+    assert (np.load(tmp_path / "block_results_status.npy") == 0).all()
 
 
 def test_cli_several_devices(built, tmp_path):

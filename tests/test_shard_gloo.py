@@ -196,3 +196,34 @@ def test_checksum_twin_and_cfg4_generator(built):
     per_contig = [int(sum(int(pb.info[b]["n_reads"]) for b in range(pb.n_blocks) if int(pb.info[b]["contig"]) == c)) for c in range(6)]
     for n in (1, 2, 3, 8):
         assert list(pb.assign_contigs(n)) == bench.assign_largest_first(per_contig, n)
+
+
+def test_bench_dump_outputs_format(tmp_path):
+    """bench.py --dump-outputs on host tensors: a small byte output whole, a large one as a fixed seeded sample (the same
+    positions run to run) plus the CRC-32 of every chunk of all of it; tables field by field; float32 / float64 only."""
+    import zlib
+    import torch
+    import bench
+    from cbc_amd import host
+    rng = np.random.default_rng(9)
+    big = rng.integers(0, 256, bench.DUMP_SAMPLE_BYTES + 3 * bench.DUMP_CRC_CHUNK + 17, dtype=np.uint8)
+    small = rng.integers(0, 256, 1000, dtype=np.uint8)
+    res = np.zeros(3, host.RESULT_DTYPE)
+    res["nbytes"] = [5, 6, 7]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": torch.from_numpy(big), "small": torch.from_numpy(small)},
+                           {"offsets": np.array([0, 5, 11, 18], dtype=np.int64), "res": res})
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["big.npy", "big_crc32.npy", "offsets.npy", "res_fail_read.npy", "res_n_symbols.npy", "res_nbytes.npy",
+                     "res_status.npy", "small.npy", "small_crc32.npy"]
+    for n in names:
+        a = np.load(tmp_path / "a" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, np.load(tmp_path / "b" / n)), n
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small.astype(np.float32))
+    s = np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and s.size == bench.DUMP_SAMPLE_BYTES and np.isin(s, np.arange(256)).all()
+    crc = np.load(tmp_path / "a" / "big_crc32.npy")
+    want = [zlib.crc32(big[c:c + bench.DUMP_CRC_CHUNK].tobytes()) for c in range(0, big.size, bench.DUMP_CRC_CHUNK)]
+    assert crc.dtype == np.float64 and crc.tolist() == want
+    assert np.load(tmp_path / "a" / "res_nbytes.npy").tolist() == [5, 6, 7]
+    assert np.load(tmp_path / "a" / "offsets.npy").tolist() == [0, 5, 11, 18]

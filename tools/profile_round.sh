@@ -21,7 +21,7 @@ for leg in $legs; do
     *) echo "unknown leg $leg"; exit 2 ;;
   esac
   P=$O/${tag}_${leg}
-  python3 $R/bench.py $args --no-e2e > ${P}_bench.log 2>&1; tail -1 ${P}_bench.log > ${P}_bench.json
+  python3 $R/bench.py $args --full --no-e2e > ${P}_bench.log 2>&1; tail -1 ${P}_bench.log > ${P}_bench.json
   rm -rf $O/prof_${tag}_${leg}
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${tag}_${leg} -o p -- python3 $R/bench.py $args --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > ${P}_rp.log 2>&1
   tail -1 ${P}_rp.log > ${P}_bench_under_rocprof.json
