@@ -998,8 +998,12 @@ struct CbcDec {
 /* ===========================================================================================
  * cbc_decode_stream: decode block `blk` completely.
  * =========================================================================================== */
-template <class W>
-CBC_FN void cbc_decode_stream(const cbc_dec_args &A, uint32_t blk, uint32_t *lds)
+/* SPAN = true (region decode, cbc_gpu_decode_region): the fourth word of every record (cbc_read_rec.tok_off, 0 otherwise)
+ * receives the read's span -- the reference bases its reconstruction covers: rl for a read coded as perfect, rl + nDel - nIns
+ * for any other -- and a span above `smax` fails the block with CBC_ST_SPAN, so the bound the block selection rests on is
+ * checked on every decode that relies on it.  The default instantiation is the plain decoder, unchanged. */
+template <class W, bool SPAN = false>
+CBC_FN void cbc_decode_stream(const cbc_dec_args &A, uint32_t blk, uint32_t *lds, uint32_t smax = 0u)
 {
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
@@ -1154,7 +1158,12 @@ CBC_FN void cbc_decode_stream(const cbc_dec_args &A, uint32_t blk, uint32_t *lds
     };
     auto ph_store = [&](uint32_t r) {
         CBC_DT(5);                                            /* copy / edits + reconstruction */
-        V32 rv0 = W::splat(pos), rv1 = W::splat(flag | (rl << 16)), rv2 = W::splat(r * stride), rv3 = W::splat(0u);
+        uint32_t span = 0u;
+        if constexpr (SPAN) {                                 /* nIns <= rl (indel_counts): no wrap */
+            span = match ? rl : rl + nDel - nIns;
+            if (span > smax) { D.fail(CBC_ST_SPAN); return; }
+        }
+        V32 rv0 = W::splat(pos), rv1 = W::splat(flag | (rl << 16)), rv2 = W::splat(r * stride), rv3 = W::splat(span);
         W::store_rec(recs4, W::splat(r), ln == 0u, rv0, rv1, rv2, rv3);
         CBC_DT(6);                                            /* record store */
     };
@@ -1210,6 +1219,7 @@ CBC_FN void cbc_decode_stream(const cbc_dec_args &A, uint32_t blk, uint32_t *lds
                 nSnp = D.dense_dec_low(D.tab(CBC_LDS_SNPS), L0, 10u, D.snps_n);
                 if (!ok()) continue;
                 if (nSnp == 0u) { defer = 2u; continue; }        /* three more counts follow: a read with indels */
+                if constexpr (SPAN) { nDel = 0u; nIns = 0u; }    /* the counts of an earlier read with indels */
                 D.edits_snp(rl, strand, nSnp, refw, dst);
                 if (!ok()) continue;
             }

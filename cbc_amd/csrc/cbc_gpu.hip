@@ -19,6 +19,7 @@
 #include "cbc_wave_gpu.h"
 #include "cbc_encode_body.h"
 #include "cbc_decode_body.h"
+#include "cbc_region_body.h"
 #include "cbc_plan.h"
 #include "cbc_stream_body.h"
 #include "cbc_long_body.h"
@@ -65,6 +66,27 @@ cbc_decode_blocks_kernel(cbc_dec_args A)
     uint32_t blk = blockIdx.x;
     if (blk >= A.n_blocks) return;
     cbc_decode_stream<WaveGPU>(A, blk, cbc_lds);
+}
+
+/* region decode (cbc_gpu_decode_region): the same decoder with each read's span in cbc_read_rec.tok_off, checked against
+ * smax; then the filter (one wavefront per block) and the text assembly (CBC_REGION_WAVES wavefronts per block) */
+__global__ void __launch_bounds__(64)
+cbc_decode_blocks_span_kernel(cbc_dec_args A, uint32_t smax)
+{
+    uint32_t blk = blockIdx.x;
+    if (blk >= A.n_blocks) return;
+    cbc_decode_stream<WaveGPU, true>(A, blk, cbc_lds, smax);
+}
+
+__global__ void __launch_bounds__(64)
+cbc_region_count_kernel(cbc_region_args A) { if (blockIdx.x < A.n_blocks) cbc_region_count<WaveGPU>(A, blockIdx.x); }
+
+#define CBC_REGION_WAVES 4u
+__global__ void __launch_bounds__(64 * CBC_REGION_WAVES)
+cbc_region_write_kernel(cbc_region_args A)
+{
+    if (blockIdx.x >= A.n_blocks) return;
+    cbc_region_write<WaveGPU>(A, blockIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), CBC_REGION_WAVES);
 }
 
 /* Whole-file stream / general-form fallback (cbc_stream_body.h): one wavefront per stream.  Workgroup w codes streams
@@ -222,7 +244,7 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
 /* grow-only device buffer owned by the context: the host-buffer entry points keep their device arrays between calls
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
-enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_COUNT };
+enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_COUNT };
 #define CBC_MAX_CHUNKS 8
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
@@ -233,6 +255,8 @@ struct cbc_gpu_ctx {
     hipStream_t s_k[CBC_N_KSTREAMS];   /* their kernel launches, chunk c on stream c % CBC_N_KSTREAMS */
     hipEvent_t ev0, ev1;
     hipEvent_t ev_chunk[CBC_MAX_CHUNKS], ev_done[CBC_N_KSTREAMS];
+    hipEvent_t ev_rg[4];           /* region decode: before and after the decode, after the filter + scan, after the text kernel */
+    int have_region_timing;
     int have_timing;
     int last_variant;              /* waves per SIMD of the encode build launched last */
     int n_cus;                     /* compute units of the device (block residency decides the kernel build) */
@@ -293,6 +317,8 @@ API int cbc_gpu_init(int device_ordinal, cbc_gpu_ctx **out)
             hipEventCreateWithFlags(&ctx->ev_done[k], hipEventDisableTiming) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     for (int k = 0; k < CBC_MAX_CHUNKS; k++)
         if (hipEventCreateWithFlags(&ctx->ev_chunk[k], hipEventDisableTiming) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
+    for (int k = 0; k < 4; k++)
+        if (hipEventCreate(&ctx->ev_rg[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) != hipSuccess || cus <= 0) cus = 256;
@@ -302,6 +328,7 @@ API int cbc_gpu_init(int device_ordinal, cbc_gpu_ctx **out)
     (void)hipFuncSetAttribute((const void *)cbc_encode_blocks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)cbc_encode_blocks_kernel_w6, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)cbc_decode_blocks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void *)cbc_decode_blocks_span_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)cbc_encode_whole_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)cbc_long_encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)cbc_long_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -319,6 +346,7 @@ API int cbc_gpu_shutdown(cbc_gpu_ctx *ctx)
     for (int k = 0; k < A_COUNT; k++) if (ctx->arena[k].p) (void)hipFree(ctx->arena[k].p);
     (void)hipEventDestroy(ctx->ev0); (void)hipEventDestroy(ctx->ev1);
     for (int k = 0; k < CBC_MAX_CHUNKS; k++) (void)hipEventDestroy(ctx->ev_chunk[k]);
+    for (int k = 0; k < 4; k++) (void)hipEventDestroy(ctx->ev_rg[k]);
     for (int k = 0; k < CBC_N_KSTREAMS; k++) { (void)hipEventDestroy(ctx->ev_done[k]); (void)hipStreamDestroy(ctx->s_k[k]); }
     (void)hipStreamDestroy(ctx->s_copy);
     (void)hipStreamDestroy(ctx->stream);
@@ -897,7 +925,8 @@ API int cbc_gpu_group_gather(cbc_gpu_group *g, uint8_t *out, uint64_t out_cap, u
  * ---------------------------------------------------------------------------------------------- */
 API uint32_t cbc_gpu_decode_lds_bytes(const cbc_lds_caps *caps) { return caps ? cbc_plan_dec_lds_bytes(caps) : 0; }
 
-API int cbc_gpu_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device_batch *b, void *hip_stream)
+/* smax = 0: the plain decoder; otherwise the span-reporting one (region decode) */
+static int decode_blocks_launch(cbc_gpu_ctx *ctx, const cbc_dec_device_batch *b, void *hip_stream, uint32_t smax)
 {
     if (!ctx || !b) return CBC_E_ARG;
     if (b->n_blocks == 0) return CBC_OK;
@@ -915,21 +944,34 @@ API int cbc_gpu_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device_batc
     A.n_blocks = b->n_blocks; A.cap_pos = b->caps.cap_pos; A.cap_var = b->caps.cap_var;
     A.var_scratch = b->d_var_scratch; A.var_scratch_words = b->var_scratch_words;
     HIPCHK(hipEventRecord(ctx->ev0, s), "hipEventRecord");
-    hipLaunchKernelGGL(cbc_decode_blocks_kernel, dim3(b->n_blocks), dim3(64), lds, s, A);
+    if (smax) hipLaunchKernelGGL(cbc_decode_blocks_span_kernel, dim3(b->n_blocks), dim3(64), lds, s, A, smax);
+    else hipLaunchKernelGGL(cbc_decode_blocks_kernel, dim3(b->n_blocks), dim3(64), lds, s, A);
     HIPCHK(hipGetLastError(), "launch cbc_decode_blocks_kernel");
     HIPCHK(hipEventRecord(ctx->ev1, s), "hipEventRecord");
     ctx->have_timing = 1;
     return CBC_OK;
 }
 
+API int cbc_gpu_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device_batch *b, void *hip_stream)
+{
+    return decode_blocks_launch(ctx, b, hip_stream, 0u);
+}
+
 /* The host-buffer decode path as a pipeline, mirror of encode_blocks_impl: the payloads (2 bytes per read) go H2D at once;
  * the blocks are decoded in chunks on the two kernel streams, and chunk c's records and bases (bytes, or 2-bit rows packed by
  * cbc_pack_2bit_kernel) come back on the copy stream while the later chunks are still being decoded.  Device arrays are the
  * context's arenas. */
+/* region decode's part of decode_blocks_impl: the span bound, the region, where the text goes and what came of it
+ * (text_bytes == NULL: the span decode alone, records and rows come back as in a plain decode) */
+struct region_req {
+    const uint64_t *window_start; uint64_t beg, end; uint32_t smax;
+    uint8_t *text; uint64_t text_cap; uint64_t *text_bytes, *n_selected;
+};
+
 static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, cbc_dec_block_desc *blocks,
                               uint32_t n_blocks, const cbc_lds_caps *caps, cbc_read_rec *recs, uint64_t n_recs,
                               uint8_t *seq, uint64_t seq_bytes, uint32_t *codes_out, uint64_t *exc_idx, uint8_t *exc_val,
-                              uint64_t exc_cap, uint64_t *n_exc, cbc_block_result *results)
+                              uint64_t exc_cap, uint64_t *n_exc, cbc_block_result *results, const region_req *rg = NULL)
 {
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     const double T0 = wall_now();
@@ -941,6 +983,8 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     const uint64_t vs_words = (uint64_t)n_blocks * caps->cap_var;
     const uint64_t n_words = two_bit ? n_recs * (stride >> 4) : 0;
     unsigned long long got = 0;
+    cbc_block_result *cnt = NULL;                             /* region decode: the filter's per-block counts */
+    uint64_t total = 0, kept = 0;
 #define GO(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = set_err(ctx, CBC_E_NODEV, what, e_); goto done; } } while (0)
 #define NEED(k, bytes, what) do { rc = arena_need(ctx, k, bytes, what); if (rc) goto done; } while (0)
     NEED(A_VS, vs_words * 4 + 16, "hipMalloc var scratch");
@@ -955,6 +999,12 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         NEED(A_EXC_V, (exc_cap ? exc_cap : 1), "hipMalloc exceptions");
         NEED(A_CNT, 8, "hipMalloc counter");
     }
+    if (rg && rg->text_bytes) {
+        NEED(A_TEXT, rg->text_cap + 16, "hipMalloc region text");
+        NEED(A_RWS, (uint64_t)n_blocks * 8, "hipMalloc window starts");
+        NEED(A_RCNT, (uint64_t)n_blocks * sizeof(cbc_block_result), "hipMalloc region counts");
+        NEED(A_OFF, ((uint64_t)n_blocks + 1) * 8, "hipMalloc region offsets");
+    }
     tm.alloc_s = wall_now() - T0;
     {
         uint8_t *d_in = (uint8_t *)ctx->arena[A_IN].p, *d_seq = (uint8_t *)ctx->arena[A_SEQ].p;
@@ -967,6 +1017,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         GO(hipMemcpyAsync(d_blocks, blocks, (uint64_t)n_blocks * sizeof(cbc_dec_block_desc), hipMemcpyHostToDevice, sc), "H2D blocks");
         GO(hipMemsetAsync(d_res, 0xff, (uint64_t)n_blocks * sizeof(cbc_block_result), sc), "memset results");
         if (two_bit) GO(hipMemsetAsync(ctx->arena[A_CNT].p, 0, 8, sc), "memset counter");
+        if (rg && rg->text_bytes) GO(hipMemcpyAsync(ctx->arena[A_RWS].p, rg->window_start, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D window starts");
         GO(hipEventRecord(ctx->ev_done[0], sc), "hipEventRecord");       /* inputs are on the device */
         tm.h2d_bytes = in_bytes + (uint64_t)n_blocks * sizeof(cbc_dec_block_desc);
         /* chunks of consecutive blocks whose outputs are consecutive too */
@@ -975,7 +1026,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         for (uint32_t b = 0; b + 1 < n_blocks && contiguous; b++)
             contiguous = blocks[b + 1].rec_base == blocks[b].rec_base + blocks[b].n_reads && blocks[b + 1].seq_base >= blocks[b].seq_base;
         contiguous = contiguous && blocks[n_blocks - 1].rec_base + blocks[n_blocks - 1].n_reads <= n_recs && blocks[n_blocks - 1].seq_base <= seq_bytes;
-        if (contiguous && n_blocks >= 512) {
+        if (contiguous && n_blocks >= 512 && !(rg && rg->text_bytes)) {          /* region decode: nothing comes back before the text is built */
             uint64_t want = (n_recs * 16 + (two_bit ? n_words * 4 : seq_bytes)) / (64ull << 20);
             if (want > CBC_MAX_CHUNKS) want = CBC_MAX_CHUNKS;
             if (want > n_blocks / 256) want = n_blocks / 256;
@@ -1003,8 +1054,27 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
             db.d_seq = d_seq; db.seq_bytes = seq_bytes + 32; db.d_results = d_res + c0;
             db.caps = *caps; db.d_var_scratch = (uint32_t *)ctx->arena[A_VS].p + (uint64_t)c0 * caps->cap_var;
             db.var_scratch_words = (uint64_t)(c1 - c0) * caps->cap_var;
-            rc = cbc_gpu_decode_blocks_device(ctx, &db, ks);
+            if (rg && rg->text_bytes) GO(hipEventRecord(ctx->ev_rg[0], ks), "hipEventRecord");
+            rc = decode_blocks_launch(ctx, &db, ks, rg ? rg->smax : 0u);
             if (rc) goto done;
+            if (rg && rg->text_bytes) {                        /* one chunk: filter, scan, text on the decode's stream */
+                GO(hipEventRecord(ctx->ev_rg[1], ks), "hipEventRecord");
+                cbc_region_args ra;
+                memset(&ra, 0, sizeof ra);
+                ra.recs = d_recs; ra.seq = d_seq; ra.blocks = d_blocks; ra.window_start = (const uint64_t *)ctx->arena[A_RWS].p;
+                ra.dec_results = d_res; ra.counts = (cbc_block_result *)ctx->arena[A_RCNT].p; ra.offsets = (const uint64_t *)ctx->arena[A_OFF].p;
+                ra.text = (uint8_t *)ctx->arena[A_TEXT].p; ra.text_cap = rg->text_cap; ra.n_recs = n_recs; ra.seq_bytes = seq_bytes + 32;
+                ra.beg = rg->beg; ra.end = rg->end; ra.n_blocks = n_blocks;
+                hipLaunchKernelGGL(cbc_region_count_kernel, dim3(n_blocks), dim3(64), 0, ks, ra);
+                GO(hipGetLastError(), "launch cbc_region_count_kernel");
+                hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_blocks);
+                GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+                GO(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+                hipLaunchKernelGGL(cbc_region_write_kernel, dim3(n_blocks), dim3(64 * CBC_REGION_WAVES), 0, ks, ra);
+                GO(hipGetLastError(), "launch cbc_region_write_kernel");
+                GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+                ctx->have_region_timing = 1;
+            }
             const uint64_t r0 = whole ? 0 : blocks[c0].rec_base, r1 = whole ? n_recs : blocks[c1 - 1].rec_base + blocks[c1 - 1].n_reads;
             if (two_bit && r1 > r0) {
                 const uint64_t w0 = r0 * (stride >> 4), w1 = r1 * (stride >> 4);
@@ -1016,7 +1086,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
             GO(hipEventRecord(ctx->ev_chunk[c], ks), "hipEventRecord");
         }
         tm.issue_s = wall_now() - T0;
-        for (uint32_t c = 0; c < n_chunks; c++) {                 /* the chunks come back in order while later ones are being decoded */
+        for (uint32_t c = 0; c < n_chunks && !(rg && rg->text_bytes); c++) {          /* the chunks come back in order while later ones are being decoded */
             const uint32_t c0 = cut[c], c1 = cut[c + 1];
             const bool whole = !contiguous || n_chunks == 1;
             const uint64_t r0 = whole ? 0 : blocks[c0].rec_base, r1 = whole ? n_recs : blocks[c1 - 1].rec_base + blocks[c1 - 1].n_reads;
@@ -1035,10 +1105,27 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         }
         res = results ? results : (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
         if (!res) { rc = CBC_E_NOMEM; goto done; }
+        if (rg && rg->text_bytes) GO(hipStreamWaitEvent(sc, ctx->ev_chunk[0], 0), "hipStreamWaitEvent");
         GO(hipMemcpyAsync(res, d_res, (uint64_t)n_blocks * sizeof(cbc_block_result), hipMemcpyDeviceToHost, sc), "D2H results");
         if (two_bit) GO(hipMemcpyAsync(&got, ctx->arena[A_CNT].p, 8, hipMemcpyDeviceToHost, sc), "D2H counter");
+        if (rg && rg->text_bytes) {
+            cnt = (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
+            if (!cnt) { rc = CBC_E_NOMEM; goto done; }
+            GO(hipMemcpyAsync(cnt, ctx->arena[A_RCNT].p, (uint64_t)n_blocks * sizeof(cbc_block_result), hipMemcpyDeviceToHost, sc), "D2H region counts");
+            GO(hipMemcpyAsync(&total, (uint64_t *)ctx->arena[A_OFF].p + n_blocks, 8, hipMemcpyDeviceToHost, sc), "D2H text size");
+        }
         GO(hipStreamSynchronize(sc), "decode kernel");
         tm.kernels_done_s = wall_now() - T0;
+        if (rg && rg->text_bytes) {
+            for (uint32_t b = 0; b < n_blocks; b++) kept += cnt[b].n_symbols;
+            *rg->text_bytes = total; *rg->n_selected = kept;
+            if (total > rg->text_cap) { rc = set_err(ctx, CBC_E_ARG, "text_cap too small for the region's text", hipSuccess); goto done; }
+            if (total) {                                       /* the one copy of the output: exactly its size */
+                GO(hipMemcpyAsync(rg->text, ctx->arena[A_TEXT].p, total, hipMemcpyDeviceToHost, sc), "D2H region text");
+                GO(hipStreamSynchronize(sc), "D2H region text");
+            }
+            tm.d2h_bytes = total;
+        }
         if (two_bit) {
             *n_exc = got;
             if (got > exc_cap) { rc = set_err(ctx, CBC_E_ARG, "more non-ACGT bases than exc_cap", hipSuccess); goto done; }
@@ -1060,6 +1147,7 @@ done:
 #undef NEED
     if (rc && rc != CBC_E_BLOCK) (void)hipDeviceSynchronize();
     if (res && res != results) free(res);
+    free(cnt);
     tm.total_s = wall_now() - T0;
     ctx->last_e2e = tm;
     return rc;
@@ -1073,6 +1161,67 @@ API int cbc_gpu_decode_blocks(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
     if (n_blocks == 0) return CBC_OK;
     return decode_blocks_impl(ctx, in, in_bytes, blocks, n_blocks, caps, recs, n_recs, seq, seq_bytes, NULL, NULL, NULL, 0, NULL, results);
+}
+
+/* region decode: the selected blocks are laid out afresh (payload range, records and rows from 0), decoded with the spans
+ * reported, filtered and assembled into text on the device (cbc_region_body.h) */
+API int cbc_gpu_decode_region(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                              uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                              uint64_t beg, uint64_t end, uint32_t smax, uint8_t *text, uint64_t text_cap,
+                              uint64_t *text_bytes, uint64_t *n_selected, cbc_block_result *results)
+{
+    if (!ctx || !blocks || !caps || !window_start || !text_bytes || !n_selected || (text_cap && !text)) return CBC_E_ARG;
+    *text_bytes = 0; *n_selected = 0;
+    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (n_blocks == 0) return CBC_OK;
+    if (!in) return CBC_E_ARG;
+    if (smax == 0 || beg < 1 || beg > end) return set_err(ctx, CBC_E_ARG, "region decode wants 1 <= beg <= end and smax > 0", hipSuccess);
+    const uint32_t stride = blocks[0].seq_stride;
+    if (stride < 4 || stride > 256 || (stride & 3u)) return set_err(ctx, CBC_E_ARG, "region decode wants seq_stride in 4..256, a multiple of 4", hipSuccess);
+    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)n_blocks * sizeof(cbc_dec_block_desc));
+    if (!bl) return CBC_E_NOMEM;
+    uint64_t in0 = UINT64_MAX, in1 = 0, nrec = 0;
+    for (uint32_t b = 0; b < n_blocks; b++) {                  /* no sums of caller values that could wrap */
+        const cbc_dec_block_desc *d = &blocks[b];
+        if (d->seq_stride != stride || d->in_off > in_bytes || d->in_bytes > in_bytes - d->in_off || d->n_reads > CBC_MAX_BLOCK_READS) {
+            free(bl); return set_err(ctx, CBC_E_ARG, "region decode: block out of range of `in`, or strides differ", hipSuccess); }
+        if (d->in_off < in0) in0 = d->in_off;
+        if (d->in_off + d->in_bytes > in1) in1 = d->in_off + d->in_bytes;
+    }
+    for (uint32_t b = 0; b < n_blocks; b++) {
+        bl[b] = blocks[b];
+        bl[b].in_off -= in0; bl[b].rec_base = nrec; bl[b].seq_base = nrec * stride;
+        nrec += bl[b].n_reads;
+    }
+    const uint64_t need = nrec * (stride + 1ull);               /* every read kept: rl + 1 <= stride + 1 bytes each */
+    region_req rg = { window_start, beg, end, smax, text, text_cap < need ? text_cap : need, text_bytes, n_selected };
+    int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
+                                nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
+    free(bl);
+    return rc;
+}
+
+API int cbc_gpu_decode_blocks_span(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, cbc_dec_block_desc *blocks,
+                                   uint32_t n_blocks, const cbc_lds_caps *caps, uint32_t smax, cbc_read_rec *recs, uint64_t n_recs,
+                                   uint8_t *seq, uint64_t seq_bytes, cbc_block_result *results)
+{
+    if (!ctx || !in || !blocks || !caps || !recs || !seq || smax == 0) return CBC_E_ARG;
+    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (n_blocks == 0) return CBC_OK;
+    region_req rg;
+    memset(&rg, 0, sizeof rg);
+    rg.smax = smax;
+    return decode_blocks_impl(ctx, in, in_bytes, blocks, n_blocks, caps, recs, n_recs, seq, seq_bytes, NULL, NULL, NULL, 0, NULL, results, &rg);
+}
+
+API int cbc_gpu_last_region_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *text_ms)
+{
+    if (!ctx || !decode_ms || !filter_ms || !text_ms || !ctx->have_region_timing) return CBC_E_ARG;
+    HIPCHK(hipEventSynchronize(ctx->ev_rg[3]), "hipEventSynchronize");
+    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(filter_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(text_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
+    return CBC_OK;
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -1673,7 +1673,8 @@ static uint64_t r64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; 
 API void cbc_unpack_plan_free(cbc_unpack_plan *u)
 {
     if (!u) return;
-    free(u->blocks); free(u->window_start); free(u->ref); free(u);
+    free(u->blocks); free(u->window_start); free(u->ref);
+    free(u->block_contig); free(u->names); free(u->contig_name_off); free(u->contig_len); free(u);
 }
 
 /* Parse a container, load the FASTA the way the packer does (contigs in file order, upper-cased,
@@ -1711,7 +1712,14 @@ API int cbc_unpack_plan_create(const uint8_t *blob, uint64_t len, const char *fa
                 rc = fail(S, CBC_E_INPUT, "contig %s#%lld has a different length in the FASTA than at compression time", "", (long long)i + 1); goto fail; }
         u->blocks = (cbc_dec_block_desc *)calloc(nb ? nb : 1, sizeof(cbc_dec_block_desc));
         u->window_start = (uint64_t *)calloc(nb ? nb : 1, sizeof(uint64_t));
-        if (!u->blocks || !u->window_start) { rc = CBC_E_NOMEM; goto fail; }
+        u->block_contig = (uint32_t *)calloc(nb ? nb : 1, sizeof(uint32_t));
+        u->names = (char *)calloc((size_t)nbytes + 1, 1);
+        u->contig_name_off = (uint32_t *)calloc(nc ? nc : 1, sizeof(uint32_t));
+        u->contig_len = (uint64_t *)calloc(nc ? nc : 1, sizeof(uint64_t));
+        if (!u->blocks || !u->window_start || !u->block_contig || !u->names || !u->contig_name_off || !u->contig_len) { rc = CBC_E_NOMEM; goto fail; }
+        memcpy(u->names, blob + CBC_CONTAINER_HDR, nbytes);   /* the header check above keeps the blob inside `len` */
+        u->names_bytes = nbytes; u->n_contigs = nc;
+        for (uint32_t i = 0; i < nc; i++) { u->contig_name_off[i] = r32(ctab + 16ull * i); u->contig_len[i] = r64(ctab + 16ull * i + 8); }
         uint32_t stride = is_long ? 0u : ((max_rl + 3u) & ~3u);
         uint64_t nrec = 0, nbases = 0;
         for (uint32_t b = 0; b < nb; b++) {
@@ -1726,7 +1734,7 @@ API int cbc_unpack_plan_create(const uint8_t *blob, uint64_t len, const char *fa
             d->in_off = poff; d->in_bytes = pbytes; d->ref_off = S->P->contigs[contig].ref_off + w0;
             d->rec_base = nrec; d->seq_base = is_long ? nbases : nrec * stride; d->n_reads = nreads; d->read_length = L0; d->seq_stride = stride;
             d->reserved[0] = is_long ? blk_bases : 0u;
-            u->window_start[b] = w0;
+            u->window_start[b] = w0; u->block_contig[b] = contig;
             nrec += nreads; nbases += ((uint64_t)blk_bases + 7u) & ~7ull;
         }
         u->n_blocks = nb; u->payloads = pay; u->payload_bytes = pay_bytes; u->caps.cap_pos = cap_pos; u->caps.cap_var = cap_var;
@@ -1741,6 +1749,95 @@ fail:
     if (S->P) cbc_packed_free(S->P);
     free(S); cbc_unpack_plan_free(u);
     return rc;
+}
+
+/* ---- region decode: parse NAME[:BEG[-END]] and select the blocks (include/cbc_host.h) ---- */
+static int region_err(char *errbuf, size_t errlen, const char *fmt, const char *a, int alen)
+{
+    if (errbuf && errlen) snprintf(errbuf, errlen, fmt, alen, a);
+    return CBC_E_INPUT;
+}
+
+/* the contig whose name is exactly s[0 .. n), -1 if none; -2: a name offset outside the blob or a name without its NUL */
+static int64_t region_contig(const cbc_unpack_plan *u, const char *s, size_t n)
+{
+    for (uint32_t c = 0; c < u->n_contigs; c++) {
+        const uint32_t off = u->contig_name_off[c];
+        if (off >= u->names_bytes) return -2;
+        const char *nm = u->names + off;
+        const size_t len = strnlen(nm, u->names_bytes - off);
+        if (len == u->names_bytes - off) return -2;
+        if (len == n && memcmp(nm, s, n) == 0) return c;
+    }
+    return -1;
+}
+
+/* a decimal number of 1..18 digits filling s[0 .. n) */
+static int region_number(const char *s, size_t n, uint64_t *v)
+{
+    if (n < 1 || n > 18) return -1;
+    uint64_t x = 0;
+    for (size_t i = 0; i < n; i++) { if (s[i] < '0' || s[i] > '9') return -1; x = x * 10u + (uint64_t)(s[i] - '0'); }
+    *v = x;
+    return 0;
+}
+
+API int cbc_unpack_region(const cbc_unpack_plan *u, const char *region, cbc_region_sel *sel, char *errbuf, size_t errlen)
+{
+    if (!u || !region || !sel) return CBC_E_ARG;
+    if (errbuf && errlen) errbuf[0] = 0;
+    memset(sel, 0, sizeof *sel);
+    if (u->long_reads)
+        return region_err(errbuf, errlen, "region decode of a long-read (version 3) container is not supported: its deletions have no small "
+                          "bound, so the index cannot tell which blocks hold a locus%.*s", "", 0);
+    if (!u->block_contig || !u->names || !u->contig_name_off || !u->contig_len) return CBC_E_ARG;
+    const size_t n = strlen(region);
+    const int ilen = n > 200 ? 200 : (int)n;
+    uint64_t beg = 1, end = UINT64_MAX;
+    int64_t c = region_contig(u, region, n);
+    if (c == -1) {                                       /* not a name as a whole: NAME:BEG or NAME:BEG-END */
+        const char *colon = strrchr(region, ':');
+        if (!colon) return region_err(errbuf, errlen, "unknown contig in region \"%.*s\"", region, ilen);
+        c = region_contig(u, region, (size_t)(colon - region));
+        if (c == -1) return region_err(errbuf, errlen, "unknown contig in region \"%.*s\"", region, ilen);
+        if (c >= 0) {
+            const char *num = colon + 1, *dash = strchr(num, '-');
+            const size_t nlen = dash ? (size_t)(dash - num) : strlen(num);
+            if (region_number(num, nlen, &beg) || (dash && region_number(dash + 1, strlen(dash + 1), &end)))
+                return region_err(errbuf, errlen, "malformed coordinates in region \"%.*s\" (want NAME, NAME:BEG or NAME:BEG-END)", region, ilen);
+            if (beg < 1) return region_err(errbuf, errlen, "region \"%.*s\" begins before base 1", region, ilen);
+            if (beg > end) return region_err(errbuf, errlen, "region \"%.*s\" ends before it begins", region, ilen);
+        }
+    }
+    if (c == -2) return region_err(errbuf, errlen, "corrupt container: a contig name lies outside the name table%.*s", "", 0);
+    const uint64_t clen = u->contig_len[c];
+    if (end > clen) end = clen;
+    if (beg > end) return region_err(errbuf, errlen, "region \"%.*s\" begins past the end of its contig", region, ilen);
+    /* the block index, checked in one bounded pass: contigs in file order, positions in order within a contig (the packer
+     * writes nothing else); then the contig's run of blocks [c0, c1) */
+    uint32_t c0 = u->n_blocks, c1 = u->n_blocks;
+    for (uint32_t b = 0; b < u->n_blocks; b++) {
+        const uint32_t cb = u->block_contig[b];
+        if (b > 0 && (cb < u->block_contig[b - 1] || (cb == u->block_contig[b - 1] && u->window_start[b] < u->window_start[b - 1])))
+            return region_err(errbuf, errlen, "corrupt container: the block index is not in contig and position order%.*s", "", 0);
+        if (cb == (uint32_t)c && c0 == u->n_blocks) c0 = b;
+        if (cb == (uint32_t)c) c1 = b + 1;
+    }
+    if (c0 == u->n_blocks) c0 = c1 = 0;
+    /* Span bound.  In block mode the decoder takes nDel as one symbol of the L0-symbol indel-count alphabet (indel_counts,
+     * cbc_decode_body.h) and nIns >= 0, so span = rl + nDel - nIns <= max_read_len + L0 - 1 for every read it reconstructs.
+     * The packer itself accepts any nDel up to 0xffff (tokenise_record, cbc_pack.c), but the encoder codes nDel & 0xff as that
+     * symbol and fails the block with CBC_ST_ASSERT when it is >= L0 (dense_code, cbc_encode_body.h): a container holds no
+     * record whose decoded nDel reaches L0, and the decoder refuses a read longer than the row (rl <= seq_stride).  The span
+     * decode checks the bound on every read (CBC_ST_SPAN), so a crafted payload cannot slip a read past the selection. */
+    const uint32_t smax = u->max_read_len + u->read_length - 1u;
+    uint32_t b1 = c0, b0 = c0;
+    while (b1 < c1 && u->window_start[b1] + 1u <= end) b1++;                   /* F(b) <= END */
+    while (b0 + 1 < c1 && u->window_start[b0 + 1] + 1u + smax < beg + 1u) b0++;  /* F(next(b)) >= BEG - SMAX + 1 */
+    if (b0 > b1) b0 = b1;
+    sel->contig = (uint32_t)c; sel->b0 = b0; sel->b1 = b1; sel->smax = smax;
+    sel->beg = beg; sel->end = end; sel->contig_len = clen;
+    return 0;
 }
 
 /* One reconstructed read per line (print_line, src/compression.c:16-40). */

@@ -198,6 +198,18 @@ def lib():
         L.cbc_gpu_host_unregister.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.cbc_gpu_checksum_device.restype = ctypes.c_int
         L.cbc_gpu_checksum_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        L.cbc_gpu_decode_region.restype = ctypes.c_int
+        L.cbc_gpu_decode_region.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                            ctypes.POINTER(host.LdsCaps), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                            ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.cbc_gpu_decode_blocks_span.restype = ctypes.c_int
+        L.cbc_gpu_decode_blocks_span.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                                 ctypes.POINTER(host.LdsCaps), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                                 ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        L.cbc_gpu_last_region_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_region_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                             ctypes.POINTER(ctypes.c_float)]
         if L.cbc_gpu_abi_version() != 1:
             raise CbcGpuError("libcbc_gpu.so ABI version mismatch")
         _lib = L
@@ -216,7 +228,8 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_checksum_device", "cbc_gpu_upload_reference_parts", "cbc_gpu_last_e2e", "cbc_gpu_host_register",
            "cbc_gpu_host_unregister", "cbc_gpu_plan_output_caps", "cbc_gpu_reserve_encode",
            "cbc_gpu_decode_stream_blocks", "cbc_gpu_group_create", "cbc_gpu_group_gather", "cbc_gpu_group_destroy", "cbc_gpu_group_last_error",
-           "cbc_gpu_stash_reset", "cbc_gpu_stash_bytes", "cbc_gpu_stash_fetch"]
+           "cbc_gpu_stash_reset", "cbc_gpu_stash_bytes", "cbc_gpu_stash_fetch", "cbc_gpu_decode_region",
+           "cbc_gpu_decode_blocks_span", "cbc_gpu_last_region_ms"]
 
 
 class Encoder:
@@ -378,6 +391,52 @@ class Encoder:
         if rc != 0 and rc != -4:
             self._check(rc, "cbc_gpu_decode_blocks")
         return recs, seq, res
+
+    def decode_blocks_span(self, plan: "host.UnpackPlan", smax):
+        """decode_blocks with every read's span in recs["tok_off"] (cbc_gpu_decode_blocks_span).  Returns (recs, seq, results)."""
+        nb = plan.n_blocks
+        blocks = plan.blocks.copy()
+        recs = np.zeros(plan.n_recs, dtype=host.REC_DTYPE)
+        seq = np.zeros(plan.n_recs * plan.seq_stride + 8, dtype=np.uint8)
+        res = np.zeros(nb, dtype=host.RESULT_DTYPE)
+        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
+        pay = np.ascontiguousarray(plan.payloads)
+        rc = lib().cbc_gpu_decode_blocks_span(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps), smax,
+                                              recs.ctypes.data, plan.n_recs, seq.ctypes.data, seq.size, res.ctypes.data)
+        if rc != 0 and rc != -4:
+            self._check(rc, "cbc_gpu_decode_blocks_span")
+        return recs, seq, res
+
+    def decode_region(self, plan: "host.UnpackPlan", region, results=False):
+        """The reads of `region` (NAME, NAME:BEG or NAME:BEG-END) as the text `cbc -x` writes for them: the index selects the
+        blocks (UnpackPlan.region), the device decodes those, filters and assembles the text (cbc_gpu_decode_region).  The
+        reference must have been uploaded (upload_reference(plan.ref)).  With results=True returns (text, n_selected,
+        selection, per-block decode results)."""
+        sel = plan.region(region)
+        nb = sel.b1 - sel.b0
+        res = np.zeros(max(nb, 1), dtype=host.RESULT_DTYPE)
+        if nb == 0:
+            return (b"", 0, sel, res[:0]) if results else b""
+        blocks = np.ascontiguousarray(plan.blocks[sel.b0:sel.b1])
+        ws = np.ascontiguousarray(plan.window_start[sel.b0:sel.b1], dtype=np.uint64)
+        cap = int(blocks["n_reads"].astype(np.uint64).sum()) * (plan.seq_stride + 1)
+        text = np.zeros(max(cap, 1), dtype=np.uint8)
+        nbytes, nsel = ctypes.c_uint64(), ctypes.c_uint64()
+        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
+        pay = np.ascontiguousarray(plan.payloads)
+        rc = lib().cbc_gpu_decode_region(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
+                                         ws.ctypes.data, sel.beg, sel.end, sel.smax, text.ctypes.data, cap,
+                                         ctypes.byref(nbytes), ctypes.byref(nsel), res.ctypes.data)
+        if rc != 0 and not (results and rc == -4):
+            self._check(rc, "cbc_gpu_decode_region")
+        out = text[:int(nbytes.value)].tobytes()
+        return (out, int(nsel.value), sel, res[:nb]) if results else out
+
+    def last_region_ms(self):
+        """(decode, filter + scan, text) kernel milliseconds of the last decode_region."""
+        a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        self._check(lib().cbc_gpu_last_region_ms(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "cbc_gpu_last_region_ms")
+        return float(a.value), float(b.value), float(c.value)
 
     def _host_batch(self, pb):
         blocks = pb.blocks.copy()

@@ -84,7 +84,15 @@ class UnpackPlanC(ctypes.Structure):
                 ("window_start", ctypes.POINTER(ctypes.c_uint64)),
                 ("caps", LdsCaps), ("read_length", ctypes.c_uint32), ("seq_stride", ctypes.c_uint32),
                 ("n_recs", ctypes.c_uint64), ("long_reads", ctypes.c_uint32), ("max_read_len", ctypes.c_uint32),
-                ("seq_total", ctypes.c_uint64)]
+                ("seq_total", ctypes.c_uint64),
+                ("block_contig", ctypes.POINTER(ctypes.c_uint32)), ("n_contigs", ctypes.c_uint32),
+                ("names_bytes", ctypes.c_uint32), ("names", ctypes.c_void_p),
+                ("contig_name_off", ctypes.POINTER(ctypes.c_uint32)), ("contig_len", ctypes.POINTER(ctypes.c_uint64))]
+
+
+class RegionSelC(ctypes.Structure):
+    _fields_ = [("contig", ctypes.c_uint32), ("b0", ctypes.c_uint32), ("b1", ctypes.c_uint32), ("smax", ctypes.c_uint32),
+                ("beg", ctypes.c_uint64), ("end", ctypes.c_uint64), ("contig_len", ctypes.c_uint64)]
 
 
 class PackOpts(ctypes.Structure):
@@ -165,6 +173,9 @@ def lib():
         L.cbc_unpack_plan_create.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_size_t,
                                              ctypes.POINTER(ctypes.POINTER(UnpackPlanC)), ctypes.c_char_p, ctypes.c_size_t]
         L.cbc_unpack_plan_free.argtypes = [ctypes.POINTER(UnpackPlanC)]
+        L.cbc_unpack_region.restype = ctypes.c_int
+        L.cbc_unpack_region.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_char_p, ctypes.POINTER(RegionSelC),
+                                        ctypes.c_char_p, ctypes.c_size_t]
         L.cbc_unpack_write_text.restype = ctypes.c_int64
         L.cbc_unpack_write_text.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_uint64]
@@ -401,6 +412,17 @@ def synth(seed, contig_len, n_reads, read_len=150, sub_rate=0.003, indel_frac=0.
     return pb, sam, fa
 
 
+class RegionSelection:
+    """What cbc_unpack_region chose: contig index, blocks [b0, b1), the clamped 1-based inclusive [beg, end], the span bound."""
+
+    def __init__(self, contig, b0, b1, beg, end, smax, contig_len):
+        self.contig, self.b0, self.b1, self.beg, self.end, self.smax, self.contig_len = contig, b0, b1, beg, end, smax, contig_len
+
+    def __repr__(self):
+        return "RegionSelection(contig=%d, blocks=[%d, %d), beg=%d, end=%d, smax=%d)" % (
+            self.contig, self.b0, self.b1, self.beg, self.end, self.smax)
+
+
 class UnpackPlan:
     """Container + FASTA -> decode launch plan (cbc_unpack_plan_create).  Keeps the container bytes alive."""
 
@@ -426,6 +448,20 @@ class UnpackPlan:
         self.long_reads = bool(p.long_reads)
         self.max_read_len = int(p.max_read_len)
         self.seq_total = int(p.seq_total)
+
+    def region(self, region):
+        """Blocks that can hold a read overlapping `region` (NAME, NAME:BEG or NAME:BEG-END, 1-based inclusive):
+        cbc_unpack_region.  Returns a RegionSelection; raises CbcInputError for a malformed or unknown region and for a
+        long-read container."""
+        if isinstance(region, str):
+            region = region.encode()
+        sel = RegionSelC()
+        err = ctypes.create_string_buffer(512)
+        rc = lib().cbc_unpack_region(self._ptr, region, ctypes.byref(sel), err, 512)
+        if rc != 0:
+            raise CbcInputError("cbc_unpack_region failed (%d): %s" % (rc, err.value.decode(errors="replace")))
+        return RegionSelection(int(sel.contig), int(sel.b0), int(sel.b1), int(sel.beg), int(sel.end), int(sel.smax),
+                               int(sel.contig_len))
 
     def text(self, recs: np.ndarray, seq: np.ndarray) -> bytes:
         """One reconstructed read per line (what `cbc -d` writes)."""

@@ -58,6 +58,8 @@ extern "C" {
 #define CBC_ST_UNSUPPORTED  7   /* raw leading-S / '*' op in the tokens (the packer emits a leading  */
                                 /* soft clip as an I op after rebuilding MD, quirk Q6); a block    */
                                 /* of more than CBC_MAX_BLOCK_READS records; a LOSSY stream         */
+#define CBC_ST_SPAN         8   /* region decode: a read covers more reference bases than the bound */
+                                /* the block selection assumed (cbc_gpu_decode_region, smax)        */
 
 /* ---- packed record layout (device and host share it) ---------------------------------------- */
 
@@ -278,6 +280,29 @@ int  cbc_gpu_decode_blocks(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_byte
                            cbc_read_rec *recs, uint64_t n_recs, uint8_t *seq, uint64_t seq_bytes,
                            cbc_block_result *results /* n_blocks or NULL */);
 uint32_t cbc_gpu_decode_lds_bytes(const cbc_lds_caps *caps);
+
+/* ---- region decode (block container version 2) ------------------------------------------------
+ * Decode only `blocks` (a contiguous run of one contig's blocks, as cbc_unpack_region in libcbc_host selects them) and keep
+ * the reads that overlap the region [beg, end] (1-based, inclusive): POS <= end and POS + span - 1 >= beg, where POS =
+ * window_start[b] + the decoded block-local POS and span = the reference bases the decoder's reconstruction covers (rlen for
+ * a read coded as perfect, rlen + nDel - nIns otherwise).  The decode kernel writes each span into cbc_read_rec.tok_off and
+ * fails the block with CBC_ST_SPAN if one exceeds `smax`; a filter kernel counts the kept reads and their text bytes per
+ * block, a scan places the blocks, and a text kernel writes every kept read + '\n' into one dense buffer -- exactly what
+ * `cbc -x` writes for those records, in container order.  Records and bases stay on the device; only the text comes back.
+ * blocks[].in_off index `in`; rec_base / seq_base are laid out by the library (the caller's array is not modified).
+ * *text_bytes = bytes of text (also when text_cap is too small: CBC_E_ARG, nothing copied), *n_selected = reads kept. */
+int  cbc_gpu_decode_region(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                           uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                           uint64_t beg, uint64_t end, uint32_t smax, uint8_t *text, uint64_t text_cap,
+                           uint64_t *text_bytes, uint64_t *n_selected, cbc_block_result *results /* n_blocks or NULL */);
+/* cbc_gpu_decode_blocks with the spans reported: recs[r].tok_off = span of record r, CBC_ST_SPAN for a span above smax (the
+ * decoder the region path runs, with its records and rows returned; what the tests check the spans with) */
+int  cbc_gpu_decode_blocks_span(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, cbc_dec_block_desc *blocks,
+                                uint32_t n_blocks, const cbc_lds_caps *caps, uint32_t smax, cbc_read_rec *recs, uint64_t n_recs,
+                                uint8_t *seq, uint64_t seq_bytes, cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_region (HIP events on its stream): the span-reporting decode, the filter
+ * (count pass + block scan) and the text assembly. */
+int  cbc_gpu_last_region_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *text_ms);
 
 /* ---- whole-file stream ("compat" mode): the reference's own file format --------------------------------------
  * compress() / decompress(), src/compression.c:112-216: ONE arithmetic stream per file, models never reset.

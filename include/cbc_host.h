@@ -180,7 +180,30 @@ typedef struct cbc_unpack_plan {
     uint32_t            long_reads;                          /* container version 3: blocks[b].reserved[0] = bases of block b, */
     uint32_t            max_read_len;                        /* blocks[b].seq_base = where they start in the output (compact)  */
     uint64_t            seq_total;                           /* bytes of bases the decode writes (+ 8 spare)                   */
+    /* the container's contig table, kept for region decode (cbc_unpack_region) */
+    uint32_t           *block_contig;                        /* per block: its contig                                           */
+    uint32_t            n_contigs;
+    uint32_t            names_bytes;
+    char               *names;                               /* owned copy of the names blob (NUL-terminated SAM RNAMEs)        */
+    uint32_t           *contig_name_off;                     /* per contig: its name in names[] (checked to be inside it)       */
+    uint64_t           *contig_len;                          /* per contig                                                      */
 } cbc_unpack_plan;
+
+/* Region decode.  `region` is NAME, NAME:BEG or NAME:BEG-END, 1-based and inclusive (samtools); a
+ * string that is a contig name as a whole means that contig, otherwise it is split at the last ':'.  END is clamped to the
+ * contig length.  The blocks [b0, b1) are the ones that can hold a read overlapping [beg, end]: with F(b) = window_start[b]
+ * + 1 and smax = max_read_len + read_length - 1 (no read the decoder reconstructs covers more reference bases), block b of
+ * the contig is selected iff F(b) <= end and (b is the contig's last block or F(next block) + smax >= beg + 1).
+ * b0 == b1: no block can hold such a read.  Returns CBC_E_INPUT with a message for a malformed or unknown region, a
+ * long-read (version 3) container, or a block index that is not in contig / position order. */
+typedef struct cbc_region_sel {
+    uint32_t contig;
+    uint32_t b0, b1;        /* selected blocks: a contiguous run of the contig's blocks */
+    uint32_t smax;          /* span bound the selection assumed (cbc_gpu_decode_region checks it) */
+    uint64_t beg, end;      /* 1-based, inclusive, end clamped to the contig length */
+    uint64_t contig_len;
+} cbc_region_sel;
+int     cbc_unpack_region(const cbc_unpack_plan *u, const char *region, cbc_region_sel *sel, char *errbuf, size_t errlen);
 
 int     cbc_unpack_plan_create(const uint8_t *blob, uint64_t len, const char *fasta, size_t fasta_len,
                                cbc_unpack_plan **out, char *errbuf, size_t errlen);
