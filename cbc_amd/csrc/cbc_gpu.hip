@@ -245,7 +245,6 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
 enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_COUNT };
-#define CBC_MAX_CHUNKS 8
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
 struct cbc_gpu_ctx {
@@ -273,6 +272,8 @@ static int set_err(cbc_gpu_ctx *c, int code, const char *what, hipError_t e)
     return code;
 }
 #define HIPCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return set_err(ctx, CBC_E_NODEV, what, e_); } while (0)
+/* the same inside a function that cleans up: `rc` takes the error and control goes to its `done:` label */
+#define GO(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = set_err(ctx, CBC_E_NODEV, what, e_); goto done; } } while (0)
 
 /* at least `bytes` in arena k; growing frees the old buffer (hipFree waits for the device) */
 static int arena_need(cbc_gpu_ctx *ctx, int k, uint64_t bytes, const char *what)
@@ -283,6 +284,18 @@ static int arena_need(cbc_gpu_ctx *ctx, int k, uint64_t bytes, const char *what)
     const uint64_t want = (bytes + (bytes >> 3) + (2ull << 20)) & ~((2ull << 20) - 1);      /* 1/8 headroom, 2 MiB granules */
     HIPCHK(hipMalloc(&a->p, want), what);
     a->cap = want;
+    return CBC_OK;
+}
+#define NEED(k, bytes, what) do { rc = arena_need(ctx, k, bytes, what); if (rc) goto done; } while (0)
+
+/* the first block whose status is not CBC_ST_OK becomes the call's error: "block <b> <verb> with status ..." */
+static int blocks_failed(cbc_gpu_ctx *ctx, const cbc_block_result *res, uint32_t n_blocks, const char *verb)
+{
+    for (uint32_t b = 0; b < n_blocks; b++)
+        if (res[b].status != CBC_ST_OK) {
+            snprintf(ctx->err, sizeof ctx->err, "block %u %s with status %u at record %u", b, verb, res[b].status, res[b].fail_read);
+            return CBC_E_BLOCK;
+        }
     return CBC_OK;
 }
 static double wall_now(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
@@ -414,11 +427,6 @@ API int cbc_gpu_reserve_encode(cbc_gpu_ctx *ctx, uint64_t n_recs, uint64_t seq_b
     return CBC_OK;
 }
 
-static int encode_blocks_launch(cbc_gpu_ctx *ctx, const cbc_device_batch *b, void *hip_stream, uint64_t resident_blocks);
-API int cbc_gpu_encode_blocks_device(cbc_gpu_ctx *ctx, const cbc_device_batch *b, void *hip_stream)
-{
-    return encode_blocks_launch(ctx, b, hip_stream, b ? b->n_blocks : 0);
-}
 /* resident_blocks: how many blocks compete for the chip while this launch runs (the chunked host-buffer path makes several
  * launches that run side by side): it, not the launch's own grid, decides the register budget of the build */
 static int encode_blocks_launch(cbc_gpu_ctx *ctx, const cbc_device_batch *b, void *hip_stream, uint64_t resident_blocks)
@@ -448,6 +456,10 @@ static int encode_blocks_launch(cbc_gpu_ctx *ctx, const cbc_device_batch *b, voi
     HIPCHK(hipEventRecord(ctx->ev1, s), "hipEventRecord");
     ctx->have_timing = 1;
     return CBC_OK;
+}
+API int cbc_gpu_encode_blocks_device(cbc_gpu_ctx *ctx, const cbc_device_batch *b, void *hip_stream)
+{
+    return encode_blocks_launch(ctx, b, hip_stream, b ? b->n_blocks : 0);
 }
 
 API int cbc_gpu_last_kernel_ms(cbc_gpu_ctx *ctx, float *ms)
@@ -534,56 +546,24 @@ API int cbc_gpu_upload_reference_2bit(cbc_gpu_ctx *ctx, const uint32_t *codes, u
     return CBC_OK;
 }
 
-static int encode_blocks_impl(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, const uint32_t *seq_codes, const cbc_2bit_run_dev *seq_runs,
-                              uint64_t n_seq_runs, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, cbc_block_result *results,
-                              const uint8_t *d_seq_ext = NULL, const uint32_t *d_tok_ext = NULL, const cbc_tok_record_summary *sums = NULL);
-
-/* cbc_plan_output() when the tokens are on the device: the per-record var-symbol bound travels in the summaries */
-static uint64_t plan_output_from_summaries(cbc_block_desc *blocks, uint32_t n_blocks, const cbc_tok_record_summary *sums)
-{
-    uint64_t off = 0;
-    for (uint32_t b = 0; b < n_blocks; b++) {
-        cbc_block_desc *bd = &blocks[b];
-        uint64_t nev = 0;
-        for (uint32_t r = 0; r < bd->n_reads; r++) nev += sums[bd->rec_base + r].nt_ev >> 16;
-        const uint64_t nsym = 136u + 2u * CBC_CAP_NAME + 16ull * bd->n_reads + 2 * nev;
-        uint64_t payload_cap = (3 * nsym + 256 + 255) & ~255ull;
-        uint64_t cap = payload_cap + ((4 * (nev + 64) + 255) & ~255ull);
-        if (cap > 0xffffff00ull) { cap = 0xffffff00ull; payload_cap = cap / 2; payload_cap &= ~255ull; }
-        bd->out_off = off; bd->out_cap = (uint32_t)cap; bd->reserved = (uint32_t)payload_cap;
-        off += cap;
-    }
-    return off;
-}
-
-/* host-buffer entry point: H2D, encode, size scan, device-side compaction, D2H */
-API int cbc_gpu_encode_blocks(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, uint8_t *out, uint64_t out_cap,
-                              uint64_t *out_offsets, cbc_block_result *results)
-{
-    if (!hb || !hb->seq) return CBC_E_ARG;
-    return encode_blocks_impl(ctx, hb, NULL, NULL, 0, out, out_cap, out_offsets, results);
-}
-API int cbc_gpu_encode_blocks_2bit(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, const uint32_t *seq_codes, const cbc_2bit_run_dev *seq_runs,
-                                   uint64_t n_seq_runs, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, cbc_block_result *results)
-{
-    if (!seq_codes || (n_seq_runs && !seq_runs)) return CBC_E_ARG;
-    return encode_blocks_impl(ctx, hb, seq_codes, seq_runs, n_seq_runs, out, out_cap, out_offsets, results);
-}
-
-/* The host-buffer encode path (timed region ii), as a pipeline:
+/* The host-buffer encode path (timed region ii), as a pipeline -- every host-buffer encode entry point
+ * (bytes, 2-bit, tokenised, long reads) is this function with the payload areas its caller planned (`scratch` bytes):
  *   - device arrays are the context's grow-only arenas (no hipMalloc / hipFree per call once they have their size);
- *   - the batch is cut into up to CBC_MAX_CHUNKS runs of consecutive blocks; chunk c's records, bases (bytes or 2-bit
- *     codes) and tokens go H2D on the copy stream, an event later its expansion (2-bit) and its encode launch run on
- *     kernel stream c % 2 -- so chunk c + 1 crosses PCIe while chunk c is being coded, and launches of neighbouring
- *     chunks share the chip (a block is one serial chain: a launch of few blocks cannot fill it alone);
+ *   - the batch is cut into up to CBC_MAX_CHUNKS runs of consecutive blocks (cbc_plan_chunks); chunk c's records, bases
+ *     (bytes or 2-bit codes) and tokens go H2D on the copy stream, followed there by its 2-bit expansion, and an event
+ *     later its encode launch runs on kernel stream c -- so chunk c + 1 crosses PCIe while chunk c is being coded, and
+ *     launches of neighbouring chunks share the chip (a block is one serial chain: a launch of few blocks cannot fill it
+ *     alone); the copy stream's order puts every expansion, the code word two chunks share included, before the encodes
+ *     that read it;
  *   - one size scan + compaction over all blocks and one D2H of the compacted bitstreams (2 bytes per read) end it.
+ * Long reads (long_reads) take the long-read launcher and stay one chunk: their launches share the context's table
+ * scratch (A_LSCR), so two of them on two streams would overwrite each other's tables.
  * Source buffers that are page-locked (cbc_gpu_host_register, or the caller's own hipHostMalloc) are read by DMA at the
- * link rate; pageable ones go through the runtime's staging, which blocks this thread but not the launches already made.
- * Needs the blocks' bases in ascending order with rec / seq / tok ranges contiguous from block to block (what the packers
- * produce); any other descriptor list is sent as one chunk covering the arrays whole. */
-static int encode_blocks_impl(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, const uint32_t *seq_codes, const cbc_2bit_run_dev *seq_runs,
-                              uint64_t n_seq_runs, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, cbc_block_result *results,
-                              const uint8_t *d_seq_ext, const uint32_t *d_tok_ext, const cbc_tok_record_summary *sums)
+ * link rate; pageable ones go through the runtime's staging, which blocks this thread but not the launches already made. */
+static int encode_blocks_impl(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, uint64_t scratch, const uint32_t *seq_codes,
+                              const cbc_2bit_run_dev *seq_runs, uint64_t n_seq_runs, uint8_t *out, uint64_t out_cap,
+                              uint64_t *out_offsets, cbc_block_result *results, const uint8_t *d_seq_ext = NULL,
+                              const uint32_t *d_tok_ext = NULL, bool long_reads = false)
 {
     if (!ctx || !hb || !out_offsets) return CBC_E_ARG;     /* out == NULL: the bitstreams stay on the device (the context's stash) */
     if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
@@ -593,17 +573,12 @@ static int encode_blocks_impl(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, const 
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     const double T0 = wall_now();
     cbc_e2e_times tm; memset(&tm, 0, sizeof tm);
-    /* payload areas from the caps alone (O(blocks)); a batch whose cap_var is not a bound -- not from the packers -- gets
-     * OUT_FULL / CAP_VAR statuses from the kernel, never a wrong byte */
-    const uint64_t scratch = sums ? plan_output_from_summaries(hb->blocks, nb, sums) : cbc_plan_output_caps(hb->blocks, nb, &hb->caps);
     cbc_block_result *res = NULL;
     uint8_t *d_compact = NULL;
     int rc = CBC_OK;
     uint64_t total = 0;
     const uint64_t ntok = hb->n_tok ? hb->n_tok : 1;
-    const cbc_block_desc *B = hb->blocks;
-#define GO(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = set_err(ctx, CBC_E_NODEV, what, e_); goto done; } } while (0)
-#define NEED(k, bytes, what) do { rc = arena_need(ctx, k, bytes, what); if (rc) goto done; } while (0)
+    const bool two_bit = seq_codes && !d_seq_ext;
     NEED(A_RECS, hb->n_recs * sizeof(cbc_read_rec) + 16, "hipMalloc recs");
     if (!d_seq_ext) NEED(A_SEQ, hb->seq_bytes + 32, "hipMalloc seq");
     if (!d_tok_ext) NEED(A_TOK, ntok * 4 + 16, "hipMalloc tok");
@@ -612,7 +587,7 @@ static int encode_blocks_impl(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, const 
     NEED(A_OUT, scratch, "hipMalloc out scratch");
     NEED(A_RES, (uint64_t)nb * sizeof(cbc_block_result), "hipMalloc results");
     NEED(A_OFF, ((uint64_t)nb + 1) * 8, "hipMalloc offsets");
-    if (seq_codes && !d_seq_ext) {
+    if (two_bit) {
         NEED(A_CODES, ((hb->seq_bytes + 15) / 16) * 4 + 16, "hipMalloc 2-bit codes");
         if (n_seq_runs) NEED(A_RUNS, n_seq_runs * sizeof(cbc_2bit_run_dev), "hipMalloc 2-bit runs");
         if (n_seq_runs > 0x7fffffffull) { rc = set_err(ctx, CBC_E_ARG, "2-bit transport: too many runs", hipSuccess); goto done; }
@@ -624,82 +599,58 @@ static int encode_blocks_impl(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, const 
         cbc_block_desc *d_blocks = (cbc_block_desc *)ctx->arena[A_BLOCKS].p;
         cbc_block_result *d_res = (cbc_block_result *)ctx->arena[A_RES].p;
         hipStream_t sc = ctx->s_copy;
-        /* chunks: runs of consecutive blocks of about equal H2D volume, when the descriptor list is contiguous */
-        uint32_t n_chunks = 1, cut[CBC_MAX_CHUNKS + 1];
-        bool contiguous = true;
-        for (uint32_t b = 0; b + 1 < nb && contiguous; b++)
-            contiguous = B[b + 1].rec_base == B[b].rec_base + B[b].n_reads && B[b + 1].seq_base >= B[b].seq_base && B[b + 1].tok_base >= B[b].tok_base;
-        contiguous = contiguous && B[0].rec_base + 0 <= hb->n_recs && B[nb - 1].rec_base + B[nb - 1].n_reads <= hb->n_recs
-                     && B[nb - 1].seq_base <= hb->seq_bytes && B[nb - 1].tok_base <= ntok;
-        const uint64_t vol = hb->n_recs * 16 + (d_seq_ext ? 0 : seq_codes ? hb->seq_bytes / 4 : hb->seq_bytes) + (d_tok_ext ? 0 : ntok * 4);
-        if (contiguous && nb >= 512) {
-            /* A block is one serial chain (~5.6 ms for 4096 reads) however few blocks a launch holds, and the link moves
-             * ~57 GB/s: chunks of >= 64 MB and >= 256 blocks, each launched on its own stream the moment it has arrived */
-            uint64_t want = vol / (64ull << 20);
-            if (want > CBC_MAX_CHUNKS) want = CBC_MAX_CHUNKS;
-            if (want > nb / 256) want = nb / 256;
-            if (want >= 2) n_chunks = (uint32_t)want;
-        }
-        cut[0] = 0; cut[n_chunks] = nb;
-        for (uint32_t c = 1; c < n_chunks; c++) {                 /* equal record counts ~ equal bytes */
-            const uint64_t target = B[0].rec_base + (B[nb - 1].rec_base + B[nb - 1].n_reads - B[0].rec_base) * c / n_chunks;
-            uint32_t lo = cut[c - 1] + 1, hi = nb - (n_chunks - c);
-            while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (B[mid].rec_base < target) lo = mid + 1; else hi = mid; }
-            cut[c] = lo;
-        }
-        tm.n_chunks = n_chunks;
+        cbc_chunk_plan P;
+        cbc_plan_chunks(hb->blocks, nb, hb->n_recs, hb->seq_bytes, hb->n_tok,
+                        hb->n_recs * 16 + (d_seq_ext ? 0 : seq_codes ? hb->seq_bytes / 4 : hb->seq_bytes) + (d_tok_ext ? 0 : ntok * 4),
+                        !long_reads, &P);
+        tm.n_chunks = P.n_chunks;
         /* small things first: descriptors, names, result slots, exception runs */
-        GO(hipMemcpyAsync(d_blocks, B, (uint64_t)nb * sizeof(cbc_block_desc), hipMemcpyHostToDevice, sc), "H2D blocks");
+        GO(hipMemcpyAsync(d_blocks, hb->blocks, (uint64_t)nb * sizeof(cbc_block_desc), hipMemcpyHostToDevice, sc), "H2D blocks");
         GO(hipMemcpyAsync(ctx->arena[A_NAMES].p, hb->names, hb->names_bytes, hipMemcpyHostToDevice, sc), "H2D names");
         GO(hipMemsetAsync(d_res, 0xff, (uint64_t)nb * sizeof(cbc_block_result), sc), "memset results");
-        if (seq_codes && !d_seq_ext && n_seq_runs)
+        if (two_bit && n_seq_runs)
             GO(hipMemcpyAsync(ctx->arena[A_RUNS].p, seq_runs, n_seq_runs * sizeof(cbc_2bit_run_dev), hipMemcpyHostToDevice, sc), "H2D 2-bit runs");
-        tm.h2d_bytes = (uint64_t)nb * sizeof(cbc_block_desc) + hb->names_bytes + (seq_codes && !d_seq_ext ? n_seq_runs * sizeof(cbc_2bit_run_dev) : 0);
-        uint64_t words_done = 0;                                  /* 2-bit words expanded so far (chunks meet inside a word) */
-        for (uint32_t c = 0; c < n_chunks; c++) {
-            const uint32_t c0 = cut[c], c1 = cut[c + 1];
-            const bool whole = !contiguous || n_chunks == 1;
-            const uint64_t r0 = whole ? 0 : B[c0].rec_base, r1 = whole ? hb->n_recs : B[c1 - 1].rec_base + B[c1 - 1].n_reads;
-            const uint64_t s0 = whole ? 0 : B[c0].seq_base, s1 = whole || c1 == nb ? hb->seq_bytes : B[c1].seq_base;
-            const uint64_t t0 = whole ? 0 : B[c0].tok_base, t1 = whole || c1 == nb ? hb->n_tok : B[c1].tok_base;
-            GO(hipMemcpyAsync(d_recs + r0 * 16, (const uint8_t *)hb->recs + r0 * 16, (r1 - r0) * 16, hipMemcpyHostToDevice, sc), "H2D recs");
-            tm.h2d_bytes += (r1 - r0) * 16;
-            uint64_t w0 = 0, w1 = 0;
-            if (d_seq_ext) { /* already resident */ }
-            else if (seq_codes) {                                  /* 2-bit transport: a quarter of the bytes cross PCIe, expanded on the device */
-                w0 = words_done; w1 = (s1 + 15) / 16; if (w1 < w0) w1 = w0;
-                if (w1 > w0) GO(hipMemcpyAsync(d_codes + w0, seq_codes + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, sc), "H2D 2-bit codes");
-                tm.h2d_bytes += (w1 - w0) * 4; words_done = w1;
-            } else if (s1 > s0) {
-                GO(hipMemcpyAsync(d_seq + s0, hb->seq + s0, s1 - s0, hipMemcpyHostToDevice, sc), "H2D seq");
-                tm.h2d_bytes += s1 - s0;
+        tm.h2d_bytes = (uint64_t)nb * sizeof(cbc_block_desc) + hb->names_bytes + (two_bit ? n_seq_runs * sizeof(cbc_2bit_run_dev) : 0);
+        for (uint32_t c = 0; c < P.n_chunks; c++) {
+            const cbc_chunk &k = P.c[c];
+            GO(hipMemcpyAsync(d_recs + k.r0 * 16, (const uint8_t *)hb->recs + k.r0 * 16, (k.r1 - k.r0) * 16, hipMemcpyHostToDevice, sc), "H2D recs");
+            tm.h2d_bytes += (k.r1 - k.r0) * 16;
+            if (two_bit) {                                         /* 2-bit transport: a quarter of the bytes cross PCIe, expanded on the device */
+                if (k.w1 > k.w0) GO(hipMemcpyAsync(d_codes + k.w0, seq_codes + k.w0, (k.w1 - k.w0) * 4, hipMemcpyHostToDevice, sc), "H2D 2-bit codes");
+                tm.h2d_bytes += (k.w1 - k.w0) * 4;
+            } else if (!d_seq_ext && k.s1 > k.s0) {
+                GO(hipMemcpyAsync(d_seq + k.s0, hb->seq + k.s0, k.s1 - k.s0, hipMemcpyHostToDevice, sc), "H2D seq");
+                tm.h2d_bytes += k.s1 - k.s0;
             }
-            if (!d_tok_ext && t1 > t0) {
-                GO(hipMemcpyAsync(d_tok + t0, hb->tok + t0, (t1 - t0) * 4, hipMemcpyHostToDevice, sc), "H2D tok");
-                tm.h2d_bytes += (t1 - t0) * 4;
+            if (!d_tok_ext && k.t1 > k.t0) {
+                GO(hipMemcpyAsync(d_tok + k.t0, hb->tok + k.t0, (k.t1 - k.t0) * 4, hipMemcpyHostToDevice, sc), "H2D tok");
+                tm.h2d_bytes += (k.t1 - k.t0) * 4;
+            }
+            if (two_bit && k.w1 > k.w0) {
+                /* on the copy stream, in chunk order: chunks meet inside a code word, which chunk c expands and patches with
+                 * its runs, and chunk c + 1's encode reads it.  (A cross-stream event behind each expansion instead cost
+                 * 2.5 ms of a cfg2 call; this costs 0.2-0.4 ms: profiles/host_pipeline_ab.json) */
+                if (k.w1 - k.w0 > 0x7fffffffull * 256ull) { rc = set_err(ctx, CBC_E_ARG, "2-bit transport: too many words", hipSuccess); goto done; }
+                hipLaunchKernelGGL(cbc_expand_2bit_kernel, dim3((unsigned)((k.w1 - k.w0 + 255) / 256)), dim3(256), 0, sc,
+                                   (const uint32_t *)(d_codes + k.w0), k.w1 - k.w0, d_seq + k.w0 * 16, hb->seq_bytes - k.w0 * 16);
+                GO(hipGetLastError(), "launch cbc_expand_2bit_kernel");
+                if (n_seq_runs) {
+                    hipLaunchKernelGGL(cbc_apply_runs_kernel, dim3((unsigned)n_seq_runs), dim3(256), 0, sc,
+                                       (const cbc_2bit_run_dev *)ctx->arena[A_RUNS].p, n_seq_runs, d_seq, hb->seq_bytes, k.w0 * 16, k.w1 * 16);
+                    GO(hipGetLastError(), "launch cbc_apply_runs_kernel");
+                }
             }
             GO(hipEventRecord(ctx->ev_chunk[c], sc), "hipEventRecord");
             hipStream_t ks = ctx->s_k[c % CBC_N_KSTREAMS];
             GO(hipStreamWaitEvent(ks, ctx->ev_chunk[c], 0), "hipStreamWaitEvent");
-            if (seq_codes && !d_seq_ext && w1 > w0) {
-                if (w1 - w0 > 0x7fffffffull * 256ull) { rc = set_err(ctx, CBC_E_ARG, "2-bit transport: too many words", hipSuccess); goto done; }
-                hipLaunchKernelGGL(cbc_expand_2bit_kernel, dim3((unsigned)((w1 - w0 + 255) / 256)), dim3(256), 0, ks,
-                                   (const uint32_t *)(d_codes + w0), w1 - w0, d_seq + w0 * 16, hb->seq_bytes - w0 * 16);
-                GO(hipGetLastError(), "launch cbc_expand_2bit_kernel");
-                if (n_seq_runs) {
-                    hipLaunchKernelGGL(cbc_apply_runs_kernel, dim3((unsigned)n_seq_runs), dim3(256), 0, ks,
-                                       (const cbc_2bit_run_dev *)ctx->arena[A_RUNS].p, n_seq_runs, d_seq, hb->seq_bytes, w0 * 16, w1 * 16);
-                    GO(hipGetLastError(), "launch cbc_apply_runs_kernel");
-                }
-            }
             cbc_device_batch db;
             memset(&db, 0, sizeof db);
             db.d_recs = (const cbc_read_rec *)d_recs; db.d_seq = d_seq_ext ? d_seq_ext : d_seq; db.d_tok = d_tok_ext ? d_tok_ext : d_tok;
-            db.d_names = (const uint8_t *)ctx->arena[A_NAMES].p; db.d_blocks = d_blocks + c0; db.n_blocks = c1 - c0;
+            db.d_names = (const uint8_t *)ctx->arena[A_NAMES].p; db.d_blocks = d_blocks + k.b0; db.n_blocks = k.b1 - k.b0;
             db.d_ref = ctx->d_ref; db.ref_bytes = ctx->ref_bytes; db.d_out = (uint8_t *)ctx->arena[A_OUT].p; db.out_bytes = scratch;
-            db.d_results = d_res + c0; db.seq_bytes = hb->seq_bytes; db.n_tok = ntok; db.n_recs = hb->n_recs;
+            db.d_results = d_res + k.b0; db.seq_bytes = hb->seq_bytes; db.n_tok = ntok; db.n_recs = hb->n_recs;
             db.caps = hb->caps;
-            rc = encode_blocks_launch(ctx, &db, ks, nb);
+            rc = long_reads ? cbc_gpu_long_encode_blocks_device(ctx, &db, ks) : encode_blocks_launch(ctx, &db, ks, nb);
             if (rc) goto done;
         }
         /* the context's own stream joins the kernel streams, then: sizes -> offsets -> compaction -> D2H */
@@ -728,12 +679,7 @@ static int encode_blocks_impl(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, const 
             GO(hipGetLastError(), "launch cbc_compact_kernel");
         }
     }
-    for (uint32_t b = 0; b < nb; b++) {
-        if (res[b].status != CBC_ST_OK && rc == CBC_OK) {
-            snprintf(ctx->err, sizeof ctx->err, "block %u failed with status %u at record %u", b, res[b].status, res[b].fail_read);
-            rc = CBC_E_BLOCK;
-        }
-    }
+    rc = blocks_failed(ctx, res, nb, "failed");
     if (!out) {
         /* keep them: appended to the stash (a grow-with-copy buffer), for cbc_gpu_group_gather / cbc_gpu_stash_fetch */
         if (total) {
@@ -751,21 +697,36 @@ static int encode_blocks_impl(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, const 
             ctx->stash_len += total;
         }
     } else {
-    if (total > out_cap) { rc = set_err(ctx, CBC_E_ARG, "out_cap too small for the compacted payloads", hipSuccess); goto done; }
-    if (total) {
-        GO(hipMemcpyAsync(out, d_compact, total, hipMemcpyDeviceToHost, ctx->stream), "D2H payloads");
-        GO(hipStreamSynchronize(ctx->stream), "D2H payloads");
-    }
+        if (total > out_cap) { rc = set_err(ctx, CBC_E_ARG, "out_cap too small for the compacted payloads", hipSuccess); goto done; }
+        if (total) {
+            GO(hipMemcpyAsync(out, d_compact, total, hipMemcpyDeviceToHost, ctx->stream), "D2H payloads");
+            GO(hipStreamSynchronize(ctx->stream), "D2H payloads");
+        }
     }
     tm.d2h_bytes = total + (uint64_t)nb * (sizeof(cbc_block_result) + 8) + 8;
 done:
-#undef GO
-#undef NEED
     if (rc && rc != CBC_E_BLOCK) (void)hipDeviceSynchronize();   /* nothing of a failed call may still be running over the arenas */
     if (res && res != results) free(res);
     tm.total_s = wall_now() - T0;
     ctx->last_e2e = tm;
     return rc;
+}
+
+/* host-buffer entry points: payload areas from the caps alone (O(blocks)); a batch whose cap_var is not a bound -- not from
+ * the packers -- gets OUT_FULL / CAP_VAR statuses from the kernel, never a wrong byte */
+API int cbc_gpu_encode_blocks(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, uint8_t *out, uint64_t out_cap,
+                              uint64_t *out_offsets, cbc_block_result *results)
+{
+    if (!hb || !hb->seq) return CBC_E_ARG;
+    return encode_blocks_impl(ctx, hb, cbc_plan_output_caps(hb->blocks, hb->n_blocks, &hb->caps), NULL, NULL, 0,
+                              out, out_cap, out_offsets, results);
+}
+API int cbc_gpu_encode_blocks_2bit(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, const uint32_t *seq_codes, const cbc_2bit_run_dev *seq_runs,
+                                   uint64_t n_seq_runs, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, cbc_block_result *results)
+{
+    if (!hb || !seq_codes || (n_seq_runs && !seq_runs)) return CBC_E_ARG;
+    return encode_blocks_impl(ctx, hb, cbc_plan_output_caps(hb->blocks, hb->n_blocks, &hb->caps), seq_codes, seq_runs, n_seq_runs,
+                              out, out_cap, out_offsets, results);
 }
 
 API int cbc_gpu_last_e2e(cbc_gpu_ctx *ctx, cbc_e2e_times *out)
@@ -957,10 +918,6 @@ API int cbc_gpu_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device_batc
     return decode_blocks_launch(ctx, b, hip_stream, 0u);
 }
 
-/* The host-buffer decode path as a pipeline, mirror of encode_blocks_impl: the payloads (2 bytes per read) go H2D at once;
- * the blocks are decoded in chunks on the two kernel streams, and chunk c's records and bases (bytes, or 2-bit rows packed by
- * cbc_pack_2bit_kernel) come back on the copy stream while the later chunks are still being decoded.  Device arrays are the
- * context's arenas. */
 /* region decode's part of decode_blocks_impl: the span bound, the region, where the text goes and what came of it
  * (text_bytes == NULL: the span decode alone, records and rows come back as in a plain decode) */
 struct region_req {
@@ -968,26 +925,31 @@ struct region_req {
     uint8_t *text; uint64_t text_cap; uint64_t *text_bytes, *n_selected;
 };
 
+/* The host-buffer decode path as a pipeline, mirror of encode_blocks_impl: the payloads (2 bytes per read) go H2D at once;
+ * the blocks are decoded in chunks (cbc_plan_chunks) on the kernel streams, and chunk c's records and bases (bytes, or 2-bit
+ * rows packed by cbc_pack_2bit_kernel) come back on the copy stream while the later chunks are still being decoded.  Device
+ * arrays are the context's arenas.  Region decode (nothing comes back before the text is built) and long reads (their
+ * launches share the context's table scratch, A_LSCR; the long decoder takes no var scratch) are one chunk. */
 static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, cbc_dec_block_desc *blocks,
                               uint32_t n_blocks, const cbc_lds_caps *caps, cbc_read_rec *recs, uint64_t n_recs,
                               uint8_t *seq, uint64_t seq_bytes, uint32_t *codes_out, uint64_t *exc_idx, uint8_t *exc_val,
-                              uint64_t exc_cap, uint64_t *n_exc, cbc_block_result *results, const region_req *rg = NULL)
+                              uint64_t exc_cap, uint64_t *n_exc, cbc_block_result *results, const region_req *rg = NULL,
+                              bool long_reads = false)
 {
+    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (n_blocks == 0) return CBC_OK;
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     const double T0 = wall_now();
     cbc_e2e_times tm; memset(&tm, 0, sizeof tm);
-    const bool two_bit = codes_out != NULL;
+    const bool two_bit = codes_out != NULL, text = rg && rg->text_bytes;
     const uint32_t stride = blocks[0].seq_stride;
     cbc_block_result *res = NULL;
     int rc = CBC_OK;
-    const uint64_t vs_words = (uint64_t)n_blocks * caps->cap_var;
     const uint64_t n_words = two_bit ? n_recs * (stride >> 4) : 0;
     unsigned long long got = 0;
     cbc_block_result *cnt = NULL;                             /* region decode: the filter's per-block counts */
     uint64_t total = 0, kept = 0;
-#define GO(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = set_err(ctx, CBC_E_NODEV, what, e_); goto done; } } while (0)
-#define NEED(k, bytes, what) do { rc = arena_need(ctx, k, bytes, what); if (rc) goto done; } while (0)
-    NEED(A_VS, vs_words * 4 + 16, "hipMalloc var scratch");
+    if (!long_reads) NEED(A_VS, (uint64_t)n_blocks * caps->cap_var * 4 + 16, "hipMalloc var scratch");
     NEED(A_IN, in_bytes + 16, "hipMalloc in");
     NEED(A_BLOCKS, (uint64_t)n_blocks * sizeof(cbc_dec_block_desc), "hipMalloc blocks");
     NEED(A_RECS, n_recs * sizeof(cbc_read_rec) + 16, "hipMalloc recs");
@@ -999,7 +961,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         NEED(A_EXC_V, (exc_cap ? exc_cap : 1), "hipMalloc exceptions");
         NEED(A_CNT, 8, "hipMalloc counter");
     }
-    if (rg && rg->text_bytes) {
+    if (text) {
         NEED(A_TEXT, rg->text_cap + 16, "hipMalloc region text");
         NEED(A_RWS, (uint64_t)n_blocks * 8, "hipMalloc window starts");
         NEED(A_RCNT, (uint64_t)n_blocks * sizeof(cbc_block_result), "hipMalloc region counts");
@@ -1017,47 +979,34 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         GO(hipMemcpyAsync(d_blocks, blocks, (uint64_t)n_blocks * sizeof(cbc_dec_block_desc), hipMemcpyHostToDevice, sc), "H2D blocks");
         GO(hipMemsetAsync(d_res, 0xff, (uint64_t)n_blocks * sizeof(cbc_block_result), sc), "memset results");
         if (two_bit) GO(hipMemsetAsync(ctx->arena[A_CNT].p, 0, 8, sc), "memset counter");
-        if (rg && rg->text_bytes) GO(hipMemcpyAsync(ctx->arena[A_RWS].p, rg->window_start, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D window starts");
+        if (text) GO(hipMemcpyAsync(ctx->arena[A_RWS].p, rg->window_start, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D window starts");
         GO(hipEventRecord(ctx->ev_done[0], sc), "hipEventRecord");       /* inputs are on the device */
         tm.h2d_bytes = in_bytes + (uint64_t)n_blocks * sizeof(cbc_dec_block_desc);
-        /* chunks of consecutive blocks whose outputs are consecutive too */
-        uint32_t n_chunks = 1, cut[CBC_MAX_CHUNKS + 1];
-        bool contiguous = true;
-        for (uint32_t b = 0; b + 1 < n_blocks && contiguous; b++)
-            contiguous = blocks[b + 1].rec_base == blocks[b].rec_base + blocks[b].n_reads && blocks[b + 1].seq_base >= blocks[b].seq_base;
-        contiguous = contiguous && blocks[n_blocks - 1].rec_base + blocks[n_blocks - 1].n_reads <= n_recs && blocks[n_blocks - 1].seq_base <= seq_bytes;
-        if (contiguous && n_blocks >= 512 && !(rg && rg->text_bytes)) {          /* region decode: nothing comes back before the text is built */
-            uint64_t want = (n_recs * 16 + (two_bit ? n_words * 4 : seq_bytes)) / (64ull << 20);
-            if (want > CBC_MAX_CHUNKS) want = CBC_MAX_CHUNKS;
-            if (want > n_blocks / 256) want = n_blocks / 256;
-            if (want >= 2) n_chunks = (uint32_t)want;
-        }
-        cut[0] = 0; cut[n_chunks] = n_blocks;
-        for (uint32_t c = 1; c < n_chunks; c++) {
-            const uint64_t target = blocks[0].rec_base + (blocks[n_blocks - 1].rec_base + blocks[n_blocks - 1].n_reads - blocks[0].rec_base) * c / n_chunks;
-            uint32_t lo = cut[c - 1] + 1, hi = n_blocks - (n_chunks - c);
-            while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (blocks[mid].rec_base < target) lo = mid + 1; else hi = mid; }
-            cut[c] = lo;
-        }
-        tm.n_chunks = n_chunks;
-        for (uint32_t c = 0; c < n_chunks; c++) {
-            const uint32_t c0 = cut[c], c1 = cut[c + 1];
-            const bool whole = !contiguous || n_chunks == 1;
-            const uint64_t s0 = whole ? 0 : blocks[c0].seq_base, s1 = whole || c1 == n_blocks ? seq_bytes : blocks[c1].seq_base;
+        cbc_chunk_plan P;
+        cbc_plan_chunks(blocks, n_blocks, n_recs, seq_bytes, 0, n_recs * 16 + (two_bit ? n_words * 4 : seq_bytes), !long_reads && !text, &P);
+        tm.n_chunks = P.n_chunks;
+        for (uint32_t c = 0; c < P.n_chunks; c++) {
+            const cbc_chunk &k = P.c[c];
             hipStream_t ks = ctx->s_k[c % CBC_N_KSTREAMS];
             GO(hipStreamWaitEvent(ks, ctx->ev_done[0], 0), "hipStreamWaitEvent");
-            if (s1 > s0) GO(hipMemsetAsync(d_seq + s0, 0, s1 - s0 + (c1 == n_blocks || whole ? 32 : 0), ks), "memset seq");
+            if (k.s1 > k.s0) GO(hipMemsetAsync(d_seq + k.s0, 0, k.s1 - k.s0 + (k.b1 == n_blocks ? 32 : 0), ks), "memset seq");
             cbc_dec_device_batch db;
             memset(&db, 0, sizeof db);
-            db.d_in = d_in; db.in_bytes = in_bytes + 16; db.d_blocks = d_blocks + c0; db.n_blocks = c1 - c0;
+            db.d_in = d_in; db.in_bytes = in_bytes + 16; db.d_blocks = d_blocks + k.b0; db.n_blocks = k.b1 - k.b0;
             db.d_ref = ctx->d_ref; db.ref_bytes = ctx->ref_bytes; db.d_recs = d_recs; db.n_recs = n_recs;
-            db.d_seq = d_seq; db.seq_bytes = seq_bytes + 32; db.d_results = d_res + c0;
-            db.caps = *caps; db.d_var_scratch = (uint32_t *)ctx->arena[A_VS].p + (uint64_t)c0 * caps->cap_var;
-            db.var_scratch_words = (uint64_t)(c1 - c0) * caps->cap_var;
-            if (rg && rg->text_bytes) GO(hipEventRecord(ctx->ev_rg[0], ks), "hipEventRecord");
-            rc = decode_blocks_launch(ctx, &db, ks, rg ? rg->smax : 0u);
+            db.d_seq = d_seq; db.d_results = d_res + k.b0; db.caps = *caps;
+            if (text) GO(hipEventRecord(ctx->ev_rg[0], ks), "hipEventRecord");
+            if (long_reads) {
+                db.seq_bytes = seq_bytes + 16;
+                rc = cbc_gpu_long_decode_blocks_device(ctx, &db, ks);
+            } else {
+                db.seq_bytes = seq_bytes + 32;
+                db.d_var_scratch = (uint32_t *)ctx->arena[A_VS].p + (uint64_t)k.b0 * caps->cap_var;
+                db.var_scratch_words = (uint64_t)(k.b1 - k.b0) * caps->cap_var;
+                rc = decode_blocks_launch(ctx, &db, ks, rg ? rg->smax : 0u);
+            }
             if (rc) goto done;
-            if (rg && rg->text_bytes) {                        /* one chunk: filter, scan, text on the decode's stream */
+            if (text) {                                        /* one chunk: filter, scan, text on the decode's stream */
                 GO(hipEventRecord(ctx->ev_rg[1], ks), "hipEventRecord");
                 cbc_region_args ra;
                 memset(&ra, 0, sizeof ra);
@@ -1075,40 +1024,36 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
                 ctx->have_region_timing = 1;
             }
-            const uint64_t r0 = whole ? 0 : blocks[c0].rec_base, r1 = whole ? n_recs : blocks[c1 - 1].rec_base + blocks[c1 - 1].n_reads;
-            if (two_bit && r1 > r0) {
-                const uint64_t w0 = r0 * (stride >> 4), w1 = r1 * (stride >> 4);
+            if (two_bit && k.r1 > k.r0) {
+                const uint64_t w0 = k.r0 * (stride >> 4), w1 = k.r1 * (stride >> 4);
                 hipLaunchKernelGGL(cbc_pack_2bit_kernel, dim3((unsigned)((w1 - w0 + 255) / 256)), dim3(256), 0, ks,
-                                   (const uint8_t *)d_seq, (const cbc_read_rec *)d_recs, r0, r1, stride, (uint32_t *)ctx->arena[A_CODES].p,
+                                   (const uint8_t *)d_seq, (const cbc_read_rec *)d_recs, k.r0, k.r1, stride, (uint32_t *)ctx->arena[A_CODES].p,
                                    (uint64_t *)ctx->arena[A_EXC_I].p, (uint8_t *)ctx->arena[A_EXC_V].p, exc_cap, (unsigned long long *)ctx->arena[A_CNT].p);
                 GO(hipGetLastError(), "launch cbc_pack_2bit_kernel");
             }
             GO(hipEventRecord(ctx->ev_chunk[c], ks), "hipEventRecord");
         }
         tm.issue_s = wall_now() - T0;
-        for (uint32_t c = 0; c < n_chunks && !(rg && rg->text_bytes); c++) {          /* the chunks come back in order while later ones are being decoded */
-            const uint32_t c0 = cut[c], c1 = cut[c + 1];
-            const bool whole = !contiguous || n_chunks == 1;
-            const uint64_t r0 = whole ? 0 : blocks[c0].rec_base, r1 = whole ? n_recs : blocks[c1 - 1].rec_base + blocks[c1 - 1].n_reads;
-            const uint64_t s0 = whole ? 0 : blocks[c0].seq_base, s1 = whole || c1 == n_blocks ? seq_bytes : blocks[c1].seq_base;
+        for (uint32_t c = 0; c < P.n_chunks && !text; c++) {         /* the chunks come back in order while later ones are being decoded */
+            const cbc_chunk &k = P.c[c];
             GO(hipStreamWaitEvent(sc, ctx->ev_chunk[c], 0), "hipStreamWaitEvent");
-            if (r1 > r0) GO(hipMemcpyAsync(recs + r0, d_recs + r0, (r1 - r0) * sizeof(cbc_read_rec), hipMemcpyDeviceToHost, sc), "D2H recs");
-            tm.d2h_bytes += (r1 - r0) * sizeof(cbc_read_rec);
+            if (k.r1 > k.r0) GO(hipMemcpyAsync(recs + k.r0, d_recs + k.r0, (k.r1 - k.r0) * sizeof(cbc_read_rec), hipMemcpyDeviceToHost, sc), "D2H recs");
+            tm.d2h_bytes += (k.r1 - k.r0) * sizeof(cbc_read_rec);
             if (two_bit) {
-                const uint64_t w0 = r0 * (stride >> 4), w1 = r1 * (stride >> 4);
+                const uint64_t w0 = k.r0 * (stride >> 4), w1 = k.r1 * (stride >> 4);
                 if (w1 > w0) GO(hipMemcpyAsync(codes_out + w0, (uint32_t *)ctx->arena[A_CODES].p + w0, (w1 - w0) * 4, hipMemcpyDeviceToHost, sc), "D2H codes");
                 tm.d2h_bytes += (w1 - w0) * 4;
-            } else if (s1 > s0) {
-                GO(hipMemcpyAsync(seq + s0, d_seq + s0, s1 - s0, hipMemcpyDeviceToHost, sc), "D2H seq");
-                tm.d2h_bytes += s1 - s0;
+            } else if (k.s1 > k.s0) {
+                GO(hipMemcpyAsync(seq + k.s0, d_seq + k.s0, k.s1 - k.s0, hipMemcpyDeviceToHost, sc), "D2H seq");
+                tm.d2h_bytes += k.s1 - k.s0;
             }
         }
         res = results ? results : (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
         if (!res) { rc = CBC_E_NOMEM; goto done; }
-        if (rg && rg->text_bytes) GO(hipStreamWaitEvent(sc, ctx->ev_chunk[0], 0), "hipStreamWaitEvent");
+        if (text) GO(hipStreamWaitEvent(sc, ctx->ev_chunk[0], 0), "hipStreamWaitEvent");
         GO(hipMemcpyAsync(res, d_res, (uint64_t)n_blocks * sizeof(cbc_block_result), hipMemcpyDeviceToHost, sc), "D2H results");
         if (two_bit) GO(hipMemcpyAsync(&got, ctx->arena[A_CNT].p, 8, hipMemcpyDeviceToHost, sc), "D2H counter");
-        if (rg && rg->text_bytes) {
+        if (text) {
             cnt = (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
             if (!cnt) { rc = CBC_E_NOMEM; goto done; }
             GO(hipMemcpyAsync(cnt, ctx->arena[A_RCNT].p, (uint64_t)n_blocks * sizeof(cbc_block_result), hipMemcpyDeviceToHost, sc), "D2H region counts");
@@ -1116,7 +1061,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         }
         GO(hipStreamSynchronize(sc), "decode kernel");
         tm.kernels_done_s = wall_now() - T0;
-        if (rg && rg->text_bytes) {
+        if (text) {
             for (uint32_t b = 0; b < n_blocks; b++) kept += cnt[b].n_symbols;
             *rg->text_bytes = total; *rg->n_selected = kept;
             if (total > rg->text_cap) { rc = set_err(ctx, CBC_E_ARG, "text_cap too small for the region's text", hipSuccess); goto done; }
@@ -1137,14 +1082,8 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
             }
         }
     }
-    for (uint32_t b = 0; b < n_blocks; b++)
-        if (res[b].status != CBC_ST_OK && rc == CBC_OK) {
-            snprintf(ctx->err, sizeof ctx->err, "block %u failed to decode with status %u at record %u", b, res[b].status, res[b].fail_read);
-            rc = CBC_E_BLOCK;
-        }
+    rc = blocks_failed(ctx, res, n_blocks, "failed to decode");
 done:
-#undef GO
-#undef NEED
     if (rc && rc != CBC_E_BLOCK) (void)hipDeviceSynchronize();
     if (res && res != results) free(res);
     free(cnt);
@@ -1158,8 +1097,6 @@ API int cbc_gpu_decode_blocks(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                               uint8_t *seq, uint64_t seq_bytes, cbc_block_result *results)
 {
     if (!ctx || !in || !blocks || !caps || !recs || !seq) return CBC_E_ARG;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
-    if (n_blocks == 0) return CBC_OK;
     return decode_blocks_impl(ctx, in, in_bytes, blocks, n_blocks, caps, recs, n_recs, seq, seq_bytes, NULL, NULL, NULL, 0, NULL, results);
 }
 
@@ -1206,8 +1143,6 @@ API int cbc_gpu_decode_blocks_span(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t
                                    uint8_t *seq, uint64_t seq_bytes, cbc_block_result *results)
 {
     if (!ctx || !in || !blocks || !caps || !recs || !seq || smax == 0) return CBC_E_ARG;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
-    if (n_blocks == 0) return CBC_OK;
     region_req rg;
     memset(&rg, 0, sizeof rg);
     rg.smax = smax;
@@ -1273,7 +1208,6 @@ static int stream_encode(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, int per_seg
     uint32_t grid = n_streams < 32u ? n_streams : 32u;            /* pool of var tables: 67 MB each */
     if (caps.cap_pos > CBC_STREAM_POS_MAX) { free(segs); free(res); return set_err(ctx, CBC_E_ARG, "cap_pos beyond MAX_ALPHA", hipSuccess); }
     if (lds > 160u * 1024u) { free(segs); free(res); return set_err(ctx, CBC_E_ARG, "stream tables need more than 160 KiB of LDS", hipSuccess); }
-#define GO(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = set_err(ctx, CBC_E_NODEV, what, e_); goto done; } } while (0)
     GO(hipMalloc(&d_recs, hb->n_recs * sizeof(cbc_read_rec) + 16), "hipMalloc recs");
     GO(hipMalloc(&d_seq, hb->seq_bytes + 16), "hipMalloc seq");
     GO(hipMalloc(&d_tok, ntok * 4 + 16), "hipMalloc tok");
@@ -1325,7 +1259,6 @@ static int stream_encode(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, int per_seg
         if (sres) { sres->nbytes = off; sres->status = res[0].status; sres->fail_read = res[0].fail_read; sres->n_symbols = res[0].n_symbols; }
     }
 done:
-#undef GO
     free(segs); free(res);
     if (d_recs) (void)hipFree(d_recs); if (d_seq) (void)hipFree(d_seq); if (d_tok) (void)hipFree(d_tok);
     if (d_names) (void)hipFree(d_names); if (d_segs) (void)hipFree(d_segs); if (d_out) (void)hipFree(d_out);
@@ -1362,7 +1295,6 @@ API int cbc_gpu_decode_stream(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     void *d_in = NULL, *d_co = NULL, *d_cl = NULL, *d_recs = NULL, *d_seq = NULL, *d_res = NULL, *d_vtab = NULL, *d_aux = NULL;
     cbc_block_result res; memset(&res, 0xff, sizeof res);
     int rc = CBC_OK;
-#define GO(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = set_err(ctx, CBC_E_NODEV, what, e_); goto done; } } while (0)
     GO(hipMalloc(&d_in, in_bytes + 16), "hipMalloc in");
     GO(hipMalloc(&d_co, (uint64_t)n_contigs * 8), "hipMalloc contigs");
     GO(hipMalloc(&d_cl, (uint64_t)n_contigs * 8), "hipMalloc contigs");
@@ -1404,7 +1336,6 @@ API int cbc_gpu_decode_stream(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         rc = CBC_E_BLOCK;
     }
 done:
-#undef GO
     if (d_in) (void)hipFree(d_in); if (d_co) (void)hipFree(d_co); if (d_cl) (void)hipFree(d_cl); if (d_recs) (void)hipFree(d_recs);
     if (d_seq) (void)hipFree(d_seq); if (d_res) (void)hipFree(d_res); if (d_vtab) (void)hipFree(d_vtab); if (d_aux) (void)hipFree(d_aux);
     return rc;
@@ -1517,79 +1448,25 @@ API int cbc_gpu_long_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device
     return CBC_OK;
 }
 
-/* host buffers in, compacted payloads out; a block whose area was too small (CBC_ST_OUT_FULL) makes the whole batch
- * run once more with the worst-case areas */
+/* host buffers in, compacted payloads out: the block pipeline (encode_blocks_impl) as one chunk.  The areas are planned at
+ * 0.5 bytes per base; a block whose area was too small (CBC_ST_OUT_FULL) makes the whole batch run once more with the
+ * worst-case areas.  out == NULL is refused: the stash is for block-mode bitstreams. */
 API int cbc_gpu_long_encode_blocks(cbc_gpu_ctx *ctx, const cbc_host_batch *hb, uint8_t *out, uint64_t out_cap,
                                    uint64_t *out_offsets, cbc_block_result *results)
 {
-    if (!ctx || !hb || !out || !out_offsets) return CBC_E_ARG;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (!ctx || !hb || !hb->seq || !out || !out_offsets) return CBC_E_ARG;
     const uint32_t nb = hb->n_blocks;
-    out_offsets[0] = 0;
-    if (nb == 0) return CBC_OK;
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    void *d_recs = NULL, *d_seq = NULL, *d_tok = NULL, *d_names = NULL, *d_blocks = NULL, *d_out = NULL, *d_res = NULL, *d_off = NULL, *d_packed = NULL;
-    cbc_block_result *res = NULL;
-    int rc = CBC_OK;
-    uint64_t total = 0, scratch = 0;
-    const uint64_t ntok = hb->n_tok ? hb->n_tok : 1;
-#define GO(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = set_err(ctx, CBC_E_NODEV, what, e_); goto done; } } while (0)
-    GO(hipMalloc(&d_recs, hb->n_recs * sizeof(cbc_read_rec) + 16), "hipMalloc recs");
-    GO(hipMalloc(&d_seq, hb->seq_bytes + 16), "hipMalloc seq");
-    GO(hipMalloc(&d_tok, ntok * 4 + 16), "hipMalloc tok");
-    GO(hipMalloc(&d_names, hb->names_bytes + 16), "hipMalloc names");
-    GO(hipMalloc(&d_blocks, (uint64_t)nb * sizeof(cbc_block_desc)), "hipMalloc blocks");
-    GO(hipMalloc(&d_res, (uint64_t)nb * sizeof(cbc_block_result)), "hipMalloc results");
-    GO(hipMalloc(&d_off, ((uint64_t)nb + 1) * 8), "hipMalloc offsets");
-    GO(hipMemcpyAsync(d_recs, hb->recs, hb->n_recs * sizeof(cbc_read_rec), hipMemcpyHostToDevice, ctx->stream), "H2D recs");
-    GO(hipMemcpyAsync(d_seq, hb->seq, hb->seq_bytes, hipMemcpyHostToDevice, ctx->stream), "H2D seq");
-    GO(hipMemcpyAsync(d_tok, hb->tok, hb->n_tok * 4, hipMemcpyHostToDevice, ctx->stream), "H2D tok");
-    GO(hipMemcpyAsync(d_names, hb->names, hb->names_bytes, hipMemcpyHostToDevice, ctx->stream), "H2D names");
-    res = results ? results : (cbc_block_result *)malloc((size_t)nb * sizeof(cbc_block_result));
-    if (!res) { rc = CBC_E_NOMEM; goto done; }
-    for (uint32_t attempt = 0; attempt < 2; attempt++) {
-        scratch = cbc_gpu_long_plan_output(hb->blocks, nb, hb->recs, attempt == 0 ? 8u : 200u);     /* 0.5, then 12.5 bytes per base */
-        if (d_out) { (void)hipFree(d_out); d_out = NULL; }
-        GO(hipMalloc(&d_out, scratch), "hipMalloc out scratch");
-        GO(hipMemcpyAsync(d_blocks, hb->blocks, (uint64_t)nb * sizeof(cbc_block_desc), hipMemcpyHostToDevice, ctx->stream), "H2D blocks");
-        GO(hipMemsetAsync(d_res, 0xff, (uint64_t)nb * sizeof(cbc_block_result), ctx->stream), "memset results");
-        cbc_device_batch db;
-        memset(&db, 0, sizeof db);
-        db.d_recs = (const cbc_read_rec *)d_recs; db.d_seq = (const uint8_t *)d_seq; db.d_tok = (const uint32_t *)d_tok;
-        db.d_names = (const uint8_t *)d_names; db.d_blocks = (const cbc_block_desc *)d_blocks; db.n_blocks = nb;
-        db.d_ref = ctx->d_ref; db.ref_bytes = ctx->ref_bytes; db.d_out = (uint8_t *)d_out; db.out_bytes = scratch;
-        db.d_results = (cbc_block_result *)d_res; db.seq_bytes = hb->seq_bytes; db.n_tok = ntok; db.n_recs = hb->n_recs; db.caps = hb->caps;
-        rc = cbc_gpu_long_encode_blocks_device(ctx, &db, CBC_CTX_STREAM);
-        if (rc) goto done;
-        GO(hipMemcpyAsync(res, d_res, (uint64_t)nb * sizeof(cbc_block_result), hipMemcpyDeviceToHost, ctx->stream), "D2H results");
-        GO(hipStreamSynchronize(ctx->stream), "long encode kernel");
-        int full = 0;
-        for (uint32_t b = 0; b < nb; b++) if (res[b].status == CBC_ST_OUT_FULL) full = 1;
-        if (!full) break;
-    }
-    GO(hipMalloc(&d_packed, scratch), "hipMalloc packed");
-    rc = cbc_gpu_compact_device(ctx, (const uint8_t *)d_out, (const cbc_block_desc *)d_blocks, (const cbc_block_result *)d_res,
-                                nb, (uint64_t *)d_off, (uint8_t *)d_packed, scratch, CBC_CTX_STREAM);
-    if (rc) goto done;
-    GO(hipMemcpyAsync(out_offsets, d_off, ((uint64_t)nb + 1) * 8, hipMemcpyDeviceToHost, ctx->stream), "D2H offsets");
-    GO(hipStreamSynchronize(ctx->stream), "compaction");
-    for (uint32_t b = 0; b < nb; b++)
-        if (res[b].status != CBC_ST_OK && rc == CBC_OK) {
-            snprintf(ctx->err, sizeof ctx->err, "block %u failed with status %u at record %u", b, res[b].status, res[b].fail_read);
-            rc = CBC_E_BLOCK;
-        }
-    total = out_offsets[nb];
-    if (total > out_cap) { rc = set_err(ctx, CBC_E_ARG, "out_cap too small for the compacted payloads", hipSuccess); goto done; }
-    if (total) {
-        GO(hipMemcpyAsync(out, d_packed, total, hipMemcpyDeviceToHost, ctx->stream), "D2H payloads");
-        GO(hipStreamSynchronize(ctx->stream), "D2H payloads");
-    }
-done:
-#undef GO
-    if (res && res != results) free(res);
-    if (d_recs) (void)hipFree(d_recs); if (d_seq) (void)hipFree(d_seq); if (d_tok) (void)hipFree(d_tok);
-    if (d_names) (void)hipFree(d_names); if (d_blocks) (void)hipFree(d_blocks); if (d_out) (void)hipFree(d_out);
-    if (d_res) (void)hipFree(d_res); if (d_off) (void)hipFree(d_off); if (d_packed) (void)hipFree(d_packed);
+    cbc_block_result *res = results ? results : (cbc_block_result *)malloc(((size_t)nb + 1) * sizeof(cbc_block_result));
+    if (!res) return CBC_E_NOMEM;
+    memset(res, 0xff, (size_t)nb * sizeof(cbc_block_result)); /* a call that fails before the results arrive: no status, no retry */
+    int rc = encode_blocks_impl(ctx, hb, cbc_gpu_long_plan_output(hb->blocks, nb, hb->recs, 8u), NULL, NULL, 0,
+                                out, out_cap, out_offsets, res, NULL, NULL, true);
+    bool full = false;
+    for (uint32_t b = 0; b < nb; b++) full = full || res[b].status == CBC_ST_OUT_FULL;
+    if (full)
+        rc = encode_blocks_impl(ctx, hb, cbc_gpu_long_plan_output(hb->blocks, nb, hb->recs, 200u), NULL, NULL, 0,
+                                out, out_cap, out_offsets, res, NULL, NULL, true);
+    if (res != results) free(res);
     return rc;
 }
 
@@ -1598,49 +1475,8 @@ API int cbc_gpu_long_decode_blocks(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t
                                    uint8_t *seq, uint64_t seq_bytes, cbc_block_result *results)
 {
     if (!ctx || !in || !blocks || !caps || !recs || !seq) return CBC_E_ARG;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
-    if (n_blocks == 0) return CBC_OK;
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    void *d_in = NULL, *d_blocks = NULL, *d_recs = NULL, *d_seq = NULL, *d_res = NULL;
-    cbc_block_result *res = NULL;
-    int rc = CBC_OK;
-#define GO(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = set_err(ctx, CBC_E_NODEV, what, e_); goto done; } } while (0)
-    GO(hipMalloc(&d_in, in_bytes + 16), "hipMalloc in");
-    GO(hipMalloc(&d_blocks, (uint64_t)n_blocks * sizeof(cbc_dec_block_desc)), "hipMalloc blocks");
-    GO(hipMalloc(&d_recs, n_recs * sizeof(cbc_read_rec) + 16), "hipMalloc recs");
-    GO(hipMalloc(&d_seq, seq_bytes + 16), "hipMalloc seq");
-    GO(hipMalloc(&d_res, (uint64_t)n_blocks * sizeof(cbc_block_result)), "hipMalloc results");
-    GO(hipMemsetAsync((uint8_t *)d_in + in_bytes, 0, 16, ctx->stream), "memset pad");
-    GO(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream), "H2D payloads");
-    GO(hipMemcpyAsync(d_blocks, blocks, (uint64_t)n_blocks * sizeof(cbc_dec_block_desc), hipMemcpyHostToDevice, ctx->stream), "H2D blocks");
-    GO(hipMemsetAsync(d_res, 0xff, (uint64_t)n_blocks * sizeof(cbc_block_result), ctx->stream), "memset results");
-    {
-        cbc_dec_device_batch db;
-        memset(&db, 0, sizeof db);
-        db.d_in = (const uint8_t *)d_in; db.in_bytes = in_bytes + 16; db.d_blocks = (const cbc_dec_block_desc *)d_blocks;
-        db.n_blocks = n_blocks; db.d_ref = ctx->d_ref; db.ref_bytes = ctx->ref_bytes; db.d_recs = (cbc_read_rec *)d_recs;
-        db.n_recs = n_recs; db.d_seq = (uint8_t *)d_seq; db.seq_bytes = seq_bytes + 16; db.d_results = (cbc_block_result *)d_res;
-        db.caps = *caps;
-        rc = cbc_gpu_long_decode_blocks_device(ctx, &db, CBC_CTX_STREAM);
-        if (rc) goto done;
-    }
-    res = results ? results : (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
-    if (!res) { rc = CBC_E_NOMEM; goto done; }
-    GO(hipMemcpyAsync(res, d_res, (uint64_t)n_blocks * sizeof(cbc_block_result), hipMemcpyDeviceToHost, ctx->stream), "D2H results");
-    GO(hipMemcpyAsync(recs, d_recs, n_recs * sizeof(cbc_read_rec), hipMemcpyDeviceToHost, ctx->stream), "D2H recs");
-    GO(hipMemcpyAsync(seq, d_seq, seq_bytes, hipMemcpyDeviceToHost, ctx->stream), "D2H seq");
-    GO(hipStreamSynchronize(ctx->stream), "long decode kernel");
-    for (uint32_t b = 0; b < n_blocks; b++)
-        if (res[b].status != CBC_ST_OK && rc == CBC_OK) {
-            snprintf(ctx->err, sizeof ctx->err, "block %u failed to decode with status %u at record %u", b, res[b].status, res[b].fail_read);
-            rc = CBC_E_BLOCK;
-        }
-done:
-#undef GO
-    if (res && res != results) free(res);
-    if (d_in) (void)hipFree(d_in); if (d_blocks) (void)hipFree(d_blocks); if (d_recs) (void)hipFree(d_recs);
-    if (d_seq) (void)hipFree(d_seq); if (d_res) (void)hipFree(d_res);
-    return rc;
+    return decode_blocks_impl(ctx, in, in_bytes, blocks, n_blocks, caps, recs, n_recs, seq, seq_bytes, NULL, NULL, NULL, 0, NULL,
+                              results, NULL, true);
 }
 
 /* decode with the bases returned as 2-bit rows (include/cbc_gpu.h) */
@@ -1710,8 +1546,7 @@ API int cbc_gpu_tokenise_sam(cbc_gpu_ctx *ctx, const char *sam, uint64_t len, ui
     uint64_t n_nl = 0, n_lines = 0, n_recs = 0, seq_bytes = 0, n_tok = 0;
     unsigned long long cnt[2] = { ~0ull, 0ull };
     cbc_tok_perline bad_pl;
-#define GO(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = set_err(ctx, CBC_E_NODEV, what, e_); goto done; } } while (0)
-#define GOR(call) do { rc = (call); if (rc) goto done; } while (0)
+#define RCCHK(call) do { rc = (call); if (rc) goto done; } while (0)
     const bool times = getenv("CBC_TOK_TIMES") != NULL;            /* diagnostic: stage wall times on stderr */
     auto now = []() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
     double T0 = now(), T1 = T0, T2 = T0, T3 = T0;
@@ -1723,7 +1558,7 @@ API int cbc_gpu_tokenise_sam(cbc_gpu_ctx *ctx, const char *sam, uint64_t len, ui
     GO(hipMalloc(&d_tmp, (len / 1024 + n_tiles / 1024 + 16) * 8), "hipMalloc scan scratch");   /* block totals of the largest scan: n_lines <= len */
     hipLaunchKernelGGL(cbc_tok_count_kernel, dim3((unsigned)n_tiles), dim3(64), 0, ctx->stream, (const uint8_t *)d_sam, len, (uint32_t *)d_tc);
     GO(hipGetLastError(), "launch cbc_tok_count_kernel");
-    GOR(scan_u32(ctx, (const uint32_t *)d_tc, n_tiles, (uint64_t *)d_tb, (uint64_t *)d_tmp, &n_nl));
+    RCCHK(scan_u32(ctx, (const uint32_t *)d_tc, n_tiles, (uint64_t *)d_tb, (uint64_t *)d_tmp, &n_nl));
     n_lines = n_nl + ((uint8_t)sam[len - 1] != '\n' ? 1 : 0);
     GO(hipMalloc(&d_ls, (n_lines + 2) * 8), "hipMalloc line starts");
     {
@@ -1747,9 +1582,9 @@ API int cbc_gpu_tokenise_sam(cbc_gpu_ctx *ctx, const char *sam, uint64_t len, ui
     hipLaunchKernelGGL(cbc_tok_status_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, ctx->stream, (const cbc_tok_perline *)d_pl,
                        n_lines, (unsigned long long *)d_cnt, (unsigned long long *)d_cnt + 1);
     GO(hipGetLastError(), "launch cbc_tok_status_kernel");
-    GOR(scan_u32(ctx, (const uint32_t *)d_isrec, n_lines, (uint64_t *)d_recof, (uint64_t *)d_tmp, &n_recs));
-    GOR(scan_u32(ctx, (const uint32_t *)d_vrl, n_lines, (uint64_t *)d_seqof, (uint64_t *)d_tmp, &seq_bytes));
-    GOR(scan_u32(ctx, (const uint32_t *)d_vnt, n_lines, (uint64_t *)d_tokof, (uint64_t *)d_tmp, &n_tok));
+    RCCHK(scan_u32(ctx, (const uint32_t *)d_isrec, n_lines, (uint64_t *)d_recof, (uint64_t *)d_tmp, &n_recs));
+    RCCHK(scan_u32(ctx, (const uint32_t *)d_vrl, n_lines, (uint64_t *)d_seqof, (uint64_t *)d_tmp, &seq_bytes));
+    RCCHK(scan_u32(ctx, (const uint32_t *)d_vnt, n_lines, (uint64_t *)d_tokof, (uint64_t *)d_tmp, &n_tok));
     GO(hipMemcpyAsync(cnt, d_cnt, 16, hipMemcpyDeviceToHost, ctx->stream), "D2H counters");
     GO(hipStreamSynchronize(ctx->stream), "tokenise pass 1");
     T2 = now();
@@ -1799,8 +1634,7 @@ API int cbc_gpu_tokenise_sam(cbc_gpu_ctx *ctx, const char *sam, uint64_t len, ui
         out->n_changes = nc;
     }
 done:
-#undef GO
-#undef GOR
+#undef RCCHK
     if (d_sam) (void)hipFree(d_sam); if (d_tc) (void)hipFree(d_tc); if (d_tb) (void)hipFree(d_tb); if (d_tmp) (void)hipFree(d_tmp);
     if (d_ls) (void)hipFree(d_ls); if (d_pl) (void)hipFree(d_pl); if (d_isrec) (void)hipFree(d_isrec); if (d_vrl) (void)hipFree(d_vrl);
     if (d_vnt) (void)hipFree(d_vnt); if (d_recof) (void)hipFree(d_recof); if (d_seqof) (void)hipFree(d_seqof); if (d_tokof) (void)hipFree(d_tokof);
@@ -1824,5 +1658,6 @@ API int cbc_gpu_encode_blocks_tokenised(cbc_gpu_ctx *ctx, const cbc_tok_result *
     if (!t || !t->d_seq || !t->d_tok || !hb) return CBC_E_ARG;
     if (hb->seq_bytes != t->seq_bytes + 8 || hb->n_tok != t->n_tok) return set_err(ctx, CBC_E_ARG, "batch and tokeniser result disagree", hipSuccess);
     if (!t->summaries || hb->n_recs != t->n_recs) return set_err(ctx, CBC_E_ARG, "batch and tokeniser result disagree", hipSuccess);
-    return encode_blocks_impl(ctx, hb, NULL, NULL, 0, out, out_cap, out_offsets, results, t->d_seq, t->d_tok, t->summaries);
+    return encode_blocks_impl(ctx, hb, cbc_plan_output_summaries(hb->blocks, hb->n_blocks, t->summaries), NULL, NULL, 0,
+                              out, out_cap, out_offsets, results, t->d_seq, t->d_tok);
 }

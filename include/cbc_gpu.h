@@ -349,7 +349,13 @@ uint32_t cbc_stream_read_length(const uint8_t *in, uint64_t in_bytes);
  * no reference parity exists for it (oracle/cbc_long.c is its CPU statement).  Batches come from cbc_pack_sam /
  * cbc_synth_long with cbc_pack_opts.long_reads = 1; cbc_device_batch / cbc_dec_device_batch are used as in block
  * mode (caps.cap_var is ignored).  cbc_dec_block_desc.reserved[0] = bases of the block, seq_base = where they go
- * (the decoder writes the bases compactly; cbc_read_rec.seq_off = offset inside the block). */
+ * (the decoder writes the bases compactly; cbc_read_rec.seq_off = offset inside the block).
+ * cbc_gpu_long_encode_blocks / cbc_gpu_long_decode_blocks go through the same pipeline as cbc_gpu_encode_blocks /
+ * cbc_gpu_decode_blocks, as one chunk: their device arrays are the context's grow-only arenas (no allocation per call once
+ * the arenas have their size), and they fill cbc_gpu_last_e2e.  The encode plans 0.5 bytes of payload per base and runs
+ * the whole batch once more with the worst-case areas when a block reports CBC_ST_OUT_FULL; out == NULL is refused.
+ * A call that fails before the blocks have run leaves every result's status at 0xffffffff.  The long decode returns zero
+ * bytes in the parts of seq the decoder does not write, as the block decode does. */
 uint64_t cbc_gpu_long_plan_output(cbc_block_desc *blocks, uint32_t n_blocks, const cbc_read_rec *recs, uint32_t bytes_per_16_bases);
 uint32_t cbc_gpu_long_lds_bytes(const cbc_lds_caps *caps);
 int  cbc_gpu_long_encode_blocks_device(cbc_gpu_ctx *ctx, const cbc_device_batch *batch, void *hip_stream);

@@ -97,6 +97,12 @@ extern "C" __attribute__((visibility("default")))
 uint64_t emu_plan_output(cbc_block_desc *blocks, uint32_t n_blocks, const cbc_read_rec *recs, const uint32_t *tok)
 { return cbc_plan_output(blocks, n_blocks, recs, tok); }
 
+/* the chunks the host-buffer encode path cuts a batch into (cbc_plan_chunks; split = 0: long reads, one chunk) */
+extern "C" __attribute__((visibility("default")))
+void emu_plan_chunks(const cbc_block_desc *blocks, uint32_t n_blocks, uint64_t n_recs, uint64_t seq_bytes, uint64_t n_tok,
+                     uint64_t vol, int split, cbc_chunk_plan *out)
+{ cbc_plan_chunks(blocks, n_blocks, n_recs, seq_bytes, n_tok, vol, split != 0, out); }
+
 extern "C" __attribute__((visibility("default")))
 int emu_decode_blocks(const cbc_dec_device_batch *b)
 {
