@@ -339,15 +339,22 @@ class Encoder:
         recs = np.zeros(plan.n_recs, dtype=host.REC_DTYPE)
         row_words = stride // 16
         codes = np.zeros(plan.n_recs * row_words + 4, dtype=np.uint32)
-        cap = max(1024, plan.n_recs * 4)
-        ei = np.zeros(cap, dtype=np.uint64); ev = np.zeros(cap, dtype=np.uint8)
         n_exc = ctypes.c_uint64(0)
         res = np.zeros(nb, dtype=host.RESULT_DTYPE)
         caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
         pay = np.ascontiguousarray(plan.payloads)
-        rc = lib().cbc_gpu_decode_blocks_2bit(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
-                                              recs.ctypes.data, plan.n_recs, codes.ctypes.data, ei.ctypes.data, ev.ctypes.data, cap,
-                                              ctypes.byref(n_exc), res.ctypes.data)
+        need = 0
+        # more non-ACGT bases than the guess: the call reports how many and copies none, so the whole decode runs again
+        # once with room for all of them (a second full decode, not a fetch: rare, batches of over 4 N per read)
+        for _ in range(2):
+            cap = max(1024, plan.n_recs * 4, need)
+            ei = np.zeros(cap, dtype=np.uint64); ev = np.zeros(cap, dtype=np.uint8)
+            rc = lib().cbc_gpu_decode_blocks_2bit(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
+                                                  recs.ctypes.data, plan.n_recs, codes.ctypes.data, ei.ctypes.data, ev.ctypes.data, cap,
+                                                  ctypes.byref(n_exc), res.ctypes.data)
+            need = int(n_exc.value)
+            if not (rc == -1 and need > cap):
+                break
         if rc != 0 and rc != -4:
             self._check(rc, "cbc_gpu_decode_blocks_2bit")
         lut = np.frombuffer(b"ACGT", dtype=np.uint8)
