@@ -219,3 +219,72 @@ int cbc_cli_decompress_region(const char *in, const char *out, const char *ref, 
     cbc_unpack_plan_free(u);
     return 0;
 }
+
+/* `cbc -d|-x ... --sam [--region NAME[:BEG[-END]]]`: the same reads as without --sam, as SAM: the
+ * header from the container's contig table (host), one alignment line per read assembled on the device
+ * (cbc_gpu_decode_sam); only the text crosses PCIe. */
+int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int verbose)
+{
+    const double t0 = now2();
+    size_t blob_len = 0, fa_len = 0;
+    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
+    if (!blob || !fa) return 1;
+    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
+        fprintf(stderr, "cbc: --sam needs a block container; %s is a single-stream (--compat) file, which stores no contig table\n", in);
+        return 1;
+    }
+    char err[512];
+    cbc_unpack_plan *u = NULL;
+    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
+    free(fa);
+    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
+    const int64_t hdr = cbc_unpack_sam_header(u, NULL, 0, err, sizeof err);
+    if (hdr < 0) { fprintf(stderr, "cbc: %s\n", hdr == CBC_E_INPUT ? err : "SAM header failed"); return 1; }
+    cbc_region_sel sel;
+    memset(&sel, 0, sizeof sel);
+    sel.b1 = u->n_blocks;
+    if (region) {
+        rc = cbc_unpack_region(u, region, &sel, err, sizeof err);
+        if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT ? err : "region selection failed"); return 1; }
+    }
+    const uint32_t nb = sel.b1 - sel.b0;
+    const uint64_t cap = cbc_unpack_sam_text_cap(u, sel.b0, sel.b1);
+    char *text = (char *)malloc((size_t)hdr + (size_t)cap + 1);
+    if (!text || cbc_unpack_sam_header(u, text, (uint64_t)hdr, err, sizeof err) != hdr) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    const double t1 = now2();
+    double t2 = t1, t3 = t1;
+    uint64_t text_bytes = 0, n_reads = 0;
+    float ms_dec = 0, ms_count = 0, ms_text = 0;
+    if (nb) {                                            /* no block to decode: the header alone, no device needed */
+        cbc_gpu_ctx *ctx = NULL;
+        rc = cbc_gpu_init(device, &ctx);
+        if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
+        if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+        t2 = now2();
+        cbc_sam_region rg = { sel.beg, sel.end, sel.smax, 0 };
+        rc = cbc_gpu_decode_sam(ctx, u->payloads, u->payload_bytes, u->blocks + sel.b0, nb, &u->caps, u->window_start + sel.b0,
+                                u->block_contig + sel.b0, u->names, u->names_bytes, u->contig_name_off, u->n_contigs,
+                                region ? &rg : NULL, (uint8_t *)text + hdr, cap, &text_bytes, &n_reads, NULL);
+        if (rc) { fprintf(stderr, "cbc: SAM decode failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+        t3 = now2();
+        if (verbose) (void)cbc_gpu_last_sam_ms(ctx, &ms_dec, &ms_count, &ms_text);
+        cbc_gpu_shutdown(ctx);
+    }
+    const size_t total = (size_t)hdr + (size_t)text_bytes;
+    FILE *fo = fopen(out, "wb");
+    if (!fo || fwrite(text, 1, total, fo) != total || fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    if (region)
+        printf("%llu reads in %s:%llu-%llu written as SAM from %u of %u blocks\n", (unsigned long long)n_reads,
+               u->names + u->contig_name_off[sel.contig], (unsigned long long)sel.beg, (unsigned long long)sel.end, nb, u->n_blocks);
+    else printf("%llu reads written as SAM from %u blocks\n", (unsigned long long)n_reads, u->n_blocks);
+    if (verbose) {
+        printf("sam: blocks [%u, %u) of %u, %llu reads, %lld header bytes, %llu text bytes\n", sel.b0, sel.b1, u->n_blocks,
+               (unsigned long long)n_reads, (long long)hdr, (unsigned long long)text_bytes);
+        printf("time: read + plan + header %.3f s, device init + reference upload %.3f s, decode + count + text %.3f s, write %.3f s\n",
+               t1 - t0, t2 - t1, t3 - t2, now2() - t3);
+        if (nb) printf("kernels: decode %.3f ms, count + scan %.3f ms, text %.3f ms\n", ms_dec, ms_count, ms_text);
+    }
+    free(text); free(blob);
+    cbc_unpack_plan_free(u);
+    return 0;
+}

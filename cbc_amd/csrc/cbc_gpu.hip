@@ -20,6 +20,7 @@
 #include "cbc_encode_body.h"
 #include "cbc_decode_body.h"
 #include "cbc_region_body.h"
+#include "cbc_sam_body.h"
 #include "cbc_plan.h"
 #include "cbc_stream_body.h"
 #include "cbc_long_body.h"
@@ -87,6 +88,19 @@ cbc_region_write_kernel(cbc_region_args A)
 {
     if (blockIdx.x >= A.n_blocks) return;
     cbc_region_write<WaveGPU>(A, blockIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), CBC_REGION_WAVES);
+}
+
+/* SAM output (cbc_gpu_decode_sam, cbc_sam_body.h): line lengths per block (one wavefront per block), then the lines
+ * (CBC_SAM_WAVES wavefronts per block, a line per wavefront at a time) */
+__global__ void __launch_bounds__(64)
+cbc_sam_count_kernel(cbc_sam_args A) { if (blockIdx.x < A.R.n_blocks) cbc_sam_count<WaveGPU>(A, blockIdx.x); }
+
+#define CBC_SAM_WAVES 4u
+__global__ void __launch_bounds__(64 * CBC_SAM_WAVES)
+cbc_sam_write_kernel(cbc_sam_args A)
+{
+    if (blockIdx.x >= A.R.n_blocks) return;
+    cbc_sam_write<WaveGPU>(A, blockIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), CBC_SAM_WAVES);
 }
 
 /* Whole-file stream / general-form fallback (cbc_stream_body.h): one wavefront per stream.  Workgroup w codes streams
@@ -244,7 +258,7 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
 /* grow-only device buffer owned by the context: the host-buffer entry points keep their device arrays between calls
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
-enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_COUNT };
+enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_COUNT };
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
 struct cbc_gpu_ctx {
@@ -256,6 +270,7 @@ struct cbc_gpu_ctx {
     hipEvent_t ev_chunk[CBC_MAX_CHUNKS], ev_done[CBC_N_KSTREAMS];
     hipEvent_t ev_rg[4];           /* region decode: before and after the decode, after the filter + scan, after the text kernel */
     int have_region_timing;
+    int have_sam_timing;           /* the same four events, recorded by cbc_gpu_decode_sam */
     int have_timing;
     int last_variant;              /* waves per SIMD of the encode build launched last */
     int n_cus;                     /* compute units of the device (block residency decides the kernel build) */
@@ -923,6 +938,8 @@ API int cbc_gpu_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device_batc
 struct region_req {
     const uint64_t *window_start; uint64_t beg, end; uint32_t smax;
     uint8_t *text; uint64_t text_cap; uint64_t *text_bytes, *n_selected;
+    /* SAM output (cbc_gpu_decode_sam): block_name != NULL; `region` = keep by [beg, end] (else every read, smax = 0) */
+    const uint32_t *block_name; const uint8_t *names; uint32_t names_bytes; int region;
 };
 
 /* The host-buffer decode path as a pipeline, mirror of encode_blocks_impl: the payloads (2 bytes per read) go H2D at once;
@@ -941,7 +958,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     const double T0 = wall_now();
     cbc_e2e_times tm; memset(&tm, 0, sizeof tm);
-    const bool two_bit = codes_out != NULL, text = rg && rg->text_bytes;
+    const bool two_bit = codes_out != NULL, text = rg && rg->text_bytes, sam = text && rg->block_name;
     const uint32_t stride = blocks[0].seq_stride;
     cbc_block_result *res = NULL;
     int rc = CBC_OK;
@@ -967,6 +984,10 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         NEED(A_RCNT, (uint64_t)n_blocks * sizeof(cbc_block_result), "hipMalloc region counts");
         NEED(A_OFF, ((uint64_t)n_blocks + 1) * 8, "hipMalloc region offsets");
     }
+    if (sam) {
+        NEED(A_SNAMES, (uint64_t)rg->names_bytes + 16, "hipMalloc contig names");
+        NEED(A_SBN, (uint64_t)n_blocks * 8, "hipMalloc block names");
+    }
     tm.alloc_s = wall_now() - T0;
     {
         uint8_t *d_in = (uint8_t *)ctx->arena[A_IN].p, *d_seq = (uint8_t *)ctx->arena[A_SEQ].p;
@@ -980,6 +1001,10 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         GO(hipMemsetAsync(d_res, 0xff, (uint64_t)n_blocks * sizeof(cbc_block_result), sc), "memset results");
         if (two_bit) GO(hipMemsetAsync(ctx->arena[A_CNT].p, 0, 8, sc), "memset counter");
         if (text) GO(hipMemcpyAsync(ctx->arena[A_RWS].p, rg->window_start, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D window starts");
+        if (sam) {
+            GO(hipMemcpyAsync(ctx->arena[A_SNAMES].p, rg->names, rg->names_bytes, hipMemcpyHostToDevice, sc), "H2D contig names");
+            GO(hipMemcpyAsync(ctx->arena[A_SBN].p, rg->block_name, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D block names");
+        }
         GO(hipEventRecord(ctx->ev_done[0], sc), "hipEventRecord");       /* inputs are on the device */
         tm.h2d_bytes = in_bytes + (uint64_t)n_blocks * sizeof(cbc_dec_block_desc);
         cbc_chunk_plan P;
@@ -1014,6 +1039,21 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 ra.dec_results = d_res; ra.counts = (cbc_block_result *)ctx->arena[A_RCNT].p; ra.offsets = (const uint64_t *)ctx->arena[A_OFF].p;
                 ra.text = (uint8_t *)ctx->arena[A_TEXT].p; ra.text_cap = rg->text_cap; ra.n_recs = n_recs; ra.seq_bytes = seq_bytes + 32;
                 ra.beg = rg->beg; ra.end = rg->end; ra.n_blocks = n_blocks;
+                if (sam) {                                     /* the same three steps with the SAM bodies */
+                    cbc_sam_args sa;
+                    memset(&sa, 0, sizeof sa);
+                    sa.R = ra; sa.block_name = (const uint32_t *)ctx->arena[A_SBN].p; sa.names = (const uint8_t *)ctx->arena[A_SNAMES].p;
+                    sa.names_bytes = rg->names_bytes; sa.region = rg->region ? 1u : 0u;
+                    hipLaunchKernelGGL(cbc_sam_count_kernel, dim3(n_blocks), dim3(64), 0, ks, sa);
+                    GO(hipGetLastError(), "launch cbc_sam_count_kernel");
+                    hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_blocks);
+                    GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+                    GO(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+                    hipLaunchKernelGGL(cbc_sam_write_kernel, dim3(n_blocks), dim3(64 * CBC_SAM_WAVES), 0, ks, sa);
+                    GO(hipGetLastError(), "launch cbc_sam_write_kernel");
+                    GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+                    ctx->have_sam_timing = 1; ctx->have_region_timing = 0;
+                } else {
                 hipLaunchKernelGGL(cbc_region_count_kernel, dim3(n_blocks), dim3(64), 0, ks, ra);
                 GO(hipGetLastError(), "launch cbc_region_count_kernel");
                 hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_blocks);
@@ -1022,7 +1062,8 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 hipLaunchKernelGGL(cbc_region_write_kernel, dim3(n_blocks), dim3(64 * CBC_REGION_WAVES), 0, ks, ra);
                 GO(hipGetLastError(), "launch cbc_region_write_kernel");
                 GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                ctx->have_region_timing = 1;
+                ctx->have_region_timing = 1; ctx->have_sam_timing = 0;
+                }
             }
             if (two_bit && k.r1 > k.r0) {
                 const uint64_t w0 = k.r0 * (stride >> 4), w1 = k.r1 * (stride >> 4);
@@ -1064,7 +1105,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         if (text) {
             for (uint32_t b = 0; b < n_blocks; b++) kept += cnt[b].n_symbols;
             *rg->text_bytes = total; *rg->n_selected = kept;
-            if (total > rg->text_cap) { rc = set_err(ctx, CBC_E_ARG, "text_cap too small for the region's text", hipSuccess); goto done; }
+            if (total > rg->text_cap) { rc = set_err(ctx, CBC_E_ARG, sam ? "text_cap too small for the SAM text" : "text_cap too small for the region's text", hipSuccess); goto done; }
             if (total) {                                       /* the one copy of the output: exactly its size */
                 GO(hipMemcpyAsync(rg->text, ctx->arena[A_TEXT].p, total, hipMemcpyDeviceToHost, sc), "D2H region text");
                 GO(hipStreamSynchronize(sc), "D2H region text");
@@ -1131,7 +1172,7 @@ API int cbc_gpu_decode_region(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         nrec += bl[b].n_reads;
     }
     const uint64_t need = nrec * (stride + 1ull);               /* every read kept: rl + 1 <= stride + 1 bytes each */
-    region_req rg = { window_start, beg, end, smax, text, text_cap < need ? text_cap : need, text_bytes, n_selected };
+    region_req rg = { window_start, beg, end, smax, text, text_cap < need ? text_cap : need, text_bytes, n_selected, NULL, NULL, 0, 0 };
     int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
                                 nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
     free(bl);
@@ -1147,6 +1188,67 @@ API int cbc_gpu_decode_blocks_span(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t
     memset(&rg, 0, sizeof rg);
     rg.smax = smax;
     return decode_blocks_impl(ctx, in, in_bytes, blocks, n_blocks, caps, recs, n_recs, seq, seq_bytes, NULL, NULL, NULL, 0, NULL, results, &rg);
+}
+
+/* SAM output: the blocks laid out afresh as for a region decode, the per-block name table made and checked on the host,
+ * then decode + count + scan + write on the device (cbc_sam_body.h) */
+API int cbc_gpu_decode_sam(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                           uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                           const uint32_t *block_contig, const char *names, uint32_t names_bytes,
+                           const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_sam_region *region,
+                           uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_reads, cbc_block_result *results)
+{
+    if (!ctx || !blocks || !caps || !window_start || !block_contig || !names || !contig_name_off || !text_bytes || !n_reads ||
+        (text_cap && !text)) return CBC_E_ARG;
+    *text_bytes = 0; *n_reads = 0;
+    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (n_blocks == 0) return CBC_OK;
+    if (!in) return CBC_E_ARG;
+    if (region && (region->smax == 0 || region->beg < 1 || region->beg > region->end))
+        return set_err(ctx, CBC_E_ARG, "SAM region decode wants 1 <= beg <= end and smax > 0", hipSuccess);
+    const uint32_t stride = blocks[0].seq_stride;
+    if (stride < 4 || stride > 256 || (stride & 3u)) return set_err(ctx, CBC_E_ARG, "SAM decode wants seq_stride in 4..256, a multiple of 4", hipSuccess);
+    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)n_blocks * sizeof(cbc_dec_block_desc));
+    uint32_t *bn = (uint32_t *)malloc((size_t)n_blocks * 8);
+    if (!bl || !bn) { free(bl); free(bn); return CBC_E_NOMEM; }
+    uint64_t in0 = UINT64_MAX, in1 = 0, nrec = 0, need = 0;
+    const char *bad = NULL;
+    for (uint32_t b = 0; b < n_blocks && !bad; b++) {          /* no sums of caller values that could wrap */
+        const cbc_dec_block_desc *d = &blocks[b];
+        if (d->seq_stride != stride || d->in_off > in_bytes || d->in_bytes > in_bytes - d->in_off || d->n_reads > CBC_MAX_BLOCK_READS) {
+            bad = "SAM decode: block out of range of `in`, or strides differ"; break; }
+        if (block_contig[b] >= n_contigs || contig_name_off[block_contig[b]] >= names_bytes) { bad = "SAM decode: a block's contig or its name lies outside the tables"; break; }
+        const uint32_t off = contig_name_off[block_contig[b]];
+        const size_t nl = strnlen(names + off, names_bytes - off);
+        if (nl == names_bytes - off || nl < 1 || nl > CBC_SAM_MAX_NAME || memchr(names + off, '\t', nl) || memchr(names + off, '\n', nl)) {
+            bad = "SAM decode: a contig name is empty, unterminated, longer than 255 bytes or holds a tab or a newline"; break; }
+        if (window_start[b] > CBC_SAM_MAX_POS) { bad = "SAM decode: a block starts past POS 2^31 - 1"; break; }
+        bn[2 * b] = off; bn[2 * b + 1] = (uint32_t)nl;
+        if (d->in_off < in0) in0 = d->in_off;
+        if (d->in_off + d->in_bytes > in1) in1 = d->in_off + d->in_bytes;
+        bl[b] = *d;
+        bl[b].rec_base = nrec; bl[b].seq_base = nrec * stride;
+        nrec += d->n_reads;
+        need += (uint64_t)d->n_reads * (35ull + nl + stride);   /* every read kept, every field at its longest */
+    }
+    if (bad) { free(bl); free(bn); return set_err(ctx, CBC_E_ARG, bad, hipSuccess); }
+    for (uint32_t b = 0; b < n_blocks; b++) bl[b].in_off -= in0;
+    region_req rg = { window_start, region ? region->beg : 1u, region ? region->end : UINT64_MAX, region ? region->smax : 0u, text,
+                      text_cap < need ? text_cap : need, text_bytes, n_reads, bn, (const uint8_t *)names, names_bytes, region != NULL };
+    int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
+                                nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
+    free(bl); free(bn);
+    return rc;
+}
+
+API int cbc_gpu_last_sam_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *count_ms, float *text_ms)
+{
+    if (!ctx || !decode_ms || !count_ms || !text_ms || !ctx->have_sam_timing) return CBC_E_ARG;
+    HIPCHK(hipEventSynchronize(ctx->ev_rg[3]), "hipEventSynchronize");
+    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(count_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(text_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
+    return CBC_OK;
 }
 
 API int cbc_gpu_last_region_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *text_ms)

@@ -41,6 +41,9 @@ static void usage(const char *p)
             "       %s -d|-x <in.cbc> <out.txt> <ref.fa>    reconstruct the reads, one per line\n"
             "         --region NAME[:BEG[-END]] (decode only the reads overlapping a locus, 1-based inclusive as in samtools;\n"
             "                                    block containers of short reads, one device)\n"
+            "         --sam (write SAM instead of bare reads: @HD, one @SQ per contig, then per read FLAG, RNAME, POS and SEQ;\n"
+            "                QNAME, MAPQ, CIGAR, mate fields and QUAL are not stored and come out as * 255 * * 0 0 *; the text is\n"
+            "                assembled on the device; alone or with --region; block containers of short reads, one device)\n"
             "options: -l (header read length = longest read)  --block-reads N (default 4096)  --device N (default 0)\n"
             "         --threads N (SAM parser threads, default one per CPU)  --verbose (stage times)\n"
             "         --compat (write the reference's own single-stream format; slow: one stream = one wavefront)\n"
@@ -418,6 +421,7 @@ static int do_compress(const char *in, const char *out, const char *ref, uint32_
 
 int cbc_cli_decompress(const char *in, const char *out, const char *ref, const int *devs, int ndev);   /* cbc_cli_unpack.c */
 int cbc_cli_decompress_region(const char *in, const char *out, const char *ref, int device, const char *region, int verbose);
+int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int verbose);
 
 int main(int argc, char **argv)
 {
@@ -426,6 +430,7 @@ int main(int argc, char **argv)
     int devs[CBC_MAX_DEVICES] = { 0 }, ndev = 0;
     uint32_t block_reads = 0;
     const char *region = NULL;
+    int sam_out = 0;
     g_main_t0 = now_s();
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
@@ -445,6 +450,7 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--threads") && i + 1 < argc) { threads = atoi(argv[++i]); if (threads < 0) threads = 0; continue; }
         if (!strcmp(a, "--verbose")) { verbose = 1; continue; }
         if (!strcmp(a, "--region") && i + 1 < argc) { region = argv[++i]; continue; }
+        if (!strcmp(a, "--sam")) { sam_out = 1; continue; }
         if (!strcmp(a, "--compat")) { compat = 1; continue; }
         if (!strcmp(a, "--long")) { long_reads = 1; continue; }
         if (!strcmp(a, "--device-parse")) { device_parse = 1; continue; }
@@ -485,6 +491,9 @@ int main(int argc, char **argv)
     }
     if (region && mode != 2) { fprintf(stderr, "cbc: --region applies to decompression (-d / -x)\n"); return 1; }
     if (region && ndev > 1) { fprintf(stderr, "cbc: --region decodes on one device; give a single --devices ordinal\n"); return 1; }
+    if (sam_out && mode != 2) { fprintf(stderr, "cbc: --sam applies to decompression (-d / -x)\n"); return 1; }
+    if (sam_out && ndev > 1) { fprintf(stderr, "cbc: --sam decodes on one device; give a single --devices ordinal\n"); return 1; }
+    if (sam_out) return cbc_cli_decompress_sam(files[0], files[1], files[2], device, region, verbose);
     if (region) return cbc_cli_decompress_region(files[0], files[1], files[2], device, region, verbose);
     if (ndev == 0) { devs[0] = device; ndev = 1; }
     return mode == 1 ? do_compress(files[0], files[1], files[2], block_reads, device, var_length, threads, verbose, compat, devs, ndev, long_reads, device_parse, want_rccl)

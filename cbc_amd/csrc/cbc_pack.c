@@ -1840,6 +1840,61 @@ API int cbc_unpack_region(const cbc_unpack_plan *u, const char *region, cbc_regi
     return 0;
 }
 
+/* ---- SAM output (include/cbc_host.h): the header, and the size of the records' text ---- */
+/* length of contig c's name, checked as region_contig checks it; -1: offset outside the table or no NUL */
+static int64_t sam_name_len(const cbc_unpack_plan *u, uint32_t c)
+{
+    const uint32_t off = u->contig_name_off[c];
+    if (off >= u->names_bytes) return -1;
+    const size_t len = strnlen(u->names + off, u->names_bytes - off);
+    return len == u->names_bytes - off ? -1 : (int64_t)len;
+}
+
+API int64_t cbc_unpack_sam_header(const cbc_unpack_plan *u, char *dst, uint64_t cap, char *errbuf, size_t errlen)
+{
+    if (!u) return CBC_E_ARG;
+    if (errbuf && errlen) errbuf[0] = 0;
+    if (u->long_reads)
+        return region_err(errbuf, errlen, "SAM output of a long-read (version 3) container is not supported%.*s", "", 0);
+    if (!u->names || !u->contig_name_off || !u->contig_len) return CBC_E_ARG;
+    static const char hd[] = "@HD\tVN:1.6\tSO:coordinate\n";
+    uint64_t n = sizeof hd - 1;
+    if (dst) { if (n > cap) return CBC_E_ARG; memcpy(dst, hd, (size_t)n); }
+    for (uint32_t c = 0; c < u->n_contigs; c++) {
+        const int64_t nl = sam_name_len(u, c);
+        if (nl < 0) return region_err(errbuf, errlen, "corrupt container: a contig name lies outside the name table%.*s", "", 0);
+        const char *nm = u->names + u->contig_name_off[c];
+        if (nl < 1 || nl > (int64_t)CBC_SAM_MAX_NAME)
+            return region_err(errbuf, errlen, "SAM output: contig name \"%.*s\" is empty or longer than 255 bytes", nm, nl > 60 ? 60 : (int)nl);
+        if (memchr(nm, '\t', (size_t)nl) || memchr(nm, '\n', (size_t)nl))
+            return region_err(errbuf, errlen, "SAM output: contig name \"%.*s\" holds a tab or a newline", nm, nl > 60 ? 60 : (int)nl);
+        if (u->contig_len[c] > CBC_SAM_MAX_POS)
+            return region_err(errbuf, errlen, "SAM output: contig \"%.*s\" is longer than 2^31 - 1 bases, the largest POS of SAM", nm, nl > 60 ? 60 : (int)nl);
+        char ln[64];
+        const int k = snprintf(ln, sizeof ln, "\tLN:%llu\n", (unsigned long long)u->contig_len[c]);
+        if (dst) {
+            if (7u + (uint64_t)nl + (uint64_t)k > cap - n) return CBC_E_ARG;
+            memcpy(dst + n, "@SQ\tSN:", 7); memcpy(dst + n + 7, nm, (size_t)nl); memcpy(dst + n + 7 + nl, ln, (size_t)k);
+        }
+        n += 7u + (uint64_t)nl + (uint64_t)k;
+    }
+    return (int64_t)n;
+}
+
+/* bytes that always hold the alignment lines of blocks [b0, b1): every read kept, FLAG 5 and POS 10 digits, SEQ a full row */
+API uint64_t cbc_unpack_sam_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1)
+{
+    if (!u || u->long_reads || !u->block_contig || !u->names || !u->contig_name_off || b0 > b1 || b1 > u->n_blocks) return 0;
+    uint64_t n = 0;
+    for (uint32_t b = b0; b < b1; b++) {
+        const uint32_t c = u->block_contig[b];
+        const int64_t nl = c < u->n_contigs ? sam_name_len(u, c) : -1;
+        if (nl < 0) return 0;
+        n += (uint64_t)u->blocks[b].n_reads * (35ull + (uint64_t)nl + u->seq_stride);
+    }
+    return n;
+}
+
 /* One reconstructed read per line (print_line, src/compression.c:16-40). */
 API int64_t cbc_unpack_write_text(const cbc_unpack_plan *u, const cbc_read_rec *recs, const uint8_t *seq,
                                   char *dst, uint64_t cap)

@@ -76,6 +76,10 @@ class E2ETimes(ctypes.Structure):
                 ("h2d_bytes", ctypes.c_uint64), ("d2h_bytes", ctypes.c_uint64), ("n_chunks", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class SamRegion(ctypes.Structure):
+    _fields_ = [("beg", ctypes.c_uint64), ("end", ctypes.c_uint64), ("smax", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class CbcGpuError(RuntimeError):
     pass
 
@@ -210,6 +214,14 @@ def lib():
         L.cbc_gpu_last_region_ms.restype = ctypes.c_int
         L.cbc_gpu_last_region_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                              ctypes.POINTER(ctypes.c_float)]
+        L.cbc_gpu_decode_sam.restype = ctypes.c_int
+        L.cbc_gpu_decode_sam.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                         ctypes.POINTER(host.LdsCaps), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(SamRegion),
+                                         ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                         ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.cbc_gpu_last_sam_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_sam_ms.argtypes = L.cbc_gpu_last_region_ms.argtypes
         if L.cbc_gpu_abi_version() != 1:
             raise CbcGpuError("libcbc_gpu.so ABI version mismatch")
         _lib = L
@@ -229,7 +241,7 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_host_unregister", "cbc_gpu_plan_output_caps", "cbc_gpu_reserve_encode",
            "cbc_gpu_decode_stream_blocks", "cbc_gpu_group_create", "cbc_gpu_group_gather", "cbc_gpu_group_destroy", "cbc_gpu_group_last_error",
            "cbc_gpu_stash_reset", "cbc_gpu_stash_bytes", "cbc_gpu_stash_fetch", "cbc_gpu_decode_region",
-           "cbc_gpu_decode_blocks_span", "cbc_gpu_last_region_ms"]
+           "cbc_gpu_decode_blocks_span", "cbc_gpu_last_region_ms", "cbc_gpu_decode_sam", "cbc_gpu_last_sam_ms"]
 
 
 class Encoder:
@@ -438,6 +450,46 @@ class Encoder:
             self._check(rc, "cbc_gpu_decode_region")
         out = text[:int(nbytes.value)].tobytes()
         return (out, int(nsel.value), sel, res[:nb]) if results else out
+
+    def decode_sam(self, plan: "host.UnpackPlan", region=None, results=False, text_cap=None):
+        """The reads of the container, or with `region` (NAME, NAME:BEG or NAME:BEG-END) the reads decode_region selects, as
+        SAM text: plan.sam_header() + one alignment line per read, assembled on the device (cbc_gpu_decode_sam).  The
+        reference must have been uploaded (upload_reference(plan.ref)).  An empty selection gives the header alone and runs
+        nothing on the device.  With results=True returns (text, n_reads, selection or None, per-block decode results).
+        text_cap: size of the buffer for the lines (default: plan.sam_text_cap of the blocks)."""
+        hdr = plan.sam_header()
+        sel = plan.region(region) if region is not None else None
+        b0, b1 = (sel.b0, sel.b1) if sel is not None else (0, plan.n_blocks)
+        nb = b1 - b0
+        res = np.zeros(max(nb, 1), dtype=host.RESULT_DTYPE)
+        if nb == 0:
+            return (hdr, 0, sel, res[:0]) if results else hdr
+        blocks = np.ascontiguousarray(plan.blocks[b0:b1])
+        ws = np.ascontiguousarray(plan.window_start[b0:b1], dtype=np.uint64)
+        bc = np.ascontiguousarray(plan.block_contig[b0:b1], dtype=np.uint32)
+        names = np.ascontiguousarray(plan.names)
+        noff = np.ascontiguousarray(plan.contig_name_off, dtype=np.uint32)
+        cap = plan.sam_text_cap(b0, b1) if text_cap is None else int(text_cap)
+        text = np.zeros(max(cap, 1), dtype=np.uint8)
+        nbytes, nrd = ctypes.c_uint64(), ctypes.c_uint64()
+        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
+        pay = np.ascontiguousarray(plan.payloads)
+        rg = SamRegion(sel.beg, sel.end, sel.smax, 0) if sel is not None else None
+        rc = lib().cbc_gpu_decode_sam(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps), ws.ctypes.data,
+                                      bc.ctypes.data, names.ctypes.data, names.size, noff.ctypes.data, plan.n_contigs,
+                                      ctypes.byref(rg) if rg is not None else None, text.ctypes.data, cap,
+                                      ctypes.byref(nbytes), ctypes.byref(nrd), res.ctypes.data)
+        self.last_sam_text_bytes = int(nbytes.value)
+        if rc != 0 and not (results and rc == -4):
+            self._check(rc, "cbc_gpu_decode_sam")
+        out = hdr + text[:int(nbytes.value)].tobytes()
+        return (out, int(nrd.value), sel, res[:nb]) if results else out
+
+    def last_sam_ms(self):
+        """(decode, count + scan, text) kernel milliseconds of the last decode_sam."""
+        a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        self._check(lib().cbc_gpu_last_sam_ms(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "cbc_gpu_last_sam_ms")
+        return float(a.value), float(b.value), float(c.value)
 
     def last_region_ms(self):
         """(decode, filter + scan, text) kernel milliseconds of the last decode_region."""

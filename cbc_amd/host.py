@@ -179,6 +179,10 @@ def lib():
         L.cbc_unpack_write_text.restype = ctypes.c_int64
         L.cbc_unpack_write_text.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_uint64]
+        L.cbc_unpack_sam_header.restype = ctypes.c_int64
+        L.cbc_unpack_sam_header.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_size_t]
+        L.cbc_unpack_sam_text_cap.restype = ctypes.c_uint64
+        L.cbc_unpack_sam_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32]
         _lib = L
     return _lib
 
@@ -448,6 +452,12 @@ class UnpackPlan:
         self.long_reads = bool(p.long_reads)
         self.max_read_len = int(p.max_read_len)
         self.seq_total = int(p.seq_total)
+        # the container's contig table (SAM output: @SQ lines, RNAME)
+        self.n_contigs = int(p.n_contigs)
+        self.block_contig = _np_view(p.block_contig, p.n_blocks, np.uint32)
+        self.contig_name_off = _np_view(p.contig_name_off, p.n_contigs, np.uint32)
+        self.contig_len = _np_view(p.contig_len, p.n_contigs, np.uint64)
+        self.names = np.frombuffer((ctypes.c_uint8 * (int(p.names_bytes) + 1)).from_address(p.names), dtype=np.uint8)[:int(p.names_bytes)]
 
     def region(self, region):
         """Blocks that can hold a read overlapping `region` (NAME, NAME:BEG or NAME:BEG-END, 1-based inclusive):
@@ -463,6 +473,24 @@ class UnpackPlan:
         return RegionSelection(int(sel.contig), int(sel.b0), int(sel.b1), int(sel.beg), int(sel.end), int(sel.smax),
                                int(sel.contig_len))
 
+    def sam_header(self) -> bytes:
+        """@HD and one @SQ line per contig of the container's table (cbc_unpack_sam_header): what precedes the alignment
+        lines of Encoder.decode_sam.  Raises CbcInputError for what SAM cannot carry: a long-read container, a contig longer
+        than 2^31 - 1 bases, a name that is empty, longer than 255 bytes or holds a tab or a newline."""
+        err = ctypes.create_string_buffer(512)
+        n = lib().cbc_unpack_sam_header(self._ptr, None, 0, err, 512)
+        if n < 0:
+            raise CbcInputError("cbc_unpack_sam_header failed (%d): %s" % (n, err.value.decode(errors="replace")))
+        dst = np.zeros(int(n), dtype=np.uint8)
+        w = lib().cbc_unpack_sam_header(self._ptr, dst.ctypes.data, int(n), err, 512)
+        if w != n:
+            raise RuntimeError("cbc_unpack_sam_header failed: %d" % w)
+        return dst.tobytes()
+
+    def sam_text_cap(self, b0=0, b1=None) -> int:
+        """Bytes that always hold the alignment lines of blocks [b0, b1) (cbc_unpack_sam_text_cap)."""
+        return int(lib().cbc_unpack_sam_text_cap(self._ptr, b0, self.n_blocks if b1 is None else b1))
+
     def text(self, recs: np.ndarray, seq: np.ndarray) -> bytes:
         """One reconstructed read per line (what `cbc -d` writes)."""
         cap = (int(self.seq_total) + int(self.n_recs) + 16) if self.long_reads else int(self.n_recs) * (self.seq_stride + 1) + 16
@@ -476,7 +504,7 @@ class UnpackPlan:
 
     def close(self):
         if self._ptr is not None:
-            for k in ("blocks", "payloads", "ref", "window_start"):
+            for k in ("blocks", "payloads", "ref", "window_start", "block_contig", "contig_name_off", "contig_len", "names"):
                 setattr(self, k, None)
             lib().cbc_unpack_plan_free(self._ptr)
             self._ptr = None

@@ -304,6 +304,33 @@ int  cbc_gpu_decode_blocks_span(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in
  * (count pass + block scan) and the text assembly. */
 int  cbc_gpu_last_region_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *text_ms);
 
+/* ---- SAM output of a decode ---------------------------------------------------------------------
+ * Decode `blocks` and write one SAM alignment line per read, text assembled on the device, in container order:
+ *     *\t<FLAG>\t<RNAME>\t<POS>\t255\t*\t*\t0\t0\t<SEQ>\t*\n
+ * FLAG = the decoded flag; RNAME = the name of the block's contig (names[contig_name_off[block_contig[b]]], NUL-terminated,
+ * at most CBC_SAM_MAX_NAME bytes, no tab or newline); POS = window_start[b] + the decoded block-local POS, at most
+ * CBC_SAM_MAX_POS; SEQ = the bases `cbc -x` writes for the read.  What the file does not store is spelled "not available".
+ * The records part only: the @HD / @SQ header is host text (cbc_unpack_sam_header, libcbc_host).
+ * region == NULL: every read of the blocks, decoded by the plain decoder.  Otherwise the blocks are a selection of
+ * cbc_unpack_region, decoded by the span-reporting decoder against region->smax (CBC_ST_SPAN), and the reads kept are those
+ * cbc_gpu_decode_region keeps for [beg, end].  A block that fails to decode contributes no line and the call returns
+ * CBC_E_BLOCK, as cbc_gpu_decode_region does.  blocks[].in_off index `in`; rec_base / seq_base are laid out by the library.
+ * *text_bytes = bytes of text (also when text_cap is too small: CBC_E_ARG, nothing copied), *n_reads = lines written.
+ * A line is 20 + digits(FLAG) + len(RNAME) + digits(POS) + rlen bytes: text_cap = sum over blocks of n_reads * (35 +
+ * len(RNAME) + seq_stride) always suffices (cbc_unpack_sam_text_cap). */
+#define CBC_SAM_MAX_NAME 255u
+#define CBC_SAM_MAX_POS  0x7fffffffu
+typedef struct cbc_sam_region { uint64_t beg, end; uint32_t smax, reserved; } cbc_sam_region;
+int  cbc_gpu_decode_sam(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                        uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                        const uint32_t *block_contig /* n_blocks */, const char *names, uint32_t names_bytes,
+                        const uint32_t *contig_name_off /* n_contigs */, uint32_t n_contigs,
+                        const cbc_sam_region *region /* or NULL */, uint8_t *text, uint64_t text_cap,
+                        uint64_t *text_bytes, uint64_t *n_reads, cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_sam (HIP events on its stream): the decode, the count pass + block scan,
+ * and the text assembly. */
+int  cbc_gpu_last_sam_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *count_ms, float *text_ms);
+
 /* ---- whole-file stream ("compat" mode): the reference's own file format --------------------------------------
  * compress() / decompress(), src/compression.c:112-216: ONE arithmetic stream per file, models never reset.
  * `batch` is a cbc_host_batch packed with cbc_pack_opts.whole_file = 1: its `blocks` are SEGMENTS of the one

@@ -205,6 +205,16 @@ typedef struct cbc_region_sel {
 } cbc_region_sel;
 int     cbc_unpack_region(const cbc_unpack_plan *u, const char *region, cbc_region_sel *sel, char *errbuf, size_t errlen);
 
+/* SAM output (the alignment lines come from cbc_gpu_decode_sam).  cbc_unpack_sam_header writes
+ *     @HD\tVN:1.6\tSO:coordinate\n   and one   @SQ\tSN:<name>\tLN:<length>\n   per contig of the container's table, in table order
+ * into dst (dst == NULL: only the size) and returns the bytes, CBC_E_ARG when cap is too small, or CBC_E_INPUT with a message:
+ * a long-read (version 3) container; a name offset outside the name table; a name that is empty, longer than
+ * CBC_SAM_MAX_NAME (255) bytes -- the limit the device path takes -- or holds a tab or a newline; a contig longer than
+ * 2^31 - 1 bases (CBC_SAM_MAX_POS: SAM has no larger POS).  cbc_unpack_sam_text_cap: a text_cap that always holds the lines of
+ * blocks [b0, b1) (0 for a plan the header function refuses or a bad range). */
+int64_t  cbc_unpack_sam_header(const cbc_unpack_plan *u, char *dst, uint64_t cap, char *errbuf, size_t errlen);
+uint64_t cbc_unpack_sam_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1);
+
 int     cbc_unpack_plan_create(const uint8_t *blob, uint64_t len, const char *fasta, size_t fasta_len,
                                cbc_unpack_plan **out, char *errbuf, size_t errlen);
 void    cbc_unpack_plan_free(cbc_unpack_plan *u);
