@@ -288,3 +288,90 @@ int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int
     cbc_unpack_plan_free(u);
     return 0;
 }
+
+/* `cbc -d|-x ... --depth [--region NAME[:BEG[-END]]]`: the coverage of the reads instead of the reads,
+ * bedGraph computed and formatted on the device (cbc_gpu_decode_depth): one call for the region's window, or one per contig
+ * that has blocks, in the order of the contig table, the texts appended.  Only the track crosses PCIe. */
+int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude, int verbose)
+{
+    const double t0 = now2();
+    size_t blob_len = 0, fa_len = 0;
+    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
+    if (!blob || !fa) return 1;
+    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
+        fprintf(stderr, "cbc: --depth needs a block container; %s is a single-stream (--compat) file, which stores no contig table\n", in);
+        return 1;
+    }
+    char err[512];
+    cbc_unpack_plan *u = NULL;
+    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
+    free(fa);
+    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
+    /* what SAM output refuses, depth refuses: a long-read container, names and lengths the text cannot carry */
+    if (cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) < 0) { fprintf(stderr, "cbc: --depth: %s\n", err[0] ? err : "the contig table is not usable"); return 1; }
+    /* the calls: the region's selection, or every contig as a whole */
+    const uint32_t n_calls = region ? 1u : u->n_contigs;
+    cbc_region_sel *sels = (cbc_region_sel *)calloc(n_calls ? n_calls : 1u, sizeof(cbc_region_sel));
+    if (!sels) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    uint64_t cap = 0, max_cap = 0;
+    for (uint32_t k = 0; k < n_calls; k++) {
+        rc = region ? cbc_unpack_region(u, region, &sels[k], err, sizeof err) : cbc_unpack_contig_blocks(u, k, &sels[k], err, sizeof err);
+        if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT ? err : "block selection failed"); return 1; }
+        const uint64_t c = cbc_unpack_depth_text_cap(u, sels[k].b0, sels[k].b1, sels[k].contig);
+        if (c > max_cap) max_cap = c;
+        cap += c;
+    }
+    (void)cap;
+    const double t1 = now2();
+    double t_init = 0, t_dev = 0;
+    FILE *fo = fopen(out, "wb");
+    if (!fo) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    char *text = (char *)malloc((size_t)max_cap + 1);
+    if (!text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    cbc_gpu_ctx *ctx = NULL;
+    uint64_t total = 0, runs = 0, kept = 0;
+    uint32_t blocks_used = 0;
+    float ms[4] = { 0, 0, 0, 0 };
+    for (uint32_t k = 0; k < n_calls; k++) {
+        const cbc_region_sel *s = &sels[k];
+        const uint32_t nb = s->b1 - s->b0;
+        if (!nb) continue;                              /* no block can hold a read of the window: no line, no device needed */
+        const double a = now2();
+        if (!ctx) {
+            rc = cbc_gpu_init(device, &ctx);
+            if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
+            if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+            t_init = now2() - a;
+        }
+        const double b = now2();
+        const char *nm = u->names + u->contig_name_off[s->contig];
+        uint64_t tb = 0, nr = 0, nk = 0;
+        rc = cbc_gpu_decode_depth(ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
+                                  nm, (uint32_t)strlen(nm), s->beg, s->end, s->smax, exclude, (uint8_t *)text,
+                                  cbc_unpack_depth_text_cap(u, s->b0, s->b1, s->contig), &tb, &nr, &nk, NULL);
+        if (rc) { fprintf(stderr, "cbc: depth failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+        t_dev += now2() - b;
+        if (verbose) {
+            float m4[4];
+            if (cbc_gpu_last_depth_ms(ctx, &m4[0], &m4[1], &m4[2], &m4[3]) == 0) for (int i = 0; i < 4; i++) ms[i] += m4[i];
+        }
+        if (tb && fwrite(text, 1, (size_t)tb, fo) != (size_t)tb) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+        total += tb; runs += nr; kept += nk; blocks_used += nb;
+    }
+    if (fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    if (ctx) cbc_gpu_shutdown(ctx);
+    if (region)
+        printf("depth of %s:%llu-%llu: %llu runs from %llu reads in %u of %u blocks\n", u->names + u->contig_name_off[sels[0].contig],
+               (unsigned long long)sels[0].beg, (unsigned long long)sels[0].end, (unsigned long long)runs, (unsigned long long)kept,
+               blocks_used, u->n_blocks);
+    else printf("depth: %llu runs from %llu reads in %u blocks\n", (unsigned long long)runs, (unsigned long long)kept, blocks_used);
+    if (verbose) {
+        printf("depth: %llu text bytes, exclude flags 0x%x\n", (unsigned long long)total, exclude);
+        printf("time: read + plan %.3f s, device init + reference upload %.3f s, decode + depth + write %.3f s\n", t1 - t0, t_init, t_dev);
+        if (ctx) printf("kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
+    }
+    free(text); free(sels); free(blob);
+    cbc_unpack_plan_free(u);
+    (void)t0;
+    return 0;
+}

@@ -21,6 +21,7 @@
 #include "cbc_decode_body.h"
 #include "cbc_region_body.h"
 #include "cbc_sam_body.h"
+#include "cbc_depth_body.h"
 #include "cbc_plan.h"
 #include "cbc_stream_body.h"
 #include "cbc_long_body.h"
@@ -102,6 +103,19 @@ cbc_sam_write_kernel(cbc_sam_args A)
     if (blockIdx.x >= A.R.n_blocks) return;
     cbc_sam_write<WaveGPU>(A, blockIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), CBC_SAM_WAVES);
 }
+
+/* Coverage (cbc_gpu_decode_depth, cbc_depth_body.h): one wavefront per block marks the reads in the difference array, one
+ * per tile sums it and (after the scans) writes the change points, one per CBC_DEPTH_LINES runs counts and writes the lines */
+__global__ void __launch_bounds__(64)
+cbc_depth_mark_kernel(cbc_depth_args A) { if (blockIdx.x < A.R.n_blocks) cbc_depth_mark<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_depth_tile_kernel(cbc_depth_args A) { cbc_depth_tile<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_depth_compact_kernel(cbc_depth_args A) { cbc_depth_compact<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_depth_count_kernel(cbc_depth_args A) { if (blockIdx.x < A.n_ttiles) cbc_depth_count<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_depth_write_kernel(cbc_depth_args A) { cbc_depth_write<WaveGPU>(A, blockIdx.x); }
 
 /* Whole-file stream / general-form fallback (cbc_stream_body.h): one wavefront per stream.  Workgroup w codes streams
  * w, w + gridDim, ... with var table w of the pool, which it re-zeroes between streams. */
@@ -258,7 +272,7 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
 /* grow-only device buffer owned by the context: the host-buffer entry points keep their device arrays between calls
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
-enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_COUNT };
+enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_COUNT };
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
 struct cbc_gpu_ctx {
@@ -268,9 +282,11 @@ struct cbc_gpu_ctx {
     hipStream_t s_k[CBC_N_KSTREAMS];   /* their kernel launches, chunk c on stream c % CBC_N_KSTREAMS */
     hipEvent_t ev0, ev1;
     hipEvent_t ev_chunk[CBC_MAX_CHUNKS], ev_done[CBC_N_KSTREAMS];
-    hipEvent_t ev_rg[4];           /* region decode: before and after the decode, after the filter + scan, after the text kernel */
+    hipEvent_t ev_rg[5];           /* region decode: before and after the decode, after the filter + scan, after the text kernel;
+                                    * coverage: decode, mark, scan + compact, text (the fifth event) */
     int have_region_timing;
     int have_sam_timing;           /* the same four events, recorded by cbc_gpu_decode_sam */
+    int have_depth_timing;         /* all five, recorded by cbc_gpu_decode_depth */
     int have_timing;
     int last_variant;              /* waves per SIMD of the encode build launched last */
     int n_cus;                     /* compute units of the device (block residency decides the kernel build) */
@@ -345,7 +361,7 @@ API int cbc_gpu_init(int device_ordinal, cbc_gpu_ctx **out)
             hipEventCreateWithFlags(&ctx->ev_done[k], hipEventDisableTiming) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     for (int k = 0; k < CBC_MAX_CHUNKS; k++)
         if (hipEventCreateWithFlags(&ctx->ev_chunk[k], hipEventDisableTiming) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
-    for (int k = 0; k < 4; k++)
+    for (int k = 0; k < 5; k++)
         if (hipEventCreate(&ctx->ev_rg[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     {
         int cus = 0;
@@ -374,7 +390,7 @@ API int cbc_gpu_shutdown(cbc_gpu_ctx *ctx)
     for (int k = 0; k < A_COUNT; k++) if (ctx->arena[k].p) (void)hipFree(ctx->arena[k].p);
     (void)hipEventDestroy(ctx->ev0); (void)hipEventDestroy(ctx->ev1);
     for (int k = 0; k < CBC_MAX_CHUNKS; k++) (void)hipEventDestroy(ctx->ev_chunk[k]);
-    for (int k = 0; k < 4; k++) (void)hipEventDestroy(ctx->ev_rg[k]);
+    for (int k = 0; k < 5; k++) (void)hipEventDestroy(ctx->ev_rg[k]);
     for (int k = 0; k < CBC_N_KSTREAMS; k++) { (void)hipEventDestroy(ctx->ev_done[k]); (void)hipStreamDestroy(ctx->s_k[k]); }
     (void)hipStreamDestroy(ctx->s_copy);
     (void)hipStreamDestroy(ctx->stream);
@@ -935,11 +951,14 @@ API int cbc_gpu_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device_batc
 
 /* region decode's part of decode_blocks_impl: the span bound, the region, where the text goes and what came of it
  * (text_bytes == NULL: the span decode alone, records and rows come back as in a plain decode) */
+struct depth_req { uint32_t exclude; uint64_t *n_runs; };
 struct region_req {
     const uint64_t *window_start; uint64_t beg, end; uint32_t smax;
     uint8_t *text; uint64_t text_cap; uint64_t *text_bytes, *n_selected;
     /* SAM output (cbc_gpu_decode_sam): block_name != NULL; `region` = keep by [beg, end] (else every read, smax = 0) */
     const uint32_t *block_name; const uint8_t *names; uint32_t names_bytes; int region;
+    /* coverage (cbc_gpu_decode_depth): depth != NULL; names / names_bytes = the one contig name, n_selected = reads kept */
+    const depth_req *depth;
 };
 
 /* The host-buffer decode path as a pipeline, mirror of encode_blocks_impl: the payloads (2 bytes per read) go H2D at once;
@@ -959,6 +978,14 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     const double T0 = wall_now();
     cbc_e2e_times tm; memset(&tm, 0, sizeof tm);
     const bool two_bit = codes_out != NULL, text = rg && rg->text_bytes, sam = text && rg->block_name;
+    const depth_req *depth = text ? rg->depth : NULL;
+    /* coverage: tiles of the difference array (W + 1 words), change points (two per read at most), text tiles of the runs */
+    const uint64_t d_words = depth ? rg->end - rg->beg + 2u : 0u;
+    const uint32_t n_tiles = (uint32_t)((d_words + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
+    const uint32_t cp_cap = depth ? (uint32_t)(2u * n_recs) : 0u;
+    const uint32_t n_ttiles = (cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
+    const uint32_t n_sized = depth ? n_ttiles : n_blocks;        /* entries the text's size scan runs over */
+    uint32_t dctr[4] = { 0, 0, 0, 0 };
     const uint32_t stride = blocks[0].seq_stride;
     cbc_block_result *res = NULL;
     int rc = CBC_OK;
@@ -981,8 +1008,20 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     if (text) {
         NEED(A_TEXT, rg->text_cap + 16, "hipMalloc region text");
         NEED(A_RWS, (uint64_t)n_blocks * 8, "hipMalloc window starts");
-        NEED(A_RCNT, (uint64_t)n_blocks * sizeof(cbc_block_result), "hipMalloc region counts");
-        NEED(A_OFF, ((uint64_t)n_blocks + 1) * 8, "hipMalloc region offsets");
+        NEED(A_RCNT, (uint64_t)n_sized * sizeof(cbc_block_result), "hipMalloc region counts");
+        NEED(A_OFF, ((uint64_t)n_sized + 1) * 8, "hipMalloc region offsets");
+    }
+    if (depth) {
+        if (arena_need(ctx, A_DDIFF, (uint64_t)n_tiles * CBC_DEPTH_TILE * 4, "hipMalloc depth window")) {
+            (void)hipGetLastError();
+            rc = set_err(ctx, CBC_E_NOMEM, "no device memory for the window's difference array (4 bytes per position)", hipSuccess);
+            goto done;
+        }
+        NEED(A_DTILE, (uint64_t)n_tiles * 2 * sizeof(cbc_block_result), "hipMalloc depth tiles");
+        NEED(A_DTOFF, ((uint64_t)n_tiles + 1) * 2 * 8, "hipMalloc depth tile offsets");
+        NEED(A_DCP, (uint64_t)cp_cap * 2 * 4 + 16, "hipMalloc depth change points");
+        NEED(A_DCTR, 16, "hipMalloc depth counters");
+        NEED(A_SNAMES, (uint64_t)rg->names_bytes + 16, "hipMalloc contig name");
     }
     if (sam) {
         NEED(A_SNAMES, (uint64_t)rg->names_bytes + 16, "hipMalloc contig names");
@@ -1001,6 +1040,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         GO(hipMemsetAsync(d_res, 0xff, (uint64_t)n_blocks * sizeof(cbc_block_result), sc), "memset results");
         if (two_bit) GO(hipMemsetAsync(ctx->arena[A_CNT].p, 0, 8, sc), "memset counter");
         if (text) GO(hipMemcpyAsync(ctx->arena[A_RWS].p, rg->window_start, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D window starts");
+        if (depth) GO(hipMemcpyAsync(ctx->arena[A_SNAMES].p, rg->names, rg->names_bytes, hipMemcpyHostToDevice, sc), "H2D contig name");
         if (sam) {
             GO(hipMemcpyAsync(ctx->arena[A_SNAMES].p, rg->names, rg->names_bytes, hipMemcpyHostToDevice, sc), "H2D contig names");
             GO(hipMemcpyAsync(ctx->arena[A_SBN].p, rg->block_name, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D block names");
@@ -1039,7 +1079,39 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 ra.dec_results = d_res; ra.counts = (cbc_block_result *)ctx->arena[A_RCNT].p; ra.offsets = (const uint64_t *)ctx->arena[A_OFF].p;
                 ra.text = (uint8_t *)ctx->arena[A_TEXT].p; ra.text_cap = rg->text_cap; ra.n_recs = n_recs; ra.seq_bytes = seq_bytes + 32;
                 ra.beg = rg->beg; ra.end = rg->end; ra.n_blocks = n_blocks;
-                if (sam) {                                     /* the same three steps with the SAM bodies */
+                if (depth) {                                   /* mark, tile sums + scans + change points, lines */
+                    cbc_depth_args da;
+                    memset(&da, 0, sizeof da);
+                    da.R = ra;
+                    da.diff = (uint32_t *)ctx->arena[A_DDIFF].p; da.diff_words = (uint64_t)n_tiles * CBC_DEPTH_TILE;
+                    da.tile_sum = (cbc_block_result *)ctx->arena[A_DTILE].p; da.tile_cnt = da.tile_sum + n_tiles;
+                    uint64_t *toff = (uint64_t *)ctx->arena[A_DTOFF].p;
+                    da.sum_off = toff; da.cnt_off = toff + n_tiles + 1;
+                    da.cp_pos = (uint32_t *)ctx->arena[A_DCP].p; da.cp_dep = da.cp_pos + cp_cap; da.cp_cap = cp_cap;
+                    da.ctr = (uint32_t *)ctx->arena[A_DCTR].p; da.name = (const uint8_t *)ctx->arena[A_SNAMES].p;
+                    da.name_len = rg->names_bytes; da.exclude = depth->exclude; da.n_tiles = n_tiles; da.n_ttiles = n_ttiles;
+                    GO(hipMemsetAsync(da.diff, 0, da.diff_words * 4, ks), "memset depth window");
+                    GO(hipMemsetAsync(da.ctr, 0, 16, ks), "memset depth counters");
+                    hipLaunchKernelGGL(cbc_depth_mark_kernel, dim3(n_blocks), dim3(64), 0, ks, da);
+                    GO(hipGetLastError(), "launch cbc_depth_mark_kernel");
+                    GO(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+                    hipLaunchKernelGGL(cbc_depth_tile_kernel, dim3(n_tiles), dim3(64), 0, ks, da);
+                    GO(hipGetLastError(), "launch cbc_depth_tile_kernel");
+                    hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)da.tile_sum, toff, n_tiles);
+                    hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)da.tile_cnt, toff + n_tiles + 1, n_tiles);
+                    GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+                    hipLaunchKernelGGL(cbc_depth_compact_kernel, dim3(n_tiles), dim3(64), 0, ks, da);
+                    GO(hipGetLastError(), "launch cbc_depth_compact_kernel");
+                    GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+                    hipLaunchKernelGGL(cbc_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
+                    GO(hipGetLastError(), "launch cbc_depth_count_kernel");
+                    hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_ttiles);
+                    GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+                    hipLaunchKernelGGL(cbc_depth_write_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
+                    GO(hipGetLastError(), "launch cbc_depth_write_kernel");
+                    GO(hipEventRecord(ctx->ev_rg[4], ks), "hipEventRecord");
+                    ctx->have_depth_timing = 1; ctx->have_sam_timing = 0; ctx->have_region_timing = 0;
+                } else if (sam) {                              /* the same three steps with the SAM bodies */
                     cbc_sam_args sa;
                     memset(&sa, 0, sizeof sa);
                     sa.R = ra; sa.block_name = (const uint32_t *)ctx->arena[A_SBN].p; sa.names = (const uint8_t *)ctx->arena[A_SNAMES].p;
@@ -1052,7 +1124,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     hipLaunchKernelGGL(cbc_sam_write_kernel, dim3(n_blocks), dim3(64 * CBC_SAM_WAVES), 0, ks, sa);
                     GO(hipGetLastError(), "launch cbc_sam_write_kernel");
                     GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                    ctx->have_sam_timing = 1; ctx->have_region_timing = 0;
+                    ctx->have_sam_timing = 1; ctx->have_region_timing = 0; ctx->have_depth_timing = 0;
                 } else {
                 hipLaunchKernelGGL(cbc_region_count_kernel, dim3(n_blocks), dim3(64), 0, ks, ra);
                 GO(hipGetLastError(), "launch cbc_region_count_kernel");
@@ -1062,7 +1134,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 hipLaunchKernelGGL(cbc_region_write_kernel, dim3(n_blocks), dim3(64 * CBC_REGION_WAVES), 0, ks, ra);
                 GO(hipGetLastError(), "launch cbc_region_write_kernel");
                 GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                ctx->have_region_timing = 1; ctx->have_sam_timing = 0;
+                ctx->have_region_timing = 1; ctx->have_sam_timing = 0; ctx->have_depth_timing = 0;
                 }
             }
             if (two_bit && k.r1 > k.r0) {
@@ -1094,7 +1166,10 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         if (text) GO(hipStreamWaitEvent(sc, ctx->ev_chunk[0], 0), "hipStreamWaitEvent");
         GO(hipMemcpyAsync(res, d_res, (uint64_t)n_blocks * sizeof(cbc_block_result), hipMemcpyDeviceToHost, sc), "D2H results");
         if (two_bit) GO(hipMemcpyAsync(&got, ctx->arena[A_CNT].p, 8, hipMemcpyDeviceToHost, sc), "D2H counter");
-        if (text) {
+        if (depth) {
+            GO(hipMemcpyAsync(dctr, ctx->arena[A_DCTR].p, 16, hipMemcpyDeviceToHost, sc), "D2H depth counters");
+            GO(hipMemcpyAsync(&total, (uint64_t *)ctx->arena[A_OFF].p + n_ttiles, 8, hipMemcpyDeviceToHost, sc), "D2H text size");
+        } else if (text) {
             cnt = (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
             if (!cnt) { rc = CBC_E_NOMEM; goto done; }
             GO(hipMemcpyAsync(cnt, ctx->arena[A_RCNT].p, (uint64_t)n_blocks * sizeof(cbc_block_result), hipMemcpyDeviceToHost, sc), "D2H region counts");
@@ -1103,9 +1178,10 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         GO(hipStreamSynchronize(sc), "decode kernel");
         tm.kernels_done_s = wall_now() - T0;
         if (text) {
-            for (uint32_t b = 0; b < n_blocks; b++) kept += cnt[b].n_symbols;
+            if (depth) { kept = dctr[0]; *depth->n_runs = dctr[1]; }
+            else for (uint32_t b = 0; b < n_blocks; b++) kept += cnt[b].n_symbols;
             *rg->text_bytes = total; *rg->n_selected = kept;
-            if (total > rg->text_cap) { rc = set_err(ctx, CBC_E_ARG, sam ? "text_cap too small for the SAM text" : "text_cap too small for the region's text", hipSuccess); goto done; }
+            if (total > rg->text_cap) { rc = set_err(ctx, CBC_E_ARG, depth ? "text_cap too small for the depth text" : sam ? "text_cap too small for the SAM text" : "text_cap too small for the region's text", hipSuccess); goto done; }
             if (total) {                                       /* the one copy of the output: exactly its size */
                 GO(hipMemcpyAsync(rg->text, ctx->arena[A_TEXT].p, total, hipMemcpyDeviceToHost, sc), "D2H region text");
                 GO(hipStreamSynchronize(sc), "D2H region text");
@@ -1172,7 +1248,7 @@ API int cbc_gpu_decode_region(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         nrec += bl[b].n_reads;
     }
     const uint64_t need = nrec * (stride + 1ull);               /* every read kept: rl + 1 <= stride + 1 bytes each */
-    region_req rg = { window_start, beg, end, smax, text, text_cap < need ? text_cap : need, text_bytes, n_selected, NULL, NULL, 0, 0 };
+    region_req rg = { window_start, beg, end, smax, text, text_cap < need ? text_cap : need, text_bytes, n_selected, NULL, NULL, 0, 0, NULL };
     int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
                                 nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
     free(bl);
@@ -1234,7 +1310,7 @@ API int cbc_gpu_decode_sam(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_byte
     if (bad) { free(bl); free(bn); return set_err(ctx, CBC_E_ARG, bad, hipSuccess); }
     for (uint32_t b = 0; b < n_blocks; b++) bl[b].in_off -= in0;
     region_req rg = { window_start, region ? region->beg : 1u, region ? region->end : UINT64_MAX, region ? region->smax : 0u, text,
-                      text_cap < need ? text_cap : need, text_bytes, n_reads, bn, (const uint8_t *)names, names_bytes, region != NULL };
+                      text_cap < need ? text_cap : need, text_bytes, n_reads, bn, (const uint8_t *)names, names_bytes, region != NULL, NULL };
     int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
                                 nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
     free(bl); free(bn);
@@ -1248,6 +1324,62 @@ API int cbc_gpu_last_sam_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *count_ms,
     HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
     HIPCHK(hipEventElapsedTime(count_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
     HIPCHK(hipEventElapsedTime(text_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
+    return CBC_OK;
+}
+
+/* coverage: the window's blocks laid out afresh as for a region decode, then span decode + mark + scan + text on the device
+ * (cbc_depth_body.h) */
+API int cbc_gpu_decode_depth(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                             uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const char *name,
+                             uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax, uint32_t exclude_flags,
+                             uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_runs, uint64_t *n_reads_kept,
+                             cbc_block_result *results)
+{
+    if (!ctx || !blocks || !caps || !window_start || !name || !text_bytes || !n_runs || !n_reads_kept || (text_cap && !text)) return CBC_E_ARG;
+    *text_bytes = 0; *n_runs = 0; *n_reads_kept = 0;
+    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (n_blocks == 0) return CBC_OK;
+    if (!in) return CBC_E_ARG;
+    if (smax == 0 || beg < 1 || beg > end || end > CBC_SAM_MAX_POS)
+        return set_err(ctx, CBC_E_ARG, "depth wants 1 <= beg <= end <= 2^31 - 1 and smax > 0", hipSuccess);
+    if (name_bytes < 1 || name_bytes > CBC_SAM_MAX_NAME || memchr(name, '\t', name_bytes) || memchr(name, '\n', name_bytes) || memchr(name, 0, name_bytes))
+        return set_err(ctx, CBC_E_ARG, "depth: the contig name is empty, longer than 255 bytes or holds a tab, a newline or a NUL", hipSuccess);
+    const uint32_t stride = blocks[0].seq_stride;
+    if (stride < 4 || stride > 256 || (stride & 3u)) return set_err(ctx, CBC_E_ARG, "depth wants seq_stride in 4..256, a multiple of 4", hipSuccess);
+    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)n_blocks * sizeof(cbc_dec_block_desc));
+    if (!bl) return CBC_E_NOMEM;
+    uint64_t in0 = UINT64_MAX, in1 = 0, nrec = 0;
+    for (uint32_t b = 0; b < n_blocks; b++) {                  /* no sums of caller values that could wrap */
+        const cbc_dec_block_desc *d = &blocks[b];
+        if (d->seq_stride != stride || d->in_off > in_bytes || d->in_bytes > in_bytes - d->in_off || d->n_reads > CBC_MAX_BLOCK_READS) {
+            free(bl); return set_err(ctx, CBC_E_ARG, "depth: block out of range of `in`, or strides differ", hipSuccess); }
+        if (d->in_off < in0) in0 = d->in_off;
+        if (d->in_off + d->in_bytes > in1) in1 = d->in_off + d->in_bytes;
+        bl[b] = *d;
+        bl[b].rec_base = nrec; bl[b].seq_base = nrec * stride;
+        nrec += d->n_reads;
+    }
+    if (nrec > 0x3fffffffull) { free(bl); return set_err(ctx, CBC_E_ARG, "depth: more than 2^30 - 1 reads in one call", hipSuccess); }
+    if (nrec == 0) { free(bl); return CBC_OK; }                 /* blocks without reads: no line */
+    for (uint32_t b = 0; b < n_blocks; b++) bl[b].in_off -= in0;
+    const uint64_t need = nrec ? (2u * nrec - 1u) * (name_bytes + 34ull) : 0u;   /* K reads: at most 2K - 1 runs */
+    depth_req dq = { exclude_flags, n_runs };
+    region_req rg = { window_start, beg, end, smax, text, text_cap < need ? text_cap : need, text_bytes, n_reads_kept, NULL,
+                      (const uint8_t *)name, name_bytes, 1, &dq };
+    int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
+                                nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
+    free(bl);
+    return rc;
+}
+
+API int cbc_gpu_last_depth_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *text_ms)
+{
+    if (!ctx || !decode_ms || !mark_ms || !scan_ms || !text_ms || !ctx->have_depth_timing) return CBC_E_ARG;
+    HIPCHK(hipEventSynchronize(ctx->ev_rg[4]), "hipEventSynchronize");
+    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(mark_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(scan_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(text_ms, ctx->ev_rg[3], ctx->ev_rg[4]), "hipEventElapsedTime");
     return CBC_OK;
 }
 

@@ -44,6 +44,11 @@ static void usage(const char *p)
             "         --sam (write SAM instead of bare reads: @HD, one @SQ per contig, then per read FLAG, RNAME, POS and SEQ;\n"
             "                QNAME, MAPQ, CIGAR, mate fields and QUAL are not stored and come out as * 255 * * 0 0 *; the text is\n"
             "                assembled on the device; alone or with --region; block containers of short reads, one device)\n"
+            "         --depth (write the coverage instead of the reads, as bedGraph: NAME, start, end (0-based, half-open), depth, one\n"
+            "                  line per run of equal non-zero depth; a read covers POS .. POS + span - 1, the bases it deletes\n"
+            "                  included; computed and formatted on the device; whole file, contig by contig, or with --region the\n"
+            "                  window alone; block containers of short reads, one device; not with --sam)\n"
+            "         --depth-exclude-flags N (with --depth: leave out reads with FLAG & N != 0; default 0, samtools uses 0x704)\n"
             "options: -l (header read length = longest read)  --block-reads N (default 4096)  --device N (default 0)\n"
             "         --threads N (SAM parser threads, default one per CPU)  --verbose (stage times)\n"
             "         --compat (write the reference's own single-stream format; slow: one stream = one wavefront)\n"
@@ -422,6 +427,7 @@ static int do_compress(const char *in, const char *out, const char *ref, uint32_
 int cbc_cli_decompress(const char *in, const char *out, const char *ref, const int *devs, int ndev);   /* cbc_cli_unpack.c */
 int cbc_cli_decompress_region(const char *in, const char *out, const char *ref, int device, const char *region, int verbose);
 int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int verbose);
+int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude, int verbose);
 
 int main(int argc, char **argv)
 {
@@ -430,7 +436,8 @@ int main(int argc, char **argv)
     int devs[CBC_MAX_DEVICES] = { 0 }, ndev = 0;
     uint32_t block_reads = 0;
     const char *region = NULL;
-    int sam_out = 0;
+    int sam_out = 0, depth_out = 0, depth_excl_given = 0;
+    uint32_t depth_exclude = 0;
     g_main_t0 = now_s();
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
@@ -451,6 +458,13 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--verbose")) { verbose = 1; continue; }
         if (!strcmp(a, "--region") && i + 1 < argc) { region = argv[++i]; continue; }
         if (!strcmp(a, "--sam")) { sam_out = 1; continue; }
+        if (!strcmp(a, "--depth")) { depth_out = 1; continue; }
+        if (!strcmp(a, "--depth-exclude-flags") && i + 1 < argc) {
+            char *e = NULL;
+            const unsigned long v = strtoul(argv[++i], &e, 0);
+            if (!e || *e || e == argv[i] || v > 0xfffful) { fprintf(stderr, "cbc: --depth-exclude-flags wants a FLAG mask in 0..65535 (decimal, 0x.. or 0..)\n"); return 1; }
+            depth_exclude = (uint32_t)v; depth_excl_given = 1; continue;
+        }
         if (!strcmp(a, "--compat")) { compat = 1; continue; }
         if (!strcmp(a, "--long")) { long_reads = 1; continue; }
         if (!strcmp(a, "--device-parse")) { device_parse = 1; continue; }
@@ -493,6 +507,11 @@ int main(int argc, char **argv)
     if (region && ndev > 1) { fprintf(stderr, "cbc: --region decodes on one device; give a single --devices ordinal\n"); return 1; }
     if (sam_out && mode != 2) { fprintf(stderr, "cbc: --sam applies to decompression (-d / -x)\n"); return 1; }
     if (sam_out && ndev > 1) { fprintf(stderr, "cbc: --sam decodes on one device; give a single --devices ordinal\n"); return 1; }
+    if (depth_out && mode != 2) { fprintf(stderr, "cbc: --depth applies to decompression (-d / -x)\n"); return 1; }
+    if (depth_out && sam_out) { fprintf(stderr, "cbc: --depth and --sam are two different outputs; give one of them\n"); return 1; }
+    if (depth_out && ndev > 1) { fprintf(stderr, "cbc: --depth decodes on one device; give a single --devices ordinal\n"); return 1; }
+    if (depth_excl_given && !depth_out) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
+    if (depth_out) return cbc_cli_decompress_depth(files[0], files[1], files[2], device, region, depth_exclude, verbose);
     if (sam_out) return cbc_cli_decompress_sam(files[0], files[1], files[2], device, region, verbose);
     if (region) return cbc_cli_decompress_region(files[0], files[1], files[2], device, region, verbose);
     if (ndev == 0) { devs[0] = device; ndev = 1; }

@@ -1895,6 +1895,29 @@ API uint64_t cbc_unpack_sam_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint
     return n;
 }
 
+/* ---- coverage output (include/cbc_host.h) ---- */
+API int cbc_unpack_contig_blocks(const cbc_unpack_plan *u, uint32_t contig, cbc_region_sel *sel, char *errbuf, size_t errlen)
+{
+    if (!u || !sel || !u->names || !u->contig_name_off || contig >= u->n_contigs) return CBC_E_ARG;
+    if (sam_name_len(u, contig) < 0)
+        return region_err(errbuf, errlen, "corrupt container: a contig name lies outside the name table%.*s", "", 0);
+    const int rc = cbc_unpack_region(u, u->names + u->contig_name_off[contig], sel, errbuf, errlen);   /* a whole name: the contig */
+    if (rc) return rc;
+    if (sel->contig != contig)
+        return region_err(errbuf, errlen, "contig name \"%.*s\" occurs twice in the container", u->names + u->contig_name_off[contig], 60);
+    return 0;
+}
+
+API uint64_t cbc_unpack_depth_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig)
+{
+    if (!u || u->long_reads || !u->names || !u->contig_name_off || b0 > b1 || b1 > u->n_blocks || contig >= u->n_contigs) return 0;
+    const int64_t nl = sam_name_len(u, contig);
+    if (nl < 0) return 0;
+    uint64_t k = 0;
+    for (uint32_t b = b0; b < b1; b++) k += u->blocks[b].n_reads;
+    return k ? (2u * k - 1u) * ((uint64_t)nl + 34u) : 0u;
+}
+
 /* One reconstructed read per line (print_line, src/compression.c:16-40). */
 API int64_t cbc_unpack_write_text(const cbc_unpack_plan *u, const cbc_read_rec *recs, const uint8_t *seq,
                                   char *dst, uint64_t cap)

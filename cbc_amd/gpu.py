@@ -222,6 +222,14 @@ def lib():
                                          ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
         L.cbc_gpu_last_sam_ms.restype = ctypes.c_int
         L.cbc_gpu_last_sam_ms.argtypes = L.cbc_gpu_last_region_ms.argtypes
+        L.cbc_gpu_decode_depth.restype = ctypes.c_int
+        L.cbc_gpu_decode_depth.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                           ctypes.POINTER(host.LdsCaps), ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32,
+                                           ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                           ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.cbc_gpu_last_depth_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_depth_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         if L.cbc_gpu_abi_version() != 1:
             raise CbcGpuError("libcbc_gpu.so ABI version mismatch")
         _lib = L
@@ -241,7 +249,8 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_host_unregister", "cbc_gpu_plan_output_caps", "cbc_gpu_reserve_encode",
            "cbc_gpu_decode_stream_blocks", "cbc_gpu_group_create", "cbc_gpu_group_gather", "cbc_gpu_group_destroy", "cbc_gpu_group_last_error",
            "cbc_gpu_stash_reset", "cbc_gpu_stash_bytes", "cbc_gpu_stash_fetch", "cbc_gpu_decode_region",
-           "cbc_gpu_decode_blocks_span", "cbc_gpu_last_region_ms", "cbc_gpu_decode_sam", "cbc_gpu_last_sam_ms"]
+           "cbc_gpu_decode_blocks_span", "cbc_gpu_last_region_ms", "cbc_gpu_decode_sam", "cbc_gpu_last_sam_ms",
+           "cbc_gpu_decode_depth", "cbc_gpu_last_depth_ms"]
 
 
 class Encoder:
@@ -484,6 +493,61 @@ class Encoder:
             self._check(rc, "cbc_gpu_decode_sam")
         out = hdr + text[:int(nbytes.value)].tobytes()
         return (out, int(nrd.value), sel, res[:nb]) if results else out
+
+    def decode_depth(self, plan: "host.UnpackPlan", region=None, exclude_flags=0, results=False, text_cap=None, smax=None):
+        """Coverage of the container's reads as bedGraph bytes (cbc_gpu_decode_depth): per maximal run of equal non-zero
+        depth `NAME\\tstart\\tend\\tdepth\\n`, 0-based half-open.  A read covers POS .. POS + span - 1, the bases it deletes
+        included (a span coverage); reads with FLAG & exclude_flags != 0 are left out.  region=None: every contig that has
+        blocks, as a whole, in the order of the contig table; otherwise (NAME, NAME:BEG or NAME:BEG-END) only the window, reads
+        clipped to it.  The reference must have been uploaded (upload_reference(plan.ref)).  A selection without blocks gives
+        b"" and runs nothing on the device.  With results=True returns (text, n_runs, n_reads_kept, per-block decode results
+        of the blocks used) and lets a failed block pass (it marks nothing); text_cap: size of the buffer of one call (default:
+        plan.depth_text_cap of its blocks); smax: the span bound the decode checks (default: the selection's)."""
+        plan.sam_header()                                     # refuses what the text cannot carry, and long-read containers
+        sels = [plan.region(region)] if region is not None else [plan.contig_blocks(c) for c in range(plan.n_contigs)]
+        out, n_runs, n_kept, allres = [], 0, 0, []
+        self.last_depth_text_bytes = 0
+        self._depth_ms = None
+        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
+        pay = np.ascontiguousarray(plan.payloads)
+        for sel in sels:
+            nb = sel.b1 - sel.b0
+            if nb == 0:
+                continue
+            blocks = np.ascontiguousarray(plan.blocks[sel.b0:sel.b1])
+            ws = np.ascontiguousarray(plan.window_start[sel.b0:sel.b1], dtype=np.uint64)
+            off = int(plan.contig_name_off[sel.contig])
+            name = plan.names[off:].tobytes().split(b"\0", 1)[0]
+            cap = plan.depth_text_cap(sel.b0, sel.b1, sel.contig) if text_cap is None else int(text_cap)
+            text = np.zeros(max(cap, 1), dtype=np.uint8)
+            res = np.zeros(nb, dtype=host.RESULT_DTYPE)
+            nbytes, nr, nk = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+            rc = lib().cbc_gpu_decode_depth(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
+                                            ws.ctypes.data, name, len(name), sel.beg, sel.end, sel.smax if smax is None else int(smax),
+                                            int(exclude_flags),
+                                            text.ctypes.data, cap, ctypes.byref(nbytes), ctypes.byref(nr), ctypes.byref(nk),
+                                            res.ctypes.data)
+            self.last_depth_text_bytes += int(nbytes.value)
+            if rc != 0 and not (results and rc == -4):
+                self._check(rc, "cbc_gpu_decode_depth")
+            ms = self.last_depth_ms(_one=True)
+            self._depth_ms = ms if self._depth_ms is None else tuple(a + b for a, b in zip(self._depth_ms, ms))
+            out.append(text[:int(nbytes.value)].tobytes())
+            n_runs += int(nr.value); n_kept += int(nk.value); allres.append(res)
+        text = b"".join(out)
+        if results:
+            return text, n_runs, n_kept, (np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE))
+        return text
+
+    def last_depth_ms(self, _one=False):
+        """(decode, mark, scan + compact, text) kernel milliseconds of the last decode_depth, summed over its calls."""
+        if not _one:
+            if getattr(self, "_depth_ms", None) is None:
+                raise CbcGpuError("no decode_depth has run on the device")
+            return self._depth_ms
+        v = [ctypes.c_float() for _ in range(4)]
+        self._check(lib().cbc_gpu_last_depth_ms(self._ctx, *[ctypes.byref(x) for x in v]), "cbc_gpu_last_depth_ms")
+        return tuple(float(x.value) for x in v)
 
     def last_sam_ms(self):
         """(decode, count + scan, text) kernel milliseconds of the last decode_sam."""

@@ -183,6 +183,10 @@ def lib():
         L.cbc_unpack_sam_header.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_size_t]
         L.cbc_unpack_sam_text_cap.restype = ctypes.c_uint64
         L.cbc_unpack_sam_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32]
+        L.cbc_unpack_contig_blocks.restype = ctypes.c_int
+        L.cbc_unpack_contig_blocks.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.POINTER(RegionSelC), ctypes.c_char_p, ctypes.c_size_t]
+        L.cbc_unpack_depth_text_cap.restype = ctypes.c_uint64
+        L.cbc_unpack_depth_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
         _lib = L
     return _lib
 
@@ -472,6 +476,20 @@ class UnpackPlan:
             raise CbcInputError("cbc_unpack_region failed (%d): %s" % (rc, err.value.decode(errors="replace")))
         return RegionSelection(int(sel.contig), int(sel.b0), int(sel.b1), int(sel.beg), int(sel.end), int(sel.smax),
                                int(sel.contig_len))
+
+    def contig_blocks(self, contig: int):
+        """The selection of contig `contig` as a whole (cbc_unpack_contig_blocks): its blocks, beg = 1, end = its length."""
+        sel = RegionSelC()
+        err = ctypes.create_string_buffer(512)
+        rc = lib().cbc_unpack_contig_blocks(self._ptr, int(contig), ctypes.byref(sel), err, 512)
+        if rc != 0:
+            raise CbcInputError("cbc_unpack_contig_blocks failed (%d): %s" % (rc, err.value.decode(errors="replace")))
+        return RegionSelection(int(sel.contig), int(sel.b0), int(sel.b1), int(sel.beg), int(sel.end), int(sel.smax),
+                               int(sel.contig_len))
+
+    def depth_text_cap(self, b0, b1, contig) -> int:
+        """Bytes that always hold the bedGraph of blocks [b0, b1) of contig `contig` (cbc_unpack_depth_text_cap)."""
+        return int(lib().cbc_unpack_depth_text_cap(self._ptr, b0, b1, contig))
 
     def sam_header(self) -> bytes:
         """@HD and one @SQ line per contig of the container's table (cbc_unpack_sam_header): what precedes the alignment

@@ -331,6 +331,30 @@ int  cbc_gpu_decode_sam(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, 
  * and the text assembly. */
 int  cbc_gpu_last_sam_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *count_ms, float *text_ms);
 
+/* ---- coverage of a decode -------------------------------------------------------------------------
+ * Decode `blocks` -- a selection of cbc_unpack_region on ONE contig, decoded by the span-reporting decoder against smax --
+ * and write the depth of the window [beg, end] (1-based, inclusive, end <= CBC_SAM_MAX_POS) as bedGraph, computed and
+ * formatted on the device: one line per maximal run of equal, non-zero depth, 0-based half-open, in position order, no header:
+ *     <name>\t<start0>\t<end0>\t<depth>\n
+ * Depth at position p = the kept reads with POS <= p <= POS + span - 1, POS = window_start[b] + the block-local POS and span
+ * the reference bases the codec's reconstruction covers (rlen for a read coded as perfect, rlen + nDel - nIns otherwise; 0
+ * covers nothing).  This is a SPAN coverage: deleted bases count as covered (the file does not say where in the read they
+ * lie) -- for ordinary CIGARs the interval M + D + N, what `bedtools genomecov -bg` and `samtools depth -J` count.  Kept =
+ * every read cbc_gpu_decode_region keeps for [beg, end] with (FLAG & exclude_flags) == 0.  Reads are clipped to the window and
+ * runs that reach its edge end there.  `name` (name_bytes of it, 1..CBC_SAM_MAX_NAME, no tab / newline / NUL) is the text of
+ * the first column.  A block that fails to decode marks nothing and the call returns CBC_E_BLOCK, as cbc_gpu_decode_region
+ * does.  *text_bytes = bytes of text (also when text_cap is too small: CBC_E_ARG, nothing copied), *n_runs = lines,
+ * *n_reads_kept = reads counted.  K reads give at most 2K - 1 runs and a line is at most name_bytes + 34 bytes
+ * (cbc_unpack_depth_text_cap).  The window costs 4 bytes of device memory per position: CBC_E_NOMEM when that cannot be had. */
+int  cbc_gpu_decode_depth(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                          uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                          const char *name, uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax,
+                          uint32_t exclude_flags, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_runs,
+                          uint64_t *n_reads_kept, cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_depth (HIP events on its stream): the span decode; zeroing + mark; tile
+ * sums, scans and change points; line count, scan and the text. */
+int  cbc_gpu_last_depth_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *text_ms);
+
 /* ---- whole-file stream ("compat" mode): the reference's own file format --------------------------------------
  * compress() / decompress(), src/compression.c:112-216: ONE arithmetic stream per file, models never reset.
  * `batch` is a cbc_host_batch packed with cbc_pack_opts.whole_file = 1: its `blocks` are SEGMENTS of the one

@@ -215,6 +215,14 @@ int     cbc_unpack_region(const cbc_unpack_plan *u, const char *region, cbc_regi
 int64_t  cbc_unpack_sam_header(const cbc_unpack_plan *u, char *dst, uint64_t cap, char *errbuf, size_t errlen);
 uint64_t cbc_unpack_sam_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1);
 
+/* Coverage output (the text comes from cbc_gpu_decode_depth).  cbc_unpack_contig_blocks: the
+ * selection of contig `contig` as a whole -- its blocks [b0, b1) (b0 == b1: the contig has none), beg = 1, end = its length,
+ * smax -- with the checks and errors of cbc_unpack_region (CBC_E_INPUT also when another contig carries the same name).
+ * cbc_unpack_depth_text_cap: a text_cap that always holds the bedGraph of blocks [b0, b1) of contig `contig`: K reads give at
+ * most 2K - 1 runs of at most len(name) + 34 bytes (0 for a plan cbc_unpack_sam_header refuses or a bad range). */
+int      cbc_unpack_contig_blocks(const cbc_unpack_plan *u, uint32_t contig, cbc_region_sel *sel, char *errbuf, size_t errlen);
+uint64_t cbc_unpack_depth_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig);
+
 int     cbc_unpack_plan_create(const uint8_t *blob, uint64_t len, const char *fasta, size_t fasta_len,
                                cbc_unpack_plan **out, char *errbuf, size_t errlen);
 void    cbc_unpack_plan_free(cbc_unpack_plan *u);
