@@ -375,3 +375,98 @@ int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, i
     (void)t0;
     return 0;
 }
+
+/* `cbc -d|-x ... --region A --region B ... [--regions-file FILE]`: the union of the loci in one pass.
+ * The target set and its blocks come from cbc_unpack_targets; reads and SAM are one call over the selected blocks of all
+ * contigs, the depth one call per contig that has intervals and blocks, the texts appended in contig-table order. */
+int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                               const char *bed_path, uint32_t output, uint32_t exclude, int verbose)
+{
+    const double t0 = now2();
+    const char *what = output == CBC_TARGETS_DEPTH ? "--depth" : output == CBC_TARGETS_SAM ? "--sam" : "--region";
+    size_t blob_len = 0, fa_len = 0, bed_len = 0;
+    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
+    if (!blob || !fa) return 1;
+    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
+        fprintf(stderr, "cbc: %s needs a block container; %s is a single-stream (--compat) file, which has no block index\n",
+                bed_path ? "--regions-file" : what, in);
+        return 1;
+    }
+    char *bed = NULL;
+    if (bed_path && !(bed = slurp2(bed_path, &bed_len))) return 1;
+    char err[512];
+    cbc_unpack_plan *u = NULL;
+    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
+    free(fa);
+    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
+    cbc_targets *T = NULL;
+    rc = cbc_unpack_targets(u, regions, n_regions, bed, bed_len, &T, err, sizeof err);
+    free(bed);
+    if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT && err[0] ? err : "target selection failed"); return 1; }
+    const int64_t hdr = output == CBC_TARGETS_SAM ? cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) : 0;
+    if (hdr < 0) { fprintf(stderr, "cbc: %s\n", err); return 1; }
+    /* the selected blocks with their window starts and contigs, gathered once */
+    const uint32_t nb = T->n_blocks;
+    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)(nb ? nb : 1) * sizeof *bl);
+    uint64_t *ws = (uint64_t *)malloc((size_t)(nb ? nb : 1) * 8);
+    uint32_t *bc = (uint32_t *)malloc((size_t)(nb ? nb : 1) * 4);
+    if (!bl || !ws || !bc) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    for (uint32_t k = 0; k < nb; k++) { const uint32_t b = T->blocks[k]; bl[k] = u->blocks[b]; ws[k] = u->window_start[b]; bc[k] = u->block_contig[b]; }
+    uint64_t cap = 0;
+    if (output == CBC_TARGETS_DEPTH) { for (uint32_t c = 0; c < u->n_contigs; c++) { const uint64_t x = cbc_unpack_targets_depth_cap(u, T, c); if (x > cap) cap = x; } }
+    else cap = cbc_unpack_targets_text_cap(u, T, output == CBC_TARGETS_SAM);
+    char *text = (char *)malloc((size_t)hdr + (size_t)cap + 1);
+    if (!text || (hdr && cbc_unpack_sam_header(u, text, (uint64_t)hdr, err, sizeof err) != hdr)) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    const double t1 = now2();
+    double t_init = 0, t_dev = 0;
+    FILE *fo = fopen(out, "wb");
+    if (!fo || (hdr && fwrite(text, 1, (size_t)hdr, fo) != (size_t)hdr)) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    cbc_gpu_ctx *ctx = NULL;
+    uint64_t total = 0, reads = 0, runs = 0;
+    float ms[4] = { 0, 0, 0, 0 };
+    const cbc_gpu_targets gt = { (const uint32_t *)T->iv, NULL, T->n_iv, T->smax };
+    const uint32_t n_calls = !nb ? 0u : output == CBC_TARGETS_DEPTH ? u->n_contigs : 1u;
+    for (uint32_t k = 0; k < n_calls; k++) {
+        const uint32_t k0 = output == CBC_TARGETS_DEPTH ? T->contig_blk_first[k] : 0u, kn = output == CBC_TARGETS_DEPTH ? T->contig_blk_count[k] : nb;
+        if (!kn) continue;                              /* no block can hold a read of the contig's intervals */
+        const double a = now2();
+        if (!ctx) {
+            rc = cbc_gpu_init(device, &ctx);
+            if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
+            if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+            t_init = now2() - a;
+        }
+        const double b = now2();
+        cbc_gpu_targets g = gt;
+        g.block_iv = T->block_iv + 2 * (size_t)k0;
+        uint64_t tb = 0, nr = 0, nn = 0;
+        rc = cbc_gpu_decode_targets(ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
+                                    u->contig_name_off, u->n_contigs, &g, output, exclude, (uint8_t *)text, cap, &tb, &nr, &nn, NULL);
+        if (rc) { fprintf(stderr, "cbc: targets decode failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+        t_dev += now2() - b;
+        if (verbose) {
+            float m4[4];
+            if (cbc_gpu_last_targets_ms(ctx, &m4[0], &m4[1], &m4[2], &m4[3]) == 0) for (int i = 0; i < 4; i++) ms[i] += m4[i];
+        }
+        if (tb && fwrite(text, 1, (size_t)tb, fo) != (size_t)tb) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+        total += tb; reads += nr; runs += nn;
+    }
+    if (fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    if (ctx) cbc_gpu_shutdown(ctx);
+    if (output == CBC_TARGETS_DEPTH)
+        printf("depth of %u intervals: %llu runs from %llu reads in %u of %u blocks\n", T->n_iv, (unsigned long long)runs,
+               (unsigned long long)reads, nb, u->n_blocks);
+    else printf("%llu reads in %u intervals %s from %u of %u blocks\n", (unsigned long long)reads, T->n_iv,
+                output == CBC_TARGETS_SAM ? "written as SAM" : "decompressed", nb, u->n_blocks);
+    if (verbose) {
+        printf("targets: %llu regions and BED lines taken, %u intervals after merging, %llu BED lines selected nothing, %llu text bytes, span bound %u\n",
+               (unsigned long long)T->n_input, T->n_iv, (unsigned long long)T->bed_unselected, (unsigned long long)total, T->smax);
+        printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + text + write %.3f s\n", t1 - t0, t_init, t_dev);
+        if (ctx) printf("kernels: decode %.3f ms, %s %.3f ms, scan + compact %.3f ms, text %.3f ms\n", ms[0],
+                        output == CBC_TARGETS_DEPTH ? "mark" : "filter + scan", ms[1], ms[2], ms[3]);
+    }
+    free(text); free(bl); free(ws); free(bc); free(blob);
+    cbc_targets_free(T);
+    cbc_unpack_plan_free(u);
+    return 0;
+}

@@ -22,6 +22,7 @@
 #include "cbc_region_body.h"
 #include "cbc_sam_body.h"
 #include "cbc_depth_body.h"
+#include "cbc_targets_body.h"
 #include "cbc_plan.h"
 #include "cbc_stream_body.h"
 #include "cbc_long_body.h"
@@ -116,6 +117,32 @@ __global__ void __launch_bounds__(64)
 cbc_depth_count_kernel(cbc_depth_args A) { if (blockIdx.x < A.n_ttiles) cbc_depth_count<WaveGPU>(A, blockIdx.x); }
 __global__ void __launch_bounds__(64)
 cbc_depth_write_kernel(cbc_depth_args A) { cbc_depth_write<WaveGPU>(A, blockIdx.x); }
+
+/* A set of regions (cbc_gpu_decode_targets, cbc_targets_body.h): the count / write pairs of the region and the SAM text with
+ * the keep rule over the interval table, and for the depth the mark and the text passes in the compressed coordinate (the
+ * tile, scan and compact passes between them are the kernels above) */
+__global__ void __launch_bounds__(64)
+cbc_targets_count_kernel(cbc_targets_args A) { if (blockIdx.x < A.S.R.n_blocks) cbc_targets_count<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64 * CBC_REGION_WAVES)
+cbc_targets_write_kernel(cbc_targets_args A)
+{
+    if (blockIdx.x >= A.S.R.n_blocks) return;
+    cbc_targets_write<WaveGPU>(A, blockIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), CBC_REGION_WAVES);
+}
+__global__ void __launch_bounds__(64)
+cbc_targets_sam_count_kernel(cbc_targets_args A) { if (blockIdx.x < A.S.R.n_blocks) cbc_targets_sam_count<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64 * CBC_SAM_WAVES)
+cbc_targets_sam_write_kernel(cbc_targets_args A)
+{
+    if (blockIdx.x >= A.S.R.n_blocks) return;
+    cbc_targets_sam_write<WaveGPU>(A, blockIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), CBC_SAM_WAVES);
+}
+__global__ void __launch_bounds__(64)
+cbc_targets_mark_kernel(cbc_tdepth_args A) { if (blockIdx.x < A.D.R.n_blocks) cbc_targets_mark<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_targets_depth_count_kernel(cbc_tdepth_args A) { if (blockIdx.x < A.D.n_ttiles) cbc_targets_depth_count<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_targets_depth_write_kernel(cbc_tdepth_args A) { cbc_targets_depth_write<WaveGPU>(A, blockIdx.x); }
 
 /* Whole-file stream / general-form fallback (cbc_stream_body.h): one wavefront per stream.  Workgroup w codes streams
  * w, w + gridDim, ... with var table w of the pool, which it re-zeroes between streams. */
@@ -272,7 +299,7 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
 /* grow-only device buffer owned by the context: the host-buffer entry points keep their device arrays between calls
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
-enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_COUNT };
+enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_COUNT };
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
 struct cbc_gpu_ctx {
@@ -287,6 +314,7 @@ struct cbc_gpu_ctx {
     int have_region_timing;
     int have_sam_timing;           /* the same four events, recorded by cbc_gpu_decode_sam */
     int have_depth_timing;         /* all five, recorded by cbc_gpu_decode_depth */
+    int have_targets_timing;       /* cbc_gpu_decode_targets: 1 = the four events of a reads / SAM call, 2 = the five of a depth call */
     int have_timing;
     int last_variant;              /* waves per SIMD of the encode build launched last */
     int n_cus;                     /* compute units of the device (block residency decides the kernel build) */
@@ -959,7 +987,12 @@ struct region_req {
     const uint32_t *block_name; const uint8_t *names; uint32_t names_bytes; int region;
     /* coverage (cbc_gpu_decode_depth): depth != NULL; names / names_bytes = the one contig name, n_selected = reads kept */
     const depth_req *depth;
+    /* a set of regions (cbc_gpu_decode_targets): tg != NULL, beg / end unused */
+    const struct targets_req *tg;
 };
+/* the interval table (n_iv pairs), per block its range of it, and for the depth the first slot of every interval in the
+ * compressed coordinate (n_iv + 1 entries; NULL for reads / SAM) */
+struct targets_req { const uint32_t *iv; uint32_t n_iv; const uint32_t *block_iv; const uint32_t *iv_off; };
 
 /* The host-buffer decode path as a pipeline, mirror of encode_blocks_impl: the payloads (2 bytes per read) go H2D at once;
  * the blocks are decoded in chunks (cbc_plan_chunks) on the kernel streams, and chunk c's records and bases (bytes, or 2-bit
@@ -980,9 +1013,10 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     const bool two_bit = codes_out != NULL, text = rg && rg->text_bytes, sam = text && rg->block_name;
     const depth_req *depth = text ? rg->depth : NULL;
     /* coverage: tiles of the difference array (W + 1 words), change points (two per read at most), text tiles of the runs */
-    const uint64_t d_words = depth ? rg->end - rg->beg + 2u : 0u;
+    const targets_req *tg = text ? rg->tg : NULL;
+    const uint64_t d_words = !depth ? 0u : tg ? tg->iv_off[tg->n_iv] : rg->end - rg->beg + 2u;
     const uint32_t n_tiles = (uint32_t)((d_words + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
-    const uint32_t cp_cap = depth ? (uint32_t)(2u * n_recs) : 0u;
+    const uint32_t cp_cap = depth ? (uint32_t)(2u * n_recs + (tg ? 2u * (uint64_t)tg->n_iv : 0u)) : 0u;   /* + two per interval edge */
     const uint32_t n_ttiles = (cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
     const uint32_t n_sized = depth ? n_ttiles : n_blocks;        /* entries the text's size scan runs over */
     uint32_t dctr[4] = { 0, 0, 0, 0 };
@@ -1027,6 +1061,11 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         NEED(A_SNAMES, (uint64_t)rg->names_bytes + 16, "hipMalloc contig names");
         NEED(A_SBN, (uint64_t)n_blocks * 8, "hipMalloc block names");
     }
+    if (tg) {
+        NEED(A_TIV, (uint64_t)tg->n_iv * 8 + 16, "hipMalloc intervals");
+        NEED(A_TBIV, (uint64_t)n_blocks * 8, "hipMalloc block intervals");
+        if (depth) NEED(A_TOFF, ((uint64_t)tg->n_iv + 1) * 4, "hipMalloc interval slots");
+    }
     tm.alloc_s = wall_now() - T0;
     {
         uint8_t *d_in = (uint8_t *)ctx->arena[A_IN].p, *d_seq = (uint8_t *)ctx->arena[A_SEQ].p;
@@ -1044,6 +1083,11 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         if (sam) {
             GO(hipMemcpyAsync(ctx->arena[A_SNAMES].p, rg->names, rg->names_bytes, hipMemcpyHostToDevice, sc), "H2D contig names");
             GO(hipMemcpyAsync(ctx->arena[A_SBN].p, rg->block_name, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D block names");
+        }
+        if (tg) {
+            GO(hipMemcpyAsync(ctx->arena[A_TIV].p, tg->iv, (uint64_t)tg->n_iv * 8, hipMemcpyHostToDevice, sc), "H2D intervals");
+            GO(hipMemcpyAsync(ctx->arena[A_TBIV].p, tg->block_iv, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D block intervals");
+            if (depth) GO(hipMemcpyAsync(ctx->arena[A_TOFF].p, tg->iv_off, ((uint64_t)tg->n_iv + 1) * 4, hipMemcpyHostToDevice, sc), "H2D interval slots");
         }
         GO(hipEventRecord(ctx->ev_done[0], sc), "hipEventRecord");       /* inputs are on the device */
         tm.h2d_bytes = in_bytes + (uint64_t)n_blocks * sizeof(cbc_dec_block_desc);
@@ -1092,6 +1136,13 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     da.name_len = rg->names_bytes; da.exclude = depth->exclude; da.n_tiles = n_tiles; da.n_ttiles = n_ttiles;
                     GO(hipMemsetAsync(da.diff, 0, da.diff_words * 4, ks), "memset depth window");
                     GO(hipMemsetAsync(da.ctr, 0, 16, ks), "memset depth counters");
+                    cbc_tdepth_args ta;
+                    memset(&ta, 0, sizeof ta);
+                    if (tg) {
+                        ta.D = da; ta.iv = (const uint32_t *)ctx->arena[A_TIV].p; ta.iv_off = (const uint32_t *)ctx->arena[A_TOFF].p;
+                        ta.block_iv = (const uint32_t *)ctx->arena[A_TBIV].p; ta.n_iv = tg->n_iv;
+                        hipLaunchKernelGGL(cbc_targets_mark_kernel, dim3(n_blocks), dim3(64), 0, ks, ta);
+                    } else
                     hipLaunchKernelGGL(cbc_depth_mark_kernel, dim3(n_blocks), dim3(64), 0, ks, da);
                     GO(hipGetLastError(), "launch cbc_depth_mark_kernel");
                     GO(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
@@ -1103,14 +1154,34 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     hipLaunchKernelGGL(cbc_depth_compact_kernel, dim3(n_tiles), dim3(64), 0, ks, da);
                     GO(hipGetLastError(), "launch cbc_depth_compact_kernel");
                     GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                    hipLaunchKernelGGL(cbc_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
+                    if (tg) hipLaunchKernelGGL(cbc_targets_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, ta);
+                    else hipLaunchKernelGGL(cbc_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
                     GO(hipGetLastError(), "launch cbc_depth_count_kernel");
                     hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_ttiles);
                     GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
-                    hipLaunchKernelGGL(cbc_depth_write_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
+                    if (tg) hipLaunchKernelGGL(cbc_targets_depth_write_kernel, dim3(n_ttiles), dim3(64), 0, ks, ta);
+                    else hipLaunchKernelGGL(cbc_depth_write_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
                     GO(hipGetLastError(), "launch cbc_depth_write_kernel");
                     GO(hipEventRecord(ctx->ev_rg[4], ks), "hipEventRecord");
-                    ctx->have_depth_timing = 1; ctx->have_sam_timing = 0; ctx->have_region_timing = 0;
+                    ctx->have_depth_timing = tg ? 0 : 1; ctx->have_targets_timing = tg ? 2 : 0; ctx->have_sam_timing = 0; ctx->have_region_timing = 0;
+                } else if (tg) {                               /* a set of regions: reads or SAM, the same three steps */
+                    cbc_targets_args ta;
+                    memset(&ta, 0, sizeof ta);
+                    ta.S.R = ra; ta.iv = (const uint32_t *)ctx->arena[A_TIV].p; ta.block_iv = (const uint32_t *)ctx->arena[A_TBIV].p; ta.n_iv = tg->n_iv;
+                    if (sam) {
+                        ta.S.block_name = (const uint32_t *)ctx->arena[A_SBN].p; ta.S.names = (const uint8_t *)ctx->arena[A_SNAMES].p;
+                        ta.S.names_bytes = rg->names_bytes;
+                        hipLaunchKernelGGL(cbc_targets_sam_count_kernel, dim3(n_blocks), dim3(64), 0, ks, ta);
+                    } else hipLaunchKernelGGL(cbc_targets_count_kernel, dim3(n_blocks), dim3(64), 0, ks, ta);
+                    GO(hipGetLastError(), "launch cbc_targets_count_kernel");
+                    hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_blocks);
+                    GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+                    GO(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+                    if (sam) hipLaunchKernelGGL(cbc_targets_sam_write_kernel, dim3(n_blocks), dim3(64 * CBC_SAM_WAVES), 0, ks, ta);
+                    else hipLaunchKernelGGL(cbc_targets_write_kernel, dim3(n_blocks), dim3(64 * CBC_REGION_WAVES), 0, ks, ta);
+                    GO(hipGetLastError(), "launch cbc_targets_write_kernel");
+                    GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+                    ctx->have_targets_timing = 1; ctx->have_sam_timing = 0; ctx->have_region_timing = 0; ctx->have_depth_timing = 0;
                 } else if (sam) {                              /* the same three steps with the SAM bodies */
                     cbc_sam_args sa;
                     memset(&sa, 0, sizeof sa);
@@ -1124,7 +1195,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     hipLaunchKernelGGL(cbc_sam_write_kernel, dim3(n_blocks), dim3(64 * CBC_SAM_WAVES), 0, ks, sa);
                     GO(hipGetLastError(), "launch cbc_sam_write_kernel");
                     GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                    ctx->have_sam_timing = 1; ctx->have_region_timing = 0; ctx->have_depth_timing = 0;
+                    ctx->have_sam_timing = 1; ctx->have_region_timing = 0; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0;
                 } else {
                 hipLaunchKernelGGL(cbc_region_count_kernel, dim3(n_blocks), dim3(64), 0, ks, ra);
                 GO(hipGetLastError(), "launch cbc_region_count_kernel");
@@ -1134,7 +1205,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 hipLaunchKernelGGL(cbc_region_write_kernel, dim3(n_blocks), dim3(64 * CBC_REGION_WAVES), 0, ks, ra);
                 GO(hipGetLastError(), "launch cbc_region_write_kernel");
                 GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                ctx->have_region_timing = 1; ctx->have_sam_timing = 0; ctx->have_depth_timing = 0;
+                ctx->have_region_timing = 1; ctx->have_sam_timing = 0; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0;
                 }
             }
             if (two_bit && k.r1 > k.r0) {
@@ -1380,6 +1451,108 @@ API int cbc_gpu_last_depth_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms
     HIPCHK(hipEventElapsedTime(mark_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
     HIPCHK(hipEventElapsedTime(scan_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
     HIPCHK(hipEventElapsedTime(text_ms, ctx->ev_rg[3], ctx->ev_rg[4]), "hipEventElapsedTime");
+    return CBC_OK;
+}
+
+/* a set of regions: the selected blocks laid out afresh as for a region decode, the tables checked
+ * on the host, then span decode + keep by the interval table + scan + text on the device (cbc_targets_body.h) */
+API int cbc_gpu_decode_targets(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                               uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                               const uint32_t *block_contig, const char *names, uint32_t names_bytes,
+                               const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_gpu_targets *t, uint32_t output,
+                               uint32_t exclude_flags, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_reads,
+                               uint64_t *n_runs, cbc_block_result *results)
+{
+    if (!ctx || !blocks || !caps || !window_start || !block_contig || !names || !contig_name_off || !t || !text_bytes || !n_reads ||
+        !n_runs || (text_cap && !text) || output > CBC_TARGETS_DEPTH) return CBC_E_ARG;
+    *text_bytes = 0; *n_reads = 0; *n_runs = 0;
+    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (n_blocks == 0) return CBC_OK;
+    if (!in || !t->iv || !t->block_iv) return CBC_E_ARG;
+    if (t->smax == 0 || t->n_iv == 0 || t->n_iv > (1u << 24))
+        return set_err(ctx, CBC_E_ARG, "targets decode wants smax > 0 and 1 .. 2^24 intervals", hipSuccess);
+    const bool depth = output == CBC_TARGETS_DEPTH, sam = output == CBC_TARGETS_SAM;
+    const uint32_t stride = blocks[0].seq_stride;
+    if (stride < 4 || stride > 256 || (stride & 3u)) return set_err(ctx, CBC_E_ARG, "targets decode wants seq_stride in 4..256, a multiple of 4", hipSuccess);
+    for (uint32_t i = 0; i < t->n_iv; i++)
+        if (t->iv[2 * i] < 1 || t->iv[2 * i] > t->iv[2 * i + 1] || t->iv[2 * i + 1] > CBC_SAM_MAX_POS)
+            return set_err(ctx, CBC_E_ARG, "targets decode: an interval is not 1 <= beg <= end <= 2^31 - 1", hipSuccess);
+    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)n_blocks * sizeof(cbc_dec_block_desc));
+    uint32_t *bn = (uint32_t *)malloc((size_t)n_blocks * 8), *biv = (uint32_t *)malloc((size_t)n_blocks * 8), *ioff = NULL;
+    if (!bl || !bn || !biv) { free(bl); free(bn); free(biv); return CBC_E_NOMEM; }
+    uint64_t in0 = UINT64_MAX, in1 = 0, nrec = 0, need = 0;
+    uint32_t lo = UINT32_MAX, hi = 0, nl0 = 0;                  /* depth: the intervals the call's blocks reach */
+    const char *bad = NULL;
+    for (uint32_t b = 0; b < n_blocks && !bad; b++) {          /* no sums of caller values that could wrap */
+        const cbc_dec_block_desc *d = &blocks[b];
+        if (d->seq_stride != stride || d->in_off > in_bytes || d->in_bytes > in_bytes - d->in_off || d->n_reads > CBC_MAX_BLOCK_READS) {
+            bad = "targets decode: block out of range of `in`, or strides differ"; break; }
+        if (block_contig[b] >= n_contigs || contig_name_off[block_contig[b]] >= names_bytes) { bad = "targets decode: a block's contig or its name lies outside the tables"; break; }
+        const uint32_t off = contig_name_off[block_contig[b]];
+        const size_t nl = strnlen(names + off, names_bytes - off);
+        if (nl == names_bytes - off || nl < 1 || nl > CBC_SAM_MAX_NAME || memchr(names + off, '\t', nl) || memchr(names + off, '\n', nl)) {
+            bad = "targets decode: a contig name is empty, unterminated, longer than 255 bytes or holds a tab or a newline"; break; }
+        if (window_start[b] > CBC_SAM_MAX_POS) { bad = "targets decode: a block starts past POS 2^31 - 1"; break; }
+        const uint32_t f = t->block_iv[2 * b], c = t->block_iv[2 * b + 1];
+        if (f > t->n_iv || c > t->n_iv - f) { bad = "targets decode: a block's interval range lies outside the table"; break; }
+        if (depth && block_contig[b] != block_contig[0]) { bad = "targets decode: a depth call takes the blocks of one contig"; break; }
+        if (c) { if (f < lo) lo = f; if (f + c > hi) hi = f + c; }
+        bn[2 * b] = off; bn[2 * b + 1] = (uint32_t)nl;
+        if (b == 0) nl0 = (uint32_t)nl;
+        if (d->in_off < in0) in0 = d->in_off;
+        if (d->in_off + d->in_bytes > in1) in1 = d->in_off + d->in_bytes;
+        bl[b] = *d;
+        bl[b].rec_base = nrec; bl[b].seq_base = nrec * stride;
+        nrec += d->n_reads;
+        need += (uint64_t)d->n_reads * (sam ? 35ull + nl + stride : stride + 1ull);
+    }
+    if (!bad && depth && nrec > 0x3fffffffull) bad = "targets decode: more than 2^30 - 1 reads in one depth call";
+    if (bad) { free(bl); free(bn); free(biv); return set_err(ctx, CBC_E_ARG, bad, hipSuccess); }
+    if (nrec == 0 || (depth && lo >= hi)) { free(bl); free(bn); free(biv); return CBC_OK; }   /* no read, or none that reaches an interval */
+    for (uint32_t b = 0; b < n_blocks; b++) bl[b].in_off -= in0;
+    targets_req tq = { t->iv, t->n_iv, t->block_iv, NULL };
+    depth_req dq = { exclude_flags, n_runs };
+    if (depth) {
+        /* the contig's intervals [lo, hi): disjoint, ascending and not touching (they are merged); block ranges relative to
+         * lo; the slots of the compressed coordinate, one spare behind each interval */
+        const uint32_t n = hi - lo;
+        ioff = (uint32_t *)malloc(((size_t)n + 1) * 4);
+        if (!ioff) { free(bl); free(bn); free(biv); return CBC_E_NOMEM; }
+        uint64_t run = 0;
+        for (uint32_t i = 0; i < n && !bad; i++) {
+            const uint32_t *p = t->iv + 2 * (size_t)(lo + i);
+            if (i && p[0] <= p[-1] + 1u) bad = "targets decode: the intervals of a depth call are not ascending and apart";
+            ioff[i] = (uint32_t)run;
+            run += (uint64_t)(p[1] - p[0]) + 2u;
+        }
+        ioff[n] = (uint32_t)run;                                /* <= 2^31 + 2^24 */
+        if (bad) { free(bl); free(bn); free(biv); free(ioff); return set_err(ctx, CBC_E_ARG, bad, hipSuccess); }
+        for (uint32_t b = 0; b < n_blocks; b++) {
+            const uint32_t c = t->block_iv[2 * b + 1];
+            biv[2 * b] = c ? t->block_iv[2 * b] - lo : 0u; biv[2 * b + 1] = c;
+        }
+        tq.iv = t->iv + 2 * (size_t)lo; tq.n_iv = n; tq.block_iv = biv; tq.iv_off = ioff;
+        need = (2u * nrec + 2ull * n - 1u) * (nl0 + 34ull);     /* K reads, n intervals: at most 2K + 2n - 1 runs */
+    }
+    region_req rg = { window_start, 1u, UINT64_MAX, t->smax, text, text_cap < need ? text_cap : need, text_bytes, n_reads,
+                      sam ? bn : NULL, depth ? (const uint8_t *)names + bn[0] : (const uint8_t *)names, depth ? nl0 : names_bytes, 1,
+                      depth ? &dq : NULL, &tq };
+    int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
+                                nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
+    free(bl); free(bn); free(biv); free(ioff);
+    return rc;
+}
+
+API int cbc_gpu_last_targets_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *scan_ms, float *text_ms)
+{
+    if (!ctx || !decode_ms || !filter_ms || !scan_ms || !text_ms || !ctx->have_targets_timing) return CBC_E_ARG;
+    const int d = ctx->have_targets_timing == 2;
+    HIPCHK(hipEventSynchronize(ctx->ev_rg[d ? 4 : 3]), "hipEventSynchronize");
+    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(filter_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
+    *scan_ms = 0.0f;
+    if (d) HIPCHK(hipEventElapsedTime(scan_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(text_ms, ctx->ev_rg[d ? 3 : 2], ctx->ev_rg[d ? 4 : 3]), "hipEventElapsedTime");
     return CBC_OK;
 }
 

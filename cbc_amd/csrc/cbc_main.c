@@ -40,7 +40,10 @@ static void usage(const char *p)
             "usage: %s -c [1] <in.sam> <out.cbc> <ref.fa>   compress the reads of a position-sorted SAM\n"
             "       %s -d|-x <in.cbc> <out.txt> <ref.fa>    reconstruct the reads, one per line\n"
             "         --region NAME[:BEG[-END]] (decode only the reads overlapping a locus, 1-based inclusive as in samtools;\n"
-            "                                    block containers of short reads, one device)\n"
+            "                                    block containers of short reads, one device; given more than once: the union of\n"
+            "                                    the loci in one pass, every read once -- earlier versions kept only the last one)\n"
+            "         --regions-file FILE (BED: chrom, start, end, 0-based half-open; with or without --region; the reads, --sam lines or\n"
+            "                              --depth runs of the merged intervals; contigs the container does not list select nothing)\n"
             "         --sam (write SAM instead of bare reads: @HD, one @SQ per contig, then per read FLAG, RNAME, POS and SEQ;\n"
             "                QNAME, MAPQ, CIGAR, mate fields and QUAL are not stored and come out as * 255 * * 0 0 *; the text is\n"
             "                assembled on the device; alone or with --region; block containers of short reads, one device)\n"
@@ -429,13 +432,18 @@ int cbc_cli_decompress_region(const char *in, const char *out, const char *ref, 
 int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int verbose);
 int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude, int verbose);
 
+int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                               const char *bed_path, uint32_t output, uint32_t exclude, int verbose);
+
 int main(int argc, char **argv)
 {
     const char *files[3] = { 0, 0, 0 };
     int nfiles = 0, mode = 0 /* 0 none, 1 compress, 2 decompress */, device = 0, var_length = 0, threads = 0, verbose = 0, compat = 0, long_reads = 0, device_parse = 0, want_rccl = 0;
     int devs[CBC_MAX_DEVICES] = { 0 }, ndev = 0;
     uint32_t block_reads = 0;
-    const char *region = NULL;
+    const char *region = NULL, *regions_file = NULL;
+    const char **regions = (const char **)calloc((size_t)argc, sizeof(char *));   /* every --region, in order */
+    uint32_t n_regions = 0;
     int sam_out = 0, depth_out = 0, depth_excl_given = 0;
     uint32_t depth_exclude = 0;
     g_main_t0 = now_s();
@@ -456,7 +464,8 @@ int main(int argc, char **argv)
         }
         if (!strcmp(a, "--threads") && i + 1 < argc) { threads = atoi(argv[++i]); if (threads < 0) threads = 0; continue; }
         if (!strcmp(a, "--verbose")) { verbose = 1; continue; }
-        if (!strcmp(a, "--region") && i + 1 < argc) { region = argv[++i]; continue; }
+        if (!strcmp(a, "--region") && i + 1 < argc) { region = argv[++i]; if (regions) regions[n_regions++] = region; continue; }
+        if (!strcmp(a, "--regions-file") && i + 1 < argc) { regions_file = argv[++i]; continue; }
         if (!strcmp(a, "--sam")) { sam_out = 1; continue; }
         if (!strcmp(a, "--depth")) { depth_out = 1; continue; }
         if (!strcmp(a, "--depth-exclude-flags") && i + 1 < argc) {
@@ -503,6 +512,9 @@ int main(int argc, char **argv)
         fprintf(stderr, "cbc: user@host:file download mode (src/main.c:306-326) is out of scope\n");
         return 1;
     }
+    if (!regions) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    if (regions_file && mode != 2) { fprintf(stderr, "cbc: --regions-file applies to decompression (-d / -x)\n"); return 1; }
+    if (regions_file && ndev > 1) { fprintf(stderr, "cbc: --regions-file decodes on one device; give a single --devices ordinal\n"); return 1; }
     if (region && mode != 2) { fprintf(stderr, "cbc: --region applies to decompression (-d / -x)\n"); return 1; }
     if (region && ndev > 1) { fprintf(stderr, "cbc: --region decodes on one device; give a single --devices ordinal\n"); return 1; }
     if (sam_out && mode != 2) { fprintf(stderr, "cbc: --sam applies to decompression (-d / -x)\n"); return 1; }
@@ -511,6 +523,10 @@ int main(int argc, char **argv)
     if (depth_out && sam_out) { fprintf(stderr, "cbc: --depth and --sam are two different outputs; give one of them\n"); return 1; }
     if (depth_out && ndev > 1) { fprintf(stderr, "cbc: --depth decodes on one device; give a single --devices ordinal\n"); return 1; }
     if (depth_excl_given && !depth_out) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
+    /* several --region or a BED file: their union in one pass; exactly one --region and no file: the single-region paths */
+    if (regions_file || n_regions > 1)
+        return cbc_cli_decompress_targets(files[0], files[1], files[2], device, regions, n_regions, regions_file,
+                                          depth_out ? CBC_TARGETS_DEPTH : sam_out ? CBC_TARGETS_SAM : CBC_TARGETS_READS, depth_exclude, verbose);
     if (depth_out) return cbc_cli_decompress_depth(files[0], files[1], files[2], device, region, depth_exclude, verbose);
     if (sam_out) return cbc_cli_decompress_sam(files[0], files[1], files[2], device, region, verbose);
     if (region) return cbc_cli_decompress_region(files[0], files[1], files[2], device, region, verbose);

@@ -1782,6 +1782,43 @@ static int region_number(const char *s, size_t n, uint64_t *v)
     return 0;
 }
 
+/* the block index, checked in one bounded pass: contigs in file order, positions in order within a contig (the packer
+ * writes nothing else); then contig c's run of blocks [c0, c1) (0, 0: it has none).  -1: the index is out of order */
+static int region_contig_run(const cbc_unpack_plan *u, uint32_t c, uint32_t *r0, uint32_t *r1)
+{
+    uint32_t c0 = u->n_blocks, c1 = u->n_blocks;
+    for (uint32_t b = 0; b < u->n_blocks; b++) {
+        const uint32_t cb = u->block_contig[b];
+        if (b > 0 && (cb < u->block_contig[b - 1] || (cb == u->block_contig[b - 1] && u->window_start[b] < u->window_start[b - 1])))
+            return -1;
+        if (cb == c && c0 == u->n_blocks) c0 = b;
+        if (cb == c) c1 = b + 1;
+    }
+    if (c0 == u->n_blocks) c0 = c1 = 0;
+    *r0 = c0; *r1 = c1;
+    return 0;
+}
+
+/* Span bound.  In block mode the decoder takes nDel as one symbol of the L0-symbol indel-count alphabet (indel_counts,
+ * cbc_decode_body.h) and nIns >= 0, so span = rl + nDel - nIns <= max_read_len + L0 - 1 for every read it reconstructs.
+ * The packer itself accepts any nDel up to 0xffff (tokenise_record, cbc_pack.c), but the encoder codes nDel & 0xff as that
+ * symbol and fails the block with CBC_ST_ASSERT when it is >= L0 (dense_code, cbc_encode_body.h): a container holds no
+ * record whose decoded nDel reaches L0, and the decoder refuses a read longer than the row (rl <= seq_stride).  The span
+ * decode checks the bound on every read (CBC_ST_SPAN), so a crafted payload cannot slip a read past the selection. */
+static uint32_t region_smax(const cbc_unpack_plan *u) { return u->max_read_len + u->read_length - 1u; }
+
+/* the selection rule of include/cbc_host.h over the contig's run [c0, c1): the blocks [b0, b1) that can hold a read
+ * overlapping [beg, end] */
+static void region_pick(const cbc_unpack_plan *u, uint32_t c0, uint32_t c1, uint64_t beg, uint64_t end, uint32_t smax,
+                        uint32_t *p0, uint32_t *p1)
+{
+    uint32_t b1 = c0, b0 = c0;
+    while (b1 < c1 && u->window_start[b1] + 1u <= end) b1++;                   /* F(b) <= END */
+    while (b0 + 1 < c1 && u->window_start[b0 + 1] + 1u + smax < beg + 1u) b0++;  /* F(next(b)) >= BEG - SMAX + 1 */
+    if (b0 > b1) b0 = b1;
+    *p0 = b0; *p1 = b1;
+}
+
 API int cbc_unpack_region(const cbc_unpack_plan *u, const char *region, cbc_region_sel *sel, char *errbuf, size_t errlen)
 {
     if (!u || !region || !sel) return CBC_E_ARG;
@@ -1813,28 +1850,11 @@ API int cbc_unpack_region(const cbc_unpack_plan *u, const char *region, cbc_regi
     const uint64_t clen = u->contig_len[c];
     if (end > clen) end = clen;
     if (beg > end) return region_err(errbuf, errlen, "region \"%.*s\" begins past the end of its contig", region, ilen);
-    /* the block index, checked in one bounded pass: contigs in file order, positions in order within a contig (the packer
-     * writes nothing else); then the contig's run of blocks [c0, c1) */
-    uint32_t c0 = u->n_blocks, c1 = u->n_blocks;
-    for (uint32_t b = 0; b < u->n_blocks; b++) {
-        const uint32_t cb = u->block_contig[b];
-        if (b > 0 && (cb < u->block_contig[b - 1] || (cb == u->block_contig[b - 1] && u->window_start[b] < u->window_start[b - 1])))
-            return region_err(errbuf, errlen, "corrupt container: the block index is not in contig and position order%.*s", "", 0);
-        if (cb == (uint32_t)c && c0 == u->n_blocks) c0 = b;
-        if (cb == (uint32_t)c) c1 = b + 1;
-    }
-    if (c0 == u->n_blocks) c0 = c1 = 0;
-    /* Span bound.  In block mode the decoder takes nDel as one symbol of the L0-symbol indel-count alphabet (indel_counts,
-     * cbc_decode_body.h) and nIns >= 0, so span = rl + nDel - nIns <= max_read_len + L0 - 1 for every read it reconstructs.
-     * The packer itself accepts any nDel up to 0xffff (tokenise_record, cbc_pack.c), but the encoder codes nDel & 0xff as that
-     * symbol and fails the block with CBC_ST_ASSERT when it is >= L0 (dense_code, cbc_encode_body.h): a container holds no
-     * record whose decoded nDel reaches L0, and the decoder refuses a read longer than the row (rl <= seq_stride).  The span
-     * decode checks the bound on every read (CBC_ST_SPAN), so a crafted payload cannot slip a read past the selection. */
-    const uint32_t smax = u->max_read_len + u->read_length - 1u;
-    uint32_t b1 = c0, b0 = c0;
-    while (b1 < c1 && u->window_start[b1] + 1u <= end) b1++;                   /* F(b) <= END */
-    while (b0 + 1 < c1 && u->window_start[b0 + 1] + 1u + smax < beg + 1u) b0++;  /* F(next(b)) >= BEG - SMAX + 1 */
-    if (b0 > b1) b0 = b1;
+    uint32_t c0, c1, b0, b1;
+    if (region_contig_run(u, (uint32_t)c, &c0, &c1))
+        return region_err(errbuf, errlen, "corrupt container: the block index is not in contig and position order%.*s", "", 0);
+    const uint32_t smax = region_smax(u);
+    region_pick(u, c0, c1, beg, end, smax, &b0, &b1);
     sel->contig = (uint32_t)c; sel->b0 = b0; sel->b1 = b1; sel->smax = smax;
     sel->beg = beg; sel->end = end; sel->contig_len = clen;
     return 0;
@@ -1916,6 +1936,202 @@ API uint64_t cbc_unpack_depth_text_cap(const cbc_unpack_plan *u, uint32_t b0, ui
     uint64_t k = 0;
     for (uint32_t b = b0; b < b1; b++) k += u->blocks[b].n_reads;
     return k ? (2u * k - 1u) * ((uint64_t)nl + 34u) : 0u;
+}
+
+/* ---- a set of regions (include/cbc_host.h) ---- */
+typedef struct { uint32_t contig, beg, end; } target_raw;
+
+static int target_cmp(const void *a, const void *b)
+{
+    const target_raw *x = (const target_raw *)a, *y = (const target_raw *)b;
+    if (x->contig != y->contig) return x->contig < y->contig ? -1 : 1;
+    if (x->beg != y->beg) return x->beg < y->beg ? -1 : 1;
+    return x->end < y->end ? -1 : x->end > y->end;
+}
+
+static int target_push(target_raw **raw, uint64_t *n, uint64_t *cap, uint32_t contig, uint64_t beg, uint64_t end)
+{
+    if (*n == *cap) {
+        const uint64_t nc = *cap ? *cap * 2u : 1024u;
+        target_raw *p = (target_raw *)realloc(*raw, (size_t)nc * sizeof(target_raw));
+        if (!p) return CBC_E_NOMEM;
+        *raw = p; *cap = nc;
+    }
+    (*raw)[*n].contig = contig; (*raw)[*n].beg = (uint32_t)beg; (*raw)[*n].end = (uint32_t)end;   /* <= 2^31 - 1: checked */
+    (*n)++;
+    return 0;
+}
+
+static int bed_err(char *errbuf, size_t errlen, uint64_t line, const char *what)
+{
+    if (errbuf && errlen) snprintf(errbuf, errlen, "BED line %llu: %s", (unsigned long long)line, what);
+    return CBC_E_INPUT;
+}
+
+static inline int bed_sep(char c) { return c == ' ' || c == '\t'; }
+
+/* the lines of a BED text into raw[]; every read stays inside bed[0 .. len) */
+static int bed_parse(const cbc_unpack_plan *u, const char *bed, size_t len, target_raw **raw, uint64_t *n, uint64_t *cap,
+                     uint64_t *unselected, char *errbuf, size_t errlen)
+{
+    uint64_t line = 0;
+    for (size_t at = 0; at < len; ) {
+        const char *s = bed + at;
+        const char *nl = (const char *)memchr(s, '\n', len - at);
+        size_t ll = nl ? (size_t)(nl - s) : len - at;
+        at += ll + (nl ? 1u : 0u);
+        line++;
+        if (ll > CBC_BED_MAX_LINE) return bed_err(errbuf, errlen, line, "longer than 65536 bytes");
+        if (ll && s[ll - 1] == '\r') ll--;
+        if (ll == 0 || s[0] == '#' || (ll >= 5 && !memcmp(s, "track", 5)) || (ll >= 7 && !memcmp(s, "browser", 7))) continue;
+        size_t f0[3], fl[3], k = 0;
+        int nf = 0;
+        while (nf < 3) {
+            while (k < ll && bed_sep(s[k])) k++;
+            if (k == ll) break;
+            f0[nf] = k;
+            while (k < ll && !bed_sep(s[k])) k++;
+            fl[nf] = k - f0[nf];
+            nf++;
+        }
+        if (nf < 3) return bed_err(errbuf, errlen, line, "fewer than three columns (want chrom, start, end)");
+        uint64_t st = 0, en = 0;
+        if (region_number(s + f0[1], fl[1], &st) || region_number(s + f0[2], fl[2], &en))
+            return bed_err(errbuf, errlen, line, "malformed or overflowing number");
+        if (st > en) return bed_err(errbuf, errlen, line, "start is past end");
+        const int64_t c = region_contig(u, s + f0[0], fl[0]);
+        if (c == -2) return region_err(errbuf, errlen, "corrupt container: a contig name lies outside the name table%.*s", "", 0);
+        if (c < 0 || st == en || st >= u->contig_len[c]) { (*unselected)++; continue; }
+        if (en > u->contig_len[c]) en = u->contig_len[c];
+        const int rc = target_push(raw, n, cap, (uint32_t)c, st + 1u, en);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+API void cbc_targets_free(cbc_targets *t)
+{
+    if (!t) return;
+    free(t->iv); free(t->contig_first); free(t->contig_count); free(t->blocks); free(t->block_iv);
+    free(t->contig_blk_first); free(t->contig_blk_count); free(t);
+}
+
+API int cbc_unpack_targets(const cbc_unpack_plan *u, const char *const *regions, uint32_t n_regions, const char *bed, size_t bed_len,
+                           cbc_targets **out, char *errbuf, size_t errlen)
+{
+    if (!u || !out || (n_regions && !regions) || (bed_len && !bed)) return CBC_E_ARG;
+    *out = NULL;
+    if (errbuf && errlen) errbuf[0] = 0;
+    /* long-read containers, names and lengths the text cannot carry; contigs <= 2^31 - 1 bases, so coordinates fit 32 bits */
+    const int64_t hdr = cbc_unpack_sam_header(u, NULL, 0, errbuf, errlen);
+    if (hdr < 0) return (int)hdr;
+    if (!u->block_contig) return CBC_E_ARG;
+    target_raw *raw = NULL;
+    uint64_t n = 0, cap = 0;
+    int rc = 0;
+    cbc_targets *t = (cbc_targets *)calloc(1, sizeof *t);
+    if (!t) return CBC_E_NOMEM;
+    for (uint32_t r = 0; r < n_regions && !rc; r++) {
+        cbc_region_sel sel;
+        if (!regions[r]) { rc = CBC_E_ARG; break; }
+        rc = cbc_unpack_region(u, regions[r], &sel, errbuf, errlen);
+        if (!rc) rc = target_push(&raw, &n, &cap, sel.contig, sel.beg, sel.end);
+    }
+    if (!rc && bed) rc = bed_parse(u, bed, bed_len, &raw, &n, &cap, &t->bed_unselected, errbuf, errlen);
+    if (rc) goto fail;
+    t->n_input = n;
+    t->n_contigs = u->n_contigs;
+    t->smax = region_smax(u);
+    if (n) qsort(raw, (size_t)n, sizeof *raw, target_cmp);
+    /* merge in place: overlapping or adjacent intervals of a contig become one */
+    uint64_t m = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (m && raw[m - 1].contig == raw[i].contig && (uint64_t)raw[m - 1].end + 1u >= raw[i].beg) {
+            if (raw[i].end > raw[m - 1].end) raw[m - 1].end = raw[i].end;
+        } else raw[m++] = raw[i];
+    }
+    if (m > CBC_TARGETS_MAX_IV) {
+        rc = region_err(errbuf, errlen, "the set of regions has more than 2^24 intervals after merging%.*s", "", 0);
+        goto fail;
+    }
+    t->n_iv = (uint32_t)m;
+    {
+        const size_t nc = u->n_contigs ? u->n_contigs : 1u;
+        t->iv = (cbc_target_iv *)calloc(m ? (size_t)m : 1u, sizeof(cbc_target_iv));
+        t->contig_first = (uint32_t *)calloc(nc, 4); t->contig_count = (uint32_t *)calloc(nc, 4);
+        t->contig_blk_first = (uint32_t *)calloc(nc, 4); t->contig_blk_count = (uint32_t *)calloc(nc, 4);
+        t->blocks = (uint32_t *)calloc(u->n_blocks ? u->n_blocks : 1u, 4);
+        t->block_iv = (uint32_t *)calloc(u->n_blocks ? u->n_blocks : 1u, 8);
+        if (!t->iv || !t->contig_first || !t->contig_count || !t->contig_blk_first || !t->contig_blk_count || !t->blocks || !t->block_iv) {
+            rc = CBC_E_NOMEM; goto fail; }
+    }
+    for (uint64_t i = 0; i < m; i++) {
+        t->iv[i].beg = raw[i].beg; t->iv[i].end = raw[i].end;
+        if (t->contig_count[raw[i].contig]++ == 0) t->contig_first[raw[i].contig] = (uint32_t)i;
+    }
+    /* the blocks: per contig with intervals, the union of the runs the single-region rule picks (both ends of a run grow with
+     * the interval, so the union is made by appending), and per block the intervals its reads can reach */
+    for (uint32_t c = 0; c < u->n_contigs; c++) {
+        if (!t->contig_count[c]) continue;
+        uint32_t c0, c1;
+        if (region_contig_run(u, c, &c0, &c1)) {
+            rc = region_err(errbuf, errlen, "corrupt container: the block index is not in contig and position order%.*s", "", 0);
+            goto fail;
+        }
+        const cbc_target_iv *iv = t->iv + t->contig_first[c];
+        const uint32_t ni = t->contig_count[c];
+        t->contig_blk_first[c] = t->n_blocks;
+        uint32_t next = c0;
+        for (uint32_t i = 0; i < ni; i++) {
+            uint32_t b0, b1;
+            region_pick(u, c0, c1, iv[i].beg, iv[i].end, t->smax, &b0, &b1);
+            for (uint32_t b = b0 > next ? b0 : next; b < b1; b++) { t->blocks[t->n_blocks++] = b; next = b + 1; }
+        }
+        t->contig_blk_count[c] = t->n_blocks - t->contig_blk_first[c];
+        uint32_t lo = 0, hi = 0;                          /* both move forward with the block */
+        for (uint32_t k = t->contig_blk_first[c]; k < t->n_blocks; k++) {
+            const uint32_t b = t->blocks[k];
+            const uint64_t F = u->window_start[b] + 1u;
+            const uint64_t reach = b + 1 < c1 ? u->window_start[b + 1] + 1u + t->smax : UINT64_MAX;
+            while (lo < ni && iv[lo].end < F) lo++;
+            if (hi < lo) hi = lo;
+            while (hi < ni && iv[hi].beg <= reach) hi++;
+            t->block_iv[2 * k] = t->contig_first[c] + lo; t->block_iv[2 * k + 1] = hi - lo;
+        }
+    }
+    free(raw);
+    *out = t;
+    return 0;
+fail:
+    free(raw);
+    cbc_targets_free(t);
+    return rc;
+}
+
+API uint64_t cbc_unpack_targets_text_cap(const cbc_unpack_plan *u, const cbc_targets *t, int sam)
+{
+    if (!u || !t || u->long_reads || !u->block_contig || !u->names || !u->contig_name_off) return 0;
+    uint64_t n = 0;
+    for (uint32_t k = 0; k < t->n_blocks; k++) {
+        const uint32_t b = t->blocks[k];
+        if (b >= u->n_blocks) return 0;
+        n += sam ? cbc_unpack_sam_text_cap(u, b, b + 1) : (uint64_t)u->blocks[b].n_reads * (u->seq_stride + 1ull);
+    }
+    return n;
+}
+
+API uint64_t cbc_unpack_targets_depth_cap(const cbc_unpack_plan *u, const cbc_targets *t, uint32_t contig)
+{
+    if (!u || !t || u->long_reads || !u->names || !u->contig_name_off || contig >= u->n_contigs || contig >= t->n_contigs) return 0;
+    const int64_t nl = sam_name_len(u, contig);
+    if (nl < 0 || !t->contig_count[contig] || !t->contig_blk_count[contig]) return 0;
+    uint64_t k = 0;
+    for (uint32_t i = 0; i < t->contig_blk_count[contig]; i++) {
+        const uint32_t b = t->blocks[t->contig_blk_first[contig] + i];
+        if (b >= u->n_blocks) return 0;
+        k += u->blocks[b].n_reads;
+    }
+    return (2u * k + 2ull * t->contig_count[contig] - 1u) * ((uint64_t)nl + 34u);
 }
 
 /* One reconstructed read per line (print_line, src/compression.c:16-40). */

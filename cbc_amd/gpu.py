@@ -76,6 +76,10 @@ class E2ETimes(ctypes.Structure):
                 ("h2d_bytes", ctypes.c_uint64), ("d2h_bytes", ctypes.c_uint64), ("n_chunks", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class GpuTargets(ctypes.Structure):
+    _fields_ = [("iv", ctypes.c_void_p), ("block_iv", ctypes.c_void_p), ("n_iv", ctypes.c_uint32), ("smax", ctypes.c_uint32)]
+
+
 class SamRegion(ctypes.Structure):
     _fields_ = [("beg", ctypes.c_uint64), ("end", ctypes.c_uint64), ("smax", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
@@ -228,6 +232,15 @@ def lib():
                                            ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                            ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.cbc_gpu_decode_targets.restype = ctypes.c_int
+        L.cbc_gpu_decode_targets.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                             ctypes.POINTER(host.LdsCaps), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(GpuTargets),
+                                             ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.cbc_gpu_last_targets_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_targets_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         L.cbc_gpu_last_depth_ms.restype = ctypes.c_int
         L.cbc_gpu_last_depth_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         if L.cbc_gpu_abi_version() != 1:
@@ -250,7 +263,7 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_decode_stream_blocks", "cbc_gpu_group_create", "cbc_gpu_group_gather", "cbc_gpu_group_destroy", "cbc_gpu_group_last_error",
            "cbc_gpu_stash_reset", "cbc_gpu_stash_bytes", "cbc_gpu_stash_fetch", "cbc_gpu_decode_region",
            "cbc_gpu_decode_blocks_span", "cbc_gpu_last_region_ms", "cbc_gpu_decode_sam", "cbc_gpu_last_sam_ms",
-           "cbc_gpu_decode_depth", "cbc_gpu_last_depth_ms"]
+           "cbc_gpu_decode_depth", "cbc_gpu_last_depth_ms", "cbc_gpu_decode_targets", "cbc_gpu_last_targets_ms"]
 
 
 class Encoder:
@@ -538,6 +551,65 @@ class Encoder:
         if results:
             return text, n_runs, n_kept, (np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE))
         return text
+
+    def decode_targets(self, plan: "host.UnpackPlan", targets, output="reads", exclude_flags=0, results=False, text_cap=None):
+        """The reads that overlap at least one interval of `targets` (a host.TargetSet of plan.targets()), in one decode of the
+        selected blocks (cbc_gpu_decode_targets).  output="reads": the text `cbc -x` writes for them, each read once, in
+        container order; "sam": plan.sam_header() + their alignment lines; "depth": the bedGraph of decode_depth restricted to
+        the set -- per merged interval what decode_depth(region=...) gives, appended in contig-table and position order, one
+        call and one decode per contig (reads with FLAG & exclude_flags != 0 left out).  An empty selection runs nothing on
+        the device.  With results=True returns (text, n_reads, n_runs, per-block decode results of the blocks decoded) and
+        lets a failed block pass (it contributes nothing); text_cap: size of the buffer of one call (default: the set's)."""
+        kind = {"reads": 0, "sam": 1, "depth": 2}[output]
+        hdr = plan.sam_header()                               # refuses what the text cannot carry, and long-read containers
+        self._targets_ms = None
+        self.last_targets_text_bytes = 0
+        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
+        pay = np.ascontiguousarray(plan.payloads)
+        names = np.ascontiguousarray(plan.names)
+        noff = np.ascontiguousarray(plan.contig_name_off, dtype=np.uint32)
+        iv = np.ascontiguousarray(targets.iv, dtype=np.uint32)
+        if kind == 2:
+            calls = [(int(targets.contig_blk_first[c]), int(targets.contig_blk_count[c]), targets.depth_cap[c])
+                     for c in range(targets.n_contigs) if targets.contig_blk_count[c]]
+        else:
+            calls = [(0, targets.n_blocks, targets.text_cap_sam if kind == 1 else targets.text_cap_reads)] if targets.n_blocks else []
+        out, n_reads, n_runs, allres = [], 0, 0, []
+        for k0, nb, cap in calls:
+            sel = np.ascontiguousarray(targets.blocks[k0:k0 + nb]).astype(np.int64)
+            blocks = np.ascontiguousarray(plan.blocks[sel])
+            ws = np.ascontiguousarray(plan.window_start[sel], dtype=np.uint64)
+            bc = np.ascontiguousarray(plan.block_contig[sel], dtype=np.uint32)
+            biv = np.ascontiguousarray(targets.block_iv[k0:k0 + nb], dtype=np.uint32)
+            cap = cap if text_cap is None else int(text_cap)
+            text = np.zeros(max(cap, 1), dtype=np.uint8)
+            res = np.zeros(nb, dtype=host.RESULT_DTYPE)
+            nbytes, nrd, nrn = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+            tg = GpuTargets(iv.ctypes.data, biv.ctypes.data, targets.n_iv, targets.smax)
+            rc = lib().cbc_gpu_decode_targets(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
+                                              ws.ctypes.data, bc.ctypes.data, names.ctypes.data, names.size, noff.ctypes.data,
+                                              plan.n_contigs, ctypes.byref(tg), kind, int(exclude_flags), text.ctypes.data, cap,
+                                              ctypes.byref(nbytes), ctypes.byref(nrd), ctypes.byref(nrn), res.ctypes.data)
+            self.last_targets_text_bytes += int(nbytes.value)
+            if rc != 0 and not (results and rc == -4):
+                self._check(rc, "cbc_gpu_decode_targets")
+            v = [ctypes.c_float() for _ in range(4)]
+            if lib().cbc_gpu_last_targets_ms(self._ctx, *[ctypes.byref(x) for x in v]) == 0:
+                ms = tuple(float(x.value) for x in v)
+                self._targets_ms = ms if self._targets_ms is None else tuple(a + b for a, b in zip(self._targets_ms, ms))
+            out.append(text[:int(nbytes.value)].tobytes() if rc in (0, -4) else b"")
+            n_reads += int(nrd.value); n_runs += int(nrn.value); allres.append(res)
+        text = (hdr if kind == 1 else b"") + b"".join(out)
+        if results:
+            return text, n_reads, n_runs, (np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE))
+        return text
+
+    def last_targets_ms(self):
+        """(decode, count + scan or mark, depth scan + compact or 0, text) kernel milliseconds of the last decode_targets,
+        summed over its calls."""
+        if getattr(self, "_targets_ms", None) is None:
+            raise CbcGpuError("no decode_targets has run on the device")
+        return self._targets_ms
 
     def last_depth_ms(self, _one=False):
         """(decode, mark, scan + compact, text) kernel milliseconds of the last decode_depth, summed over its calls."""

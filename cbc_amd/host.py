@@ -90,6 +90,15 @@ class UnpackPlanC(ctypes.Structure):
                 ("contig_name_off", ctypes.POINTER(ctypes.c_uint32)), ("contig_len", ctypes.POINTER(ctypes.c_uint64))]
 
 
+class TargetsC(ctypes.Structure):
+    _fields_ = [("iv", ctypes.POINTER(ctypes.c_uint32)), ("n_iv", ctypes.c_uint32), ("n_contigs", ctypes.c_uint32),
+                ("contig_first", ctypes.POINTER(ctypes.c_uint32)), ("contig_count", ctypes.POINTER(ctypes.c_uint32)),
+                ("blocks", ctypes.POINTER(ctypes.c_uint32)), ("n_blocks", ctypes.c_uint32), ("smax", ctypes.c_uint32),
+                ("block_iv", ctypes.POINTER(ctypes.c_uint32)),
+                ("contig_blk_first", ctypes.POINTER(ctypes.c_uint32)), ("contig_blk_count", ctypes.POINTER(ctypes.c_uint32)),
+                ("bed_unselected", ctypes.c_uint64), ("n_input", ctypes.c_uint64)]
+
+
 class RegionSelC(ctypes.Structure):
     _fields_ = [("contig", ctypes.c_uint32), ("b0", ctypes.c_uint32), ("b1", ctypes.c_uint32), ("smax", ctypes.c_uint32),
                 ("beg", ctypes.c_uint64), ("end", ctypes.c_uint64), ("contig_len", ctypes.c_uint64)]
@@ -187,6 +196,15 @@ def lib():
         L.cbc_unpack_contig_blocks.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.POINTER(RegionSelC), ctypes.c_char_p, ctypes.c_size_t]
         L.cbc_unpack_depth_text_cap.restype = ctypes.c_uint64
         L.cbc_unpack_depth_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+        L.cbc_unpack_targets.restype = ctypes.c_int
+        L.cbc_unpack_targets.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.POINTER(ctypes.POINTER(TargetsC)), ctypes.c_char_p, ctypes.c_size_t]
+        L.cbc_targets_free.restype = None
+        L.cbc_targets_free.argtypes = [ctypes.POINTER(TargetsC)]
+        L.cbc_unpack_targets_text_cap.restype = ctypes.c_uint64
+        L.cbc_unpack_targets_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(TargetsC), ctypes.c_int]
+        L.cbc_unpack_targets_depth_cap.restype = ctypes.c_uint64
+        L.cbc_unpack_targets_depth_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(TargetsC), ctypes.c_uint32]
         _lib = L
     return _lib
 
@@ -431,6 +449,41 @@ class RegionSelection:
             self.contig, self.b0, self.b1, self.beg, self.end, self.smax)
 
 
+class TargetSet:
+    """What cbc_unpack_targets made of a list of regions and a BED text (copies; nothing of the C object is kept):
+    iv            (n_iv, 2) uint32: the merged intervals beg, end, 1-based inclusive, grouped per contig in table order
+    contig_first, contig_count      per contig: its part of iv
+    blocks        the selected blocks, ascending (the union of the single-region selections of the merged intervals)
+    block_iv      (n_blocks, 2) uint32: per selected block the first interval and the count of those its reads can reach
+    contig_blk_first, contig_blk_count   per contig: its part of blocks
+    smax, bed_unselected (BED lines that selected nothing), n_input (regions + BED lines taken, before merging),
+    text_cap_reads, text_cap_sam, depth_cap[c]: buffer sizes that always hold the output."""
+
+    def __init__(self, plan, ptr):
+        t = ptr.contents
+        n_iv, nb, nc = int(t.n_iv), int(t.n_blocks), int(t.n_contigs)
+        self.n_iv, self.n_blocks, self.n_contigs, self.smax = n_iv, nb, nc, int(t.smax)
+        self.iv = _np_view(t.iv, 2 * n_iv, np.uint32).copy().reshape(n_iv, 2) if n_iv else np.zeros((0, 2), dtype=np.uint32)
+        self.contig_first = _np_view(t.contig_first, nc, np.uint32).copy()
+        self.contig_count = _np_view(t.contig_count, nc, np.uint32).copy()
+        self.blocks = _np_view(t.blocks, nb, np.uint32).copy() if nb else np.zeros(0, dtype=np.uint32)
+        self.block_iv = _np_view(t.block_iv, 2 * nb, np.uint32).copy().reshape(nb, 2) if nb else np.zeros((0, 2), dtype=np.uint32)
+        self.contig_blk_first = _np_view(t.contig_blk_first, nc, np.uint32).copy()
+        self.contig_blk_count = _np_view(t.contig_blk_count, nc, np.uint32).copy()
+        self.bed_unselected, self.n_input = int(t.bed_unselected), int(t.n_input)
+        self.text_cap_reads = int(lib().cbc_unpack_targets_text_cap(plan._ptr, ptr, 0))
+        self.text_cap_sam = int(lib().cbc_unpack_targets_text_cap(plan._ptr, ptr, 1))
+        self.depth_cap = [int(lib().cbc_unpack_targets_depth_cap(plan._ptr, ptr, c)) for c in range(nc)]
+
+    def intervals(self):
+        """[(contig, beg, end)] of the merged intervals, in order."""
+        return [(c, int(b), int(e)) for c in range(self.n_contigs)
+                for b, e in self.iv[int(self.contig_first[c]):int(self.contig_first[c]) + int(self.contig_count[c])]]
+
+    def __repr__(self):
+        return "TargetSet(%d intervals, %d blocks, smax=%d)" % (self.n_iv, self.n_blocks, self.smax)
+
+
 class UnpackPlan:
     """Container + FASTA -> decode launch plan (cbc_unpack_plan_create).  Keeps the container bytes alive."""
 
@@ -476,6 +529,28 @@ class UnpackPlan:
             raise CbcInputError("cbc_unpack_region failed (%d): %s" % (rc, err.value.decode(errors="replace")))
         return RegionSelection(int(sel.contig), int(sel.b0), int(sel.b1), int(sel.beg), int(sel.end), int(sel.smax),
                                int(sel.contig_len))
+
+    def targets(self, regions=(), bed=None):
+        """The target set of the region strings `regions` (each NAME, NAME:BEG or NAME:BEG-END, as for region()) and the BED
+        text `bed` (bytes; None: no file): cbc_unpack_targets.  Returns a TargetSet; raises CbcInputError for what region()
+        refuses, for a BED line that is malformed (the message names the line) and for what sam_header() refuses."""
+        if isinstance(regions, (str, bytes)):
+            regions = [regions]
+        rs = [r.encode() if isinstance(r, str) else bytes(r) for r in regions]
+        arr = (ctypes.c_char_p * max(len(rs), 1))(*rs)
+        if isinstance(bed, str):
+            bed = bed.encode()
+        buf = np.frombuffer(bed, dtype=np.uint8).copy() if bed else None       # exactly the bytes: no terminator behind them
+        out = ctypes.POINTER(TargetsC)()
+        err = ctypes.create_string_buffer(512)
+        rc = lib().cbc_unpack_targets(self._ptr, arr, len(rs), buf.ctypes.data if buf is not None else None,
+                                      buf.size if buf is not None else 0, ctypes.byref(out), err, 512)
+        if rc != 0:
+            raise CbcInputError("cbc_unpack_targets failed (%d): %s" % (rc, err.value.decode(errors="replace")))
+        try:
+            return TargetSet(self, out)
+        finally:
+            lib().cbc_targets_free(out)
 
     def contig_blocks(self, contig: int):
         """The selection of contig `contig` as a whole (cbc_unpack_contig_blocks): its blocks, beg = 1, end = its length."""

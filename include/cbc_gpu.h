@@ -355,6 +355,38 @@ int  cbc_gpu_decode_depth(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes
  * sums, scans and change points; line count, scan and the text. */
 int  cbc_gpu_last_depth_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *text_ms);
 
+/* ---- decode of a set of regions -------------------------------------------------------------------
+ * `blocks` are the blocks a target set selects (cbc_unpack_targets of libcbc_host: the union of the single-region selections
+ * of its merged intervals), gathered by the caller with their window starts and contigs; they are decoded ONCE by the
+ * span-reporting decoder against t->smax.  t->iv holds n_iv intervals as pairs beg, end (1-based, inclusive, <= CBC_SAM_MAX_POS),
+ * grouped per contig, ascending, disjoint and not touching inside a contig; t->block_iv gives for block b of the call the first
+ * interval and the count of the intervals of its contig that its reads can reach.  A read is selected when it overlaps at
+ * least one interval: POS <= end and POS + span - 1 >= beg, the rule of cbc_gpu_decode_region.
+ *   CBC_TARGETS_READS  every selected read once, in the order of the blocks, the bytes cbc_gpu_decode_region writes for it
+ *   CBC_TARGETS_SAM    the same reads as the alignment lines cbc_gpu_decode_sam writes (no header)
+ *   CBC_TARGETS_DEPTH  the blocks of ONE contig: the bedGraph of cbc_gpu_decode_depth restricted to the intervals -- byte for
+ *                      byte the texts of its calls for each interval in turn; reads with FLAG & exclude_flags != 0 left out.
+ *                      Device memory follows the set (4 bytes per position inside the intervals), not the contig.
+ * *n_reads = reads selected (depth: reads counted), *n_runs = lines of a depth call.  A block that fails to decode contributes
+ * nothing and the call returns CBC_E_BLOCK; *text_bytes is also set when text_cap is too small (CBC_E_ARG, nothing copied). */
+#define CBC_TARGETS_READS 0u
+#define CBC_TARGETS_SAM   1u
+#define CBC_TARGETS_DEPTH 2u
+typedef struct cbc_gpu_targets {
+    const uint32_t *iv;          /* n_iv pairs beg, end */
+    const uint32_t *block_iv;    /* per block of the call: first interval, count */
+    uint32_t n_iv, smax;
+} cbc_gpu_targets;
+int  cbc_gpu_decode_targets(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                            uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                            const uint32_t *block_contig /* n_blocks */, const char *names, uint32_t names_bytes,
+                            const uint32_t *contig_name_off /* n_contigs */, uint32_t n_contigs, const cbc_gpu_targets *t,
+                            uint32_t output, uint32_t exclude_flags, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes,
+                            uint64_t *n_reads, uint64_t *n_runs, cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_targets: the span decode; the count pass + scan (depth: zeroing + mark); for
+ * the depth the tile sums, scans and change points (else 0); the text. */
+int  cbc_gpu_last_targets_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *scan_ms, float *text_ms);
+
 /* ---- whole-file stream ("compat" mode): the reference's own file format --------------------------------------
  * compress() / decompress(), src/compression.c:112-216: ONE arithmetic stream per file, models never reset.
  * `batch` is a cbc_host_batch packed with cbc_pack_opts.whole_file = 1: its `blocks` are SEGMENTS of the one

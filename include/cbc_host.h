@@ -223,6 +223,48 @@ uint64_t cbc_unpack_sam_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t
 int      cbc_unpack_contig_blocks(const cbc_unpack_plan *u, uint32_t contig, cbc_region_sel *sel, char *errbuf, size_t errlen);
 uint64_t cbc_unpack_depth_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig);
 
+/* Decode of a set of regions (the text comes from cbc_gpu_decode_targets).  The set is every string of
+ * `regions` (parsed, clamped and refused exactly as cbc_unpack_region does) plus the lines of the BED text `bed` (bed_len bytes,
+ * need not end in a newline or a NUL; NULL: none).  BED: fields separated by tabs or runs of spaces, at least `chrom start0 end0`
+ * (0-based, half-open), further columns ignored; empty lines and lines starting with '#', "track" or "browser" are skipped; CRLF
+ * line ends are taken; end0 past the contig's end is clamped.  A line with start0 == end0, a line naming a contig that is not in
+ * the container's table (the packer lists only contigs that have reads) and a line starting at or past its contig's end select
+ * nothing and are counted in bed_unselected.  start0 > end0, a number that is malformed or longer than 18 digits, fewer than
+ * three columns or a line longer than CBC_BED_MAX_LINE bytes is CBC_E_INPUT with a message naming the line (1-based).
+ * Per contig the intervals are sorted and merged where they overlap or touch (end + 1 >= next beg); contigs come in table order.
+ * More than CBC_TARGETS_MAX_IV intervals after merging are refused, and so is what cbc_unpack_sam_header refuses (long-read
+ * containers, names and lengths the text and the 32-bit device coordinates cannot carry).
+ *   iv[contig_first[c] .. + contig_count[c])   contig c's merged intervals, 1-based inclusive
+ *   blocks[n_blocks]                           the selected blocks, ascending: the union of the cbc_unpack_region selections
+ *                                              of the merged intervals (the same rule, the same index check)
+ *   block_iv[2 b], block_iv[2 b + 1]           for selected block b: first interval (index in iv) and count of the intervals
+ *                                              its reads can reach: end >= F(b) and beg <= F(next block of the contig) + smax
+ *   contig_blk_first / contig_blk_count        contig c's part of blocks[]
+ * Free with cbc_targets_free. */
+#define CBC_TARGETS_MAX_IV (1u << 24)
+#define CBC_BED_MAX_LINE   65536u
+typedef struct cbc_target_iv { uint32_t beg, end; } cbc_target_iv;
+typedef struct cbc_targets {
+    cbc_target_iv *iv;        uint32_t n_iv;
+    uint32_t       n_contigs;
+    uint32_t      *contig_first, *contig_count;
+    uint32_t      *blocks;    uint32_t n_blocks;
+    uint32_t       smax;
+    uint32_t      *block_iv;
+    uint32_t      *contig_blk_first, *contig_blk_count;
+    uint64_t       bed_unselected;       /* BED lines that selected nothing */
+    uint64_t       n_input;              /* regions + BED lines taken, before merging */
+} cbc_targets;
+int      cbc_unpack_targets(const cbc_unpack_plan *u, const char *const *regions, uint32_t n_regions, const char *bed, size_t bed_len,
+                            cbc_targets **out, char *errbuf, size_t errlen);
+void     cbc_targets_free(cbc_targets *t);
+/* text_cap that always holds the output of the set: the sum of the per-block bounds of the selected blocks (sam = 0: rlen + 1
+ * bytes per read; 1: the bound of cbc_unpack_sam_text_cap), and for the depth of contig c: K reads in its selected blocks and n
+ * intervals change the depth at no more than 2K + 2n positions, so at most 2K + 2n - 1 runs of len(name) + 34 bytes (0: no
+ * intervals or no blocks there, or a bad argument) */
+uint64_t cbc_unpack_targets_text_cap(const cbc_unpack_plan *u, const cbc_targets *t, int sam);
+uint64_t cbc_unpack_targets_depth_cap(const cbc_unpack_plan *u, const cbc_targets *t, uint32_t contig);
+
 int     cbc_unpack_plan_create(const uint8_t *blob, uint64_t len, const char *fasta, size_t fasta_len,
                                cbc_unpack_plan **out, char *errbuf, size_t errlen);
 void    cbc_unpack_plan_free(cbc_unpack_plan *u);
