@@ -470,3 +470,113 @@ int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref,
     cbc_unpack_plan_free(u);
     return 0;
 }
+
+/* `cbc -d|-x ... --bedcov [--region A ...] [--regions-file FILE] [--window N] [--min-depth D]`: one line per query -- per
+ * --region, per BED line (unmerged, in input order), per contig when neither is given, or per window of those -- with the sum
+ * of the depth, the positions with depth >= D and the mean.  The numbers come from one
+ * cbc_gpu_decode_coverage per contig that has intervals and blocks; the text is formatted here, so that it comes out in input
+ * order across contigs.  12 bytes per query cross PCIe. */
+int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                              const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose)
+{
+    const double t0 = now2();
+    size_t blob_len = 0, fa_len = 0, bed_len = 0;
+    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
+    if (!blob || !fa) return 1;
+    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
+        fprintf(stderr, "cbc: --bedcov needs a block container; %s is a single-stream (--compat) file, which has no block index\n", in);
+        return 1;
+    }
+    char *bed = NULL;
+    if (bed_path && !(bed = slurp2(bed_path, &bed_len))) return 1;
+    char err[512];
+    cbc_unpack_plan *u = NULL;
+    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
+    free(fa);
+    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
+    cbc_queries *Q = NULL;
+    rc = cbc_unpack_queries(u, regions, n_regions, bed, bed_len, window, &Q, err, sizeof err);
+    if (rc) { fprintf(stderr, "cbc: --bedcov: %s\n", rc == CBC_E_INPUT && err[0] ? err : "query selection failed"); return 1; }
+    const cbc_targets *T = Q->targets;
+    const uint64_t nq = Q->n_q;
+    const uint32_t nb = T->n_blocks, nc = u->n_contigs;
+    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)(nb ? nb : 1) * sizeof *bl);
+    uint64_t *ws = (uint64_t *)malloc((size_t)(nb ? nb : 1) * 8);
+    uint32_t *bc = (uint32_t *)malloc((size_t)(nb ? nb : 1) * 4);
+    uint64_t *sum = (uint64_t *)calloc((size_t)(nq ? nq : 1), 8), *csum = (uint64_t *)malloc((size_t)(nq ? nq : 1) * 8);
+    uint32_t *cov = (uint32_t *)calloc((size_t)(nq ? nq : 1), 4), *ccov = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 4);
+    uint32_t *qq = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 8), *qi = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 4);
+    uint64_t *cfirst = (uint64_t *)calloc((size_t)nc + 2, 8);
+    if (!bl || !ws || !bc || !sum || !csum || !cov || !ccov || !qq || !qi || !cfirst) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    for (uint32_t k = 0; k < nb; k++) { const uint32_t b = T->blocks[k]; bl[k] = u->blocks[b]; ws[k] = u->window_start[b]; bc[k] = u->block_contig[b]; }
+    /* the queries that hold a position, grouped per contig (a counting sort: the order inside a contig stays the input's) */
+    for (uint64_t i = 0; i < nq; i++) if (Q->q[i].contig != CBC_QUERY_UNKNOWN && Q->q[i].end0 > Q->q[i].start0) cfirst[Q->q[i].contig + 2]++;
+    for (uint32_t c = 0; c < nc; c++) cfirst[c + 2] += cfirst[c + 1];
+    for (uint64_t i = 0; i < nq; i++) {
+        const cbc_query *x = &Q->q[i];
+        if (x->contig == CBC_QUERY_UNKNOWN || x->end0 == x->start0) continue;
+        const uint64_t at = cfirst[x->contig + 1]++;
+        qq[2 * at] = x->slot; qq[2 * at + 1] = x->end + 1u - x->beg; qi[at] = (uint32_t)i;
+    }                                                    /* now cfirst[c] .. cfirst[c + 1]: contig c's part */
+    const double t1 = now2();
+    double t_init = 0, t_dev = 0;
+    cbc_gpu_ctx *ctx = NULL;
+    uint64_t reads = 0;
+    uint32_t blocks_used = 0;
+    float ms[7] = { 0, 0, 0, 0, 0, 0, 0 };
+    const cbc_gpu_targets gt = { (const uint32_t *)T->iv, NULL, T->n_iv, T->smax };
+    for (uint32_t c = 0; c < nc && nb; c++) {
+        const uint32_t k0 = T->contig_blk_first[c], kn = T->contig_blk_count[c];
+        const uint64_t q0 = cfirst[c], qn = cfirst[c + 1] - cfirst[c];
+        if (!kn || !qn || !T->contig_count[c]) continue;   /* no block can hold a read of the contig's intervals: zeros */
+        const double a = now2();
+        if (!ctx) {
+            rc = cbc_gpu_init(device, &ctx);
+            if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
+            if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+            t_init = now2() - a;
+        }
+        const double b = now2();
+        cbc_gpu_targets g = gt;
+        g.block_iv = T->block_iv + 2 * (size_t)k0;
+        uint64_t nr = 0;
+        rc = cbc_gpu_decode_coverage(ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
+                                     u->contig_name_off, u->n_contigs, &g, T->contig_first[c], T->contig_count[c], qq + 2 * q0,
+                                     (uint32_t)qn, exclude, min_depth, csum + q0, ccov + q0, &nr, NULL);
+        if (rc) { fprintf(stderr, "cbc: coverage failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+        t_dev += now2() - b;
+        if (verbose) {
+            float m7[7];
+            if (cbc_gpu_last_coverage_ms(ctx, &m7[0], &m7[1], &m7[2], &m7[3], &m7[4], &m7[5], &m7[6]) == 0) for (int i = 0; i < 7; i++) ms[i] += m7[i];
+        }
+        for (uint64_t k = q0; k < q0 + qn; k++) { sum[qi[k]] = csum[k]; cov[qi[k]] = ccov[k]; }
+        reads += nr; blocks_used += kn;
+    }
+    if (ctx) cbc_gpu_shutdown(ctx);
+    const double t2 = now2();
+    FILE *fo = fopen(out, "wb");
+    if (!fo) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    for (uint64_t i = 0; i < nq; i++) {
+        const cbc_query *x = &Q->q[i];
+        char mean[32];
+        (void)cbc_coverage_mean(sum[i], x->end0 - x->start0, mean);
+        const char *nm = x->contig == CBC_QUERY_UNKNOWN ? bed + x->name_off : u->names + u->contig_name_off[x->contig];
+        const int nl = x->contig == CBC_QUERY_UNKNOWN ? (int)x->name_len : (int)strlen(nm);
+        if (fprintf(fo, "%.*s\t%llu\t%llu\t%llu\t%u\t%s\n", nl, nm, (unsigned long long)x->start0, (unsigned long long)x->end0,
+                    (unsigned long long)sum[i], cov[i], mean) < 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    }
+    if (fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    printf("coverage of %llu queries from %llu reads in %u of %u blocks\n", (unsigned long long)nq, (unsigned long long)reads, blocks_used, u->n_blocks);
+    if (verbose) {
+        printf("bedcov: %llu queries, %u intervals after merging, %u blocks selected, %llu BED lines selected nothing, window %llu, min depth %u, exclude flags 0x%x\n",
+               (unsigned long long)nq, T->n_iv, nb, (unsigned long long)T->bed_unselected, (unsigned long long)window, min_depth, exclude);
+        printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + coverage %.3f s, format + write %.3f s\n",
+               t1 - t0, t_init, t_dev, now2() - t2);
+        if (ctx) printf("kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, weights %.3f ms, weight scans %.3f ms, prefixes %.3f ms, lookup %.3f ms\n",
+                        ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6]);
+    }
+    free(bl); free(ws); free(bc); free(sum); free(csum); free(cov); free(ccov); free(qq); free(qi); free(cfirst); free(bed); free(blob);
+    cbc_queries_free(Q);
+    cbc_unpack_plan_free(u);
+    return 0;
+}

@@ -23,6 +23,7 @@
 #include "cbc_sam_body.h"
 #include "cbc_depth_body.h"
 #include "cbc_targets_body.h"
+#include "cbc_cov_body.h"
 #include "cbc_plan.h"
 #include "cbc_stream_body.h"
 #include "cbc_long_body.h"
@@ -143,6 +144,15 @@ __global__ void __launch_bounds__(64)
 cbc_targets_depth_count_kernel(cbc_tdepth_args A) { if (blockIdx.x < A.D.n_ttiles) cbc_targets_depth_count<WaveGPU>(A, blockIdx.x); }
 __global__ void __launch_bounds__(64)
 cbc_targets_depth_write_kernel(cbc_tdepth_args A) { cbc_targets_depth_write<WaveGPU>(A, blockIdx.x); }
+
+/* Per-query coverage summary (cbc_gpu_decode_coverage, cbc_cov_body.h), behind the mark / tile / scan / compact passes above:
+ * one wavefront per CBC_DEPTH_LINES runs weighs them and (after the scans) stores the prefixes, one lane per query looks up */
+__global__ void __launch_bounds__(64)
+cbc_cov_weights_kernel(cbc_cov_args A) { cbc_cov_weights<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_cov_apply_kernel(cbc_cov_args A) { cbc_cov_apply<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_cov_lookup_kernel(cbc_cov_args A) { cbc_cov_lookup<WaveGPU>(A, blockIdx.x); }
 
 /* Whole-file stream / general-form fallback (cbc_stream_body.h): one wavefront per stream.  Workgroup w codes streams
  * w, w + gridDim, ... with var table w of the pool, which it re-zeroes between streams. */
@@ -299,7 +309,7 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
 /* grow-only device buffer owned by the context: the host-buffer entry points keep their device arrays between calls
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
-enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_COUNT };
+enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_COUNT };
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
 struct cbc_gpu_ctx {
@@ -315,6 +325,8 @@ struct cbc_gpu_ctx {
     int have_sam_timing;           /* the same four events, recorded by cbc_gpu_decode_sam */
     int have_depth_timing;         /* all five, recorded by cbc_gpu_decode_depth */
     int have_targets_timing;       /* cbc_gpu_decode_targets: 1 = the four events of a reads / SAM call, 2 = the five of a depth call */
+    hipEvent_t ev_cov[4];          /* cbc_gpu_decode_coverage: behind ev_rg[3], after the weights, their scans, the apply and the lookup */
+    int have_cov_timing;
     int have_timing;
     int last_variant;              /* waves per SIMD of the encode build launched last */
     int n_cus;                     /* compute units of the device (block residency decides the kernel build) */
@@ -391,6 +403,8 @@ API int cbc_gpu_init(int device_ordinal, cbc_gpu_ctx **out)
         if (hipEventCreateWithFlags(&ctx->ev_chunk[k], hipEventDisableTiming) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     for (int k = 0; k < 5; k++)
         if (hipEventCreate(&ctx->ev_rg[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
+    for (int k = 0; k < 4; k++)
+        if (hipEventCreate(&ctx->ev_cov[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) != hipSuccess || cus <= 0) cus = 256;
@@ -419,6 +433,7 @@ API int cbc_gpu_shutdown(cbc_gpu_ctx *ctx)
     (void)hipEventDestroy(ctx->ev0); (void)hipEventDestroy(ctx->ev1);
     for (int k = 0; k < CBC_MAX_CHUNKS; k++) (void)hipEventDestroy(ctx->ev_chunk[k]);
     for (int k = 0; k < 5; k++) (void)hipEventDestroy(ctx->ev_rg[k]);
+    for (int k = 0; k < 4; k++) (void)hipEventDestroy(ctx->ev_cov[k]);
     for (int k = 0; k < CBC_N_KSTREAMS; k++) { (void)hipEventDestroy(ctx->ev_done[k]); (void)hipStreamDestroy(ctx->s_k[k]); }
     (void)hipStreamDestroy(ctx->s_copy);
     (void)hipStreamDestroy(ctx->stream);
@@ -989,7 +1004,11 @@ struct region_req {
     const depth_req *depth;
     /* a set of regions (cbc_gpu_decode_targets): tg != NULL, beg / end unused */
     const struct targets_req *tg;
+    /* per-query summary instead of the depth text (cbc_gpu_decode_coverage): cov != NULL, with depth and tg */
+    const struct cov_req *cov;
 };
+/* the queries (n_q pairs slot, len in the compressed coordinate), the depth that counts as covered, where the results go */
+struct cov_req { const uint32_t *q; uint32_t n_q, min_depth; uint64_t *sum; uint32_t *covered; };
 /* the interval table (n_iv pairs), per block its range of it, and for the depth the first slot of every interval in the
  * compressed coordinate (n_iv + 1 entries; NULL for reads / SAM) */
 struct targets_req { const uint32_t *iv; uint32_t n_iv; const uint32_t *block_iv; const uint32_t *iv_off; };
@@ -1014,6 +1033,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     const depth_req *depth = text ? rg->depth : NULL;
     /* coverage: tiles of the difference array (W + 1 words), change points (two per read at most), text tiles of the runs */
     const targets_req *tg = text ? rg->tg : NULL;
+    const cov_req *cov = depth && tg ? rg->cov : NULL;
     const uint64_t d_words = !depth ? 0u : tg ? tg->iv_off[tg->n_iv] : rg->end - rg->beg + 2u;
     const uint32_t n_tiles = (uint32_t)((d_words + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
     const uint32_t cp_cap = depth ? (uint32_t)(2u * n_recs + (tg ? 2u * (uint64_t)tg->n_iv : 0u)) : 0u;   /* + two per interval edge */
@@ -1066,6 +1086,16 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         NEED(A_TBIV, (uint64_t)n_blocks * 8, "hipMalloc block intervals");
         if (depth) NEED(A_TOFF, ((uint64_t)tg->n_iv + 1) * 4, "hipMalloc interval slots");
     }
+    if (cov) {
+        NEED(A_CVTILE, (uint64_t)n_ttiles * 3 * sizeof(cbc_block_result) + ((uint64_t)n_ttiles + 1) * 3 * 8, "hipMalloc coverage tiles");
+        if (arena_need(ctx, A_CVPRE, (uint64_t)cp_cap * 12 + 16, "hipMalloc coverage prefixes")) {
+            (void)hipGetLastError();
+            rc = set_err(ctx, CBC_E_NOMEM, "no device memory for the coverage prefixes (12 bytes per change point)", hipSuccess);
+            goto done;
+        }
+        NEED(A_CVQ, (uint64_t)cov->n_q * 8 + 16, "hipMalloc coverage queries");
+        NEED(A_CVOUT, (uint64_t)cov->n_q * 12 + 16, "hipMalloc coverage results");
+    }
     tm.alloc_s = wall_now() - T0;
     {
         uint8_t *d_in = (uint8_t *)ctx->arena[A_IN].p, *d_seq = (uint8_t *)ctx->arena[A_SEQ].p;
@@ -1089,6 +1119,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
             GO(hipMemcpyAsync(ctx->arena[A_TBIV].p, tg->block_iv, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D block intervals");
             if (depth) GO(hipMemcpyAsync(ctx->arena[A_TOFF].p, tg->iv_off, ((uint64_t)tg->n_iv + 1) * 4, hipMemcpyHostToDevice, sc), "H2D interval slots");
         }
+        if (cov) GO(hipMemcpyAsync(ctx->arena[A_CVQ].p, cov->q, (uint64_t)cov->n_q * 8, hipMemcpyHostToDevice, sc), "H2D coverage queries");
         GO(hipEventRecord(ctx->ev_done[0], sc), "hipEventRecord");       /* inputs are on the device */
         tm.h2d_bytes = in_bytes + (uint64_t)n_blocks * sizeof(cbc_dec_block_desc);
         cbc_chunk_plan P;
@@ -1154,6 +1185,33 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     hipLaunchKernelGGL(cbc_depth_compact_kernel, dim3(n_tiles), dim3(64), 0, ks, da);
                     GO(hipGetLastError(), "launch cbc_depth_compact_kernel");
                     GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+                    if (cov) {                                 /* weights, their scans, prefixes, lookup: no text */
+                        cbc_cov_args ca;
+                        memset(&ca, 0, sizeof ca);
+                        ca.cp_pos = da.cp_pos; ca.cp_dep = da.cp_dep; ca.cnt_off = da.cnt_off;
+                        ca.tile_wlo = (cbc_block_result *)ctx->arena[A_CVTILE].p; ca.tile_whi = ca.tile_wlo + n_ttiles; ca.tile_cov = ca.tile_whi + n_ttiles;
+                        uint64_t *woff = (uint64_t *)(ca.tile_cov + n_ttiles);
+                        ca.wlo_off = woff; ca.whi_off = woff + (n_ttiles + 1); ca.cov_off = woff + 2 * ((uint64_t)n_ttiles + 1);
+                        ca.pre_lo = (uint32_t *)ctx->arena[A_CVPRE].p; ca.pre_hi = ca.pre_lo + cp_cap; ca.pre_cov = ca.pre_hi + cp_cap;
+                        ca.q = (const uint32_t *)ctx->arena[A_CVQ].p; ca.sum = (uint32_t *)ctx->arena[A_CVOUT].p; ca.covered = ca.sum + 2 * (uint64_t)cov->n_q;
+                        ca.cp_cap = cp_cap; ca.n_tiles = n_tiles; ca.n_ttiles = n_ttiles; ca.n_q = cov->n_q; ca.min_depth = cov->min_depth;
+                        ca.slots = (uint32_t)d_words;
+                        hipLaunchKernelGGL(cbc_cov_weights_kernel, dim3(n_ttiles), dim3(64), 0, ks, ca);
+                        GO(hipGetLastError(), "launch cbc_cov_weights_kernel");
+                        GO(hipEventRecord(ctx->ev_cov[0], ks), "hipEventRecord");
+                        hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ca.tile_wlo, woff, n_ttiles);
+                        hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ca.tile_whi, woff + (n_ttiles + 1), n_ttiles);
+                        hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ca.tile_cov, woff + 2 * ((uint64_t)n_ttiles + 1), n_ttiles);
+                        GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+                        GO(hipEventRecord(ctx->ev_cov[1], ks), "hipEventRecord");
+                        hipLaunchKernelGGL(cbc_cov_apply_kernel, dim3(n_ttiles), dim3(64), 0, ks, ca);
+                        GO(hipGetLastError(), "launch cbc_cov_apply_kernel");
+                        GO(hipEventRecord(ctx->ev_cov[2], ks), "hipEventRecord");
+                        hipLaunchKernelGGL(cbc_cov_lookup_kernel, dim3((cov->n_q + 63u) / 64u), dim3(64), 0, ks, ca);
+                        GO(hipGetLastError(), "launch cbc_cov_lookup_kernel");
+                        GO(hipEventRecord(ctx->ev_cov[3], ks), "hipEventRecord");
+                        ctx->have_cov_timing = 1; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0; ctx->have_sam_timing = 0; ctx->have_region_timing = 0;
+                    } else {
                     if (tg) hipLaunchKernelGGL(cbc_targets_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, ta);
                     else hipLaunchKernelGGL(cbc_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
                     GO(hipGetLastError(), "launch cbc_depth_count_kernel");
@@ -1164,6 +1222,8 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     GO(hipGetLastError(), "launch cbc_depth_write_kernel");
                     GO(hipEventRecord(ctx->ev_rg[4], ks), "hipEventRecord");
                     ctx->have_depth_timing = tg ? 0 : 1; ctx->have_targets_timing = tg ? 2 : 0; ctx->have_sam_timing = 0; ctx->have_region_timing = 0;
+                    ctx->have_cov_timing = 0;
+                    }
                 } else if (tg) {                               /* a set of regions: reads or SAM, the same three steps */
                     cbc_targets_args ta;
                     memset(&ta, 0, sizeof ta);
@@ -1181,7 +1241,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     else hipLaunchKernelGGL(cbc_targets_write_kernel, dim3(n_blocks), dim3(64 * CBC_REGION_WAVES), 0, ks, ta);
                     GO(hipGetLastError(), "launch cbc_targets_write_kernel");
                     GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                    ctx->have_targets_timing = 1; ctx->have_sam_timing = 0; ctx->have_region_timing = 0; ctx->have_depth_timing = 0;
+                    ctx->have_targets_timing = 1; ctx->have_sam_timing = 0; ctx->have_region_timing = 0; ctx->have_depth_timing = 0; ctx->have_cov_timing = 0;
                 } else if (sam) {                              /* the same three steps with the SAM bodies */
                     cbc_sam_args sa;
                     memset(&sa, 0, sizeof sa);
@@ -1195,7 +1255,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     hipLaunchKernelGGL(cbc_sam_write_kernel, dim3(n_blocks), dim3(64 * CBC_SAM_WAVES), 0, ks, sa);
                     GO(hipGetLastError(), "launch cbc_sam_write_kernel");
                     GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                    ctx->have_sam_timing = 1; ctx->have_region_timing = 0; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0;
+                    ctx->have_sam_timing = 1; ctx->have_region_timing = 0; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0; ctx->have_cov_timing = 0;
                 } else {
                 hipLaunchKernelGGL(cbc_region_count_kernel, dim3(n_blocks), dim3(64), 0, ks, ra);
                 GO(hipGetLastError(), "launch cbc_region_count_kernel");
@@ -1205,7 +1265,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 hipLaunchKernelGGL(cbc_region_write_kernel, dim3(n_blocks), dim3(64 * CBC_REGION_WAVES), 0, ks, ra);
                 GO(hipGetLastError(), "launch cbc_region_write_kernel");
                 GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                ctx->have_region_timing = 1; ctx->have_sam_timing = 0; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0;
+                ctx->have_region_timing = 1; ctx->have_sam_timing = 0; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0; ctx->have_cov_timing = 0;
                 }
             }
             if (two_bit && k.r1 > k.r0) {
@@ -1239,7 +1299,11 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         if (two_bit) GO(hipMemcpyAsync(&got, ctx->arena[A_CNT].p, 8, hipMemcpyDeviceToHost, sc), "D2H counter");
         if (depth) {
             GO(hipMemcpyAsync(dctr, ctx->arena[A_DCTR].p, 16, hipMemcpyDeviceToHost, sc), "D2H depth counters");
-            GO(hipMemcpyAsync(&total, (uint64_t *)ctx->arena[A_OFF].p + n_ttiles, 8, hipMemcpyDeviceToHost, sc), "D2H text size");
+            if (!cov) GO(hipMemcpyAsync(&total, (uint64_t *)ctx->arena[A_OFF].p + n_ttiles, 8, hipMemcpyDeviceToHost, sc), "D2H text size");
+            else {                                             /* the numbers, not the track: 12 bytes per query */
+                GO(hipMemcpyAsync(cov->sum, ctx->arena[A_CVOUT].p, (uint64_t)cov->n_q * 8, hipMemcpyDeviceToHost, sc), "D2H coverage sums");
+                GO(hipMemcpyAsync(cov->covered, (uint64_t *)ctx->arena[A_CVOUT].p + cov->n_q, (uint64_t)cov->n_q * 4, hipMemcpyDeviceToHost, sc), "D2H coverage counts");
+            }
         } else if (text) {
             cnt = (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
             if (!cnt) { rc = CBC_E_NOMEM; goto done; }
@@ -1456,12 +1520,14 @@ API int cbc_gpu_last_depth_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms
 
 /* a set of regions: the selected blocks laid out afresh as for a region decode, the tables checked
  * on the host, then span decode + keep by the interval table + scan + text on the device (cbc_targets_body.h) */
-API int cbc_gpu_decode_targets(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+/* cov != NULL (cbc_gpu_decode_coverage): a depth call whose compressed coordinate is laid over the intervals
+ * [iv_first, iv_first + iv_count) -- the contig's, whether a block reaches them or not -- and that ends in the query passes */
+static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                                uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
                                const uint32_t *block_contig, const char *names, uint32_t names_bytes,
                                const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_gpu_targets *t, uint32_t output,
                                uint32_t exclude_flags, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_reads,
-                               uint64_t *n_runs, cbc_block_result *results)
+                               uint64_t *n_runs, cbc_block_result *results, const cov_req *cov, uint32_t iv_first, uint32_t iv_count)
 {
     if (!ctx || !blocks || !caps || !window_start || !block_contig || !names || !contig_name_off || !t || !text_bytes || !n_reads ||
         !n_runs || (text_cap && !text) || output > CBC_TARGETS_DEPTH) return CBC_E_ARG;
@@ -1496,6 +1562,8 @@ API int cbc_gpu_decode_targets(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
         const uint32_t f = t->block_iv[2 * b], c = t->block_iv[2 * b + 1];
         if (f > t->n_iv || c > t->n_iv - f) { bad = "targets decode: a block's interval range lies outside the table"; break; }
         if (depth && block_contig[b] != block_contig[0]) { bad = "targets decode: a depth call takes the blocks of one contig"; break; }
+        if (cov && c && (f < iv_first || f - iv_first > iv_count || c > iv_count - (f - iv_first))) {
+            bad = "coverage: a block's interval range lies outside the contig's intervals"; break; }
         if (c) { if (f < lo) lo = f; if (f + c > hi) hi = f + c; }
         bn[2 * b] = off; bn[2 * b + 1] = (uint32_t)nl;
         if (b == 0) nl0 = (uint32_t)nl;
@@ -1509,6 +1577,7 @@ API int cbc_gpu_decode_targets(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
     if (!bad && depth && nrec > 0x3fffffffull) bad = "targets decode: more than 2^30 - 1 reads in one depth call";
     if (bad) { free(bl); free(bn); free(biv); return set_err(ctx, CBC_E_ARG, bad, hipSuccess); }
     if (nrec == 0 || (depth && lo >= hi)) { free(bl); free(bn); free(biv); return CBC_OK; }   /* no read, or none that reaches an interval */
+    if (cov) { lo = iv_first; hi = iv_first + iv_count; }      /* the slots of the queries count from the contig's first interval */
     for (uint32_t b = 0; b < n_blocks; b++) bl[b].in_off -= in0;
     targets_req tq = { t->iv, t->n_iv, t->block_iv, NULL };
     depth_req dq = { exclude_flags, n_runs };
@@ -1526,6 +1595,8 @@ API int cbc_gpu_decode_targets(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
             run += (uint64_t)(p[1] - p[0]) + 2u;
         }
         ioff[n] = (uint32_t)run;                                /* <= 2^31 + 2^24 */
+        for (uint32_t i = 0; cov && i < cov->n_q && !bad; i++)   /* no query reaches past the slots */
+            if (cov->q[2 * i] > ioff[n] || cov->q[2 * i + 1] > ioff[n] - cov->q[2 * i]) bad = "coverage: a query lies outside the compressed coordinate";
         if (bad) { free(bl); free(bn); free(biv); free(ioff); return set_err(ctx, CBC_E_ARG, bad, hipSuccess); }
         for (uint32_t b = 0; b < n_blocks; b++) {
             const uint32_t c = t->block_iv[2 * b + 1];
@@ -1536,11 +1607,60 @@ API int cbc_gpu_decode_targets(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
     }
     region_req rg = { window_start, 1u, UINT64_MAX, t->smax, text, text_cap < need ? text_cap : need, text_bytes, n_reads,
                       sam ? bn : NULL, depth ? (const uint8_t *)names + bn[0] : (const uint8_t *)names, depth ? nl0 : names_bytes, 1,
-                      depth ? &dq : NULL, &tq };
+                      depth ? &dq : NULL, &tq, cov };
     int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
                                 nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
     free(bl); free(bn); free(biv); free(ioff);
     return rc;
+}
+
+API int cbc_gpu_decode_targets(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                               uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                               const uint32_t *block_contig, const char *names, uint32_t names_bytes,
+                               const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_gpu_targets *t, uint32_t output,
+                               uint32_t exclude_flags, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_reads,
+                               uint64_t *n_runs, cbc_block_result *results)
+{
+    return decode_targets_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
+                               n_contigs, t, output, exclude_flags, text, text_cap, text_bytes, n_reads, n_runs, results, NULL, 0u, 0u);
+}
+
+/* per-query coverage summary: the depth form of cbc_gpu_decode_targets up to the change points, then
+ * the weights, their scans, the prefixes and the lookup (cbc_cov_body.h); only the numbers come back */
+API int cbc_gpu_decode_coverage(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                                const uint32_t *block_contig, const char *names, uint32_t names_bytes,
+                                const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_gpu_targets *t,
+                                uint32_t iv_first, uint32_t iv_count, const uint32_t *q, uint32_t n_q, uint32_t exclude_flags,
+                                uint32_t min_depth, uint64_t *sum, uint32_t *covered, uint64_t *n_reads, cbc_block_result *results)
+{
+    if (!ctx || !t || !n_reads || (n_q && (!q || !sum || !covered))) return CBC_E_ARG;
+    *n_reads = 0;
+    if (n_q) { memset(sum, 0, (size_t)n_q * 8); memset(covered, 0, (size_t)n_q * 4); }
+    if (min_depth < 1 || n_q > (1u << 24) || iv_count < 1 || iv_first > t->n_iv || iv_count > t->n_iv - iv_first)
+        return set_err(ctx, CBC_E_ARG, "coverage wants min_depth >= 1, at most 2^24 queries and the contig's intervals inside the table", hipSuccess);
+    if (n_q == 0) return CBC_OK;
+    const cov_req cq = { q, n_q, min_depth, sum, covered };
+    uint64_t text_bytes = 0, n_runs = 0;
+    return decode_targets_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
+                               n_contigs, t, CBC_TARGETS_DEPTH, exclude_flags, NULL, 0, &text_bytes, n_reads, &n_runs, results, &cq,
+                               iv_first, iv_count);
+}
+
+/* kernel times of the most recent cbc_gpu_decode_coverage */
+API int cbc_gpu_last_coverage_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *weights_ms,
+                                 float *wscan_ms, float *apply_ms, float *lookup_ms)
+{
+    if (!ctx || !decode_ms || !mark_ms || !scan_ms || !weights_ms || !wscan_ms || !apply_ms || !lookup_ms || !ctx->have_cov_timing) return CBC_E_ARG;
+    HIPCHK(hipEventSynchronize(ctx->ev_cov[3]), "hipEventSynchronize");
+    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(mark_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(scan_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(weights_ms, ctx->ev_rg[3], ctx->ev_cov[0]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(wscan_ms, ctx->ev_cov[0], ctx->ev_cov[1]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(apply_ms, ctx->ev_cov[1], ctx->ev_cov[2]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(lookup_ms, ctx->ev_cov[2], ctx->ev_cov[3]), "hipEventElapsedTime");
+    return CBC_OK;
 }
 
 API int cbc_gpu_last_targets_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *scan_ms, float *text_ms)

@@ -51,7 +51,11 @@ static void usage(const char *p)
             "                  line per run of equal non-zero depth; a read covers POS .. POS + span - 1, the bases it deletes\n"
             "                  included; computed and formatted on the device; whole file, contig by contig, or with --region the\n"
             "                  window alone; block containers of short reads, one device; not with --sam)\n"
-            "         --depth-exclude-flags N (with --depth: leave out reads with FLAG & N != 0; default 0, samtools uses 0x704)\n"
+            "         --depth-exclude-flags N (with --depth or --bedcov: leave out reads with FLAG & N != 0; default 0, samtools uses 0x704)\n"
+            "         --bedcov (one line per --region and per BED line, unmerged and in input order -- per contig when neither is\n"
+            "                   given: NAME, start, end, sum of the depth, positions with depth >= D, mean depth with two decimals;\n"
+            "                   depth as for --depth; the numbers are computed on the device; not with --sam or --depth)\n"
+            "         --window N (with --bedcov: cut every query into windows of N bases)  --min-depth D (with --bedcov: default 1)\n"
             "options: -l (header read length = longest read)  --block-reads N (default 4096)  --device N (default 0)\n"
             "         --threads N (SAM parser threads, default one per CPU)  --verbose (stage times)\n"
             "         --compat (write the reference's own single-stream format; slow: one stream = one wavefront)\n"
@@ -434,6 +438,8 @@ int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, i
 
 int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                                const char *bed_path, uint32_t output, uint32_t exclude, int verbose);
+int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                              const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose);
 
 int main(int argc, char **argv)
 {
@@ -446,6 +452,9 @@ int main(int argc, char **argv)
     uint32_t n_regions = 0;
     int sam_out = 0, depth_out = 0, depth_excl_given = 0;
     uint32_t depth_exclude = 0;
+    int bedcov = 0, window_given = 0, min_depth_given = 0;
+    uint64_t cov_window = 0;
+    uint32_t cov_min_depth = 1;
     g_main_t0 = now_s();
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
@@ -473,6 +482,17 @@ int main(int argc, char **argv)
             const unsigned long v = strtoul(argv[++i], &e, 0);
             if (!e || *e || e == argv[i] || v > 0xfffful) { fprintf(stderr, "cbc: --depth-exclude-flags wants a FLAG mask in 0..65535 (decimal, 0x.. or 0..)\n"); return 1; }
             depth_exclude = (uint32_t)v; depth_excl_given = 1; continue;
+        }
+        if (!strcmp(a, "--bedcov")) { bedcov = 1; continue; }
+        if ((!strcmp(a, "--window") || !strcmp(a, "--min-depth")) && i + 1 < argc) {
+            const int w = a[2] == 'w';
+            char *e = NULL;
+            const char *v = argv[++i];
+            const unsigned long long x = strtoull(v, &e, 10);
+            if (v[0] < '0' || v[0] > '9' || !e || *e || strlen(v) > 18 || x < 1 || (!w && x > 0xffffffffull)) {
+                fprintf(stderr, w ? "cbc: --window wants a number of bases, 1 or more\n" : "cbc: --min-depth wants a depth in 1..4294967295\n"); return 1; }
+            if (w) { cov_window = x; window_given = 1; } else { cov_min_depth = (uint32_t)x; min_depth_given = 1; }
+            continue;
         }
         if (!strcmp(a, "--compat")) { compat = 1; continue; }
         if (!strcmp(a, "--long")) { long_reads = 1; continue; }
@@ -522,7 +542,14 @@ int main(int argc, char **argv)
     if (depth_out && mode != 2) { fprintf(stderr, "cbc: --depth applies to decompression (-d / -x)\n"); return 1; }
     if (depth_out && sam_out) { fprintf(stderr, "cbc: --depth and --sam are two different outputs; give one of them\n"); return 1; }
     if (depth_out && ndev > 1) { fprintf(stderr, "cbc: --depth decodes on one device; give a single --devices ordinal\n"); return 1; }
-    if (depth_excl_given && !depth_out) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
+    if ((window_given || min_depth_given) && !bedcov) { fprintf(stderr, "cbc: %s applies to --bedcov\n", window_given ? "--window" : "--min-depth"); return 1; }
+    if (bedcov && mode != 2) { fprintf(stderr, "cbc: --bedcov applies to decompression (-d / -x)\n"); return 1; }
+    if (bedcov && (sam_out || depth_out)) { fprintf(stderr, "cbc: --bedcov, --depth and --sam are different outputs; give one of them\n"); return 1; }
+    if (bedcov && ndev > 1) { fprintf(stderr, "cbc: --bedcov decodes on one device; give a single --devices ordinal\n"); return 1; }
+    if (depth_excl_given && !depth_out && !bedcov) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
+    if (bedcov)
+        return cbc_cli_decompress_bedcov(files[0], files[1], files[2], device, regions, n_regions, regions_file, cov_window, cov_min_depth,
+                                         depth_exclude, verbose);
     /* several --region or a BED file: their union in one pass; exactly one --region and no file: the single-region paths */
     if (regions_file || n_regions > 1)
         return cbc_cli_decompress_targets(files[0], files[1], files[2], device, regions, n_regions, regions_file,

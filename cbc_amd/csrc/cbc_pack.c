@@ -1962,6 +1962,27 @@ static int target_push(target_raw **raw, uint64_t *n, uint64_t *cap, uint32_t co
     return 0;
 }
 
+/* the unmerged query list of cbc_unpack_queries; NULL where only the set is wanted */
+typedef struct { cbc_query *q; uint64_t n, cap; } query_list;
+
+/* a query of a known contig: [beg, end] 1-based inclusive, beg == end + 1 when it holds no position */
+static int query_push(query_list *L, uint32_t contig, uint64_t beg, uint64_t end, size_t name_off, size_t name_len, uint64_t s0, uint64_t e0)
+{
+    if (!L) return 0;
+    if (L->n == L->cap) {
+        const uint64_t nc = L->cap ? L->cap * 2u : 1024u;
+        cbc_query *p = (cbc_query *)realloc(L->q, (size_t)nc * sizeof(cbc_query));
+        if (!p) return CBC_E_NOMEM;
+        L->q = p; L->cap = nc;
+    }
+    cbc_query *x = &L->q[L->n++];
+    memset(x, 0, sizeof *x);
+    x->contig = contig; x->beg = (uint32_t)beg; x->end = (uint32_t)end;
+    x->name_off = (uint32_t)name_off; x->name_len = (uint32_t)name_len;
+    x->start0 = contig == CBC_QUERY_UNKNOWN ? s0 : beg - 1u; x->end0 = contig == CBC_QUERY_UNKNOWN ? e0 : end;
+    return 0;
+}
+
 static int bed_err(char *errbuf, size_t errlen, uint64_t line, const char *what)
 {
     if (errbuf && errlen) snprintf(errbuf, errlen, "BED line %llu: %s", (unsigned long long)line, what);
@@ -1972,7 +1993,7 @@ static inline int bed_sep(char c) { return c == ' ' || c == '\t'; }
 
 /* the lines of a BED text into raw[]; every read stays inside bed[0 .. len) */
 static int bed_parse(const cbc_unpack_plan *u, const char *bed, size_t len, target_raw **raw, uint64_t *n, uint64_t *cap,
-                     uint64_t *unselected, char *errbuf, size_t errlen)
+                     uint64_t *unselected, query_list *ql, char *errbuf, size_t errlen)
 {
     uint64_t line = 0;
     for (size_t at = 0; at < len; ) {
@@ -2001,13 +2022,24 @@ static int bed_parse(const cbc_unpack_plan *u, const char *bed, size_t len, targ
         if (st > en) return bed_err(errbuf, errlen, line, "start is past end");
         const int64_t c = region_contig(u, s + f0[0], fl[0]);
         if (c == -2) return region_err(errbuf, errlen, "corrupt container: a contig name lies outside the name table%.*s", "", 0);
-        if (c < 0 || st == en || st >= u->contig_len[c]) { (*unselected)++; continue; }
+        if (c < 0 || st == en || st >= u->contig_len[c]) {
+            (*unselected)++;
+            /* still a query: the chrom text and the numbers as given, or both ends clamped to the contig (no position) */
+            const uint64_t cl = c < 0 ? 0u : u->contig_len[c];
+            const int qrc = c < 0 ? query_push(ql, CBC_QUERY_UNKNOWN, 1u, 0u, (size_t)(s + f0[0] - bed), fl[0], st, en)
+                                  : query_push(ql, (uint32_t)c, (st < cl ? st : cl) + 1u, en < cl ? en : cl, 0, 0, 0, 0);
+            if (qrc) return qrc;
+            continue;
+        }
         if (en > u->contig_len[c]) en = u->contig_len[c];
-        const int rc = target_push(raw, n, cap, (uint32_t)c, st + 1u, en);
+        int rc = target_push(raw, n, cap, (uint32_t)c, st + 1u, en);
+        if (!rc) rc = query_push(ql, (uint32_t)c, st + 1u, en, 0, 0, 0, 0);
         if (rc) return rc;
     }
     return 0;
 }
+
+static int targets_build(const cbc_unpack_plan *u, cbc_targets *t, target_raw *raw, uint64_t n, char *errbuf, size_t errlen);
 
 API void cbc_targets_free(cbc_targets *t)
 {
@@ -2037,8 +2069,22 @@ API int cbc_unpack_targets(const cbc_unpack_plan *u, const char *const *regions,
         rc = cbc_unpack_region(u, regions[r], &sel, errbuf, errlen);
         if (!rc) rc = target_push(&raw, &n, &cap, sel.contig, sel.beg, sel.end);
     }
-    if (!rc && bed) rc = bed_parse(u, bed, bed_len, &raw, &n, &cap, &t->bed_unselected, errbuf, errlen);
+    if (!rc && bed) rc = bed_parse(u, bed, bed_len, &raw, &n, &cap, &t->bed_unselected, NULL, errbuf, errlen);
+    if (!rc) rc = targets_build(u, t, raw, n, errbuf, errlen);
     if (rc) goto fail;
+    free(raw);
+    *out = t;
+    return 0;
+fail:
+    free(raw);
+    cbc_targets_free(t);
+    return rc;
+}
+
+/* raw[0 .. n) (any order; sorted and merged in place) -> the intervals, the blocks and the per-block ranges of t */
+static int targets_build(const cbc_unpack_plan *u, cbc_targets *t, target_raw *raw, uint64_t n, char *errbuf, size_t errlen)
+{
+    int rc = 0;
     t->n_input = n;
     t->n_contigs = u->n_contigs;
     t->smax = region_smax(u);
@@ -2050,10 +2096,8 @@ API int cbc_unpack_targets(const cbc_unpack_plan *u, const char *const *regions,
             if (raw[i].end > raw[m - 1].end) raw[m - 1].end = raw[i].end;
         } else raw[m++] = raw[i];
     }
-    if (m > CBC_TARGETS_MAX_IV) {
-        rc = region_err(errbuf, errlen, "the set of regions has more than 2^24 intervals after merging%.*s", "", 0);
-        goto fail;
-    }
+    if (m > CBC_TARGETS_MAX_IV)
+        return region_err(errbuf, errlen, "the set of regions has more than 2^24 intervals after merging%.*s", "", 0);
     t->n_iv = (uint32_t)m;
     {
         const size_t nc = u->n_contigs ? u->n_contigs : 1u;
@@ -2062,8 +2106,8 @@ API int cbc_unpack_targets(const cbc_unpack_plan *u, const char *const *regions,
         t->contig_blk_first = (uint32_t *)calloc(nc, 4); t->contig_blk_count = (uint32_t *)calloc(nc, 4);
         t->blocks = (uint32_t *)calloc(u->n_blocks ? u->n_blocks : 1u, 4);
         t->block_iv = (uint32_t *)calloc(u->n_blocks ? u->n_blocks : 1u, 8);
-        if (!t->iv || !t->contig_first || !t->contig_count || !t->contig_blk_first || !t->contig_blk_count || !t->blocks || !t->block_iv) {
-            rc = CBC_E_NOMEM; goto fail; }
+        if (!t->iv || !t->contig_first || !t->contig_count || !t->contig_blk_first || !t->contig_blk_count || !t->blocks || !t->block_iv)
+            return CBC_E_NOMEM;
     }
     for (uint64_t i = 0; i < m; i++) {
         t->iv[i].beg = raw[i].beg; t->iv[i].end = raw[i].end;
@@ -2074,10 +2118,8 @@ API int cbc_unpack_targets(const cbc_unpack_plan *u, const char *const *regions,
     for (uint32_t c = 0; c < u->n_contigs; c++) {
         if (!t->contig_count[c]) continue;
         uint32_t c0, c1;
-        if (region_contig_run(u, c, &c0, &c1)) {
-            rc = region_err(errbuf, errlen, "corrupt container: the block index is not in contig and position order%.*s", "", 0);
-            goto fail;
-        }
+        if (region_contig_run(u, c, &c0, &c1))
+            return region_err(errbuf, errlen, "corrupt container: the block index is not in contig and position order%.*s", "", 0);
         const cbc_target_iv *iv = t->iv + t->contig_first[c];
         const uint32_t ni = t->contig_count[c];
         t->contig_blk_first[c] = t->n_blocks;
@@ -2099,12 +2141,6 @@ API int cbc_unpack_targets(const cbc_unpack_plan *u, const char *const *regions,
             t->block_iv[2 * k] = t->contig_first[c] + lo; t->block_iv[2 * k + 1] = hi - lo;
         }
     }
-    free(raw);
-    *out = t;
-    return 0;
-fail:
-    free(raw);
-    cbc_targets_free(t);
     return rc;
 }
 
@@ -2132,6 +2168,109 @@ API uint64_t cbc_unpack_targets_depth_cap(const cbc_unpack_plan *u, const cbc_ta
         k += u->blocks[b].n_reads;
     }
     return (2u * k + 2ull * t->contig_count[contig] - 1u) * ((uint64_t)nl + 34u);
+}
+
+/* ---- per-target coverage summary (include/cbc_host.h) ---- */
+API void cbc_queries_free(cbc_queries *q)
+{
+    if (!q) return;
+    free(q->q); cbc_targets_free(q->targets); free(q);
+}
+
+API int cbc_coverage_mean(uint64_t sum, uint64_t len, char *dst)
+{
+    if (!dst) return CBC_E_ARG;
+    uint64_t m = 0;
+    if (len) { const uint64_t q = sum / len, r = sum % len; m = q * 100u + (r * 100u + len / 2u) / len; }
+    return sprintf(dst, "%llu.%02u", (unsigned long long)(m / 100u), (unsigned)(m % 100u));
+}
+
+API int cbc_unpack_queries(const cbc_unpack_plan *u, const char *const *regions, uint32_t n_regions, const char *bed, size_t bed_len,
+                           uint64_t window, cbc_queries **out, char *errbuf, size_t errlen)
+{
+    if (!u || !out || (n_regions && !regions) || (bed_len && !bed) || (uint64_t)bed_len > 0xffffffffull) return CBC_E_ARG;
+    *out = NULL;
+    if (errbuf && errlen) errbuf[0] = 0;
+    const int64_t hdr = cbc_unpack_sam_header(u, NULL, 0, errbuf, errlen);   /* what cbc_unpack_targets refuses */
+    if (hdr < 0) return (int)hdr;
+    if (!u->block_contig) return CBC_E_ARG;
+    target_raw *raw = NULL;
+    uint64_t n = 0, cap = 0;
+    query_list L = { NULL, 0, 0 };
+    uint32_t *iv_slot = NULL;
+    int rc = 0;
+    cbc_queries *Q = (cbc_queries *)calloc(1, sizeof *Q);
+    cbc_targets *t = (cbc_targets *)calloc(1, sizeof *t);
+    if (!Q || !t) { free(Q); free(t); return CBC_E_NOMEM; }
+    Q->targets = t;
+    for (uint32_t r = 0; r < n_regions && !rc; r++) {
+        cbc_region_sel sel;
+        if (!regions[r]) { rc = CBC_E_ARG; break; }
+        rc = cbc_unpack_region(u, regions[r], &sel, errbuf, errlen);
+        if (!rc) rc = target_push(&raw, &n, &cap, sel.contig, sel.beg, sel.end);
+        if (!rc) rc = query_push(&L, sel.contig, sel.beg, sel.end, 0, 0, 0, 0);
+    }
+    if (!rc && bed) rc = bed_parse(u, bed, bed_len, &raw, &n, &cap, &t->bed_unselected, &L, errbuf, errlen);
+    for (uint32_t c = 0; !n_regions && !bed && c < u->n_contigs && !rc; c++) {   /* no input: every contig as a whole */
+        cbc_region_sel sel;
+        rc = cbc_unpack_contig_blocks(u, c, &sel, errbuf, errlen);
+        if (!rc) rc = target_push(&raw, &n, &cap, sel.contig, sel.beg, sel.end);
+        if (!rc) rc = query_push(&L, sel.contig, sel.beg, sel.end, 0, 0, 0, 0);
+    }
+    if (!rc) rc = targets_build(u, t, raw, n, errbuf, errlen);
+    if (rc) goto fail;
+    {
+        /* the windows: counted first, so that a refused list allocates nothing */
+        uint64_t total = 0;
+        for (uint64_t i = 0; i < L.n && total <= CBC_TARGETS_MAX_IV; i++) {
+            const uint64_t len = L.q[i].end0 - L.q[i].start0;
+            total += window && len ? (len - 1u) / window + 1u : 1u;
+        }
+        if (total > CBC_TARGETS_MAX_IV) {
+            rc = region_err(errbuf, errlen, "more than 2^24 coverage queries%.*s", window ? " after cutting into windows" : "", 64);
+            goto fail;
+        }
+        Q->q = (cbc_query *)calloc(total ? (size_t)total : 1u, sizeof(cbc_query));
+        if (!Q->q) { rc = CBC_E_NOMEM; goto fail; }
+        for (uint64_t i = 0; i < L.n; i++) {
+            const cbc_query *x = &L.q[i];
+            const uint64_t len = x->end0 - x->start0, step = window && len ? window : (len ? len : 1u);
+            for (uint64_t o = 0; o == 0 || o < len; o += step) {
+                cbc_query *y = &Q->q[Q->n_q++];
+                *y = *x;
+                y->start0 = x->start0 + o;
+                y->end0 = len - o > step ? y->start0 + step : x->end0;
+                if (x->contig != CBC_QUERY_UNKNOWN) { y->beg = (uint32_t)(y->start0 + 1u); y->end = (uint32_t)y->end0; }
+            }
+        }
+    }
+    /* the slots: per contig the merged intervals end to end with one spare slot behind each (at most 2^31 + 2^24 of them) */
+    iv_slot = (uint32_t *)malloc(((size_t)t->n_iv + 1u) * 4u);
+    if (!iv_slot) { rc = CBC_E_NOMEM; goto fail; }
+    for (uint32_t c = 0; c < t->n_contigs; c++) {
+        uint64_t run = 0;
+        for (uint32_t i = 0; i < t->contig_count[c]; i++) {
+            const cbc_target_iv *v = &t->iv[t->contig_first[c] + i];
+            iv_slot[t->contig_first[c] + i] = (uint32_t)run;
+            run += (uint64_t)(v->end - v->beg) + 2u;
+        }
+    }
+    for (uint64_t i = 0; i < Q->n_q; i++) {
+        cbc_query *y = &Q->q[i];
+        if (y->contig == CBC_QUERY_UNKNOWN || y->end0 == y->start0) continue;
+        const cbc_target_iv *iv = t->iv + t->contig_first[y->contig];
+        uint32_t lo = 0, hi = t->contig_count[y->contig];            /* the last interval with beg <= the query's */
+        while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (iv[mid].beg <= y->beg) lo = mid; else hi = mid; }
+        if (hi == 0 || iv[lo].beg > y->beg || iv[lo].end < y->end) { rc = CBC_E_ARG; goto fail; }   /* merging lost a query: never */
+        y->slot = iv_slot[t->contig_first[y->contig] + lo] + (y->beg - iv[lo].beg);
+    }
+    free(iv_slot); free(raw); free(L.q);
+    *out = Q;
+    return 0;
+fail:
+    free(iv_slot); free(raw); free(L.q);
+    cbc_queries_free(Q);
+    return rc;
 }
 
 /* One reconstructed read per line (print_line, src/compression.c:16-40). */

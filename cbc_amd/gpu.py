@@ -241,6 +241,15 @@ def lib():
                                              ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
         L.cbc_gpu_last_targets_ms.restype = ctypes.c_int
         L.cbc_gpu_last_targets_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
+        L.cbc_gpu_decode_coverage.restype = ctypes.c_int
+        L.cbc_gpu_decode_coverage.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                              ctypes.POINTER(host.LdsCaps), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(GpuTargets),
+                                              ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                              ctypes.c_void_p]
+        L.cbc_gpu_last_coverage_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_coverage_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 7
         L.cbc_gpu_last_depth_ms.restype = ctypes.c_int
         L.cbc_gpu_last_depth_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         if L.cbc_gpu_abi_version() != 1:
@@ -263,7 +272,8 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_decode_stream_blocks", "cbc_gpu_group_create", "cbc_gpu_group_gather", "cbc_gpu_group_destroy", "cbc_gpu_group_last_error",
            "cbc_gpu_stash_reset", "cbc_gpu_stash_bytes", "cbc_gpu_stash_fetch", "cbc_gpu_decode_region",
            "cbc_gpu_decode_blocks_span", "cbc_gpu_last_region_ms", "cbc_gpu_decode_sam", "cbc_gpu_last_sam_ms",
-           "cbc_gpu_decode_depth", "cbc_gpu_last_depth_ms", "cbc_gpu_decode_targets", "cbc_gpu_last_targets_ms"]
+           "cbc_gpu_decode_depth", "cbc_gpu_last_depth_ms", "cbc_gpu_decode_targets", "cbc_gpu_last_targets_ms",
+           "cbc_gpu_decode_coverage", "cbc_gpu_last_coverage_ms"]
 
 
 class Encoder:
@@ -603,6 +613,66 @@ class Encoder:
         if results:
             return text, n_reads, n_runs, (np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE))
         return text
+
+    def decode_coverage(self, plan: "host.UnpackPlan", queries, exclude_flags=0, min_depth=1, results=False):
+        """Per-query coverage summary (cbc_gpu_decode_coverage): for every query of `queries` (a host.QuerySet of
+        plan.queries()) the sum of the depth over its positions and the number of its positions with depth >= min_depth; depth
+        as decode_depth counts it (reads with FLAG & exclude_flags != 0 left out).  One call and one decode per contig that has
+        queries, intervals and blocks; only the numbers cross PCIe.  Returns numpy arrays in query order: contig (int64, -1:
+        not in the container's table), start0, end0 (uint64, 0-based half-open), sum (uint64), covered (uint32).  With
+        results=True the per-block decode results of the blocks decoded are appended and a failed block passes (it contributes
+        nothing); otherwise it raises CbcGpuError."""
+        plan.sam_header()                                     # refuses what the coordinates cannot carry, and long-read containers
+        ts = queries.targets
+        self._coverage_ms = None
+        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
+        pay = np.ascontiguousarray(plan.payloads)
+        names = np.ascontiguousarray(plan.names)
+        noff = np.ascontiguousarray(plan.contig_name_off, dtype=np.uint32)
+        iv = np.ascontiguousarray(ts.iv, dtype=np.uint32)
+        total = np.zeros(queries.n_q, dtype=np.uint64)
+        covered = np.zeros(queries.n_q, dtype=np.uint32)
+        length = (queries.end0 - queries.start0).astype(np.uint64)
+        allres = []
+        for c in range(ts.n_contigs):
+            k0, nb, ni = int(ts.contig_blk_first[c]), int(ts.contig_blk_count[c]), int(ts.contig_count[c])
+            idx = np.flatnonzero((queries.contig == c) & (length > 0))
+            if not nb or not ni or not len(idx):
+                continue
+            sel = np.ascontiguousarray(ts.blocks[k0:k0 + nb]).astype(np.int64)
+            blocks = np.ascontiguousarray(plan.blocks[sel])
+            ws = np.ascontiguousarray(plan.window_start[sel], dtype=np.uint64)
+            bc = np.ascontiguousarray(plan.block_contig[sel], dtype=np.uint32)
+            biv = np.ascontiguousarray(ts.block_iv[k0:k0 + nb], dtype=np.uint32)
+            q = np.ascontiguousarray(np.stack([queries.q["slot"][idx], length[idx].astype(np.uint32)], axis=1), dtype=np.uint32)
+            s, cv = np.zeros(len(idx), dtype=np.uint64), np.zeros(len(idx), dtype=np.uint32)
+            res = np.zeros(nb, dtype=host.RESULT_DTYPE)
+            nrd = ctypes.c_uint64()
+            tg = GpuTargets(iv.ctypes.data, biv.ctypes.data, ts.n_iv, ts.smax)
+            rc = lib().cbc_gpu_decode_coverage(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
+                                               ws.ctypes.data, bc.ctypes.data, names.ctypes.data, names.size, noff.ctypes.data,
+                                               plan.n_contigs, ctypes.byref(tg), int(ts.contig_first[c]), ni, q.ctypes.data, len(idx),
+                                               int(exclude_flags), int(min_depth), s.ctypes.data, cv.ctypes.data, ctypes.byref(nrd),
+                                               res.ctypes.data)
+            if rc != 0 and not (results and rc == -4):
+                self._check(rc, "cbc_gpu_decode_coverage")
+            v = [ctypes.c_float() for _ in range(7)]
+            if lib().cbc_gpu_last_coverage_ms(self._ctx, *[ctypes.byref(x) for x in v]) == 0:
+                ms = tuple(float(x.value) for x in v)
+                self._coverage_ms = ms if self._coverage_ms is None else tuple(a + b for a, b in zip(self._coverage_ms, ms))
+            total[idx], covered[idx] = s, cv
+            allres.append(res)
+        out = (queries.contig.copy(), queries.start0.copy(), queries.end0.copy(), total, covered)
+        if results:
+            return out + ((np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE)),)
+        return out
+
+    def last_coverage_ms(self):
+        """(decode, mark, scan + compact, weights, weight scans, prefixes, lookup) kernel milliseconds of the last
+        decode_coverage, summed over its calls."""
+        if getattr(self, "_coverage_ms", None) is None:
+            raise CbcGpuError("no decode_coverage has run on the device")
+        return self._coverage_ms
 
     def last_targets_ms(self):
         """(decode, count + scan or mark, depth scan + compact or 0, text) kernel milliseconds of the last decode_targets,

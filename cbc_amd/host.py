@@ -99,6 +99,15 @@ class TargetsC(ctypes.Structure):
                 ("bed_unselected", ctypes.c_uint64), ("n_input", ctypes.c_uint64)]
 
 
+class QueriesC(ctypes.Structure):
+    _fields_ = [("q", ctypes.c_void_p), ("n_q", ctypes.c_uint64), ("targets", ctypes.POINTER(TargetsC))]
+
+
+QUERY_DTYPE = np.dtype([("contig", "<u4"), ("beg", "<u4"), ("end", "<u4"), ("slot", "<u4"), ("name_off", "<u4"), ("name_len", "<u4"),
+                        ("start0", "<u8"), ("end0", "<u8")])
+QUERY_UNKNOWN = 0xffffffff
+
+
 class RegionSelC(ctypes.Structure):
     _fields_ = [("contig", ctypes.c_uint32), ("b0", ctypes.c_uint32), ("b1", ctypes.c_uint32), ("smax", ctypes.c_uint32),
                 ("beg", ctypes.c_uint64), ("end", ctypes.c_uint64), ("contig_len", ctypes.c_uint64)]
@@ -205,8 +214,25 @@ def lib():
         L.cbc_unpack_targets_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(TargetsC), ctypes.c_int]
         L.cbc_unpack_targets_depth_cap.restype = ctypes.c_uint64
         L.cbc_unpack_targets_depth_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(TargetsC), ctypes.c_uint32]
+        L.cbc_unpack_queries.restype = ctypes.c_int
+        L.cbc_unpack_queries.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(QueriesC)), ctypes.c_char_p,
+                                         ctypes.c_size_t]
+        L.cbc_queries_free.restype = None
+        L.cbc_queries_free.argtypes = [ctypes.POINTER(QueriesC)]
+        L.cbc_coverage_mean.restype = ctypes.c_int
+        L.cbc_coverage_mean.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p]
         _lib = L
     return _lib
+
+
+def coverage_mean(total: int, length: int) -> bytes:
+    """The mean depth total / length with two decimals by the integer rule of cbc_coverage_mean (what `cbc --bedcov` prints)."""
+    buf = ctypes.create_string_buffer(32)
+    n = lib().cbc_coverage_mean(int(total), int(length), buf)
+    if n < 0:
+        raise ValueError("cbc_coverage_mean failed (%d)" % n)
+    return buf.raw[:n]
 
 
 def _opts(block_reads=None, max_cap_pos=None, max_cap_var=None, var_length=False, threads=None, whole_file=False,
@@ -484,6 +510,36 @@ class TargetSet:
         return "TargetSet(%d intervals, %d blocks, smax=%d)" % (self.n_iv, self.n_blocks, self.smax)
 
 
+class QuerySet:
+    """What cbc_unpack_queries made of a list of regions, a BED text and a window (copies; nothing of the C object is kept):
+    q             structured array (QUERY_DTYPE), one entry per query in input order: contig (QUERY_UNKNOWN: not in the table),
+                  beg / end (1-based inclusive, clamped), slot (first slot in the contig's compressed coordinate), name_off /
+                  name_len (unknown contig: the chrom text inside the BED text), start0 / end0 (what the output echoes)
+    contig        int64, -1 for an unknown contig;  start0, end0: uint64;  length = end0 - start0
+    targets       the TargetSet of the same input (merged intervals, selected blocks)"""
+
+    def __init__(self, plan, ptr, bed):
+        c = ptr.contents
+        self.n_q = int(c.n_q)
+        self.q = _np_view(ctypes.cast(c.q, ctypes.POINTER(ctypes.c_uint8)), self.n_q * QUERY_DTYPE.itemsize, np.uint8).copy().view(QUERY_DTYPE) \
+            if self.n_q else np.zeros(0, dtype=QUERY_DTYPE)
+        self.targets = TargetSet(plan, c.targets)
+        self.contig = np.where(self.q["contig"] == QUERY_UNKNOWN, -1, self.q["contig"].astype(np.int64))
+        self.start0, self.end0 = self.q["start0"].copy(), self.q["end0"].copy()
+        self._bed = bytes(bed) if bed else b""
+        self._names = [plan.names[int(o):].tobytes().split(b"\0", 1)[0] for o in plan.contig_name_off]
+
+    def chrom(self, i):
+        """The first column of query i: the contig's name, or the BED line's own text for a contig the container does not list."""
+        x = self.q[i]
+        if int(x["contig"]) == QUERY_UNKNOWN:
+            return self._bed[int(x["name_off"]):int(x["name_off"]) + int(x["name_len"])]
+        return self._names[int(x["contig"])]
+
+    def __repr__(self):
+        return "QuerySet(%d queries, %r)" % (self.n_q, self.targets)
+
+
 class UnpackPlan:
     """Container + FASTA -> decode launch plan (cbc_unpack_plan_create).  Keeps the container bytes alive."""
 
@@ -551,6 +607,30 @@ class UnpackPlan:
             return TargetSet(self, out)
         finally:
             lib().cbc_targets_free(out)
+
+    def queries(self, regions=(), bed=None, window=0):
+        """The query list of a per-target coverage summary (cbc_unpack_queries): every region string, then every BED line,
+        unmerged and in input order -- lines that select nothing included, with length 0 -- or one query per contig when
+        regions is empty and bed is None; window > 0 cuts every query into windows of that many bases.  Returns a QuerySet;
+        raises CbcInputError for what targets() refuses and for more than 2^24 queries."""
+        if isinstance(regions, (str, bytes)):
+            regions = [regions]
+        rs = [r.encode() if isinstance(r, str) else bytes(r) for r in regions]
+        arr = (ctypes.c_char_p * max(len(rs), 1))(*rs)
+        if isinstance(bed, str):
+            bed = bed.encode()
+        # exactly the bytes: no terminator behind them; an empty text is still a text (no line), not "no file"
+        buf = None if bed is None else np.frombuffer(bed, dtype=np.uint8).copy() if len(bed) else np.zeros(1, dtype=np.uint8)
+        out = ctypes.POINTER(QueriesC)()
+        err = ctypes.create_string_buffer(512)
+        rc = lib().cbc_unpack_queries(self._ptr, arr, len(rs), buf.ctypes.data if buf is not None else None,
+                                      len(bed) if bed is not None else 0, int(window), ctypes.byref(out), err, 512)
+        if rc != 0:
+            raise CbcInputError("cbc_unpack_queries failed (%d): %s" % (rc, err.value.decode(errors="replace")))
+        try:
+            return QuerySet(self, out, bed)
+        finally:
+            lib().cbc_queries_free(out)
 
     def contig_blocks(self, contig: int):
         """The selection of contig `contig` as a whole (cbc_unpack_contig_blocks): its blocks, beg = 1, end = its length."""

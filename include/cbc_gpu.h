@@ -387,6 +387,32 @@ int  cbc_gpu_decode_targets(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_byt
  * the depth the tile sums, scans and change points (else 0); the text. */
 int  cbc_gpu_last_targets_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *scan_ms, float *text_ms);
 
+/* ---- per-query coverage summary -------------------------------------------------------------------
+ * The depth form of cbc_gpu_decode_targets -- the selected blocks of ONE contig, decoded once, marked in the compressed
+ * coordinate of the contig's merged intervals -- without the text: for every query the sum of the depth over its positions and
+ * the number of its positions with depth >= min_depth (>= 1), computed on the device from the change points; 12 bytes per query
+ * come back.  Depth is that of cbc_gpu_decode_depth (span coverage, reads with FLAG & exclude_flags != 0 left out).
+ *   t, iv_first, iv_count   the interval table of cbc_unpack_queries / cbc_unpack_targets and the contig's part of it
+ *                           (contig_first[c], contig_count[c]); t->block_iv as for cbc_gpu_decode_targets.  The compressed
+ *                           coordinate lays these intervals end to end with one spare slot behind each.
+ *   q                       n_q <= 2^24 pairs slot, len: the query's first slot and its length; a query lies inside one
+ *                           interval (slot = slots in front of the interval + start - interval beg: cbc_query.slot)
+ *   sum[n_q], covered[n_q]  the results, in the order of q; all zero when no block reaches an interval
+ * One call runs as one chunk on one stream with no host round trip between its kernels.  A block that fails to decode
+ * contributes nothing and the call returns CBC_E_BLOCK; CBC_E_NOMEM when the difference array or the prefix tables (12 bytes
+ * per change point) cannot be had; CBC_E_ARG for a query that reaches past the slots.  *n_reads = reads counted. */
+int  cbc_gpu_decode_coverage(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                             uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                             const uint32_t *block_contig /* n_blocks */, const char *names, uint32_t names_bytes,
+                             const uint32_t *contig_name_off /* n_contigs */, uint32_t n_contigs, const cbc_gpu_targets *t,
+                             uint32_t iv_first, uint32_t iv_count, const uint32_t *q /* n_q pairs slot, len */, uint32_t n_q,
+                             uint32_t exclude_flags, uint32_t min_depth, uint64_t *sum, uint32_t *covered, uint64_t *n_reads,
+                             cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_coverage: the span decode; zeroing + mark; tile sums, scans and change
+ * points; then the four new passes: run weights, the scans of their tile totals, the prefixes, the lookup. */
+int  cbc_gpu_last_coverage_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *weights_ms,
+                              float *wscan_ms, float *apply_ms, float *lookup_ms);
+
 /* ---- whole-file stream ("compat" mode): the reference's own file format --------------------------------------
  * compress() / decompress(), src/compression.c:112-216: ONE arithmetic stream per file, models never reset.
  * `batch` is a cbc_host_batch packed with cbc_pack_opts.whole_file = 1: its `blocks` are SEGMENTS of the one

@@ -265,6 +265,41 @@ void     cbc_targets_free(cbc_targets *t);
 uint64_t cbc_unpack_targets_text_cap(const cbc_unpack_plan *u, const cbc_targets *t, int sam);
 uint64_t cbc_unpack_targets_depth_cap(const cbc_unpack_plan *u, const cbc_targets *t, uint32_t contig);
 
+/* Per-target coverage summary (the numbers come from cbc_gpu_decode_coverage).  The QUERY list, in this
+ * order and never merged or de-duplicated: every string of `regions` (parsed, clamped and refused as cbc_unpack_region does),
+ * then every line of the BED text that cbc_unpack_targets would take or count in bed_unselected (the same parser, the same
+ * errors) -- a line that selects nothing stays in the list with len = 0, so the list joins 1:1 with the input; with neither a
+ * region nor a BED text, one query per contig of the container's table, the whole contig, in table order
+ * (cbc_unpack_contig_blocks).  window > 0: every query is replaced by consecutive windows of `window` bases from its own
+ * start on, the last one possibly shorter.  More than CBC_TARGETS_MAX_IV queries are CBC_E_INPUT with a message.
+ *   q[i].contig            index in the container's table, CBC_QUERY_UNKNOWN for a BED line whose chrom is not in it
+ *   q[i].beg, q[i].end     known contig: 1-based inclusive, both clamped to the contig's length; len = end + 1 - beg may be 0
+ *                          (start0 == end0, or a start at or past the contig's end)
+ *   q[i].slot              len > 0: the query's first slot in the compressed coordinate of its contig -- the contig's merged
+ *                          intervals end to end, one spare slot behind each: the slots in front of the interval that holds
+ *                          the query + beg - that interval's beg
+ *   q[i].name_off/name_len unknown contig: the chrom text, bed[name_off .. + name_len)
+ *   q[i].start0, q[i].end0 what the output echoes, 0-based half-open: beg - 1 and end for a known contig, the coordinates as
+ *                          given (cut into windows like any other) for an unknown one
+ *   targets                the cbc_targets that cbc_unpack_targets builds from the same (uncut) input
+ * Free with cbc_queries_free. */
+#define CBC_QUERY_UNKNOWN 0xffffffffu
+typedef struct cbc_query {
+    uint32_t contig, beg, end, slot;
+    uint32_t name_off, name_len;
+    uint64_t start0, end0;
+} cbc_query;
+typedef struct cbc_queries {
+    cbc_query   *q;  uint64_t n_q;
+    cbc_targets *targets;
+} cbc_queries;
+int      cbc_unpack_queries(const cbc_unpack_plan *u, const char *const *regions, uint32_t n_regions, const char *bed, size_t bed_len,
+                            uint64_t window, cbc_queries **out, char *errbuf, size_t errlen);
+void     cbc_queries_free(cbc_queries *q);
+/* "<m / 100>.<two digits of m % 100>" of the mean sum / len rounded half up in integers: q = sum / len, r = sum % len,
+ * m = q * 100 + (r * 100 + len / 2) / len; len == 0: "0.00".  Returns the characters written (dst holds at least 24). */
+int      cbc_coverage_mean(uint64_t sum, uint64_t len, char *dst);
+
 int     cbc_unpack_plan_create(const uint8_t *blob, uint64_t len, const char *fasta, size_t fasta_len,
                                cbc_unpack_plan **out, char *errbuf, size_t errlen);
 void    cbc_unpack_plan_free(cbc_unpack_plan *u);
