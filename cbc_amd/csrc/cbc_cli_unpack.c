@@ -580,3 +580,139 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
     cbc_unpack_plan_free(u);
     return 0;
 }
+
+/* `cbc -d|-x ... --depth-hist [--region A ...] [--regions-file FILE] [--hist-max M]`: per contig how many positions have each
+ * depth, then the same summed over the listed contigs under the name "genome" (DESIGN.md section 4.16).  Without regions every
+ * contig of the table is counted whole; with them the merged intervals, every position once, and a contig is listed when an
+ * interval lies on it.  The non-zero bins come from one cbc_gpu_decode_depth_hist per contig that has blocks; the depth-0 bin,
+ * the genome sums and the text are made here.  A few hundred bytes per contig cross PCIe. */
+typedef struct hist_bin { uint64_t depth, bases; } hist_bin;
+static int hist_bin_cmp(const void *a, const void *b)
+{
+    const uint64_t x = ((const hist_bin *)a)->depth, y = ((const hist_bin *)b)->depth;
+    return x < y ? -1 : x > y;
+}
+static int hist_line(FILE *fo, const char *name, uint64_t depth, uint64_t bases, uint64_t size)
+{
+    char fr[40];
+    (void)cbc_hist_fraction(bases, size, fr);
+    return fprintf(fo, "%s\t%llu\t%llu\t%llu\t%s\n", name, (unsigned long long)depth, (unsigned long long)bases, (unsigned long long)size, fr) < 0;
+}
+
+int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                            const char *bed_path, uint32_t max_depth, uint32_t exclude, int verbose)
+{
+    const double t0 = now2();
+    size_t blob_len = 0, fa_len = 0, bed_len = 0;
+    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
+    if (!blob || !fa) return 1;
+    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
+        fprintf(stderr, "cbc: --depth-hist needs a block container; %s is a single-stream (--compat) file, which has no block index\n", in);
+        return 1;
+    }
+    char *bed = NULL;
+    if (bed_path && !(bed = slurp2(bed_path, &bed_len))) return 1;
+    char err[512];
+    cbc_unpack_plan *u = NULL;
+    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
+    free(fa);
+    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
+    /* the intervals and their blocks: the target set of the regions, or every contig whole (the query list's own set) */
+    cbc_targets *T = NULL;
+    cbc_queries *Q = NULL;
+    if (n_regions || bed_path) rc = cbc_unpack_targets(u, regions, n_regions, bed, bed_len, &T, err, sizeof err);
+    else { rc = cbc_unpack_queries(u, NULL, 0, NULL, 0, 0, &Q, err, sizeof err); if (!rc) T = Q->targets; }
+    free(bed);
+    if (rc) { fprintf(stderr, "cbc: --depth-hist: %s\n", rc == CBC_E_INPUT && err[0] ? err : "target selection failed"); return 1; }
+    const uint32_t nb = T->n_blocks, nc = u->n_contigs;
+    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)(nb ? nb : 1) * sizeof *bl);
+    uint64_t *ws = (uint64_t *)malloc((size_t)(nb ? nb : 1) * 8);
+    uint32_t *bc = (uint32_t *)malloc((size_t)(nb ? nb : 1) * 4);
+    if (!bl || !ws || !bc) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    for (uint32_t k = 0; k < nb; k++) { const uint32_t b = T->blocks[k]; bl[k] = u->blocks[b]; ws[k] = u->window_start[b]; bc[k] = u->block_contig[b]; }
+    const double t1 = now2();
+    double t_init = 0, t_dev = 0;
+    FILE *fo = fopen(out, "wb");
+    if (!fo) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    cbc_gpu_ctx *ctx = NULL;
+    hist_bin *all = NULL;                                    /* every contig's bins, for the genome block */
+    size_t n_all = 0, cap_all = 0;
+    uint64_t reads = 0, gsize = 0;
+    uint32_t blocks_used = 0, listed = 0;
+    float ms[5] = { 0, 0, 0, 0, 0 };
+    const cbc_gpu_targets gt = { (const uint32_t *)T->iv, NULL, T->n_iv, T->smax };
+    for (uint32_t c = 0; c < nc && c < T->n_contigs; c++) {
+        if (!T->contig_count[c]) continue;                  /* no interval on the contig: not listed */
+        const uint32_t k0 = T->contig_blk_first[c], kn = T->contig_blk_count[c];
+        const uint64_t size = cbc_unpack_targets_size(T, c);
+        const char *nm = u->names + u->contig_name_off[c];
+        uint32_t n_bins = 0, *bd = NULL, *bb = NULL;
+        if (kn) {                                           /* else no block can hold a read of the intervals: depth 0 everywhere */
+            const double a = now2();
+            if (!ctx) {
+                rc = cbc_gpu_init(device, &ctx);
+                if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
+                if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+                t_init = now2() - a;
+            }
+            const double b = now2();
+            uint64_t k_reads = 0, nr = 0;
+            for (uint32_t k = 0; k < kn; k++) k_reads += bl[k0 + k].n_reads;
+            const uint64_t fold = max_depth ? max_depth : 0xffffffffull;
+            const uint32_t cap = (uint32_t)(k_reads < fold ? k_reads : fold);   /* a depth cannot pass the reads */
+            bd = (uint32_t *)malloc((size_t)(cap ? cap : 1) * 4); bb = (uint32_t *)malloc((size_t)(cap ? cap : 1) * 4);
+            if (!bd || !bb) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+            cbc_gpu_targets g = gt;
+            g.block_iv = T->block_iv + 2 * (size_t)k0;
+            rc = cbc_gpu_decode_depth_hist(ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
+                                           u->contig_name_off, u->n_contigs, &g, T->contig_first[c], T->contig_count[c], exclude, max_depth,
+                                           bd, bb, cap, &n_bins, &nr, NULL);
+            if (rc) { fprintf(stderr, "cbc: depth histogram failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+            t_dev += now2() - b;
+            if (verbose) {
+                float m5[5];
+                if (cbc_gpu_last_hist_ms(ctx, &m5[0], &m5[1], &m5[2], &m5[3], &m5[4]) == 0) for (int i = 0; i < 5; i++) ms[i] += m5[i];
+            }
+            reads += nr; blocks_used += kn;
+        }
+        uint64_t covered = 0;
+        for (uint32_t i = 0; i < n_bins; i++) covered += bb[i];
+        if (covered > size) { fprintf(stderr, "cbc: depth histogram failed: the bins of %s hold more positions than its intervals\n", nm); return 1; }
+        if (n_all + n_bins + 1u > cap_all) {
+            cap_all = (n_all + n_bins + 1u) * 2u;
+            all = (hist_bin *)realloc(all, cap_all * sizeof *all);
+            if (!all) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+        }
+        int bad = 0;
+        if (size - covered) { bad |= hist_line(fo, nm, 0, size - covered, size); all[n_all].depth = 0; all[n_all++].bases = size - covered; }
+        for (uint32_t i = 0; i < n_bins; i++) { bad |= hist_line(fo, nm, bd[i], bb[i], size); all[n_all].depth = bd[i]; all[n_all++].bases = bb[i]; }
+        if (bad) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+        free(bd); free(bb);
+        gsize += size; listed++;
+    }
+    if (ctx) cbc_gpu_shutdown(ctx);
+    if (listed) {                                            /* the genome block: the bins summed over the listed contigs, 64 bits */
+        qsort(all, n_all, sizeof *all, hist_bin_cmp);
+        for (size_t i = 0; i < n_all; ) {
+            uint64_t bases = 0;
+            size_t j = i;
+            for (; j < n_all && all[j].depth == all[i].depth; j++) bases += all[j].bases;
+            if (hist_line(fo, "genome", all[i].depth, bases, gsize)) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+            i = j;
+        }
+    }
+    if (fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    printf("depth histogram of %u contigs, %llu positions, from %llu reads in %u of %u blocks\n", listed, (unsigned long long)gsize,
+           (unsigned long long)reads, blocks_used, u->n_blocks);
+    if (verbose) {
+        printf("depth-hist: %u intervals after merging, %u blocks selected, %llu BED lines selected nothing, fold at %u, exclude flags 0x%x\n",
+               T->n_iv, nb, (unsigned long long)T->bed_unselected, max_depth, exclude);
+        printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + histogram + write %.3f s\n", t1 - t0, t_init, t_dev);
+        if (ctx) printf("kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, zero + accumulate %.3f ms, bin compaction %.3f ms\n",
+                        ms[0], ms[1], ms[2], ms[3], ms[4]);
+    }
+    free(all); free(bl); free(ws); free(bc); free(blob);
+    if (Q) cbc_queries_free(Q); else cbc_targets_free(T);
+    cbc_unpack_plan_free(u);
+    return 0;
+}

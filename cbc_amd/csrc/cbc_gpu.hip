@@ -24,6 +24,7 @@
 #include "cbc_depth_body.h"
 #include "cbc_targets_body.h"
 #include "cbc_cov_body.h"
+#include "cbc_hist_body.h"
 #include "cbc_plan.h"
 #include "cbc_stream_body.h"
 #include "cbc_long_body.h"
@@ -153,6 +154,24 @@ __global__ void __launch_bounds__(64)
 cbc_cov_apply_kernel(cbc_cov_args A) { cbc_cov_apply<WaveGPU>(A, blockIdx.x); }
 __global__ void __launch_bounds__(64)
 cbc_cov_lookup_kernel(cbc_cov_args A) { cbc_cov_lookup<WaveGPU>(A, blockIdx.x); }
+
+/* Depth histogram (cbc_gpu_decode_depth_hist, cbc_hist_body.h), behind the same mark / tile / scan / compact passes: a bounded
+ * grid of one-wavefront workgroups adds the runs' lengths to the bins of their depths (shallow bins in the workgroup's LDS table,
+ * flushed once), then one wavefront per tile of bins counts and (after the scan) writes the non-zero ones as pairs */
+__global__ void __launch_bounds__(64)
+cbc_hist_accum_kernel(cbc_hist_args A)
+{
+#ifndef CBC_HIST_NO_LDS
+    __shared__ uint32_t tab[CBC_HIST_LDS];
+#else
+    uint32_t *tab = NULL;
+#endif
+    cbc_hist_accum<WaveGPU>(A, blockIdx.x, tab);
+}
+__global__ void __launch_bounds__(64)
+cbc_hist_count_kernel(cbc_hist_args A) { cbc_hist_count<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_hist_write_kernel(cbc_hist_args A) { cbc_hist_write<WaveGPU>(A, blockIdx.x); }
 
 /* Whole-file stream / general-form fallback (cbc_stream_body.h): one wavefront per stream.  Workgroup w codes streams
  * w, w + gridDim, ... with var table w of the pool, which it re-zeroes between streams. */
@@ -309,7 +328,7 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
 /* grow-only device buffer owned by the context: the host-buffer entry points keep their device arrays between calls
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
-enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_COUNT };
+enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_COUNT };
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
 struct cbc_gpu_ctx {
@@ -327,6 +346,8 @@ struct cbc_gpu_ctx {
     int have_targets_timing;       /* cbc_gpu_decode_targets: 1 = the four events of a reads / SAM call, 2 = the five of a depth call */
     hipEvent_t ev_cov[4];          /* cbc_gpu_decode_coverage: behind ev_rg[3], after the weights, their scans, the apply and the lookup */
     int have_cov_timing;
+    hipEvent_t ev_hist[2];         /* cbc_gpu_decode_depth_hist: behind ev_rg[3], after zeroing + accumulate and after the bin compaction */
+    int have_hist_timing;
     int have_timing;
     int last_variant;              /* waves per SIMD of the encode build launched last */
     int n_cus;                     /* compute units of the device (block residency decides the kernel build) */
@@ -405,6 +426,8 @@ API int cbc_gpu_init(int device_ordinal, cbc_gpu_ctx **out)
         if (hipEventCreate(&ctx->ev_rg[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     for (int k = 0; k < 4; k++)
         if (hipEventCreate(&ctx->ev_cov[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
+    for (int k = 0; k < 2; k++)
+        if (hipEventCreate(&ctx->ev_hist[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) != hipSuccess || cus <= 0) cus = 256;
@@ -434,6 +457,7 @@ API int cbc_gpu_shutdown(cbc_gpu_ctx *ctx)
     for (int k = 0; k < CBC_MAX_CHUNKS; k++) (void)hipEventDestroy(ctx->ev_chunk[k]);
     for (int k = 0; k < 5; k++) (void)hipEventDestroy(ctx->ev_rg[k]);
     for (int k = 0; k < 4; k++) (void)hipEventDestroy(ctx->ev_cov[k]);
+    for (int k = 0; k < 2; k++) (void)hipEventDestroy(ctx->ev_hist[k]);
     for (int k = 0; k < CBC_N_KSTREAMS; k++) { (void)hipEventDestroy(ctx->ev_done[k]); (void)hipStreamDestroy(ctx->s_k[k]); }
     (void)hipStreamDestroy(ctx->s_copy);
     (void)hipStreamDestroy(ctx->stream);
@@ -1006,7 +1030,11 @@ struct region_req {
     const struct targets_req *tg;
     /* per-query summary instead of the depth text (cbc_gpu_decode_coverage): cov != NULL, with depth and tg */
     const struct cov_req *cov;
+    /* depth histogram instead of the depth text (cbc_gpu_decode_depth_hist): hist != NULL, with depth and tg, without cov */
+    const struct hist_req *hist;
 };
+/* the depth from which the bins fold (2^32 - 1: none), where the pairs go (bin_cap of each) and how many there are */
+struct hist_req { uint32_t fold; uint32_t *bin_depth, *bin_bases; uint32_t bin_cap; uint32_t *n_bins; };
 /* the queries (n_q pairs slot, len in the compressed coordinate), the depth that counts as covered, where the results go */
 struct cov_req { const uint32_t *q; uint32_t n_q, min_depth; uint64_t *sum; uint32_t *covered; };
 /* the interval table (n_iv pairs), per block its range of it, and for the depth the first slot of every interval in the
@@ -1039,6 +1067,11 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     const uint32_t cp_cap = depth ? (uint32_t)(2u * n_recs + (tg ? 2u * (uint64_t)tg->n_iv : 0u)) : 0u;   /* + two per interval edge */
     const uint32_t n_ttiles = (cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
     const uint32_t n_sized = depth ? n_ttiles : n_blocks;        /* entries the text's size scan runs over */
+    const hist_req *hist = depth && tg && !cov ? rg->hist : NULL;
+    /* histogram: min(fold, reads) + 1 bins in whole tiles; the non-zero ones are fewer than the bins and than the runs */
+    const uint64_t h_bins = hist ? (n_recs < hist->fold ? n_recs : hist->fold) + 1u : 0u;
+    const uint32_t n_btiles = (uint32_t)((h_bins + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
+    const uint32_t h_out_cap = hist ? (uint32_t)(h_bins - 1u < cp_cap ? h_bins - 1u : cp_cap) : 0u;
     uint32_t dctr[4] = { 0, 0, 0, 0 };
     const uint32_t stride = blocks[0].seq_stride;
     cbc_block_result *res = NULL;
@@ -1046,7 +1079,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     const uint64_t n_words = two_bit ? n_recs * (stride >> 4) : 0;
     unsigned long long got = 0;
     cbc_block_result *cnt = NULL;                             /* region decode: the filter's per-block counts */
-    uint64_t total = 0, kept = 0;
+    uint64_t total = 0, kept = 0, h_count = 0;
     if (!long_reads) NEED(A_VS, (uint64_t)n_blocks * caps->cap_var * 4 + 16, "hipMalloc var scratch");
     NEED(A_IN, in_bytes + 16, "hipMalloc in");
     NEED(A_BLOCKS, (uint64_t)n_blocks * sizeof(cbc_dec_block_desc), "hipMalloc blocks");
@@ -1095,6 +1128,15 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         }
         NEED(A_CVQ, (uint64_t)cov->n_q * 8 + 16, "hipMalloc coverage queries");
         NEED(A_CVOUT, (uint64_t)cov->n_q * 12 + 16, "hipMalloc coverage results");
+    }
+    if (hist) {
+        if (arena_need(ctx, A_HBINS, (uint64_t)n_btiles * CBC_DEPTH_TILE * 4, "hipMalloc histogram bins") ||
+            arena_need(ctx, A_HOUT, (uint64_t)h_out_cap * 8 + 16, "hipMalloc histogram pairs")) {
+            (void)hipGetLastError();
+            rc = set_err(ctx, CBC_E_NOMEM, "no device memory for the histogram's bins (4 bytes per bin, 8 per non-zero one)", hipSuccess);
+            goto done;
+        }
+        NEED(A_HTILE, (uint64_t)n_btiles * sizeof(cbc_block_result) + ((uint64_t)n_btiles + 1) * 8, "hipMalloc histogram tiles");
     }
     tm.alloc_s = wall_now() - T0;
     {
@@ -1148,6 +1190,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
             if (rc) goto done;
             if (text) {                                        /* one chunk: filter, scan, text on the decode's stream */
                 GO(hipEventRecord(ctx->ev_rg[1], ks), "hipEventRecord");
+                ctx->have_hist_timing = 0;
                 cbc_region_args ra;
                 memset(&ra, 0, sizeof ra);
                 ra.recs = d_recs; ra.seq = d_seq; ra.blocks = d_blocks; ra.window_start = (const uint64_t *)ctx->arena[A_RWS].p;
@@ -1211,6 +1254,30 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                         GO(hipGetLastError(), "launch cbc_cov_lookup_kernel");
                         GO(hipEventRecord(ctx->ev_cov[3], ks), "hipEventRecord");
                         ctx->have_cov_timing = 1; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0; ctx->have_sam_timing = 0; ctx->have_region_timing = 0;
+                    } else if (hist) {                         /* zero, accumulate, count + scan + write of the bins: no text */
+                        cbc_hist_args ha;
+                        memset(&ha, 0, sizeof ha);
+                        ha.cp_pos = da.cp_pos; ha.cp_dep = da.cp_dep; ha.cnt_off = da.cnt_off;
+                        ha.bins = (uint32_t *)ctx->arena[A_HBINS].p;
+                        ha.tile_nz = (cbc_block_result *)ctx->arena[A_HTILE].p;
+                        uint64_t *hoff = (uint64_t *)(ha.tile_nz + n_btiles);
+                        ha.nz_off = hoff;
+                        ha.out_depth = (uint32_t *)ctx->arena[A_HOUT].p; ha.out_bases = ha.out_depth + h_out_cap;
+                        ha.cp_cap = cp_cap; ha.n_tiles = n_tiles; ha.n_ttiles = n_ttiles; ha.fold = hist->fold;
+                        ha.n_bins = (uint32_t)h_bins; ha.n_btiles = n_btiles; ha.out_cap = h_out_cap;
+                        ha.grid = n_ttiles < CBC_HIST_GRID ? n_ttiles : CBC_HIST_GRID;
+                        GO(hipMemsetAsync(ha.bins, 0, (uint64_t)n_btiles * CBC_DEPTH_TILE * 4, ks), "memset histogram bins");
+                        hipLaunchKernelGGL(cbc_hist_accum_kernel, dim3(ha.grid), dim3(64), 0, ks, ha);
+                        GO(hipGetLastError(), "launch cbc_hist_accum_kernel");
+                        GO(hipEventRecord(ctx->ev_hist[0], ks), "hipEventRecord");
+                        hipLaunchKernelGGL(cbc_hist_count_kernel, dim3(n_btiles), dim3(64), 0, ks, ha);
+                        GO(hipGetLastError(), "launch cbc_hist_count_kernel");
+                        hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ha.tile_nz, hoff, n_btiles);
+                        GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+                        hipLaunchKernelGGL(cbc_hist_write_kernel, dim3(n_btiles), dim3(64), 0, ks, ha);
+                        GO(hipGetLastError(), "launch cbc_hist_write_kernel");
+                        GO(hipEventRecord(ctx->ev_hist[1], ks), "hipEventRecord");
+                        ctx->have_hist_timing = 1; ctx->have_cov_timing = 0; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0; ctx->have_sam_timing = 0; ctx->have_region_timing = 0;
                     } else {
                     if (tg) hipLaunchKernelGGL(cbc_targets_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, ta);
                     else hipLaunchKernelGGL(cbc_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
@@ -1299,7 +1366,8 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         if (two_bit) GO(hipMemcpyAsync(&got, ctx->arena[A_CNT].p, 8, hipMemcpyDeviceToHost, sc), "D2H counter");
         if (depth) {
             GO(hipMemcpyAsync(dctr, ctx->arena[A_DCTR].p, 16, hipMemcpyDeviceToHost, sc), "D2H depth counters");
-            if (!cov) GO(hipMemcpyAsync(&total, (uint64_t *)ctx->arena[A_OFF].p + n_ttiles, 8, hipMemcpyDeviceToHost, sc), "D2H text size");
+            if (hist) GO(hipMemcpyAsync(&h_count, (uint64_t *)((cbc_block_result *)ctx->arena[A_HTILE].p + n_btiles) + n_btiles, 8, hipMemcpyDeviceToHost, sc), "D2H histogram size");
+            else if (!cov) GO(hipMemcpyAsync(&total, (uint64_t *)ctx->arena[A_OFF].p + n_ttiles, 8, hipMemcpyDeviceToHost, sc), "D2H text size");
             else {                                             /* the numbers, not the track: 12 bytes per query */
                 GO(hipMemcpyAsync(cov->sum, ctx->arena[A_CVOUT].p, (uint64_t)cov->n_q * 8, hipMemcpyDeviceToHost, sc), "D2H coverage sums");
                 GO(hipMemcpyAsync(cov->covered, (uint64_t *)ctx->arena[A_CVOUT].p + cov->n_q, (uint64_t)cov->n_q * 4, hipMemcpyDeviceToHost, sc), "D2H coverage counts");
@@ -1322,6 +1390,20 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 GO(hipStreamSynchronize(sc), "D2H region text");
             }
             tm.d2h_bytes = total;
+        }
+        if (hist) {                                            /* the pairs: exactly as many as there are; none when a block failed */
+            bool failed = false;
+            for (uint32_t b = 0; b < n_blocks && !failed; b++) failed = res[b].status != CBC_ST_OK;
+            if (!failed) {
+                *hist->n_bins = h_count > 0xffffffffull ? 0xffffffffu : (uint32_t)h_count;
+                if (h_count > h_out_cap || h_count > hist->bin_cap) { rc = set_err(ctx, CBC_E_ARG, "bin_cap too small for the histogram's non-zero bins", hipSuccess); goto done; }
+                if (h_count) {
+                    GO(hipMemcpyAsync(hist->bin_depth, ctx->arena[A_HOUT].p, h_count * 4, hipMemcpyDeviceToHost, sc), "D2H histogram depths");
+                    GO(hipMemcpyAsync(hist->bin_bases, (uint32_t *)ctx->arena[A_HOUT].p + h_out_cap, h_count * 4, hipMemcpyDeviceToHost, sc), "D2H histogram bases");
+                    GO(hipStreamSynchronize(sc), "D2H histogram");
+                }
+                tm.d2h_bytes = h_count * 8;
+            }
         }
         if (two_bit) {
             *n_exc = got;
@@ -1527,8 +1609,10 @@ static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
                                const uint32_t *block_contig, const char *names, uint32_t names_bytes,
                                const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_gpu_targets *t, uint32_t output,
                                uint32_t exclude_flags, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_reads,
-                               uint64_t *n_runs, cbc_block_result *results, const cov_req *cov, uint32_t iv_first, uint32_t iv_count)
+                               uint64_t *n_runs, cbc_block_result *results, const cov_req *cov, uint32_t iv_first, uint32_t iv_count,
+                               const hist_req *hist = NULL)
 {
+    const bool whole = cov || hist;                            /* the compressed coordinate over all the contig's intervals */
     if (!ctx || !blocks || !caps || !window_start || !block_contig || !names || !contig_name_off || !t || !text_bytes || !n_reads ||
         !n_runs || (text_cap && !text) || output > CBC_TARGETS_DEPTH) return CBC_E_ARG;
     *text_bytes = 0; *n_reads = 0; *n_runs = 0;
@@ -1562,7 +1646,7 @@ static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
         const uint32_t f = t->block_iv[2 * b], c = t->block_iv[2 * b + 1];
         if (f > t->n_iv || c > t->n_iv - f) { bad = "targets decode: a block's interval range lies outside the table"; break; }
         if (depth && block_contig[b] != block_contig[0]) { bad = "targets decode: a depth call takes the blocks of one contig"; break; }
-        if (cov && c && (f < iv_first || f - iv_first > iv_count || c > iv_count - (f - iv_first))) {
+        if (whole && c && (f < iv_first || f - iv_first > iv_count || c > iv_count - (f - iv_first))) {
             bad = "coverage: a block's interval range lies outside the contig's intervals"; break; }
         if (c) { if (f < lo) lo = f; if (f + c > hi) hi = f + c; }
         bn[2 * b] = off; bn[2 * b + 1] = (uint32_t)nl;
@@ -1577,7 +1661,7 @@ static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
     if (!bad && depth && nrec > 0x3fffffffull) bad = "targets decode: more than 2^30 - 1 reads in one depth call";
     if (bad) { free(bl); free(bn); free(biv); return set_err(ctx, CBC_E_ARG, bad, hipSuccess); }
     if (nrec == 0 || (depth && lo >= hi)) { free(bl); free(bn); free(biv); return CBC_OK; }   /* no read, or none that reaches an interval */
-    if (cov) { lo = iv_first; hi = iv_first + iv_count; }      /* the slots of the queries count from the contig's first interval */
+    if (whole) { lo = iv_first; hi = iv_first + iv_count; }      /* the slots of the queries count from the contig's first interval */
     for (uint32_t b = 0; b < n_blocks; b++) bl[b].in_off -= in0;
     targets_req tq = { t->iv, t->n_iv, t->block_iv, NULL };
     depth_req dq = { exclude_flags, n_runs };
@@ -1607,7 +1691,7 @@ static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
     }
     region_req rg = { window_start, 1u, UINT64_MAX, t->smax, text, text_cap < need ? text_cap : need, text_bytes, n_reads,
                       sam ? bn : NULL, depth ? (const uint8_t *)names + bn[0] : (const uint8_t *)names, depth ? nl0 : names_bytes, 1,
-                      depth ? &dq : NULL, &tq, cov };
+                      depth ? &dq : NULL, &tq, cov, hist };
     int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
                                 nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
     free(bl); free(bn); free(biv); free(ioff);
@@ -1645,6 +1729,41 @@ API int cbc_gpu_decode_coverage(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in
     return decode_targets_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
                                n_contigs, t, CBC_TARGETS_DEPTH, exclude_flags, NULL, 0, &text_bytes, n_reads, &n_runs, results, &cq,
                                iv_first, iv_count);
+}
+
+/* depth histogram: the depth form of cbc_gpu_decode_targets up to the change points, laid over all the
+ * contig's intervals as for the coverage summary, then zero + accumulate and the compaction of the bins (cbc_hist_body.h); only
+ * the non-zero bins come back */
+API int cbc_gpu_decode_depth_hist(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                  uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                                  const uint32_t *block_contig, const char *names, uint32_t names_bytes,
+                                  const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_gpu_targets *t,
+                                  uint32_t iv_first, uint32_t iv_count, uint32_t exclude_flags, uint32_t max_depth,
+                                  uint32_t *bin_depth, uint32_t *bin_bases, uint32_t bin_cap, uint32_t *n_bins, uint64_t *n_reads,
+                                  cbc_block_result *results)
+{
+    if (!ctx || !t || !n_reads || !n_bins || (bin_cap && (!bin_depth || !bin_bases))) return CBC_E_ARG;
+    *n_reads = 0; *n_bins = 0;
+    if (iv_count < 1 || iv_first > t->n_iv || iv_count > t->n_iv - iv_first)
+        return set_err(ctx, CBC_E_ARG, "depth histogram wants the contig's intervals inside the table", hipSuccess);
+    const hist_req hq = { max_depth ? max_depth : 0xffffffffu, bin_depth, bin_bases, bin_cap, n_bins };
+    uint64_t text_bytes = 0, n_runs = 0;
+    return decode_targets_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
+                               n_contigs, t, CBC_TARGETS_DEPTH, exclude_flags, NULL, 0, &text_bytes, n_reads, &n_runs, results, NULL,
+                               iv_first, iv_count, &hq);
+}
+
+/* kernel times of the most recent cbc_gpu_decode_depth_hist */
+API int cbc_gpu_last_hist_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *accum_ms, float *compact_ms)
+{
+    if (!ctx || !decode_ms || !mark_ms || !scan_ms || !accum_ms || !compact_ms || !ctx->have_hist_timing) return CBC_E_ARG;
+    HIPCHK(hipEventSynchronize(ctx->ev_hist[1]), "hipEventSynchronize");
+    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(mark_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(scan_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(accum_ms, ctx->ev_rg[3], ctx->ev_hist[0]), "hipEventElapsedTime");
+    HIPCHK(hipEventElapsedTime(compact_ms, ctx->ev_hist[0], ctx->ev_hist[1]), "hipEventElapsedTime");
+    return CBC_OK;
 }
 
 /* kernel times of the most recent cbc_gpu_decode_coverage */

@@ -56,6 +56,11 @@ static void usage(const char *p)
             "                   given: NAME, start, end, sum of the depth, positions with depth >= D, mean depth with two decimals;\n"
             "                   depth as for --depth; the numbers are computed on the device; not with --sam or --depth)\n"
             "         --window N (with --bedcov: cut every query into windows of N bases)  --min-depth D (with --bedcov: default 1)\n"
+            "         --depth-hist (per contig and depth how many positions have it: NAME, depth, bases, positions counted, fraction\n"
+            "                       with six decimals; then the same summed under the name genome; depth as for --depth; whole contigs,\n"
+            "                       or the merged intervals of --region / --regions-file; binned on the device; takes\n"
+            "                       --depth-exclude-flags; not with --sam, --depth or --bedcov)\n"
+            "         --hist-max M (with --depth-hist: count every depth >= M in bin M; default: no folding)\n"
             "options: -l (header read length = longest read)  --block-reads N (default 4096)  --device N (default 0)\n"
             "         --threads N (SAM parser threads, default one per CPU)  --verbose (stage times)\n"
             "         --compat (write the reference's own single-stream format; slow: one stream = one wavefront)\n"
@@ -440,6 +445,8 @@ int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref,
                                const char *bed_path, uint32_t output, uint32_t exclude, int verbose);
 int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                               const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose);
+int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                            const char *bed_path, uint32_t max_depth, uint32_t exclude, int verbose);
 
 int main(int argc, char **argv)
 {
@@ -455,6 +462,8 @@ int main(int argc, char **argv)
     int bedcov = 0, window_given = 0, min_depth_given = 0;
     uint64_t cov_window = 0;
     uint32_t cov_min_depth = 1;
+    int depth_hist = 0, hist_max_given = 0;
+    uint32_t hist_max = 0;
     g_main_t0 = now_s();
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
@@ -493,6 +502,15 @@ int main(int argc, char **argv)
                 fprintf(stderr, w ? "cbc: --window wants a number of bases, 1 or more\n" : "cbc: --min-depth wants a depth in 1..4294967295\n"); return 1; }
             if (w) { cov_window = x; window_given = 1; } else { cov_min_depth = (uint32_t)x; min_depth_given = 1; }
             continue;
+        }
+        if (!strcmp(a, "--depth-hist")) { depth_hist = 1; continue; }
+        if (!strcmp(a, "--hist-max") && i + 1 < argc) {
+            char *e = NULL;
+            const char *v = argv[++i];
+            const unsigned long long x = strtoull(v, &e, 10);
+            if (v[0] < '0' || v[0] > '9' || !e || *e || strlen(v) > 18 || x < 1 || x > 0xffffffffull) {
+                fprintf(stderr, "cbc: --hist-max wants a depth in 1..4294967295\n"); return 1; }
+            hist_max = (uint32_t)x; hist_max_given = 1; continue;
         }
         if (!strcmp(a, "--compat")) { compat = 1; continue; }
         if (!strcmp(a, "--long")) { long_reads = 1; continue; }
@@ -546,6 +564,12 @@ int main(int argc, char **argv)
     if (bedcov && mode != 2) { fprintf(stderr, "cbc: --bedcov applies to decompression (-d / -x)\n"); return 1; }
     if (bedcov && (sam_out || depth_out)) { fprintf(stderr, "cbc: --bedcov, --depth and --sam are different outputs; give one of them\n"); return 1; }
     if (bedcov && ndev > 1) { fprintf(stderr, "cbc: --bedcov decodes on one device; give a single --devices ordinal\n"); return 1; }
+    if (hist_max_given && !depth_hist) { fprintf(stderr, "cbc: --hist-max applies to --depth-hist\n"); return 1; }
+    if (depth_hist && mode != 2) { fprintf(stderr, "cbc: --depth-hist applies to decompression (-d / -x)\n"); return 1; }
+    if (depth_hist && (sam_out || depth_out || bedcov)) { fprintf(stderr, "cbc: --depth-hist, --bedcov, --depth and --sam are different outputs; give one of them\n"); return 1; }
+    if (depth_hist && ndev > 1) { fprintf(stderr, "cbc: --depth-hist decodes on one device; give a single --devices ordinal\n"); return 1; }
+    if (depth_hist)
+        return cbc_cli_decompress_hist(files[0], files[1], files[2], device, regions, n_regions, regions_file, hist_max, depth_exclude, verbose);
     if (depth_excl_given && !depth_out && !bedcov) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
     if (bedcov)
         return cbc_cli_decompress_bedcov(files[0], files[1], files[2], device, regions, n_regions, regions_file, cov_window, cov_min_depth,

@@ -2185,6 +2185,26 @@ API int cbc_coverage_mean(uint64_t sum, uint64_t len, char *dst)
     return sprintf(dst, "%llu.%02u", (unsigned long long)(m / 100u), (unsigned)(m % 100u));
 }
 
+/* ---- depth histogram (include/cbc_host.h) ---- */
+API uint64_t cbc_unpack_targets_size(const cbc_targets *t, uint32_t contig)
+{
+    if (!t || contig >= t->n_contigs) return 0;
+    uint64_t n = 0;
+    for (uint32_t i = 0; i < t->contig_count[contig]; i++) {
+        const cbc_target_iv *v = &t->iv[t->contig_first[contig] + i];
+        n += (uint64_t)(v->end - v->beg) + 1u;
+    }
+    return n;
+}
+
+API int cbc_hist_fraction(uint64_t bases, uint64_t size, char *dst)
+{
+    if (!dst) return CBC_E_ARG;
+    uint64_t m = 0;
+    if (size) m = (uint64_t)(((unsigned __int128)bases * 1000000u + size / 2u) / size);   /* 128 bits: a genome's sums are 64 */
+    return sprintf(dst, "%llu.%06u", (unsigned long long)(m / 1000000u), (unsigned)(m % 1000000u));
+}
+
 API int cbc_unpack_queries(const cbc_unpack_plan *u, const char *const *regions, uint32_t n_regions, const char *bed, size_t bed_len,
                            uint64_t window, cbc_queries **out, char *errbuf, size_t errlen)
 {

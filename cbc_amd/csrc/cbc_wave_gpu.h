@@ -102,6 +102,10 @@ struct WaveGPU {
     /* OR into LDS words: lanes may name the same word (ds_or_b32) */
     static CBC_FN void lds_add(uint32_t *p, V32 idx, V32 val, Mask m) { if (m) __hip_atomic_fetch_add(p + idx, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
     static CBC_FN void lds_or(uint32_t *p, V32 idx, V32 val, Mask m) { if (m) __hip_atomic_fetch_or(p + idx, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    /* a table in LDS that ONE wavefront owns (cbc_hist_body.h): zero a word and read it back around the lds_add above; the
+     * wavefront's LDS operations complete in the order it issues them, so no barrier stands between them */
+    static CBC_FN void lds_zero(uint32_t *p, V32 idx, Mask m) { if (m) p[idx] = 0u; }
+    static CBC_FN V32 lds_read(const uint32_t *p, V32 idx, Mask m) { return m ? p[idx] : 0u; }
     static CBC_FN void set_lane(V32 &v, uint32_t k, uint32_t val) { v = lane() == k ? val : v; }
     static CBC_FN V32 bswap_v(V32 x) { return __builtin_bswap32(x); }
     /* A wave-uniform value deliberately kept in a VECTOR register: every lane computes the same thing.

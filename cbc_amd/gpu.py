@@ -250,6 +250,15 @@ def lib():
                                               ctypes.c_void_p]
         L.cbc_gpu_last_coverage_ms.restype = ctypes.c_int
         L.cbc_gpu_last_coverage_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 7
+        L.cbc_gpu_decode_depth_hist.restype = ctypes.c_int
+        L.cbc_gpu_decode_depth_hist.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                                ctypes.POINTER(host.LdsCaps), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(GpuTargets),
+                                                ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.cbc_gpu_last_hist_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_hist_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 5
         L.cbc_gpu_last_depth_ms.restype = ctypes.c_int
         L.cbc_gpu_last_depth_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         if L.cbc_gpu_abi_version() != 1:
@@ -273,7 +282,7 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_stash_reset", "cbc_gpu_stash_bytes", "cbc_gpu_stash_fetch", "cbc_gpu_decode_region",
            "cbc_gpu_decode_blocks_span", "cbc_gpu_last_region_ms", "cbc_gpu_decode_sam", "cbc_gpu_last_sam_ms",
            "cbc_gpu_decode_depth", "cbc_gpu_last_depth_ms", "cbc_gpu_decode_targets", "cbc_gpu_last_targets_ms",
-           "cbc_gpu_decode_coverage", "cbc_gpu_last_coverage_ms"]
+           "cbc_gpu_decode_coverage", "cbc_gpu_last_coverage_ms", "cbc_gpu_decode_depth_hist", "cbc_gpu_last_hist_ms"]
 
 
 class Encoder:
@@ -673,6 +682,74 @@ class Encoder:
         if getattr(self, "_coverage_ms", None) is None:
             raise CbcGpuError("no decode_coverage has run on the device")
         return self._coverage_ms
+
+    def decode_depth_hist(self, plan: "host.UnpackPlan", targets=None, exclude_flags=0, max_depth=0, results=False):
+        """Depth histogram (cbc_gpu_decode_depth_hist): per contig how many positions have each depth; depth as decode_depth
+        counts it (reads with FLAG & exclude_flags != 0 left out).  targets=None: every contig of the container's table, whole;
+        a host.TargetSet of plan.targets(): the positions of its merged intervals, every position once, and a contig is listed
+        when an interval lies on it.  max_depth > 0: every depth >= max_depth is counted in bin max_depth.  One call and one
+        decode per contig that has blocks; only the non-zero bins cross PCIe, and the depth-0 bin is size less their sum.
+        Returns a list, in table order, of (contig, depth (uint32, ascending), bases (uint64, all > 0), size) with
+        bases.sum() == size.  With results=True returns (that list, the per-block decode results of the blocks decoded) and
+        lets a failed block pass (its contig's call gives no bins: everything in depth 0); otherwise it raises CbcGpuError."""
+        plan.sam_header()                                     # refuses what the coordinates cannot carry, and long-read containers
+        ts = plan.queries().targets if targets is None else targets
+        if not 0 <= int(max_depth) <= 0xffffffff:
+            raise ValueError("max_depth is 0 (no folding) or 1 .. 2^32 - 1")
+        self._hist_ms = None
+        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
+        pay = np.ascontiguousarray(plan.payloads)
+        names = np.ascontiguousarray(plan.names)
+        noff = np.ascontiguousarray(plan.contig_name_off, dtype=np.uint32)
+        iv = np.ascontiguousarray(ts.iv, dtype=np.uint32)
+        out, allres = [], []
+        for c in range(ts.n_contigs):
+            k0, nb, f, ni = int(ts.contig_blk_first[c]), int(ts.contig_blk_count[c]), int(ts.contig_first[c]), int(ts.contig_count[c])
+            if not ni:
+                continue
+            size = ts.size[c]
+            depth, bases = np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint64)
+            if nb:
+                sel = np.ascontiguousarray(ts.blocks[k0:k0 + nb]).astype(np.int64)
+                blocks = np.ascontiguousarray(plan.blocks[sel])
+                ws = np.ascontiguousarray(plan.window_start[sel], dtype=np.uint64)
+                bc = np.ascontiguousarray(plan.block_contig[sel], dtype=np.uint32)
+                biv = np.ascontiguousarray(ts.block_iv[k0:k0 + nb], dtype=np.uint32)
+                cap = max(1, min(int(blocks["n_reads"].astype(np.int64).sum()), int(max_depth) or 0xffffffff))
+                bd, bb = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+                res = np.zeros(nb, dtype=host.RESULT_DTYPE)
+                nbin, nrd = ctypes.c_uint32(), ctypes.c_uint64()
+                tg = GpuTargets(iv.ctypes.data, biv.ctypes.data, ts.n_iv, ts.smax)
+                rc = lib().cbc_gpu_decode_depth_hist(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
+                                                     ws.ctypes.data, bc.ctypes.data, names.ctypes.data, names.size, noff.ctypes.data,
+                                                     plan.n_contigs, ctypes.byref(tg), f, ni, int(exclude_flags), int(max_depth),
+                                                     bd.ctypes.data, bb.ctypes.data, cap, ctypes.byref(nbin), ctypes.byref(nrd),
+                                                     res.ctypes.data)
+                if rc != 0 and not (results and rc == -4):
+                    self._check(rc, "cbc_gpu_decode_depth_hist")
+                v = [ctypes.c_float() for _ in range(5)]
+                if lib().cbc_gpu_last_hist_ms(self._ctx, *[ctypes.byref(x) for x in v]) == 0:
+                    ms = tuple(float(x.value) for x in v)
+                    self._hist_ms = ms if self._hist_ms is None else tuple(a + b for a, b in zip(self._hist_ms, ms))
+                n = int(nbin.value)
+                depth, bases = bd[:n].copy(), bb[:n].astype(np.uint64)
+                allres.append(res)
+            zero = size - int(bases.sum())
+            if zero < 0:
+                raise CbcGpuError("cbc_gpu_decode_depth_hist: the bins of contig %d hold more positions than its intervals" % c)
+            if zero:
+                depth, bases = np.concatenate([np.zeros(1, dtype=np.uint32), depth]), np.concatenate([np.array([zero], dtype=np.uint64), bases])
+            out.append((c, depth, bases, size))
+        if results:
+            return out, (np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE))
+        return out
+
+    def last_hist_ms(self):
+        """(decode, mark, scan + compact, zero + accumulate, bin compaction) kernel milliseconds of the last decode_depth_hist,
+        summed over its calls."""
+        if getattr(self, "_hist_ms", None) is None:
+            raise CbcGpuError("no decode_depth_hist has run on the device")
+        return self._hist_ms
 
     def last_targets_ms(self):
         """(decode, count + scan or mark, depth scan + compact or 0, text) kernel milliseconds of the last decode_targets,

@@ -222,8 +222,21 @@ def lib():
         L.cbc_queries_free.argtypes = [ctypes.POINTER(QueriesC)]
         L.cbc_coverage_mean.restype = ctypes.c_int
         L.cbc_coverage_mean.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p]
+        L.cbc_unpack_targets_size.restype = ctypes.c_uint64
+        L.cbc_unpack_targets_size.argtypes = [ctypes.POINTER(TargetsC), ctypes.c_uint32]
+        L.cbc_hist_fraction.restype = ctypes.c_int
+        L.cbc_hist_fraction.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p]
         _lib = L
     return _lib
+
+
+def hist_fraction(bases: int, size: int) -> bytes:
+    """bases / size with six decimals by the integer rule of cbc_hist_fraction (what `cbc --depth-hist` prints)."""
+    buf = ctypes.create_string_buffer(40)
+    n = lib().cbc_hist_fraction(int(bases), int(size), buf)
+    if n < 0:
+        raise ValueError("cbc_hist_fraction failed (%d)" % n)
+    return buf.raw[:n]
 
 
 def coverage_mean(total: int, length: int) -> bytes:
@@ -483,7 +496,8 @@ class TargetSet:
     block_iv      (n_blocks, 2) uint32: per selected block the first interval and the count of those its reads can reach
     contig_blk_first, contig_blk_count   per contig: its part of blocks
     smax, bed_unselected (BED lines that selected nothing), n_input (regions + BED lines taken, before merging),
-    text_cap_reads, text_cap_sam, depth_cap[c]: buffer sizes that always hold the output."""
+    text_cap_reads, text_cap_sam, depth_cap[c]: buffer sizes that always hold the output;
+    size[c]: the positions inside contig c's merged intervals (cbc_unpack_targets_size)."""
 
     def __init__(self, plan, ptr):
         t = ptr.contents
@@ -500,6 +514,7 @@ class TargetSet:
         self.text_cap_reads = int(lib().cbc_unpack_targets_text_cap(plan._ptr, ptr, 0))
         self.text_cap_sam = int(lib().cbc_unpack_targets_text_cap(plan._ptr, ptr, 1))
         self.depth_cap = [int(lib().cbc_unpack_targets_depth_cap(plan._ptr, ptr, c)) for c in range(nc)]
+        self.size = [int(lib().cbc_unpack_targets_size(ptr, c)) for c in range(nc)]
 
     def intervals(self):
         """[(contig, beg, end)] of the merged intervals, in order."""

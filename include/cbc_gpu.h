@@ -413,6 +413,31 @@ int  cbc_gpu_decode_coverage(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_by
 int  cbc_gpu_last_coverage_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *weights_ms,
                               float *wscan_ms, float *apply_ms, float *lookup_ms);
 
+/* ---- depth histogram --------------------------------------------------------------------------------
+ * The depth form of cbc_gpu_decode_targets -- the selected blocks of ONE contig, decoded once, marked in the compressed
+ * coordinate of all the contig's merged intervals (t, iv_first, iv_count as for cbc_gpu_decode_coverage) -- without the text:
+ * how many positions inside the intervals have each depth >= 1, binned on the device from the change points.  Depth is that of
+ * cbc_gpu_decode_depth (span coverage, reads with FLAG & exclude_flags != 0 left out).  max_depth > 0: every depth >= max_depth
+ * is counted in bin max_depth (0: no folding).
+ *   bin_depth[bin_cap], bin_bases[bin_cap]   the bins with bases > 0, ascending in depth.  The depth-0 bin is never among
+ *                           them: it is the positions of the intervals less the sum of bin_bases, the caller's subtraction.
+ *   *n_bins                 how many there are, also when bin_cap is too small (CBC_E_ARG, nothing copied); at most
+ *                           min(max_depth or 2^32 - 1, reads of the call's blocks)
+ * A bin is 32 bits on the device and exact: its bases are at most the slots of one contig's compressed coordinate,
+ * <= 2^31 + 2^24 < 2^32.  The bin table costs 4 bytes per depth up to min(max_depth, reads): CBC_E_NOMEM when it or the
+ * difference array cannot be had.  One call runs as one chunk on one stream with no host round trip between its kernels.  A
+ * block that fails to decode contributes nothing; the call returns CBC_E_BLOCK with *n_bins = 0.  *n_reads = reads counted. */
+int  cbc_gpu_decode_depth_hist(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                               uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                               const uint32_t *block_contig /* n_blocks */, const char *names, uint32_t names_bytes,
+                               const uint32_t *contig_name_off /* n_contigs */, uint32_t n_contigs, const cbc_gpu_targets *t,
+                               uint32_t iv_first, uint32_t iv_count, uint32_t exclude_flags, uint32_t max_depth,
+                               uint32_t *bin_depth, uint32_t *bin_bases, uint32_t bin_cap, uint32_t *n_bins, uint64_t *n_reads,
+                               cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_depth_hist: the span decode; zeroing + mark; tile sums, scans and change
+ * points; then the new passes: zeroing the bins + accumulate, and the count, scan and write of the non-zero bins. */
+int  cbc_gpu_last_hist_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *accum_ms, float *compact_ms);
+
 /* ---- whole-file stream ("compat" mode): the reference's own file format --------------------------------------
  * compress() / decompress(), src/compression.c:112-216: ONE arithmetic stream per file, models never reset.
  * `batch` is a cbc_host_batch packed with cbc_pack_opts.whole_file = 1: its `blocks` are SEGMENTS of the one

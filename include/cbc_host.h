@@ -300,6 +300,14 @@ void     cbc_queries_free(cbc_queries *q);
  * m = q * 100 + (r * 100 + len / 2) / len; len == 0: "0.00".  Returns the characters written (dst holds at least 24). */
 int      cbc_coverage_mean(uint64_t sum, uint64_t len, char *dst);
 
+/* Depth histogram (the bins come from cbc_gpu_decode_depth_hist).  The interval table and the selected
+ * blocks are those of cbc_unpack_targets, or of cbc_unpack_queries without regions for "every contig whole".
+ * cbc_unpack_targets_size: the positions counted on contig c = the sum of the lengths of its merged intervals (0: none).
+ * cbc_hist_fraction: "<m / 10^6>.<six digits of m % 10^6>" of bases / size rounded half up in integers,
+ * m = (bases * 10^6 + size / 2) / size; size == 0: "0.000000".  Returns the characters written (dst holds at least 32). */
+uint64_t cbc_unpack_targets_size(const cbc_targets *t, uint32_t contig);
+int      cbc_hist_fraction(uint64_t bases, uint64_t size, char *dst);
+
 int     cbc_unpack_plan_create(const uint8_t *blob, uint64_t len, const char *fasta, size_t fasta_len,
                                cbc_unpack_plan **out, char *errbuf, size_t errlen);
 void    cbc_unpack_plan_free(cbc_unpack_plan *u);
