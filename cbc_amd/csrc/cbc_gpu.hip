@@ -331,6 +331,10 @@ struct cbc_arena { void *p; uint64_t cap; };
 enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_COUNT };
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
+/* what decode_blocks_impl runs behind the decode (its post-decode stage): nothing (plain, 2-bit, span, long reads), or the
+ * stage of cbc_gpu_decode_region, _sam, _depth, _targets (reads, SAM, depth), _coverage, _depth_hist */
+enum post_kind { POST_NONE, POST_REGION, POST_SAM, POST_DEPTH, POST_TG_READS, POST_TG_SAM, POST_TG_DEPTH, POST_COV, POST_HIST };
+
 struct cbc_gpu_ctx {
     int device;
     hipStream_t stream;
@@ -340,14 +344,10 @@ struct cbc_gpu_ctx {
     hipEvent_t ev_chunk[CBC_MAX_CHUNKS], ev_done[CBC_N_KSTREAMS];
     hipEvent_t ev_rg[5];           /* region decode: before and after the decode, after the filter + scan, after the text kernel;
                                     * coverage: decode, mark, scan + compact, text (the fifth event) */
-    int have_region_timing;
-    int have_sam_timing;           /* the same four events, recorded by cbc_gpu_decode_sam */
-    int have_depth_timing;         /* all five, recorded by cbc_gpu_decode_depth */
-    int have_targets_timing;       /* cbc_gpu_decode_targets: 1 = the four events of a reads / SAM call, 2 = the five of a depth call */
     hipEvent_t ev_cov[4];          /* cbc_gpu_decode_coverage: behind ev_rg[3], after the weights, their scans, the apply and the lookup */
-    int have_cov_timing;
     hipEvent_t ev_hist[2];         /* cbc_gpu_decode_depth_hist: behind ev_rg[3], after zeroing + accumulate and after the bin compaction */
-    int have_hist_timing;
+    post_kind last_post;           /* whose times those events hold: the kind of the most recent call with a post-decode stage
+                                    * (POST_NONE: none yet), set by decode_blocks_impl and asked by the cbc_gpu_last_*_ms */
     int have_timing;
     int last_variant;              /* waves per SIMD of the encode build launched last */
     int n_cus;                     /* compute units of the device (block residency decides the kernel build) */
@@ -1016,40 +1016,382 @@ API int cbc_gpu_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device_batc
     return decode_blocks_launch(ctx, b, hip_stream, 0u);
 }
 
-/* region decode's part of decode_blocks_impl: the span bound, the region, where the text goes and what came of it
- * (text_bytes == NULL: the span decode alone, records and rows come back as in a plain decode) */
-struct depth_req { uint32_t exclude; uint64_t *n_runs; };
-struct region_req {
-    const uint64_t *window_start; uint64_t beg, end; uint32_t smax;
-    uint8_t *text; uint64_t text_cap; uint64_t *text_bytes, *n_selected;
-    /* SAM output (cbc_gpu_decode_sam): block_name != NULL; `region` = keep by [beg, end] (else every read, smax = 0) */
-    const uint32_t *block_name; const uint8_t *names; uint32_t names_bytes; int region;
-    /* coverage (cbc_gpu_decode_depth): depth != NULL; names / names_bytes = the one contig name, n_selected = reads kept */
-    const depth_req *depth;
-    /* a set of regions (cbc_gpu_decode_targets): tg != NULL, beg / end unused */
-    const struct targets_req *tg;
-    /* per-query summary instead of the depth text (cbc_gpu_decode_coverage): cov != NULL, with depth and tg */
-    const struct cov_req *cov;
-    /* depth histogram instead of the depth text (cbc_gpu_decode_depth_hist): hist != NULL, with depth and tg, without cov */
-    const struct hist_req *hist;
-};
-/* the depth from which the bins fold (2^32 - 1: none), where the pairs go (bin_cap of each) and how many there are */
-struct hist_req { uint32_t fold; uint32_t *bin_depth, *bin_bases; uint32_t bin_cap; uint32_t *n_bins; };
+static bool post_is_depth(post_kind k) { return k == POST_DEPTH || k == POST_TG_DEPTH || k == POST_COV || k == POST_HIST; }
+static bool post_is_sam(post_kind k) { return k == POST_SAM || k == POST_TG_SAM; }
+static bool post_is_targets(post_kind k) { return k == POST_TG_READS || k == POST_TG_SAM || k == POST_TG_DEPTH || k == POST_COV || k == POST_HIST; }
+
 /* the queries (n_q pairs slot, len in the compressed coordinate), the depth that counts as covered, where the results go */
 struct cov_req { const uint32_t *q; uint32_t n_q, min_depth; uint64_t *sum; uint32_t *covered; };
-/* the interval table (n_iv pairs), per block its range of it, and for the depth the first slot of every interval in the
- * compressed coordinate (n_iv + 1 entries; NULL for reads / SAM) */
-struct targets_req { const uint32_t *iv; uint32_t n_iv; const uint32_t *block_iv; const uint32_t *iv_off; };
+/* the depth from which the bins fold (2^32 - 1: none), where the pairs go (bin_cap of each) and how many there are */
+struct hist_req { uint32_t fold; uint32_t *bin_depth, *bin_bases; uint32_t bin_cap; uint32_t *n_bins; };
+
+/* What decode_blocks_impl does behind the decode of a one-chunk call.  `kind` alone says which post-decode stage runs;
+ * the members below it are read by the kinds named in front of them and are zero otherwise. */
+struct post_req {
+    post_kind kind;
+    uint32_t smax;                 /* > 0: the span-reporting decoder.  POST_NONE reads nothing else (cbc_gpu_decode_blocks_span) */
+    /* every other kind: per block its window start, where the output text goes and what came of it (coverage and
+     * histogram: text_cap = 0); n_selected = reads kept */
+    const uint64_t *window_start;
+    uint8_t *text; uint64_t text_cap; uint64_t *text_bytes, *n_selected;
+    /* REGION, SAM, DEPTH: keep by [beg, end]; SAM with region == 0 keeps every read (smax = 0).  Targets kinds: 1, 2^64 - 1 */
+    uint64_t beg, end; int region;
+    /* SAM, TG_SAM: the contig-name table and per block the (offset, length) of its name; depth kinds: the one contig name */
+    const uint8_t *names; uint32_t names_bytes; const uint32_t *block_name;
+    /* depth kinds: the flags that drop a read, where the number of runs goes */
+    uint32_t exclude; uint64_t *n_runs;
+    /* targets kinds: the interval table (n_iv pairs), per block its range of it, and for the depth kinds the first slot of
+     * every interval in the compressed coordinate (n_iv + 1 entries) */
+    const uint32_t *iv; uint32_t n_iv; const uint32_t *block_iv, *iv_off;
+    cov_req cov;                   /* COV */
+    hist_req hist;                 /* HIST */
+};
+
+/* sizes derived from the request: tiles of the difference array (d_words = W + 1 words), change points (two per read at most,
+ * two per interval edge), text tiles of the runs, entries the text's size scan runs over; histogram: min(fold, reads) + 1 bins
+ * in whole tiles, the non-zero ones are fewer than the bins and than the runs */
+struct post_sizes { uint64_t d_words, h_bins; uint32_t n_tiles, cp_cap, n_ttiles, n_sized, n_btiles, h_out_cap; };
+
+static post_sizes post_sizes_of(const post_req *rg, uint32_t n_blocks, uint64_t n_recs)
+{
+    post_sizes z;
+    memset(&z, 0, sizeof z);
+    z.n_sized = n_blocks;
+    if (!rg || !post_is_depth(rg->kind)) return z;
+    const bool tg = post_is_targets(rg->kind);
+    z.d_words = tg ? rg->iv_off[rg->n_iv] : rg->end - rg->beg + 2u;
+    z.n_tiles = (uint32_t)((z.d_words + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
+    z.cp_cap = (uint32_t)(2u * n_recs + (tg ? 2u * (uint64_t)rg->n_iv : 0u));
+    z.n_ttiles = (z.cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
+    z.n_sized = z.n_ttiles;
+    if (rg->kind != POST_HIST) return z;
+    z.h_bins = (n_recs < rg->hist.fold ? n_recs : rg->hist.fold) + 1u;
+    z.n_btiles = (uint32_t)((z.h_bins + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
+    z.h_out_cap = (uint32_t)(z.h_bins - 1u < z.cp_cap ? z.h_bins - 1u : z.cp_cap);
+    return z;
+}
+
+/* post stage, step 1: its arenas */
+static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z, uint32_t n_blocks)
+{
+    const post_kind k = rg->kind;
+    int rc = CBC_OK;
+    NEED(A_TEXT, rg->text_cap + 16, "hipMalloc region text");
+    NEED(A_RWS, (uint64_t)n_blocks * 8, "hipMalloc window starts");
+    NEED(A_RCNT, (uint64_t)z.n_sized * sizeof(cbc_block_result), "hipMalloc region counts");
+    NEED(A_OFF, ((uint64_t)z.n_sized + 1) * 8, "hipMalloc region offsets");
+    if (post_is_depth(k)) {
+        if (arena_need(ctx, A_DDIFF, (uint64_t)z.n_tiles * CBC_DEPTH_TILE * 4, "hipMalloc depth window")) {
+            (void)hipGetLastError();
+            return set_err(ctx, CBC_E_NOMEM, "no device memory for the window's difference array (4 bytes per position)", hipSuccess);
+        }
+        NEED(A_DTILE, (uint64_t)z.n_tiles * 2 * sizeof(cbc_block_result), "hipMalloc depth tiles");
+        NEED(A_DTOFF, ((uint64_t)z.n_tiles + 1) * 2 * 8, "hipMalloc depth tile offsets");
+        NEED(A_DCP, (uint64_t)z.cp_cap * 2 * 4 + 16, "hipMalloc depth change points");
+        NEED(A_DCTR, 16, "hipMalloc depth counters");
+        NEED(A_SNAMES, (uint64_t)rg->names_bytes + 16, "hipMalloc contig name");
+    }
+    if (post_is_sam(k)) {
+        NEED(A_SNAMES, (uint64_t)rg->names_bytes + 16, "hipMalloc contig names");
+        NEED(A_SBN, (uint64_t)n_blocks * 8, "hipMalloc block names");
+    }
+    if (post_is_targets(k)) {
+        NEED(A_TIV, (uint64_t)rg->n_iv * 8 + 16, "hipMalloc intervals");
+        NEED(A_TBIV, (uint64_t)n_blocks * 8, "hipMalloc block intervals");
+        if (post_is_depth(k)) NEED(A_TOFF, ((uint64_t)rg->n_iv + 1) * 4, "hipMalloc interval slots");
+    }
+    if (k == POST_COV) {
+        NEED(A_CVTILE, (uint64_t)z.n_ttiles * 3 * sizeof(cbc_block_result) + ((uint64_t)z.n_ttiles + 1) * 3 * 8, "hipMalloc coverage tiles");
+        if (arena_need(ctx, A_CVPRE, (uint64_t)z.cp_cap * 12 + 16, "hipMalloc coverage prefixes")) {
+            (void)hipGetLastError();
+            return set_err(ctx, CBC_E_NOMEM, "no device memory for the coverage prefixes (12 bytes per change point)", hipSuccess);
+        }
+        NEED(A_CVQ, (uint64_t)rg->cov.n_q * 8 + 16, "hipMalloc coverage queries");
+        NEED(A_CVOUT, (uint64_t)rg->cov.n_q * 12 + 16, "hipMalloc coverage results");
+    }
+    if (k == POST_HIST) {
+        if (arena_need(ctx, A_HBINS, (uint64_t)z.n_btiles * CBC_DEPTH_TILE * 4, "hipMalloc histogram bins") ||
+            arena_need(ctx, A_HOUT, (uint64_t)z.h_out_cap * 8 + 16, "hipMalloc histogram pairs")) {
+            (void)hipGetLastError();
+            return set_err(ctx, CBC_E_NOMEM, "no device memory for the histogram's bins (4 bytes per bin, 8 per non-zero one)", hipSuccess);
+        }
+        NEED(A_HTILE, (uint64_t)z.n_btiles * sizeof(cbc_block_result) + ((uint64_t)z.n_btiles + 1) * 8, "hipMalloc histogram tiles");
+    }
+done:
+    return rc;
+}
+
+/* post stage, step 2: its small tables go H2D on the copy stream, behind the payloads */
+static int post_h2d(cbc_gpu_ctx *ctx, const post_req *rg, uint32_t n_blocks, hipStream_t sc)
+{
+    const post_kind k = rg->kind;
+    HIPCHK(hipMemcpyAsync(ctx->arena[A_RWS].p, rg->window_start, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D window starts");
+    if (post_is_depth(k)) HIPCHK(hipMemcpyAsync(ctx->arena[A_SNAMES].p, rg->names, rg->names_bytes, hipMemcpyHostToDevice, sc), "H2D contig name");
+    if (post_is_sam(k)) {
+        HIPCHK(hipMemcpyAsync(ctx->arena[A_SNAMES].p, rg->names, rg->names_bytes, hipMemcpyHostToDevice, sc), "H2D contig names");
+        HIPCHK(hipMemcpyAsync(ctx->arena[A_SBN].p, rg->block_name, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D block names");
+    }
+    if (post_is_targets(k)) {
+        HIPCHK(hipMemcpyAsync(ctx->arena[A_TIV].p, rg->iv, (uint64_t)rg->n_iv * 8, hipMemcpyHostToDevice, sc), "H2D intervals");
+        HIPCHK(hipMemcpyAsync(ctx->arena[A_TBIV].p, rg->block_iv, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D block intervals");
+        if (post_is_depth(k)) HIPCHK(hipMemcpyAsync(ctx->arena[A_TOFF].p, rg->iv_off, ((uint64_t)rg->n_iv + 1) * 4, hipMemcpyHostToDevice, sc), "H2D interval slots");
+    }
+    if (k == POST_COV) HIPCHK(hipMemcpyAsync(ctx->arena[A_CVQ].p, rg->cov.q, (uint64_t)rg->cov.n_q * 8, hipMemcpyHostToDevice, sc), "H2D coverage queries");
+    return CBC_OK;
+}
+
+/* post stage, step 3: the launches, on the decode's stream.  Every kind's kernels take the region arguments first. */
+static void post_region_args(cbc_gpu_ctx *ctx, const post_req *rg, uint32_t n_blocks, uint64_t n_recs, uint64_t seq_bytes, cbc_region_args *ra)
+{
+    memset(ra, 0, sizeof *ra);
+    ra->recs = (cbc_read_rec *)ctx->arena[A_RECS].p; ra->seq = (uint8_t *)ctx->arena[A_SEQ].p;
+    ra->blocks = (cbc_dec_block_desc *)ctx->arena[A_BLOCKS].p; ra->window_start = (const uint64_t *)ctx->arena[A_RWS].p;
+    ra->dec_results = (cbc_block_result *)ctx->arena[A_RES].p; ra->counts = (cbc_block_result *)ctx->arena[A_RCNT].p;
+    ra->offsets = (const uint64_t *)ctx->arena[A_OFF].p;
+    ra->text = (uint8_t *)ctx->arena[A_TEXT].p; ra->text_cap = rg->text_cap; ra->n_recs = n_recs; ra->seq_bytes = seq_bytes + 32;
+    ra->beg = rg->beg; ra->end = rg->end; ra->n_blocks = n_blocks;
+}
+
+static void launch_scan_sizes(hipStream_t s, const cbc_block_result *sizes, uint64_t *offsets, uint32_t n)
+{
+    hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, s, sizes, offsets, n);
+}
+
+/* region text: filter + count, scan, write */
+static int launch_region_text(cbc_gpu_ctx *ctx, hipStream_t ks, const cbc_region_args &ra)
+{
+    hipLaunchKernelGGL(cbc_region_count_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, ra);
+    HIPCHK(hipGetLastError(), "launch cbc_region_count_kernel");
+    launch_scan_sizes(ks, ra.counts, (uint64_t *)ctx->arena[A_OFF].p, ra.n_blocks);
+    HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+    hipLaunchKernelGGL(cbc_region_write_kernel, dim3(ra.n_blocks), dim3(64 * CBC_REGION_WAVES), 0, ks, ra);
+    HIPCHK(hipGetLastError(), "launch cbc_region_write_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
+/* SAM text: the same three steps with the SAM bodies */
+static int launch_sam_text(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const cbc_region_args &ra)
+{
+    cbc_sam_args sa;
+    memset(&sa, 0, sizeof sa);
+    sa.R = ra; sa.block_name = (const uint32_t *)ctx->arena[A_SBN].p; sa.names = (const uint8_t *)ctx->arena[A_SNAMES].p;
+    sa.names_bytes = rg->names_bytes; sa.region = rg->region ? 1u : 0u;
+    hipLaunchKernelGGL(cbc_sam_count_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, sa);
+    HIPCHK(hipGetLastError(), "launch cbc_sam_count_kernel");
+    launch_scan_sizes(ks, ra.counts, (uint64_t *)ctx->arena[A_OFF].p, ra.n_blocks);
+    HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+    hipLaunchKernelGGL(cbc_sam_write_kernel, dim3(ra.n_blocks), dim3(64 * CBC_SAM_WAVES), 0, ks, sa);
+    HIPCHK(hipGetLastError(), "launch cbc_sam_write_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
+/* a set of regions, reads or SAM: the same three steps, kept by the interval table */
+static int launch_targets_text(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const cbc_region_args &ra)
+{
+    const bool sam = rg->kind == POST_TG_SAM;
+    cbc_targets_args ta;
+    memset(&ta, 0, sizeof ta);
+    ta.S.R = ra; ta.iv = (const uint32_t *)ctx->arena[A_TIV].p; ta.block_iv = (const uint32_t *)ctx->arena[A_TBIV].p; ta.n_iv = rg->n_iv;
+    if (sam) {
+        ta.S.block_name = (const uint32_t *)ctx->arena[A_SBN].p; ta.S.names = (const uint8_t *)ctx->arena[A_SNAMES].p;
+        ta.S.names_bytes = rg->names_bytes;
+        hipLaunchKernelGGL(cbc_targets_sam_count_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, ta);
+    } else hipLaunchKernelGGL(cbc_targets_count_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, ta);
+    HIPCHK(hipGetLastError(), "launch cbc_targets_count_kernel");
+    launch_scan_sizes(ks, ra.counts, (uint64_t *)ctx->arena[A_OFF].p, ra.n_blocks);
+    HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+    if (sam) hipLaunchKernelGGL(cbc_targets_sam_write_kernel, dim3(ra.n_blocks), dim3(64 * CBC_SAM_WAVES), 0, ks, ta);
+    else hipLaunchKernelGGL(cbc_targets_write_kernel, dim3(ra.n_blocks), dim3(64 * CBC_REGION_WAVES), 0, ks, ta);
+    HIPCHK(hipGetLastError(), "launch cbc_targets_write_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
+/* the front of every depth kind: mark, tile sums, their two scans, the change points.  `da` and `ta` (filled for the targets
+ * kinds, whose mark kernel reads the interval table) are what the tails go on with. */
+static int launch_depth_front(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const post_sizes &z, const cbc_region_args &ra,
+                              cbc_depth_args *da, cbc_tdepth_args *ta)
+{
+    const uint32_t n_tiles = z.n_tiles;
+    memset(da, 0, sizeof *da);
+    da->R = ra;
+    da->diff = (uint32_t *)ctx->arena[A_DDIFF].p; da->diff_words = (uint64_t)n_tiles * CBC_DEPTH_TILE;
+    da->tile_sum = (cbc_block_result *)ctx->arena[A_DTILE].p; da->tile_cnt = da->tile_sum + n_tiles;
+    uint64_t *toff = (uint64_t *)ctx->arena[A_DTOFF].p;
+    da->sum_off = toff; da->cnt_off = toff + n_tiles + 1;
+    da->cp_pos = (uint32_t *)ctx->arena[A_DCP].p; da->cp_dep = da->cp_pos + z.cp_cap; da->cp_cap = z.cp_cap;
+    da->ctr = (uint32_t *)ctx->arena[A_DCTR].p; da->name = (const uint8_t *)ctx->arena[A_SNAMES].p;
+    da->name_len = rg->names_bytes; da->exclude = rg->exclude; da->n_tiles = n_tiles; da->n_ttiles = z.n_ttiles;
+    HIPCHK(hipMemsetAsync(da->diff, 0, da->diff_words * 4, ks), "memset depth window");
+    HIPCHK(hipMemsetAsync(da->ctr, 0, 16, ks), "memset depth counters");
+    memset(ta, 0, sizeof *ta);
+    if (post_is_targets(rg->kind)) {
+        ta->D = *da; ta->iv = (const uint32_t *)ctx->arena[A_TIV].p; ta->iv_off = (const uint32_t *)ctx->arena[A_TOFF].p;
+        ta->block_iv = (const uint32_t *)ctx->arena[A_TBIV].p; ta->n_iv = rg->n_iv;
+        hipLaunchKernelGGL(cbc_targets_mark_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, *ta);
+    } else hipLaunchKernelGGL(cbc_depth_mark_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, *da);
+    HIPCHK(hipGetLastError(), "launch cbc_depth_mark_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+    hipLaunchKernelGGL(cbc_depth_tile_kernel, dim3(n_tiles), dim3(64), 0, ks, *da);
+    HIPCHK(hipGetLastError(), "launch cbc_depth_tile_kernel");
+    launch_scan_sizes(ks, da->tile_sum, toff, n_tiles);
+    launch_scan_sizes(ks, da->tile_cnt, toff + n_tiles + 1, n_tiles);
+    HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+    hipLaunchKernelGGL(cbc_depth_compact_kernel, dim3(n_tiles), dim3(64), 0, ks, *da);
+    HIPCHK(hipGetLastError(), "launch cbc_depth_compact_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
+/* depth text: lines per text tile, scan, write; the targets kernels name the runs by their interval */
+static int launch_depth_text(cbc_gpu_ctx *ctx, hipStream_t ks, bool tg, const post_sizes &z, const cbc_depth_args &da, const cbc_tdepth_args &ta)
+{
+    const uint32_t n_ttiles = z.n_ttiles;
+    if (tg) hipLaunchKernelGGL(cbc_targets_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, ta);
+    else hipLaunchKernelGGL(cbc_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
+    HIPCHK(hipGetLastError(), "launch cbc_depth_count_kernel");
+    launch_scan_sizes(ks, da.R.counts, (uint64_t *)ctx->arena[A_OFF].p, n_ttiles);
+    HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+    if (tg) hipLaunchKernelGGL(cbc_targets_depth_write_kernel, dim3(n_ttiles), dim3(64), 0, ks, ta);
+    else hipLaunchKernelGGL(cbc_depth_write_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
+    HIPCHK(hipGetLastError(), "launch cbc_depth_write_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[4], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
+/* coverage: weights, their scans, prefixes, lookup: no text */
+static int launch_coverage(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *cov, const post_sizes &z, const cbc_depth_args &da)
+{
+    const uint32_t n_ttiles = z.n_ttiles, cp_cap = z.cp_cap;
+    cbc_cov_args ca;
+    memset(&ca, 0, sizeof ca);
+    ca.cp_pos = da.cp_pos; ca.cp_dep = da.cp_dep; ca.cnt_off = da.cnt_off;
+    ca.tile_wlo = (cbc_block_result *)ctx->arena[A_CVTILE].p; ca.tile_whi = ca.tile_wlo + n_ttiles; ca.tile_cov = ca.tile_whi + n_ttiles;
+    uint64_t *woff = (uint64_t *)(ca.tile_cov + n_ttiles);
+    ca.wlo_off = woff; ca.whi_off = woff + (n_ttiles + 1); ca.cov_off = woff + 2 * ((uint64_t)n_ttiles + 1);
+    ca.pre_lo = (uint32_t *)ctx->arena[A_CVPRE].p; ca.pre_hi = ca.pre_lo + cp_cap; ca.pre_cov = ca.pre_hi + cp_cap;
+    ca.q = (const uint32_t *)ctx->arena[A_CVQ].p; ca.sum = (uint32_t *)ctx->arena[A_CVOUT].p; ca.covered = ca.sum + 2 * (uint64_t)cov->n_q;
+    ca.cp_cap = cp_cap; ca.n_tiles = z.n_tiles; ca.n_ttiles = n_ttiles; ca.n_q = cov->n_q; ca.min_depth = cov->min_depth;
+    ca.slots = (uint32_t)z.d_words;
+    hipLaunchKernelGGL(cbc_cov_weights_kernel, dim3(n_ttiles), dim3(64), 0, ks, ca);
+    HIPCHK(hipGetLastError(), "launch cbc_cov_weights_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_cov[0], ks), "hipEventRecord");
+    launch_scan_sizes(ks, ca.tile_wlo, woff, n_ttiles);
+    launch_scan_sizes(ks, ca.tile_whi, woff + (n_ttiles + 1), n_ttiles);
+    launch_scan_sizes(ks, ca.tile_cov, woff + 2 * ((uint64_t)n_ttiles + 1), n_ttiles);
+    HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_cov[1], ks), "hipEventRecord");
+    hipLaunchKernelGGL(cbc_cov_apply_kernel, dim3(n_ttiles), dim3(64), 0, ks, ca);
+    HIPCHK(hipGetLastError(), "launch cbc_cov_apply_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_cov[2], ks), "hipEventRecord");
+    hipLaunchKernelGGL(cbc_cov_lookup_kernel, dim3((cov->n_q + 63u) / 64u), dim3(64), 0, ks, ca);
+    HIPCHK(hipGetLastError(), "launch cbc_cov_lookup_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_cov[3], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
+/* histogram: zero, accumulate, count + scan + write of the bins: no text */
+static int launch_hist(cbc_gpu_ctx *ctx, hipStream_t ks, const hist_req *hist, const post_sizes &z, const cbc_depth_args &da)
+{
+    const uint32_t n_btiles = z.n_btiles;
+    cbc_hist_args ha;
+    memset(&ha, 0, sizeof ha);
+    ha.cp_pos = da.cp_pos; ha.cp_dep = da.cp_dep; ha.cnt_off = da.cnt_off;
+    ha.bins = (uint32_t *)ctx->arena[A_HBINS].p;
+    ha.tile_nz = (cbc_block_result *)ctx->arena[A_HTILE].p;
+    uint64_t *hoff = (uint64_t *)(ha.tile_nz + n_btiles);
+    ha.nz_off = hoff;
+    ha.out_depth = (uint32_t *)ctx->arena[A_HOUT].p; ha.out_bases = ha.out_depth + z.h_out_cap;
+    ha.cp_cap = z.cp_cap; ha.n_tiles = z.n_tiles; ha.n_ttiles = z.n_ttiles; ha.fold = hist->fold;
+    ha.n_bins = (uint32_t)z.h_bins; ha.n_btiles = n_btiles; ha.out_cap = z.h_out_cap;
+    ha.grid = z.n_ttiles < CBC_HIST_GRID ? z.n_ttiles : CBC_HIST_GRID;
+    HIPCHK(hipMemsetAsync(ha.bins, 0, (uint64_t)n_btiles * CBC_DEPTH_TILE * 4, ks), "memset histogram bins");
+    hipLaunchKernelGGL(cbc_hist_accum_kernel, dim3(ha.grid), dim3(64), 0, ks, ha);
+    HIPCHK(hipGetLastError(), "launch cbc_hist_accum_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_hist[0], ks), "hipEventRecord");
+    hipLaunchKernelGGL(cbc_hist_count_kernel, dim3(n_btiles), dim3(64), 0, ks, ha);
+    HIPCHK(hipGetLastError(), "launch cbc_hist_count_kernel");
+    launch_scan_sizes(ks, ha.tile_nz, hoff, n_btiles);
+    HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+    hipLaunchKernelGGL(cbc_hist_write_kernel, dim3(n_btiles), dim3(64), 0, ks, ha);
+    HIPCHK(hipGetLastError(), "launch cbc_hist_write_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_hist[1], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
+/* post stage, step 4: its results.  First the small ones, queued behind the block results and ahead of the call's one wait:
+ * the counters, the size of the text or of the histogram, the coverage numbers. */
+struct post_got { uint32_t dctr[4]; uint64_t total, h_count; cbc_block_result *cnt; /* region / SAM / reads: the filter's per-block counts */ };
+
+static int post_fetch_sizes(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z, uint32_t n_blocks, hipStream_t sc, post_got *g)
+{
+    if (post_is_depth(rg->kind)) {
+        HIPCHK(hipMemcpyAsync(g->dctr, ctx->arena[A_DCTR].p, 16, hipMemcpyDeviceToHost, sc), "D2H depth counters");
+        if (rg->kind == POST_HIST)
+            HIPCHK(hipMemcpyAsync(&g->h_count, (uint64_t *)((cbc_block_result *)ctx->arena[A_HTILE].p + z.n_btiles) + z.n_btiles, 8, hipMemcpyDeviceToHost, sc), "D2H histogram size");
+        else if (rg->kind != POST_COV)
+            HIPCHK(hipMemcpyAsync(&g->total, (uint64_t *)ctx->arena[A_OFF].p + z.n_ttiles, 8, hipMemcpyDeviceToHost, sc), "D2H text size");
+        else {                                                 /* the numbers, not the track: 12 bytes per query */
+            HIPCHK(hipMemcpyAsync(rg->cov.sum, ctx->arena[A_CVOUT].p, (uint64_t)rg->cov.n_q * 8, hipMemcpyDeviceToHost, sc), "D2H coverage sums");
+            HIPCHK(hipMemcpyAsync(rg->cov.covered, (uint64_t *)ctx->arena[A_CVOUT].p + rg->cov.n_q, (uint64_t)rg->cov.n_q * 4, hipMemcpyDeviceToHost, sc), "D2H coverage counts");
+        }
+        return CBC_OK;
+    }
+    g->cnt = (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
+    if (!g->cnt) return CBC_E_NOMEM;
+    HIPCHK(hipMemcpyAsync(g->cnt, ctx->arena[A_RCNT].p, (uint64_t)n_blocks * sizeof(cbc_block_result), hipMemcpyDeviceToHost, sc), "D2H region counts");
+    HIPCHK(hipMemcpyAsync(&g->total, (uint64_t *)ctx->arena[A_OFF].p + n_blocks, 8, hipMemcpyDeviceToHost, sc), "D2H text size");
+    return CBC_OK;
+}
+
+/* ... then, once those are on the host, the output itself in one copy of exactly its size: the text, or the histogram's
+ * pairs (none when a block failed).  A second wait only when there is something to fetch. */
+static int post_fetch_output(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z, uint32_t n_blocks, const cbc_block_result *res,
+                             hipStream_t sc, const post_got *g, uint64_t *d2h_bytes)
+{
+    const bool depth = post_is_depth(rg->kind);
+    uint64_t kept = 0;
+    if (depth) { kept = g->dctr[0]; *rg->n_runs = g->dctr[1]; }
+    else for (uint32_t b = 0; b < n_blocks; b++) kept += g->cnt[b].n_symbols;
+    *rg->text_bytes = g->total; *rg->n_selected = kept;
+    if (g->total > rg->text_cap)
+        return set_err(ctx, CBC_E_ARG, depth ? "text_cap too small for the depth text" : post_is_sam(rg->kind) ? "text_cap too small for the SAM text" : "text_cap too small for the region's text", hipSuccess);
+    if (g->total) {
+        HIPCHK(hipMemcpyAsync(rg->text, ctx->arena[A_TEXT].p, g->total, hipMemcpyDeviceToHost, sc), "D2H region text");
+        HIPCHK(hipStreamSynchronize(sc), "D2H region text");
+    }
+    *d2h_bytes = g->total;
+    if (rg->kind != POST_HIST) return CBC_OK;
+    for (uint32_t b = 0; b < n_blocks; b++) if (res[b].status != CBC_ST_OK) return CBC_OK;
+    const hist_req *hist = &rg->hist;
+    const uint64_t h_count = g->h_count;
+    *hist->n_bins = h_count > 0xffffffffull ? 0xffffffffu : (uint32_t)h_count;
+    if (h_count > z.h_out_cap || h_count > hist->bin_cap) return set_err(ctx, CBC_E_ARG, "bin_cap too small for the histogram's non-zero bins", hipSuccess);
+    if (h_count) {
+        HIPCHK(hipMemcpyAsync(hist->bin_depth, ctx->arena[A_HOUT].p, h_count * 4, hipMemcpyDeviceToHost, sc), "D2H histogram depths");
+        HIPCHK(hipMemcpyAsync(hist->bin_bases, (uint32_t *)ctx->arena[A_HOUT].p + z.h_out_cap, h_count * 4, hipMemcpyDeviceToHost, sc), "D2H histogram bases");
+        HIPCHK(hipStreamSynchronize(sc), "D2H histogram");
+    }
+    *d2h_bytes = h_count * 8;
+    return CBC_OK;
+}
 
 /* The host-buffer decode path as a pipeline, mirror of encode_blocks_impl: the payloads (2 bytes per read) go H2D at once;
  * the blocks are decoded in chunks (cbc_plan_chunks) on the kernel streams, and chunk c's records and bases (bytes, or 2-bit
  * rows packed by cbc_pack_2bit_kernel) come back on the copy stream while the later chunks are still being decoded.  Device
- * arrays are the context's arenas.  Region decode (nothing comes back before the text is built) and long reads (their
- * launches share the context's table scratch, A_LSCR; the long decoder takes no var scratch) are one chunk. */
+ * arrays are the context's arenas.  Long reads (their launches share the context's table scratch, A_LSCR; the long decoder
+ * takes no var scratch) are one chunk.  So is a call with a post-decode stage (rg->kind != POST_NONE): nothing comes back
+ * before its output is built, so its four steps above -- post_arenas, post_h2d, one launch_* sequence chosen by the kind,
+ * post_fetch_sizes / post_fetch_output -- hang off the one chunk, on its kernel stream, and take the place of the chunked D2H. */
 static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, cbc_dec_block_desc *blocks,
                               uint32_t n_blocks, const cbc_lds_caps *caps, cbc_read_rec *recs, uint64_t n_recs,
                               uint8_t *seq, uint64_t seq_bytes, uint32_t *codes_out, uint64_t *exc_idx, uint8_t *exc_val,
-                              uint64_t exc_cap, uint64_t *n_exc, cbc_block_result *results, const region_req *rg = NULL,
+                              uint64_t exc_cap, uint64_t *n_exc, cbc_block_result *results, const post_req *rg = NULL,
                               bool long_reads = false)
 {
     if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
@@ -1057,29 +1399,14 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     const double T0 = wall_now();
     cbc_e2e_times tm; memset(&tm, 0, sizeof tm);
-    const bool two_bit = codes_out != NULL, text = rg && rg->text_bytes, sam = text && rg->block_name;
-    const depth_req *depth = text ? rg->depth : NULL;
-    /* coverage: tiles of the difference array (W + 1 words), change points (two per read at most), text tiles of the runs */
-    const targets_req *tg = text ? rg->tg : NULL;
-    const cov_req *cov = depth && tg ? rg->cov : NULL;
-    const uint64_t d_words = !depth ? 0u : tg ? tg->iv_off[tg->n_iv] : rg->end - rg->beg + 2u;
-    const uint32_t n_tiles = (uint32_t)((d_words + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
-    const uint32_t cp_cap = depth ? (uint32_t)(2u * n_recs + (tg ? 2u * (uint64_t)tg->n_iv : 0u)) : 0u;   /* + two per interval edge */
-    const uint32_t n_ttiles = (cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
-    const uint32_t n_sized = depth ? n_ttiles : n_blocks;        /* entries the text's size scan runs over */
-    const hist_req *hist = depth && tg && !cov ? rg->hist : NULL;
-    /* histogram: min(fold, reads) + 1 bins in whole tiles; the non-zero ones are fewer than the bins and than the runs */
-    const uint64_t h_bins = hist ? (n_recs < hist->fold ? n_recs : hist->fold) + 1u : 0u;
-    const uint32_t n_btiles = (uint32_t)((h_bins + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
-    const uint32_t h_out_cap = hist ? (uint32_t)(h_bins - 1u < cp_cap ? h_bins - 1u : cp_cap) : 0u;
-    uint32_t dctr[4] = { 0, 0, 0, 0 };
+    const bool two_bit = codes_out != NULL, post = rg && rg->kind != POST_NONE;
+    const post_sizes z = post_sizes_of(rg, n_blocks, n_recs);
+    post_got pg; memset(&pg, 0, sizeof pg);
     const uint32_t stride = blocks[0].seq_stride;
     cbc_block_result *res = NULL;
     int rc = CBC_OK;
     const uint64_t n_words = two_bit ? n_recs * (stride >> 4) : 0;
     unsigned long long got = 0;
-    cbc_block_result *cnt = NULL;                             /* region decode: the filter's per-block counts */
-    uint64_t total = 0, kept = 0, h_count = 0;
     if (!long_reads) NEED(A_VS, (uint64_t)n_blocks * caps->cap_var * 4 + 16, "hipMalloc var scratch");
     NEED(A_IN, in_bytes + 16, "hipMalloc in");
     NEED(A_BLOCKS, (uint64_t)n_blocks * sizeof(cbc_dec_block_desc), "hipMalloc blocks");
@@ -1092,52 +1419,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         NEED(A_EXC_V, (exc_cap ? exc_cap : 1), "hipMalloc exceptions");
         NEED(A_CNT, 8, "hipMalloc counter");
     }
-    if (text) {
-        NEED(A_TEXT, rg->text_cap + 16, "hipMalloc region text");
-        NEED(A_RWS, (uint64_t)n_blocks * 8, "hipMalloc window starts");
-        NEED(A_RCNT, (uint64_t)n_sized * sizeof(cbc_block_result), "hipMalloc region counts");
-        NEED(A_OFF, ((uint64_t)n_sized + 1) * 8, "hipMalloc region offsets");
-    }
-    if (depth) {
-        if (arena_need(ctx, A_DDIFF, (uint64_t)n_tiles * CBC_DEPTH_TILE * 4, "hipMalloc depth window")) {
-            (void)hipGetLastError();
-            rc = set_err(ctx, CBC_E_NOMEM, "no device memory for the window's difference array (4 bytes per position)", hipSuccess);
-            goto done;
-        }
-        NEED(A_DTILE, (uint64_t)n_tiles * 2 * sizeof(cbc_block_result), "hipMalloc depth tiles");
-        NEED(A_DTOFF, ((uint64_t)n_tiles + 1) * 2 * 8, "hipMalloc depth tile offsets");
-        NEED(A_DCP, (uint64_t)cp_cap * 2 * 4 + 16, "hipMalloc depth change points");
-        NEED(A_DCTR, 16, "hipMalloc depth counters");
-        NEED(A_SNAMES, (uint64_t)rg->names_bytes + 16, "hipMalloc contig name");
-    }
-    if (sam) {
-        NEED(A_SNAMES, (uint64_t)rg->names_bytes + 16, "hipMalloc contig names");
-        NEED(A_SBN, (uint64_t)n_blocks * 8, "hipMalloc block names");
-    }
-    if (tg) {
-        NEED(A_TIV, (uint64_t)tg->n_iv * 8 + 16, "hipMalloc intervals");
-        NEED(A_TBIV, (uint64_t)n_blocks * 8, "hipMalloc block intervals");
-        if (depth) NEED(A_TOFF, ((uint64_t)tg->n_iv + 1) * 4, "hipMalloc interval slots");
-    }
-    if (cov) {
-        NEED(A_CVTILE, (uint64_t)n_ttiles * 3 * sizeof(cbc_block_result) + ((uint64_t)n_ttiles + 1) * 3 * 8, "hipMalloc coverage tiles");
-        if (arena_need(ctx, A_CVPRE, (uint64_t)cp_cap * 12 + 16, "hipMalloc coverage prefixes")) {
-            (void)hipGetLastError();
-            rc = set_err(ctx, CBC_E_NOMEM, "no device memory for the coverage prefixes (12 bytes per change point)", hipSuccess);
-            goto done;
-        }
-        NEED(A_CVQ, (uint64_t)cov->n_q * 8 + 16, "hipMalloc coverage queries");
-        NEED(A_CVOUT, (uint64_t)cov->n_q * 12 + 16, "hipMalloc coverage results");
-    }
-    if (hist) {
-        if (arena_need(ctx, A_HBINS, (uint64_t)n_btiles * CBC_DEPTH_TILE * 4, "hipMalloc histogram bins") ||
-            arena_need(ctx, A_HOUT, (uint64_t)h_out_cap * 8 + 16, "hipMalloc histogram pairs")) {
-            (void)hipGetLastError();
-            rc = set_err(ctx, CBC_E_NOMEM, "no device memory for the histogram's bins (4 bytes per bin, 8 per non-zero one)", hipSuccess);
-            goto done;
-        }
-        NEED(A_HTILE, (uint64_t)n_btiles * sizeof(cbc_block_result) + ((uint64_t)n_btiles + 1) * 8, "hipMalloc histogram tiles");
-    }
+    if (post && (rc = post_arenas(ctx, rg, z, n_blocks)) != CBC_OK) goto done;
     tm.alloc_s = wall_now() - T0;
     {
         uint8_t *d_in = (uint8_t *)ctx->arena[A_IN].p, *d_seq = (uint8_t *)ctx->arena[A_SEQ].p;
@@ -1150,22 +1432,11 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         GO(hipMemcpyAsync(d_blocks, blocks, (uint64_t)n_blocks * sizeof(cbc_dec_block_desc), hipMemcpyHostToDevice, sc), "H2D blocks");
         GO(hipMemsetAsync(d_res, 0xff, (uint64_t)n_blocks * sizeof(cbc_block_result), sc), "memset results");
         if (two_bit) GO(hipMemsetAsync(ctx->arena[A_CNT].p, 0, 8, sc), "memset counter");
-        if (text) GO(hipMemcpyAsync(ctx->arena[A_RWS].p, rg->window_start, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D window starts");
-        if (depth) GO(hipMemcpyAsync(ctx->arena[A_SNAMES].p, rg->names, rg->names_bytes, hipMemcpyHostToDevice, sc), "H2D contig name");
-        if (sam) {
-            GO(hipMemcpyAsync(ctx->arena[A_SNAMES].p, rg->names, rg->names_bytes, hipMemcpyHostToDevice, sc), "H2D contig names");
-            GO(hipMemcpyAsync(ctx->arena[A_SBN].p, rg->block_name, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D block names");
-        }
-        if (tg) {
-            GO(hipMemcpyAsync(ctx->arena[A_TIV].p, tg->iv, (uint64_t)tg->n_iv * 8, hipMemcpyHostToDevice, sc), "H2D intervals");
-            GO(hipMemcpyAsync(ctx->arena[A_TBIV].p, tg->block_iv, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D block intervals");
-            if (depth) GO(hipMemcpyAsync(ctx->arena[A_TOFF].p, tg->iv_off, ((uint64_t)tg->n_iv + 1) * 4, hipMemcpyHostToDevice, sc), "H2D interval slots");
-        }
-        if (cov) GO(hipMemcpyAsync(ctx->arena[A_CVQ].p, cov->q, (uint64_t)cov->n_q * 8, hipMemcpyHostToDevice, sc), "H2D coverage queries");
+        if (post && (rc = post_h2d(ctx, rg, n_blocks, sc)) != CBC_OK) goto done;
         GO(hipEventRecord(ctx->ev_done[0], sc), "hipEventRecord");       /* inputs are on the device */
         tm.h2d_bytes = in_bytes + (uint64_t)n_blocks * sizeof(cbc_dec_block_desc);
         cbc_chunk_plan P;
-        cbc_plan_chunks(blocks, n_blocks, n_recs, seq_bytes, 0, n_recs * 16 + (two_bit ? n_words * 4 : seq_bytes), !long_reads && !text, &P);
+        cbc_plan_chunks(blocks, n_blocks, n_recs, seq_bytes, 0, n_recs * 16 + (two_bit ? n_words * 4 : seq_bytes), !long_reads && !post, &P);
         tm.n_chunks = P.n_chunks;
         for (uint32_t c = 0; c < P.n_chunks; c++) {
             const cbc_chunk &k = P.c[c];
@@ -1177,7 +1448,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
             db.d_in = d_in; db.in_bytes = in_bytes + 16; db.d_blocks = d_blocks + k.b0; db.n_blocks = k.b1 - k.b0;
             db.d_ref = ctx->d_ref; db.ref_bytes = ctx->ref_bytes; db.d_recs = d_recs; db.n_recs = n_recs;
             db.d_seq = d_seq; db.d_results = d_res + k.b0; db.caps = *caps;
-            if (text) GO(hipEventRecord(ctx->ev_rg[0], ks), "hipEventRecord");
+            if (post) GO(hipEventRecord(ctx->ev_rg[0], ks), "hipEventRecord");
             if (long_reads) {
                 db.seq_bytes = seq_bytes + 16;
                 rc = cbc_gpu_long_decode_blocks_device(ctx, &db, ks);
@@ -1188,152 +1459,32 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 rc = decode_blocks_launch(ctx, &db, ks, rg ? rg->smax : 0u);
             }
             if (rc) goto done;
-            if (text) {                                        /* one chunk: filter, scan, text on the decode's stream */
-                GO(hipEventRecord(ctx->ev_rg[1], ks), "hipEventRecord");
-                ctx->have_hist_timing = 0;
+            if (post) {                                        /* one chunk: the stage's launches on the decode's stream */
                 cbc_region_args ra;
-                memset(&ra, 0, sizeof ra);
-                ra.recs = d_recs; ra.seq = d_seq; ra.blocks = d_blocks; ra.window_start = (const uint64_t *)ctx->arena[A_RWS].p;
-                ra.dec_results = d_res; ra.counts = (cbc_block_result *)ctx->arena[A_RCNT].p; ra.offsets = (const uint64_t *)ctx->arena[A_OFF].p;
-                ra.text = (uint8_t *)ctx->arena[A_TEXT].p; ra.text_cap = rg->text_cap; ra.n_recs = n_recs; ra.seq_bytes = seq_bytes + 32;
-                ra.beg = rg->beg; ra.end = rg->end; ra.n_blocks = n_blocks;
-                if (depth) {                                   /* mark, tile sums + scans + change points, lines */
-                    cbc_depth_args da;
-                    memset(&da, 0, sizeof da);
-                    da.R = ra;
-                    da.diff = (uint32_t *)ctx->arena[A_DDIFF].p; da.diff_words = (uint64_t)n_tiles * CBC_DEPTH_TILE;
-                    da.tile_sum = (cbc_block_result *)ctx->arena[A_DTILE].p; da.tile_cnt = da.tile_sum + n_tiles;
-                    uint64_t *toff = (uint64_t *)ctx->arena[A_DTOFF].p;
-                    da.sum_off = toff; da.cnt_off = toff + n_tiles + 1;
-                    da.cp_pos = (uint32_t *)ctx->arena[A_DCP].p; da.cp_dep = da.cp_pos + cp_cap; da.cp_cap = cp_cap;
-                    da.ctr = (uint32_t *)ctx->arena[A_DCTR].p; da.name = (const uint8_t *)ctx->arena[A_SNAMES].p;
-                    da.name_len = rg->names_bytes; da.exclude = depth->exclude; da.n_tiles = n_tiles; da.n_ttiles = n_ttiles;
-                    GO(hipMemsetAsync(da.diff, 0, da.diff_words * 4, ks), "memset depth window");
-                    GO(hipMemsetAsync(da.ctr, 0, 16, ks), "memset depth counters");
-                    cbc_tdepth_args ta;
-                    memset(&ta, 0, sizeof ta);
-                    if (tg) {
-                        ta.D = da; ta.iv = (const uint32_t *)ctx->arena[A_TIV].p; ta.iv_off = (const uint32_t *)ctx->arena[A_TOFF].p;
-                        ta.block_iv = (const uint32_t *)ctx->arena[A_TBIV].p; ta.n_iv = tg->n_iv;
-                        hipLaunchKernelGGL(cbc_targets_mark_kernel, dim3(n_blocks), dim3(64), 0, ks, ta);
-                    } else
-                    hipLaunchKernelGGL(cbc_depth_mark_kernel, dim3(n_blocks), dim3(64), 0, ks, da);
-                    GO(hipGetLastError(), "launch cbc_depth_mark_kernel");
-                    GO(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
-                    hipLaunchKernelGGL(cbc_depth_tile_kernel, dim3(n_tiles), dim3(64), 0, ks, da);
-                    GO(hipGetLastError(), "launch cbc_depth_tile_kernel");
-                    hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)da.tile_sum, toff, n_tiles);
-                    hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)da.tile_cnt, toff + n_tiles + 1, n_tiles);
-                    GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
-                    hipLaunchKernelGGL(cbc_depth_compact_kernel, dim3(n_tiles), dim3(64), 0, ks, da);
-                    GO(hipGetLastError(), "launch cbc_depth_compact_kernel");
-                    GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                    if (cov) {                                 /* weights, their scans, prefixes, lookup: no text */
-                        cbc_cov_args ca;
-                        memset(&ca, 0, sizeof ca);
-                        ca.cp_pos = da.cp_pos; ca.cp_dep = da.cp_dep; ca.cnt_off = da.cnt_off;
-                        ca.tile_wlo = (cbc_block_result *)ctx->arena[A_CVTILE].p; ca.tile_whi = ca.tile_wlo + n_ttiles; ca.tile_cov = ca.tile_whi + n_ttiles;
-                        uint64_t *woff = (uint64_t *)(ca.tile_cov + n_ttiles);
-                        ca.wlo_off = woff; ca.whi_off = woff + (n_ttiles + 1); ca.cov_off = woff + 2 * ((uint64_t)n_ttiles + 1);
-                        ca.pre_lo = (uint32_t *)ctx->arena[A_CVPRE].p; ca.pre_hi = ca.pre_lo + cp_cap; ca.pre_cov = ca.pre_hi + cp_cap;
-                        ca.q = (const uint32_t *)ctx->arena[A_CVQ].p; ca.sum = (uint32_t *)ctx->arena[A_CVOUT].p; ca.covered = ca.sum + 2 * (uint64_t)cov->n_q;
-                        ca.cp_cap = cp_cap; ca.n_tiles = n_tiles; ca.n_ttiles = n_ttiles; ca.n_q = cov->n_q; ca.min_depth = cov->min_depth;
-                        ca.slots = (uint32_t)d_words;
-                        hipLaunchKernelGGL(cbc_cov_weights_kernel, dim3(n_ttiles), dim3(64), 0, ks, ca);
-                        GO(hipGetLastError(), "launch cbc_cov_weights_kernel");
-                        GO(hipEventRecord(ctx->ev_cov[0], ks), "hipEventRecord");
-                        hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ca.tile_wlo, woff, n_ttiles);
-                        hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ca.tile_whi, woff + (n_ttiles + 1), n_ttiles);
-                        hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ca.tile_cov, woff + 2 * ((uint64_t)n_ttiles + 1), n_ttiles);
-                        GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
-                        GO(hipEventRecord(ctx->ev_cov[1], ks), "hipEventRecord");
-                        hipLaunchKernelGGL(cbc_cov_apply_kernel, dim3(n_ttiles), dim3(64), 0, ks, ca);
-                        GO(hipGetLastError(), "launch cbc_cov_apply_kernel");
-                        GO(hipEventRecord(ctx->ev_cov[2], ks), "hipEventRecord");
-                        hipLaunchKernelGGL(cbc_cov_lookup_kernel, dim3((cov->n_q + 63u) / 64u), dim3(64), 0, ks, ca);
-                        GO(hipGetLastError(), "launch cbc_cov_lookup_kernel");
-                        GO(hipEventRecord(ctx->ev_cov[3], ks), "hipEventRecord");
-                        ctx->have_cov_timing = 1; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0; ctx->have_sam_timing = 0; ctx->have_region_timing = 0;
-                    } else if (hist) {                         /* zero, accumulate, count + scan + write of the bins: no text */
-                        cbc_hist_args ha;
-                        memset(&ha, 0, sizeof ha);
-                        ha.cp_pos = da.cp_pos; ha.cp_dep = da.cp_dep; ha.cnt_off = da.cnt_off;
-                        ha.bins = (uint32_t *)ctx->arena[A_HBINS].p;
-                        ha.tile_nz = (cbc_block_result *)ctx->arena[A_HTILE].p;
-                        uint64_t *hoff = (uint64_t *)(ha.tile_nz + n_btiles);
-                        ha.nz_off = hoff;
-                        ha.out_depth = (uint32_t *)ctx->arena[A_HOUT].p; ha.out_bases = ha.out_depth + h_out_cap;
-                        ha.cp_cap = cp_cap; ha.n_tiles = n_tiles; ha.n_ttiles = n_ttiles; ha.fold = hist->fold;
-                        ha.n_bins = (uint32_t)h_bins; ha.n_btiles = n_btiles; ha.out_cap = h_out_cap;
-                        ha.grid = n_ttiles < CBC_HIST_GRID ? n_ttiles : CBC_HIST_GRID;
-                        GO(hipMemsetAsync(ha.bins, 0, (uint64_t)n_btiles * CBC_DEPTH_TILE * 4, ks), "memset histogram bins");
-                        hipLaunchKernelGGL(cbc_hist_accum_kernel, dim3(ha.grid), dim3(64), 0, ks, ha);
-                        GO(hipGetLastError(), "launch cbc_hist_accum_kernel");
-                        GO(hipEventRecord(ctx->ev_hist[0], ks), "hipEventRecord");
-                        hipLaunchKernelGGL(cbc_hist_count_kernel, dim3(n_btiles), dim3(64), 0, ks, ha);
-                        GO(hipGetLastError(), "launch cbc_hist_count_kernel");
-                        hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ha.tile_nz, hoff, n_btiles);
-                        GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
-                        hipLaunchKernelGGL(cbc_hist_write_kernel, dim3(n_btiles), dim3(64), 0, ks, ha);
-                        GO(hipGetLastError(), "launch cbc_hist_write_kernel");
-                        GO(hipEventRecord(ctx->ev_hist[1], ks), "hipEventRecord");
-                        ctx->have_hist_timing = 1; ctx->have_cov_timing = 0; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0; ctx->have_sam_timing = 0; ctx->have_region_timing = 0;
-                    } else {
-                    if (tg) hipLaunchKernelGGL(cbc_targets_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, ta);
-                    else hipLaunchKernelGGL(cbc_depth_count_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
-                    GO(hipGetLastError(), "launch cbc_depth_count_kernel");
-                    hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_ttiles);
-                    GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
-                    if (tg) hipLaunchKernelGGL(cbc_targets_depth_write_kernel, dim3(n_ttiles), dim3(64), 0, ks, ta);
-                    else hipLaunchKernelGGL(cbc_depth_write_kernel, dim3(n_ttiles), dim3(64), 0, ks, da);
-                    GO(hipGetLastError(), "launch cbc_depth_write_kernel");
-                    GO(hipEventRecord(ctx->ev_rg[4], ks), "hipEventRecord");
-                    ctx->have_depth_timing = tg ? 0 : 1; ctx->have_targets_timing = tg ? 2 : 0; ctx->have_sam_timing = 0; ctx->have_region_timing = 0;
-                    ctx->have_cov_timing = 0;
-                    }
-                } else if (tg) {                               /* a set of regions: reads or SAM, the same three steps */
-                    cbc_targets_args ta;
-                    memset(&ta, 0, sizeof ta);
-                    ta.S.R = ra; ta.iv = (const uint32_t *)ctx->arena[A_TIV].p; ta.block_iv = (const uint32_t *)ctx->arena[A_TBIV].p; ta.n_iv = tg->n_iv;
-                    if (sam) {
-                        ta.S.block_name = (const uint32_t *)ctx->arena[A_SBN].p; ta.S.names = (const uint8_t *)ctx->arena[A_SNAMES].p;
-                        ta.S.names_bytes = rg->names_bytes;
-                        hipLaunchKernelGGL(cbc_targets_sam_count_kernel, dim3(n_blocks), dim3(64), 0, ks, ta);
-                    } else hipLaunchKernelGGL(cbc_targets_count_kernel, dim3(n_blocks), dim3(64), 0, ks, ta);
-                    GO(hipGetLastError(), "launch cbc_targets_count_kernel");
-                    hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_blocks);
-                    GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
-                    GO(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
-                    if (sam) hipLaunchKernelGGL(cbc_targets_sam_write_kernel, dim3(n_blocks), dim3(64 * CBC_SAM_WAVES), 0, ks, ta);
-                    else hipLaunchKernelGGL(cbc_targets_write_kernel, dim3(n_blocks), dim3(64 * CBC_REGION_WAVES), 0, ks, ta);
-                    GO(hipGetLastError(), "launch cbc_targets_write_kernel");
-                    GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                    ctx->have_targets_timing = 1; ctx->have_sam_timing = 0; ctx->have_region_timing = 0; ctx->have_depth_timing = 0; ctx->have_cov_timing = 0;
-                } else if (sam) {                              /* the same three steps with the SAM bodies */
-                    cbc_sam_args sa;
-                    memset(&sa, 0, sizeof sa);
-                    sa.R = ra; sa.block_name = (const uint32_t *)ctx->arena[A_SBN].p; sa.names = (const uint8_t *)ctx->arena[A_SNAMES].p;
-                    sa.names_bytes = rg->names_bytes; sa.region = rg->region ? 1u : 0u;
-                    hipLaunchKernelGGL(cbc_sam_count_kernel, dim3(n_blocks), dim3(64), 0, ks, sa);
-                    GO(hipGetLastError(), "launch cbc_sam_count_kernel");
-                    hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_blocks);
-                    GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
-                    GO(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
-                    hipLaunchKernelGGL(cbc_sam_write_kernel, dim3(n_blocks), dim3(64 * CBC_SAM_WAVES), 0, ks, sa);
-                    GO(hipGetLastError(), "launch cbc_sam_write_kernel");
-                    GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                    ctx->have_sam_timing = 1; ctx->have_region_timing = 0; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0; ctx->have_cov_timing = 0;
-                } else {
-                hipLaunchKernelGGL(cbc_region_count_kernel, dim3(n_blocks), dim3(64), 0, ks, ra);
-                GO(hipGetLastError(), "launch cbc_region_count_kernel");
-                hipLaunchKernelGGL(cbc_scan_sizes_kernel, dim3(1), dim3(1024), 0, ks, (const cbc_block_result *)ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_blocks);
-                GO(hipGetLastError(), "launch cbc_scan_sizes_kernel");
-                GO(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
-                hipLaunchKernelGGL(cbc_region_write_kernel, dim3(n_blocks), dim3(64 * CBC_REGION_WAVES), 0, ks, ra);
-                GO(hipGetLastError(), "launch cbc_region_write_kernel");
-                GO(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-                ctx->have_region_timing = 1; ctx->have_sam_timing = 0; ctx->have_depth_timing = 0; ctx->have_targets_timing = 0; ctx->have_cov_timing = 0;
+                cbc_depth_args da;
+                cbc_tdepth_args ta;
+                GO(hipEventRecord(ctx->ev_rg[1], ks), "hipEventRecord");
+                post_region_args(ctx, rg, n_blocks, n_recs, seq_bytes, &ra);
+                switch (rg->kind) {
+                case POST_NONE: break;
+                case POST_REGION: rc = launch_region_text(ctx, ks, ra); break;
+                case POST_SAM: rc = launch_sam_text(ctx, ks, rg, ra); break;
+                case POST_TG_READS: case POST_TG_SAM: rc = launch_targets_text(ctx, ks, rg, ra); break;
+                case POST_DEPTH: case POST_TG_DEPTH:
+                    rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
+                    if (!rc) rc = launch_depth_text(ctx, ks, rg->kind == POST_TG_DEPTH, z, da, ta);
+                    break;
+                case POST_COV:
+                    rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
+                    if (!rc) rc = launch_coverage(ctx, ks, &rg->cov, z, da);
+                    break;
+                case POST_HIST:
+                    rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
+                    if (!rc) rc = launch_hist(ctx, ks, &rg->hist, z, da);
+                    break;
                 }
+                if (rc) goto done;
+                ctx->last_post = rg->kind;                     /* the events now hold this call's times */
             }
             if (two_bit && k.r1 > k.r0) {
                 const uint64_t w0 = k.r0 * (stride >> 4), w1 = k.r1 * (stride >> 4);
@@ -1345,7 +1496,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
             GO(hipEventRecord(ctx->ev_chunk[c], ks), "hipEventRecord");
         }
         tm.issue_s = wall_now() - T0;
-        for (uint32_t c = 0; c < P.n_chunks && !text; c++) {         /* the chunks come back in order while later ones are being decoded */
+        for (uint32_t c = 0; c < P.n_chunks && !post; c++) {         /* the chunks come back in order while later ones are being decoded */
             const cbc_chunk &k = P.c[c];
             GO(hipStreamWaitEvent(sc, ctx->ev_chunk[c], 0), "hipStreamWaitEvent");
             if (k.r1 > k.r0) GO(hipMemcpyAsync(recs + k.r0, d_recs + k.r0, (k.r1 - k.r0) * sizeof(cbc_read_rec), hipMemcpyDeviceToHost, sc), "D2H recs");
@@ -1361,50 +1512,13 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         }
         res = results ? results : (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
         if (!res) { rc = CBC_E_NOMEM; goto done; }
-        if (text) GO(hipStreamWaitEvent(sc, ctx->ev_chunk[0], 0), "hipStreamWaitEvent");
+        if (post) GO(hipStreamWaitEvent(sc, ctx->ev_chunk[0], 0), "hipStreamWaitEvent");
         GO(hipMemcpyAsync(res, d_res, (uint64_t)n_blocks * sizeof(cbc_block_result), hipMemcpyDeviceToHost, sc), "D2H results");
         if (two_bit) GO(hipMemcpyAsync(&got, ctx->arena[A_CNT].p, 8, hipMemcpyDeviceToHost, sc), "D2H counter");
-        if (depth) {
-            GO(hipMemcpyAsync(dctr, ctx->arena[A_DCTR].p, 16, hipMemcpyDeviceToHost, sc), "D2H depth counters");
-            if (hist) GO(hipMemcpyAsync(&h_count, (uint64_t *)((cbc_block_result *)ctx->arena[A_HTILE].p + n_btiles) + n_btiles, 8, hipMemcpyDeviceToHost, sc), "D2H histogram size");
-            else if (!cov) GO(hipMemcpyAsync(&total, (uint64_t *)ctx->arena[A_OFF].p + n_ttiles, 8, hipMemcpyDeviceToHost, sc), "D2H text size");
-            else {                                             /* the numbers, not the track: 12 bytes per query */
-                GO(hipMemcpyAsync(cov->sum, ctx->arena[A_CVOUT].p, (uint64_t)cov->n_q * 8, hipMemcpyDeviceToHost, sc), "D2H coverage sums");
-                GO(hipMemcpyAsync(cov->covered, (uint64_t *)ctx->arena[A_CVOUT].p + cov->n_q, (uint64_t)cov->n_q * 4, hipMemcpyDeviceToHost, sc), "D2H coverage counts");
-            }
-        } else if (text) {
-            cnt = (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
-            if (!cnt) { rc = CBC_E_NOMEM; goto done; }
-            GO(hipMemcpyAsync(cnt, ctx->arena[A_RCNT].p, (uint64_t)n_blocks * sizeof(cbc_block_result), hipMemcpyDeviceToHost, sc), "D2H region counts");
-            GO(hipMemcpyAsync(&total, (uint64_t *)ctx->arena[A_OFF].p + n_blocks, 8, hipMemcpyDeviceToHost, sc), "D2H text size");
-        }
+        if (post && (rc = post_fetch_sizes(ctx, rg, z, n_blocks, sc, &pg)) != CBC_OK) goto done;
         GO(hipStreamSynchronize(sc), "decode kernel");
         tm.kernels_done_s = wall_now() - T0;
-        if (text) {
-            if (depth) { kept = dctr[0]; *depth->n_runs = dctr[1]; }
-            else for (uint32_t b = 0; b < n_blocks; b++) kept += cnt[b].n_symbols;
-            *rg->text_bytes = total; *rg->n_selected = kept;
-            if (total > rg->text_cap) { rc = set_err(ctx, CBC_E_ARG, depth ? "text_cap too small for the depth text" : sam ? "text_cap too small for the SAM text" : "text_cap too small for the region's text", hipSuccess); goto done; }
-            if (total) {                                       /* the one copy of the output: exactly its size */
-                GO(hipMemcpyAsync(rg->text, ctx->arena[A_TEXT].p, total, hipMemcpyDeviceToHost, sc), "D2H region text");
-                GO(hipStreamSynchronize(sc), "D2H region text");
-            }
-            tm.d2h_bytes = total;
-        }
-        if (hist) {                                            /* the pairs: exactly as many as there are; none when a block failed */
-            bool failed = false;
-            for (uint32_t b = 0; b < n_blocks && !failed; b++) failed = res[b].status != CBC_ST_OK;
-            if (!failed) {
-                *hist->n_bins = h_count > 0xffffffffull ? 0xffffffffu : (uint32_t)h_count;
-                if (h_count > h_out_cap || h_count > hist->bin_cap) { rc = set_err(ctx, CBC_E_ARG, "bin_cap too small for the histogram's non-zero bins", hipSuccess); goto done; }
-                if (h_count) {
-                    GO(hipMemcpyAsync(hist->bin_depth, ctx->arena[A_HOUT].p, h_count * 4, hipMemcpyDeviceToHost, sc), "D2H histogram depths");
-                    GO(hipMemcpyAsync(hist->bin_bases, (uint32_t *)ctx->arena[A_HOUT].p + h_out_cap, h_count * 4, hipMemcpyDeviceToHost, sc), "D2H histogram bases");
-                    GO(hipStreamSynchronize(sc), "D2H histogram");
-                }
-                tm.d2h_bytes = h_count * 8;
-            }
-        }
+        if (post && (rc = post_fetch_output(ctx, rg, z, n_blocks, res, sc, &pg, &tm.d2h_bytes)) != CBC_OK) goto done;
         if (two_bit) {
             *n_exc = got;
             if (got > exc_cap) { rc = set_err(ctx, CBC_E_ARG, "more non-ACGT bases than exc_cap", hipSuccess); goto done; }
@@ -1420,7 +1534,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
 done:
     if (rc && rc != CBC_E_BLOCK) (void)hipDeviceSynchronize();
     if (res && res != results) free(res);
-    free(cnt);
+    free(pg.cnt);
     tm.total_s = wall_now() - T0;
     ctx->last_e2e = tm;
     return rc;
@@ -1434,8 +1548,92 @@ API int cbc_gpu_decode_blocks(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     return decode_blocks_impl(ctx, in, in_bytes, blocks, n_blocks, caps, recs, n_recs, seq, seq_bytes, NULL, NULL, NULL, 0, NULL, results);
 }
 
-/* region decode: the selected blocks are laid out afresh (payload range, records and rows from 0), decoded with the spans
- * reported, filtered and assembled into text on the device (cbc_region_body.h) */
+/* The blocks a region / SAM / depth / targets call selected, laid out afresh: payloads from in0, records and rows from 0.
+ * With the contig-name tables (SAM, targets) also bn, per block the (offset, length) of its contig's name, and name_sum,
+ * the bytes all the reads' contig names take. */
+struct name_tables { const uint64_t *window_start; const uint32_t *block_contig; const char *names; uint32_t names_bytes;
+                     const uint32_t *contig_name_off; uint32_t n_contigs; };
+struct block_layout { cbc_dec_block_desc *bl; uint32_t *bn; uint64_t in0, in1, nrec, name_sum; };
+
+static void layout_free(block_layout *L) { free(L->bl); free(L->bn); L->bl = NULL; L->bn = NULL; }
+
+static int layout_err(cbc_gpu_ctx *ctx, const char *who, const char *what)
+{
+    char msg[192];
+    snprintf(msg, sizeof msg, "%s%s", who, what);
+    return set_err(ctx, CBC_E_ARG, msg, hipSuccess);
+}
+
+/* `who` opens the messages ("region decode", "SAM decode", "depth", "targets decode").  Per block: its range in `in`, then
+ * (nt != NULL) its contig, the name and the window start.  On an error nothing stays allocated; after CBC_OK the caller
+ * ends with layout_free. */
+static int relayout_blocks(cbc_gpu_ctx *ctx, const char *who, uint64_t in_bytes, const cbc_dec_block_desc *blocks, uint32_t n_blocks,
+                           const name_tables *nt, block_layout *L)
+{
+    memset(L, 0, sizeof *L);
+    L->in0 = UINT64_MAX;
+    const uint32_t stride = blocks[0].seq_stride;
+    if (stride < 4 || stride > 256 || (stride & 3u)) return layout_err(ctx, who, " wants seq_stride in 4..256, a multiple of 4");
+    L->bl = (cbc_dec_block_desc *)malloc((size_t)n_blocks * sizeof(cbc_dec_block_desc));
+    if (nt) L->bn = (uint32_t *)malloc((size_t)n_blocks * 8);
+    if (!L->bl || (nt && !L->bn)) { layout_free(L); return CBC_E_NOMEM; }
+    const char *bad = NULL;
+    for (uint32_t b = 0; b < n_blocks; b++) {                  /* no sums of caller values that could wrap */
+        const cbc_dec_block_desc *d = &blocks[b];
+        size_t nl = 0;
+        if (d->seq_stride != stride || d->in_off > in_bytes || d->in_bytes > in_bytes - d->in_off || d->n_reads > CBC_MAX_BLOCK_READS) {
+            bad = ": block out of range of `in`, or strides differ"; break; }
+        if (nt) {
+            if (nt->block_contig[b] >= nt->n_contigs || nt->contig_name_off[nt->block_contig[b]] >= nt->names_bytes) {
+                bad = ": a block's contig or its name lies outside the tables"; break; }
+            const uint32_t off = nt->contig_name_off[nt->block_contig[b]];
+            const char *name = nt->names + off;
+            nl = strnlen(name, nt->names_bytes - off);
+            if (nl == nt->names_bytes - off || nl < 1 || nl > CBC_SAM_MAX_NAME || memchr(name, '\t', nl) || memchr(name, '\n', nl)) {
+                bad = ": a contig name is empty, unterminated, longer than 255 bytes or holds a tab or a newline"; break; }
+            if (nt->window_start[b] > CBC_SAM_MAX_POS) { bad = ": a block starts past POS 2^31 - 1"; break; }
+            L->bn[2 * b] = off; L->bn[2 * b + 1] = (uint32_t)nl;
+        }
+        if (d->in_off < L->in0) L->in0 = d->in_off;
+        if (d->in_off + d->in_bytes > L->in1) L->in1 = d->in_off + d->in_bytes;
+        L->bl[b] = *d;
+        L->bl[b].rec_base = L->nrec; L->bl[b].seq_base = L->nrec * stride;
+        L->nrec += d->n_reads;
+        L->name_sum += (uint64_t)d->n_reads * nl;
+    }
+    if (bad) { layout_free(L); return layout_err(ctx, who, bad); }
+    for (uint32_t b = 0; b < n_blocks; b++) L->bl[b].in_off -= L->in0;
+    return CBC_OK;
+}
+
+/* the request every laid-out call starts from, and the call itself: records and rows stay on the device */
+static void post_req_init(post_req *rg, post_kind kind, uint32_t smax, const uint64_t *window_start, uint8_t *text, uint64_t text_cap,
+                          uint64_t need, uint64_t *text_bytes, uint64_t *n_selected)
+{
+    memset(rg, 0, sizeof *rg);
+    rg->kind = kind; rg->smax = smax; rg->window_start = window_start; rg->region = 1;
+    rg->text = text; rg->text_cap = text_cap < need ? text_cap : need; rg->text_bytes = text_bytes; rg->n_selected = n_selected;
+}
+
+static int decode_laid_out(cbc_gpu_ctx *ctx, const uint8_t *in, const block_layout *L, uint32_t n_blocks, const cbc_lds_caps *caps,
+                           cbc_block_result *results, const post_req *rg)
+{
+    return decode_blocks_impl(ctx, in + L->in0, L->in1 - L->in0, L->bl, n_blocks, caps, (cbc_read_rec *)NULL, L->nrec, (uint8_t *)NULL,
+                              L->nrec * L->bl[0].seq_stride + 8, NULL, NULL, NULL, 0, NULL, results, rg);
+}
+
+/* Kernel times of the most recent call with a post-decode stage: out[i] = the time from ev[i] to ev[i + 1], for the n
+ * stretches between n + 1 consecutive events of that call. */
+static int last_ms(cbc_gpu_ctx *ctx, const hipEvent_t *ev, float *const *out, int n)
+{
+    for (int i = 0; i < n; i++) if (!out[i]) return CBC_E_ARG;
+    HIPCHK(hipEventSynchronize(ev[n]), "hipEventSynchronize");
+    for (int i = 0; i < n; i++) HIPCHK(hipEventElapsedTime(out[i], ev[i], ev[i + 1]), "hipEventElapsedTime");
+    return CBC_OK;
+}
+
+/* region decode: the selected blocks are laid out afresh, decoded with the spans reported, filtered and assembled into text
+ * on the device (cbc_region_body.h) */
 API int cbc_gpu_decode_region(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                               uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
                               uint64_t beg, uint64_t end, uint32_t smax, uint8_t *text, uint64_t text_cap,
@@ -1447,28 +1645,14 @@ API int cbc_gpu_decode_region(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     if (n_blocks == 0) return CBC_OK;
     if (!in) return CBC_E_ARG;
     if (smax == 0 || beg < 1 || beg > end) return set_err(ctx, CBC_E_ARG, "region decode wants 1 <= beg <= end and smax > 0", hipSuccess);
-    const uint32_t stride = blocks[0].seq_stride;
-    if (stride < 4 || stride > 256 || (stride & 3u)) return set_err(ctx, CBC_E_ARG, "region decode wants seq_stride in 4..256, a multiple of 4", hipSuccess);
-    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)n_blocks * sizeof(cbc_dec_block_desc));
-    if (!bl) return CBC_E_NOMEM;
-    uint64_t in0 = UINT64_MAX, in1 = 0, nrec = 0;
-    for (uint32_t b = 0; b < n_blocks; b++) {                  /* no sums of caller values that could wrap */
-        const cbc_dec_block_desc *d = &blocks[b];
-        if (d->seq_stride != stride || d->in_off > in_bytes || d->in_bytes > in_bytes - d->in_off || d->n_reads > CBC_MAX_BLOCK_READS) {
-            free(bl); return set_err(ctx, CBC_E_ARG, "region decode: block out of range of `in`, or strides differ", hipSuccess); }
-        if (d->in_off < in0) in0 = d->in_off;
-        if (d->in_off + d->in_bytes > in1) in1 = d->in_off + d->in_bytes;
-    }
-    for (uint32_t b = 0; b < n_blocks; b++) {
-        bl[b] = blocks[b];
-        bl[b].in_off -= in0; bl[b].rec_base = nrec; bl[b].seq_base = nrec * stride;
-        nrec += bl[b].n_reads;
-    }
-    const uint64_t need = nrec * (stride + 1ull);               /* every read kept: rl + 1 <= stride + 1 bytes each */
-    region_req rg = { window_start, beg, end, smax, text, text_cap < need ? text_cap : need, text_bytes, n_selected, NULL, NULL, 0, 0, NULL };
-    int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
-                                nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
-    free(bl);
+    block_layout L;
+    int rc = relayout_blocks(ctx, "region decode", in_bytes, blocks, n_blocks, NULL, &L);
+    if (rc) return rc;
+    post_req rg;                                               /* every read kept: rl + 1 <= stride + 1 bytes each */
+    post_req_init(&rg, POST_REGION, smax, window_start, text, text_cap, L.nrec * (blocks[0].seq_stride + 1ull), text_bytes, n_selected);
+    rg.beg = beg; rg.end = end;
+    rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
+    layout_free(&L);
     return rc;
 }
 
@@ -1477,9 +1661,9 @@ API int cbc_gpu_decode_blocks_span(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t
                                    uint8_t *seq, uint64_t seq_bytes, cbc_block_result *results)
 {
     if (!ctx || !in || !blocks || !caps || !recs || !seq || smax == 0) return CBC_E_ARG;
-    region_req rg;
+    post_req rg;
     memset(&rg, 0, sizeof rg);
-    rg.smax = smax;
+    rg.kind = POST_NONE; rg.smax = smax;
     return decode_blocks_impl(ctx, in, in_bytes, blocks, n_blocks, caps, recs, n_recs, seq, seq_bytes, NULL, NULL, NULL, 0, NULL, results, &rg);
 }
 
@@ -1499,49 +1683,25 @@ API int cbc_gpu_decode_sam(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_byte
     if (!in) return CBC_E_ARG;
     if (region && (region->smax == 0 || region->beg < 1 || region->beg > region->end))
         return set_err(ctx, CBC_E_ARG, "SAM region decode wants 1 <= beg <= end and smax > 0", hipSuccess);
-    const uint32_t stride = blocks[0].seq_stride;
-    if (stride < 4 || stride > 256 || (stride & 3u)) return set_err(ctx, CBC_E_ARG, "SAM decode wants seq_stride in 4..256, a multiple of 4", hipSuccess);
-    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)n_blocks * sizeof(cbc_dec_block_desc));
-    uint32_t *bn = (uint32_t *)malloc((size_t)n_blocks * 8);
-    if (!bl || !bn) { free(bl); free(bn); return CBC_E_NOMEM; }
-    uint64_t in0 = UINT64_MAX, in1 = 0, nrec = 0, need = 0;
-    const char *bad = NULL;
-    for (uint32_t b = 0; b < n_blocks && !bad; b++) {          /* no sums of caller values that could wrap */
-        const cbc_dec_block_desc *d = &blocks[b];
-        if (d->seq_stride != stride || d->in_off > in_bytes || d->in_bytes > in_bytes - d->in_off || d->n_reads > CBC_MAX_BLOCK_READS) {
-            bad = "SAM decode: block out of range of `in`, or strides differ"; break; }
-        if (block_contig[b] >= n_contigs || contig_name_off[block_contig[b]] >= names_bytes) { bad = "SAM decode: a block's contig or its name lies outside the tables"; break; }
-        const uint32_t off = contig_name_off[block_contig[b]];
-        const size_t nl = strnlen(names + off, names_bytes - off);
-        if (nl == names_bytes - off || nl < 1 || nl > CBC_SAM_MAX_NAME || memchr(names + off, '\t', nl) || memchr(names + off, '\n', nl)) {
-            bad = "SAM decode: a contig name is empty, unterminated, longer than 255 bytes or holds a tab or a newline"; break; }
-        if (window_start[b] > CBC_SAM_MAX_POS) { bad = "SAM decode: a block starts past POS 2^31 - 1"; break; }
-        bn[2 * b] = off; bn[2 * b + 1] = (uint32_t)nl;
-        if (d->in_off < in0) in0 = d->in_off;
-        if (d->in_off + d->in_bytes > in1) in1 = d->in_off + d->in_bytes;
-        bl[b] = *d;
-        bl[b].rec_base = nrec; bl[b].seq_base = nrec * stride;
-        nrec += d->n_reads;
-        need += (uint64_t)d->n_reads * (35ull + nl + stride);   /* every read kept, every field at its longest */
-    }
-    if (bad) { free(bl); free(bn); return set_err(ctx, CBC_E_ARG, bad, hipSuccess); }
-    for (uint32_t b = 0; b < n_blocks; b++) bl[b].in_off -= in0;
-    region_req rg = { window_start, region ? region->beg : 1u, region ? region->end : UINT64_MAX, region ? region->smax : 0u, text,
-                      text_cap < need ? text_cap : need, text_bytes, n_reads, bn, (const uint8_t *)names, names_bytes, region != NULL, NULL };
-    int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
-                                nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
-    free(bl); free(bn);
+    const name_tables nt = { window_start, block_contig, names, names_bytes, contig_name_off, n_contigs };
+    block_layout L;
+    int rc = relayout_blocks(ctx, "SAM decode", in_bytes, blocks, n_blocks, &nt, &L);
+    if (rc) return rc;
+    post_req rg;                                               /* every read kept, every field at its longest */
+    post_req_init(&rg, POST_SAM, region ? region->smax : 0u, window_start, text, text_cap,
+                  L.nrec * (35ull + blocks[0].seq_stride) + L.name_sum, text_bytes, n_reads);
+    rg.beg = region ? region->beg : 1u; rg.end = region ? region->end : UINT64_MAX; rg.region = region != NULL;
+    rg.names = (const uint8_t *)names; rg.names_bytes = names_bytes; rg.block_name = L.bn;
+    rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
+    layout_free(&L);
     return rc;
 }
 
 API int cbc_gpu_last_sam_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *count_ms, float *text_ms)
 {
-    if (!ctx || !decode_ms || !count_ms || !text_ms || !ctx->have_sam_timing) return CBC_E_ARG;
-    HIPCHK(hipEventSynchronize(ctx->ev_rg[3]), "hipEventSynchronize");
-    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(count_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(text_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
-    return CBC_OK;
+    if (!ctx || ctx->last_post != POST_SAM) return CBC_E_ARG;
+    float *const out[] = { decode_ms, count_ms, text_ms };
+    return last_ms(ctx, ctx->ev_rg, out, 3);
 }
 
 /* coverage: the window's blocks laid out afresh as for a region decode, then span decode + mark + scan + text on the device
@@ -1561,49 +1721,33 @@ API int cbc_gpu_decode_depth(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_by
         return set_err(ctx, CBC_E_ARG, "depth wants 1 <= beg <= end <= 2^31 - 1 and smax > 0", hipSuccess);
     if (name_bytes < 1 || name_bytes > CBC_SAM_MAX_NAME || memchr(name, '\t', name_bytes) || memchr(name, '\n', name_bytes) || memchr(name, 0, name_bytes))
         return set_err(ctx, CBC_E_ARG, "depth: the contig name is empty, longer than 255 bytes or holds a tab, a newline or a NUL", hipSuccess);
-    const uint32_t stride = blocks[0].seq_stride;
-    if (stride < 4 || stride > 256 || (stride & 3u)) return set_err(ctx, CBC_E_ARG, "depth wants seq_stride in 4..256, a multiple of 4", hipSuccess);
-    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)n_blocks * sizeof(cbc_dec_block_desc));
-    if (!bl) return CBC_E_NOMEM;
-    uint64_t in0 = UINT64_MAX, in1 = 0, nrec = 0;
-    for (uint32_t b = 0; b < n_blocks; b++) {                  /* no sums of caller values that could wrap */
-        const cbc_dec_block_desc *d = &blocks[b];
-        if (d->seq_stride != stride || d->in_off > in_bytes || d->in_bytes > in_bytes - d->in_off || d->n_reads > CBC_MAX_BLOCK_READS) {
-            free(bl); return set_err(ctx, CBC_E_ARG, "depth: block out of range of `in`, or strides differ", hipSuccess); }
-        if (d->in_off < in0) in0 = d->in_off;
-        if (d->in_off + d->in_bytes > in1) in1 = d->in_off + d->in_bytes;
-        bl[b] = *d;
-        bl[b].rec_base = nrec; bl[b].seq_base = nrec * stride;
-        nrec += d->n_reads;
+    block_layout L;
+    int rc = relayout_blocks(ctx, "depth", in_bytes, blocks, n_blocks, NULL, &L);
+    if (rc) return rc;
+    if (L.nrec > 0x3fffffffull) rc = set_err(ctx, CBC_E_ARG, "depth: more than 2^30 - 1 reads in one call", hipSuccess);
+    else if (L.nrec) {                                         /* blocks without reads: no line */
+        post_req rg;                                           /* K reads: at most 2K - 1 runs */
+        post_req_init(&rg, POST_DEPTH, smax, window_start, text, text_cap, (2u * L.nrec - 1u) * (name_bytes + 34ull), text_bytes, n_reads_kept);
+        rg.beg = beg; rg.end = end;
+        rg.names = (const uint8_t *)name; rg.names_bytes = name_bytes; rg.exclude = exclude_flags; rg.n_runs = n_runs;
+        rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
     }
-    if (nrec > 0x3fffffffull) { free(bl); return set_err(ctx, CBC_E_ARG, "depth: more than 2^30 - 1 reads in one call", hipSuccess); }
-    if (nrec == 0) { free(bl); return CBC_OK; }                 /* blocks without reads: no line */
-    for (uint32_t b = 0; b < n_blocks; b++) bl[b].in_off -= in0;
-    const uint64_t need = nrec ? (2u * nrec - 1u) * (name_bytes + 34ull) : 0u;   /* K reads: at most 2K - 1 runs */
-    depth_req dq = { exclude_flags, n_runs };
-    region_req rg = { window_start, beg, end, smax, text, text_cap < need ? text_cap : need, text_bytes, n_reads_kept, NULL,
-                      (const uint8_t *)name, name_bytes, 1, &dq };
-    int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
-                                nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
-    free(bl);
+    layout_free(&L);
     return rc;
 }
 
 API int cbc_gpu_last_depth_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *text_ms)
 {
-    if (!ctx || !decode_ms || !mark_ms || !scan_ms || !text_ms || !ctx->have_depth_timing) return CBC_E_ARG;
-    HIPCHK(hipEventSynchronize(ctx->ev_rg[4]), "hipEventSynchronize");
-    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(mark_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(scan_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(text_ms, ctx->ev_rg[3], ctx->ev_rg[4]), "hipEventElapsedTime");
-    return CBC_OK;
+    if (!ctx || ctx->last_post != POST_DEPTH) return CBC_E_ARG;
+    float *const out[] = { decode_ms, mark_ms, scan_ms, text_ms };
+    return last_ms(ctx, ctx->ev_rg, out, 4);
 }
 
 /* a set of regions: the selected blocks laid out afresh as for a region decode, the tables checked
  * on the host, then span decode + keep by the interval table + scan + text on the device (cbc_targets_body.h) */
-/* cov != NULL (cbc_gpu_decode_coverage): a depth call whose compressed coordinate is laid over the intervals
- * [iv_first, iv_first + iv_count) -- the contig's, whether a block reaches them or not -- and that ends in the query passes */
+/* cov != NULL (cbc_gpu_decode_coverage) or hist != NULL (cbc_gpu_decode_depth_hist): a depth call whose compressed
+ * coordinate is laid over the intervals [iv_first, iv_first + iv_count) -- the contig's, whether a block reaches them or
+ * not -- and that ends in the query passes or in the bins */
 static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                                uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
                                const uint32_t *block_contig, const char *names, uint32_t names_bytes,
@@ -1622,79 +1766,67 @@ static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
     if (t->smax == 0 || t->n_iv == 0 || t->n_iv > (1u << 24))
         return set_err(ctx, CBC_E_ARG, "targets decode wants smax > 0 and 1 .. 2^24 intervals", hipSuccess);
     const bool depth = output == CBC_TARGETS_DEPTH, sam = output == CBC_TARGETS_SAM;
-    const uint32_t stride = blocks[0].seq_stride;
-    if (stride < 4 || stride > 256 || (stride & 3u)) return set_err(ctx, CBC_E_ARG, "targets decode wants seq_stride in 4..256, a multiple of 4", hipSuccess);
     for (uint32_t i = 0; i < t->n_iv; i++)
         if (t->iv[2 * i] < 1 || t->iv[2 * i] > t->iv[2 * i + 1] || t->iv[2 * i + 1] > CBC_SAM_MAX_POS)
             return set_err(ctx, CBC_E_ARG, "targets decode: an interval is not 1 <= beg <= end <= 2^31 - 1", hipSuccess);
-    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)n_blocks * sizeof(cbc_dec_block_desc));
-    uint32_t *bn = (uint32_t *)malloc((size_t)n_blocks * 8), *biv = (uint32_t *)malloc((size_t)n_blocks * 8), *ioff = NULL;
-    if (!bl || !bn || !biv) { free(bl); free(bn); free(biv); return CBC_E_NOMEM; }
-    uint64_t in0 = UINT64_MAX, in1 = 0, nrec = 0, need = 0;
-    uint32_t lo = UINT32_MAX, hi = 0, nl0 = 0;                  /* depth: the intervals the call's blocks reach */
-    const char *bad = NULL;
-    for (uint32_t b = 0; b < n_blocks && !bad; b++) {          /* no sums of caller values that could wrap */
-        const cbc_dec_block_desc *d = &blocks[b];
-        if (d->seq_stride != stride || d->in_off > in_bytes || d->in_bytes > in_bytes - d->in_off || d->n_reads > CBC_MAX_BLOCK_READS) {
-            bad = "targets decode: block out of range of `in`, or strides differ"; break; }
-        if (block_contig[b] >= n_contigs || contig_name_off[block_contig[b]] >= names_bytes) { bad = "targets decode: a block's contig or its name lies outside the tables"; break; }
-        const uint32_t off = contig_name_off[block_contig[b]];
-        const size_t nl = strnlen(names + off, names_bytes - off);
-        if (nl == names_bytes - off || nl < 1 || nl > CBC_SAM_MAX_NAME || memchr(names + off, '\t', nl) || memchr(names + off, '\n', nl)) {
-            bad = "targets decode: a contig name is empty, unterminated, longer than 255 bytes or holds a tab or a newline"; break; }
-        if (window_start[b] > CBC_SAM_MAX_POS) { bad = "targets decode: a block starts past POS 2^31 - 1"; break; }
+    const name_tables nt = { window_start, block_contig, names, names_bytes, contig_name_off, n_contigs };
+    block_layout L;
+    int rc = relayout_blocks(ctx, "targets decode", in_bytes, blocks, n_blocks, &nt, &L);
+    if (rc) return rc;
+    uint32_t *biv = NULL, *ioff = NULL;
+    uint32_t lo = UINT32_MAX, hi = 0;                           /* depth: the intervals the call's blocks reach */
+    const uint32_t stride = blocks[0].seq_stride;
+    const char *bad = NULL;                                     /* a defect found below: its message, then out */
+    post_req rg;
+    for (uint32_t b = 0; b < n_blocks; b++) {
         const uint32_t f = t->block_iv[2 * b], c = t->block_iv[2 * b + 1];
-        if (f > t->n_iv || c > t->n_iv - f) { bad = "targets decode: a block's interval range lies outside the table"; break; }
-        if (depth && block_contig[b] != block_contig[0]) { bad = "targets decode: a depth call takes the blocks of one contig"; break; }
+        if (f > t->n_iv || c > t->n_iv - f) { bad = "targets decode: a block's interval range lies outside the table"; goto out; }
+        if (depth && block_contig[b] != block_contig[0]) { bad = "targets decode: a depth call takes the blocks of one contig"; goto out; }
         if (whole && c && (f < iv_first || f - iv_first > iv_count || c > iv_count - (f - iv_first))) {
-            bad = "coverage: a block's interval range lies outside the contig's intervals"; break; }
+            bad = "coverage: a block's interval range lies outside the contig's intervals"; goto out; }
         if (c) { if (f < lo) lo = f; if (f + c > hi) hi = f + c; }
-        bn[2 * b] = off; bn[2 * b + 1] = (uint32_t)nl;
-        if (b == 0) nl0 = (uint32_t)nl;
-        if (d->in_off < in0) in0 = d->in_off;
-        if (d->in_off + d->in_bytes > in1) in1 = d->in_off + d->in_bytes;
-        bl[b] = *d;
-        bl[b].rec_base = nrec; bl[b].seq_base = nrec * stride;
-        nrec += d->n_reads;
-        need += (uint64_t)d->n_reads * (sam ? 35ull + nl + stride : stride + 1ull);
     }
-    if (!bad && depth && nrec > 0x3fffffffull) bad = "targets decode: more than 2^30 - 1 reads in one depth call";
-    if (bad) { free(bl); free(bn); free(biv); return set_err(ctx, CBC_E_ARG, bad, hipSuccess); }
-    if (nrec == 0 || (depth && lo >= hi)) { free(bl); free(bn); free(biv); return CBC_OK; }   /* no read, or none that reaches an interval */
-    if (whole) { lo = iv_first; hi = iv_first + iv_count; }      /* the slots of the queries count from the contig's first interval */
-    for (uint32_t b = 0; b < n_blocks; b++) bl[b].in_off -= in0;
-    targets_req tq = { t->iv, t->n_iv, t->block_iv, NULL };
-    depth_req dq = { exclude_flags, n_runs };
+    if (depth && L.nrec > 0x3fffffffull) { bad = "targets decode: more than 2^30 - 1 reads in one depth call"; goto out; }
+    if (!L.nrec || (depth && lo >= hi)) goto out;               /* no read, or none that reaches an interval: CBC_OK */
+    post_req_init(&rg, cov ? POST_COV : hist ? POST_HIST : depth ? POST_TG_DEPTH : sam ? POST_TG_SAM : POST_TG_READS, t->smax,
+                  window_start, text, text_cap, sam ? L.nrec * (35ull + stride) + L.name_sum : L.nrec * (stride + 1ull), text_bytes, n_reads);
+    rg.beg = 1u; rg.end = UINT64_MAX;
+    rg.names = (const uint8_t *)names; rg.names_bytes = names_bytes; rg.block_name = sam ? L.bn : NULL;
+    rg.iv = t->iv; rg.n_iv = t->n_iv; rg.block_iv = t->block_iv;
     if (depth) {
         /* the contig's intervals [lo, hi): disjoint, ascending and not touching (they are merged); block ranges relative to
          * lo; the slots of the compressed coordinate, one spare behind each interval */
-        const uint32_t n = hi - lo;
+        if (whole) { lo = iv_first; hi = iv_first + iv_count; }          /* the slots of the queries count from the contig's first interval */
+        const uint32_t n = hi - lo, nl0 = L.bn[1];
+        biv = (uint32_t *)malloc((size_t)n_blocks * 8);
         ioff = (uint32_t *)malloc(((size_t)n + 1) * 4);
-        if (!ioff) { free(bl); free(bn); free(biv); return CBC_E_NOMEM; }
+        if (!biv || !ioff) { rc = CBC_E_NOMEM; goto out; }
         uint64_t run = 0;
-        for (uint32_t i = 0; i < n && !bad; i++) {
+        for (uint32_t i = 0; i < n; i++) {
             const uint32_t *p = t->iv + 2 * (size_t)(lo + i);
-            if (i && p[0] <= p[-1] + 1u) bad = "targets decode: the intervals of a depth call are not ascending and apart";
+            if (i && p[0] <= p[-1] + 1u) { bad = "targets decode: the intervals of a depth call are not ascending and apart"; goto out; }
             ioff[i] = (uint32_t)run;
             run += (uint64_t)(p[1] - p[0]) + 2u;
         }
         ioff[n] = (uint32_t)run;                                /* <= 2^31 + 2^24 */
-        for (uint32_t i = 0; cov && i < cov->n_q && !bad; i++)   /* no query reaches past the slots */
-            if (cov->q[2 * i] > ioff[n] || cov->q[2 * i + 1] > ioff[n] - cov->q[2 * i]) bad = "coverage: a query lies outside the compressed coordinate";
-        if (bad) { free(bl); free(bn); free(biv); free(ioff); return set_err(ctx, CBC_E_ARG, bad, hipSuccess); }
+        for (uint32_t i = 0; cov && i < cov->n_q; i++)          /* no query reaches past the slots */
+            if (cov->q[2 * i] > ioff[n] || cov->q[2 * i + 1] > ioff[n] - cov->q[2 * i]) {
+                bad = "coverage: a query lies outside the compressed coordinate"; goto out; }
         for (uint32_t b = 0; b < n_blocks; b++) {
             const uint32_t c = t->block_iv[2 * b + 1];
             biv[2 * b] = c ? t->block_iv[2 * b] - lo : 0u; biv[2 * b + 1] = c;
         }
-        tq.iv = t->iv + 2 * (size_t)lo; tq.n_iv = n; tq.block_iv = biv; tq.iv_off = ioff;
-        need = (2u * nrec + 2ull * n - 1u) * (nl0 + 34ull);     /* K reads, n intervals: at most 2K + 2n - 1 runs */
+        rg.iv = t->iv + 2 * (size_t)lo; rg.n_iv = n; rg.block_iv = biv; rg.iv_off = ioff;
+        rg.names = (const uint8_t *)names + L.bn[0]; rg.names_bytes = nl0; rg.exclude = exclude_flags; rg.n_runs = n_runs;
+        if (cov) rg.cov = *cov;
+        if (hist) rg.hist = *hist;
+        const uint64_t need = (2u * L.nrec + 2ull * n - 1u) * (nl0 + 34ull);   /* K reads, n intervals: at most 2K + 2n - 1 runs */
+        rg.text_cap = text_cap < need ? text_cap : need;
     }
-    region_req rg = { window_start, 1u, UINT64_MAX, t->smax, text, text_cap < need ? text_cap : need, text_bytes, n_reads,
-                      sam ? bn : NULL, depth ? (const uint8_t *)names + bn[0] : (const uint8_t *)names, depth ? nl0 : names_bytes, 1,
-                      depth ? &dq : NULL, &tq, cov, hist };
-    int rc = decode_blocks_impl(ctx, in + in0, in1 - in0, bl, n_blocks, caps, (cbc_read_rec *)NULL, nrec, (uint8_t *)NULL,
-                                nrec * stride + 8, NULL, NULL, NULL, 0, NULL, results, &rg);
-    free(bl); free(bn); free(biv); free(ioff);
+    rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
+out:
+    if (bad) rc = set_err(ctx, CBC_E_ARG, bad, hipSuccess);
+    layout_free(&L); free(biv); free(ioff);
     return rc;
 }
 
@@ -1756,53 +1888,38 @@ API int cbc_gpu_decode_depth_hist(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t 
 /* kernel times of the most recent cbc_gpu_decode_depth_hist */
 API int cbc_gpu_last_hist_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *accum_ms, float *compact_ms)
 {
-    if (!ctx || !decode_ms || !mark_ms || !scan_ms || !accum_ms || !compact_ms || !ctx->have_hist_timing) return CBC_E_ARG;
-    HIPCHK(hipEventSynchronize(ctx->ev_hist[1]), "hipEventSynchronize");
-    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(mark_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(scan_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(accum_ms, ctx->ev_rg[3], ctx->ev_hist[0]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(compact_ms, ctx->ev_hist[0], ctx->ev_hist[1]), "hipEventElapsedTime");
-    return CBC_OK;
+    if (!ctx || ctx->last_post != POST_HIST) return CBC_E_ARG;
+    const hipEvent_t ev[] = { ctx->ev_rg[0], ctx->ev_rg[1], ctx->ev_rg[2], ctx->ev_rg[3], ctx->ev_hist[0], ctx->ev_hist[1] };
+    float *const out[] = { decode_ms, mark_ms, scan_ms, accum_ms, compact_ms };
+    return last_ms(ctx, ev, out, 5);
 }
 
 /* kernel times of the most recent cbc_gpu_decode_coverage */
 API int cbc_gpu_last_coverage_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *weights_ms,
                                  float *wscan_ms, float *apply_ms, float *lookup_ms)
 {
-    if (!ctx || !decode_ms || !mark_ms || !scan_ms || !weights_ms || !wscan_ms || !apply_ms || !lookup_ms || !ctx->have_cov_timing) return CBC_E_ARG;
-    HIPCHK(hipEventSynchronize(ctx->ev_cov[3]), "hipEventSynchronize");
-    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(mark_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(scan_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(weights_ms, ctx->ev_rg[3], ctx->ev_cov[0]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(wscan_ms, ctx->ev_cov[0], ctx->ev_cov[1]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(apply_ms, ctx->ev_cov[1], ctx->ev_cov[2]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(lookup_ms, ctx->ev_cov[2], ctx->ev_cov[3]), "hipEventElapsedTime");
-    return CBC_OK;
+    if (!ctx || ctx->last_post != POST_COV) return CBC_E_ARG;
+    const hipEvent_t ev[] = { ctx->ev_rg[0], ctx->ev_rg[1], ctx->ev_rg[2], ctx->ev_rg[3], ctx->ev_cov[0], ctx->ev_cov[1], ctx->ev_cov[2], ctx->ev_cov[3] };
+    float *const out[] = { decode_ms, mark_ms, scan_ms, weights_ms, wscan_ms, apply_ms, lookup_ms };
+    return last_ms(ctx, ev, out, 7);
 }
 
+/* a reads / SAM call has no scan stretch of its own: scan_ms = 0 */
 API int cbc_gpu_last_targets_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *scan_ms, float *text_ms)
 {
-    if (!ctx || !decode_ms || !filter_ms || !scan_ms || !text_ms || !ctx->have_targets_timing) return CBC_E_ARG;
-    const int d = ctx->have_targets_timing == 2;
-    HIPCHK(hipEventSynchronize(ctx->ev_rg[d ? 4 : 3]), "hipEventSynchronize");
-    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(filter_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
+    if (!ctx || !decode_ms || !filter_ms || !scan_ms || !text_ms) return CBC_E_ARG;
+    float *const out4[] = { decode_ms, filter_ms, scan_ms, text_ms }, *const out3[] = { decode_ms, filter_ms, text_ms };
+    if (ctx->last_post == POST_TG_DEPTH) return last_ms(ctx, ctx->ev_rg, out4, 4);
+    if (ctx->last_post != POST_TG_READS && ctx->last_post != POST_TG_SAM) return CBC_E_ARG;
     *scan_ms = 0.0f;
-    if (d) HIPCHK(hipEventElapsedTime(scan_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(text_ms, ctx->ev_rg[d ? 3 : 2], ctx->ev_rg[d ? 4 : 3]), "hipEventElapsedTime");
-    return CBC_OK;
+    return last_ms(ctx, ctx->ev_rg, out3, 3);
 }
 
 API int cbc_gpu_last_region_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *text_ms)
 {
-    if (!ctx || !decode_ms || !filter_ms || !text_ms || !ctx->have_region_timing) return CBC_E_ARG;
-    HIPCHK(hipEventSynchronize(ctx->ev_rg[3]), "hipEventSynchronize");
-    HIPCHK(hipEventElapsedTime(decode_ms, ctx->ev_rg[0], ctx->ev_rg[1]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(filter_ms, ctx->ev_rg[1], ctx->ev_rg[2]), "hipEventElapsedTime");
-    HIPCHK(hipEventElapsedTime(text_ms, ctx->ev_rg[2], ctx->ev_rg[3]), "hipEventElapsedTime");
-    return CBC_OK;
+    if (!ctx || ctx->last_post != POST_REGION) return CBC_E_ARG;
+    float *const out[] = { decode_ms, filter_ms, text_ms };
+    return last_ms(ctx, ctx->ev_rg, out, 3);
 }
 
 /* ------------------------------------------------------------------------------------------------
