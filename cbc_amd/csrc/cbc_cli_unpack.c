@@ -475,10 +475,15 @@ int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref,
  * --region, per BED line (unmerged, in input order), per contig when neither is given, or per window of those -- with the sum
  * of the depth, the positions with depth >= D and the mean.  The numbers come from one
  * cbc_gpu_decode_coverage per contig that has intervals and blocks; the text is formatted here, so that it comes out in input
- * order across contigs.  12 bytes per query cross PCIe. */
-int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
-                              const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose)
+ * order across contigs.  12 bytes per query cross PCIe.
+ * `--thresholds T1,..` / `--count-reads`: n_thr more columns, the positions with depth >= Ti, and one
+ * last column, the kept reads with a base in the query, from cbc_gpu_decode_coverage_ext; with neither, the call, the kernels,
+ * the bytes and the messages are those of the plain summary. */
+static int bedcov_run(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                      const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose,
+                      const uint32_t *thr, uint32_t n_thr, int count_reads)
 {
+    const int ext = n_thr || count_reads;
     const double t0 = now2();
     size_t blob_len = 0, fa_len = 0, bed_len = 0;
     char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
@@ -507,7 +512,10 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
     uint32_t *cov = (uint32_t *)calloc((size_t)(nq ? nq : 1), 4), *ccov = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 4);
     uint32_t *qq = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 8), *qi = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 4);
     uint64_t *cfirst = (uint64_t *)calloc((size_t)nc + 2, 8);
-    if (!bl || !ws || !bc || !sum || !csum || !cov || !ccov || !qq || !qi || !cfirst) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    /* the extra columns, gathered and scattered per contig like sum and covered */
+    uint32_t *xthr = (uint32_t *)calloc((size_t)(nq ? nq : 1) * (n_thr ? n_thr : 1), 4), *cthr = (uint32_t *)malloc((size_t)(nq ? nq : 1) * (n_thr ? n_thr : 1) * 4);
+    uint32_t *xrd = (uint32_t *)calloc((size_t)(nq ? nq : 1), 4), *crd = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 4);
+    if (!bl || !ws || !bc || !sum || !csum || !cov || !ccov || !qq || !qi || !cfirst || !xthr || !cthr || !xrd || !crd) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
     for (uint32_t k = 0; k < nb; k++) { const uint32_t b = T->blocks[k]; bl[k] = u->blocks[b]; ws[k] = u->window_start[b]; bc[k] = u->block_contig[b]; }
     /* the queries that hold a position, grouped per contig (a counting sort: the order inside a contig stays the input's) */
     for (uint64_t i = 0; i < nq; i++) if (Q->q[i].contig != CBC_QUERY_UNKNOWN && Q->q[i].end0 > Q->q[i].start0) cfirst[Q->q[i].contig + 2]++;
@@ -523,7 +531,7 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
     cbc_gpu_ctx *ctx = NULL;
     uint64_t reads = 0;
     uint32_t blocks_used = 0;
-    float ms[7] = { 0, 0, 0, 0, 0, 0, 0 };
+    float ms[7] = { 0, 0, 0, 0, 0, 0, 0 }, xms[5] = { 0, 0, 0, 0, 0 };
     const cbc_gpu_targets gt = { (const uint32_t *)T->iv, NULL, T->n_iv, T->smax };
     for (uint32_t c = 0; c < nc && nb; c++) {
         const uint32_t k0 = T->contig_blk_first[c], kn = T->contig_blk_count[c];
@@ -540,16 +548,29 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
         cbc_gpu_targets g = gt;
         g.block_iv = T->block_iv + 2 * (size_t)k0;
         uint64_t nr = 0;
-        rc = cbc_gpu_decode_coverage(ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
-                                     u->contig_name_off, u->n_contigs, &g, T->contig_first[c], T->contig_count[c], qq + 2 * q0,
-                                     (uint32_t)qn, exclude, min_depth, csum + q0, ccov + q0, &nr, NULL);
+        if (ext)
+            rc = cbc_gpu_decode_coverage_ext(ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
+                                             u->contig_name_off, u->n_contigs, &g, T->contig_first[c], T->contig_count[c], qq + 2 * q0,
+                                             (uint32_t)qn, exclude, min_depth, csum + q0, ccov + q0, &nr, NULL, thr, n_thr,
+                                             cthr + q0 * n_thr, count_reads ? crd + q0 : NULL);
+        else
+            rc = cbc_gpu_decode_coverage(ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
+                                         u->contig_name_off, u->n_contigs, &g, T->contig_first[c], T->contig_count[c], qq + 2 * q0,
+                                         (uint32_t)qn, exclude, min_depth, csum + q0, ccov + q0, &nr, NULL);
         if (rc) { fprintf(stderr, "cbc: coverage failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
         t_dev += now2() - b;
-        if (verbose) {
+        if (verbose && ext) {
+            float m7[7], m5[5];
+            if (cbc_gpu_last_coverage_ext_ms(ctx, m7, m5) == 0) { for (int i = 0; i < 7; i++) ms[i] += m7[i]; for (int i = 0; i < 5; i++) xms[i] += m5[i]; }
+        } else if (verbose) {
             float m7[7];
             if (cbc_gpu_last_coverage_ms(ctx, &m7[0], &m7[1], &m7[2], &m7[3], &m7[4], &m7[5], &m7[6]) == 0) for (int i = 0; i < 7; i++) ms[i] += m7[i];
         }
         for (uint64_t k = q0; k < q0 + qn; k++) { sum[qi[k]] = csum[k]; cov[qi[k]] = ccov[k]; }
+        for (uint64_t k = q0; ext && k < q0 + qn; k++) {
+            for (uint32_t t = 0; t < n_thr; t++) xthr[(size_t)qi[k] * n_thr + t] = cthr[k * n_thr + t];
+            if (count_reads) xrd[qi[k]] = crd[k];
+        }
         reads += nr; blocks_used += kn;
     }
     if (ctx) cbc_gpu_shutdown(ctx);
@@ -562,8 +583,11 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
         (void)cbc_coverage_mean(sum[i], x->end0 - x->start0, mean);
         const char *nm = x->contig == CBC_QUERY_UNKNOWN ? bed + x->name_off : u->names + u->contig_name_off[x->contig];
         const int nl = x->contig == CBC_QUERY_UNKNOWN ? (int)x->name_len : (int)strlen(nm);
-        if (fprintf(fo, "%.*s\t%llu\t%llu\t%llu\t%u\t%s\n", nl, nm, (unsigned long long)x->start0, (unsigned long long)x->end0,
-                    (unsigned long long)sum[i], cov[i], mean) < 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+        int bad = fprintf(fo, "%.*s\t%llu\t%llu\t%llu\t%u\t%s", nl, nm, (unsigned long long)x->start0, (unsigned long long)x->end0,
+                          (unsigned long long)sum[i], cov[i], mean) < 0;
+        for (uint32_t t = 0; t < n_thr && !bad; t++) bad = fprintf(fo, "\t%u", xthr[(size_t)i * n_thr + t]) < 0;
+        if (count_reads && !bad) bad = fprintf(fo, "\t%u", xrd[i]) < 0;
+        if (bad || fputc('\n', fo) == EOF) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
     }
     if (fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
     printf("coverage of %llu queries from %llu reads in %u of %u blocks\n", (unsigned long long)nq, (unsigned long long)reads, blocks_used, u->n_blocks);
@@ -574,11 +598,27 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
                t1 - t0, t_init, t_dev, now2() - t2);
         if (ctx) printf("kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, weights %.3f ms, weight scans %.3f ms, prefixes %.3f ms, lookup %.3f ms\n",
                         ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6]);
+        if (ctx && ext) printf("kernels: start points %.3f ms, threshold weights %.3f ms, their scans %.3f ms, their prefixes %.3f ms, threshold + read lookup %.3f ms\n",
+                               xms[0], xms[1], xms[2], xms[3], xms[4]);
     }
+    free(xthr); free(cthr); free(xrd); free(crd);
     free(bl); free(ws); free(bc); free(sum); free(csum); free(cov); free(ccov); free(qq); free(qi); free(cfirst); free(bed); free(blob);
     cbc_queries_free(Q);
     cbc_unpack_plan_free(u);
     return 0;
+}
+
+int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                              const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose)
+{
+    return bedcov_run(in, out, ref, device, regions, n_regions, bed_path, window, min_depth, exclude, verbose, NULL, 0u, 0);
+}
+
+int cbc_cli_decompress_bedcov_ext(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                                  const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose,
+                                  const uint32_t *thr, uint32_t n_thr, int count_reads)
+{
+    return bedcov_run(in, out, ref, device, regions, n_regions, bed_path, window, min_depth, exclude, verbose, thr, n_thr, count_reads);
 }
 
 /* `cbc -d|-x ... --depth-hist [--region A ...] [--regions-file FILE] [--hist-max M]`: per contig how many positions have each

@@ -24,6 +24,7 @@
 #include "cbc_depth_body.h"
 #include "cbc_targets_body.h"
 #include "cbc_cov_body.h"
+#include "cbc_covx_body.h"
 #include "cbc_hist_body.h"
 #include "cbc_plan.h"
 #include "cbc_stream_body.h"
@@ -154,6 +155,18 @@ __global__ void __launch_bounds__(64)
 cbc_cov_apply_kernel(cbc_cov_args A) { cbc_cov_apply<WaveGPU>(A, blockIdx.x); }
 __global__ void __launch_bounds__(64)
 cbc_cov_lookup_kernel(cbc_cov_args A) { cbc_cov_lookup<WaveGPU>(A, blockIdx.x); }
+
+/* Read counts and depth thresholds per query (cbc_gpu_decode_coverage_ext, cbc_covx_body.h): the mark pass that also notes
+ * where every piece starts (the tile, scan and compact kernels above then run over the starts as they do over the difference
+ * array), one wavefront per CBC_DEPTH_LINES runs for the thresholds' weights and prefixes, one lane per query for the lookup */
+__global__ void __launch_bounds__(64)
+cbc_targets_mark_starts_kernel(cbc_tdepth_args A, uint32_t *starts) { if (blockIdx.x < A.D.R.n_blocks) cbc_targets_mark<WaveGPU, true>(A, blockIdx.x, starts); }
+__global__ void __launch_bounds__(64)
+cbc_covx_weights_kernel(cbc_covx_args A) { cbc_covx_weights<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_covx_apply_kernel(cbc_covx_args A) { cbc_covx_apply<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_covx_lookup_kernel(cbc_covx_args A) { cbc_covx_lookup<WaveGPU>(A, blockIdx.x); }
 
 /* Depth histogram (cbc_gpu_decode_depth_hist, cbc_hist_body.h), behind the same mark / tile / scan / compact passes: a bounded
  * grid of one-wavefront workgroups adds the runs' lengths to the bins of their depths (shallow bins in the workgroup's LDS table,
@@ -328,12 +341,12 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
 /* grow-only device buffer owned by the context: the host-buffer entry points keep their device arrays between calls
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
-enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_COUNT };
+enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_XSTARTS, A_XTILE, A_XSP, A_XTHR, A_XPRE, A_XOUT, A_COUNT };
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
 /* what decode_blocks_impl runs behind the decode (its post-decode stage): nothing (plain, 2-bit, span, long reads), or the
- * stage of cbc_gpu_decode_region, _sam, _depth, _targets (reads, SAM, depth), _coverage, _depth_hist */
-enum post_kind { POST_NONE, POST_REGION, POST_SAM, POST_DEPTH, POST_TG_READS, POST_TG_SAM, POST_TG_DEPTH, POST_COV, POST_HIST };
+ * stage of cbc_gpu_decode_region, _sam, _depth, _targets (reads, SAM, depth), _coverage, _depth_hist, _coverage_ext */
+enum post_kind { POST_NONE, POST_REGION, POST_SAM, POST_DEPTH, POST_TG_READS, POST_TG_SAM, POST_TG_DEPTH, POST_COV, POST_HIST, POST_COVX };
 
 struct cbc_gpu_ctx {
     int device;
@@ -345,6 +358,8 @@ struct cbc_gpu_ctx {
     hipEvent_t ev_rg[5];           /* region decode: before and after the decode, after the filter + scan, after the text kernel;
                                     * coverage: decode, mark, scan + compact, text (the fifth event) */
     hipEvent_t ev_cov[4];          /* cbc_gpu_decode_coverage: behind ev_rg[3], after the weights, their scans, the apply and the lookup */
+    hipEvent_t ev_covx[5];         /* cbc_gpu_decode_coverage_ext: behind ev_cov[3], after the start points' scans + compact, the thresholds'
+                                    * weights, their scans, their prefixes and the lookup */
     hipEvent_t ev_hist[2];         /* cbc_gpu_decode_depth_hist: behind ev_rg[3], after zeroing + accumulate and after the bin compaction */
     post_kind last_post;           /* whose times those events hold: the kind of the most recent call with a post-decode stage
                                     * (POST_NONE: none yet), set by decode_blocks_impl and asked by the cbc_gpu_last_*_ms */
@@ -428,6 +443,8 @@ API int cbc_gpu_init(int device_ordinal, cbc_gpu_ctx **out)
         if (hipEventCreate(&ctx->ev_cov[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     for (int k = 0; k < 2; k++)
         if (hipEventCreate(&ctx->ev_hist[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
+    for (int k = 0; k < 5; k++)
+        if (hipEventCreate(&ctx->ev_covx[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) != hipSuccess || cus <= 0) cus = 256;
@@ -458,6 +475,7 @@ API int cbc_gpu_shutdown(cbc_gpu_ctx *ctx)
     for (int k = 0; k < 5; k++) (void)hipEventDestroy(ctx->ev_rg[k]);
     for (int k = 0; k < 4; k++) (void)hipEventDestroy(ctx->ev_cov[k]);
     for (int k = 0; k < 2; k++) (void)hipEventDestroy(ctx->ev_hist[k]);
+    for (int k = 0; k < 5; k++) (void)hipEventDestroy(ctx->ev_covx[k]);
     for (int k = 0; k < CBC_N_KSTREAMS; k++) { (void)hipEventDestroy(ctx->ev_done[k]); (void)hipStreamDestroy(ctx->s_k[k]); }
     (void)hipStreamDestroy(ctx->s_copy);
     (void)hipStreamDestroy(ctx->stream);
@@ -1016,12 +1034,15 @@ API int cbc_gpu_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device_batc
     return decode_blocks_launch(ctx, b, hip_stream, 0u);
 }
 
-static bool post_is_depth(post_kind k) { return k == POST_DEPTH || k == POST_TG_DEPTH || k == POST_COV || k == POST_HIST; }
+static bool post_is_cov(post_kind k) { return k == POST_COV || k == POST_COVX; }
+static bool post_is_depth(post_kind k) { return k == POST_DEPTH || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST; }
 static bool post_is_sam(post_kind k) { return k == POST_SAM || k == POST_TG_SAM; }
-static bool post_is_targets(post_kind k) { return k == POST_TG_READS || k == POST_TG_SAM || k == POST_TG_DEPTH || k == POST_COV || k == POST_HIST; }
+static bool post_is_targets(post_kind k) { return k == POST_TG_READS || k == POST_TG_SAM || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST; }
 
 /* the queries (n_q pairs slot, len in the compressed coordinate), the depth that counts as covered, where the results go */
-struct cov_req { const uint32_t *q; uint32_t n_q, min_depth; uint64_t *sum; uint32_t *covered; };
+struct cov_req { const uint32_t *q; uint32_t n_q, min_depth; uint64_t *sum; uint32_t *covered;
+                 /* COVX: the thresholds, where their n_q * n_thr counts go, where the read counts go (NULL: none) */
+                 bool ext; const uint32_t *thr; uint32_t n_thr; uint32_t *thr_covered, *reads; };
 /* the depth from which the bins fold (2^32 - 1: none), where the pairs go (bin_cap of each) and how many there are */
 struct hist_req { uint32_t fold; uint32_t *bin_depth, *bin_bases; uint32_t bin_cap; uint32_t *n_bins; };
 
@@ -1043,14 +1064,14 @@ struct post_req {
     /* targets kinds: the interval table (n_iv pairs), per block its range of it, and for the depth kinds the first slot of
      * every interval in the compressed coordinate (n_iv + 1 entries) */
     const uint32_t *iv; uint32_t n_iv; const uint32_t *block_iv, *iv_off;
-    cov_req cov;                   /* COV */
+    cov_req cov;                   /* COV, COVX */
     hist_req hist;                 /* HIST */
 };
 
 /* sizes derived from the request: tiles of the difference array (d_words = W + 1 words), change points (two per read at most,
- * two per interval edge), text tiles of the runs, entries the text's size scan runs over; histogram: min(fold, reads) + 1 bins
+ * two per interval edge; start points: one per read and interval), text tiles of the runs, entries the text's size scan runs over; histogram: min(fold, reads) + 1 bins
  * in whole tiles, the non-zero ones are fewer than the bins and than the runs */
-struct post_sizes { uint64_t d_words, h_bins; uint32_t n_tiles, cp_cap, n_ttiles, n_sized, n_btiles, h_out_cap; };
+struct post_sizes { uint64_t d_words, h_bins; uint32_t n_tiles, cp_cap, n_ttiles, n_sized, n_btiles, h_out_cap, sp_cap; };
 
 static post_sizes post_sizes_of(const post_req *rg, uint32_t n_blocks, uint64_t n_recs)
 {
@@ -1064,6 +1085,8 @@ static post_sizes post_sizes_of(const post_req *rg, uint32_t n_blocks, uint64_t 
     z.cp_cap = (uint32_t)(2u * n_recs + (tg ? 2u * (uint64_t)rg->n_iv : 0u));
     z.n_ttiles = (z.cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
     z.n_sized = z.n_ttiles;
+    /* start points: a piece starts where its read starts or on an interval's first slot */
+    if (rg->kind == POST_COVX) z.sp_cap = (uint32_t)(n_recs + rg->n_iv);
     if (rg->kind != POST_HIST) return z;
     z.h_bins = (n_recs < rg->hist.fold ? n_recs : rg->hist.fold) + 1u;
     z.n_btiles = (uint32_t)((z.h_bins + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
@@ -1100,7 +1123,7 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
         NEED(A_TBIV, (uint64_t)n_blocks * 8, "hipMalloc block intervals");
         if (post_is_depth(k)) NEED(A_TOFF, ((uint64_t)rg->n_iv + 1) * 4, "hipMalloc interval slots");
     }
-    if (k == POST_COV) {
+    if (post_is_cov(k)) {
         NEED(A_CVTILE, (uint64_t)z.n_ttiles * 3 * sizeof(cbc_block_result) + ((uint64_t)z.n_ttiles + 1) * 3 * 8, "hipMalloc coverage tiles");
         if (arena_need(ctx, A_CVPRE, (uint64_t)z.cp_cap * 12 + 16, "hipMalloc coverage prefixes")) {
             (void)hipGetLastError();
@@ -1108,6 +1131,25 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
         }
         NEED(A_CVQ, (uint64_t)rg->cov.n_q * 8 + 16, "hipMalloc coverage queries");
         NEED(A_CVOUT, (uint64_t)rg->cov.n_q * 12 + 16, "hipMalloc coverage results");
+    }
+    if (k == POST_COVX) {
+        const cov_req *cv = &rg->cov;
+        if (cv->reads) {                                       /* the pieces' first slots: a second array of the difference array's size */
+            if (arena_need(ctx, A_XSTARTS, (uint64_t)z.n_tiles * CBC_DEPTH_TILE * 4, "hipMalloc start slots")) {
+                (void)hipGetLastError();
+                return set_err(ctx, CBC_E_NOMEM, "no device memory for the pieces' start slots (4 bytes per position)", hipSuccess);
+            }
+            NEED(A_XTILE, (uint64_t)z.n_tiles * 2 * sizeof(cbc_block_result) + ((uint64_t)z.n_tiles + 1) * 2 * 8, "hipMalloc start tiles");
+            NEED(A_XSP, (uint64_t)z.sp_cap * 2 * 4 + 16, "hipMalloc start points");
+        }
+        if (cv->n_thr) {
+            NEED(A_XTHR, (uint64_t)cv->n_thr * (z.n_ttiles * sizeof(cbc_block_result) + ((uint64_t)z.n_ttiles + 1) * 8), "hipMalloc threshold tiles");
+            if (arena_need(ctx, A_XPRE, (uint64_t)z.cp_cap * 4 * cv->n_thr + 16, "hipMalloc threshold prefixes")) {
+                (void)hipGetLastError();
+                return set_err(ctx, CBC_E_NOMEM, "no device memory for the threshold prefixes (4 bytes per threshold and change point)", hipSuccess);
+            }
+        }
+        NEED(A_XOUT, (uint64_t)cv->n_q * 4 * (cv->n_thr + 1ull) + 16, "hipMalloc threshold and read counts");
     }
     if (k == POST_HIST) {
         if (arena_need(ctx, A_HBINS, (uint64_t)z.n_btiles * CBC_DEPTH_TILE * 4, "hipMalloc histogram bins") ||
@@ -1136,7 +1178,7 @@ static int post_h2d(cbc_gpu_ctx *ctx, const post_req *rg, uint32_t n_blocks, hip
         HIPCHK(hipMemcpyAsync(ctx->arena[A_TBIV].p, rg->block_iv, (uint64_t)n_blocks * 8, hipMemcpyHostToDevice, sc), "H2D block intervals");
         if (post_is_depth(k)) HIPCHK(hipMemcpyAsync(ctx->arena[A_TOFF].p, rg->iv_off, ((uint64_t)rg->n_iv + 1) * 4, hipMemcpyHostToDevice, sc), "H2D interval slots");
     }
-    if (k == POST_COV) HIPCHK(hipMemcpyAsync(ctx->arena[A_CVQ].p, rg->cov.q, (uint64_t)rg->cov.n_q * 8, hipMemcpyHostToDevice, sc), "H2D coverage queries");
+    if (post_is_cov(k)) HIPCHK(hipMemcpyAsync(ctx->arena[A_CVQ].p, rg->cov.q, (uint64_t)rg->cov.n_q * 8, hipMemcpyHostToDevice, sc), "H2D coverage queries");
     return CBC_OK;
 }
 
@@ -1233,7 +1275,11 @@ static int launch_depth_front(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *
     if (post_is_targets(rg->kind)) {
         ta->D = *da; ta->iv = (const uint32_t *)ctx->arena[A_TIV].p; ta->iv_off = (const uint32_t *)ctx->arena[A_TOFF].p;
         ta->block_iv = (const uint32_t *)ctx->arena[A_TBIV].p; ta->n_iv = rg->n_iv;
-        hipLaunchKernelGGL(cbc_targets_mark_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, *ta);
+        if (rg->kind == POST_COVX && rg->cov.reads) {          /* the mark that also notes the pieces' first slots */
+            uint32_t *starts = (uint32_t *)ctx->arena[A_XSTARTS].p;
+            HIPCHK(hipMemsetAsync(starts, 0, da->diff_words * 4, ks), "memset start slots");
+            hipLaunchKernelGGL(cbc_targets_mark_starts_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, *ta, starts);
+        } else hipLaunchKernelGGL(cbc_targets_mark_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, *ta);
     } else hipLaunchKernelGGL(cbc_depth_mark_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, *da);
     HIPCHK(hipGetLastError(), "launch cbc_depth_mark_kernel");
     HIPCHK(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
@@ -1295,6 +1341,61 @@ static int launch_coverage(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *cov,
     return CBC_OK;
 }
 
+/* read counts and thresholds, behind launch_coverage: the start points (tile sums, scans, compact over the starts), the
+ * thresholds' weights, their scans and prefixes, the lookup.  A pass nobody asked for is not launched; its event still is. */
+static int launch_coverage_ext(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *cov, const post_sizes &z, const cbc_depth_args &da)
+{
+    const uint32_t n_tiles = z.n_tiles, n_ttiles = z.n_ttiles, n_thr = cov->n_thr;
+    cbc_covx_args xa;
+    memset(&xa, 0, sizeof xa);
+    xa.cp_pos = da.cp_pos; xa.cp_dep = da.cp_dep; xa.cnt_off = da.cnt_off;
+    xa.q = (const uint32_t *)ctx->arena[A_CVQ].p;
+    xa.thr_covered = (uint32_t *)ctx->arena[A_XOUT].p;
+    xa.n_thr = n_thr; xa.cp_cap = z.cp_cap; xa.sp_cap = z.sp_cap; xa.n_tiles = n_tiles; xa.n_ttiles = n_ttiles; xa.n_q = cov->n_q;
+    xa.slots = (uint32_t)z.d_words;
+    for (uint32_t t = 0; t < n_thr; t++) xa.thr[t] = cov->thr[t];
+    if (cov->reads) {
+        cbc_depth_args sa = da;                                /* the depth passes over the starts: CS in the place of the depth */
+        sa.diff = (uint32_t *)ctx->arena[A_XSTARTS].p;
+        sa.tile_sum = (cbc_block_result *)ctx->arena[A_XTILE].p; sa.tile_cnt = sa.tile_sum + n_tiles;
+        uint64_t *soff = (uint64_t *)(sa.tile_cnt + n_tiles);
+        sa.sum_off = soff; sa.cnt_off = soff + n_tiles + 1;
+        sa.cp_pos = (uint32_t *)ctx->arena[A_XSP].p; sa.cp_dep = sa.cp_pos + z.sp_cap; sa.cp_cap = z.sp_cap;
+        hipLaunchKernelGGL(cbc_depth_tile_kernel, dim3(n_tiles), dim3(64), 0, ks, sa);
+        HIPCHK(hipGetLastError(), "launch cbc_depth_tile_kernel");
+        launch_scan_sizes(ks, sa.tile_sum, soff, n_tiles);
+        launch_scan_sizes(ks, sa.tile_cnt, soff + n_tiles + 1, n_tiles);
+        HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+        hipLaunchKernelGGL(cbc_depth_compact_kernel, dim3(n_tiles), dim3(64), 0, ks, sa);
+        HIPCHK(hipGetLastError(), "launch cbc_depth_compact_kernel");
+        xa.sp_pos = sa.cp_pos; xa.sp_cnt = sa.cp_dep; xa.sp_off = sa.cnt_off;
+        xa.reads = xa.thr_covered + (uint64_t)cov->n_q * n_thr;
+    }
+    HIPCHK(hipEventRecord(ctx->ev_covx[0], ks), "hipEventRecord");
+    if (n_thr) {
+        xa.tile_thr = (cbc_block_result *)ctx->arena[A_XTHR].p;
+        uint64_t *toff = (uint64_t *)(xa.tile_thr + (uint64_t)n_thr * n_ttiles);
+        xa.thr_off = toff;
+        xa.pre_thr = (uint32_t *)ctx->arena[A_XPRE].p;
+        hipLaunchKernelGGL(cbc_covx_weights_kernel, dim3(n_ttiles), dim3(64), 0, ks, xa);
+        HIPCHK(hipGetLastError(), "launch cbc_covx_weights_kernel");
+        HIPCHK(hipEventRecord(ctx->ev_covx[1], ks), "hipEventRecord");
+        for (uint32_t t = 0; t < n_thr; t++) launch_scan_sizes(ks, xa.tile_thr + (uint64_t)t * n_ttiles, toff + (uint64_t)t * (n_ttiles + 1u), n_ttiles);
+        HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+        HIPCHK(hipEventRecord(ctx->ev_covx[2], ks), "hipEventRecord");
+        hipLaunchKernelGGL(cbc_covx_apply_kernel, dim3(n_ttiles), dim3(64), 0, ks, xa);
+        HIPCHK(hipGetLastError(), "launch cbc_covx_apply_kernel");
+        HIPCHK(hipEventRecord(ctx->ev_covx[3], ks), "hipEventRecord");
+    } else
+        for (int k = 1; k < 4; k++) HIPCHK(hipEventRecord(ctx->ev_covx[k], ks), "hipEventRecord");
+    if (n_thr || cov->reads) {
+        hipLaunchKernelGGL(cbc_covx_lookup_kernel, dim3((cov->n_q + 63u) / 64u), dim3(64), 0, ks, xa);
+        HIPCHK(hipGetLastError(), "launch cbc_covx_lookup_kernel");
+    }
+    HIPCHK(hipEventRecord(ctx->ev_covx[4], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
 /* histogram: zero, accumulate, count + scan + write of the bins: no text */
 static int launch_hist(cbc_gpu_ctx *ctx, hipStream_t ks, const hist_req *hist, const post_sizes &z, const cbc_depth_args &da)
 {
@@ -1334,11 +1435,15 @@ static int post_fetch_sizes(cbc_gpu_ctx *ctx, const post_req *rg, const post_siz
         HIPCHK(hipMemcpyAsync(g->dctr, ctx->arena[A_DCTR].p, 16, hipMemcpyDeviceToHost, sc), "D2H depth counters");
         if (rg->kind == POST_HIST)
             HIPCHK(hipMemcpyAsync(&g->h_count, (uint64_t *)((cbc_block_result *)ctx->arena[A_HTILE].p + z.n_btiles) + z.n_btiles, 8, hipMemcpyDeviceToHost, sc), "D2H histogram size");
-        else if (rg->kind != POST_COV)
+        else if (!post_is_cov(rg->kind))
             HIPCHK(hipMemcpyAsync(&g->total, (uint64_t *)ctx->arena[A_OFF].p + z.n_ttiles, 8, hipMemcpyDeviceToHost, sc), "D2H text size");
         else {                                                 /* the numbers, not the track: 12 bytes per query */
             HIPCHK(hipMemcpyAsync(rg->cov.sum, ctx->arena[A_CVOUT].p, (uint64_t)rg->cov.n_q * 8, hipMemcpyDeviceToHost, sc), "D2H coverage sums");
             HIPCHK(hipMemcpyAsync(rg->cov.covered, (uint64_t *)ctx->arena[A_CVOUT].p + rg->cov.n_q, (uint64_t)rg->cov.n_q * 4, hipMemcpyDeviceToHost, sc), "D2H coverage counts");
+            if (rg->kind == POST_COVX && rg->cov.n_thr)        /* + 4 bytes per threshold and query, + 4 for the read count */
+                HIPCHK(hipMemcpyAsync(rg->cov.thr_covered, ctx->arena[A_XOUT].p, (uint64_t)rg->cov.n_q * rg->cov.n_thr * 4, hipMemcpyDeviceToHost, sc), "D2H threshold counts");
+            if (rg->kind == POST_COVX && rg->cov.reads)
+                HIPCHK(hipMemcpyAsync(rg->cov.reads, (uint32_t *)ctx->arena[A_XOUT].p + (uint64_t)rg->cov.n_q * rg->cov.n_thr, (uint64_t)rg->cov.n_q * 4, hipMemcpyDeviceToHost, sc), "D2H read counts");
         }
         return CBC_OK;
     }
@@ -1477,6 +1582,11 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 case POST_COV:
                     rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
                     if (!rc) rc = launch_coverage(ctx, ks, &rg->cov, z, da);
+                    break;
+                case POST_COVX:
+                    rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
+                    if (!rc) rc = launch_coverage(ctx, ks, &rg->cov, z, da);
+                    if (!rc) rc = launch_coverage_ext(ctx, ks, &rg->cov, z, da);
                     break;
                 case POST_HIST:
                     rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
@@ -1788,7 +1898,7 @@ static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
     }
     if (depth && L.nrec > 0x3fffffffull) { bad = "targets decode: more than 2^30 - 1 reads in one depth call"; goto out; }
     if (!L.nrec || (depth && lo >= hi)) goto out;               /* no read, or none that reaches an interval: CBC_OK */
-    post_req_init(&rg, cov ? POST_COV : hist ? POST_HIST : depth ? POST_TG_DEPTH : sam ? POST_TG_SAM : POST_TG_READS, t->smax,
+    post_req_init(&rg, cov ? (cov->ext ? POST_COVX : POST_COV) : hist ? POST_HIST : depth ? POST_TG_DEPTH : sam ? POST_TG_SAM : POST_TG_READS, t->smax,
                   window_start, text, text_cap, sam ? L.nrec * (35ull + stride) + L.name_sum : L.nrec * (stride + 1ull), text_bytes, n_reads);
     rg.beg = 1u; rg.end = UINT64_MAX;
     rg.names = (const uint8_t *)names; rg.names_bytes = names_bytes; rg.block_name = sam ? L.bn : NULL;
@@ -1856,11 +1966,60 @@ API int cbc_gpu_decode_coverage(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in
     if (min_depth < 1 || n_q > (1u << 24) || iv_count < 1 || iv_first > t->n_iv || iv_count > t->n_iv - iv_first)
         return set_err(ctx, CBC_E_ARG, "coverage wants min_depth >= 1, at most 2^24 queries and the contig's intervals inside the table", hipSuccess);
     if (n_q == 0) return CBC_OK;
-    const cov_req cq = { q, n_q, min_depth, sum, covered };
+    const cov_req cq = { q, n_q, min_depth, sum, covered, false, NULL, 0u, NULL, NULL };
     uint64_t text_bytes = 0, n_runs = 0;
     return decode_targets_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
                                n_contigs, t, CBC_TARGETS_DEPTH, exclude_flags, NULL, 0, &text_bytes, n_reads, &n_runs, results, &cq,
                                iv_first, iv_count);
+}
+
+/* read counts and depth thresholds per query: cbc_gpu_decode_coverage with the mark pass that notes
+ * the pieces' first slots, then the start points, the thresholds' weights, scans and prefixes and one lookup (cbc_covx_body.h) */
+API int cbc_gpu_decode_coverage_ext(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                    uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                                    const uint32_t *block_contig, const char *names, uint32_t names_bytes,
+                                    const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_gpu_targets *t,
+                                    uint32_t iv_first, uint32_t iv_count, const uint32_t *q, uint32_t n_q, uint32_t exclude_flags,
+                                    uint32_t min_depth, uint64_t *sum, uint32_t *covered, uint64_t *n_reads, cbc_block_result *results,
+                                    const uint32_t *thresholds, uint32_t n_thr, uint32_t *thr_covered, uint32_t *reads)
+{
+    if (!ctx || !t || !n_reads || (n_q && (!q || !sum || !covered)) || (n_thr && !thresholds) || (n_q && n_thr && !thr_covered)) return CBC_E_ARG;
+    *n_reads = 0;
+    if (n_q) { memset(sum, 0, (size_t)n_q * 8); memset(covered, 0, (size_t)n_q * 4); }
+    if (n_q <= (1u << 24) && n_thr <= CBC_COVX_MAX_THR) {
+        if (n_thr) memset(thr_covered, 0, (size_t)n_q * n_thr * 4);
+        if (reads) memset(reads, 0, (size_t)n_q * 4);
+    }
+    if (min_depth < 1 || n_q > (1u << 24) || iv_count < 1 || iv_first > t->n_iv || iv_count > t->n_iv - iv_first)
+        return set_err(ctx, CBC_E_ARG, "coverage wants min_depth >= 1, at most 2^24 queries and the contig's intervals inside the table", hipSuccess);
+    bool asc = n_thr <= CBC_COVX_MAX_THR;
+    for (uint32_t i = 0; asc && i < n_thr; i++) asc = thresholds[i] >= 1u && (i == 0 || thresholds[i] > thresholds[i - 1]);
+    if (!asc) return set_err(ctx, CBC_E_ARG, "coverage wants at most 8 thresholds, each >= 1 and strictly ascending", hipSuccess);
+    if (n_q == 0) return CBC_OK;
+    const cov_req cq = { q, n_q, min_depth, sum, covered, true, thresholds, n_thr, thr_covered, reads };
+    uint64_t text_bytes = 0, n_runs = 0;
+    const int rc = decode_targets_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes,
+                                       contig_name_off, n_contigs, t, CBC_TARGETS_DEPTH, exclude_flags, NULL, 0, &text_bytes, n_reads, &n_runs,
+                                       results, &cq, iv_first, iv_count);
+    if (rc == CBC_E_BLOCK) {                                   /* a failed block: no numbers */
+        memset(sum, 0, (size_t)n_q * 8); memset(covered, 0, (size_t)n_q * 4);
+        if (n_thr) memset(thr_covered, 0, (size_t)n_q * n_thr * 4);
+        if (reads) memset(reads, 0, (size_t)n_q * 4);
+    }
+    return rc;
+}
+
+/* kernel times of the most recent cbc_gpu_decode_coverage_ext: cov_ms[7] as cbc_gpu_last_coverage_ms gives them (the mark is
+ * the one that also notes the starts), ext_ms[5] the added passes */
+API int cbc_gpu_last_coverage_ext_ms(cbc_gpu_ctx *ctx, float *cov_ms, float *ext_ms)
+{
+    if (!ctx || !cov_ms || !ext_ms || ctx->last_post != POST_COVX) return CBC_E_ARG;
+    const hipEvent_t ev[] = { ctx->ev_rg[0], ctx->ev_rg[1], ctx->ev_rg[2], ctx->ev_rg[3], ctx->ev_cov[0], ctx->ev_cov[1], ctx->ev_cov[2], ctx->ev_cov[3],
+                              ctx->ev_covx[0], ctx->ev_covx[1], ctx->ev_covx[2], ctx->ev_covx[3], ctx->ev_covx[4] };
+    float *out[12];
+    for (int i = 0; i < 7; i++) out[i] = cov_ms + i;
+    for (int i = 0; i < 5; i++) out[7 + i] = ext_ms + i;
+    return last_ms(ctx, ev, out, 12);
 }
 
 /* depth histogram: the depth form of cbc_gpu_decode_targets up to the change points, laid over all the

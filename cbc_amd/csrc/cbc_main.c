@@ -56,6 +56,9 @@ static void usage(const char *p)
             "                   given: NAME, start, end, sum of the depth, positions with depth >= D, mean depth with two decimals;\n"
             "                   depth as for --depth; the numbers are computed on the device; not with --sam or --depth)\n"
             "         --window N (with --bedcov: cut every query into windows of N bases)  --min-depth D (with --bedcov: default 1)\n"
+            "         --thresholds T1,T2,... (with --bedcov: 1 to 8 depths, ascending; one more column each, the positions with depth >= Ti)\n"
+            "         --count-reads (with --bedcov: a last column, the kept reads with at least one covered base in the query; a read\n"
+            "                        that overlaps two queries counts in both)\n"
             "         --depth-hist (per contig and depth how many positions have it: NAME, depth, bases, positions counted, fraction\n"
             "                       with six decimals; then the same summed under the name genome; depth as for --depth; whole contigs,\n"
             "                       or the merged intervals of --region / --regions-file; binned on the device; takes\n"
@@ -445,6 +448,9 @@ int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref,
                                const char *bed_path, uint32_t output, uint32_t exclude, int verbose);
 int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                               const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose);
+int cbc_cli_decompress_bedcov_ext(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                                  const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose,
+                                  const uint32_t *thr, uint32_t n_thr, int count_reads);
 int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                             const char *bed_path, uint32_t max_depth, uint32_t exclude, int verbose);
 
@@ -462,6 +468,8 @@ int main(int argc, char **argv)
     int bedcov = 0, window_given = 0, min_depth_given = 0;
     uint64_t cov_window = 0;
     uint32_t cov_min_depth = 1;
+    int count_reads = 0, thr_given = 0;
+    uint32_t thr[8], n_thr = 0;
     int depth_hist = 0, hist_max_given = 0;
     uint32_t hist_max = 0;
     g_main_t0 = now_s();
@@ -502,6 +510,21 @@ int main(int argc, char **argv)
                 fprintf(stderr, w ? "cbc: --window wants a number of bases, 1 or more\n" : "cbc: --min-depth wants a depth in 1..4294967295\n"); return 1; }
             if (w) { cov_window = x; window_given = 1; } else { cov_min_depth = (uint32_t)x; min_depth_given = 1; }
             continue;
+        }
+        if (!strcmp(a, "--count-reads")) { count_reads = 1; continue; }
+        if (!strcmp(a, "--thresholds") && i + 1 < argc) {         /* T1,T2,...: 1 to 8 decimal depths, strictly ascending */
+            const char *v = argv[++i];
+            int ok = v[0] != 0;
+            n_thr = 0;
+            while (ok && *v) {
+                char *e = NULL;
+                const unsigned long long x = strtoull(v, &e, 10);
+                ok = v[0] >= '0' && v[0] <= '9' && e && e - v <= 10 && x >= 1 && x <= 0xffffffffull && n_thr < 8 && (n_thr == 0 || x > thr[n_thr - 1]) &&
+                     (*e == 0 || (*e == ',' && e[1] != 0));
+                if (ok) { thr[n_thr++] = (uint32_t)x; v = *e ? e + 1 : e; }
+            }
+            if (!ok) { fprintf(stderr, "cbc: --thresholds wants 1 to 8 depths in 1..4294967295, separated by commas and strictly ascending\n"); return 1; }
+            thr_given = 1; continue;
         }
         if (!strcmp(a, "--depth-hist")) { depth_hist = 1; continue; }
         if (!strcmp(a, "--hist-max") && i + 1 < argc) {
@@ -561,6 +584,7 @@ int main(int argc, char **argv)
     if (depth_out && sam_out) { fprintf(stderr, "cbc: --depth and --sam are two different outputs; give one of them\n"); return 1; }
     if (depth_out && ndev > 1) { fprintf(stderr, "cbc: --depth decodes on one device; give a single --devices ordinal\n"); return 1; }
     if ((window_given || min_depth_given) && !bedcov) { fprintf(stderr, "cbc: %s applies to --bedcov\n", window_given ? "--window" : "--min-depth"); return 1; }
+    if ((thr_given || count_reads) && !bedcov) { fprintf(stderr, "cbc: %s applies to --bedcov\n", thr_given ? "--thresholds" : "--count-reads"); return 1; }
     if (bedcov && mode != 2) { fprintf(stderr, "cbc: --bedcov applies to decompression (-d / -x)\n"); return 1; }
     if (bedcov && (sam_out || depth_out)) { fprintf(stderr, "cbc: --bedcov, --depth and --sam are different outputs; give one of them\n"); return 1; }
     if (bedcov && ndev > 1) { fprintf(stderr, "cbc: --bedcov decodes on one device; give a single --devices ordinal\n"); return 1; }
@@ -571,6 +595,9 @@ int main(int argc, char **argv)
     if (depth_hist)
         return cbc_cli_decompress_hist(files[0], files[1], files[2], device, regions, n_regions, regions_file, hist_max, depth_exclude, verbose);
     if (depth_excl_given && !depth_out && !bedcov) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
+    if (bedcov && (thr_given || count_reads))
+        return cbc_cli_decompress_bedcov_ext(files[0], files[1], files[2], device, regions, n_regions, regions_file, cov_window, cov_min_depth,
+                                             depth_exclude, verbose, thr, n_thr, count_reads);
     if (bedcov)
         return cbc_cli_decompress_bedcov(files[0], files[1], files[2], device, regions, n_regions, regions_file, cov_window, cov_min_depth,
                                          depth_exclude, verbose);

@@ -215,8 +215,10 @@ CBC_FN void cbc_targets_sam_write(const cbc_targets_args &A, uint32_t blk, uint3
 }
 
 /* ---- depth: mark ------------------------------------------------------------------------------------------------------- */
-template <class W>
-CBC_FN void cbc_targets_mark(const cbc_tdepth_args &A, uint32_t blk)
+/* STARTS (cbc_gpu_decode_coverage_ext, cbc_covx_body.h): per piece also +1 at its first slot in `starts`, an array as long as
+ * the difference array */
+template <class W, bool STARTS = false>
+CBC_FN void cbc_targets_mark(const cbc_tdepth_args &A, uint32_t blk, uint32_t *starts = NULL)
 {
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
@@ -244,6 +246,7 @@ CBC_FN void cbc_targets_mark(const cbc_tdepth_args &A, uint32_t blk)
             const Mask w = act & (t >= s) & (i1 > i0) & (i1 < lim);
             W::list_add(A.D.diff, i0, W::splat(1u), w);
             W::list_add(A.D.diff, i1, W::splat(0xffffffffu), w);
+            if (STARTS) W::list_add(starts, i0, W::splat(1u), w);
             i = i + 1u;
             act = act & (i < T.cnt);
         }

@@ -248,6 +248,11 @@ def lib():
                                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                               ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                               ctypes.c_void_p]
+        L.cbc_gpu_decode_coverage_ext.restype = ctypes.c_int
+        L.cbc_gpu_decode_coverage_ext.argtypes = L.cbc_gpu_decode_coverage.argtypes + [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                                                       ctypes.c_void_p]
+        L.cbc_gpu_last_coverage_ext_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_coverage_ext_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.cbc_gpu_last_coverage_ms.restype = ctypes.c_int
         L.cbc_gpu_last_coverage_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 7
         L.cbc_gpu_decode_depth_hist.restype = ctypes.c_int
@@ -282,7 +287,8 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_stash_reset", "cbc_gpu_stash_bytes", "cbc_gpu_stash_fetch", "cbc_gpu_decode_region",
            "cbc_gpu_decode_blocks_span", "cbc_gpu_last_region_ms", "cbc_gpu_decode_sam", "cbc_gpu_last_sam_ms",
            "cbc_gpu_decode_depth", "cbc_gpu_last_depth_ms", "cbc_gpu_decode_targets", "cbc_gpu_last_targets_ms",
-           "cbc_gpu_decode_coverage", "cbc_gpu_last_coverage_ms", "cbc_gpu_decode_depth_hist", "cbc_gpu_last_hist_ms"]
+           "cbc_gpu_decode_coverage", "cbc_gpu_last_coverage_ms", "cbc_gpu_decode_depth_hist", "cbc_gpu_last_hist_ms",
+           "cbc_gpu_decode_coverage_ext", "cbc_gpu_last_coverage_ext_ms"]
 
 
 class Encoder:
@@ -623,17 +629,30 @@ class Encoder:
             return text, n_reads, n_runs, (np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE))
         return text
 
-    def decode_coverage(self, plan: "host.UnpackPlan", queries, exclude_flags=0, min_depth=1, results=False):
+    def decode_coverage(self, plan: "host.UnpackPlan", queries, exclude_flags=0, min_depth=1, results=False, thresholds=(),
+                        count_reads=False):
         """Per-query coverage summary (cbc_gpu_decode_coverage): for every query of `queries` (a host.QuerySet of
         plan.queries()) the sum of the depth over its positions and the number of its positions with depth >= min_depth; depth
         as decode_depth counts it (reads with FLAG & exclude_flags != 0 left out).  One call and one decode per contig that has
         queries, intervals and blocks; only the numbers cross PCIe.  Returns numpy arrays in query order: contig (int64, -1:
-        not in the container's table), start0, end0 (uint64, 0-based half-open), sum (uint64), covered (uint32).  With
+        not in the container's table), start0, end0 (uint64, 0-based half-open), sum (uint64), covered (uint32).
+        thresholds (1 to 8 depths >= 1, strictly ascending) and / or count_reads=True go through
+        cbc_gpu_decode_coverage_ext: then thr (uint32, shape [n_q, T]: the positions with depth >= thresholds[t]) and / or reads
+        (uint32: the kept reads with at least one covered base in the query) follow covered, in that order.  With
         results=True the per-block decode results of the blocks decoded are appended and a failed block passes (it contributes
         nothing); otherwise it raises CbcGpuError."""
         plan.sam_header()                                     # refuses what the coordinates cannot carry, and long-read containers
         ts = queries.targets
+        thr = np.ascontiguousarray([int(t) for t in thresholds], dtype=np.uint64)
+        ext = bool(len(thr)) or bool(count_reads)
+        if len(thr) > 8 or (len(thr) and (thr.min() < 1 or thr.max() > 0xffffffff or (np.diff(thr.astype(np.int64)) <= 0).any())):
+            raise ValueError("thresholds are 1 to 8 depths in 1 .. 2^32 - 1, strictly ascending")
+        thr = thr.astype(np.uint32)
+        T = len(thr)
+        xthr = np.zeros((queries.n_q, T), dtype=np.uint32)
+        xreads = np.zeros(queries.n_q, dtype=np.uint32)
         self._coverage_ms = None
+        self._coverage_ext_ms = None
         caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
         pay = np.ascontiguousarray(plan.payloads)
         names = np.ascontiguousarray(plan.names)
@@ -658,20 +677,37 @@ class Encoder:
             res = np.zeros(nb, dtype=host.RESULT_DTYPE)
             nrd = ctypes.c_uint64()
             tg = GpuTargets(iv.ctypes.data, biv.ctypes.data, ts.n_iv, ts.smax)
-            rc = lib().cbc_gpu_decode_coverage(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
-                                               ws.ctypes.data, bc.ctypes.data, names.ctypes.data, names.size, noff.ctypes.data,
-                                               plan.n_contigs, ctypes.byref(tg), int(ts.contig_first[c]), ni, q.ctypes.data, len(idx),
-                                               int(exclude_flags), int(min_depth), s.ctypes.data, cv.ctypes.data, ctypes.byref(nrd),
-                                               res.ctypes.data)
-            if rc != 0 and not (results and rc == -4):
-                self._check(rc, "cbc_gpu_decode_coverage")
-            v = [ctypes.c_float() for _ in range(7)]
-            if lib().cbc_gpu_last_coverage_ms(self._ctx, *[ctypes.byref(x) for x in v]) == 0:
-                ms = tuple(float(x.value) for x in v)
-                self._coverage_ms = ms if self._coverage_ms is None else tuple(a + b for a, b in zip(self._coverage_ms, ms))
+            args = (self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
+                    ws.ctypes.data, bc.ctypes.data, names.ctypes.data, names.size, noff.ctypes.data,
+                    plan.n_contigs, ctypes.byref(tg), int(ts.contig_first[c]), ni, q.ctypes.data, len(idx),
+                    int(exclude_flags), int(min_depth), s.ctypes.data, cv.ctypes.data, ctypes.byref(nrd),
+                    res.ctypes.data)
+            if ext:
+                tc, rd = np.zeros((len(idx), T), dtype=np.uint32), np.zeros(len(idx), dtype=np.uint32)
+                rc = lib().cbc_gpu_decode_coverage_ext(*args, thr.ctypes.data if T else None, T, tc.ctypes.data if T else None,
+                                                       rd.ctypes.data if count_reads else None)
+                if rc != 0 and not (results and rc == -4):
+                    self._check(rc, "cbc_gpu_decode_coverage_ext")
+                v7, v5 = (ctypes.c_float * 7)(), (ctypes.c_float * 5)()
+                if lib().cbc_gpu_last_coverage_ext_ms(self._ctx, v7, v5) == 0:
+                    ms = tuple(float(x) for x in v7) + tuple(float(x) for x in v5)
+                    self._coverage_ext_ms = ms if self._coverage_ext_ms is None else tuple(a + b for a, b in zip(self._coverage_ext_ms, ms))
+                xthr[idx], xreads[idx] = tc, rd
+            else:
+                rc = lib().cbc_gpu_decode_coverage(*args)
+                if rc != 0 and not (results and rc == -4):
+                    self._check(rc, "cbc_gpu_decode_coverage")
+                v = [ctypes.c_float() for _ in range(7)]
+                if lib().cbc_gpu_last_coverage_ms(self._ctx, *[ctypes.byref(x) for x in v]) == 0:
+                    ms = tuple(float(x.value) for x in v)
+                    self._coverage_ms = ms if self._coverage_ms is None else tuple(a + b for a, b in zip(self._coverage_ms, ms))
             total[idx], covered[idx] = s, cv
             allres.append(res)
         out = (queries.contig.copy(), queries.start0.copy(), queries.end0.copy(), total, covered)
+        if T:
+            out += (xthr,)
+        if count_reads:
+            out += (xreads,)
         if results:
             return out + ((np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE)),)
         return out
@@ -682,6 +718,14 @@ class Encoder:
         if getattr(self, "_coverage_ms", None) is None:
             raise CbcGpuError("no decode_coverage has run on the device")
         return self._coverage_ms
+
+    def last_coverage_ext_ms(self):
+        """Kernel milliseconds of the last decode_coverage with thresholds or count_reads, summed over its calls: the seven of
+        last_coverage_ms (the mark also notes where the pieces start), then the start points (tile sums, scans, compact), the
+        thresholds' weights, their scans, their prefixes, the lookup."""
+        if getattr(self, "_coverage_ext_ms", None) is None:
+            raise CbcGpuError("no decode_coverage with thresholds or count_reads has run on the device")
+        return self._coverage_ext_ms
 
     def decode_depth_hist(self, plan: "host.UnpackPlan", targets=None, exclude_flags=0, max_depth=0, results=False):
         """Depth histogram (cbc_gpu_decode_depth_hist): per contig how many positions have each depth; depth as decode_depth

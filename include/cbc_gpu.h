@@ -413,6 +413,31 @@ int  cbc_gpu_decode_coverage(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_by
 int  cbc_gpu_last_coverage_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *weights_ms,
                               float *wscan_ms, float *apply_ms, float *lookup_ms);
 
+/* ---- per-query read counts and depth thresholds ------------------------------------------------------
+ * cbc_gpu_decode_coverage with two more answers per query, from data that call already leaves on the device:
+ *   thresholds[n_thr]       0 .. 8 depths, each >= 1, strictly ascending (CBC_E_ARG otherwise)
+ *   thr_covered[n_q * n_thr] query-major: the positions of query i with depth >= thresholds[t] at [i * n_thr + t]
+ *   reads[n_q] or NULL      the kept reads (FLAG & exclude_flags == 0, span >= 1) with at least one covered base in the query:
+ *                           POS <= end and POS + span - 1 >= beg.  A read that overlaps two queries counts in both.
+ * sum and covered are those of cbc_gpu_decode_coverage.  With reads != NULL the call keeps a second array of the difference
+ * array's size (4 bytes per slot) and 8 bytes per start point; the thresholds cost 4 bytes per threshold and change point:
+ * CBC_E_NOMEM when they cannot be had.  4 * (n_thr + 1) more bytes per query come back.  One chunk, one stream, no host round
+ * trip between the kernels.  A block that fails to decode contributes nothing and the call returns CBC_E_BLOCK with all four
+ * outputs zeroed. */
+int  cbc_gpu_decode_coverage_ext(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                 uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                                 const uint32_t *block_contig /* n_blocks */, const char *names, uint32_t names_bytes,
+                                 const uint32_t *contig_name_off /* n_contigs */, uint32_t n_contigs, const cbc_gpu_targets *t,
+                                 uint32_t iv_first, uint32_t iv_count, const uint32_t *q /* n_q pairs slot, len */, uint32_t n_q,
+                                 uint32_t exclude_flags, uint32_t min_depth, uint64_t *sum, uint32_t *covered, uint64_t *n_reads,
+                                 cbc_block_result *results /* n_blocks or NULL */, const uint32_t *thresholds, uint32_t n_thr,
+                                 uint32_t *thr_covered /* n_q * n_thr, query-major */, uint32_t *reads /* n_q or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_coverage_ext.  cov_ms[7]: the stretches of cbc_gpu_last_coverage_ms, the mark
+ * being the one that also notes where the pieces start.  ext_ms[5]: the start points (tile sums, scans, compact over the
+ * starts); the thresholds' weights; the scans of their tile totals; their prefixes; the lookup.  A pass that was not asked for
+ * takes no time. */
+int  cbc_gpu_last_coverage_ext_ms(cbc_gpu_ctx *ctx, float *cov_ms /* 7 */, float *ext_ms /* 5 */);
+
 /* ---- depth histogram --------------------------------------------------------------------------------
  * The depth form of cbc_gpu_decode_targets -- the selected blocks of ONE contig, decoded once, marked in the compressed
  * coordinate of all the contig's merged intervals (t, iv_first, iv_count as for cbc_gpu_decode_coverage) -- without the text:
