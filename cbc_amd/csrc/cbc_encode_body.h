@@ -10,9 +10,11 @@
  * Where the 64 lanes are used:
  *   - one lane per RECORD for the per-record models (rlength, pos, flag, match): inside a block
  *     they are counting models, so (cum, count) of 64 records come from ballots / v_mbcnt
- *     (fixed_group); one lane per SYMBOL for the scaled fractions the coder step divides by
+ *     (fixed_group); likewise for the token headers and the SNP-count symbol of a group's imperfect
+ *     records (prep_group); one lane per SYMBOL for the scaled fractions the coder step divides by
  *     (frac32) and for placing the output bits (pack)
- *   - read-vs-reference compare: 4 bases per lane, one ballot            (read_compression.c:291-296)
+ *   - read-vs-reference compare: one lane per record, 4 bases per step, one ballot per group
+ *                                                                        (read_compression.c:291-296)
  *   - cumulative-frequency lookup of the edit models: masked gather of the sparse/dense table +
  *     wave sum                                                           (stream_model.c:64-69)
  *   - var-context statistics: ballot + popcount over the block's var events
@@ -809,20 +811,6 @@ struct CbcEnc {
         }
         n = card + W::reduce_add(a);
     }
-    /* dense_code() for a caller that has checked x < 64 and n + step < CBC_RESCALE (the SNP count of an ordinary read): no
-     * table sweep, no rescale at this call site */
-    CBC_MFN void dense_code_low(uint32_t *exc, uint32_t step, uint32_t x, uint32_t &n)
-    {
-        const V32 ln = W::lane();
-        const V32 e = W::load32(exc, ln, ln <= x, 0u);
-        const uint32_t cnt = 1u + W::readlane(e, x);
-        uint32_t lo = x;
-        if (x < 4u) { for (uint32_t s = 0; s < x; s++) lo += W::readlane(e, s); }
-        else lo += W::reduce_add(W::select(ln < x, e, W::splat(0u)));
-        encode(lo, cnt, n);
-        W::write_uni(exc, x, cnt - 1u + step);
-        n += step;
-    }
     CBC_MFN void dense_code(uint32_t *exc, uint32_t card, uint32_t step, uint32_t x, uint32_t &n)
     {
         if (x >= card) { fail(CBC_ST_ASSERT); return; }       /* assert(x < alphabetCard) stream_model.c:62 */
@@ -1364,15 +1352,75 @@ struct CbcEnc {
     CBC_MFN uint32_t win_first(uint32_t p, uint32_t rl) { return win.first(p, rl); }
     CBC_MFN void win_set(uint32_t k) { win.set(k); }
 
+    /* ---- group pass of the wavefront that owns the edit models: what the imperfect records of a group (the lanes in `neq`)
+     * need before their serial part and what does not depend on any adaptive state but the SNP-count model's, one lane per
+     * record.  Like fixed_group() for the per-record models.
+     *   a. token header: tok[r_tok], tok[r_tok + 1] gathered under the bounds of the block's token area; the validity test of
+     *      edits() and the "ordinary" predicate (valid, no indels, fewer than 64 SNPs, L0 >= 64, no leading clip) become
+     *      lane masks, `ord` their ballot.  A lane that is not ordinary goes through edits<0>, which repeats the tests
+     *      on the scalar unit and reports what it always reported.
+     *   b. the SNP-count model in counting form.  Every imperfect record codes exactly one symbol of it (nSnp & 0xff for a
+     *      SNP-only record, 0 for one with indels: read_compression.c:557-564), step 10, and inside a block kernel the model
+     *      cannot rescale, so count(s) = table before the group + 10 * (lower lanes with s) and the total is the running
+     *      snps_n: one iteration per DISTINCT symbol, the table written once after all lookups.  Lanes left out (invalid
+     *      header, symbol >= L0) get cnt = 0; edits<0> stops the block at them, so they are never counted by a record that
+     *      is coded.  A group that could reach the rescale point (uniform guard) is not counted and has no ordinary lanes.
+     * (Preparing the first SNP of every ordinary record per lane as well measured slower: profiles/group_prep_ab.log.) */
+    struct Prep { V32 hdr0, lo, cnt; uint64_t ord; };
+    CBC_MFN void prep_group(Prep &P, uint64_t neq, const V32 &r_tok, const uint32_t *tokb, uint32_t n_tok_blk)
+    {
+        const V32 zero = W::splat(0u);
+        const Mask im = W::lane_bit(neq);
+        const V32 hdr0 = W::load32(tokb, r_tok, im & (r_tok < n_tok_blk), 0u);
+        const V32 hdr1 = W::load32(tokb, r_tok + 1u, im & ((r_tok + 1u) < n_tok_blk), 0u);
+        const V32 n_cig = hdr0 & 0xffffu, n_md = hdr0 >> 16;
+        const Mask valid = im & ((r_tok + 2u + n_cig + n_md) <= n_tok_blk) & (n_md < 1024u) &
+                           ((hdr1 & 0xffffu) < 1024u) & ((hdr1 >> 16) < 1024u);
+        const Mask snp_only = hdr1 == 0u;
+        /* b. */
+        const V32 symv = W::select(snp_only, n_md & 0xffu, zero);
+        const bool counted = snps_n + 10u * W::popc64(neq) + 10u < CBC_RESCALE;
+        V32 lo_base = zero, lo_extra = zero, cntv = zero, newv = zero;
+        if (counted) {
+            const Mask cm = valid & (symv < L0);               /* assert(x < alphabetCard) stream_model.c:62 */
+            uint64_t rem = W::ballot(cm);
+            while (rem) {
+                const uint32_t v = W::readlane(symv, W::ctz64(rem));
+                const Mask mv = cm & (symv == v);
+                const uint64_t m = W::ballot(mv);
+                rem &= ~m;
+                uint32_t lo0, cnt0;
+                dense_lookup(snps_exc, v, lo0, cnt0);
+                const V32 before = W::prefix_popc(m) * 10u;
+                cntv = W::select(mv, before + cnt0, cntv);
+                lo_base = W::select(mv, W::splat(lo0), lo_base);
+                lo_extra = lo_extra + W::select(cm & (symv > v), before, zero);
+                newv = W::select(mv, W::splat(cnt0 - 1u + 10u * W::popc64(m)), newv);
+            }
+            W::store32(snps_exc, symv, newv, cm);              /* after all lookups; lanes with the same symbol store the same word */
+        }
+        P.hdr0 = hdr0; P.lo = lo_base + lo_extra; P.cnt = cntv;
+        /* a. */
+        Mask ord = valid & snp_only & (n_md < 64u);
+        if (!(counted && L0 >= 64u)) ord = W::lane_bit(0ull);
+        {   /* a leading soft clip / '*': edits<0> refuses the record after its SNPs */
+            const V32 op0 = W::load32(tokb, r_tok + 2u, ord & (n_cig != 0u), 0u) & 15u;
+            ord = ord & ((n_cig == 0u) | ((op0 != (uint32_t)CBC_OP_STAR) & (op0 != (uint32_t)CBC_OP_S)));
+        }
+        P.ord = W::ballot(ord);
+    }
+
     /* compress_edits for an imperfect read (read_compression.c:308-600).
      * The packer has already counted the edits (token word 1) and checked that the MD string is
      * consistent with the read, so every MD token becomes exactly one SNP: numSnps = n_md. */
-    /* MODE 0: any record.  MODE 1: the caller has looked at the token header -- no indels, fewer than 64 SNPs, no rescale of
-     * the SNP-count model due; the model wavefront codes runs of such records in a loop that holds neither the CIGAR walks nor
-     * a table sweep.  (MODE 2: indels only.) */
+    /* MODE 0: any record.  MODE 1: a record prep_group() found ordinary -- header valid, no indels, fewer than 64 SNPs, no
+     * leading clip, its SNP-count symbol counted; the model wavefront codes runs of such records in a loop that holds neither
+     * the CIGAR walks nor a table access, and takes the header from `pr`.  (MODE 2: indels only.)
+     * `pr` of a MODE 0 record: the counted SNP-count symbol if pr.cnt != 0, nothing otherwise (the stream kernel). */
+    struct PrepRec { uint32_t hdr0, lo, cnt; };
     template <int MODE = 0>
     CBC_MFN void edits(uint32_t pos, uint32_t flw, uint32_t tok_off, const V32 &seqv, const V32 &tokv,
-                       const uint32_t *tokb, uint32_t n_tok_blk)
+                       const uint32_t *tokb, uint32_t n_tok_blk, const PrepRec pr = PrepRec{0u, 0u, 0u})
     {
             CbcEnc &E = *this;
             const uint32_t rl = flw >> 16, strand = (flw >> 4) & 1u;
@@ -1382,11 +1430,11 @@ struct CbcEnc {
                 E.win_shift(d > 256u ? 256u : d);
                 E.win_pos = pos;
             }
-            const uint32_t hdr = W::readlane(tokv, 0u), hdr1 = W::readlane(tokv, 1u);
+            const uint32_t hdr = MODE == 1 ? pr.hdr0 : W::readlane(tokv, 0u), hdr1 = MODE == 1 ? 0u : W::readlane(tokv, 1u);
             const uint32_t n_cig = hdr & 0xffffu, n_md = hdr >> 16;
             const uint32_t nSnp = n_md, nDel = hdr1 & 0xffffu, nIns = hdr1 >> 16;
-            if (tok_off + 2u + n_cig + n_md > n_tok_blk || nSnp >= 1024u || nDel >= 1024u || nIns >= 1024u) {
-                E.fail(CBC_ST_ASSERT); return;
+            if (MODE != 1 && (tok_off + 2u + n_cig + n_md > n_tok_blk || nSnp >= 1024u || nDel >= 1024u || nIns >= 1024u)) {
+                E.fail(CBC_ST_ASSERT); return;                /* MODE 1: prep_group() made this test, one lane per record */
             }
             CBC_TSM(11);                                      /* window slide, token header (waits for the prefetched loads) */
 #define CBC_TOK(i) ((i) < 64u ? W::readlane(tokv, (i)) : W::read_uni(tokb + tok_off, (i)))
@@ -1406,7 +1454,7 @@ struct CbcEnc {
             if (MODE != 2 && snp_only) {
                 /* SNP-only read (:557-558, :573-593): no insertion can interleave, so the MD tokens are
                  * the SNP list in order -- one loop, no CIGAR walk */
-                if (MODE == 1) E.dense_code_low(E.snps_exc, 10u, nSnp, E.snps_n);     /* the caller checked: nSnp < 64 <= L0, no rescale */
+                if (MODE == 1 || pr.cnt) { E.encode(pr.lo, pr.cnt, E.snps_n); E.snps_n += 10u; }   /* counted by prep_group() */
                 else E.dense_code(E.snps_exc, L0, 10u, nSnp & 0xffu, E.snps_n);
                 CBC_TSM(12);                                  /* edit counts */
                 uint32_t cum = 0, p = 0, k = 0;
@@ -1420,11 +1468,12 @@ struct CbcEnc {
                     }
                     if (k < n_md && E.status == CBC_ST_OK) E.drain();
                 }
-                /* a leading soft clip / '*' is rejected by the packer; refuse it here as well */
-                { const uint32_t t0 = CBC_TOK(2u); const uint32_t op0 = t0 & 15u;
+                /* a leading soft clip / '*' is rejected by the packer; refuse it here as well (MODE 1: prep_group() looked) */
+                if (MODE != 1) { const uint32_t t0 = CBC_TOK(2u); const uint32_t op0 = t0 & 15u;
                   if (n_cig && (op0 == CBC_OP_STAR || op0 == CBC_OP_S)) E.fail(CBC_ST_UNSUPPORTED); }
             } else if (MODE != 1) {
-                E.dense_code(E.snps_exc, L0, 10u, 0u, E.snps_n);                 /* :561-564 */
+                if (pr.cnt) { E.encode(pr.lo, pr.cnt, E.snps_n); E.snps_n += 10u; }   /* :561-564; counted by prep_group() */
+                else E.dense_code(E.snps_exc, L0, 10u, 0u, E.snps_n);
                 E.dense_code(E.indels_exc, L0, 16u, nSnp & 0xffu, E.indels_n);
                 E.dense_code(E.indels_exc, L0, 16u, nDel & 0xffu, E.indels_n);
                 E.dense_code(E.indels_exc, L0, 16u, nIns & 0xffu, E.indels_n);
@@ -1622,28 +1671,36 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         E.rname_code(E.prevChar, (uint32_t)'\n');
         E.rname_code((uint32_t)'\n', 0u);
     };
-    /* match test of a group's records (read_compression.c:291-296): lane l compares bases 4l..4l+3;
-     * the loads of 8 records are in flight together */
+    /* match test of a group's records (read_compression.c:291-296), one lane per RECORD: lane j walks the dwords of
+     * record j and ORs up read ^ reference, one ballot at the end gives the mask.  Whole dwords (4c + 4 <= rl) go
+     * through the chunk loop, eight dwords = sixteen loads in flight per round; the last, partial dword of a record
+     * whose length is no multiple of 4 is loaded once after the loop and masked to its rl & 3 bytes.  The bytes
+     * touched are 4 * ceil(rl / 4) of each buffer, inside what load_group() validated.  Lanes past the group's end
+     * hold zero records (rl = 0): no loads.  (The earlier form took one record per round, 4 bases per lane: 64 rounds
+     * of three readlanes, two address forms, two loads, tail mask, compare, ballot, OR -- ~25 instructions per record;
+     * this form: ~7 per dword for all 64 records.  A/B: profiles/group_prep_ab.log.) */
     auto match_group = [&](uint32_t cn, const V32 &r_pos, const V32 &r_fl, const V32 &r_seq) -> uint64_t {
-        uint64_t neq = 0;
-        for (uint32_t j0 = 0; j0 < cn; j0 += 8u) {
-            V32 sv[8], rv[8]; uint32_t rls[8];
-            const V32 bo = ln * 4u;
-            for (uint32_t q = 0; q < 8u; q++) {                 /* lanes past cn hold zero records: nothing is loaded */
-                const uint32_t jj = (j0 + q) & 63u;
-                const uint32_t pos = W::readlane(r_pos, jj), so = W::readlane(r_seq, jj);
-                rls[q] = (j0 + q < cn) ? W::readlane(r_fl, jj) >> 16 : 0u;
-                sv[q] = W::load32_bytes(seqb + so, bo, bo < rls[q]);
-                rv[q] = W::load32_bytes(refb + (pos - 1u), bo, bo < rls[q]);
-            }
+        const V32 vrl = W::select(ln < cn, r_fl >> 16, W::splat(0u));
+        const V32 ro = r_pos - 1u;
+        const uint32_t nd = W::uni(W::readlane(W::scan_incl_max(vrl), 63u) >> 2);      /* whole dwords of the longest record */
+        V32 acc = W::splat(0u);
+        for (uint32_t c = 0; c < nd; c += 8u) {
+            V32 sv[8], rv[8];
             for (uint32_t q = 0; q < 8u; q++) {
-                const uint32_t rl = rls[q];
-                V32 bmask = W::select(bo + 4u <= rl, W::splat(0xffffffffu),
-                                      W::select(bo < rl, (W::splat(1u) << ((W::splat(rl) - bo) * 8u)) - 1u, W::splat(0u)));
-                if (W::ballot(((sv[q] ^ rv[q]) & bmask) != 0u)) neq |= 1ull << ((j0 + q) & 63u);
+                const uint32_t b = (c + q) * 4u;
+                const Mask m = vrl >= b + 4u;
+                sv[q] = W::load32_bytes(seqb + b, r_seq, m);        /* the dword's offset on the uniform base: an immediate */
+                rv[q] = W::load32_bytes(refb + b, ro, m);
             }
+            for (uint32_t q = 0; q < 8u; q++) acc = acc | (sv[q] ^ rv[q]);
         }
-        return neq;
+        {
+            const V32 tail = vrl & 3u, lb = vrl - tail;                                /* the partial dword: bytes lb .. rl - 1 */
+            const Mask m = tail != 0u;
+            const V32 s = W::load32_bytes(seqb, r_seq + lb, m), r = W::load32_bytes(refb, ro + lb, m);
+            acc = acc | ((s ^ r) & ((W::splat(1u) << (tail * 8u)) - 1u));
+        }
+        return W::ballot(acc != 0u);
     };
     /* the 64 records of a group, validated one lane each so that the per-record loads need no clamping:
      * read length 1..252, POS >= 1, bases and reference window inside the buffers */
@@ -1683,40 +1740,37 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
             E.publish(CBC_BF_GROUP, neq);
 #endif
             if (c0 == 0u) { gen_rname(); E.seg_end(); }
+            typename CbcEnc<W>::Prep P;
+            E.prep_group(P, neq, r_tok, tokb, n_tok_blk);
+            CBC_TS(14);                                       /* group pass */
             /* software prefetch: bases and tokens of the next imperfect record */
             uint64_t todo = neq;
             V32 nx_seq = W::splat(0u), nx_tok = W::splat(0u);
-            if (todo) {
+            auto prefetch = [&]() {
                 const uint32_t jn = W::ctz64(todo);
                 const uint32_t so = W::readlane(r_seq, jn), to = W::readlane(r_tok, jn), nrl = W::readlane(r_fl, jn) >> 16;
                 V32 bo = ln * 4u;
                 nx_seq = W::load32_bytes(seqb + so, bo, bo < nrl);
                 nx_tok = W::load32(tokb + to, ln, (ln + to) < n_tok_blk, 0u);
-            }
+            };
+            if (todo) prefetch();
             /* the record at the head of `todo` (its bases and tokens are in nx_seq / nx_tok), and the next one's loads */
             auto one = [&](auto mode) {
                 const uint32_t j = W::ctz64(todo);
                 todo &= todo - 1ull;
                 E.cur_read = c0 + j;
                 const V32 seqv = nx_seq, tokv = nx_tok;
-                if (todo) {
-                    const uint32_t jn = W::ctz64(todo);
-                    const uint32_t so = W::readlane(r_seq, jn), to = W::readlane(r_tok, jn), nrl = W::readlane(r_fl, jn) >> 16;
-                    V32 bo = ln * 4u;
-                    nx_seq = W::load32_bytes(seqb + so, bo, bo < nrl);
-                    nx_tok = W::load32(tokb + to, ln, (ln + to) < n_tok_blk, 0u);
-                }
-                E.template edits<decltype(mode)::value>(W::readlane(r_pos, j), W::readlane(r_fl, j), W::readlane(r_tok, j), seqv, tokv, tokb, n_tok_blk);
+                if (todo) prefetch();
+                const typename CbcEnc<W>::PrepRec pr = { decltype(mode)::value == 1 ? W::readlane(P.hdr0, j) : 0u, W::readlane(P.lo, j), W::readlane(P.cnt, j) };
+                E.template edits<decltype(mode)::value>(W::readlane(r_pos, j), W::readlane(r_fl, j), W::readlane(r_tok, j), seqv, tokv, tokb, n_tok_blk, pr);
                 E.seg_end_fits();
                 CBC_TS(1);                                    /* edits of one record */
                 if (E.q_len >= CBC_BATCH_MIN) E.drain();      /* hand over once a few records' symbols are pending */
             };
-            /* runs of ordinary records -- SNPs only (token word 1 = deletions | insertions << 16 is zero), fewer than 64 of
-             * them, the SNP-count model not about to rescale -- go through a loop whose body holds no CIGAR walk and no table
-             * sweep; any other record is coded between two such runs by the general form */
-            auto ordinary = [&]() { return W::readlane(nx_tok, 1u) == 0u && (W::readlane(nx_tok, 0u) >> 16) < 64u && L0 >= 64u && E.snps_n + 10u < CBC_RESCALE; };
+            /* runs of ordinary records (P.ord) go through a loop whose body holds no CIGAR walk, no header test and no table
+             * access; any other record is coded between two such runs by the general form */
             while (todo && E.status == CBC_ST_OK) {
-                while (todo && E.status == CBC_ST_OK && ordinary()) one(std::integral_constant<int, 1>());
+                while (todo && E.status == CBC_ST_OK && ((P.ord >> W::ctz64(todo)) & 1ull)) one(std::integral_constant<int, 1>());
                 if (todo && E.status == CBC_ST_OK) one(std::integral_constant<int, 0>());
             }
         }
@@ -1755,9 +1809,11 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         const uint32_t cn = n_reads - c0 < 64u ? n_reads - c0 : 64u;
         E.cur_read = c0;
         uint64_t neq;
+        typename CbcEnc<W>::Prep P;                           /* fused role only */
         if (fused) {
             if (!load_group(c0, r_pos, r_fl, r_seq, r_tok, true)) break;
             neq = match_group(cn, r_pos, r_fl, r_seq);
+            E.prep_group(P, neq, r_tok, tokb, n_tok_blk);
         } else {
 #ifndef CBC_MATCH_IN_MODEL
             neq = neq_ahead;                                  /* posted one group ago */
@@ -1832,7 +1888,9 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
                     const V32 bo = ln * 4u;
                     const V32 seqv = W::load32_bytes(seqb + so, bo, bo < (flw >> 16));
                     const V32 tokv = W::load32(tokb + to, ln, (ln + to) < n_tok_blk, 0u);
-                    E.edits(W::readlane(r_pos, j), flw, to, seqv, tokv, tokb, n_tok_blk);
+                    const typename CbcEnc<W>::PrepRec pr = { W::readlane(P.hdr0, j), W::readlane(P.lo, j), W::readlane(P.cnt, j) };
+                    if ((P.ord >> j) & 1ull) E.template edits<1>(W::readlane(r_pos, j), flw, to, seqv, tokv, tokb, n_tok_blk, pr);
+                    else E.edits(W::readlane(r_pos, j), flw, to, seqv, tokv, tokb, n_tok_blk, pr);
                     E.seg_end();
                 } else E.seg_consume();
             }
