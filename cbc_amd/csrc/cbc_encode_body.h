@@ -75,6 +75,7 @@
 #endif
 #define CBC_LDS_CTL     (CBC_LDS_BATCH + CBC_BATCH_SLOTS * CBC_BATCH_WORDS)   /* 8: produced, consumed */
 #define CBC_LDS_RING    (CBC_LDS_CTL + 8u)
+#define CBC_LDS_RUN     (CBC_LDS_RING + CBC_RING_WORDS)   /* CBC_RUN_WORDS: scratch of run_pass() (model / fused wavefront) */
 #define CBC_LDS_FIXED   CBC_PLAN_LDS_FIXED_WORDS
 /* then pos_val[cap_pos], pos_occ[cap_pos], pos_pre[cap_pos]; the var-event list lives in global memory (see var_code) */
 
@@ -262,6 +263,7 @@ struct CbcEnc {
     V32 fkey, fexc; uint32_t fcount;        /* flag: sparse, one entry per lane                */
     V32 hkey, hexc; uint32_t hc0, hc1, hc2, hc3, hn0, hn1, hn2, hn3;   /* codebook ctx 0..3: sparse, 8 lanes each */
     uint32_t *rlen_exc, *snps_exc, *indels_exc, *rname_key, *rname_exc, *pos_val, *pos_occ, *pos_pre, *pos_idx, *var_ev, *bloom, *p0ev;
+    uint32_t *runs;                          /* CBC_RUN_WORDS of LDS: run_pass() scatters through it (block kernels only) */
     uint32_t snps_n, indels_n;
     uint32_t rn_count, rn_cap;               /* contig-name pairs in use / capacity (CBC_CAP_NAME in the block kernels) */
     uint32_t *vtab;                          /* GEN: var excess table in global memory, row = context, L0 words per row */
@@ -1357,13 +1359,13 @@ struct CbcEnc {
      * record.  Like fixed_group() for the per-record models.
      *   a. token header: tok[r_tok], tok[r_tok + 1] gathered under the bounds of the block's token area; the validity test of
      *      edits() and the "ordinary" predicate (valid, no indels, fewer than 64 SNPs, L0 >= 64, no leading clip) become
-     *      lane masks, `ord` their ballot.  A lane that is not ordinary goes through edits<0>, which repeats the tests
+     *      lane masks, `ord` their ballot.  A lane that is not ordinary goes through edits(), which repeats the tests
      *      on the scalar unit and reports what it always reported.
      *   b. the SNP-count model in counting form.  Every imperfect record codes exactly one symbol of it (nSnp & 0xff for a
      *      SNP-only record, 0 for one with indels: read_compression.c:557-564), step 10, and inside a block kernel the model
      *      cannot rescale, so count(s) = table before the group + 10 * (lower lanes with s) and the total is the running
      *      snps_n: one iteration per DISTINCT symbol, the table written once after all lookups.  Lanes left out (invalid
-     *      header, symbol >= L0) get cnt = 0; edits<0> stops the block at them, so they are never counted by a record that
+     *      header, symbol >= L0) get cnt = 0; edits() stops the block at them, so they are never counted by a record that
      *      is coded.  A group that could reach the rescale point (uniform guard) is not counted and has no ordinary lanes.
      * (Preparing the first SNP of every ordinary record per lane as well measured slower: profiles/group_prep_ab.log.) */
     struct Prep { V32 hdr0, lo, cnt; uint64_t ord; };
@@ -1403,24 +1405,180 @@ struct CbcEnc {
         /* a. */
         Mask ord = valid & snp_only & (n_md < 64u);
         if (!(counted && L0 >= 64u)) ord = W::lane_bit(0ull);
-        {   /* a leading soft clip / '*': edits<0> refuses the record after its SNPs */
+        {   /* a leading soft clip / '*': edits() refuses the record after its SNPs */
             const V32 op0 = W::load32(tokb, r_tok + 2u, ord & (n_cig != 0u), 0u) & 15u;
             ord = ord & ((n_cig == 0u) | ((op0 != (uint32_t)CBC_OP_STAR) & (op0 != (uint32_t)CBC_OP_S)));
         }
         P.ord = W::ballot(ord);
     }
 
+    /* ---- run pass of the wavefront that owns the edit models: SNP positions, var contexts, chars rows / symbols and window
+     * marks of a RUN of ordinary records, one lane per SNP in stream order (record, then MD token).  A run = the ordinary
+     * records (P.ord) at the head of `todo` up to the next imperfect record that is not ordinary, as many as hold at most 64
+     * SNPs together (an ordinary record has fewer than 64, so a run is never empty).
+     * Why this needs no serial state: snpInRef is only ever set (read_compression.c:589) and a SNP asks for the first mark in
+     * [POS + p, POS + rl) (:703-718), so "the marks a SNP sees" = the window as it stood before the run + the marks of the
+     * lanes below it; marks of its own record lie below its query, and what a slide would have dropped lies below the later
+     * record's POS, hence below every query of it (a jump of 256 or more, which clears the window, included).
+     *   - owner of a lane: prefix sum of the records' SNP counts, the heads scattered through LDS (a byte per lane: the
+     *     scratch is 16 words, which keeps a cfg2 workgroup's LDS inside the allocation granule that lets ten share a CU),
+     *     prefix maximum
+     *   - token, then p before / after the SNP: segmented prefix sum of gap + 1; the read byte sits at p_after - 1
+     *   - distance: the window's 8 words broadcast and masked per lane at the lane's own offset from win_pos, then an unsigned
+     *     subtract-and-min over the marks of the lower lanes
+     * The result is ONE register, lane k = ctx (16 bits) | gap (8) << 16 | chars row (3) << 24 | chars symbol (3) << 27, which
+     * run_record() walks; the window is slid once to the last record's POS with the run's marks OR-ed in through LDS (two
+     * SNPs may mark one position).  A lane the serial code would stop at or treat specially (gap >= L0, a mark outside the
+     * window's 256 positions, a context out of range) makes the pass return false with nothing changed: the caller sends
+     * the run's records through edits(), which reports what it always reported.
+     * The LDS accesses are unconditional in every lane on purpose (a masked-off lane ORs 0 into word 0, the lanes that
+     * share a word store the same value): store, OR and load must stay three instructions of the whole wavefront in
+     * this order.  Under a lane mask the compiler is free to give each side of the mask its own copy of the OR, and the
+     * lanes of one side then OR before the other side's store (seen on gfx950: marks lost).  Nothing in the language orders
+     * the three across lanes; the gfx950 code of both kernels was read and holds one ds_write_b32, one ds_or_b32 and one
+     * ds_read_b32 per round trip, in this order, and the GPU tests of tests/test_snp_pass_gpu.py fail if marks are lost. */
+    /* Chars rows 0..4 (step 8) in counting form: inside a run only the run's SNPs touch them, and unless a row could reach
+     * its rescale point within the run (uniform guard; then run_record() codes the run's chars by small_code() as ever)
+     *     count = table + 8 * (lower lanes with the same row and symbol), cum and total likewise,
+     * one iteration per DISTINCT (row, symbol) of the run, the lane table written once -- the form fixed_group() uses for
+     * the match model.  (cum, count, total), each below 2^20, travel in two registers: ca = cum | count[11:0] << 20,
+     * cb = total | count[19:12] << 20.  Row 5 (insertions) is only coded by edits(), between runs. */
+#ifndef CBC_CHARS_GUARD_AT
+#define CBC_CHARS_GUARD_AT CBC_RESCALE                    /* tests lower it to take the small_code() path for some runs */
+#endif
+    struct Run { V32 pk, ca, cb; uint64_t rm; uint32_t s, counted; };   /* rm: the run's records; s: the next lane run_record() takes */
+    CBC_MFN V32 basepair_v(const V32 &c)
+    {
+        return W::select(c == (uint32_t)'A', W::splat(0u), W::select(c == (uint32_t)'C', W::splat(1u),
+               W::select(c == (uint32_t)'G', W::splat(2u), W::select(c == (uint32_t)'T', W::splat(3u), W::splat(4u)))));
+    }
+    CBC_MFN bool run_pass(Run &R, const Prep &P, uint64_t todo, const V32 &r_pos, const V32 &r_fl, const V32 &r_seq, const V32 &r_tok,
+                          const uint32_t *tokb, const uint8_t *seqb)
+    {
+        const V32 ln = W::lane(), zero = W::splat(0u);
+        const uint64_t nonord = todo & ~P.ord;               /* the head of `todo` is ordinary: its lowest bit lies above it */
+        const uint64_t cand = nonord ? todo & ((1ull << W::ctz64(nonord)) - 1ull) : todo;
+        const Mask cm = W::lane_bit(cand);
+        const V32 incl = W::scan_incl_add(W::select(cm, P.hdr0 >> 16, zero));
+        const uint64_t rm = W::ballot(cm & (incl <= 64u));
+        const Mask inrun = W::lane_bit(rm);
+        const V32 cntv = W::select(inrun, P.hdr0 >> 16, zero), excl = incl - cntv;
+        const uint32_t last = (uint32_t)(rm >> 32) ? 63u - W::clz32((uint32_t)(rm >> 32)) : 31u - W::clz32((uint32_t)rm);
+        const uint32_t total = W::readlane(incl, last);
+        R.rm = rm; R.s = 0u;
+#ifdef CBC_WIN_SCALAR                                        /* A/B form of the window: no lane form to read, every run goes through edits() */
+        return false;
+#else
+        /* owner of every SNP lane */
+        const Mask head = inrun & (cntv != 0u);
+        W::store32(runs, ln & 15u, zero, W::all());            /* one byte per SNP lane: record + 1 at the lane its SNPs start at */
+        W::lds_or(runs, W::select(head, excl >> 2, zero), W::select(head, (ln + 1u) << ((excl & 3u) * 8u), zero), W::all());
+        const V32 own = W::scan_incl_max((W::load32(runs, ln >> 2, W::all(), 0u) >> ((ln & 3u) * 8u)) & 0xffu) - 1u;
+        const Mask live = ln < total;
+        const V32 o_excl = W::lane_gather(excl, own), o_hdr = W::lane_gather(P.hdr0, own), o_tok = W::lane_gather(r_tok, own);
+        const V32 o_fl = W::lane_gather(r_fl, own), o_seq = W::lane_gather(r_seq, own), o_pos = W::lane_gather(r_pos, own);
+        /* token, positions, read byte (prep_group() checked the token range, the group's validation the bases) */
+        const V32 t = W::load32(tokb, o_tok + 2u + (o_hdr & 0xffffu) + (ln - o_excl), live, 0u);
+        const V32 gap = t >> 8, g1 = W::select(live, gap + 1u, zero);
+        const V32 sc = W::scan_incl_add(g1);
+        const V32 p_after = sc - W::lane_gather(sc - g1, o_excl), p_before = p_after - g1;
+        const V32 rl = o_fl >> 16, cum = p_after - 1u;
+        const V32 byte = W::load8(seqb, o_seq + cum, live & (cum < rl));
+        /* nearest mark at or after the query start, as a distance.  Coordinates: relative to win_pos */
+        const V32 off = o_pos - win_pos, qlo = off + p_before, mark = off + cum;
+        V32 best = W::splat(0xffffffffu);
+        if (W::ballot(win.w != 0u)) {
+            const V32 qw = qlo >> 5, qm = W::splat(0xffffffffu) << (qlo & 31u);
+            for (uint32_t i = 8u; i-- > 0u; ) {                /* downwards: the lowest word with a mark wins */
+                const uint32_t wv = W::readlane(win.w, i);
+                if (wv == 0u) continue;
+                const V32 bits = W::select(qw == i, qm & wv, W::select(qw < i, W::splat(wv), zero));
+                best = W::select(bits != 0u, (W::ctz_v(bits) + 32u * i) - qlo, best);
+            }
+        }
+        for (uint32_t j = 0; j + 1u < total; j++) {
+            const V32 dj = W::splat(W::readlane(mark, j)) - qlo;       /* a mark below the query: a huge value */
+            best = W::select((ln > j) & (dj < best), dj, best);
+        }
+        const Mask found = (p_before < rl) & (best < rl - p_before);
+        const V32 d = W::select(found, best, rl + 2u);                 /* CbcWin::first */
+        const V32 ctx = (((d << 7) + p_before) << 1) | ((o_fl >> 4) & 1u);
+        if (W::ballot(live & ((gap >= L0) | (cum >= 256u) | (ctx >= CBC_NVARCTX)))) return false;
+        const V32 row = basepair_v(t & 0xffu), sym = basepair_v(byte);
+        R.pk = ctx | (gap << 16) | (row << 24) | (sym << 27);
+        {   /* chars in counting form */
+            const V32 tl = row * 8u + CBC_LT_CHARS;
+            const V32 t0 = W::lane_gather(small, tl), t1 = W::lane_gather(small, tl + 1u), t2 = W::lane_gather(small, tl + 2u),
+                      t3 = W::lane_gather(small, tl + 3u), t4 = W::lane_gather(small, tl + 4u);
+            V32 c_n = t0 + t1 + t2 + t3 + t4;
+            R.counted = W::ballot(live & (c_n + 8u * total >= CBC_CHARS_GUARD_AT)) ? 0u : 1u;
+            if (R.counted) {
+                V32 c_lo = W::select(sym > 0u, t0, zero) + W::select(sym > 1u, t1, zero) + W::select(sym > 2u, t2, zero) + W::select(sym > 3u, t3, zero);
+                V32 c_cnt = W::select(sym == 0u, t0, W::select(sym == 1u, t1, W::select(sym == 2u, t2, W::select(sym == 3u, t3, t4))));
+                const V32 key = row * 8u + sym;
+                uint64_t rem = W::ballot(live);
+                while (rem) {
+                    const uint32_t v = W::readlane(key, W::ctz64(rem));
+                    const Mask mv = live & (key == v);
+                    const uint64_t m = W::ballot(mv);
+                    rem &= ~m;
+                    const V32 before = W::prefix_popc(m) * 8u;
+                    const Mask same_row = live & ((key >> 3) == (v >> 3));
+                    c_cnt = c_cnt + W::select(mv, before, zero);
+                    c_lo = c_lo + W::select(same_row & (key > v), before, zero);
+                    c_n = c_n + W::select(same_row, before, zero);
+                    small = W::select(ln == CBC_LT_CHARS + v, small + 8u * W::popc64(m), small);
+                }
+                R.ca = c_lo | ((c_cnt & 0xfffu) << 20);
+                R.cb = c_n | ((c_cnt >> 12) << 20);
+            }
+        }
+        /* the window after the run: at the last record's POS, the run's marks in it */
+        const uint32_t npos = W::readlane(r_pos, last), slide = npos - win_pos;
+        win.shift(slide > 256u ? 256u : slide);
+        win_pos = npos;
+        const V32 mk = mark - slide;                                   /* below the new base: a huge value */
+        const Mask keep = live & (mk < 256u);
+        W::store32(runs, ln & 7u, W::lane_gather(win.w, ln & 7u), W::all());      /* eight lanes per word, the same value */
+        W::lds_or(runs, W::select(keep, mk >> 5, zero), W::select(keep, W::splat(1u) << (mk & 31u), zero), W::all());
+        win.w = W::select(ln < 8u, W::load32(runs, ln & 7u, W::all(), 0u), zero);
+        return true;
+#endif
+    }
+    /* one record of the run: its SNP-count symbol (counted by prep_group()), then var and chars of its n SNPs from the lanes */
+    CBC_MFN void run_record(Run &R, uint32_t n, uint32_t lo, uint32_t cnt)
+    {
+        encode(lo, cnt, snps_n); snps_n += 10u;
+        CBC_TSM(12);                                          /* edit counts */
+        uint32_t k = R.s;
+        const uint32_t end = k + n;
+        R.s = end;
+        while (k < end && status == CBC_ST_OK) {              /* a full symbol queue (a read with dozens of SNPs) is handed over first */
+            for (; k < end && status == CBC_ST_OK && q_len < 56u; k++) {
+                const uint32_t x = W::readlane(R.pk, k);
+                var_code(x & 0xffffu, (x >> 16) & 0xffu);
+                CBC_TSM(7);
+                if (R.counted) {
+                    const uint32_t a = W::readlane(R.ca, k), b = W::readlane(R.cb, k);
+                    encode(a & 0xfffffu, (a >> 20) | ((b >> 20) << 12), b & 0xfffffu);
+                } else small_code(CBC_LT_CHARS + ((x >> 24) & 7u) * 8u, 5u, 8u, x >> 27);
+                CBC_TSM(8);
+            }
+            if (k < end && status == CBC_ST_OK) drain();
+        }
+        CBC_TSM(13);
+    }
+
+
     /* compress_edits for an imperfect read (read_compression.c:308-600).
      * The packer has already counted the edits (token word 1) and checked that the MD string is
      * consistent with the read, so every MD token becomes exactly one SNP: numSnps = n_md. */
-    /* MODE 0: any record.  MODE 1: a record prep_group() found ordinary -- header valid, no indels, fewer than 64 SNPs, no
-     * leading clip, its SNP-count symbol counted; the model wavefront codes runs of such records in a loop that holds neither
-     * the CIGAR walks nor a table access, and takes the header from `pr`.  (MODE 2: indels only.)
-     * `pr` of a MODE 0 record: the counted SNP-count symbol if pr.cnt != 0, nothing otherwise (the stream kernel). */
-    struct PrepRec { uint32_t hdr0, lo, cnt; };
-    template <int MODE = 0>
+    /* Any record.  In the block kernels the records prep_group() found ordinary do not come here: run_pass() / run_record()
+     * code them; this form takes every other record, and the ordinary ones of a run that run_pass() refused.
+     * `pr`: the counted SNP-count symbol if pr.cnt != 0, nothing otherwise (the stream kernel). */
+    struct PrepRec { uint32_t lo, cnt; };
     CBC_MFN void edits(uint32_t pos, uint32_t flw, uint32_t tok_off, const V32 &seqv, const V32 &tokv,
-                       const uint32_t *tokb, uint32_t n_tok_blk, const PrepRec pr = PrepRec{0u, 0u, 0u})
+                       const uint32_t *tokb, uint32_t n_tok_blk, const PrepRec pr = PrepRec{0u, 0u})
     {
             CbcEnc &E = *this;
             const uint32_t rl = flw >> 16, strand = (flw >> 4) & 1u;
@@ -1430,11 +1588,11 @@ struct CbcEnc {
                 E.win_shift(d > 256u ? 256u : d);
                 E.win_pos = pos;
             }
-            const uint32_t hdr = MODE == 1 ? pr.hdr0 : W::readlane(tokv, 0u), hdr1 = MODE == 1 ? 0u : W::readlane(tokv, 1u);
+            const uint32_t hdr = W::readlane(tokv, 0u), hdr1 = W::readlane(tokv, 1u);
             const uint32_t n_cig = hdr & 0xffffu, n_md = hdr >> 16;
             const uint32_t nSnp = n_md, nDel = hdr1 & 0xffffu, nIns = hdr1 >> 16;
-            if (MODE != 1 && (tok_off + 2u + n_cig + n_md > n_tok_blk || nSnp >= 1024u || nDel >= 1024u || nIns >= 1024u)) {
-                E.fail(CBC_ST_ASSERT); return;                /* MODE 1: prep_group() made this test, one lane per record */
+            if (tok_off + 2u + n_cig + n_md > n_tok_blk || nSnp >= 1024u || nDel >= 1024u || nIns >= 1024u) {
+                E.fail(CBC_ST_ASSERT); return;
             }
             CBC_TSM(11);                                      /* window slide, token header (waits for the prefetched loads) */
 #define CBC_TOK(i) ((i) < 64u ? W::readlane(tokv, (i)) : W::read_uni(tokb + tok_off, (i)))
@@ -1450,11 +1608,11 @@ struct CbcEnc {
                 E.small_code(CBC_LT_CHARS + cbc_basepair(letter_) * 8u, 5u, 8u, cbc_basepair(CBC_READ_BYTE(cum_))); \
                 CBC_TS(8);                                                                                  \
             } while (0)
-            const bool snp_only = MODE == 1 ? true : MODE == 2 ? false : (nDel | nIns) == 0u;
-            if (MODE != 2 && snp_only) {
+            const bool snp_only = (nDel | nIns) == 0u;
+            if (snp_only) {
                 /* SNP-only read (:557-558, :573-593): no insertion can interleave, so the MD tokens are
                  * the SNP list in order -- one loop, no CIGAR walk */
-                if (MODE == 1 || pr.cnt) { E.encode(pr.lo, pr.cnt, E.snps_n); E.snps_n += 10u; }   /* counted by prep_group() */
+                if (pr.cnt) { E.encode(pr.lo, pr.cnt, E.snps_n); E.snps_n += 10u; }   /* counted by prep_group() */
                 else E.dense_code(E.snps_exc, L0, 10u, nSnp & 0xffu, E.snps_n);
                 CBC_TSM(12);                                  /* edit counts */
                 uint32_t cum = 0, p = 0, k = 0;
@@ -1468,10 +1626,10 @@ struct CbcEnc {
                     }
                     if (k < n_md && E.status == CBC_ST_OK) E.drain();
                 }
-                /* a leading soft clip / '*' is rejected by the packer; refuse it here as well (MODE 1: prep_group() looked) */
-                if (MODE != 1) { const uint32_t t0 = CBC_TOK(2u); const uint32_t op0 = t0 & 15u;
+                /* a leading soft clip / '*' is rejected by the packer; refuse it here as well */
+                { const uint32_t t0 = CBC_TOK(2u); const uint32_t op0 = t0 & 15u;
                   if (n_cig && (op0 == CBC_OP_STAR || op0 == CBC_OP_S)) E.fail(CBC_ST_UNSUPPORTED); }
-            } else if (MODE != 1) {
+            } else {
                 if (pr.cnt) { E.encode(pr.lo, pr.cnt, E.snps_n); E.snps_n += 10u; }   /* :561-564; counted by prep_group() */
                 else E.dense_code(E.snps_exc, L0, 10u, 0u, E.snps_n);
                 E.dense_code(E.indels_exc, L0, 16u, nSnp & 0xffu, E.indels_n);
@@ -1590,7 +1748,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
     E.L0 = L0;
     E.rlen_exc = lds + CBC_LDS_RLEN; E.snps_exc = lds + CBC_LDS_SNPS; E.indels_exc = lds + CBC_LDS_INDELS;
     E.rname_key = lds + CBC_LDS_RNKEY; E.rname_exc = lds + CBC_LDS_RNEXC;
-    E.bloom = lds + CBC_LDS_BLOOM; E.p0ev = lds + CBC_LDS_P0;
+    E.bloom = lds + CBC_LDS_BLOOM; E.p0ev = lds + CBC_LDS_P0; E.runs = lds + CBC_LDS_RUN;
     E.pos_val = lds + CBC_LDS_FIXED; E.pos_occ = E.pos_val + A.cap_pos; E.pos_pre = E.pos_occ + A.cap_pos;
     E.fsp_key = E.fsp_exc = nullptr; E.fsp_count = 0; E.pos_ov_val = E.pos_ov_occ = nullptr; E.pos_lds_cap = 0xffffffc0u; E.palpha = nullptr;
     E.pos_idx = E.pos_pre + A.cap_pos;
@@ -1743,35 +1901,51 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
             typename CbcEnc<W>::Prep P;
             E.prep_group(P, neq, r_tok, tokb, n_tok_blk);
             CBC_TS(14);                                       /* group pass */
-            /* software prefetch: bases and tokens of the next imperfect record */
+            /* Runs of ordinary records (P.ord) go through run_pass() and a loop whose body holds no CIGAR walk, no header
+             * test, no window and no table access but the models'; any other record is coded between two runs by the general
+             * form, its bases and tokens prefetched while the records before it are coded. */
             uint64_t todo = neq;
             V32 nx_seq = W::splat(0u), nx_tok = W::splat(0u);
-            auto prefetch = [&]() {
-                const uint32_t jn = W::ctz64(todo);
+            uint32_t nx_j = 64u;                              /* the record nx_seq / nx_tok belong to */
+            auto prefetch = [&](uint32_t jn) {
                 const uint32_t so = W::readlane(r_seq, jn), to = W::readlane(r_tok, jn), nrl = W::readlane(r_fl, jn) >> 16;
                 V32 bo = ln * 4u;
                 nx_seq = W::load32_bytes(seqb + so, bo, bo < nrl);
                 nx_tok = W::load32(tokb + to, ln, (ln + to) < n_tok_blk, 0u);
+                nx_j = jn;
             };
-            if (todo) prefetch();
-            /* the record at the head of `todo` (its bases and tokens are in nx_seq / nx_tok), and the next one's loads */
-            auto one = [&](auto mode) {
+            auto prefetch_if_general = [&](uint64_t rest) {
+                if (rest) { const uint32_t jn = W::ctz64(rest); if (!((P.ord >> jn) & 1ull)) prefetch(jn); }
+            };
+            typename CbcEnc<W>::Run R;
+            R.pk = W::splat(0u); R.ca = R.pk; R.cb = R.pk; R.rm = 0ull; R.s = 0u; R.counted = 0u;
+            while (todo && E.status == CBC_ST_OK) {
                 const uint32_t j = W::ctz64(todo);
+                if ((P.ord >> j) & 1ull) {
+                    if (!E.run_pass(R, P, todo, r_pos, r_fl, r_seq, r_tok, tokb, seqb)) { P.ord &= ~R.rm; continue; }
+                    todo &= ~R.rm;
+                    prefetch_if_general(todo);
+                    CBC_TS(2);                                /* run pass */
+                    for (uint64_t rr = R.rm; rr && E.status == CBC_ST_OK; rr &= rr - 1ull) {
+                        const uint32_t jr = W::ctz64(rr);
+                        E.cur_read = c0 + jr;
+                        E.run_record(R, W::readlane(P.hdr0, jr) >> 16, W::readlane(P.lo, jr), W::readlane(P.cnt, jr));
+                        E.seg_end_fits();
+                        CBC_TS(1);                            /* edits of one record */
+                        if (E.q_len >= CBC_BATCH_MIN) E.drain();      /* hand over once a few records' symbols are pending */
+                    }
+                    continue;
+                }
+                if (nx_j != j) prefetch(j);
                 todo &= todo - 1ull;
                 E.cur_read = c0 + j;
                 const V32 seqv = nx_seq, tokv = nx_tok;
-                if (todo) prefetch();
-                const typename CbcEnc<W>::PrepRec pr = { decltype(mode)::value == 1 ? W::readlane(P.hdr0, j) : 0u, W::readlane(P.lo, j), W::readlane(P.cnt, j) };
-                E.template edits<decltype(mode)::value>(W::readlane(r_pos, j), W::readlane(r_fl, j), W::readlane(r_tok, j), seqv, tokv, tokb, n_tok_blk, pr);
+                prefetch_if_general(todo);
+                const typename CbcEnc<W>::PrepRec pr = { W::readlane(P.lo, j), W::readlane(P.cnt, j) };
+                E.edits(W::readlane(r_pos, j), W::readlane(r_fl, j), W::readlane(r_tok, j), seqv, tokv, tokb, n_tok_blk, pr);
                 E.seg_end_fits();
-                CBC_TS(1);                                    /* edits of one record */
-                if (E.q_len >= CBC_BATCH_MIN) E.drain();      /* hand over once a few records' symbols are pending */
-            };
-            /* runs of ordinary records (P.ord) go through a loop whose body holds no CIGAR walk, no header test and no table
-             * access; any other record is coded between two such runs by the general form */
-            while (todo && E.status == CBC_ST_OK) {
-                while (todo && E.status == CBC_ST_OK && ((P.ord >> W::ctz64(todo)) & 1ull)) one(std::integral_constant<int, 1>());
-                if (todo && E.status == CBC_ST_OK) one(std::integral_constant<int, 0>());
+                CBC_TS(1);
+                if (E.q_len >= CBC_BATCH_MIN) E.drain();
             }
         }
         if (E.status == CBC_ST_OK) { gen_sentinel(); E.seg_end(); }
@@ -1810,6 +1984,8 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         E.cur_read = c0;
         uint64_t neq;
         typename CbcEnc<W>::Prep P;                           /* fused role only */
+        typename CbcEnc<W>::Run R;
+        R.pk = W::splat(0u); R.ca = R.pk; R.cb = R.pk; R.rm = 0ull; R.s = 0u; R.counted = 0u;
         if (fused) {
             if (!load_group(c0, r_pos, r_fl, r_seq, r_tok, true)) break;
             neq = match_group(cn, r_pos, r_fl, r_seq);
@@ -1884,13 +2060,19 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
             E.step_fixed(CBC_LZ(W::readlane(F.m_lo, j)), CBC_LZ(W::readlane(m_hi, j)), CBC_LZ(W::readlane(F.m_n, j)), W::readlane(m_fl, j), W::readlane(m_fh, j));
             if ((neq >> j) & 1ull) {
                 if (fused) {
-                    const uint32_t so = W::readlane(r_seq, j), to = W::readlane(r_tok, j), flw = W::readlane(r_fl, j);
-                    const V32 bo = ln * 4u;
-                    const V32 seqv = W::load32_bytes(seqb + so, bo, bo < (flw >> 16));
-                    const V32 tokv = W::load32(tokb + to, ln, (ln + to) < n_tok_blk, 0u);
-                    const typename CbcEnc<W>::PrepRec pr = { W::readlane(P.hdr0, j), W::readlane(P.lo, j), W::readlane(P.cnt, j) };
-                    if ((P.ord >> j) & 1ull) E.template edits<1>(W::readlane(r_pos, j), flw, to, seqv, tokv, tokb, n_tok_blk, pr);
-                    else E.edits(W::readlane(r_pos, j), flw, to, seqv, tokv, tokb, n_tok_blk, pr);
+                    /* an ordinary record outside the run at hand opens the next run (a refused run: its records are no
+                     * longer ordinary) */
+                    if (((P.ord >> j) & 1ull) && !((R.rm >> j) & 1ull) &&
+                        !E.run_pass(R, P, neq & (~0ull << j), r_pos, r_fl, r_seq, r_tok, tokb, seqb)) P.ord &= ~R.rm;
+                    if ((P.ord >> j) & 1ull) E.run_record(R, W::readlane(P.hdr0, j) >> 16, W::readlane(P.lo, j), W::readlane(P.cnt, j));
+                    else {
+                        const uint32_t so = W::readlane(r_seq, j), to = W::readlane(r_tok, j), flw = W::readlane(r_fl, j);
+                        const V32 bo = ln * 4u;
+                        const V32 seqv = W::load32_bytes(seqb + so, bo, bo < (flw >> 16));
+                        const V32 tokv = W::load32(tokb + to, ln, (ln + to) < n_tok_blk, 0u);
+                        const typename CbcEnc<W>::PrepRec pr = { W::readlane(P.lo, j), W::readlane(P.cnt, j) };
+                        E.edits(W::readlane(r_pos, j), flw, to, seqv, tokv, tokb, n_tok_blk, pr);
+                    }
                     E.seg_end();
                 } else E.seg_consume();
             }

@@ -27,8 +27,9 @@
 #define CBC_POS_IDX_WORDS 256u                      /* 0: no index table (A/B) */
 #endif
 #define CBC_RING_WORDS  256u                       /* output bit ring of the coder wave (power of two) */
-/* encoder: tables, hand-off ring, its two counters (8 words), output ring; then 3 x cap_pos */
-#define CBC_PLAN_LDS_FIXED_WORDS (CBC_PLAN_TABLE_WORDS + CBC_BATCH_SLOTS * CBC_BATCH_WORDS + 8u + CBC_RING_WORDS)
+#define CBC_RUN_WORDS   16u                        /* scratch of the encoder's SNP run pass: one byte per SNP lane, then the window's 8 words */
+/* encoder: tables, hand-off ring, its two counters (8 words), output ring, run-pass scratch; then 3 x cap_pos */
+#define CBC_PLAN_LDS_FIXED_WORDS (CBC_PLAN_TABLE_WORDS + CBC_BATCH_SLOTS * CBC_BATCH_WORDS + 8u + CBC_RING_WORDS + CBC_RUN_WORDS)
 
 /* LDS per wavefront: fixed tables + the POS alphabet.  The var-event list is NOT in LDS: it lives in
  * global memory behind the block's payload area (encode) / in the decode scratch, so caps->cap_var
