@@ -756,3 +756,77 @@ int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, in
     cbc_unpack_plan_free(u);
     return 0;
 }
+
+/* `cbc -d|-x ... --stats [--region A ...] [--regions-file FILE] [--stats-exclude-flags N]`: the tables of a first look at the reads
+ *  instead of the reads.  Without regions every block is decoded by the plain decoder; with them the
+ * selected blocks of the target set by the span decoder, each selected read counted once.  One cbc_gpu_decode_stats; the tables
+ * (about 270 KB) cross PCIe and cbc_stats_text makes the text. */
+int cbc_cli_decompress_stats(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                             const char *bed_path, uint32_t exclude, int verbose)
+{
+    const double t0 = now2();
+    size_t blob_len = 0, fa_len = 0, bed_len = 0;
+    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
+    if (!blob || !fa) return 1;
+    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
+        fprintf(stderr, "cbc: --stats needs a block container; %s is a single-stream (--compat) file, which has no block index\n", in);
+        return 1;
+    }
+    char *bed = NULL;
+    if (bed_path && !(bed = slurp2(bed_path, &bed_len))) return 1;
+    char err[512];
+    cbc_unpack_plan *u = NULL;
+    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
+    free(fa);
+    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
+    /* what SAM output refuses, the statistics refuse: a long-read container, names and lengths the coordinates cannot carry */
+    if (cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) < 0) { fprintf(stderr, "cbc: --stats: %s\n", err[0] ? err : "the contig table is not usable"); return 1; }
+    cbc_targets *T = NULL;
+    const int tg = n_regions || bed_path;
+    if (tg) {
+        rc = cbc_unpack_targets(u, regions, n_regions, bed, bed_len, &T, err, sizeof err);
+        if (rc) { fprintf(stderr, "cbc: --stats: %s\n", rc == CBC_E_INPUT && err[0] ? err : "target selection failed"); return 1; }
+    }
+    free(bed);
+    const uint32_t nb = tg ? T->n_blocks : u->n_blocks;
+    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)(nb ? nb : 1) * sizeof *bl);
+    uint64_t *ws = (uint64_t *)malloc((size_t)(nb ? nb : 1) * 8);
+    cbc_gpu_stats *st = (cbc_gpu_stats *)calloc(1, sizeof *st);
+    const uint64_t cap = cbc_stats_text_cap();
+    char *text = (char *)malloc((size_t)cap);
+    if (!bl || !ws || !st || !text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    for (uint32_t k = 0; k < nb; k++) { const uint32_t b = tg ? T->blocks[k] : k; bl[k] = u->blocks[b]; ws[k] = u->window_start[b]; }
+    const double t1 = now2();
+    double t_init = 0, t_dev = 0;
+    float ms[2] = { 0, 0 };
+    cbc_gpu_ctx *ctx = NULL;
+    if (nb) {                                                /* else nothing runs: all-zero tables */
+        const double a = now2();
+        rc = cbc_gpu_init(device, &ctx);
+        if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
+        if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+        t_init = now2() - a;
+        const double b = now2();
+        const cbc_gpu_targets gt = { tg ? (const uint32_t *)T->iv : NULL, tg ? T->block_iv : NULL, tg ? T->n_iv : 0u, tg ? T->smax : 0u };
+        rc = cbc_gpu_decode_stats(ctx, u->payloads, u->payload_bytes, bl, nb, &u->caps, ws, tg ? &gt : NULL, exclude, st, NULL);
+        if (rc) { fprintf(stderr, "cbc: statistics failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
+        t_dev = now2() - b;
+        if (verbose) (void)cbc_gpu_last_stats_ms(ctx, &ms[0], &ms[1]);
+        cbc_gpu_shutdown(ctx);
+    }
+    const int64_t n = cbc_stats_text(st, text, cap);
+    FILE *fo = n < 0 ? NULL : fopen(out, "wb");
+    if (!fo || fwrite(text, 1, (size_t)n, fo) != (size_t)n || fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    printf("statistics of %llu reads (%llu excluded) from %u of %u blocks\n", (unsigned long long)st->reads, (unsigned long long)st->excluded, nb, u->n_blocks);
+    if (verbose) {
+        if (tg) printf("stats: %u intervals after merging, %u blocks selected, %llu BED lines selected nothing, exclude flags 0x%x\n",
+                       T->n_iv, nb, (unsigned long long)T->bed_unselected, exclude);
+        else printf("stats: the whole file, exclude flags 0x%x\n", exclude);
+        printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + statistics %.3f s\n", t1 - t0, t_init, t_dev);
+        if (ctx) printf("kernels: decode %.3f ms, statistics %.3f ms\n", ms[0], ms[1]);
+    }
+    free(text); free(st); free(bl); free(ws); free(blob);
+    if (T) cbc_targets_free(T);
+    cbc_unpack_plan_free(u);
+    return 0;
+}

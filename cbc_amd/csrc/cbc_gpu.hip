@@ -26,6 +26,7 @@
 #include "cbc_cov_body.h"
 #include "cbc_covx_body.h"
 #include "cbc_hist_body.h"
+#include "cbc_stats_body.h"
 #include "cbc_plan.h"
 #include "cbc_stream_body.h"
 #include "cbc_long_body.h"
@@ -186,6 +187,25 @@ cbc_hist_count_kernel(cbc_hist_args A) { cbc_hist_count<WaveGPU>(A, blockIdx.x);
 __global__ void __launch_bounds__(64)
 cbc_hist_write_kernel(cbc_hist_args A) { cbc_hist_write<WaveGPU>(A, blockIdx.x); }
 
+/* Read statistics (cbc_gpu_decode_stats, cbc_stats_body.h), behind the plain decode or the span decode of a target set: a bounded
+ * grid of workgroups of CBC_STATS_WAVES wavefronts strides over the record groups; the wavefronts of a workgroup share its count
+ * tables in LDS (zero, barrier, accumulate, barrier, flush) */
+template <bool TG>
+static __device__ __forceinline__ void cbc_stats_workgroup(const cbc_stats_args &A)
+{
+    __shared__ uint32_t tab[CBC_STATS_LDS];
+    const uint32_t wave = WaveGPU::uni(threadIdx.x >> 6);      /* wave-uniform: the unit's block and rows stay in scalar registers */
+    cbc_stats_zero<WaveGPU>(tab, wave, CBC_STATS_WAVES);
+    __syncthreads();
+    cbc_stats_accum<WaveGPU, TG>(A, blockIdx.x, wave, CBC_STATS_WAVES, tab);
+    __syncthreads();
+    cbc_stats_flush<WaveGPU>(A, tab, wave, CBC_STATS_WAVES);
+}
+__global__ void __launch_bounds__(64 * CBC_STATS_WAVES)
+cbc_stats_kernel(cbc_stats_args A) { cbc_stats_workgroup<false>(A); }
+__global__ void __launch_bounds__(64 * CBC_STATS_WAVES)
+cbc_targets_stats_kernel(cbc_stats_args A) { cbc_stats_workgroup<true>(A); }
+
 /* Whole-file stream / general-form fallback (cbc_stream_body.h): one wavefront per stream.  Workgroup w codes streams
  * w, w + gridDim, ... with var table w of the pool, which it re-zeroes between streams. */
 __global__ void __launch_bounds__(64)
@@ -341,12 +361,14 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
 /* grow-only device buffer owned by the context: the host-buffer entry points keep their device arrays between calls
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
-enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_XSTARTS, A_XTILE, A_XSP, A_XTHR, A_XPRE, A_XOUT, A_COUNT };
+enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_XSTARTS, A_XTILE, A_XSP, A_XTHR, A_XPRE, A_XOUT, A_STATS, A_COUNT };
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
 /* what decode_blocks_impl runs behind the decode (its post-decode stage): nothing (plain, 2-bit, span, long reads), or the
- * stage of cbc_gpu_decode_region, _sam, _depth, _targets (reads, SAM, depth), _coverage, _depth_hist, _coverage_ext */
-enum post_kind { POST_NONE, POST_REGION, POST_SAM, POST_DEPTH, POST_TG_READS, POST_TG_SAM, POST_TG_DEPTH, POST_COV, POST_HIST, POST_COVX };
+ * stage of cbc_gpu_decode_region, _sam, _depth, _targets (reads, SAM, depth), _coverage, _depth_hist, _coverage_ext, _stats (whole
+ * file, target set) */
+enum post_kind { POST_NONE, POST_REGION, POST_SAM, POST_DEPTH, POST_TG_READS, POST_TG_SAM, POST_TG_DEPTH, POST_COV, POST_HIST, POST_COVX,
+                 POST_STATS, POST_TG_STATS };
 
 struct cbc_gpu_ctx {
     int device;
@@ -1037,7 +1059,8 @@ API int cbc_gpu_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device_batc
 static bool post_is_cov(post_kind k) { return k == POST_COV || k == POST_COVX; }
 static bool post_is_depth(post_kind k) { return k == POST_DEPTH || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST; }
 static bool post_is_sam(post_kind k) { return k == POST_SAM || k == POST_TG_SAM; }
-static bool post_is_targets(post_kind k) { return k == POST_TG_READS || k == POST_TG_SAM || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST; }
+static bool post_is_targets(post_kind k) { return k == POST_TG_READS || k == POST_TG_SAM || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || k == POST_TG_STATS; }
+static bool post_is_stats(post_kind k) { return k == POST_STATS || k == POST_TG_STATS; }
 
 /* the queries (n_q pairs slot, len in the compressed coordinate), the depth that counts as covered, where the results go */
 struct cov_req { const uint32_t *q; uint32_t n_q, min_depth; uint64_t *sum; uint32_t *covered;
@@ -1066,6 +1089,8 @@ struct post_req {
     const uint32_t *iv; uint32_t n_iv; const uint32_t *block_iv, *iv_off;
     cov_req cov;                   /* COV, COVX */
     hist_req hist;                 /* HIST */
+    /* STATS, TG_STATS (with `exclude`): where the tables go, the record groups of the largest block */
+    cbc_gpu_stats *stats; uint32_t stats_gmax;
 };
 
 /* sizes derived from the request: tiles of the difference array (d_words = W + 1 words), change points (two per read at most,
@@ -1159,6 +1184,7 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
         }
         NEED(A_HTILE, (uint64_t)z.n_btiles * sizeof(cbc_block_result) + ((uint64_t)z.n_btiles + 1) * 8, "hipMalloc histogram tiles");
     }
+    if (post_is_stats(k)) NEED(A_STATS, (uint64_t)CBC_STATS_WORDS * 4, "hipMalloc statistics tables");
 done:
     return rc;
 }
@@ -1425,9 +1451,30 @@ static int launch_hist(cbc_gpu_ctx *ctx, hipStream_t ks, const hist_req *hist, c
     return CBC_OK;
 }
 
+/* read statistics: zero the tables, one pass over the records and rows: no text */
+static int launch_stats(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const cbc_region_args &ra)
+{
+    cbc_stats_args sa;
+    memset(&sa, 0, sizeof sa);
+    sa.R = ra; sa.tab = (uint32_t *)ctx->arena[A_STATS].p; sa.exclude = rg->exclude; sa.gmax = rg->stats_gmax;
+    const uint64_t units = (uint64_t)ra.n_blocks * sa.gmax, wgs = (units + CBC_STATS_WAVES - 1u) / CBC_STATS_WAVES;
+    sa.grid = wgs < CBC_STATS_GRID ? (uint32_t)wgs : CBC_STATS_GRID;
+    HIPCHK(hipMemsetAsync(sa.tab, 0, (uint64_t)CBC_STATS_WORDS * 4, ks), "memset statistics tables");
+    if (sa.grid) {
+        if (rg->kind == POST_TG_STATS) {
+            sa.iv = (const uint32_t *)ctx->arena[A_TIV].p; sa.block_iv = (const uint32_t *)ctx->arena[A_TBIV].p; sa.n_iv = rg->n_iv;
+            hipLaunchKernelGGL(cbc_targets_stats_kernel, dim3(sa.grid), dim3(64 * CBC_STATS_WAVES), 0, ks, sa);
+        } else hipLaunchKernelGGL(cbc_stats_kernel, dim3(sa.grid), dim3(64 * CBC_STATS_WAVES), 0, ks, sa);
+        HIPCHK(hipGetLastError(), "launch cbc_stats_kernel");
+    }
+    HIPCHK(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
 /* post stage, step 4: its results.  First the small ones, queued behind the block results and ahead of the call's one wait:
  * the counters, the size of the text or of the histogram, the coverage numbers. */
-struct post_got { uint32_t dctr[4]; uint64_t total, h_count; cbc_block_result *cnt; /* region / SAM / reads: the filter's per-block counts */ };
+struct post_got { uint32_t dctr[4]; uint64_t total, h_count; cbc_block_result *cnt; /* region / SAM / reads: the filter's per-block counts */
+                  uint32_t *stats; /* STATS: the device's tables, CBC_STATS_WORDS */ };
 
 static int post_fetch_sizes(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z, uint32_t n_blocks, hipStream_t sc, post_got *g)
 {
@@ -1447,6 +1494,12 @@ static int post_fetch_sizes(cbc_gpu_ctx *ctx, const post_req *rg, const post_siz
         }
         return CBC_OK;
     }
+    if (post_is_stats(rg->kind)) {                             /* the tables are the output: about 270 KB, no second wait */
+        g->stats = (uint32_t *)malloc((size_t)CBC_STATS_WORDS * 4);
+        if (!g->stats) return CBC_E_NOMEM;
+        HIPCHK(hipMemcpyAsync(g->stats, ctx->arena[A_STATS].p, (uint64_t)CBC_STATS_WORDS * 4, hipMemcpyDeviceToHost, sc), "D2H statistics tables");
+        return CBC_OK;
+    }
     g->cnt = (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
     if (!g->cnt) return CBC_E_NOMEM;
     HIPCHK(hipMemcpyAsync(g->cnt, ctx->arena[A_RCNT].p, (uint64_t)n_blocks * sizeof(cbc_block_result), hipMemcpyDeviceToHost, sc), "D2H region counts");
@@ -1461,6 +1514,12 @@ static int post_fetch_output(cbc_gpu_ctx *ctx, const post_req *rg, const post_si
 {
     const bool depth = post_is_depth(rg->kind);
     uint64_t kept = 0;
+    if (post_is_stats(rg->kind)) {                             /* all zero when a block failed */
+        for (uint32_t b = 0; b < n_blocks; b++) if (res[b].status != CBC_ST_OK) return CBC_OK;
+        cbc_stats_finish(g->stats, rg->stats);
+        *d2h_bytes = (uint64_t)CBC_STATS_WORDS * 4;
+        return CBC_OK;
+    }
     if (depth) { kept = g->dctr[0]; *rg->n_runs = g->dctr[1]; }
     else for (uint32_t b = 0; b < n_blocks; b++) kept += g->cnt[b].n_symbols;
     *rg->text_bytes = g->total; *rg->n_selected = kept;
@@ -1592,6 +1651,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
                     if (!rc) rc = launch_hist(ctx, ks, &rg->hist, z, da);
                     break;
+                case POST_STATS: case POST_TG_STATS: rc = launch_stats(ctx, ks, rg, ra); break;
                 }
                 if (rc) goto done;
                 ctx->last_post = rg->kind;                     /* the events now hold this call's times */
@@ -1644,7 +1704,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
 done:
     if (rc && rc != CBC_E_BLOCK) (void)hipDeviceSynchronize();
     if (res && res != results) free(res);
-    free(pg.cnt);
+    free(pg.cnt); free(pg.stats);
     tm.total_s = wall_now() - T0;
     ctx->last_e2e = tm;
     return rc;
@@ -2042,6 +2102,57 @@ API int cbc_gpu_decode_depth_hist(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t 
     return decode_targets_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
                                n_contigs, t, CBC_TARGETS_DEPTH, exclude_flags, NULL, 0, &text_bytes, n_reads, &n_runs, results, NULL,
                                iv_first, iv_count, &hq);
+}
+
+/* read statistics: the blocks laid out afresh as for a region decode, the plain decode (t == NULL) or the
+ * span decode and the keep rule of a target set, then one pass over the records and rows (cbc_stats_body.h); only the tables
+ * come back */
+API int cbc_gpu_decode_stats(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                             uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const cbc_gpu_targets *t,
+                             uint32_t exclude_flags, cbc_gpu_stats *out, cbc_block_result *results)
+{
+    if (!ctx || !out) return CBC_E_ARG;
+    memset(out, 0, sizeof *out);
+    if (!blocks || !caps || !window_start) return CBC_E_ARG;
+    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (n_blocks == 0) return CBC_OK;
+    if (!in || (t && (!t->iv || !t->block_iv))) return CBC_E_ARG;
+    if (t && (t->smax == 0 || t->n_iv == 0 || t->n_iv > (1u << 24)))
+        return set_err(ctx, CBC_E_ARG, "statistics of a target set want smax > 0 and 1 .. 2^24 intervals", hipSuccess);
+    for (uint32_t i = 0; t && i < t->n_iv; i++)
+        if (t->iv[2 * i] < 1 || t->iv[2 * i] > t->iv[2 * i + 1] || t->iv[2 * i + 1] > CBC_SAM_MAX_POS)
+            return set_err(ctx, CBC_E_ARG, "statistics: an interval is not 1 <= beg <= end <= 2^31 - 1", hipSuccess);
+    uint32_t most = 0;
+    for (uint32_t b = 0; b < n_blocks; b++) {
+        if (blocks[b].n_reads > most) most = blocks[b].n_reads;
+        if (!t) continue;
+        const uint32_t f = t->block_iv[2 * b], c = t->block_iv[2 * b + 1];
+        if (f > t->n_iv || c > t->n_iv - f) return set_err(ctx, CBC_E_ARG, "statistics: a block's interval range lies outside the table", hipSuccess);
+        if (window_start[b] > CBC_SAM_MAX_POS) return set_err(ctx, CBC_E_ARG, "statistics: a block starts past POS 2^31 - 1", hipSuccess);
+    }
+    block_layout L;
+    int rc = relayout_blocks(ctx, "statistics", in_bytes, blocks, n_blocks, NULL, &L);
+    if (rc) return rc;
+    if (L.nrec > 0xffffffffull) { layout_free(&L); return set_err(ctx, CBC_E_ARG, "statistics: more than 2^32 - 1 reads in one call", hipSuccess); }
+    if (L.nrec) {
+        uint64_t text_bytes = 0, n_sel = 0;
+        post_req rg;
+        post_req_init(&rg, t ? POST_TG_STATS : POST_STATS, t ? t->smax : 0u, window_start, NULL, 0, 0, &text_bytes, &n_sel);
+        rg.beg = 1u; rg.end = UINT64_MAX;
+        if (t) { rg.iv = t->iv; rg.n_iv = t->n_iv; rg.block_iv = t->block_iv; }
+        rg.exclude = exclude_flags; rg.stats = out; rg.stats_gmax = (most + 63u) / 64u;
+        rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
+    }
+    layout_free(&L);
+    return rc;
+}
+
+/* kernel times of the most recent cbc_gpu_decode_stats */
+API int cbc_gpu_last_stats_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *stats_ms)
+{
+    if (!ctx || !post_is_stats(ctx->last_post)) return CBC_E_ARG;
+    float *const out[] = { decode_ms, stats_ms };
+    return last_ms(ctx, ctx->ev_rg, out, 2);
 }
 
 /* kernel times of the most recent cbc_gpu_decode_depth_hist */

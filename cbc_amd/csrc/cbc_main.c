@@ -64,6 +64,11 @@ static void usage(const char *p)
             "                       or the merged intervals of --region / --regions-file; binned on the device; takes\n"
             "                       --depth-exclude-flags; not with --sam, --depth or --bedcov)\n"
             "         --hist-max M (with --depth-hist: count every depth >= M in bin M; default: no folding)\n"
+            "         --stats (tables about the reads instead of the reads, tab-separated: SN summary numbers, FS flag categories\n"
+            "                  as qc-passed and qc-failed, FL reads per FLAG, RL reads per length, GC reads per GC percent, BC bases\n"
+            "                  A, C, G, T, other per sequencing cycle; the whole file, or the reads --region / --regions-file select,\n"
+            "                  each once; counted on the device; not with --sam, --depth, --bedcov or --depth-hist)\n"
+            "         --stats-exclude-flags N (with --stats: reads with FLAG & N != 0 are counted as excluded only; default 0)\n"
             "options: -l (header read length = longest read)  --block-reads N (default 4096)  --device N (default 0)\n"
             "         --threads N (SAM parser threads, default one per CPU)  --verbose (stage times)\n"
             "         --compat (write the reference's own single-stream format; slow: one stream = one wavefront)\n"
@@ -454,6 +459,9 @@ int cbc_cli_decompress_bedcov_ext(const char *in, const char *out, const char *r
 int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                             const char *bed_path, uint32_t max_depth, uint32_t exclude, int verbose);
 
+int cbc_cli_decompress_stats(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                             const char *bed_path, uint32_t exclude, int verbose);
+
 int main(int argc, char **argv)
 {
     const char *files[3] = { 0, 0, 0 };
@@ -472,6 +480,8 @@ int main(int argc, char **argv)
     uint32_t thr[8], n_thr = 0;
     int depth_hist = 0, hist_max_given = 0;
     uint32_t hist_max = 0;
+    int stats_out = 0, stats_excl_given = 0;
+    uint32_t stats_exclude = 0;
     g_main_t0 = now_s();
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
@@ -535,6 +545,13 @@ int main(int argc, char **argv)
                 fprintf(stderr, "cbc: --hist-max wants a depth in 1..4294967295\n"); return 1; }
             hist_max = (uint32_t)x; hist_max_given = 1; continue;
         }
+        if (!strcmp(a, "--stats")) { stats_out = 1; continue; }
+        if (!strcmp(a, "--stats-exclude-flags") && i + 1 < argc) {
+            char *e = NULL;
+            const unsigned long v = strtoul(argv[++i], &e, 0);
+            if (!e || *e || e == argv[i] || v > 0xfffful) { fprintf(stderr, "cbc: --stats-exclude-flags wants a FLAG mask in 0..65535 (decimal, 0x.. or 0..)\n"); return 1; }
+            stats_exclude = (uint32_t)v; stats_excl_given = 1; continue;
+        }
         if (!strcmp(a, "--compat")) { compat = 1; continue; }
         if (!strcmp(a, "--long")) { long_reads = 1; continue; }
         if (!strcmp(a, "--device-parse")) { device_parse = 1; continue; }
@@ -592,9 +609,14 @@ int main(int argc, char **argv)
     if (depth_hist && mode != 2) { fprintf(stderr, "cbc: --depth-hist applies to decompression (-d / -x)\n"); return 1; }
     if (depth_hist && (sam_out || depth_out || bedcov)) { fprintf(stderr, "cbc: --depth-hist, --bedcov, --depth and --sam are different outputs; give one of them\n"); return 1; }
     if (depth_hist && ndev > 1) { fprintf(stderr, "cbc: --depth-hist decodes on one device; give a single --devices ordinal\n"); return 1; }
+    if (stats_excl_given && !stats_out) { fprintf(stderr, "cbc: --stats-exclude-flags applies to --stats\n"); return 1; }
+    if (stats_out && mode != 2) { fprintf(stderr, "cbc: --stats applies to decompression (-d / -x)\n"); return 1; }
+    if (stats_out && (sam_out || depth_out || bedcov || depth_hist)) { fprintf(stderr, "cbc: --stats, --depth-hist, --bedcov, --depth and --sam are different outputs; give one of them\n"); return 1; }
+    if (stats_out && ndev > 1) { fprintf(stderr, "cbc: --stats decodes on one device; give a single --devices ordinal\n"); return 1; }
     if (depth_hist)
         return cbc_cli_decompress_hist(files[0], files[1], files[2], device, regions, n_regions, regions_file, hist_max, depth_exclude, verbose);
     if (depth_excl_given && !depth_out && !bedcov) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
+    if (stats_out) return cbc_cli_decompress_stats(files[0], files[1], files[2], device, regions, n_regions, regions_file, stats_exclude, verbose);
     if (bedcov && (thr_given || count_reads))
         return cbc_cli_decompress_bedcov_ext(files[0], files[1], files[2], device, regions, n_regions, regions_file, cov_window, cov_min_depth,
                                              depth_exclude, verbose, thr, n_thr, count_reads);

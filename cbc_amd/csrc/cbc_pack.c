@@ -2185,6 +2185,57 @@ API int cbc_coverage_mean(uint64_t sum, uint64_t len, char *dst)
     return sprintf(dst, "%llu.%02u", (unsigned long long)(m / 100u), (unsigned)(m % 100u));
 }
 
+/* ---- read statistics (include/cbc_host.h) ---- */
+#define STATS_N_FS 15
+static const char *const stats_fs_name[STATS_N_FS] = {
+    "total", "primary", "secondary", "supplementary", "duplicates", "primary duplicates", "mapped", "primary mapped",
+    "paired in sequencing", "read1", "read2", "properly paired", "with itself and mate mapped", "singletons", "reverse strand" };
+
+API uint64_t cbc_stats_text_cap(void)
+{
+    /* per line: the tag and its tab, the longest name or key, a tab and the longest number per column, the newline */
+    return 11u * (3u + 14u + 1u + 23u + 1u) + STATS_N_FS * (3u + 27u + 2u * (1u + 20u) + 1u) + (uint64_t)CBC_STATS_FLAG_BINS * (3u + 5u + 1u + 10u + 1u) +
+           CBC_STATS_LEN_BINS * (3u + 3u + 1u + 10u + 1u) + CBC_STATS_GC_BINS * (3u + 3u + 1u + 10u + 1u) + CBC_STATS_CYCLES * (3u + 3u + 5u * (1u + 10u) + 1u);
+}
+
+API int64_t cbc_stats_text(const cbc_gpu_stats *s, char *dst, uint64_t cap)
+{
+    if (!s || !dst || cap < cbc_stats_text_cap()) return CBC_E_ARG;
+    char *p = dst;
+    uint64_t bases = 0, sym[5] = { 0, 0, 0, 0, 0 }, fs[STATS_N_FS][2];
+    uint32_t lmin = 0, lmax = 0;
+    int any = 0;
+    for (uint32_t l = 0; l < CBC_STATS_LEN_BINS; l++)
+        if (s->len[l]) { bases += (uint64_t)l * s->len[l]; if (!any) lmin = l; lmax = l; any = 1; }
+    for (uint32_t k = 0; k < 5u; k++) for (uint32_t c = 0; c < CBC_STATS_CYCLES; c++) sym[k] += s->cyc[k * CBC_STATS_CYCLES + c];
+    char mean[32];
+    (void)cbc_coverage_mean(bases, s->reads, mean);
+    p += sprintf(p, "SN\treads\t%llu\nSN\treads excluded\t%llu\nSN\tbases\t%llu\n", (unsigned long long)s->reads, (unsigned long long)s->excluded,
+                 (unsigned long long)bases);
+    p += sprintf(p, "SN\tminimum length\t%u\nSN\tmaximum length\t%u\nSN\taverage length\t%s\n", lmin, lmax, mean);
+    p += sprintf(p, "SN\tbases A\t%llu\nSN\tbases C\t%llu\nSN\tbases G\t%llu\nSN\tbases T\t%llu\nSN\tbases other\t%llu\n", (unsigned long long)sym[0],
+                 (unsigned long long)sym[1], (unsigned long long)sym[2], (unsigned long long)sym[3], (unsigned long long)sym[4]);
+    memset(fs, 0, sizeof fs);
+    for (uint32_t f = 0; f < CBC_STATS_FLAG_BINS; f++) {
+        const uint64_t n = s->flag[f];
+        if (!n) continue;
+        const int q = (f & 0x200u) != 0, sec = (f & 0x100u) != 0, sup = !sec && (f & 0x800u), pri = !sec && !sup;
+        const int dup = (f & 0x400u) != 0, map = !(f & 0x4u), pair = pri && (f & 0x1u);
+        const int in[STATS_N_FS] = { 1, pri, sec, sup, dup, pri && dup, map, pri && map, pair, pair && (f & 0x40u), pair && (f & 0x80u),
+                                     pair && (f & 0x2u) && map, pair && map && !(f & 0x8u), pair && map && (f & 0x8u), (f & 0x10u) != 0 };
+        for (int k = 0; k < STATS_N_FS; k++) if (in[k]) fs[k][q] += n;
+    }
+    for (int k = 0; k < STATS_N_FS; k++)
+        p += sprintf(p, "FS\t%s\t%llu\t%llu\n", stats_fs_name[k], (unsigned long long)fs[k][0], (unsigned long long)fs[k][1]);
+    for (uint32_t f = 0; f < CBC_STATS_FLAG_BINS; f++) if (s->flag[f]) p += sprintf(p, "FL\t%u\t%u\n", f, s->flag[f]);
+    for (uint32_t l = 0; l < CBC_STATS_LEN_BINS; l++) if (s->len[l]) p += sprintf(p, "RL\t%u\t%u\n", l, s->len[l]);
+    for (uint32_t g = 0; g < CBC_STATS_GC_BINS; g++) if (s->gc[g]) p += sprintf(p, "GC\t%u\t%u\n", g, s->gc[g]);
+    for (uint32_t c = 0; c < lmax && c < CBC_STATS_CYCLES; c++)
+        p += sprintf(p, "BC\t%u\t%u\t%u\t%u\t%u\t%u\n", c + 1u, s->cyc[c], s->cyc[CBC_STATS_CYCLES + c], s->cyc[2u * CBC_STATS_CYCLES + c],
+                     s->cyc[3u * CBC_STATS_CYCLES + c], s->cyc[4u * CBC_STATS_CYCLES + c]);
+    return (int64_t)(p - dst);
+}
+
 /* ---- depth histogram (include/cbc_host.h) ---- */
 API uint64_t cbc_unpack_targets_size(const cbc_targets *t, uint32_t contig)
 {

@@ -264,6 +264,12 @@ def lib():
                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
         L.cbc_gpu_last_hist_ms.restype = ctypes.c_int
         L.cbc_gpu_last_hist_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 5
+        L.cbc_gpu_decode_stats.restype = ctypes.c_int
+        L.cbc_gpu_decode_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                           ctypes.POINTER(host.LdsCaps), ctypes.c_void_p, ctypes.POINTER(GpuTargets), ctypes.c_uint32,
+                                           ctypes.POINTER(host.GpuStats), ctypes.c_void_p]
+        L.cbc_gpu_last_stats_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_stats_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 2
         L.cbc_gpu_last_depth_ms.restype = ctypes.c_int
         L.cbc_gpu_last_depth_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         if L.cbc_gpu_abi_version() != 1:
@@ -287,7 +293,8 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_stash_reset", "cbc_gpu_stash_bytes", "cbc_gpu_stash_fetch", "cbc_gpu_decode_region",
            "cbc_gpu_decode_blocks_span", "cbc_gpu_last_region_ms", "cbc_gpu_decode_sam", "cbc_gpu_last_sam_ms",
            "cbc_gpu_decode_depth", "cbc_gpu_last_depth_ms", "cbc_gpu_decode_targets", "cbc_gpu_last_targets_ms",
-           "cbc_gpu_decode_coverage", "cbc_gpu_last_coverage_ms", "cbc_gpu_decode_depth_hist", "cbc_gpu_last_hist_ms",
+           "cbc_gpu_decode_coverage", "cbc_gpu_last_coverage_ms", "cbc_gpu_decode_depth_hist", "cbc_gpu_last_hist_ms", "cbc_gpu_decode_stats",
+           "cbc_gpu_last_stats_ms",
            "cbc_gpu_decode_coverage_ext", "cbc_gpu_last_coverage_ext_ms"]
 
 
@@ -794,6 +801,54 @@ class Encoder:
         if getattr(self, "_hist_ms", None) is None:
             raise CbcGpuError("no decode_depth_hist has run on the device")
         return self._hist_ms
+
+    def decode_stats(self, plan: "host.UnpackPlan", targets=None, exclude_flags=0, results=False):
+        """Read statistics (cbc_gpu_decode_stats): the count tables of a first look at the reads, filled on the device in one pass
+        over the decoded records and rows.  targets=None: every read of the container (plain decode); a host.TargetSet of
+        plan.targets(): the reads decode_targets selects for it, each once.  A read with FLAG & exclude_flags != 0 is counted in
+        `excluded` and nowhere else.  Returns a dict: reads, excluded (int), flag (65536,), len (257,), gc (101,) and cyc (5, 256;
+        rows A, C, G, T, other by sequencing cycle), uint32 arrays.  A selection without blocks runs nothing and gives all-zero
+        tables.  With results=True returns (that dict, the per-block decode results) and lets a failed block pass (the tables are
+        all zero then); otherwise it raises CbcGpuError."""
+        plan.sam_header()                                     # refuses what the coordinates cannot carry, and long-read containers
+        if not 0 <= int(exclude_flags) <= 0xffff:
+            raise ValueError("exclude_flags is a FLAG mask in 0 .. 65535")
+        self._stats_ms = None
+        st = host.GpuStats()
+        if targets is None:
+            sel = np.arange(plan.n_blocks, dtype=np.int64)
+        else:
+            sel = np.ascontiguousarray(targets.blocks).astype(np.int64)
+        nb = len(sel)
+        res = np.zeros(nb, dtype=host.RESULT_DTYPE)
+        if nb:
+            caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
+            pay = np.ascontiguousarray(plan.payloads)
+            blocks = np.ascontiguousarray(plan.blocks[sel])
+            ws = np.ascontiguousarray(plan.window_start[sel], dtype=np.uint64)
+            tg = None
+            if targets is not None:
+                iv = np.ascontiguousarray(targets.iv, dtype=np.uint32)
+                biv = np.ascontiguousarray(targets.block_iv, dtype=np.uint32)
+                tg = GpuTargets(iv.ctypes.data, biv.ctypes.data, targets.n_iv, targets.smax)
+            rc = lib().cbc_gpu_decode_stats(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps), ws.ctypes.data,
+                                            ctypes.byref(tg) if tg is not None else None, int(exclude_flags), ctypes.byref(st),
+                                            res.ctypes.data)
+            if rc != 0 and not (results and rc == -4):
+                self._check(rc, "cbc_gpu_decode_stats")
+            v = [ctypes.c_float() for _ in range(2)]
+            if lib().cbc_gpu_last_stats_ms(self._ctx, *[ctypes.byref(x) for x in v]) == 0:
+                self._stats_ms = tuple(float(x.value) for x in v)
+        out = dict(reads=int(st.reads), excluded=int(st.excluded), flag=np.ctypeslib.as_array(st.flag).copy(),
+                   len=np.ctypeslib.as_array(st.len).copy(), gc=np.ctypeslib.as_array(st.gc).copy(),
+                   cyc=np.ctypeslib.as_array(st.cyc).copy().reshape(5, 256))
+        return (out, res) if results else out
+
+    def last_stats_ms(self):
+        """(decode, zeroing + statistics pass) kernel milliseconds of the last decode_stats."""
+        if getattr(self, "_stats_ms", None) is None:
+            raise CbcGpuError("no decode_stats has run on the device")
+        return self._stats_ms
 
     def last_targets_ms(self):
         """(decode, count + scan or mark, depth scan + compact or 0, text) kernel milliseconds of the last decode_targets,

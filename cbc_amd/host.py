@@ -226,8 +226,38 @@ def lib():
         L.cbc_unpack_targets_size.argtypes = [ctypes.POINTER(TargetsC), ctypes.c_uint32]
         L.cbc_hist_fraction.restype = ctypes.c_int
         L.cbc_hist_fraction.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p]
+        L.cbc_stats_text_cap.restype = ctypes.c_uint64
+        L.cbc_stats_text_cap.argtypes = []
+        L.cbc_stats_text.restype = ctypes.c_int64
+        L.cbc_stats_text.argtypes = [ctypes.POINTER(GpuStats), ctypes.c_char_p, ctypes.c_uint64]
         _lib = L
     return _lib
+
+
+class GpuStats(ctypes.Structure):
+    """cbc_gpu_stats (include/cbc_gpu.h): the tables of cbc_gpu_decode_stats."""
+    _fields_ = [("reads", ctypes.c_uint64), ("excluded", ctypes.c_uint64), ("flag", ctypes.c_uint32 * 65536),
+                ("len", ctypes.c_uint32 * 257), ("gc", ctypes.c_uint32 * 101), ("cyc", ctypes.c_uint32 * (5 * 256))]
+
+
+def stats_text(stats) -> bytes:
+    """What `cbc -x --stats` writes for the tables (cbc_stats_text).  stats: the dict of Encoder.decode_stats -- reads, excluded,
+    flag (65536), len (257), gc (101), cyc (5, 256) -- or a GpuStats."""
+    if not isinstance(stats, GpuStats):
+        st = GpuStats()
+        st.reads, st.excluded = int(stats["reads"]), int(stats["excluded"])
+        for name, n in (("flag", 65536), ("len", 257), ("gc", 101), ("cyc", 1280)):
+            a = np.ascontiguousarray(stats[name], dtype=np.uint32).reshape(-1)
+            if a.size != n:
+                raise ValueError("stats[%r] wants %d counters" % (name, n))
+            ctypes.memmove(getattr(st, name), a.ctypes.data, 4 * n)
+        stats = st
+    cap = int(lib().cbc_stats_text_cap())
+    buf = ctypes.create_string_buffer(cap)
+    n = lib().cbc_stats_text(ctypes.byref(stats), buf, cap)
+    if n < 0:
+        raise ValueError("cbc_stats_text failed (%d)" % n)
+    return buf.raw[:n]
 
 
 def hist_fraction(bases: int, size: int) -> bytes:

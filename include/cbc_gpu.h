@@ -463,6 +463,42 @@ int  cbc_gpu_decode_depth_hist(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
  * points; then the new passes: zeroing the bins + accumulate, and the count, scan and write of the non-zero bins. */
 int  cbc_gpu_last_hist_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *accum_ms, float *compact_ms);
 
+/* ---- read statistics ----------------------------------------------------------------------------------
+ * The tables of a first look at an alignment file (flag categories, read lengths, GC content per read, base composition per
+ * sequencing cycle), counted on the device in one streaming pass over the decoded records and rows; about 270 KB come back
+ * whatever the size of the file.
+ *   t == NULL   every read of the blocks, decoded by the plain decoder (window_start is not looked at beyond its presence)
+ *   t != NULL   the reads cbc_gpu_decode_targets selects for the interval table (the same keep rule, each read once), decoded by
+ *               the span-reporting decoder; the blocks may lie on several contigs, block_iv indexes the whole table
+ * A read with FLAG & exclude_flags != 0 is counted in `excluded` and nowhere else.
+ *   flag[f]            reads with FLAG f
+ *   len[l]             reads of length l (a row holds at most 256 bases)
+ *   gc[p]              reads of length >= 1 with floor(100 * (bytes 'G' and 'C') / length) = p
+ *   cyc[s * 256 + c]   s = 0 .. 4 for A, C, G, T, other: reads whose base in sequencing cycle c (0-based) is s.  Cycle c of a
+ *                      read with FLAG & 16 == 0 is SEQ[c]; with FLAG & 16 it is the complement (A <-> T, C <-> G) of
+ *                      SEQ[len - 1 - c].  A base is A, C, G or T only if its byte is exactly that letter.
+ *   reads              the reads counted = the sum of len[]
+ * Every counter is 32 bits on the device and exact: none can pass the reads of the call, and a call over more than 2^32 - 1
+ * reads is CBC_E_ARG.  One call runs as one chunk on one stream with no host round trip between its kernels.  A block that fails
+ * to decode contributes nothing; the call returns CBC_E_BLOCK with *out all zero. */
+#define CBC_STATS_FLAG_BINS 65536u
+#define CBC_STATS_LEN_BINS  257u
+#define CBC_STATS_GC_BINS   101u
+#define CBC_STATS_CYCLES    256u
+typedef struct cbc_gpu_stats {
+    uint64_t reads, excluded;
+    uint32_t flag[CBC_STATS_FLAG_BINS];
+    uint32_t len[CBC_STATS_LEN_BINS];
+    uint32_t gc[CBC_STATS_GC_BINS];
+    uint32_t cyc[5u * CBC_STATS_CYCLES];
+} cbc_gpu_stats;
+int  cbc_gpu_decode_stats(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                          uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                          const cbc_gpu_targets *t /* or NULL */, uint32_t exclude_flags, cbc_gpu_stats *out,
+                          cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_stats: the decode; zeroing the tables + the statistics pass. */
+int  cbc_gpu_last_stats_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *stats_ms);
+
 /* ---- whole-file stream ("compat" mode): the reference's own file format --------------------------------------
  * compress() / decompress(), src/compression.c:112-216: ONE arithmetic stream per file, models never reset.
  * `batch` is a cbc_host_batch packed with cbc_pack_opts.whole_file = 1: its `blocks` are SEGMENTS of the one

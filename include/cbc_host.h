@@ -308,6 +308,17 @@ int      cbc_coverage_mean(uint64_t sum, uint64_t len, char *dst);
 uint64_t cbc_unpack_targets_size(const cbc_targets *t, uint32_t contig);
 int      cbc_hist_fraction(uint64_t bases, uint64_t size, char *dst);
 
+/* Read statistics (the tables come from cbc_gpu_decode_stats).  cbc_stats_text writes what
+ * `cbc -x --stats` writes, tab-separated, in this order: 11 SN lines (reads, reads excluded, bases, minimum length, maximum
+ * length, average length, bases A, bases C, bases G, bases T, bases other), 15 FS lines (category, qc-passed, qc-failed; the
+ * classes of `samtools flagstat`), then one FL line per FLAG value that occurs, one RL line per length that occurs, one GC line
+ * per percent that occurs, each ascending, and one BC line per cycle 1 .. maximum length (A, C, G, T, other).  Every number is
+ * an integer from the tables except the average length, which has two decimals by the rule of cbc_coverage_mean(bases, reads).
+ * Minimum and maximum length are 0 and the average is "0.00" when there are no reads.  Returns the bytes written, or CBC_E_ARG
+ * when cap is below cbc_stats_text_cap(), the size that holds the text of any tables (every line at its longest). */
+uint64_t cbc_stats_text_cap(void);
+int64_t  cbc_stats_text(const cbc_gpu_stats *s, char *dst, uint64_t cap);
+
 int     cbc_unpack_plan_create(const uint8_t *blob, uint64_t len, const char *fasta, size_t fasta_len,
                                cbc_unpack_plan **out, char *errbuf, size_t errlen);
 void    cbc_unpack_plan_free(cbc_unpack_plan *u);
