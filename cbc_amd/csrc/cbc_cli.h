@@ -1,0 +1,29 @@
+/*
+ * cbc_cli.h -- the decode side of the `cbc` command line (cbc_cli_unpack.c), as cbc_main.c calls it.  Every function reads
+ * the container `in` and the FASTA `ref`, writes `out` and returns the process's exit status.
+ */
+#ifndef CBC_CLI_H
+#define CBC_CLI_H
+#include <stdint.h>
+
+/* every read, one per line; either file format; contiguous block ranges over the listed devices */
+int cbc_cli_decompress(const char *in, const char *out, const char *ref, const int *devs, int ndev);
+
+/* exactly one region (for --sam and --depth: at most one, NULL = the whole file) */
+int cbc_cli_decompress_region(const char *in, const char *out, const char *ref, int device, const char *region, int verbose);
+int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int verbose);
+int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude, int verbose);
+
+/* any number of regions and / or a BED file (bed_path NULL: none); output: CBC_TARGETS_READS, _SAM or _DEPTH */
+int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                               const char *bed_path, uint32_t output, uint32_t exclude, int verbose);
+/* n_thr == 0 and !count_reads: the plain summary */
+int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                              const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose,
+                              const uint32_t *thr, uint32_t n_thr, int count_reads);
+int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                            const char *bed_path, uint32_t max_depth, uint32_t exclude, int verbose);
+int cbc_cli_decompress_stats(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                             const char *bed_path, uint32_t exclude, int verbose);
+
+#endif

@@ -9,6 +9,7 @@
 #include <pthread.h>
 #include <time.h>
 #include "../../include/cbc_host.h"
+#include "cbc_cli.h"
 
 static char *slurp2(const char *path, size_t *len)
 {
@@ -158,65 +159,123 @@ int cbc_cli_decompress(const char *in, const char *out, const char *ref, const i
     return 0;
 }
 
+/* ---- the decode modes that write something other than every read (DESIGN.md sections 4.10 - 4.18).  The steps they share are
+ * written once, cli_open .. cli_close; each mode function below is what it selects, its call loop and what it prints. ---- */
+static double now2(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+
+typedef struct cli_run {
+    char *blob, *bed;                 /* the container; the BED text, kept to the end (bedcov prints unknown contig names out of it) */
+    size_t blob_len, bed_len;
+    cbc_unpack_plan *u;
+    cbc_gpu_ctx *ctx;                 /* opened by the first cli_device */
+    int device, used;                 /* used: a device was opened, so there are kernel times to print */
+    double t0, t1, t_init, t_dev;     /* start, selection done (set by the mode), seconds in cli_device, seconds in the decode calls */
+} cli_run;
+
+/* container and FASTA read, the magic checked (opt: the option the message names; lacks: what a single stream does not have),
+ * then the BED file, then the plan */
+static int cli_open(cli_run *r, const char *in, const char *ref, const char *bed_path, int device, const char *opt, const char *lacks)
+{
+    memset(r, 0, sizeof *r);
+    r->t0 = now2();
+    r->device = device;
+    size_t fa_len = 0;
+    r->blob = slurp2(in, &r->blob_len);
+    char *fa = slurp2(ref, &fa_len);
+    if (!r->blob || !fa) return 1;
+    if (r->blob_len < 4 || memcmp(r->blob, "CBCB", 4) != 0) {
+        fprintf(stderr, "cbc: %s needs a block container; %s is a single-stream (--compat) file, which %s\n", opt, in, lacks);
+        return 1;
+    }
+    if (bed_path && !(r->bed = slurp2(bed_path, &r->bed_len))) return 1;
+    char err[512];
+    const int rc = cbc_unpack_plan_create((const uint8_t *)r->blob, r->blob_len, fa, fa_len, &r->u, err, sizeof err);
+    free(fa);
+    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
+    return 0;
+}
+
+/* the device, opened and given the reference when the first call needs it: a selection without blocks needs none */
+static int cli_device(cli_run *r)
+{
+    if (r->ctx) return 0;
+    const double a = now2();
+    const int rc = cbc_gpu_init(r->device, &r->ctx);
+    if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
+    if (cbc_gpu_upload_reference(r->ctx, r->u->ref, r->u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(r->ctx)); return 1; }
+    r->used = 1;
+    r->t_init = now2() - a;
+    return 0;
+}
+
+static void cli_close(cli_run *r)
+{
+    if (r->ctx) cbc_gpu_shutdown(r->ctx);
+    free(r->bed); free(r->blob);
+    cbc_unpack_plan_free(r->u);
+}
+
+/* descriptors, window starts and (bc != NULL) contigs of the blocks sel[0 .. nb), or of blocks 0 .. nb when sel == NULL */
+static int cli_gather(const cbc_unpack_plan *u, const uint32_t *sel, uint32_t nb, cbc_dec_block_desc **bl, uint64_t **ws, uint32_t **bc)
+{
+    *bl = (cbc_dec_block_desc *)malloc((size_t)(nb ? nb : 1) * sizeof **bl);
+    *ws = (uint64_t *)malloc((size_t)(nb ? nb : 1) * 8);
+    if (bc) *bc = (uint32_t *)malloc((size_t)(nb ? nb : 1) * 4);
+    if (!*bl || !*ws || (bc && !*bc)) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    for (uint32_t k = 0; k < nb; k++) {
+        const uint32_t b = sel ? sel[k] : k;
+        (*bl)[k] = u->blocks[b]; (*ws)[k] = u->window_start[b];
+        if (bc) (*bc)[k] = u->block_contig[b];
+    }
+    return 0;
+}
+
+static void add_ms(float *sum, const float *ms, int n) { for (int i = 0; i < n; i++) sum[i] += ms[i]; }
+static int cannot_write(const char *out) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+
 /* `cbc -d|-x ... --region NAME[:BEG[-END]]`: the index selects the blocks that can hold a read overlapping the locus
  * (cbc_unpack_region), the device decodes only those, filters the reads and assembles their text (cbc_gpu_decode_region);
  * the output is what `cbc -x` writes for those reads, in the same order. */
-static double now2(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
-
 int cbc_cli_decompress_region(const char *in, const char *out, const char *ref, int device, const char *region, int verbose)
 {
-    const double t0 = now2();
-    size_t blob_len = 0, fa_len = 0;
-    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
-    if (!blob || !fa) return 1;
-    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
-        fprintf(stderr, "cbc: --region needs a block container; %s is a single-stream (--compat) file, which has no block index\n", in);
-        return 1;
-    }
+    cli_run r;
+    if (cli_open(&r, in, ref, NULL, device, "--region", "has no block index")) return 1;
+    const cbc_unpack_plan *u = r.u;
     char err[512];
-    cbc_unpack_plan *u = NULL;
-    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
-    free(fa);
-    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
     cbc_region_sel sel;
-    rc = cbc_unpack_region(u, region, &sel, err, sizeof err);
+    int rc = cbc_unpack_region(u, region, &sel, err, sizeof err);
     if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT ? err : "region selection failed"); return 1; }
     const uint32_t nb = sel.b1 - sel.b0;
     uint64_t cap = 0;
     for (uint32_t b = sel.b0; b < sel.b1; b++) cap += (uint64_t)u->blocks[b].n_reads * (u->seq_stride + 1u);
     char *text = (char *)malloc((size_t)(cap ? cap : 1));
     if (!text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    const double t1 = now2();
-    double t2 = t1, t3 = t1;
+    r.t1 = now2();
     uint64_t text_bytes = 0, n_sel = 0;
-    float ms_dec = 0, ms_filter = 0, ms_text = 0;
+    float ms[3] = { 0, 0, 0 };
     if (nb) {                                            /* no block can hold such a read: no device needed */
-        cbc_gpu_ctx *ctx = NULL;
-        rc = cbc_gpu_init(device, &ctx);
-        if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
-        if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-        t2 = now2();
-        rc = cbc_gpu_decode_region(ctx, u->payloads, u->payload_bytes, u->blocks + sel.b0, nb, &u->caps, u->window_start + sel.b0,
+        if (cli_device(&r)) return 1;
+        const double b = now2();
+        rc = cbc_gpu_decode_region(r.ctx, u->payloads, u->payload_bytes, u->blocks + sel.b0, nb, &u->caps, u->window_start + sel.b0,
                                    sel.beg, sel.end, sel.smax, (uint8_t *)text, cap, &text_bytes, &n_sel, NULL);
-        if (rc) { fprintf(stderr, "cbc: region decode failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-        t3 = now2();
-        if (verbose) (void)cbc_gpu_last_region_ms(ctx, &ms_dec, &ms_filter, &ms_text);
-        cbc_gpu_shutdown(ctx);
+        if (rc) { fprintf(stderr, "cbc: region decode failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
+        r.t_dev = now2() - b;
+        if (verbose) (void)cbc_gpu_last_region_ms(r.ctx, &ms[0], &ms[1], &ms[2]);
     }
+    const double t3 = now2();
     FILE *fo = fopen(out, "wb");
-    if (!fo || (text_bytes && fwrite(text, 1, (size_t)text_bytes, fo) != (size_t)text_bytes) || fclose(fo) != 0) {
-        fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    if (!fo || (text_bytes && fwrite(text, 1, (size_t)text_bytes, fo) != (size_t)text_bytes) || fclose(fo) != 0) return cannot_write(out);
     printf("%llu reads in %s:%llu-%llu decompressed from %u of %u blocks\n", (unsigned long long)n_sel,
            u->names + u->contig_name_off[sel.contig], (unsigned long long)sel.beg, (unsigned long long)sel.end, nb, u->n_blocks);
     if (verbose) {
         printf("region: blocks [%u, %u) of %u selected, %llu reads written, %llu text bytes, span bound %u\n", sel.b0, sel.b1, u->n_blocks,
                (unsigned long long)n_sel, (unsigned long long)text_bytes, sel.smax);
         printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + filter + text %.3f s, write %.3f s\n",
-               t1 - t0, t2 - t1, t3 - t2, now2() - t3);
-        if (nb) printf("kernels: decode %.3f ms, filter + scan %.3f ms, text %.3f ms\n", ms_dec, ms_filter, ms_text);
+               r.t1 - r.t0, r.t_init, r.t_dev, now2() - t3);
+        if (r.used) printf("kernels: decode %.3f ms, filter + scan %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2]);
     }
-    free(text); free(blob);
-    cbc_unpack_plan_free(u);
+    free(text);
+    cli_close(&r);
     return 0;
 }
 
@@ -225,54 +284,39 @@ int cbc_cli_decompress_region(const char *in, const char *out, const char *ref, 
  * (cbc_gpu_decode_sam); only the text crosses PCIe. */
 int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int verbose)
 {
-    const double t0 = now2();
-    size_t blob_len = 0, fa_len = 0;
-    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
-    if (!blob || !fa) return 1;
-    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
-        fprintf(stderr, "cbc: --sam needs a block container; %s is a single-stream (--compat) file, which stores no contig table\n", in);
-        return 1;
-    }
+    cli_run r;
+    if (cli_open(&r, in, ref, NULL, device, "--sam", "stores no contig table")) return 1;
+    const cbc_unpack_plan *u = r.u;
     char err[512];
-    cbc_unpack_plan *u = NULL;
-    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
-    free(fa);
-    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
     const int64_t hdr = cbc_unpack_sam_header(u, NULL, 0, err, sizeof err);
     if (hdr < 0) { fprintf(stderr, "cbc: %s\n", hdr == CBC_E_INPUT ? err : "SAM header failed"); return 1; }
     cbc_region_sel sel;
     memset(&sel, 0, sizeof sel);
     sel.b1 = u->n_blocks;
-    if (region) {
-        rc = cbc_unpack_region(u, region, &sel, err, sizeof err);
-        if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT ? err : "region selection failed"); return 1; }
-    }
+    int rc = region ? cbc_unpack_region(u, region, &sel, err, sizeof err) : 0;
+    if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT ? err : "region selection failed"); return 1; }
     const uint32_t nb = sel.b1 - sel.b0;
     const uint64_t cap = cbc_unpack_sam_text_cap(u, sel.b0, sel.b1);
     char *text = (char *)malloc((size_t)hdr + (size_t)cap + 1);
     if (!text || cbc_unpack_sam_header(u, text, (uint64_t)hdr, err, sizeof err) != hdr) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    const double t1 = now2();
-    double t2 = t1, t3 = t1;
+    r.t1 = now2();
     uint64_t text_bytes = 0, n_reads = 0;
-    float ms_dec = 0, ms_count = 0, ms_text = 0;
+    float ms[3] = { 0, 0, 0 };
     if (nb) {                                            /* no block to decode: the header alone, no device needed */
-        cbc_gpu_ctx *ctx = NULL;
-        rc = cbc_gpu_init(device, &ctx);
-        if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
-        if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-        t2 = now2();
+        if (cli_device(&r)) return 1;
+        const double b = now2();
         cbc_sam_region rg = { sel.beg, sel.end, sel.smax, 0 };
-        rc = cbc_gpu_decode_sam(ctx, u->payloads, u->payload_bytes, u->blocks + sel.b0, nb, &u->caps, u->window_start + sel.b0,
+        rc = cbc_gpu_decode_sam(r.ctx, u->payloads, u->payload_bytes, u->blocks + sel.b0, nb, &u->caps, u->window_start + sel.b0,
                                 u->block_contig + sel.b0, u->names, u->names_bytes, u->contig_name_off, u->n_contigs,
                                 region ? &rg : NULL, (uint8_t *)text + hdr, cap, &text_bytes, &n_reads, NULL);
-        if (rc) { fprintf(stderr, "cbc: SAM decode failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-        t3 = now2();
-        if (verbose) (void)cbc_gpu_last_sam_ms(ctx, &ms_dec, &ms_count, &ms_text);
-        cbc_gpu_shutdown(ctx);
+        if (rc) { fprintf(stderr, "cbc: SAM decode failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
+        r.t_dev = now2() - b;
+        if (verbose) (void)cbc_gpu_last_sam_ms(r.ctx, &ms[0], &ms[1], &ms[2]);
     }
+    const double t3 = now2();
     const size_t total = (size_t)hdr + (size_t)text_bytes;
     FILE *fo = fopen(out, "wb");
-    if (!fo || fwrite(text, 1, total, fo) != total || fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    if (!fo || fwrite(text, 1, total, fo) != total || fclose(fo) != 0) return cannot_write(out);
     if (region)
         printf("%llu reads in %s:%llu-%llu written as SAM from %u of %u blocks\n", (unsigned long long)n_reads,
                u->names + u->contig_name_off[sel.contig], (unsigned long long)sel.beg, (unsigned long long)sel.end, nb, u->n_blocks);
@@ -281,11 +325,11 @@ int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int
         printf("sam: blocks [%u, %u) of %u, %llu reads, %lld header bytes, %llu text bytes\n", sel.b0, sel.b1, u->n_blocks,
                (unsigned long long)n_reads, (long long)hdr, (unsigned long long)text_bytes);
         printf("time: read + plan + header %.3f s, device init + reference upload %.3f s, decode + count + text %.3f s, write %.3f s\n",
-               t1 - t0, t2 - t1, t3 - t2, now2() - t3);
-        if (nb) printf("kernels: decode %.3f ms, count + scan %.3f ms, text %.3f ms\n", ms_dec, ms_count, ms_text);
+               r.t1 - r.t0, r.t_init, r.t_dev, now2() - t3);
+        if (r.used) printf("kernels: decode %.3f ms, count + scan %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2]);
     }
-    free(text); free(blob);
-    cbc_unpack_plan_free(u);
+    free(text);
+    cli_close(&r);
     return 0;
 }
 
@@ -294,72 +338,50 @@ int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int
  * that has blocks, in the order of the contig table, the texts appended.  Only the track crosses PCIe. */
 int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude, int verbose)
 {
-    const double t0 = now2();
-    size_t blob_len = 0, fa_len = 0;
-    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
-    if (!blob || !fa) return 1;
-    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
-        fprintf(stderr, "cbc: --depth needs a block container; %s is a single-stream (--compat) file, which stores no contig table\n", in);
-        return 1;
-    }
+    cli_run r;
+    if (cli_open(&r, in, ref, NULL, device, "--depth", "stores no contig table")) return 1;
+    const cbc_unpack_plan *u = r.u;
     char err[512];
-    cbc_unpack_plan *u = NULL;
-    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
-    free(fa);
-    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
     /* what SAM output refuses, depth refuses: a long-read container, names and lengths the text cannot carry */
     if (cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) < 0) { fprintf(stderr, "cbc: --depth: %s\n", err[0] ? err : "the contig table is not usable"); return 1; }
     /* the calls: the region's selection, or every contig as a whole */
     const uint32_t n_calls = region ? 1u : u->n_contigs;
     cbc_region_sel *sels = (cbc_region_sel *)calloc(n_calls ? n_calls : 1u, sizeof(cbc_region_sel));
     if (!sels) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    uint64_t cap = 0, max_cap = 0;
+    uint64_t max_cap = 0;
+    int rc;
     for (uint32_t k = 0; k < n_calls; k++) {
         rc = region ? cbc_unpack_region(u, region, &sels[k], err, sizeof err) : cbc_unpack_contig_blocks(u, k, &sels[k], err, sizeof err);
         if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT ? err : "block selection failed"); return 1; }
         const uint64_t c = cbc_unpack_depth_text_cap(u, sels[k].b0, sels[k].b1, sels[k].contig);
         if (c > max_cap) max_cap = c;
-        cap += c;
     }
-    (void)cap;
-    const double t1 = now2();
-    double t_init = 0, t_dev = 0;
+    r.t1 = now2();
     FILE *fo = fopen(out, "wb");
-    if (!fo) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    if (!fo) return cannot_write(out);
     char *text = (char *)malloc((size_t)max_cap + 1);
     if (!text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    cbc_gpu_ctx *ctx = NULL;
     uint64_t total = 0, runs = 0, kept = 0;
     uint32_t blocks_used = 0;
-    float ms[4] = { 0, 0, 0, 0 };
+    float ms[4] = { 0, 0, 0, 0 }, m[4];
     for (uint32_t k = 0; k < n_calls; k++) {
         const cbc_region_sel *s = &sels[k];
         const uint32_t nb = s->b1 - s->b0;
         if (!nb) continue;                              /* no block can hold a read of the window: no line, no device needed */
-        const double a = now2();
-        if (!ctx) {
-            rc = cbc_gpu_init(device, &ctx);
-            if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
-            if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-            t_init = now2() - a;
-        }
+        if (cli_device(&r)) return 1;
         const double b = now2();
         const char *nm = u->names + u->contig_name_off[s->contig];
         uint64_t tb = 0, nr = 0, nk = 0;
-        rc = cbc_gpu_decode_depth(ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
+        rc = cbc_gpu_decode_depth(r.ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
                                   nm, (uint32_t)strlen(nm), s->beg, s->end, s->smax, exclude, (uint8_t *)text,
                                   cbc_unpack_depth_text_cap(u, s->b0, s->b1, s->contig), &tb, &nr, &nk, NULL);
-        if (rc) { fprintf(stderr, "cbc: depth failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-        t_dev += now2() - b;
-        if (verbose) {
-            float m4[4];
-            if (cbc_gpu_last_depth_ms(ctx, &m4[0], &m4[1], &m4[2], &m4[3]) == 0) for (int i = 0; i < 4; i++) ms[i] += m4[i];
-        }
-        if (tb && fwrite(text, 1, (size_t)tb, fo) != (size_t)tb) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+        if (rc) { fprintf(stderr, "cbc: depth failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
+        r.t_dev += now2() - b;
+        if (verbose && cbc_gpu_last_depth_ms(r.ctx, &m[0], &m[1], &m[2], &m[3]) == 0) add_ms(ms, m, 4);
+        if (tb && fwrite(text, 1, (size_t)tb, fo) != (size_t)tb) return cannot_write(out);
         total += tb; runs += nr; kept += nk; blocks_used += nb;
     }
-    if (fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
-    if (ctx) cbc_gpu_shutdown(ctx);
+    if (fclose(fo) != 0) return cannot_write(out);
     if (region)
         printf("depth of %s:%llu-%llu: %llu runs from %llu reads in %u of %u blocks\n", u->names + u->contig_name_off[sels[0].contig],
                (unsigned long long)sels[0].beg, (unsigned long long)sels[0].end, (unsigned long long)runs, (unsigned long long)kept,
@@ -367,12 +389,11 @@ int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, i
     else printf("depth: %llu runs from %llu reads in %u blocks\n", (unsigned long long)runs, (unsigned long long)kept, blocks_used);
     if (verbose) {
         printf("depth: %llu text bytes, exclude flags 0x%x\n", (unsigned long long)total, exclude);
-        printf("time: read + plan %.3f s, device init + reference upload %.3f s, decode + depth + write %.3f s\n", t1 - t0, t_init, t_dev);
-        if (ctx) printf("kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
+        printf("time: read + plan %.3f s, device init + reference upload %.3f s, decode + depth + write %.3f s\n", r.t1 - r.t0, r.t_init, r.t_dev);
+        if (r.used) printf("kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
     }
-    free(text); free(sels); free(blob);
-    cbc_unpack_plan_free(u);
-    (void)t0;
+    free(text); free(sels);
+    cli_close(&r);
     return 0;
 }
 
@@ -382,92 +403,61 @@ int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, i
 int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                                const char *bed_path, uint32_t output, uint32_t exclude, int verbose)
 {
-    const double t0 = now2();
-    const char *what = output == CBC_TARGETS_DEPTH ? "--depth" : output == CBC_TARGETS_SAM ? "--sam" : "--region";
-    size_t blob_len = 0, fa_len = 0, bed_len = 0;
-    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
-    if (!blob || !fa) return 1;
-    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
-        fprintf(stderr, "cbc: %s needs a block container; %s is a single-stream (--compat) file, which has no block index\n",
-                bed_path ? "--regions-file" : what, in);
-        return 1;
-    }
-    char *bed = NULL;
-    if (bed_path && !(bed = slurp2(bed_path, &bed_len))) return 1;
+    const int depth = output == CBC_TARGETS_DEPTH, sam = output == CBC_TARGETS_SAM;
+    cli_run r;
+    if (cli_open(&r, in, ref, bed_path, device, bed_path ? "--regions-file" : depth ? "--depth" : sam ? "--sam" : "--region", "has no block index")) return 1;
+    const cbc_unpack_plan *u = r.u;
     char err[512];
-    cbc_unpack_plan *u = NULL;
-    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
-    free(fa);
-    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
     cbc_targets *T = NULL;
-    rc = cbc_unpack_targets(u, regions, n_regions, bed, bed_len, &T, err, sizeof err);
-    free(bed);
+    int rc = cbc_unpack_targets(u, regions, n_regions, r.bed, r.bed_len, &T, err, sizeof err);
     if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT && err[0] ? err : "target selection failed"); return 1; }
-    const int64_t hdr = output == CBC_TARGETS_SAM ? cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) : 0;
+    const int64_t hdr = sam ? cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) : 0;
     if (hdr < 0) { fprintf(stderr, "cbc: %s\n", err); return 1; }
-    /* the selected blocks with their window starts and contigs, gathered once */
     const uint32_t nb = T->n_blocks;
-    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)(nb ? nb : 1) * sizeof *bl);
-    uint64_t *ws = (uint64_t *)malloc((size_t)(nb ? nb : 1) * 8);
-    uint32_t *bc = (uint32_t *)malloc((size_t)(nb ? nb : 1) * 4);
-    if (!bl || !ws || !bc) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    for (uint32_t k = 0; k < nb; k++) { const uint32_t b = T->blocks[k]; bl[k] = u->blocks[b]; ws[k] = u->window_start[b]; bc[k] = u->block_contig[b]; }
+    cbc_dec_block_desc *bl; uint64_t *ws; uint32_t *bc;
+    if (cli_gather(u, T->blocks, nb, &bl, &ws, &bc)) return 1;
     uint64_t cap = 0;
-    if (output == CBC_TARGETS_DEPTH) { for (uint32_t c = 0; c < u->n_contigs; c++) { const uint64_t x = cbc_unpack_targets_depth_cap(u, T, c); if (x > cap) cap = x; } }
-    else cap = cbc_unpack_targets_text_cap(u, T, output == CBC_TARGETS_SAM);
+    if (depth) { for (uint32_t c = 0; c < u->n_contigs; c++) { const uint64_t x = cbc_unpack_targets_depth_cap(u, T, c); if (x > cap) cap = x; } }
+    else cap = cbc_unpack_targets_text_cap(u, T, sam);
     char *text = (char *)malloc((size_t)hdr + (size_t)cap + 1);
     if (!text || (hdr && cbc_unpack_sam_header(u, text, (uint64_t)hdr, err, sizeof err) != hdr)) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    const double t1 = now2();
-    double t_init = 0, t_dev = 0;
+    r.t1 = now2();
     FILE *fo = fopen(out, "wb");
-    if (!fo || (hdr && fwrite(text, 1, (size_t)hdr, fo) != (size_t)hdr)) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
-    cbc_gpu_ctx *ctx = NULL;
+    if (!fo || (hdr && fwrite(text, 1, (size_t)hdr, fo) != (size_t)hdr)) return cannot_write(out);
     uint64_t total = 0, reads = 0, runs = 0;
-    float ms[4] = { 0, 0, 0, 0 };
-    const cbc_gpu_targets gt = { (const uint32_t *)T->iv, NULL, T->n_iv, T->smax };
-    const uint32_t n_calls = !nb ? 0u : output == CBC_TARGETS_DEPTH ? u->n_contigs : 1u;
+    float ms[4] = { 0, 0, 0, 0 }, m[4];
+    const uint32_t n_calls = !nb ? 0u : depth ? u->n_contigs : 1u;
     for (uint32_t k = 0; k < n_calls; k++) {
-        const uint32_t k0 = output == CBC_TARGETS_DEPTH ? T->contig_blk_first[k] : 0u, kn = output == CBC_TARGETS_DEPTH ? T->contig_blk_count[k] : nb;
+        const uint32_t k0 = depth ? T->contig_blk_first[k] : 0u, kn = depth ? T->contig_blk_count[k] : nb;
         if (!kn) continue;                              /* no block can hold a read of the contig's intervals */
-        const double a = now2();
-        if (!ctx) {
-            rc = cbc_gpu_init(device, &ctx);
-            if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
-            if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-            t_init = now2() - a;
-        }
+        if (cli_device(&r)) return 1;
         const double b = now2();
-        cbc_gpu_targets g = gt;
-        g.block_iv = T->block_iv + 2 * (size_t)k0;
+        const cbc_gpu_targets g = { (const uint32_t *)T->iv, T->block_iv + 2 * (size_t)k0, T->n_iv, T->smax };
         uint64_t tb = 0, nr = 0, nn = 0;
-        rc = cbc_gpu_decode_targets(ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
+        rc = cbc_gpu_decode_targets(r.ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
                                     u->contig_name_off, u->n_contigs, &g, output, exclude, (uint8_t *)text, cap, &tb, &nr, &nn, NULL);
-        if (rc) { fprintf(stderr, "cbc: targets decode failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-        t_dev += now2() - b;
-        if (verbose) {
-            float m4[4];
-            if (cbc_gpu_last_targets_ms(ctx, &m4[0], &m4[1], &m4[2], &m4[3]) == 0) for (int i = 0; i < 4; i++) ms[i] += m4[i];
-        }
-        if (tb && fwrite(text, 1, (size_t)tb, fo) != (size_t)tb) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+        if (rc) { fprintf(stderr, "cbc: targets decode failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
+        r.t_dev += now2() - b;
+        if (verbose && cbc_gpu_last_targets_ms(r.ctx, &m[0], &m[1], &m[2], &m[3]) == 0) add_ms(ms, m, 4);
+        if (tb && fwrite(text, 1, (size_t)tb, fo) != (size_t)tb) return cannot_write(out);
         total += tb; reads += nr; runs += nn;
     }
-    if (fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
-    if (ctx) cbc_gpu_shutdown(ctx);
-    if (output == CBC_TARGETS_DEPTH)
+    if (fclose(fo) != 0) return cannot_write(out);
+    if (depth)
         printf("depth of %u intervals: %llu runs from %llu reads in %u of %u blocks\n", T->n_iv, (unsigned long long)runs,
                (unsigned long long)reads, nb, u->n_blocks);
     else printf("%llu reads in %u intervals %s from %u of %u blocks\n", (unsigned long long)reads, T->n_iv,
-                output == CBC_TARGETS_SAM ? "written as SAM" : "decompressed", nb, u->n_blocks);
+                sam ? "written as SAM" : "decompressed", nb, u->n_blocks);
     if (verbose) {
         printf("targets: %llu regions and BED lines taken, %u intervals after merging, %llu BED lines selected nothing, %llu text bytes, span bound %u\n",
                (unsigned long long)T->n_input, T->n_iv, (unsigned long long)T->bed_unselected, (unsigned long long)total, T->smax);
-        printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + text + write %.3f s\n", t1 - t0, t_init, t_dev);
-        if (ctx) printf("kernels: decode %.3f ms, %s %.3f ms, scan + compact %.3f ms, text %.3f ms\n", ms[0],
-                        output == CBC_TARGETS_DEPTH ? "mark" : "filter + scan", ms[1], ms[2], ms[3]);
+        printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + text + write %.3f s\n", r.t1 - r.t0, r.t_init, r.t_dev);
+        if (r.used) printf("kernels: decode %.3f ms, %s %.3f ms, scan + compact %.3f ms, text %.3f ms\n", ms[0],
+                           depth ? "mark" : "filter + scan", ms[1], ms[2], ms[3]);
     }
-    free(text); free(bl); free(ws); free(bc); free(blob);
+    free(text); free(bl); free(ws); free(bc);
     cbc_targets_free(T);
-    cbc_unpack_plan_free(u);
+    cli_close(&r);
     return 0;
 }
 
@@ -477,37 +467,25 @@ int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref,
  * cbc_gpu_decode_coverage per contig that has intervals and blocks; the text is formatted here, so that it comes out in input
  * order across contigs.  12 bytes per query cross PCIe.
  * `--thresholds T1,..` / `--count-reads`: n_thr more columns, the positions with depth >= Ti, and one
- * last column, the kept reads with a base in the query, from cbc_gpu_decode_coverage_ext; with neither, the call, the kernels,
- * the bytes and the messages are those of the plain summary. */
-static int bedcov_run(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
-                      const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose,
-                      const uint32_t *thr, uint32_t n_thr, int count_reads)
+ * last column, the kept reads with a base in the query, from cbc_gpu_decode_coverage_ext; with neither (n_thr == 0 and
+ * !count_reads), the call, the kernels, the bytes and the messages are those of the plain summary. */
+int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
+                              const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose,
+                              const uint32_t *thr, uint32_t n_thr, int count_reads)
 {
     const int ext = n_thr || count_reads;
-    const double t0 = now2();
-    size_t blob_len = 0, fa_len = 0, bed_len = 0;
-    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
-    if (!blob || !fa) return 1;
-    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
-        fprintf(stderr, "cbc: --bedcov needs a block container; %s is a single-stream (--compat) file, which has no block index\n", in);
-        return 1;
-    }
-    char *bed = NULL;
-    if (bed_path && !(bed = slurp2(bed_path, &bed_len))) return 1;
+    cli_run r;
+    if (cli_open(&r, in, ref, bed_path, device, "--bedcov", "has no block index")) return 1;
+    const cbc_unpack_plan *u = r.u;
     char err[512];
-    cbc_unpack_plan *u = NULL;
-    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
-    free(fa);
-    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
     cbc_queries *Q = NULL;
-    rc = cbc_unpack_queries(u, regions, n_regions, bed, bed_len, window, &Q, err, sizeof err);
+    int rc = cbc_unpack_queries(u, regions, n_regions, r.bed, r.bed_len, window, &Q, err, sizeof err);
     if (rc) { fprintf(stderr, "cbc: --bedcov: %s\n", rc == CBC_E_INPUT && err[0] ? err : "query selection failed"); return 1; }
     const cbc_targets *T = Q->targets;
     const uint64_t nq = Q->n_q;
     const uint32_t nb = T->n_blocks, nc = u->n_contigs;
-    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)(nb ? nb : 1) * sizeof *bl);
-    uint64_t *ws = (uint64_t *)malloc((size_t)(nb ? nb : 1) * 8);
-    uint32_t *bc = (uint32_t *)malloc((size_t)(nb ? nb : 1) * 4);
+    cbc_dec_block_desc *bl; uint64_t *ws; uint32_t *bc;
+    if (cli_gather(u, T->blocks, nb, &bl, &ws, &bc)) return 1;
     uint64_t *sum = (uint64_t *)calloc((size_t)(nq ? nq : 1), 8), *csum = (uint64_t *)malloc((size_t)(nq ? nq : 1) * 8);
     uint32_t *cov = (uint32_t *)calloc((size_t)(nq ? nq : 1), 4), *ccov = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 4);
     uint32_t *qq = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 8), *qi = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 4);
@@ -515,8 +493,7 @@ static int bedcov_run(const char *in, const char *out, const char *ref, int devi
     /* the extra columns, gathered and scattered per contig like sum and covered */
     uint32_t *xthr = (uint32_t *)calloc((size_t)(nq ? nq : 1) * (n_thr ? n_thr : 1), 4), *cthr = (uint32_t *)malloc((size_t)(nq ? nq : 1) * (n_thr ? n_thr : 1) * 4);
     uint32_t *xrd = (uint32_t *)calloc((size_t)(nq ? nq : 1), 4), *crd = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 4);
-    if (!bl || !ws || !bc || !sum || !csum || !cov || !ccov || !qq || !qi || !cfirst || !xthr || !cthr || !xrd || !crd) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    for (uint32_t k = 0; k < nb; k++) { const uint32_t b = T->blocks[k]; bl[k] = u->blocks[b]; ws[k] = u->window_start[b]; bc[k] = u->block_contig[b]; }
+    if (!sum || !csum || !cov || !ccov || !qq || !qi || !cfirst || !xthr || !cthr || !xrd || !crd) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
     /* the queries that hold a position, grouped per contig (a counting sort: the order inside a contig stays the input's) */
     for (uint64_t i = 0; i < nq; i++) if (Q->q[i].contig != CBC_QUERY_UNKNOWN && Q->q[i].end0 > Q->q[i].start0) cfirst[Q->q[i].contig + 2]++;
     for (uint32_t c = 0; c < nc; c++) cfirst[c + 2] += cfirst[c + 1];
@@ -526,46 +503,31 @@ static int bedcov_run(const char *in, const char *out, const char *ref, int devi
         const uint64_t at = cfirst[x->contig + 1]++;
         qq[2 * at] = x->slot; qq[2 * at + 1] = x->end + 1u - x->beg; qi[at] = (uint32_t)i;
     }                                                    /* now cfirst[c] .. cfirst[c + 1]: contig c's part */
-    const double t1 = now2();
-    double t_init = 0, t_dev = 0;
-    cbc_gpu_ctx *ctx = NULL;
+    r.t1 = now2();
     uint64_t reads = 0;
     uint32_t blocks_used = 0;
-    float ms[7] = { 0, 0, 0, 0, 0, 0, 0 }, xms[5] = { 0, 0, 0, 0, 0 };
-    const cbc_gpu_targets gt = { (const uint32_t *)T->iv, NULL, T->n_iv, T->smax };
+    float ms[7] = { 0, 0, 0, 0, 0, 0, 0 }, xms[5] = { 0, 0, 0, 0, 0 }, m[7], xm[5];
     for (uint32_t c = 0; c < nc && nb; c++) {
         const uint32_t k0 = T->contig_blk_first[c], kn = T->contig_blk_count[c];
         const uint64_t q0 = cfirst[c], qn = cfirst[c + 1] - cfirst[c];
         if (!kn || !qn || !T->contig_count[c]) continue;   /* no block can hold a read of the contig's intervals: zeros */
-        const double a = now2();
-        if (!ctx) {
-            rc = cbc_gpu_init(device, &ctx);
-            if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
-            if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-            t_init = now2() - a;
-        }
+        if (cli_device(&r)) return 1;
         const double b = now2();
-        cbc_gpu_targets g = gt;
-        g.block_iv = T->block_iv + 2 * (size_t)k0;
+        const cbc_gpu_targets g = { (const uint32_t *)T->iv, T->block_iv + 2 * (size_t)k0, T->n_iv, T->smax };
         uint64_t nr = 0;
         if (ext)
-            rc = cbc_gpu_decode_coverage_ext(ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
+            rc = cbc_gpu_decode_coverage_ext(r.ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
                                              u->contig_name_off, u->n_contigs, &g, T->contig_first[c], T->contig_count[c], qq + 2 * q0,
                                              (uint32_t)qn, exclude, min_depth, csum + q0, ccov + q0, &nr, NULL, thr, n_thr,
                                              cthr + q0 * n_thr, count_reads ? crd + q0 : NULL);
         else
-            rc = cbc_gpu_decode_coverage(ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
+            rc = cbc_gpu_decode_coverage(r.ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
                                          u->contig_name_off, u->n_contigs, &g, T->contig_first[c], T->contig_count[c], qq + 2 * q0,
                                          (uint32_t)qn, exclude, min_depth, csum + q0, ccov + q0, &nr, NULL);
-        if (rc) { fprintf(stderr, "cbc: coverage failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-        t_dev += now2() - b;
-        if (verbose && ext) {
-            float m7[7], m5[5];
-            if (cbc_gpu_last_coverage_ext_ms(ctx, m7, m5) == 0) { for (int i = 0; i < 7; i++) ms[i] += m7[i]; for (int i = 0; i < 5; i++) xms[i] += m5[i]; }
-        } else if (verbose) {
-            float m7[7];
-            if (cbc_gpu_last_coverage_ms(ctx, &m7[0], &m7[1], &m7[2], &m7[3], &m7[4], &m7[5], &m7[6]) == 0) for (int i = 0; i < 7; i++) ms[i] += m7[i];
-        }
+        if (rc) { fprintf(stderr, "cbc: coverage failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
+        r.t_dev += now2() - b;
+        if (verbose && ext) { if (cbc_gpu_last_coverage_ext_ms(r.ctx, m, xm) == 0) { add_ms(ms, m, 7); add_ms(xms, xm, 5); } }
+        else if (verbose && cbc_gpu_last_coverage_ms(r.ctx, &m[0], &m[1], &m[2], &m[3], &m[4], &m[5], &m[6]) == 0) add_ms(ms, m, 7);
         for (uint64_t k = q0; k < q0 + qn; k++) { sum[qi[k]] = csum[k]; cov[qi[k]] = ccov[k]; }
         for (uint64_t k = q0; ext && k < q0 + qn; k++) {
             for (uint32_t t = 0; t < n_thr; t++) xthr[(size_t)qi[k] * n_thr + t] = cthr[k * n_thr + t];
@@ -573,52 +535,38 @@ static int bedcov_run(const char *in, const char *out, const char *ref, int devi
         }
         reads += nr; blocks_used += kn;
     }
-    if (ctx) cbc_gpu_shutdown(ctx);
     const double t2 = now2();
     FILE *fo = fopen(out, "wb");
-    if (!fo) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    if (!fo) return cannot_write(out);
     for (uint64_t i = 0; i < nq; i++) {
         const cbc_query *x = &Q->q[i];
         char mean[32];
         (void)cbc_coverage_mean(sum[i], x->end0 - x->start0, mean);
-        const char *nm = x->contig == CBC_QUERY_UNKNOWN ? bed + x->name_off : u->names + u->contig_name_off[x->contig];
+        const char *nm = x->contig == CBC_QUERY_UNKNOWN ? r.bed + x->name_off : u->names + u->contig_name_off[x->contig];
         const int nl = x->contig == CBC_QUERY_UNKNOWN ? (int)x->name_len : (int)strlen(nm);
         int bad = fprintf(fo, "%.*s\t%llu\t%llu\t%llu\t%u\t%s", nl, nm, (unsigned long long)x->start0, (unsigned long long)x->end0,
                           (unsigned long long)sum[i], cov[i], mean) < 0;
         for (uint32_t t = 0; t < n_thr && !bad; t++) bad = fprintf(fo, "\t%u", xthr[(size_t)i * n_thr + t]) < 0;
         if (count_reads && !bad) bad = fprintf(fo, "\t%u", xrd[i]) < 0;
-        if (bad || fputc('\n', fo) == EOF) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+        if (bad || fputc('\n', fo) == EOF) return cannot_write(out);
     }
-    if (fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    if (fclose(fo) != 0) return cannot_write(out);
     printf("coverage of %llu queries from %llu reads in %u of %u blocks\n", (unsigned long long)nq, (unsigned long long)reads, blocks_used, u->n_blocks);
     if (verbose) {
         printf("bedcov: %llu queries, %u intervals after merging, %u blocks selected, %llu BED lines selected nothing, window %llu, min depth %u, exclude flags 0x%x\n",
                (unsigned long long)nq, T->n_iv, nb, (unsigned long long)T->bed_unselected, (unsigned long long)window, min_depth, exclude);
         printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + coverage %.3f s, format + write %.3f s\n",
-               t1 - t0, t_init, t_dev, now2() - t2);
-        if (ctx) printf("kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, weights %.3f ms, weight scans %.3f ms, prefixes %.3f ms, lookup %.3f ms\n",
-                        ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6]);
-        if (ctx && ext) printf("kernels: start points %.3f ms, threshold weights %.3f ms, their scans %.3f ms, their prefixes %.3f ms, threshold + read lookup %.3f ms\n",
-                               xms[0], xms[1], xms[2], xms[3], xms[4]);
+               r.t1 - r.t0, r.t_init, r.t_dev, now2() - t2);
+        if (r.used) printf("kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, weights %.3f ms, weight scans %.3f ms, prefixes %.3f ms, lookup %.3f ms\n",
+                           ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6]);
+        if (r.used && ext) printf("kernels: start points %.3f ms, threshold weights %.3f ms, their scans %.3f ms, their prefixes %.3f ms, threshold + read lookup %.3f ms\n",
+                                  xms[0], xms[1], xms[2], xms[3], xms[4]);
     }
     free(xthr); free(cthr); free(xrd); free(crd);
-    free(bl); free(ws); free(bc); free(sum); free(csum); free(cov); free(ccov); free(qq); free(qi); free(cfirst); free(bed); free(blob);
+    free(bl); free(ws); free(bc); free(sum); free(csum); free(cov); free(ccov); free(qq); free(qi); free(cfirst);
     cbc_queries_free(Q);
-    cbc_unpack_plan_free(u);
+    cli_close(&r);
     return 0;
-}
-
-int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
-                              const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose)
-{
-    return bedcov_run(in, out, ref, device, regions, n_regions, bed_path, window, min_depth, exclude, verbose, NULL, 0u, 0);
-}
-
-int cbc_cli_decompress_bedcov_ext(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
-                                  const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose,
-                                  const uint32_t *thr, uint32_t n_thr, int count_reads)
-{
-    return bedcov_run(in, out, ref, device, regions, n_regions, bed_path, window, min_depth, exclude, verbose, thr, n_thr, count_reads);
 }
 
 /* `cbc -d|-x ... --depth-hist [--region A ...] [--regions-file FILE] [--hist-max M]`: per contig how many positions have each
@@ -642,45 +590,28 @@ static int hist_line(FILE *fo, const char *name, uint64_t depth, uint64_t bases,
 int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                             const char *bed_path, uint32_t max_depth, uint32_t exclude, int verbose)
 {
-    const double t0 = now2();
-    size_t blob_len = 0, fa_len = 0, bed_len = 0;
-    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
-    if (!blob || !fa) return 1;
-    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
-        fprintf(stderr, "cbc: --depth-hist needs a block container; %s is a single-stream (--compat) file, which has no block index\n", in);
-        return 1;
-    }
-    char *bed = NULL;
-    if (bed_path && !(bed = slurp2(bed_path, &bed_len))) return 1;
+    cli_run r;
+    if (cli_open(&r, in, ref, bed_path, device, "--depth-hist", "has no block index")) return 1;
+    const cbc_unpack_plan *u = r.u;
     char err[512];
-    cbc_unpack_plan *u = NULL;
-    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
-    free(fa);
-    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
     /* the intervals and their blocks: the target set of the regions, or every contig whole (the query list's own set) */
     cbc_targets *T = NULL;
     cbc_queries *Q = NULL;
-    if (n_regions || bed_path) rc = cbc_unpack_targets(u, regions, n_regions, bed, bed_len, &T, err, sizeof err);
+    int rc;
+    if (n_regions || bed_path) rc = cbc_unpack_targets(u, regions, n_regions, r.bed, r.bed_len, &T, err, sizeof err);
     else { rc = cbc_unpack_queries(u, NULL, 0, NULL, 0, 0, &Q, err, sizeof err); if (!rc) T = Q->targets; }
-    free(bed);
     if (rc) { fprintf(stderr, "cbc: --depth-hist: %s\n", rc == CBC_E_INPUT && err[0] ? err : "target selection failed"); return 1; }
     const uint32_t nb = T->n_blocks, nc = u->n_contigs;
-    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)(nb ? nb : 1) * sizeof *bl);
-    uint64_t *ws = (uint64_t *)malloc((size_t)(nb ? nb : 1) * 8);
-    uint32_t *bc = (uint32_t *)malloc((size_t)(nb ? nb : 1) * 4);
-    if (!bl || !ws || !bc) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    for (uint32_t k = 0; k < nb; k++) { const uint32_t b = T->blocks[k]; bl[k] = u->blocks[b]; ws[k] = u->window_start[b]; bc[k] = u->block_contig[b]; }
-    const double t1 = now2();
-    double t_init = 0, t_dev = 0;
+    cbc_dec_block_desc *bl; uint64_t *ws; uint32_t *bc;
+    if (cli_gather(u, T->blocks, nb, &bl, &ws, &bc)) return 1;
+    r.t1 = now2();
     FILE *fo = fopen(out, "wb");
-    if (!fo) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
-    cbc_gpu_ctx *ctx = NULL;
+    if (!fo) return cannot_write(out);
     hist_bin *all = NULL;                                    /* every contig's bins, for the genome block */
     size_t n_all = 0, cap_all = 0;
     uint64_t reads = 0, gsize = 0;
     uint32_t blocks_used = 0, listed = 0;
-    float ms[5] = { 0, 0, 0, 0, 0 };
-    const cbc_gpu_targets gt = { (const uint32_t *)T->iv, NULL, T->n_iv, T->smax };
+    float ms[5] = { 0, 0, 0, 0, 0 }, m[5];
     for (uint32_t c = 0; c < nc && c < T->n_contigs; c++) {
         if (!T->contig_count[c]) continue;                  /* no interval on the contig: not listed */
         const uint32_t k0 = T->contig_blk_first[c], kn = T->contig_blk_count[c];
@@ -688,13 +619,7 @@ int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, in
         const char *nm = u->names + u->contig_name_off[c];
         uint32_t n_bins = 0, *bd = NULL, *bb = NULL;
         if (kn) {                                           /* else no block can hold a read of the intervals: depth 0 everywhere */
-            const double a = now2();
-            if (!ctx) {
-                rc = cbc_gpu_init(device, &ctx);
-                if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
-                if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-                t_init = now2() - a;
-            }
+            if (cli_device(&r)) return 1;
             const double b = now2();
             uint64_t k_reads = 0, nr = 0;
             for (uint32_t k = 0; k < kn; k++) k_reads += bl[k0 + k].n_reads;
@@ -702,17 +627,13 @@ int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, in
             const uint32_t cap = (uint32_t)(k_reads < fold ? k_reads : fold);   /* a depth cannot pass the reads */
             bd = (uint32_t *)malloc((size_t)(cap ? cap : 1) * 4); bb = (uint32_t *)malloc((size_t)(cap ? cap : 1) * 4);
             if (!bd || !bb) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-            cbc_gpu_targets g = gt;
-            g.block_iv = T->block_iv + 2 * (size_t)k0;
-            rc = cbc_gpu_decode_depth_hist(ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
+            const cbc_gpu_targets g = { (const uint32_t *)T->iv, T->block_iv + 2 * (size_t)k0, T->n_iv, T->smax };
+            rc = cbc_gpu_decode_depth_hist(r.ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
                                            u->contig_name_off, u->n_contigs, &g, T->contig_first[c], T->contig_count[c], exclude, max_depth,
                                            bd, bb, cap, &n_bins, &nr, NULL);
-            if (rc) { fprintf(stderr, "cbc: depth histogram failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-            t_dev += now2() - b;
-            if (verbose) {
-                float m5[5];
-                if (cbc_gpu_last_hist_ms(ctx, &m5[0], &m5[1], &m5[2], &m5[3], &m5[4]) == 0) for (int i = 0; i < 5; i++) ms[i] += m5[i];
-            }
+            if (rc) { fprintf(stderr, "cbc: depth histogram failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
+            r.t_dev += now2() - b;
+            if (verbose && cbc_gpu_last_hist_ms(r.ctx, &m[0], &m[1], &m[2], &m[3], &m[4]) == 0) add_ms(ms, m, 5);
             reads += nr; blocks_used += kn;
         }
         uint64_t covered = 0;
@@ -726,34 +647,33 @@ int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, in
         int bad = 0;
         if (size - covered) { bad |= hist_line(fo, nm, 0, size - covered, size); all[n_all].depth = 0; all[n_all++].bases = size - covered; }
         for (uint32_t i = 0; i < n_bins; i++) { bad |= hist_line(fo, nm, bd[i], bb[i], size); all[n_all].depth = bd[i]; all[n_all++].bases = bb[i]; }
-        if (bad) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+        if (bad) return cannot_write(out);
         free(bd); free(bb);
         gsize += size; listed++;
     }
-    if (ctx) cbc_gpu_shutdown(ctx);
     if (listed) {                                            /* the genome block: the bins summed over the listed contigs, 64 bits */
         qsort(all, n_all, sizeof *all, hist_bin_cmp);
         for (size_t i = 0; i < n_all; ) {
             uint64_t bases = 0;
             size_t j = i;
             for (; j < n_all && all[j].depth == all[i].depth; j++) bases += all[j].bases;
-            if (hist_line(fo, "genome", all[i].depth, bases, gsize)) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+            if (hist_line(fo, "genome", all[i].depth, bases, gsize)) return cannot_write(out);
             i = j;
         }
     }
-    if (fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    if (fclose(fo) != 0) return cannot_write(out);
     printf("depth histogram of %u contigs, %llu positions, from %llu reads in %u of %u blocks\n", listed, (unsigned long long)gsize,
            (unsigned long long)reads, blocks_used, u->n_blocks);
     if (verbose) {
         printf("depth-hist: %u intervals after merging, %u blocks selected, %llu BED lines selected nothing, fold at %u, exclude flags 0x%x\n",
                T->n_iv, nb, (unsigned long long)T->bed_unselected, max_depth, exclude);
-        printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + histogram + write %.3f s\n", t1 - t0, t_init, t_dev);
-        if (ctx) printf("kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, zero + accumulate %.3f ms, bin compaction %.3f ms\n",
-                        ms[0], ms[1], ms[2], ms[3], ms[4]);
+        printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + histogram + write %.3f s\n", r.t1 - r.t0, r.t_init, r.t_dev);
+        if (r.used) printf("kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, zero + accumulate %.3f ms, bin compaction %.3f ms\n",
+                           ms[0], ms[1], ms[2], ms[3], ms[4]);
     }
-    free(all); free(bl); free(ws); free(bc); free(blob);
+    free(all); free(bl); free(ws); free(bc);
     if (Q) cbc_queries_free(Q); else cbc_targets_free(T);
-    cbc_unpack_plan_free(u);
+    cli_close(&r);
     return 0;
 }
 
@@ -764,69 +684,46 @@ int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, in
 int cbc_cli_decompress_stats(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                              const char *bed_path, uint32_t exclude, int verbose)
 {
-    const double t0 = now2();
-    size_t blob_len = 0, fa_len = 0, bed_len = 0;
-    char *blob = slurp2(in, &blob_len), *fa = slurp2(ref, &fa_len);
-    if (!blob || !fa) return 1;
-    if (blob_len < 4 || memcmp(blob, "CBCB", 4) != 0) {
-        fprintf(stderr, "cbc: --stats needs a block container; %s is a single-stream (--compat) file, which has no block index\n", in);
-        return 1;
-    }
-    char *bed = NULL;
-    if (bed_path && !(bed = slurp2(bed_path, &bed_len))) return 1;
+    cli_run r;
+    if (cli_open(&r, in, ref, bed_path, device, "--stats", "has no block index")) return 1;
+    const cbc_unpack_plan *u = r.u;
     char err[512];
-    cbc_unpack_plan *u = NULL;
-    int rc = cbc_unpack_plan_create((const uint8_t *)blob, blob_len, fa, fa_len, &u, err, sizeof err);
-    free(fa);
-    if (rc) { fprintf(stderr, "cbc: %s\n", err); return 1; }
     /* what SAM output refuses, the statistics refuse: a long-read container, names and lengths the coordinates cannot carry */
     if (cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) < 0) { fprintf(stderr, "cbc: --stats: %s\n", err[0] ? err : "the contig table is not usable"); return 1; }
-    cbc_targets *T = NULL;
-    const int tg = n_regions || bed_path;
-    if (tg) {
-        rc = cbc_unpack_targets(u, regions, n_regions, bed, bed_len, &T, err, sizeof err);
-        if (rc) { fprintf(stderr, "cbc: --stats: %s\n", rc == CBC_E_INPUT && err[0] ? err : "target selection failed"); return 1; }
-    }
-    free(bed);
-    const uint32_t nb = tg ? T->n_blocks : u->n_blocks;
-    cbc_dec_block_desc *bl = (cbc_dec_block_desc *)malloc((size_t)(nb ? nb : 1) * sizeof *bl);
-    uint64_t *ws = (uint64_t *)malloc((size_t)(nb ? nb : 1) * 8);
+    cbc_targets *T = NULL;                                   /* NULL: the whole file */
+    int rc = n_regions || bed_path ? cbc_unpack_targets(u, regions, n_regions, r.bed, r.bed_len, &T, err, sizeof err) : 0;
+    if (rc) { fprintf(stderr, "cbc: --stats: %s\n", rc == CBC_E_INPUT && err[0] ? err : "target selection failed"); return 1; }
+    const uint32_t nb = T ? T->n_blocks : u->n_blocks;
+    cbc_dec_block_desc *bl; uint64_t *ws;
     cbc_gpu_stats *st = (cbc_gpu_stats *)calloc(1, sizeof *st);
     const uint64_t cap = cbc_stats_text_cap();
     char *text = (char *)malloc((size_t)cap);
-    if (!bl || !ws || !st || !text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    for (uint32_t k = 0; k < nb; k++) { const uint32_t b = tg ? T->blocks[k] : k; bl[k] = u->blocks[b]; ws[k] = u->window_start[b]; }
-    const double t1 = now2();
-    double t_init = 0, t_dev = 0;
+    if (!st || !text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    if (cli_gather(u, T ? T->blocks : NULL, nb, &bl, &ws, NULL)) return 1;
+    r.t1 = now2();
     float ms[2] = { 0, 0 };
-    cbc_gpu_ctx *ctx = NULL;
     if (nb) {                                                /* else nothing runs: all-zero tables */
-        const double a = now2();
-        rc = cbc_gpu_init(device, &ctx);
-        if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
-        if (cbc_gpu_upload_reference(ctx, u->ref, u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-        t_init = now2() - a;
+        if (cli_device(&r)) return 1;
         const double b = now2();
-        const cbc_gpu_targets gt = { tg ? (const uint32_t *)T->iv : NULL, tg ? T->block_iv : NULL, tg ? T->n_iv : 0u, tg ? T->smax : 0u };
-        rc = cbc_gpu_decode_stats(ctx, u->payloads, u->payload_bytes, bl, nb, &u->caps, ws, tg ? &gt : NULL, exclude, st, NULL);
-        if (rc) { fprintf(stderr, "cbc: statistics failed: %s\n", cbc_gpu_last_error(ctx)); return 1; }
-        t_dev = now2() - b;
-        if (verbose) (void)cbc_gpu_last_stats_ms(ctx, &ms[0], &ms[1]);
-        cbc_gpu_shutdown(ctx);
+        const cbc_gpu_targets gt = { T ? (const uint32_t *)T->iv : NULL, T ? T->block_iv : NULL, T ? T->n_iv : 0u, T ? T->smax : 0u };
+        rc = cbc_gpu_decode_stats(r.ctx, u->payloads, u->payload_bytes, bl, nb, &u->caps, ws, T ? &gt : NULL, exclude, st, NULL);
+        if (rc) { fprintf(stderr, "cbc: statistics failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
+        r.t_dev = now2() - b;
+        if (verbose) (void)cbc_gpu_last_stats_ms(r.ctx, &ms[0], &ms[1]);
     }
     const int64_t n = cbc_stats_text(st, text, cap);
     FILE *fo = n < 0 ? NULL : fopen(out, "wb");
-    if (!fo || fwrite(text, 1, (size_t)n, fo) != (size_t)n || fclose(fo) != 0) { fprintf(stderr, "cbc: cannot write %s\n", out); return 1; }
+    if (!fo || fwrite(text, 1, (size_t)n, fo) != (size_t)n || fclose(fo) != 0) return cannot_write(out);
     printf("statistics of %llu reads (%llu excluded) from %u of %u blocks\n", (unsigned long long)st->reads, (unsigned long long)st->excluded, nb, u->n_blocks);
     if (verbose) {
-        if (tg) printf("stats: %u intervals after merging, %u blocks selected, %llu BED lines selected nothing, exclude flags 0x%x\n",
-                       T->n_iv, nb, (unsigned long long)T->bed_unselected, exclude);
+        if (T) printf("stats: %u intervals after merging, %u blocks selected, %llu BED lines selected nothing, exclude flags 0x%x\n",
+                      T->n_iv, nb, (unsigned long long)T->bed_unselected, exclude);
         else printf("stats: the whole file, exclude flags 0x%x\n", exclude);
-        printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + statistics %.3f s\n", t1 - t0, t_init, t_dev);
-        if (ctx) printf("kernels: decode %.3f ms, statistics %.3f ms\n", ms[0], ms[1]);
+        printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + statistics %.3f s\n", r.t1 - r.t0, r.t_init, r.t_dev);
+        if (r.used) printf("kernels: decode %.3f ms, statistics %.3f ms\n", ms[0], ms[1]);
     }
-    free(text); free(st); free(bl); free(ws); free(blob);
+    free(text); free(st); free(bl); free(ws);
     if (T) cbc_targets_free(T);
-    cbc_unpack_plan_free(u);
+    cli_close(&r);
     return 0;
 }

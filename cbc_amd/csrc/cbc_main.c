@@ -33,6 +33,7 @@
 #include <sys/stat.h>
 #include <pthread.h>
 #include "../../include/cbc_host.h"
+#include "cbc_cli.h"
 
 static void usage(const char *p)
 {
@@ -103,6 +104,26 @@ static int is_number(const char *s)
     char *e = NULL;
     (void)strtod(s, &e);
     return e && *e == 0;
+}
+
+/* the value of --depth-exclude-flags / --stats-exclude-flags */
+static int parse_flag_mask(const char *opt, const char *v, uint32_t *mask)
+{
+    char *e = NULL;
+    const unsigned long x = strtoul(v, &e, 0);
+    if (!e || *e || e == v || x > 0xfffful) { fprintf(stderr, "cbc: %s wants a FLAG mask in 0..65535 (decimal, 0x.. or 0..)\n", opt); return 0; }
+    *mask = (uint32_t)x;
+    return 1;
+}
+
+/* the value of --window, --min-depth, --hist-max: decimal digits, at most 18 of them, 1 .. max; wants: the message's words for that */
+static int parse_count(const char *opt, const char *v, uint64_t max, const char *wants, uint64_t *n)
+{
+    char *e = NULL;
+    const unsigned long long x = strtoull(v, &e, 10);
+    if (v[0] < '0' || v[0] > '9' || !e || *e || strlen(v) > 18 || x < 1 || x > max) { fprintf(stderr, "cbc: %s wants %s\n", opt, wants); return 0; }
+    *n = x;
+    return 1;
 }
 
 /* ---- several devices: whole contigs are dealt to the devices (cbc_assign_contigs), one
@@ -444,24 +465,6 @@ static int do_compress(const char *in, const char *out, const char *ref, uint32_
     return 0;
 }
 
-int cbc_cli_decompress(const char *in, const char *out, const char *ref, const int *devs, int ndev);   /* cbc_cli_unpack.c */
-int cbc_cli_decompress_region(const char *in, const char *out, const char *ref, int device, const char *region, int verbose);
-int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int verbose);
-int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude, int verbose);
-
-int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
-                               const char *bed_path, uint32_t output, uint32_t exclude, int verbose);
-int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
-                              const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose);
-int cbc_cli_decompress_bedcov_ext(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
-                                  const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose,
-                                  const uint32_t *thr, uint32_t n_thr, int count_reads);
-int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
-                            const char *bed_path, uint32_t max_depth, uint32_t exclude, int verbose);
-
-int cbc_cli_decompress_stats(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
-                             const char *bed_path, uint32_t exclude, int verbose);
-
 int main(int argc, char **argv)
 {
     const char *files[3] = { 0, 0, 0 };
@@ -469,12 +472,12 @@ int main(int argc, char **argv)
     int devs[CBC_MAX_DEVICES] = { 0 }, ndev = 0;
     uint32_t block_reads = 0;
     const char *region = NULL, *regions_file = NULL;
-    const char **regions = (const char **)calloc((size_t)argc, sizeof(char *));   /* every --region, in order */
+    const char *regions[argc];                                   /* every --region, in order */
     uint32_t n_regions = 0;
     int sam_out = 0, depth_out = 0, depth_excl_given = 0;
     uint32_t depth_exclude = 0;
     int bedcov = 0, window_given = 0, min_depth_given = 0;
-    uint64_t cov_window = 0;
+    uint64_t cov_window = 0, n = 0;
     uint32_t cov_min_depth = 1;
     int count_reads = 0, thr_given = 0;
     uint32_t thr[8], n_thr = 0;
@@ -500,27 +503,16 @@ int main(int argc, char **argv)
         }
         if (!strcmp(a, "--threads") && i + 1 < argc) { threads = atoi(argv[++i]); if (threads < 0) threads = 0; continue; }
         if (!strcmp(a, "--verbose")) { verbose = 1; continue; }
-        if (!strcmp(a, "--region") && i + 1 < argc) { region = argv[++i]; if (regions) regions[n_regions++] = region; continue; }
+        if (!strcmp(a, "--region") && i + 1 < argc) { region = regions[n_regions++] = argv[++i]; continue; }
         if (!strcmp(a, "--regions-file") && i + 1 < argc) { regions_file = argv[++i]; continue; }
         if (!strcmp(a, "--sam")) { sam_out = 1; continue; }
         if (!strcmp(a, "--depth")) { depth_out = 1; continue; }
-        if (!strcmp(a, "--depth-exclude-flags") && i + 1 < argc) {
-            char *e = NULL;
-            const unsigned long v = strtoul(argv[++i], &e, 0);
-            if (!e || *e || e == argv[i] || v > 0xfffful) { fprintf(stderr, "cbc: --depth-exclude-flags wants a FLAG mask in 0..65535 (decimal, 0x.. or 0..)\n"); return 1; }
-            depth_exclude = (uint32_t)v; depth_excl_given = 1; continue;
-        }
+        if (!strcmp(a, "--depth-exclude-flags") && i + 1 < argc) { if (!parse_flag_mask(a, argv[++i], &depth_exclude)) return 1; depth_excl_given = 1; continue; }
+        if (!strcmp(a, "--stats-exclude-flags") && i + 1 < argc) { if (!parse_flag_mask(a, argv[++i], &stats_exclude)) return 1; stats_excl_given = 1; continue; }
         if (!strcmp(a, "--bedcov")) { bedcov = 1; continue; }
-        if ((!strcmp(a, "--window") || !strcmp(a, "--min-depth")) && i + 1 < argc) {
-            const int w = a[2] == 'w';
-            char *e = NULL;
-            const char *v = argv[++i];
-            const unsigned long long x = strtoull(v, &e, 10);
-            if (v[0] < '0' || v[0] > '9' || !e || *e || strlen(v) > 18 || x < 1 || (!w && x > 0xffffffffull)) {
-                fprintf(stderr, w ? "cbc: --window wants a number of bases, 1 or more\n" : "cbc: --min-depth wants a depth in 1..4294967295\n"); return 1; }
-            if (w) { cov_window = x; window_given = 1; } else { cov_min_depth = (uint32_t)x; min_depth_given = 1; }
-            continue;
-        }
+        if (!strcmp(a, "--window") && i + 1 < argc) { if (!parse_count(a, argv[++i], UINT64_MAX, "a number of bases, 1 or more", &cov_window)) return 1; window_given = 1; continue; }
+        if (!strcmp(a, "--min-depth") && i + 1 < argc) { if (!parse_count(a, argv[++i], 0xffffffffull, "a depth in 1..4294967295", &n)) return 1; cov_min_depth = (uint32_t)n; min_depth_given = 1; continue; }
+        if (!strcmp(a, "--hist-max") && i + 1 < argc) { if (!parse_count(a, argv[++i], 0xffffffffull, "a depth in 1..4294967295", &n)) return 1; hist_max = (uint32_t)n; hist_max_given = 1; continue; }
         if (!strcmp(a, "--count-reads")) { count_reads = 1; continue; }
         if (!strcmp(a, "--thresholds") && i + 1 < argc) {         /* T1,T2,...: 1 to 8 decimal depths, strictly ascending */
             const char *v = argv[++i];
@@ -537,21 +529,7 @@ int main(int argc, char **argv)
             thr_given = 1; continue;
         }
         if (!strcmp(a, "--depth-hist")) { depth_hist = 1; continue; }
-        if (!strcmp(a, "--hist-max") && i + 1 < argc) {
-            char *e = NULL;
-            const char *v = argv[++i];
-            const unsigned long long x = strtoull(v, &e, 10);
-            if (v[0] < '0' || v[0] > '9' || !e || *e || strlen(v) > 18 || x < 1 || x > 0xffffffffull) {
-                fprintf(stderr, "cbc: --hist-max wants a depth in 1..4294967295\n"); return 1; }
-            hist_max = (uint32_t)x; hist_max_given = 1; continue;
-        }
         if (!strcmp(a, "--stats")) { stats_out = 1; continue; }
-        if (!strcmp(a, "--stats-exclude-flags") && i + 1 < argc) {
-            char *e = NULL;
-            const unsigned long v = strtoul(argv[++i], &e, 0);
-            if (!e || *e || e == argv[i] || v > 0xfffful) { fprintf(stderr, "cbc: --stats-exclude-flags wants a FLAG mask in 0..65535 (decimal, 0x.. or 0..)\n"); return 1; }
-            stats_exclude = (uint32_t)v; stats_excl_given = 1; continue;
-        }
         if (!strcmp(a, "--compat")) { compat = 1; continue; }
         if (!strcmp(a, "--long")) { long_reads = 1; continue; }
         if (!strcmp(a, "--device-parse")) { device_parse = 1; continue; }
@@ -590,39 +568,33 @@ int main(int argc, char **argv)
         fprintf(stderr, "cbc: user@host:file download mode (src/main.c:306-326) is out of scope\n");
         return 1;
     }
-    if (!regions) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    if (regions_file && mode != 2) { fprintf(stderr, "cbc: --regions-file applies to decompression (-d / -x)\n"); return 1; }
-    if (regions_file && ndev > 1) { fprintf(stderr, "cbc: --regions-file decodes on one device; give a single --devices ordinal\n"); return 1; }
-    if (region && mode != 2) { fprintf(stderr, "cbc: --region applies to decompression (-d / -x)\n"); return 1; }
-    if (region && ndev > 1) { fprintf(stderr, "cbc: --region decodes on one device; give a single --devices ordinal\n"); return 1; }
-    if (sam_out && mode != 2) { fprintf(stderr, "cbc: --sam applies to decompression (-d / -x)\n"); return 1; }
-    if (sam_out && ndev > 1) { fprintf(stderr, "cbc: --sam decodes on one device; give a single --devices ordinal\n"); return 1; }
-    if (depth_out && mode != 2) { fprintf(stderr, "cbc: --depth applies to decompression (-d / -x)\n"); return 1; }
-    if (depth_out && sam_out) { fprintf(stderr, "cbc: --depth and --sam are two different outputs; give one of them\n"); return 1; }
-    if (depth_out && ndev > 1) { fprintf(stderr, "cbc: --depth decodes on one device; give a single --devices ordinal\n"); return 1; }
-    if ((window_given || min_depth_given) && !bedcov) { fprintf(stderr, "cbc: %s applies to --bedcov\n", window_given ? "--window" : "--min-depth"); return 1; }
-    if ((thr_given || count_reads) && !bedcov) { fprintf(stderr, "cbc: %s applies to --bedcov\n", thr_given ? "--thresholds" : "--count-reads"); return 1; }
-    if (bedcov && mode != 2) { fprintf(stderr, "cbc: --bedcov applies to decompression (-d / -x)\n"); return 1; }
-    if (bedcov && (sam_out || depth_out)) { fprintf(stderr, "cbc: --bedcov, --depth and --sam are different outputs; give one of them\n"); return 1; }
-    if (bedcov && ndev > 1) { fprintf(stderr, "cbc: --bedcov decodes on one device; give a single --devices ordinal\n"); return 1; }
-    if (hist_max_given && !depth_hist) { fprintf(stderr, "cbc: --hist-max applies to --depth-hist\n"); return 1; }
-    if (depth_hist && mode != 2) { fprintf(stderr, "cbc: --depth-hist applies to decompression (-d / -x)\n"); return 1; }
-    if (depth_hist && (sam_out || depth_out || bedcov)) { fprintf(stderr, "cbc: --depth-hist, --bedcov, --depth and --sam are different outputs; give one of them\n"); return 1; }
-    if (depth_hist && ndev > 1) { fprintf(stderr, "cbc: --depth-hist decodes on one device; give a single --devices ordinal\n"); return 1; }
-    if (stats_excl_given && !stats_out) { fprintf(stderr, "cbc: --stats-exclude-flags applies to --stats\n"); return 1; }
-    if (stats_out && mode != 2) { fprintf(stderr, "cbc: --stats applies to decompression (-d / -x)\n"); return 1; }
-    if (stats_out && (sam_out || depth_out || bedcov || depth_hist)) { fprintf(stderr, "cbc: --stats, --depth-hist, --bedcov, --depth and --sam are different outputs; give one of them\n"); return 1; }
-    if (stats_out && ndev > 1) { fprintf(stderr, "cbc: --stats decodes on one device; give a single --devices ordinal\n"); return 1; }
+    /* the selection and output options, in the order their refusals are tried: each applies to decompression, clashes with
+     * every output listed before it (said in its own sentence) and decodes on one device; `owned` is the first given option that
+     * means something only with this one */
+    const struct { const char *name; int given; const char *clash, *owned; } opts[] = {
+        { "--regions-file", regions_file != NULL, NULL, NULL },
+        { "--region", region != NULL, NULL, NULL },
+        { "--sam", sam_out, NULL, NULL },
+        { "--depth", depth_out, "--depth and --sam are two different outputs", NULL },
+        { "--bedcov", bedcov, "--bedcov, --depth and --sam are different outputs",
+          window_given ? "--window" : min_depth_given ? "--min-depth" : thr_given ? "--thresholds" : count_reads ? "--count-reads" : NULL },
+        { "--depth-hist", depth_hist, "--depth-hist, --bedcov, --depth and --sam are different outputs", hist_max_given ? "--hist-max" : NULL },
+        { "--stats", stats_out, "--stats, --depth-hist, --bedcov, --depth and --sam are different outputs", stats_excl_given ? "--stats-exclude-flags" : NULL },
+    };
+    for (size_t k = 0; k < sizeof opts / sizeof opts[0]; k++) {
+        if (opts[k].owned && !opts[k].given) { fprintf(stderr, "cbc: %s applies to %s\n", opts[k].owned, opts[k].name); return 1; }
+        if (!opts[k].given) continue;
+        if (mode != 2) { fprintf(stderr, "cbc: %s applies to decompression (-d / -x)\n", opts[k].name); return 1; }
+        for (size_t j = 2; j < k; j++) if (opts[j].given) { fprintf(stderr, "cbc: %s; give one of them\n", opts[k].clash); return 1; }
+        if (ndev > 1) { fprintf(stderr, "cbc: %s decodes on one device; give a single --devices ordinal\n", opts[k].name); return 1; }
+    }
     if (depth_hist)
         return cbc_cli_decompress_hist(files[0], files[1], files[2], device, regions, n_regions, regions_file, hist_max, depth_exclude, verbose);
     if (depth_excl_given && !depth_out && !bedcov) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
     if (stats_out) return cbc_cli_decompress_stats(files[0], files[1], files[2], device, regions, n_regions, regions_file, stats_exclude, verbose);
-    if (bedcov && (thr_given || count_reads))
-        return cbc_cli_decompress_bedcov_ext(files[0], files[1], files[2], device, regions, n_regions, regions_file, cov_window, cov_min_depth,
-                                             depth_exclude, verbose, thr, n_thr, count_reads);
-    if (bedcov)
+    if (bedcov)                                                   /* no --thresholds, no --count-reads: n_thr is 0, the plain summary */
         return cbc_cli_decompress_bedcov(files[0], files[1], files[2], device, regions, n_regions, regions_file, cov_window, cov_min_depth,
-                                         depth_exclude, verbose);
+                                         depth_exclude, verbose, thr, n_thr, count_reads);
     /* several --region or a BED file: their union in one pass; exactly one --region and no file: the single-region paths */
     if (regions_file || n_regions > 1)
         return cbc_cli_decompress_targets(files[0], files[1], files[2], device, regions, n_regions, regions_file,

@@ -316,6 +316,49 @@ class Encoder:
             msg = lib().cbc_gpu_last_error(self._ctx)
             raise CbcGpuError("%s failed (%d): %s" % (what, rc, msg.decode(errors="replace") if msg else ""))
 
+    # ---- what the decode_* wrappers below share ----
+
+    def _check_blocks(self, rc, what, results):
+        """_check, except that with results=True a failed block (rc -4) passes: the caller hands out the per-block results."""
+        if rc != 0 and not (results and rc == -4):
+            self._check(rc, what)
+
+    @staticmethod
+    def _plan_args(plan):
+        """(caps, payloads, names, name offsets) of a plan as the C calls take them; the caller keeps them alive over the call."""
+        return (host.LdsCaps(plan.cap_pos, plan.cap_var), np.ascontiguousarray(plan.payloads), np.ascontiguousarray(plan.names),
+                np.ascontiguousarray(plan.contig_name_off, dtype=np.uint32))
+
+    @staticmethod
+    def _gather(plan, sel, biv=None):
+        """(descriptors, window starts, contigs) of the blocks `sel`, a slice or an array of block indices, as contiguous arrays;
+        biv: the rows of a target set's block_iv that go with them, appended as a fourth."""
+        if not isinstance(sel, slice):
+            sel = np.ascontiguousarray(sel).astype(np.int64)
+        out = (np.ascontiguousarray(plan.blocks[sel]), np.ascontiguousarray(plan.window_start[sel], dtype=np.uint64),
+               np.ascontiguousarray(plan.block_contig[sel], dtype=np.uint32))
+        return out if biv is None else out + (np.ascontiguousarray(biv, dtype=np.uint32),)
+
+    @staticmethod
+    def _cat(allres):
+        return np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE)
+
+    def _last_ms(self, name, n, at=None, must=False):
+        """The n floats of lib().<name> (a cbc_gpu_last_*_ms) as a tuple, None when the call reports none (must=True: raise).
+        at: where in the n floats each pointer argument starts (default: one argument per float)."""
+        buf = (ctypes.c_float * n)()
+        rc = getattr(lib(), name)(self._ctx, *[ctypes.cast(ctypes.byref(buf, 4 * i), ctypes.POINTER(ctypes.c_float))
+                                               for i in (at or range(n))])
+        if must:
+            self._check(rc, name)
+        return tuple(buf) if rc == 0 else None
+
+    def _add_ms(self, attr, name, n, at=None, must=False):
+        """Adds the kernel milliseconds of the last call (_last_ms) to the tuple in self.<attr>, which starts as None."""
+        ms, old = self._last_ms(name, n, at, must), getattr(self, attr)
+        if ms is not None:
+            setattr(self, attr, ms if old is None else tuple(a + b for a, b in zip(old, ms)))
+
     def upload_reference(self, ref: np.ndarray):
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         self._check(lib().cbc_gpu_upload_reference(self._ctx, ref.ctypes.data, ref.size), "cbc_gpu_upload_reference")
@@ -490,18 +533,15 @@ class Encoder:
         res = np.zeros(max(nb, 1), dtype=host.RESULT_DTYPE)
         if nb == 0:
             return (b"", 0, sel, res[:0]) if results else b""
-        blocks = np.ascontiguousarray(plan.blocks[sel.b0:sel.b1])
-        ws = np.ascontiguousarray(plan.window_start[sel.b0:sel.b1], dtype=np.uint64)
+        blocks, ws, _ = self._gather(plan, slice(sel.b0, sel.b1))
         cap = int(blocks["n_reads"].astype(np.uint64).sum()) * (plan.seq_stride + 1)
         text = np.zeros(max(cap, 1), dtype=np.uint8)
         nbytes, nsel = ctypes.c_uint64(), ctypes.c_uint64()
-        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
-        pay = np.ascontiguousarray(plan.payloads)
+        caps, pay, _, _ = self._plan_args(plan)
         rc = lib().cbc_gpu_decode_region(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
                                          ws.ctypes.data, sel.beg, sel.end, sel.smax, text.ctypes.data, cap,
                                          ctypes.byref(nbytes), ctypes.byref(nsel), res.ctypes.data)
-        if rc != 0 and not (results and rc == -4):
-            self._check(rc, "cbc_gpu_decode_region")
+        self._check_blocks(rc, "cbc_gpu_decode_region", results)
         out = text[:int(nbytes.value)].tobytes()
         return (out, int(nsel.value), sel, res[:nb]) if results else out
 
@@ -518,24 +558,18 @@ class Encoder:
         res = np.zeros(max(nb, 1), dtype=host.RESULT_DTYPE)
         if nb == 0:
             return (hdr, 0, sel, res[:0]) if results else hdr
-        blocks = np.ascontiguousarray(plan.blocks[b0:b1])
-        ws = np.ascontiguousarray(plan.window_start[b0:b1], dtype=np.uint64)
-        bc = np.ascontiguousarray(plan.block_contig[b0:b1], dtype=np.uint32)
-        names = np.ascontiguousarray(plan.names)
-        noff = np.ascontiguousarray(plan.contig_name_off, dtype=np.uint32)
+        blocks, ws, bc = self._gather(plan, slice(b0, b1))
+        caps, pay, names, noff = self._plan_args(plan)
         cap = plan.sam_text_cap(b0, b1) if text_cap is None else int(text_cap)
         text = np.zeros(max(cap, 1), dtype=np.uint8)
         nbytes, nrd = ctypes.c_uint64(), ctypes.c_uint64()
-        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
-        pay = np.ascontiguousarray(plan.payloads)
         rg = SamRegion(sel.beg, sel.end, sel.smax, 0) if sel is not None else None
         rc = lib().cbc_gpu_decode_sam(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps), ws.ctypes.data,
                                       bc.ctypes.data, names.ctypes.data, names.size, noff.ctypes.data, plan.n_contigs,
                                       ctypes.byref(rg) if rg is not None else None, text.ctypes.data, cap,
                                       ctypes.byref(nbytes), ctypes.byref(nrd), res.ctypes.data)
         self.last_sam_text_bytes = int(nbytes.value)
-        if rc != 0 and not (results and rc == -4):
-            self._check(rc, "cbc_gpu_decode_sam")
+        self._check_blocks(rc, "cbc_gpu_decode_sam", results)
         out = hdr + text[:int(nbytes.value)].tobytes()
         return (out, int(nrd.value), sel, res[:nb]) if results else out
 
@@ -553,14 +587,12 @@ class Encoder:
         out, n_runs, n_kept, allres = [], 0, 0, []
         self.last_depth_text_bytes = 0
         self._depth_ms = None
-        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
-        pay = np.ascontiguousarray(plan.payloads)
+        caps, pay, _, _ = self._plan_args(plan)
         for sel in sels:
             nb = sel.b1 - sel.b0
             if nb == 0:
                 continue
-            blocks = np.ascontiguousarray(plan.blocks[sel.b0:sel.b1])
-            ws = np.ascontiguousarray(plan.window_start[sel.b0:sel.b1], dtype=np.uint64)
+            blocks, ws, _ = self._gather(plan, slice(sel.b0, sel.b1))
             off = int(plan.contig_name_off[sel.contig])
             name = plan.names[off:].tobytes().split(b"\0", 1)[0]
             cap = plan.depth_text_cap(sel.b0, sel.b1, sel.contig) if text_cap is None else int(text_cap)
@@ -573,15 +605,13 @@ class Encoder:
                                             text.ctypes.data, cap, ctypes.byref(nbytes), ctypes.byref(nr), ctypes.byref(nk),
                                             res.ctypes.data)
             self.last_depth_text_bytes += int(nbytes.value)
-            if rc != 0 and not (results and rc == -4):
-                self._check(rc, "cbc_gpu_decode_depth")
-            ms = self.last_depth_ms(_one=True)
-            self._depth_ms = ms if self._depth_ms is None else tuple(a + b for a, b in zip(self._depth_ms, ms))
+            self._check_blocks(rc, "cbc_gpu_decode_depth", results)
+            self._add_ms("_depth_ms", "cbc_gpu_last_depth_ms", 4, must=True)
             out.append(text[:int(nbytes.value)].tobytes())
             n_runs += int(nr.value); n_kept += int(nk.value); allres.append(res)
         text = b"".join(out)
         if results:
-            return text, n_runs, n_kept, (np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE))
+            return text, n_runs, n_kept, self._cat(allres)
         return text
 
     def decode_targets(self, plan: "host.UnpackPlan", targets, output="reads", exclude_flags=0, results=False, text_cap=None):
@@ -596,10 +626,7 @@ class Encoder:
         hdr = plan.sam_header()                               # refuses what the text cannot carry, and long-read containers
         self._targets_ms = None
         self.last_targets_text_bytes = 0
-        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
-        pay = np.ascontiguousarray(plan.payloads)
-        names = np.ascontiguousarray(plan.names)
-        noff = np.ascontiguousarray(plan.contig_name_off, dtype=np.uint32)
+        caps, pay, names, noff = self._plan_args(plan)
         iv = np.ascontiguousarray(targets.iv, dtype=np.uint32)
         if kind == 2:
             calls = [(int(targets.contig_blk_first[c]), int(targets.contig_blk_count[c]), targets.depth_cap[c])
@@ -608,11 +635,7 @@ class Encoder:
             calls = [(0, targets.n_blocks, targets.text_cap_sam if kind == 1 else targets.text_cap_reads)] if targets.n_blocks else []
         out, n_reads, n_runs, allres = [], 0, 0, []
         for k0, nb, cap in calls:
-            sel = np.ascontiguousarray(targets.blocks[k0:k0 + nb]).astype(np.int64)
-            blocks = np.ascontiguousarray(plan.blocks[sel])
-            ws = np.ascontiguousarray(plan.window_start[sel], dtype=np.uint64)
-            bc = np.ascontiguousarray(plan.block_contig[sel], dtype=np.uint32)
-            biv = np.ascontiguousarray(targets.block_iv[k0:k0 + nb], dtype=np.uint32)
+            blocks, ws, bc, biv = self._gather(plan, targets.blocks[k0:k0 + nb], targets.block_iv[k0:k0 + nb])
             cap = cap if text_cap is None else int(text_cap)
             text = np.zeros(max(cap, 1), dtype=np.uint8)
             res = np.zeros(nb, dtype=host.RESULT_DTYPE)
@@ -623,17 +646,13 @@ class Encoder:
                                               plan.n_contigs, ctypes.byref(tg), kind, int(exclude_flags), text.ctypes.data, cap,
                                               ctypes.byref(nbytes), ctypes.byref(nrd), ctypes.byref(nrn), res.ctypes.data)
             self.last_targets_text_bytes += int(nbytes.value)
-            if rc != 0 and not (results and rc == -4):
-                self._check(rc, "cbc_gpu_decode_targets")
-            v = [ctypes.c_float() for _ in range(4)]
-            if lib().cbc_gpu_last_targets_ms(self._ctx, *[ctypes.byref(x) for x in v]) == 0:
-                ms = tuple(float(x.value) for x in v)
-                self._targets_ms = ms if self._targets_ms is None else tuple(a + b for a, b in zip(self._targets_ms, ms))
+            self._check_blocks(rc, "cbc_gpu_decode_targets", results)
+            self._add_ms("_targets_ms", "cbc_gpu_last_targets_ms", 4)
             out.append(text[:int(nbytes.value)].tobytes() if rc in (0, -4) else b"")
             n_reads += int(nrd.value); n_runs += int(nrn.value); allres.append(res)
         text = (hdr if kind == 1 else b"") + b"".join(out)
         if results:
-            return text, n_reads, n_runs, (np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE))
+            return text, n_reads, n_runs, self._cat(allres)
         return text
 
     def decode_coverage(self, plan: "host.UnpackPlan", queries, exclude_flags=0, min_depth=1, results=False, thresholds=(),
@@ -660,10 +679,7 @@ class Encoder:
         xreads = np.zeros(queries.n_q, dtype=np.uint32)
         self._coverage_ms = None
         self._coverage_ext_ms = None
-        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
-        pay = np.ascontiguousarray(plan.payloads)
-        names = np.ascontiguousarray(plan.names)
-        noff = np.ascontiguousarray(plan.contig_name_off, dtype=np.uint32)
+        caps, pay, names, noff = self._plan_args(plan)
         iv = np.ascontiguousarray(ts.iv, dtype=np.uint32)
         total = np.zeros(queries.n_q, dtype=np.uint64)
         covered = np.zeros(queries.n_q, dtype=np.uint32)
@@ -674,11 +690,7 @@ class Encoder:
             idx = np.flatnonzero((queries.contig == c) & (length > 0))
             if not nb or not ni or not len(idx):
                 continue
-            sel = np.ascontiguousarray(ts.blocks[k0:k0 + nb]).astype(np.int64)
-            blocks = np.ascontiguousarray(plan.blocks[sel])
-            ws = np.ascontiguousarray(plan.window_start[sel], dtype=np.uint64)
-            bc = np.ascontiguousarray(plan.block_contig[sel], dtype=np.uint32)
-            biv = np.ascontiguousarray(ts.block_iv[k0:k0 + nb], dtype=np.uint32)
+            blocks, ws, bc, biv = self._gather(plan, ts.blocks[k0:k0 + nb], ts.block_iv[k0:k0 + nb])
             q = np.ascontiguousarray(np.stack([queries.q["slot"][idx], length[idx].astype(np.uint32)], axis=1), dtype=np.uint32)
             s, cv = np.zeros(len(idx), dtype=np.uint64), np.zeros(len(idx), dtype=np.uint32)
             res = np.zeros(nb, dtype=host.RESULT_DTYPE)
@@ -693,21 +705,13 @@ class Encoder:
                 tc, rd = np.zeros((len(idx), T), dtype=np.uint32), np.zeros(len(idx), dtype=np.uint32)
                 rc = lib().cbc_gpu_decode_coverage_ext(*args, thr.ctypes.data if T else None, T, tc.ctypes.data if T else None,
                                                        rd.ctypes.data if count_reads else None)
-                if rc != 0 and not (results and rc == -4):
-                    self._check(rc, "cbc_gpu_decode_coverage_ext")
-                v7, v5 = (ctypes.c_float * 7)(), (ctypes.c_float * 5)()
-                if lib().cbc_gpu_last_coverage_ext_ms(self._ctx, v7, v5) == 0:
-                    ms = tuple(float(x) for x in v7) + tuple(float(x) for x in v5)
-                    self._coverage_ext_ms = ms if self._coverage_ext_ms is None else tuple(a + b for a, b in zip(self._coverage_ext_ms, ms))
+                self._check_blocks(rc, "cbc_gpu_decode_coverage_ext", results)
+                self._add_ms("_coverage_ext_ms", "cbc_gpu_last_coverage_ext_ms", 12, at=(0, 7))
                 xthr[idx], xreads[idx] = tc, rd
             else:
                 rc = lib().cbc_gpu_decode_coverage(*args)
-                if rc != 0 and not (results and rc == -4):
-                    self._check(rc, "cbc_gpu_decode_coverage")
-                v = [ctypes.c_float() for _ in range(7)]
-                if lib().cbc_gpu_last_coverage_ms(self._ctx, *[ctypes.byref(x) for x in v]) == 0:
-                    ms = tuple(float(x.value) for x in v)
-                    self._coverage_ms = ms if self._coverage_ms is None else tuple(a + b for a, b in zip(self._coverage_ms, ms))
+                self._check_blocks(rc, "cbc_gpu_decode_coverage", results)
+                self._add_ms("_coverage_ms", "cbc_gpu_last_coverage_ms", 7)
             total[idx], covered[idx] = s, cv
             allres.append(res)
         out = (queries.contig.copy(), queries.start0.copy(), queries.end0.copy(), total, covered)
@@ -716,7 +720,7 @@ class Encoder:
         if count_reads:
             out += (xreads,)
         if results:
-            return out + ((np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE)),)
+            return out + (self._cat(allres),)
         return out
 
     def last_coverage_ms(self):
@@ -748,10 +752,7 @@ class Encoder:
         if not 0 <= int(max_depth) <= 0xffffffff:
             raise ValueError("max_depth is 0 (no folding) or 1 .. 2^32 - 1")
         self._hist_ms = None
-        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
-        pay = np.ascontiguousarray(plan.payloads)
-        names = np.ascontiguousarray(plan.names)
-        noff = np.ascontiguousarray(plan.contig_name_off, dtype=np.uint32)
+        caps, pay, names, noff = self._plan_args(plan)
         iv = np.ascontiguousarray(ts.iv, dtype=np.uint32)
         out, allres = [], []
         for c in range(ts.n_contigs):
@@ -761,11 +762,7 @@ class Encoder:
             size = ts.size[c]
             depth, bases = np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint64)
             if nb:
-                sel = np.ascontiguousarray(ts.blocks[k0:k0 + nb]).astype(np.int64)
-                blocks = np.ascontiguousarray(plan.blocks[sel])
-                ws = np.ascontiguousarray(plan.window_start[sel], dtype=np.uint64)
-                bc = np.ascontiguousarray(plan.block_contig[sel], dtype=np.uint32)
-                biv = np.ascontiguousarray(ts.block_iv[k0:k0 + nb], dtype=np.uint32)
+                blocks, ws, bc, biv = self._gather(plan, ts.blocks[k0:k0 + nb], ts.block_iv[k0:k0 + nb])
                 cap = max(1, min(int(blocks["n_reads"].astype(np.int64).sum()), int(max_depth) or 0xffffffff))
                 bd, bb = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
                 res = np.zeros(nb, dtype=host.RESULT_DTYPE)
@@ -776,12 +773,8 @@ class Encoder:
                                                      plan.n_contigs, ctypes.byref(tg), f, ni, int(exclude_flags), int(max_depth),
                                                      bd.ctypes.data, bb.ctypes.data, cap, ctypes.byref(nbin), ctypes.byref(nrd),
                                                      res.ctypes.data)
-                if rc != 0 and not (results and rc == -4):
-                    self._check(rc, "cbc_gpu_decode_depth_hist")
-                v = [ctypes.c_float() for _ in range(5)]
-                if lib().cbc_gpu_last_hist_ms(self._ctx, *[ctypes.byref(x) for x in v]) == 0:
-                    ms = tuple(float(x.value) for x in v)
-                    self._hist_ms = ms if self._hist_ms is None else tuple(a + b for a, b in zip(self._hist_ms, ms))
+                self._check_blocks(rc, "cbc_gpu_decode_depth_hist", results)
+                self._add_ms("_hist_ms", "cbc_gpu_last_hist_ms", 5)
                 n = int(nbin.value)
                 depth, bases = bd[:n].copy(), bb[:n].astype(np.uint64)
                 allres.append(res)
@@ -792,7 +785,7 @@ class Encoder:
                 depth, bases = np.concatenate([np.zeros(1, dtype=np.uint32), depth]), np.concatenate([np.array([zero], dtype=np.uint64), bases])
             out.append((c, depth, bases, size))
         if results:
-            return out, (np.concatenate(allres) if allres else np.zeros(0, dtype=host.RESULT_DTYPE))
+            return out, self._cat(allres)
         return out
 
     def last_hist_ms(self):
@@ -815,30 +808,22 @@ class Encoder:
             raise ValueError("exclude_flags is a FLAG mask in 0 .. 65535")
         self._stats_ms = None
         st = host.GpuStats()
-        if targets is None:
-            sel = np.arange(plan.n_blocks, dtype=np.int64)
-        else:
-            sel = np.ascontiguousarray(targets.blocks).astype(np.int64)
-        nb = len(sel)
+        nb = plan.n_blocks if targets is None else len(targets.blocks)
         res = np.zeros(nb, dtype=host.RESULT_DTYPE)
         if nb:
-            caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
-            pay = np.ascontiguousarray(plan.payloads)
-            blocks = np.ascontiguousarray(plan.blocks[sel])
-            ws = np.ascontiguousarray(plan.window_start[sel], dtype=np.uint64)
+            caps, pay, _, _ = self._plan_args(plan)
             tg = None
-            if targets is not None:
+            if targets is None:
+                blocks, ws, _ = self._gather(plan, slice(0, nb))
+            else:
+                blocks, ws, _, biv = self._gather(plan, targets.blocks, targets.block_iv)
                 iv = np.ascontiguousarray(targets.iv, dtype=np.uint32)
-                biv = np.ascontiguousarray(targets.block_iv, dtype=np.uint32)
                 tg = GpuTargets(iv.ctypes.data, biv.ctypes.data, targets.n_iv, targets.smax)
             rc = lib().cbc_gpu_decode_stats(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps), ws.ctypes.data,
                                             ctypes.byref(tg) if tg is not None else None, int(exclude_flags), ctypes.byref(st),
                                             res.ctypes.data)
-            if rc != 0 and not (results and rc == -4):
-                self._check(rc, "cbc_gpu_decode_stats")
-            v = [ctypes.c_float() for _ in range(2)]
-            if lib().cbc_gpu_last_stats_ms(self._ctx, *[ctypes.byref(x) for x in v]) == 0:
-                self._stats_ms = tuple(float(x.value) for x in v)
+            self._check_blocks(rc, "cbc_gpu_decode_stats", results)
+            self._add_ms("_stats_ms", "cbc_gpu_last_stats_ms", 2)
         out = dict(reads=int(st.reads), excluded=int(st.excluded), flag=np.ctypeslib.as_array(st.flag).copy(),
                    len=np.ctypeslib.as_array(st.len).copy(), gc=np.ctypeslib.as_array(st.gc).copy(),
                    cyc=np.ctypeslib.as_array(st.cyc).copy().reshape(5, 256))
@@ -863,21 +848,15 @@ class Encoder:
             if getattr(self, "_depth_ms", None) is None:
                 raise CbcGpuError("no decode_depth has run on the device")
             return self._depth_ms
-        v = [ctypes.c_float() for _ in range(4)]
-        self._check(lib().cbc_gpu_last_depth_ms(self._ctx, *[ctypes.byref(x) for x in v]), "cbc_gpu_last_depth_ms")
-        return tuple(float(x.value) for x in v)
+        return self._last_ms("cbc_gpu_last_depth_ms", 4, must=True)
 
     def last_sam_ms(self):
         """(decode, count + scan, text) kernel milliseconds of the last decode_sam."""
-        a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
-        self._check(lib().cbc_gpu_last_sam_ms(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "cbc_gpu_last_sam_ms")
-        return float(a.value), float(b.value), float(c.value)
+        return self._last_ms("cbc_gpu_last_sam_ms", 3, must=True)
 
     def last_region_ms(self):
         """(decode, filter + scan, text) kernel milliseconds of the last decode_region."""
-        a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
-        self._check(lib().cbc_gpu_last_region_ms(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "cbc_gpu_last_region_ms")
-        return float(a.value), float(b.value), float(c.value)
+        return self._last_ms("cbc_gpu_last_region_ms", 3, must=True)
 
     def _host_batch(self, pb):
         blocks = pb.blocks.copy()
