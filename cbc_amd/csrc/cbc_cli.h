@@ -20,7 +20,7 @@ int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref,
 /* n_thr == 0 and !count_reads: the plain summary */
 int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                               const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose,
-                              const uint32_t *thr, uint32_t n_thr, int count_reads);
+                              const uint32_t *thr, uint32_t n_thr, int count_reads, const uint32_t *pct, uint32_t n_pct);
 int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                             const char *bed_path, uint32_t max_depth, uint32_t exclude, int verbose);
 int cbc_cli_decompress_stats(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,

@@ -468,12 +468,14 @@ int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref,
  * order across contigs.  12 bytes per query cross PCIe.
  * `--thresholds T1,..` / `--count-reads`: n_thr more columns, the positions with depth >= Ti, and one
  * last column, the kept reads with a base in the query, from cbc_gpu_decode_coverage_ext; with neither (n_thr == 0 and
- * !count_reads), the call, the kernels, the bytes and the messages are those of the plain summary. */
+ * !count_reads), the call, the kernels, the bytes and the messages are those of the plain summary.
+ * `--quantiles P1,..`: n_pct more columns behind the thresholds' and in front of the read count, the
+ * nearest-rank depth quantiles of the query's positions, from cbc_gpu_decode_coverage_quant; without it nothing changes. */
 int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                               const char *bed_path, uint64_t window, uint32_t min_depth, uint32_t exclude, int verbose,
-                              const uint32_t *thr, uint32_t n_thr, int count_reads)
+                              const uint32_t *thr, uint32_t n_thr, int count_reads, const uint32_t *pct, uint32_t n_pct)
 {
-    const int ext = n_thr || count_reads;
+    const int ext = n_thr || count_reads || n_pct;
     cli_run r;
     if (cli_open(&r, in, ref, bed_path, device, "--bedcov", "has no block index")) return 1;
     const cbc_unpack_plan *u = r.u;
@@ -493,7 +495,8 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
     /* the extra columns, gathered and scattered per contig like sum and covered */
     uint32_t *xthr = (uint32_t *)calloc((size_t)(nq ? nq : 1) * (n_thr ? n_thr : 1), 4), *cthr = (uint32_t *)malloc((size_t)(nq ? nq : 1) * (n_thr ? n_thr : 1) * 4);
     uint32_t *xrd = (uint32_t *)calloc((size_t)(nq ? nq : 1), 4), *crd = (uint32_t *)malloc((size_t)(nq ? nq : 1) * 4);
-    if (!sum || !csum || !cov || !ccov || !qq || !qi || !cfirst || !xthr || !cthr || !xrd || !crd) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    uint32_t *xqd = (uint32_t *)calloc((size_t)(nq ? nq : 1) * (n_pct ? n_pct : 1), 4), *cqd = (uint32_t *)malloc((size_t)(nq ? nq : 1) * (n_pct ? n_pct : 1) * 4);
+    if (!sum || !csum || !cov || !ccov || !qq || !qi || !cfirst || !xthr || !cthr || !xrd || !crd || !xqd || !cqd) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
     /* the queries that hold a position, grouped per contig (a counting sort: the order inside a contig stays the input's) */
     for (uint64_t i = 0; i < nq; i++) if (Q->q[i].contig != CBC_QUERY_UNKNOWN && Q->q[i].end0 > Q->q[i].start0) cfirst[Q->q[i].contig + 2]++;
     for (uint32_t c = 0; c < nc; c++) cfirst[c + 2] += cfirst[c + 1];
@@ -506,7 +509,7 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
     r.t1 = now2();
     uint64_t reads = 0;
     uint32_t blocks_used = 0;
-    float ms[7] = { 0, 0, 0, 0, 0, 0, 0 }, xms[5] = { 0, 0, 0, 0, 0 }, m[7], xm[5];
+    float ms[7] = { 0, 0, 0, 0, 0, 0, 0 }, xms[5] = { 0, 0, 0, 0, 0 }, m[7], xm[5], qms = 0, qm;
     for (uint32_t c = 0; c < nc && nb; c++) {
         const uint32_t k0 = T->contig_blk_first[c], kn = T->contig_blk_count[c];
         const uint64_t q0 = cfirst[c], qn = cfirst[c + 1] - cfirst[c];
@@ -515,7 +518,12 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
         const double b = now2();
         const cbc_gpu_targets g = { (const uint32_t *)T->iv, T->block_iv + 2 * (size_t)k0, T->n_iv, T->smax };
         uint64_t nr = 0;
-        if (ext)
+        if (n_pct)
+            rc = cbc_gpu_decode_coverage_quant(r.ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
+                                               u->contig_name_off, u->n_contigs, &g, T->contig_first[c], T->contig_count[c], qq + 2 * q0,
+                                               (uint32_t)qn, exclude, min_depth, csum + q0, ccov + q0, &nr, NULL, thr, n_thr,
+                                               cthr + q0 * n_thr, count_reads ? crd + q0 : NULL, pct, n_pct, cqd + q0 * n_pct);
+        else if (ext)
             rc = cbc_gpu_decode_coverage_ext(r.ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
                                              u->contig_name_off, u->n_contigs, &g, T->contig_first[c], T->contig_count[c], qq + 2 * q0,
                                              (uint32_t)qn, exclude, min_depth, csum + q0, ccov + q0, &nr, NULL, thr, n_thr,
@@ -526,12 +534,14 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
                                          (uint32_t)qn, exclude, min_depth, csum + q0, ccov + q0, &nr, NULL);
         if (rc) { fprintf(stderr, "cbc: coverage failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
         r.t_dev += now2() - b;
-        if (verbose && ext) { if (cbc_gpu_last_coverage_ext_ms(r.ctx, m, xm) == 0) { add_ms(ms, m, 7); add_ms(xms, xm, 5); } }
+        if (verbose && n_pct) { if (cbc_gpu_last_coverage_quant_ms(r.ctx, m, xm, &qm) == 0) { add_ms(ms, m, 7); add_ms(xms, xm, 5); qms += qm; } }
+        else if (verbose && ext) { if (cbc_gpu_last_coverage_ext_ms(r.ctx, m, xm) == 0) { add_ms(ms, m, 7); add_ms(xms, xm, 5); } }
         else if (verbose && cbc_gpu_last_coverage_ms(r.ctx, &m[0], &m[1], &m[2], &m[3], &m[4], &m[5], &m[6]) == 0) add_ms(ms, m, 7);
         for (uint64_t k = q0; k < q0 + qn; k++) { sum[qi[k]] = csum[k]; cov[qi[k]] = ccov[k]; }
         for (uint64_t k = q0; ext && k < q0 + qn; k++) {
             for (uint32_t t = 0; t < n_thr; t++) xthr[(size_t)qi[k] * n_thr + t] = cthr[k * n_thr + t];
             if (count_reads) xrd[qi[k]] = crd[k];
+            for (uint32_t t = 0; t < n_pct; t++) xqd[(size_t)qi[k] * n_pct + t] = cqd[k * n_pct + t];
         }
         reads += nr; blocks_used += kn;
     }
@@ -547,6 +557,7 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
         int bad = fprintf(fo, "%.*s\t%llu\t%llu\t%llu\t%u\t%s", nl, nm, (unsigned long long)x->start0, (unsigned long long)x->end0,
                           (unsigned long long)sum[i], cov[i], mean) < 0;
         for (uint32_t t = 0; t < n_thr && !bad; t++) bad = fprintf(fo, "\t%u", xthr[(size_t)i * n_thr + t]) < 0;
+        for (uint32_t t = 0; t < n_pct && !bad; t++) bad = fprintf(fo, "\t%u", xqd[(size_t)i * n_pct + t]) < 0;
         if (count_reads && !bad) bad = fprintf(fo, "\t%u", xrd[i]) < 0;
         if (bad || fputc('\n', fo) == EOF) return cannot_write(out);
     }
@@ -561,8 +572,9 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
                            ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6]);
         if (r.used && ext) printf("kernels: start points %.3f ms, threshold weights %.3f ms, their scans %.3f ms, their prefixes %.3f ms, threshold + read lookup %.3f ms\n",
                                   xms[0], xms[1], xms[2], xms[3], xms[4]);
+        if (r.used && n_pct) printf("kernels: quantile selection %.3f ms\n", qms);
     }
-    free(xthr); free(cthr); free(xrd); free(crd);
+    free(xthr); free(cthr); free(xrd); free(crd); free(xqd); free(cqd);
     free(bl); free(ws); free(bc); free(sum); free(csum); free(cov); free(ccov); free(qq); free(qi); free(cfirst);
     cbc_queries_free(Q);
     cli_close(&r);

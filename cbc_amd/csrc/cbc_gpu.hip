@@ -25,6 +25,7 @@
 #include "cbc_targets_body.h"
 #include "cbc_cov_body.h"
 #include "cbc_covx_body.h"
+#include "cbc_quant_body.h"
 #include "cbc_hist_body.h"
 #include "cbc_stats_body.h"
 #include "cbc_plan.h"
@@ -168,6 +169,15 @@ __global__ void __launch_bounds__(64)
 cbc_covx_apply_kernel(cbc_covx_args A) { cbc_covx_apply<WaveGPU>(A, blockIdx.x); }
 __global__ void __launch_bounds__(64)
 cbc_covx_lookup_kernel(cbc_covx_args A) { cbc_covx_lookup<WaveGPU>(A, blockIdx.x); }
+
+/* Depth quantiles per query (cbc_gpu_decode_coverage_quant, cbc_quant_body.h), behind the passes above: one wavefront per query
+ * selects all its quantiles from the runs it holds, in registers up to 64 runs and through its own LDS table beyond */
+__global__ void __launch_bounds__(64)
+cbc_quant_select_kernel(cbc_quant_args A)
+{
+    __shared__ uint32_t tab[CBC_QUANT_LDS];
+    cbc_quant_select<WaveGPU>(A, blockIdx.x, tab);
+}
 
 /* Depth histogram (cbc_gpu_decode_depth_hist, cbc_hist_body.h), behind the same mark / tile / scan / compact passes: a bounded
  * grid of one-wavefront workgroups adds the runs' lengths to the bins of their depths (shallow bins in the workgroup's LDS table,
@@ -368,7 +378,7 @@ enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A
  * stage of cbc_gpu_decode_region, _sam, _depth, _targets (reads, SAM, depth), _coverage, _depth_hist, _coverage_ext, _stats (whole
  * file, target set) */
 enum post_kind { POST_NONE, POST_REGION, POST_SAM, POST_DEPTH, POST_TG_READS, POST_TG_SAM, POST_TG_DEPTH, POST_COV, POST_HIST, POST_COVX,
-                 POST_STATS, POST_TG_STATS };
+                 POST_STATS, POST_TG_STATS, POST_COVQ };
 
 struct cbc_gpu_ctx {
     int device;
@@ -383,6 +393,7 @@ struct cbc_gpu_ctx {
     hipEvent_t ev_covx[5];         /* cbc_gpu_decode_coverage_ext: behind ev_cov[3], after the start points' scans + compact, the thresholds'
                                     * weights, their scans, their prefixes and the lookup */
     hipEvent_t ev_hist[2];         /* cbc_gpu_decode_depth_hist: behind ev_rg[3], after zeroing + accumulate and after the bin compaction */
+    hipEvent_t ev_quant;           /* cbc_gpu_decode_coverage_quant: behind ev_covx[4], after the selection */
     post_kind last_post;           /* whose times those events hold: the kind of the most recent call with a post-decode stage
                                     * (POST_NONE: none yet), set by decode_blocks_impl and asked by the cbc_gpu_last_*_ms */
     int have_timing;
@@ -467,6 +478,7 @@ API int cbc_gpu_init(int device_ordinal, cbc_gpu_ctx **out)
         if (hipEventCreate(&ctx->ev_hist[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     for (int k = 0; k < 5; k++)
         if (hipEventCreate(&ctx->ev_covx[k]) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
+    if (hipEventCreate(&ctx->ev_quant) != hipSuccess) { delete ctx; return CBC_E_NODEV; }
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) != hipSuccess || cus <= 0) cus = 256;
@@ -498,6 +510,7 @@ API int cbc_gpu_shutdown(cbc_gpu_ctx *ctx)
     for (int k = 0; k < 4; k++) (void)hipEventDestroy(ctx->ev_cov[k]);
     for (int k = 0; k < 2; k++) (void)hipEventDestroy(ctx->ev_hist[k]);
     for (int k = 0; k < 5; k++) (void)hipEventDestroy(ctx->ev_covx[k]);
+    (void)hipEventDestroy(ctx->ev_quant);
     for (int k = 0; k < CBC_N_KSTREAMS; k++) { (void)hipEventDestroy(ctx->ev_done[k]); (void)hipStreamDestroy(ctx->s_k[k]); }
     (void)hipStreamDestroy(ctx->s_copy);
     (void)hipStreamDestroy(ctx->stream);
@@ -1056,7 +1069,8 @@ API int cbc_gpu_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device_batc
     return decode_blocks_launch(ctx, b, hip_stream, 0u);
 }
 
-static bool post_is_cov(post_kind k) { return k == POST_COV || k == POST_COVX; }
+static bool post_is_covx(post_kind k) { return k == POST_COVX || k == POST_COVQ; }
+static bool post_is_cov(post_kind k) { return k == POST_COV || post_is_covx(k); }
 static bool post_is_depth(post_kind k) { return k == POST_DEPTH || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST; }
 static bool post_is_sam(post_kind k) { return k == POST_SAM || k == POST_TG_SAM; }
 static bool post_is_targets(post_kind k) { return k == POST_TG_READS || k == POST_TG_SAM || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || k == POST_TG_STATS; }
@@ -1065,7 +1079,9 @@ static bool post_is_stats(post_kind k) { return k == POST_STATS || k == POST_TG_
 /* the queries (n_q pairs slot, len in the compressed coordinate), the depth that counts as covered, where the results go */
 struct cov_req { const uint32_t *q; uint32_t n_q, min_depth; uint64_t *sum; uint32_t *covered;
                  /* COVX: the thresholds, where their n_q * n_thr counts go, where the read counts go (NULL: none) */
-                 bool ext; const uint32_t *thr; uint32_t n_thr; uint32_t *thr_covered, *reads; };
+                 bool ext; const uint32_t *thr; uint32_t n_thr; uint32_t *thr_covered, *reads;
+                 /* COVQ: the percentages, where the n_q * n_quant depths go */
+                 const uint32_t *pct; uint32_t n_quant; uint32_t *quant; };
 /* the depth from which the bins fold (2^32 - 1: none), where the pairs go (bin_cap of each) and how many there are */
 struct hist_req { uint32_t fold; uint32_t *bin_depth, *bin_bases; uint32_t bin_cap; uint32_t *n_bins; };
 
@@ -1111,7 +1127,7 @@ static post_sizes post_sizes_of(const post_req *rg, uint32_t n_blocks, uint64_t 
     z.n_ttiles = (z.cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
     z.n_sized = z.n_ttiles;
     /* start points: a piece starts where its read starts or on an interval's first slot */
-    if (rg->kind == POST_COVX) z.sp_cap = (uint32_t)(n_recs + rg->n_iv);
+    if (post_is_covx(rg->kind)) z.sp_cap = (uint32_t)(n_recs + rg->n_iv);
     if (rg->kind != POST_HIST) return z;
     z.h_bins = (n_recs < rg->hist.fold ? n_recs : rg->hist.fold) + 1u;
     z.n_btiles = (uint32_t)((z.h_bins + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
@@ -1157,7 +1173,7 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
         NEED(A_CVQ, (uint64_t)rg->cov.n_q * 8 + 16, "hipMalloc coverage queries");
         NEED(A_CVOUT, (uint64_t)rg->cov.n_q * 12 + 16, "hipMalloc coverage results");
     }
-    if (k == POST_COVX) {
+    if (post_is_covx(k)) {
         const cov_req *cv = &rg->cov;
         if (cv->reads) {                                       /* the pieces' first slots: a second array of the difference array's size */
             if (arena_need(ctx, A_XSTARTS, (uint64_t)z.n_tiles * CBC_DEPTH_TILE * 4, "hipMalloc start slots")) {
@@ -1174,7 +1190,7 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
                 return set_err(ctx, CBC_E_NOMEM, "no device memory for the threshold prefixes (4 bytes per threshold and change point)", hipSuccess);
             }
         }
-        NEED(A_XOUT, (uint64_t)cv->n_q * 4 * (cv->n_thr + 1ull) + 16, "hipMalloc threshold and read counts");
+        NEED(A_XOUT, (uint64_t)cv->n_q * 4 * (cv->n_thr + 1ull + (k == POST_COVQ ? cv->n_quant : 0u)) + 16, "hipMalloc threshold and read counts");
     }
     if (k == POST_HIST) {
         if (arena_need(ctx, A_HBINS, (uint64_t)z.n_btiles * CBC_DEPTH_TILE * 4, "hipMalloc histogram bins") ||
@@ -1301,7 +1317,7 @@ static int launch_depth_front(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *
     if (post_is_targets(rg->kind)) {
         ta->D = *da; ta->iv = (const uint32_t *)ctx->arena[A_TIV].p; ta->iv_off = (const uint32_t *)ctx->arena[A_TOFF].p;
         ta->block_iv = (const uint32_t *)ctx->arena[A_TBIV].p; ta->n_iv = rg->n_iv;
-        if (rg->kind == POST_COVX && rg->cov.reads) {          /* the mark that also notes the pieces' first slots */
+        if (post_is_covx(rg->kind) && rg->cov.reads) {        /* the mark that also notes the pieces' first slots */
             uint32_t *starts = (uint32_t *)ctx->arena[A_XSTARTS].p;
             HIPCHK(hipMemsetAsync(starts, 0, da->diff_words * 4, ks), "memset start slots");
             hipLaunchKernelGGL(cbc_targets_mark_starts_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, *ta, starts);
@@ -1422,6 +1438,22 @@ static int launch_coverage_ext(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *
     return CBC_OK;
 }
 
+/* depth quantiles, behind launch_coverage_ext: one wavefront per query; its results behind the thresholds' and the read counts' */
+static int launch_coverage_quant(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *cov, const post_sizes &z, const cbc_depth_args &da)
+{
+    cbc_quant_args qa;
+    memset(&qa, 0, sizeof qa);
+    qa.cp_pos = da.cp_pos; qa.cp_dep = da.cp_dep; qa.cnt_off = da.cnt_off;
+    qa.q = (const uint32_t *)ctx->arena[A_CVQ].p;
+    qa.quant = (uint32_t *)ctx->arena[A_XOUT].p + (uint64_t)cov->n_q * (cov->n_thr + 1ull);
+    qa.n_quant = cov->n_quant; qa.cp_cap = z.cp_cap; qa.n_tiles = z.n_tiles; qa.n_q = cov->n_q; qa.slots = (uint32_t)z.d_words;
+    for (uint32_t t = 0; t < cov->n_quant; t++) qa.pct[t] = cov->pct[t];
+    hipLaunchKernelGGL(cbc_quant_select_kernel, dim3(cov->n_q), dim3(64), 0, ks, qa);
+    HIPCHK(hipGetLastError(), "launch cbc_quant_select_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_quant, ks), "hipEventRecord");
+    return CBC_OK;
+}
+
 /* histogram: zero, accumulate, count + scan + write of the bins: no text */
 static int launch_hist(cbc_gpu_ctx *ctx, hipStream_t ks, const hist_req *hist, const post_sizes &z, const cbc_depth_args &da)
 {
@@ -1487,10 +1519,12 @@ static int post_fetch_sizes(cbc_gpu_ctx *ctx, const post_req *rg, const post_siz
         else {                                                 /* the numbers, not the track: 12 bytes per query */
             HIPCHK(hipMemcpyAsync(rg->cov.sum, ctx->arena[A_CVOUT].p, (uint64_t)rg->cov.n_q * 8, hipMemcpyDeviceToHost, sc), "D2H coverage sums");
             HIPCHK(hipMemcpyAsync(rg->cov.covered, (uint64_t *)ctx->arena[A_CVOUT].p + rg->cov.n_q, (uint64_t)rg->cov.n_q * 4, hipMemcpyDeviceToHost, sc), "D2H coverage counts");
-            if (rg->kind == POST_COVX && rg->cov.n_thr)        /* + 4 bytes per threshold and query, + 4 for the read count */
+            if (post_is_covx(rg->kind) && rg->cov.n_thr)      /* + 4 bytes per threshold and query, + 4 for the read count */
                 HIPCHK(hipMemcpyAsync(rg->cov.thr_covered, ctx->arena[A_XOUT].p, (uint64_t)rg->cov.n_q * rg->cov.n_thr * 4, hipMemcpyDeviceToHost, sc), "D2H threshold counts");
-            if (rg->kind == POST_COVX && rg->cov.reads)
+            if (post_is_covx(rg->kind) && rg->cov.reads)
                 HIPCHK(hipMemcpyAsync(rg->cov.reads, (uint32_t *)ctx->arena[A_XOUT].p + (uint64_t)rg->cov.n_q * rg->cov.n_thr, (uint64_t)rg->cov.n_q * 4, hipMemcpyDeviceToHost, sc), "D2H read counts");
+            if (rg->kind == POST_COVQ)                         /* + 4 bytes per quantile and query, behind the read counts' place */
+                HIPCHK(hipMemcpyAsync(rg->cov.quant, (uint32_t *)ctx->arena[A_XOUT].p + (uint64_t)rg->cov.n_q * (rg->cov.n_thr + 1ull), (uint64_t)rg->cov.n_q * rg->cov.n_quant * 4, hipMemcpyDeviceToHost, sc), "D2H depth quantiles");
         }
         return CBC_OK;
     }
@@ -1646,6 +1680,12 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
                     if (!rc) rc = launch_coverage(ctx, ks, &rg->cov, z, da);
                     if (!rc) rc = launch_coverage_ext(ctx, ks, &rg->cov, z, da);
+                    break;
+                case POST_COVQ:
+                    rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
+                    if (!rc) rc = launch_coverage(ctx, ks, &rg->cov, z, da);
+                    if (!rc) rc = launch_coverage_ext(ctx, ks, &rg->cov, z, da);
+                    if (!rc) rc = launch_coverage_quant(ctx, ks, &rg->cov, z, da);
                     break;
                 case POST_HIST:
                     rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
@@ -1958,7 +1998,7 @@ static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
     }
     if (depth && L.nrec > 0x3fffffffull) { bad = "targets decode: more than 2^30 - 1 reads in one depth call"; goto out; }
     if (!L.nrec || (depth && lo >= hi)) goto out;               /* no read, or none that reaches an interval: CBC_OK */
-    post_req_init(&rg, cov ? (cov->ext ? POST_COVX : POST_COV) : hist ? POST_HIST : depth ? POST_TG_DEPTH : sam ? POST_TG_SAM : POST_TG_READS, t->smax,
+    post_req_init(&rg, cov ? (cov->n_quant ? POST_COVQ : cov->ext ? POST_COVX : POST_COV) : hist ? POST_HIST : depth ? POST_TG_DEPTH : sam ? POST_TG_SAM : POST_TG_READS, t->smax,
                   window_start, text, text_cap, sam ? L.nrec * (35ull + stride) + L.name_sum : L.nrec * (stride + 1ull), text_bytes, n_reads);
     rg.beg = 1u; rg.end = UINT64_MAX;
     rg.names = (const uint8_t *)names; rg.names_bytes = names_bytes; rg.block_name = sam ? L.bn : NULL;
@@ -2026,7 +2066,7 @@ API int cbc_gpu_decode_coverage(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in
     if (min_depth < 1 || n_q > (1u << 24) || iv_count < 1 || iv_first > t->n_iv || iv_count > t->n_iv - iv_first)
         return set_err(ctx, CBC_E_ARG, "coverage wants min_depth >= 1, at most 2^24 queries and the contig's intervals inside the table", hipSuccess);
     if (n_q == 0) return CBC_OK;
-    const cov_req cq = { q, n_q, min_depth, sum, covered, false, NULL, 0u, NULL, NULL };
+    const cov_req cq = { q, n_q, min_depth, sum, covered, false, NULL, 0u, NULL, NULL, NULL, 0u, NULL };
     uint64_t text_bytes = 0, n_runs = 0;
     return decode_targets_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
                                n_contigs, t, CBC_TARGETS_DEPTH, exclude_flags, NULL, 0, &text_bytes, n_reads, &n_runs, results, &cq,
@@ -2034,29 +2074,37 @@ API int cbc_gpu_decode_coverage(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in
 }
 
 /* read counts and depth thresholds per query: cbc_gpu_decode_coverage with the mark pass that notes
- * the pieces' first slots, then the start points, the thresholds' weights, scans and prefixes and one lookup (cbc_covx_body.h) */
-API int cbc_gpu_decode_coverage_ext(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+ * the pieces' first slots, then the start points, the thresholds' weights, scans and prefixes and one lookup (cbc_covx_body.h);
+ * with n_quant != 0 the depth quantiles per query behind them: one wavefront per query selects them
+ * from the change points (cbc_quant_body.h) */
+static int decode_coverage_ext_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                                     uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
                                     const uint32_t *block_contig, const char *names, uint32_t names_bytes,
                                     const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_gpu_targets *t,
                                     uint32_t iv_first, uint32_t iv_count, const uint32_t *q, uint32_t n_q, uint32_t exclude_flags,
                                     uint32_t min_depth, uint64_t *sum, uint32_t *covered, uint64_t *n_reads, cbc_block_result *results,
-                                    const uint32_t *thresholds, uint32_t n_thr, uint32_t *thr_covered, uint32_t *reads)
+                                    const uint32_t *thresholds, uint32_t n_thr, uint32_t *thr_covered, uint32_t *reads,
+                                    const uint32_t *quantiles, uint32_t n_quant, uint32_t *quant_depth)
 {
-    if (!ctx || !t || !n_reads || (n_q && (!q || !sum || !covered)) || (n_thr && !thresholds) || (n_q && n_thr && !thr_covered)) return CBC_E_ARG;
+    if (!ctx || !t || !n_reads || (n_q && (!q || !sum || !covered)) || (n_thr && !thresholds) || (n_q && n_thr && !thr_covered) ||
+        (n_quant && (!quantiles || (n_q && !quant_depth)))) return CBC_E_ARG;
     *n_reads = 0;
     if (n_q) { memset(sum, 0, (size_t)n_q * 8); memset(covered, 0, (size_t)n_q * 4); }
-    if (n_q <= (1u << 24) && n_thr <= CBC_COVX_MAX_THR) {
+    if (n_q <= (1u << 24) && n_thr <= CBC_COVX_MAX_THR && n_quant <= CBC_QUANT_MAX) {
         if (n_thr) memset(thr_covered, 0, (size_t)n_q * n_thr * 4);
         if (reads) memset(reads, 0, (size_t)n_q * 4);
+        if (n_quant && n_q) memset(quant_depth, 0, (size_t)n_q * n_quant * 4);
     }
     if (min_depth < 1 || n_q > (1u << 24) || iv_count < 1 || iv_first > t->n_iv || iv_count > t->n_iv - iv_first)
         return set_err(ctx, CBC_E_ARG, "coverage wants min_depth >= 1, at most 2^24 queries and the contig's intervals inside the table", hipSuccess);
     bool asc = n_thr <= CBC_COVX_MAX_THR;
     for (uint32_t i = 0; asc && i < n_thr; i++) asc = thresholds[i] >= 1u && (i == 0 || thresholds[i] > thresholds[i - 1]);
     if (!asc) return set_err(ctx, CBC_E_ARG, "coverage wants at most 8 thresholds, each >= 1 and strictly ascending", hipSuccess);
+    asc = n_quant <= CBC_QUANT_MAX;
+    for (uint32_t i = 0; asc && i < n_quant; i++) asc = quantiles[i] <= 100u && (i == 0 || quantiles[i] > quantiles[i - 1]);
+    if (!asc) return set_err(ctx, CBC_E_ARG, "coverage wants 1 to 8 quantiles, percentages in 0..100 and strictly ascending", hipSuccess);
     if (n_q == 0) return CBC_OK;
-    const cov_req cq = { q, n_q, min_depth, sum, covered, true, thresholds, n_thr, thr_covered, reads };
+    const cov_req cq = { q, n_q, min_depth, sum, covered, true, thresholds, n_thr, thr_covered, reads, quantiles, n_quant, quant_depth };
     uint64_t text_bytes = 0, n_runs = 0;
     const int rc = decode_targets_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes,
                                        contig_name_off, n_contigs, t, CBC_TARGETS_DEPTH, exclude_flags, NULL, 0, &text_bytes, n_reads, &n_runs,
@@ -2065,8 +2113,22 @@ API int cbc_gpu_decode_coverage_ext(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_
         memset(sum, 0, (size_t)n_q * 8); memset(covered, 0, (size_t)n_q * 4);
         if (n_thr) memset(thr_covered, 0, (size_t)n_q * n_thr * 4);
         if (reads) memset(reads, 0, (size_t)n_q * 4);
+        if (n_quant) memset(quant_depth, 0, (size_t)n_q * n_quant * 4);
     }
     return rc;
+}
+
+API int cbc_gpu_decode_coverage_ext(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                    uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                                    const uint32_t *block_contig, const char *names, uint32_t names_bytes,
+                                    const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_gpu_targets *t,
+                                    uint32_t iv_first, uint32_t iv_count, const uint32_t *q, uint32_t n_q, uint32_t exclude_flags,
+                                    uint32_t min_depth, uint64_t *sum, uint32_t *covered, uint64_t *n_reads, cbc_block_result *results,
+                                    const uint32_t *thresholds, uint32_t n_thr, uint32_t *thr_covered, uint32_t *reads)
+{
+    return decode_coverage_ext_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
+                                   n_contigs, t, iv_first, iv_count, q, n_q, exclude_flags, min_depth, sum, covered, n_reads, results, thresholds,
+                                   n_thr, thr_covered, reads, NULL, 0u, NULL);
 }
 
 /* kernel times of the most recent cbc_gpu_decode_coverage_ext: cov_ms[7] as cbc_gpu_last_coverage_ms gives them (the mark is
@@ -2080,6 +2142,35 @@ API int cbc_gpu_last_coverage_ext_ms(cbc_gpu_ctx *ctx, float *cov_ms, float *ext
     for (int i = 0; i < 7; i++) out[i] = cov_ms + i;
     for (int i = 0; i < 5; i++) out[7 + i] = ext_ms + i;
     return last_ms(ctx, ev, out, 12);
+}
+
+/* depth quantiles per query; n_quant == 0: the call above */
+API int cbc_gpu_decode_coverage_quant(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                      uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                                      const uint32_t *block_contig, const char *names, uint32_t names_bytes,
+                                      const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_gpu_targets *t,
+                                      uint32_t iv_first, uint32_t iv_count, const uint32_t *q, uint32_t n_q, uint32_t exclude_flags,
+                                      uint32_t min_depth, uint64_t *sum, uint32_t *covered, uint64_t *n_reads, cbc_block_result *results,
+                                      const uint32_t *thresholds, uint32_t n_thr, uint32_t *thr_covered, uint32_t *reads,
+                                      const uint32_t *quantiles, uint32_t n_quant, uint32_t *quant_depth)
+{
+    return decode_coverage_ext_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
+                                   n_contigs, t, iv_first, iv_count, q, n_q, exclude_flags, min_depth, sum, covered, n_reads, results, thresholds,
+                                   n_thr, thr_covered, reads, quantiles, n_quant, quant_depth);
+}
+
+/* kernel times of the most recent cbc_gpu_decode_coverage_quant: cov_ms[7] and ext_ms[5] as cbc_gpu_last_coverage_ext_ms gives
+ * them, quant_ms[1] the selection */
+API int cbc_gpu_last_coverage_quant_ms(cbc_gpu_ctx *ctx, float *cov_ms, float *ext_ms, float *quant_ms)
+{
+    if (!ctx || !cov_ms || !ext_ms || !quant_ms || ctx->last_post != POST_COVQ) return CBC_E_ARG;
+    const hipEvent_t ev[] = { ctx->ev_rg[0], ctx->ev_rg[1], ctx->ev_rg[2], ctx->ev_rg[3], ctx->ev_cov[0], ctx->ev_cov[1], ctx->ev_cov[2], ctx->ev_cov[3],
+                              ctx->ev_covx[0], ctx->ev_covx[1], ctx->ev_covx[2], ctx->ev_covx[3], ctx->ev_covx[4], ctx->ev_quant };
+    float *out[13];
+    for (int i = 0; i < 7; i++) out[i] = cov_ms + i;
+    for (int i = 0; i < 5; i++) out[7 + i] = ext_ms + i;
+    out[12] = quant_ms;
+    return last_ms(ctx, ev, out, 13);
 }
 
 /* depth histogram: the depth form of cbc_gpu_decode_targets up to the change points, laid over all the

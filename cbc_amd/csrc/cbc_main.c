@@ -60,6 +60,10 @@ static void usage(const char *p)
             "         --thresholds T1,T2,... (with --bedcov: 1 to 8 depths, ascending; one more column each, the positions with depth >= Ti)\n"
             "         --count-reads (with --bedcov: a last column, the kept reads with at least one covered base in the query; a read\n"
             "                        that overlaps two queries counts in both)\n"
+            "         --quantiles P1,P2,... (with --bedcov: 1 to 8 percentages in 0..100, ascending; one more column each, behind the\n"
+            "                                thresholds' and in front of the read count: the depth of rank max(1, ceil(P * len / 100))\n"
+            "                                among the query's positions, zeros included -- 0 the minimum, 50 the lower median, 100\n"
+            "                                the maximum)\n"
             "         --depth-hist (per contig and depth how many positions have it: NAME, depth, bases, positions counted, fraction\n"
             "                       with six decimals; then the same summed under the name genome; depth as for --depth; whole contigs,\n"
             "                       or the merged intervals of --region / --regions-file; binned on the device; takes\n"
@@ -481,6 +485,8 @@ int main(int argc, char **argv)
     uint32_t cov_min_depth = 1;
     int count_reads = 0, thr_given = 0;
     uint32_t thr[8], n_thr = 0;
+    int quant_given = 0;
+    uint32_t pct[8], n_pct = 0;
     int depth_hist = 0, hist_max_given = 0;
     uint32_t hist_max = 0;
     int stats_out = 0, stats_excl_given = 0;
@@ -527,6 +533,20 @@ int main(int argc, char **argv)
             }
             if (!ok) { fprintf(stderr, "cbc: --thresholds wants 1 to 8 depths in 1..4294967295, separated by commas and strictly ascending\n"); return 1; }
             thr_given = 1; continue;
+        }
+        if (!strcmp(a, "--quantiles") && i + 1 < argc) {          /* P1,P2,...: 1 to 8 decimal percentages, strictly ascending */
+            const char *v = argv[++i];
+            int ok = v[0] != 0;
+            n_pct = 0;
+            while (ok && *v) {
+                char *e = NULL;
+                const unsigned long long x = strtoull(v, &e, 10);
+                ok = v[0] >= '0' && v[0] <= '9' && e && e - v <= 3 && x <= 100 && n_pct < 8 && (n_pct == 0 || x > pct[n_pct - 1]) &&
+                     (*e == 0 || (*e == ',' && e[1] != 0));
+                if (ok) { pct[n_pct++] = (uint32_t)x; v = *e ? e + 1 : e; }
+            }
+            if (!ok) { fprintf(stderr, "cbc: --quantiles wants 1 to 8 percentages in 0..100, separated by commas and strictly ascending\n"); return 1; }
+            quant_given = 1; continue;
         }
         if (!strcmp(a, "--depth-hist")) { depth_hist = 1; continue; }
         if (!strcmp(a, "--stats")) { stats_out = 1; continue; }
@@ -577,7 +597,8 @@ int main(int argc, char **argv)
         { "--sam", sam_out, NULL, NULL },
         { "--depth", depth_out, "--depth and --sam are two different outputs", NULL },
         { "--bedcov", bedcov, "--bedcov, --depth and --sam are different outputs",
-          window_given ? "--window" : min_depth_given ? "--min-depth" : thr_given ? "--thresholds" : count_reads ? "--count-reads" : NULL },
+          window_given ? "--window" : min_depth_given ? "--min-depth" : thr_given ? "--thresholds" : count_reads ? "--count-reads" :
+          quant_given ? "--quantiles" : NULL },
         { "--depth-hist", depth_hist, "--depth-hist, --bedcov, --depth and --sam are different outputs", hist_max_given ? "--hist-max" : NULL },
         { "--stats", stats_out, "--stats, --depth-hist, --bedcov, --depth and --sam are different outputs", stats_excl_given ? "--stats-exclude-flags" : NULL },
     };
@@ -592,9 +613,9 @@ int main(int argc, char **argv)
         return cbc_cli_decompress_hist(files[0], files[1], files[2], device, regions, n_regions, regions_file, hist_max, depth_exclude, verbose);
     if (depth_excl_given && !depth_out && !bedcov) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
     if (stats_out) return cbc_cli_decompress_stats(files[0], files[1], files[2], device, regions, n_regions, regions_file, stats_exclude, verbose);
-    if (bedcov)                                                   /* no --thresholds, no --count-reads: n_thr is 0, the plain summary */
+    if (bedcov)                                                   /* no --thresholds, --count-reads, --quantiles: the plain summary */
         return cbc_cli_decompress_bedcov(files[0], files[1], files[2], device, regions, n_regions, regions_file, cov_window, cov_min_depth,
-                                         depth_exclude, verbose, thr, n_thr, count_reads);
+                                         depth_exclude, verbose, thr, n_thr, count_reads, pct, n_pct);
     /* several --region or a BED file: their union in one pass; exactly one --region and no file: the single-region paths */
     if (regions_file || n_regions > 1)
         return cbc_cli_decompress_targets(files[0], files[1], files[2], device, regions, n_regions, regions_file,

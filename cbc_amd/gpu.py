@@ -253,6 +253,10 @@ def lib():
                                                                                        ctypes.c_void_p]
         L.cbc_gpu_last_coverage_ext_ms.restype = ctypes.c_int
         L.cbc_gpu_last_coverage_ext_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+        L.cbc_gpu_decode_coverage_quant.restype = ctypes.c_int
+        L.cbc_gpu_decode_coverage_quant.argtypes = L.cbc_gpu_decode_coverage_ext.argtypes + [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+        L.cbc_gpu_last_coverage_quant_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_coverage_quant_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 3
         L.cbc_gpu_last_coverage_ms.restype = ctypes.c_int
         L.cbc_gpu_last_coverage_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 7
         L.cbc_gpu_decode_depth_hist.restype = ctypes.c_int
@@ -295,7 +299,8 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_decode_depth", "cbc_gpu_last_depth_ms", "cbc_gpu_decode_targets", "cbc_gpu_last_targets_ms",
            "cbc_gpu_decode_coverage", "cbc_gpu_last_coverage_ms", "cbc_gpu_decode_depth_hist", "cbc_gpu_last_hist_ms", "cbc_gpu_decode_stats",
            "cbc_gpu_last_stats_ms",
-           "cbc_gpu_decode_coverage_ext", "cbc_gpu_last_coverage_ext_ms"]
+           "cbc_gpu_decode_coverage_ext", "cbc_gpu_last_coverage_ext_ms",
+           "cbc_gpu_decode_coverage_quant", "cbc_gpu_last_coverage_quant_ms"]
 
 
 class Encoder:
@@ -667,6 +672,28 @@ class Encoder:
         (uint32: the kept reads with at least one covered base in the query) follow covered, in that order.  With
         results=True the per-block decode results of the blocks decoded are appended and a failed block passes (it contributes
         nothing); otherwise it raises CbcGpuError."""
+        return self._coverage(plan, queries, exclude_flags, min_depth, results, thresholds, count_reads, ())
+
+    def decode_coverage_quant(self, plan: "host.UnpackPlan", queries, quantiles, exclude_flags=0, min_depth=1, results=False,
+                              thresholds=(), count_reads=False):
+        """decode_coverage with the depth quantiles of every query (cbc_gpu_decode_coverage_quant).  quantiles: 1 to 8 integer
+        percentages in 0..100, strictly ascending (ValueError otherwise).  The result of decode_coverage gains quant (uint32,
+        shape [n_q, len(quantiles)]) after thr, when thresholds were asked for, and before reads, when reads were asked for;
+        results stays last.  With the depths of the query's positions sorted ascending, zeros included, quant is the value of
+        rank max(1, ceil(p * len / 100)): p = 0 the minimum, 50 the lower median, 100 the maximum; a query that selects nothing
+        gives 0."""
+        try:
+            pct = [int(p) for p in quantiles]
+            if any(p != x for p, x in zip(pct, quantiles)):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError("quantiles are 1 to 8 integer percentages in 0..100, strictly ascending") from None
+        if not 1 <= len(pct) <= 8 or any(p < 0 or p > 100 for p in pct) or any(b <= a for a, b in zip(pct, pct[1:])):
+            raise ValueError("quantiles are 1 to 8 integer percentages in 0..100, strictly ascending")
+        return self._coverage(plan, queries, exclude_flags, min_depth, results, thresholds, count_reads, pct)
+
+    def _coverage(self, plan, queries, exclude_flags, min_depth, results, thresholds, count_reads, pct):
+        """decode_coverage (pct empty) and decode_coverage_quant (pct: the checked percentages)."""
         plan.sam_header()                                     # refuses what the coordinates cannot carry, and long-read containers
         ts = queries.targets
         thr = np.ascontiguousarray([int(t) for t in thresholds], dtype=np.uint64)
@@ -675,10 +702,14 @@ class Encoder:
             raise ValueError("thresholds are 1 to 8 depths in 1 .. 2^32 - 1, strictly ascending")
         thr = thr.astype(np.uint32)
         T = len(thr)
+        pct = np.ascontiguousarray(pct, dtype=np.uint32)
+        Q = len(pct)
+        xquant = np.zeros((queries.n_q, Q), dtype=np.uint32)
         xthr = np.zeros((queries.n_q, T), dtype=np.uint32)
         xreads = np.zeros(queries.n_q, dtype=np.uint32)
         self._coverage_ms = None
         self._coverage_ext_ms = None
+        self._coverage_quant_ms = None
         caps, pay, names, noff = self._plan_args(plan)
         iv = np.ascontiguousarray(ts.iv, dtype=np.uint32)
         total = np.zeros(queries.n_q, dtype=np.uint64)
@@ -701,7 +732,15 @@ class Encoder:
                     plan.n_contigs, ctypes.byref(tg), int(ts.contig_first[c]), ni, q.ctypes.data, len(idx),
                     int(exclude_flags), int(min_depth), s.ctypes.data, cv.ctypes.data, ctypes.byref(nrd),
                     res.ctypes.data)
-            if ext:
+            if Q:
+                tc, rd = np.zeros((len(idx), T), dtype=np.uint32), np.zeros(len(idx), dtype=np.uint32)
+                qd = np.zeros((len(idx), Q), dtype=np.uint32)
+                rc = lib().cbc_gpu_decode_coverage_quant(*args, thr.ctypes.data if T else None, T, tc.ctypes.data if T else None,
+                                                         rd.ctypes.data if count_reads else None, pct.ctypes.data, Q, qd.ctypes.data)
+                self._check_blocks(rc, "cbc_gpu_decode_coverage_quant", results)
+                self._add_ms("_coverage_quant_ms", "cbc_gpu_last_coverage_quant_ms", 13, at=(0, 7, 12))
+                xthr[idx], xreads[idx], xquant[idx] = tc, rd, qd
+            elif ext:
                 tc, rd = np.zeros((len(idx), T), dtype=np.uint32), np.zeros(len(idx), dtype=np.uint32)
                 rc = lib().cbc_gpu_decode_coverage_ext(*args, thr.ctypes.data if T else None, T, tc.ctypes.data if T else None,
                                                        rd.ctypes.data if count_reads else None)
@@ -717,6 +756,8 @@ class Encoder:
         out = (queries.contig.copy(), queries.start0.copy(), queries.end0.copy(), total, covered)
         if T:
             out += (xthr,)
+        if Q:
+            out += (xquant,)
         if count_reads:
             out += (xreads,)
         if results:
@@ -737,6 +778,13 @@ class Encoder:
         if getattr(self, "_coverage_ext_ms", None) is None:
             raise CbcGpuError("no decode_coverage with thresholds or count_reads has run on the device")
         return self._coverage_ext_ms
+
+    def last_coverage_quant_ms(self):
+        """Kernel milliseconds of the last decode_coverage_quant, summed over its calls: the twelve of
+        last_coverage_ext_ms, then the selection pass."""
+        if getattr(self, "_coverage_quant_ms", None) is None:
+            raise CbcGpuError("no decode_coverage_quant has run on the device")
+        return self._coverage_quant_ms
 
     def decode_depth_hist(self, plan: "host.UnpackPlan", targets=None, exclude_flags=0, max_depth=0, results=False):
         """Depth histogram (cbc_gpu_decode_depth_hist): per contig how many positions have each depth; depth as decode_depth

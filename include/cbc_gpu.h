@@ -438,6 +438,32 @@ int  cbc_gpu_decode_coverage_ext(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t i
  * takes no time. */
 int  cbc_gpu_last_coverage_ext_ms(cbc_gpu_ctx *ctx, float *cov_ms /* 7 */, float *ext_ms /* 5 */);
 
+/* ---- per-query depth quantiles ------------------------------------------------------------------------
+ * cbc_gpu_decode_coverage_ext with one more answer per query, selected on the device from the change points that call leaves:
+ *   quantiles[n_quant]      1 .. CBC_QUANT_MAX integer percentages in 0..100, strictly ascending (CBC_E_ARG otherwise);
+ *                           n_quant == 0: the call is cbc_gpu_decode_coverage_ext
+ *   quant_depth[n_q * n_quant] query-major: with the depths of the len positions of query i sorted ascending, d(0) <= .. <=
+ *                           d(len - 1), the value d(k - 1) for k = max(1, ceil(p * len / 100)) -- the nearest-rank (lower)
+ *                           quantile: p = 0 the minimum, 50 the lower median, 100 the maximum.  Zero-depth positions count.
+ *                           A query of no position gives 0.
+ * One wavefront selects all quantiles of one query; its table is in LDS, so the pass takes no device memory beyond 4 more bytes
+ * per quantile and query in the result arena, which also come back.  One chunk, one stream, no host round trip between the
+ * kernels.  A block that fails to decode contributes nothing and the call returns CBC_E_BLOCK with all five outputs zeroed. */
+#define CBC_QUANT_MAX 8u
+int  cbc_gpu_decode_coverage_quant(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                   uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                                   const uint32_t *block_contig /* n_blocks */, const char *names, uint32_t names_bytes,
+                                   const uint32_t *contig_name_off /* n_contigs */, uint32_t n_contigs, const cbc_gpu_targets *t,
+                                   uint32_t iv_first, uint32_t iv_count, const uint32_t *q /* n_q pairs slot, len */, uint32_t n_q,
+                                   uint32_t exclude_flags, uint32_t min_depth, uint64_t *sum, uint32_t *covered, uint64_t *n_reads,
+                                   cbc_block_result *results /* n_blocks or NULL */, const uint32_t *thresholds, uint32_t n_thr,
+                                   uint32_t *thr_covered /* n_q * n_thr, query-major */, uint32_t *reads /* n_q or NULL */,
+                                   const uint32_t *quantiles, uint32_t n_quant,
+                                   uint32_t *quant_depth /* n_q * n_quant, query-major */);
+/* Kernel times of the most recent cbc_gpu_decode_coverage_quant (with n_quant >= 1): cov_ms[7] and ext_ms[5] as
+ * cbc_gpu_last_coverage_ext_ms gives them, quant_ms[1] the selection pass. */
+int  cbc_gpu_last_coverage_quant_ms(cbc_gpu_ctx *ctx, float *cov_ms /* 7 */, float *ext_ms /* 5 */, float *quant_ms /* 1 */);
+
 /* ---- depth histogram --------------------------------------------------------------------------------
  * The depth form of cbc_gpu_decode_targets -- the selected blocks of ONE contig, decoded once, marked in the compressed
  * coordinate of all the contig's merged intervals (t, iv_first, iv_count as for cbc_gpu_decode_coverage) -- without the text:
