@@ -229,6 +229,11 @@ struct CbcWin {
 #endif
 };
 
+/* does the wave policy supply the lane writes under one mask (W::set_lane2_uv / W::set_lane3: cbc_wave_gpu.h)?  The
+ * CPU lock-step emulation's policy does not and gets the plain form, which writes the same lanes. */
+template <class W, class = void> struct CbcHasLaneN : std::false_type {};
+template <class W> struct CbcHasLaneN<W, std::void_t<decltype(&W::set_lane2_uv), decltype(&W::set_lane3)>> : std::true_type {};
+
 template <class W, bool GEN = false>
 struct CbcEnc {
     typedef typename W::V32 V32;
@@ -392,12 +397,28 @@ struct CbcEnc {
 #ifdef CBC_EMU_TRACE                     /* tests/emu debugging aid: log every symbol as the models emit it */
         cbc_emu_trace(cur_read, lo, cnt, n);
 #endif
-        V32 ln = W::lane();
-        Mask here = ln == q_len;
-        q_lo = W::select(here, W::splat(lo), q_lo);
-        q_cnt = W::select(here, W::splat(cnt), q_cnt);
-        q_n = W::select(here, W::splat(n), q_n);
+        q_put(lo, cnt, n);
+    }
+    /* one queue entry / one recorded step: in the block kernels all registers of the entry are written under one lane
+     * mask (W::set_lane3 / W::set_lane2_uv: no select directly behind another one in the encoding that pays for it).
+     * The GEN kernels keep the plain form: the long-read encoder is bound by vector issue, where the extra moves of the
+     * one-mask form cost more than the select pairs (cfg5 140.8 -> 142.9 ms with it, profiles/lookahead_ab.log). */
+    CBC_MFN void q_put(uint32_t lo, uint32_t cnt, uint32_t n)
+    {
+        if constexpr (!GEN && CbcHasLaneN<W>::value) W::set_lane3(q_lo, q_cnt, q_n, q_len, lo, cnt, n);
+        else {
+            V32 ln = W::lane();
+            Mask here = ln == q_len;
+            q_lo = W::select(here, W::splat(lo), q_lo);
+            q_cnt = W::select(here, W::splat(cnt), q_cnt);
+            q_n = W::select(here, W::splat(n), q_n);
+        }
         q_len++;
+    }
+    CBC_MFN void rec_put(Uv rec, Uv k3)
+    {
+        if constexpr (!GEN && CbcHasLaneN<W>::value) W::set_lane2_uv(rec_a, rec_s, rec_n, rec, k3);
+        else { W::set_lane_uv(rec_a, rec_n, rec); W::set_lane_uv(rec_s, rec_n, k3); }
     }
     /* ---- hand-off between the two wavefronts ------------------------------------------------------
      * The coder wave owns the per-record ("fixed") models and codes their symbols straight from
@@ -423,22 +444,14 @@ struct CbcEnc {
     {
         if (role != CBC_ROLE_MODEL) { drain_q(); return; }
         if (q_len >= 64u) publish(0u, 0ull);
-        V32 ln = W::lane();
-        Mask here = ln == q_len;
-        q_lo = W::select(here, W::splat(0u), q_lo); q_cnt = W::select(here, W::splat(1u), q_cnt);
-        q_n = W::select(here, W::splat(CBC_END_N), q_n);
-        q_len++;
+        q_put(0u, 1u, CBC_END_N);
     }
     /* seg_end() of the model wavefront where the caller knows the END entry fits (edits() drains at 56 entries and adds at
      * most two per check): no hand-off code at this call site */
     CBC_MFN void seg_end_fits()
     {
         W::expect_eq(q_len < 64u ? 1u : 0u, 1u, "seg_end_fits: queue full");
-        V32 ln = W::lane();
-        Mask here = ln == q_len;
-        q_lo = W::select(here, W::splat(0u), q_lo); q_cnt = W::select(here, W::splat(1u), q_cnt);
-        q_n = W::select(here, W::splat(CBC_END_N), q_n);
-        q_len++;
+        q_put(0u, 1u, CBC_END_N);
     }
     CBC_MFN void publish(uint32_t flags, uint64_t neq)
     {
@@ -462,8 +475,7 @@ struct CbcEnc {
     {
         Uv rec, k3;
         code1(lo, hi, n, flo, fhi, rec, k3);
-        W::set_lane_uv(rec_a, rec_n, rec);
-        W::set_lane_uv(rec_s, rec_n, k3);
+        rec_put(rec, k3);
         nsym++;
         if (++rec_n >= CBC_REC_PACK_AT) { pack(rec_a, rec_s, rec_n); rec_n = 0; }    /* leaves room for a record's 8 fixed symbols */
     }
@@ -482,9 +494,49 @@ struct CbcEnc {
 #ifdef CBC_ABLATE_SETLANE         /* timing experiments only */
         rec_a ^= rec; rec_s ^= k3;
 #else
-        W::set_lane_uv(rec_a, rec_n, rec);
-        W::set_lane_uv(rec_s, rec_n, k3);
+        rec_put(rec, k3);
 #endif
+        nsym++; rec_n++;
+    }
+    /* step_fixed() for a symbol that usually shifts nothing although its cum is not 0: rlength[0] with reads of one
+     * length (its count lies within 254 of the model's total, like the step_known0() symbols, but it is not symbol 0).
+     * The lower bound moves here, so thr0 does not apply and the test is the recurrence's own on l' = l + ql and
+     * u = l - 1 + qh: no E1/E2 iff bit 25 of l' ^ u is set (l' <= u: l' has it clear and u has it set), and then no E3
+     * iff not (bit 24 of l' set and bit 24 of u clear).  Such a step only moves l and the range: pack() would find
+     * k1 = k3 = 0, so it records nothing and takes no lane.  Any other step goes through the usual tail. */
+    template <class FLO, class FHI, class FN>
+    CBC_MFN void step_fixed_quiet(FLO lo_of, FHI hi_of, FN n_of, uint32_t flo, uint32_t fhi)
+    {
+#ifdef CBC_ABLATE_CODER         /* timing experiments only */
+        step_fixed(lo_of, hi_of, n_of, flo, fhi); return;
+#endif
+        Uv ql, qh, tl, th;
+        W::mul64(rng, flo, ql, tl); W::mul64(rng, fhi, qh, th);
+        if (W::uv_ge(tl | th, 0xfc000000u)) {                 /* the remainder test of code1_lazy() */
+            const uint32_t lo = lo_of(), hi = hi_of(), n = n_of();
+            ql += (rng * lo - ql * n >= n) ? 1u : 0u;
+            qh += (rng * hi - qh * n >= n) ? 1u : 0u;
+        }
+#ifndef __HIP_DEVICE_COMPILE__
+        W::expect_eq(W::uv_scalar(ql), (uint32_t)((uint64_t)W::uv_scalar(rng) * lo_of() / n_of()), "scaled_div(cum), quiet step");
+        W::expect_eq(W::uv_scalar(qh), (uint32_t)((uint64_t)W::uv_scalar(rng) * hi_of() / n_of()), "scaled_div(cum + count), quiet step");
+#endif
+        const Uv l1 = l + ql, u = lm1 + qh;
+        const Uv still = (l1 ^ u) & ~((l1 & ~u) << 1);         /* bit 25: no E1/E2 and no E3 */
+        if (W::uv_ge(still & (1u << 25), 1u)) {
+#ifndef __HIP_DEVICE_COMPILE__     /* emulation: the full recurrence agrees that nothing shifts */
+            const uint32_t lf = W::uv_scalar(l1), uf = W::uv_scalar(u);
+            W::expect_eq(W::clz32((((lf ^ uf) & CBC_M26) << 6) | 32u), 0u, "step_fixed_quiet: E1/E2 would shift");
+            W::expect_eq(W::clz32(((((~lf | uf) << 7) | 127u))), 0u, "step_fixed_quiet: E3 would shift");
+#endif
+            l = l1; rng = qh - ql;
+            set_l_forms();
+            nsym++;
+            return;
+        }
+        Uv rec, k3;
+        code_tail(ql, qh, rec, k3);
+        rec_put(rec, k3);
         nsym++; rec_n++;
     }
     /* the symbols queued by this wavefront itself (fused form; in the coder wave: its own few queued ones).
@@ -551,8 +603,7 @@ struct CbcEnc {
                     Uv rec, k3;
                     code1_lazy(W::readlane(b_fl, k), W::readlane(b_fh, k), [&]() -> uint32_t { return W::readlane(b_lo, k); },
                                [&]() -> uint32_t { return W::readlane(b_hi, k); }, [&]() -> uint32_t { return W::readlane(b_n, k); }, rec, k3);
-                    W::set_lane_uv(rec_a, rec_n, rec);
-                    W::set_lane_uv(rec_s, rec_n, k3);
+                    rec_put(rec, k3);
                     nsym++;
                     if (++rec_n >= CBC_REC_PACK_AT) { pack(rec_a, rec_s, rec_n); rec_n = 0; }
                 }
@@ -575,8 +626,7 @@ struct CbcEnc {
                 Uv rec, k3;
                 code1_lazy(W::readlane(b_fl, k), W::readlane(b_fh, k), [&]() -> uint32_t { return W::readlane(b_lo, k); },
                            [&]() -> uint32_t { return W::readlane(b_hi, k); }, [&]() -> uint32_t { return W::readlane(b_n, k); }, rec, k3);
-                W::set_lane_uv(rec_a, rec_n, rec);
-                W::set_lane_uv(rec_s, rec_n, k3);
+                rec_put(rec, k3);
                 nsym++;
                 if (++rec_n >= CBC_REC_PACK_AT) { pack(rec_a, rec_s, rec_n); rec_n = 0; }
             }
@@ -732,8 +782,7 @@ struct CbcEnc {
         }
         Uv rec, k3;
         code_tail(W::uv(0u), qh, rec, k3);
-        W::set_lane_uv(rec_a, rec_n, rec);
-        W::set_lane_uv(rec_s, rec_n, k3);
+        rec_put(rec, k3);
         rec_n++;
     }
     CBC_MFN uint32_t finish()                        /* encoder_last_step :348-363 + stream_finish_byte */
@@ -1970,9 +2019,11 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         V32 a_pos, a_fl, a_seq, a_tok;
         const uint32_t an = n_reads - g0 < 64u ? n_reads - g0 : 64u;
         const uint32_t saved = E.cur_read;
+        CBC_TS(9);                                            /* coder wave: coding */
         const bool okg = load_group(g0, a_pos, a_fl, a_seq, a_tok, true);
         neq_ahead = okg ? match_group(an, a_pos, a_fl, a_seq) : 0ull;
         E.post_group(g0 >> 6, neq_ahead, okg ? 0u : 1u);
+        CBC_TS(15);                                           /* coder wave: look-ahead (group loads, match test, post) */
         if (okg) E.cur_read = saved;
     };
     if (!fused && n_reads != 0u && E.status == CBC_ST_OK) look_ahead(0u);
@@ -2043,7 +2094,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
              *    pass; contexts 1..3 only ever code symbol 0, each once per record -- */
             {
                 const uint32_t tn = 255u + 10u * r, tf = W::readlane(t_fh, j);
-                E.step_fixed(CBC_LZ(W::readlane(F.rl_lo, j)), CBC_LZ(W::readlane(rl_hi, j)), CBC_LZ(tn), W::readlane(rl_fl, j), W::readlane(rl_fh, j));
+                E.step_fixed_quiet(CBC_LZ(W::readlane(F.rl_lo, j)), CBC_LZ(W::readlane(rl_hi, j)), CBC_LZ(tn), W::readlane(rl_fl, j), W::readlane(rl_fh, j));
                 E.step_known0(CBC_LZ(W::readlane(t_hi, j)), CBC_LZ(tn), tf);
                 E.step_known0(CBC_LZ(W::readlane(t_hi, j)), CBC_LZ(tn), tf);
                 E.step_known0(CBC_LZ(W::readlane(t_hi, j)), CBC_LZ(tn), tf);

@@ -33,6 +33,10 @@
 #include "cbc_long_body.h"
 #include "cbc_tokenise.h"
 
+/* the block kernels take their lane writes under one mask from the GPU policy; without this the body would fall back to
+ * the plain form silently (same bytes, slower) if a helper were renamed or overloaded */
+static_assert(CbcHasLaneN<WaveGPU>::value, "WaveGPU must supply set_lane2_uv and set_lane3");
+
 #define API extern "C" __attribute__((visibility("default")))
 /* internal marker: "use the context's own stream" (host-buffer entry points only) */
 #define CBC_CTX_STREAM ((void *)(uintptr_t)1)

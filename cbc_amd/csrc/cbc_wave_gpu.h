@@ -123,6 +123,21 @@ struct WaveGPU {
     static CBC_FN void mul64(Uv a, uint32_t b, Uv &hi, Uv &lo) { uint64_t p = (uint64_t)a * b; hi = (uint32_t)(p >> 32); lo = (uint32_t)p; }
     static CBC_FN Uv clz_uv(Uv x) { return (uint32_t)__builtin_clz(x); }                  /* x != 0 */
     static CBC_FN void set_lane_uv(V32 &v, uint32_t k, Uv val) { v = lane() == k ? val : v; }
+    /* Two or three registers written at lane k under ONE lane mask.  A VOP2 v_cndmask_b32 issued directly after another
+     * one costs ~23 cycles of the SIMD (profiles/r03_ubench_issue.log, tools/ub4.hip); the compiler writes the selects
+     * of one mask back to back in that encoding.  Here the mask is held in a scalar register pair and every select is
+     * the VOP3 encoding, which does not pay that. */
+    static CBC_FN void cnd_e64(V32 &v, V32 val, uint64_t m) { asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(v) : "v"(val), "s"(m)); }
+    static CBC_FN void set_lane2_uv(V32 &a, V32 &b, uint32_t k, Uv va, Uv vb)
+    {
+        const uint64_t m = __builtin_amdgcn_uicmp(lane(), k, 32);                     /* 32 = ICMP_EQ */
+        cnd_e64(a, va, m); cnd_e64(b, vb, m);
+    }
+    static CBC_FN void set_lane3(V32 &a, V32 &b, V32 &c, uint32_t k, uint32_t va, uint32_t vb, uint32_t vc)
+    {
+        const uint64_t m = __builtin_amdgcn_uicmp(lane(), k, 32);
+        cnd_e64(a, va, m); cnd_e64(b, vb, m); cnd_e64(c, vc, m);
+    }
     /* The decoder's coder state (l, range, tag - l), wave-uniform like the encoder's: in vector registers by default -- the
      * decode kernel issues 845 scalar against 502 vector instructions per record and the scalar unit is the port its
      * wavefronts queue on -- or in scalar registers with -DCBC_DEC_STATE_SCALAR (A/B).  Conditions on it go through

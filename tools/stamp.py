@@ -20,7 +20,7 @@ sums=np.zeros(16)
 for b in range(pb.n_blocks):
     o=int(blocks[b]['out_off'])+int(blocks[b]['out_cap'])-128; sums+=out[o:o+128].view(np.uint64).astype(np.float64)
     o=int(blocks[b]['out_off']); sums+=out[o:o+128].view(np.uint64).astype(np.float64)
-names=['M: grp loads+match','M: seg_end','M: run pass (positions, contexts, chars symbols, window marks one lane per SNP)','M: edits() only: to the first win_first of a record / between SNPs','M: edits() only: win_first','M: until publish','M: at barrier','M: var_code','M: chars (run_record); win_set+chars (edits())','C: coding','C: waiting','M: publish; edits() only: prefetch, window slide, token header','M: edit counts','M: rest of edits()','M: group pass (token headers, SNP counts)','-']
+names=['M: grp loads+match','M: seg_end','M: run pass (positions, contexts, chars symbols, window marks one lane per SNP)','M: edits() only: to the first win_first of a record / between SNPs','M: edits() only: win_first','M: until publish','M: at barrier','M: var_code','M: chars (run_record); win_set+chars (edits())','C: coding','C: waiting','M: publish; edits() only: prefetch, window slide, token header','M: edit counts','M: rest of edits()','M: group pass (token headers, SNP counts)','C: look-ahead (group loads, validation, match test, post; before: inside C: coding)']
 tot=sums.sum()
 for n,v in zip(names,sums): print('%-12s %8.0f cycles/read  %5.1f%%'%(n, v/pb.n_recs, 100*v/tot))
 print('total stamped cycles/read', tot/pb.n_recs)
