@@ -397,6 +397,77 @@ int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, i
     return 0;
 }
 
+/* `cbc -d|-x ... --pileup [--region NAME[:BEG[-END]]]`: what the reads show at the positions where they disagree with the
+ * reference, counted and formatted on the device (cbc_gpu_decode_pileup): one call for the region's
+ * window, or one per contig that has blocks, in the order of the contig table, the texts appended.  Only the lines cross PCIe.
+ * A call starts with a buffer of 64 MiB + 64 bytes per read of its blocks (or the bound, if that is less); the library reports
+ * the size of a text that does not fit, and the call is made once more with exactly that. */
+int cbc_cli_decompress_pileup(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,
+                              uint32_t min_alt, uint32_t edits_per_read, int verbose)
+{
+    cli_run r;
+    if (cli_open(&r, in, ref, NULL, device, "--pileup", "stores no contig table")) return 1;
+    const cbc_unpack_plan *u = r.u;
+    char err[512];
+    if (cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) < 0) { fprintf(stderr, "cbc: --pileup: %s\n", err[0] ? err : "the contig table is not usable"); return 1; }
+    const uint32_t n_calls = region ? 1u : u->n_contigs;
+    cbc_region_sel *sels = (cbc_region_sel *)calloc(n_calls ? n_calls : 1u, sizeof(cbc_region_sel));
+    if (!sels) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    int rc;
+    for (uint32_t k = 0; k < n_calls; k++) {
+        rc = region ? cbc_unpack_region(u, region, &sels[k], err, sizeof err) : cbc_unpack_contig_blocks(u, k, &sels[k], err, sizeof err);
+        if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT ? err : "block selection failed"); return 1; }
+    }
+    r.t1 = now2();
+    FILE *fo = fopen(out, "wb");
+    if (!fo) return cannot_write(out);
+    uint64_t total = 0, lines = 0, kept = 0, have = 0;
+    char *text = NULL;
+    uint32_t blocks_used = 0;
+    float ms[4] = { 0, 0, 0, 0 }, m[4];
+    for (uint32_t k = 0; k < n_calls; k++) {
+        const cbc_region_sel *s = &sels[k];
+        const uint32_t nb = s->b1 - s->b0;
+        if (!nb) continue;                              /* no block can hold a read of the window: no line, no device needed */
+        if (cli_device(&r)) return 1;
+        const double b = now2();
+        const char *nm = u->names + u->contig_name_off[s->contig];
+        const uint64_t bound = cbc_unpack_pileup_text_cap(u, s->b0, s->b1, s->contig, s->beg, s->end, s->smax);
+        uint64_t first = 64ull << 20, tb = 0, nl = 0, nk = 0;
+        for (uint32_t q = s->b0; q < s->b1; q++) first += 64ull * u->blocks[q].n_reads;
+        uint64_t cap = bound < first ? bound : first;
+        for (int attempt = 0; attempt < 2; attempt++) {
+            if (cap > have) { free(text); text = (char *)malloc((size_t)cap + 1); have = cap; }
+            if (!text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+            rc = cbc_gpu_decode_pileup(r.ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
+                                       nm, (uint32_t)strlen(nm), s->beg, s->end, s->smax, exclude, min_alt, edits_per_read,
+                                       (uint8_t *)text, cap, &tb, &nl, &nk, NULL);
+            if (!(rc == CBC_E_ARG && tb > cap && tb <= bound)) break;
+            cap = tb;                                   /* the text's own size */
+        }
+        if (rc) { fprintf(stderr, "cbc: pileup failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
+        r.t_dev += now2() - b;
+        if (verbose && cbc_gpu_last_pileup_ms(r.ctx, &m[0], &m[1], &m[2], &m[3]) == 0) add_ms(ms, m, 4);
+        if (tb && fwrite(text, 1, (size_t)tb, fo) != (size_t)tb) return cannot_write(out);
+        total += tb; lines += nl; kept += nk; blocks_used += nb;
+    }
+    if (fclose(fo) != 0) return cannot_write(out);
+    if (region)
+        printf("pileup of %s:%llu-%llu: %llu positions from %llu reads in %u of %u blocks\n", u->names + u->contig_name_off[sels[0].contig],
+               (unsigned long long)sels[0].beg, (unsigned long long)sels[0].end, (unsigned long long)lines, (unsigned long long)kept,
+               blocks_used, u->n_blocks);
+    else printf("pileup: %llu positions from %llu reads in %u blocks\n", (unsigned long long)lines, (unsigned long long)kept, blocks_used);
+    if (verbose) {
+        printf("pileup: %llu text bytes, exclude flags 0x%x, min alt %u, edits per read %u\n", (unsigned long long)total, exclude, min_alt,
+               edits_per_read ? edits_per_read : CBC_EDITS_PER_READ);
+        printf("time: read + plan %.3f s, device init + reference upload %.3f s, decode + pileup + write %.3f s\n", r.t1 - r.t0, r.t_init, r.t_dev);
+        if (r.used) printf("kernels: edits decode %.3f ms, mark + events %.3f ms, scans %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
+    }
+    free(text); free(sels);
+    cli_close(&r);
+    return 0;
+}
+
 /* `cbc -d|-x ... --region A --region B ... [--regions-file FILE]`: the union of the loci in one pass.
  * The target set and its blocks come from cbc_unpack_targets; reads and SAM are one call over the selected blocks of all
  * contigs, the depth one call per contig that has intervals and blocks, the texts appended in contig-table order. */

@@ -61,6 +61,20 @@ struct cbc_dec_args {
     uint32_t n_blocks, cap_pos, cap_var;
 };
 
+/* EDITS = true (cbc_decode_blocks_edits_kernel): where the edit-reporting decoder leaves the alignment
+ * of the reads with indels.  Block blk owns entries [rec_base * per_read, (rec_base + n_reads) * per_read) of `arena`, 16 bits
+ * each: per such record its nDel matched coordinates (edits_indel's dels[]), then its nIns read indices (insl[] >> 8), in decode
+ * order.  A coordinate is a sum of at most 255 var symbols below 256 and a read index adds at most 254 to one: both stay below
+ * 2^16.  side[2 r] = the record's first entry, relative to the block's; side[2 r + 1] = nDel | nIns << 16 (0 for every read
+ * without indels). */
+struct cbc_dec_edits {
+    uint32_t *side;          /* 2 words per record, indexed like recs                  */
+    uint16_t *arena;
+    uint64_t  arena_entries; /* entries behind `arena`                                 */
+    uint32_t  per_read;      /* a block's capacity = n_reads * per_read entries        */
+    uint32_t  reserved;
+};
+
 CBC_FN uint32_t cbc_basechar(uint32_t b)             /* basepair2char sam_models.c:23-33 */
 {
     return b == 0u ? 'A' : b == 1u ? 'C' : b == 2u ? 'G' : b == 3u ? 'T' : 'N';
@@ -1001,10 +1015,14 @@ struct CbcDec {
 /* SPAN = true (region decode, cbc_gpu_decode_region): the fourth word of every record (cbc_read_rec.tok_off, 0 otherwise)
  * receives the read's span -- the reference bases its reconstruction covers: rl for a read coded as perfect, rl + nDel - nIns
  * for any other -- and a span above `smax` fails the block with CBC_ST_SPAN, so the bound the block selection rests on is
- * checked on every decode that relies on it.  The default instantiation is the plain decoder, unchanged. */
-template <class W, bool SPAN = false>
-CBC_FN void cbc_decode_stream(const cbc_dec_args &A, uint32_t blk, uint32_t *lds, uint32_t smax = 0u)
+ * checked on every decode that relies on it.  The default instantiation is the plain decoder, unchanged.
+ * EDITS = true (with SPAN): a record with indels also leaves its deletion coordinates and insertion indices in E's arena and
+ * every record its entry in E's side array (cbc_dec_edits); a block whose entries pass its capacity fails with CBC_ST_EDITS
+ * before anything is written past it.  Neither of the other two instantiations holds a line of it. */
+template <class W, bool SPAN = false, bool EDITS = false>
+CBC_FN void cbc_decode_stream(const cbc_dec_args &A, uint32_t blk, uint32_t *lds, uint32_t smax = 0u, const cbc_dec_edits *E = nullptr)
 {
+    static_assert(SPAN || !EDITS, "the edit-reporting decoder reports the spans too");
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
     const V32 ln = W::lane();
@@ -1033,6 +1051,15 @@ CBC_FN void cbc_decode_stream(const cbc_dec_args &A, uint32_t blk, uint32_t *lds
     D.tail_valid = in_bytes & 3u;
     if (!args_ok) { D.nwords_in = 0; D.fail(CBC_ST_ASSERT); }
     if (n_reads > CBC_MAX_BLOCK_READS) D.fail(CBC_ST_UNSUPPORTED);   /* the closed forms below assume no rescale */
+    /* EDITS: the block's part of the arena and of the side array; ed_used = entries taken so far */
+    uint16_t *ed_arena = nullptr; uint32_t *ed_side = nullptr; uint32_t ed_cap = 0u, ed_used = 0u;
+    if constexpr (EDITS) {
+        const uint64_t cap64 = (uint64_t)n_reads * E->per_read, base64 = rec_base * E->per_read;
+        /* args_ok: rec_base + n_reads <= n_recs < 2^40 or so, per_read <= 510: no product wraps */
+        if (args_ok && E->per_read >= 1u && E->per_read <= 510u && cbc_fits64(base64, cap64, E->arena_entries)) {
+            ed_arena = E->arena + base64; ed_side = E->side + 2u * rec_base; ed_cap = (uint32_t)cap64;
+        } else D.fail(CBC_ST_ASSERT);
+    }
 
     for (uint32_t b = 0; b < CBC_DLDS_FIXED; b += 64u) W::store32(lds, ln + b, W::splat(0u), (ln + b) < CBC_DLDS_FIXED);
     D.rlen_n = 255u; D.rl123_c0 = 1u; D.rl123_n = 255u; D.snps_n = L0; D.indels_n = L0; D.rn_count = 0;
@@ -1165,6 +1192,10 @@ CBC_FN void cbc_decode_stream(const cbc_dec_args &A, uint32_t blk, uint32_t *lds
         }
         V32 rv0 = W::splat(pos), rv1 = W::splat(flag | (rl << 16)), rv2 = W::splat(r * stride), rv3 = W::splat(span);
         W::store_rec(recs4, W::splat(r), ln == 0u, rv0, rv1, rv2, rv3);
+        if constexpr (EDITS) {                                /* lanes 0, 1: first entry, counts */
+            const uint32_t nd = match ? 0u : nDel, ni = match ? 0u : nIns;
+            W::store32(ed_side, ln + 2u * r, W::select(ln == 0u, W::splat((nd | ni) ? ed_used - nd - ni : 0u), W::splat(nd | (ni << 16))), ln < 2u);
+        }
         CBC_DT(6);                                            /* record store */
     };
     /* a record from step `from` on with every model in its complete form (record 0, and what the loop deferred) */
@@ -1188,7 +1219,23 @@ CBC_FN void cbc_decode_stream(const cbc_dec_args &A, uint32_t blk, uint32_t *lds
         if (from == 2u) { nDel = 0; nIns = 0; D.indel_counts(rl, nSnp, nDel, nIns); }
         if (ok() && !match) {
             if ((nDel | nIns) == 0u) D.edits_snp(rl, strand, nSnp, refw, dst);
-            else D.edits_indel(pos, rl, strand, nSnp, nDel, nIns, dst, refb, tmpb, lds + CBC_DLDS_TMP, dels, insl);
+            else {
+                D.edits_indel(pos, rl, strand, nSnp, nDel, nIns, dst, refb, tmpb, lds + CBC_DLDS_TMP, dels, insl);
+                if constexpr (EDITS) {
+                    /* the lists edits_indel() has just filled, out of LDS one lane per entry: nDel, nIns <= 255 each */
+                    const uint32_t ne = nDel + nIns;
+                    if (ok() && ne > ed_cap - ed_used) D.fail(CBC_ST_EDITS);
+                    if (ok()) {
+                        for (uint32_t b = 0; b < ne; b += 64u) {
+                            const V32 e = ln + b;
+                            const Mask isd = e < nDel, isi = !isd & (e < ne);
+                            const V32 dv_ = W::load32(dels, e, isd, 0u), iv_ = W::load32(insl, e - nDel, isi, 0u) >> 8;
+                            W::store16(ed_arena, e + ed_used, W::select(isd, dv_, iv_), isd | isi);
+                        }
+                        ed_used += ne;
+                    }
+                }
+            }
         }
         if (ok()) ph_store(r);
     };

@@ -3,7 +3,7 @@
  * (cbc_gpu_decode_depth, include/cbc_gpu.h).
  *
  * Depth at reference position p = the kept reads with POS <= p <= POS + span - 1 (a SPAN coverage: the bases a read
- * deletes count as covered, the file does not say where in the read they lie).  POS = window_start + local POS, span as
+ * deletes count as covered: this pass reads the span alone, cbc_pileup_body.h reads where they lie).  POS = window_start + local POS, span as
  * the decoder reports it (cbc_region_body.h); kept = the reads cbc_region_keep keeps for the window [beg, end], minus
  * those with FLAG & exclude != 0 or span == 0.  The output is bedGraph, one line per maximal run of equal non-zero depth
  * inside the window, 0-based half-open:   <name>\t<start0>\t<end0>\t<depth>\n

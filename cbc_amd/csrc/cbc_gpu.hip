@@ -28,6 +28,7 @@
 #include "cbc_quant_body.h"
 #include "cbc_hist_body.h"
 #include "cbc_stats_body.h"
+#include "cbc_pileup_body.h"
 #include "cbc_plan.h"
 #include "cbc_stream_body.h"
 #include "cbc_long_body.h"
@@ -89,6 +90,26 @@ cbc_decode_blocks_span_kernel(cbc_dec_args A, uint32_t smax)
     if (blk >= A.n_blocks) return;
     cbc_decode_stream<WaveGPU, true>(A, blk, cbc_lds, smax);
 }
+
+/* per-position allele counts (cbc_gpu_decode_pileup, cbc_pileup_body.h): the span decoder that also leaves the alignment of
+ * the reads with indels (cbc_dec_edits); then, behind cbc_depth_mark_kernel, CBC_PILEUP_WAVES wavefronts per block add the
+ * mismatches, deleted bases and insertion events, and one wavefront per tile of positions counts and writes the lines */
+__global__ void __launch_bounds__(64)
+cbc_decode_blocks_edits_kernel(cbc_dec_args A, uint32_t smax, cbc_dec_edits E)
+{
+    uint32_t blk = blockIdx.x;
+    if (blk >= A.n_blocks) return;
+    cbc_decode_stream<WaveGPU, true, true>(A, blk, cbc_lds, smax, &E);
+}
+__global__ void __launch_bounds__(64 * CBC_PILEUP_WAVES)
+cbc_pileup_events_kernel(cbc_pileup_args A)
+{
+    if (blockIdx.x < A.D.R.n_blocks) cbc_pileup_events<WaveGPU>(A, blockIdx.x, WaveGPU::uni(threadIdx.x >> 6), CBC_PILEUP_WAVES);
+}
+__global__ void __launch_bounds__(64)
+cbc_pileup_count_kernel(cbc_pileup_args A) { cbc_pileup_count<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_pileup_write_kernel(cbc_pileup_args A) { cbc_pileup_write<WaveGPU>(A, blockIdx.x); }
 
 __global__ void __launch_bounds__(64)
 cbc_region_count_kernel(cbc_region_args A) { if (blockIdx.x < A.n_blocks) cbc_region_count<WaveGPU>(A, blockIdx.x); }
@@ -375,14 +396,14 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
 /* grow-only device buffer owned by the context: the host-buffer entry points keep their device arrays between calls
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
-enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_XSTARTS, A_XTILE, A_XSP, A_XTHR, A_XPRE, A_XOUT, A_STATS, A_COUNT };
+enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_XSTARTS, A_XTILE, A_XSP, A_XTHR, A_XPRE, A_XOUT, A_STATS, A_ESIDE, A_EARENA, A_PTAB, A_COUNT };
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
 /* what decode_blocks_impl runs behind the decode (its post-decode stage): nothing (plain, 2-bit, span, long reads), or the
  * stage of cbc_gpu_decode_region, _sam, _depth, _targets (reads, SAM, depth), _coverage, _depth_hist, _coverage_ext, _stats (whole
  * file, target set) */
 enum post_kind { POST_NONE, POST_REGION, POST_SAM, POST_DEPTH, POST_TG_READS, POST_TG_SAM, POST_TG_DEPTH, POST_COV, POST_HIST, POST_COVX,
-                 POST_STATS, POST_TG_STATS, POST_COVQ };
+                 POST_STATS, POST_TG_STATS, POST_COVQ, POST_PILEUP };
 
 struct cbc_gpu_ctx {
     int device;
@@ -437,7 +458,11 @@ static int blocks_failed(cbc_gpu_ctx *ctx, const cbc_block_result *res, uint32_t
 {
     for (uint32_t b = 0; b < n_blocks; b++)
         if (res[b].status != CBC_ST_OK) {
-            snprintf(ctx->err, sizeof ctx->err, "block %u %s with status %u at record %u", b, verb, res[b].status, res[b].fail_read);
+            if (res[b].status == CBC_ST_EDITS)
+                snprintf(ctx->err, sizeof ctx->err, "block %u %s with status %u at record %u: its reads with indels hold more deleted and inserted "
+                         "bases than its edit arena (raise --max-edits-per-read / edits_per_read)", b, verb, res[b].status, res[b].fail_read);
+            else
+                snprintf(ctx->err, sizeof ctx->err, "block %u %s with status %u at record %u", b, verb, res[b].status, res[b].fail_read);
             return CBC_E_BLOCK;
         }
     return CBC_OK;
@@ -493,6 +518,7 @@ API int cbc_gpu_init(int device_ordinal, cbc_gpu_ctx **out)
     (void)hipFuncSetAttribute((const void *)cbc_encode_blocks_kernel_w6, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)cbc_decode_blocks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)cbc_decode_blocks_span_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void *)cbc_decode_blocks_edits_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)cbc_encode_whole_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)cbc_long_encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)cbc_long_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1041,8 +1067,8 @@ API int cbc_gpu_group_gather(cbc_gpu_group *g, uint8_t *out, uint64_t out_cap, u
  * ---------------------------------------------------------------------------------------------- */
 API uint32_t cbc_gpu_decode_lds_bytes(const cbc_lds_caps *caps) { return caps ? cbc_plan_dec_lds_bytes(caps) : 0; }
 
-/* smax = 0: the plain decoder; otherwise the span-reporting one (region decode) */
-static int decode_blocks_launch(cbc_gpu_ctx *ctx, const cbc_dec_device_batch *b, void *hip_stream, uint32_t smax)
+/* smax = 0: the plain decoder; otherwise the span-reporting one (region decode), with E the one that reports its edits too */
+static int decode_blocks_launch(cbc_gpu_ctx *ctx, const cbc_dec_device_batch *b, void *hip_stream, uint32_t smax, const cbc_dec_edits *E = NULL)
 {
     if (!ctx || !b) return CBC_E_ARG;
     if (b->n_blocks == 0) return CBC_OK;
@@ -1060,7 +1086,8 @@ static int decode_blocks_launch(cbc_gpu_ctx *ctx, const cbc_dec_device_batch *b,
     A.n_blocks = b->n_blocks; A.cap_pos = b->caps.cap_pos; A.cap_var = b->caps.cap_var;
     A.var_scratch = b->d_var_scratch; A.var_scratch_words = b->var_scratch_words;
     HIPCHK(hipEventRecord(ctx->ev0, s), "hipEventRecord");
-    if (smax) hipLaunchKernelGGL(cbc_decode_blocks_span_kernel, dim3(b->n_blocks), dim3(64), lds, s, A, smax);
+    if (smax && E) hipLaunchKernelGGL(cbc_decode_blocks_edits_kernel, dim3(b->n_blocks), dim3(64), lds, s, A, smax, *E);
+    else if (smax) hipLaunchKernelGGL(cbc_decode_blocks_span_kernel, dim3(b->n_blocks), dim3(64), lds, s, A, smax);
     else hipLaunchKernelGGL(cbc_decode_blocks_kernel, dim3(b->n_blocks), dim3(64), lds, s, A);
     HIPCHK(hipGetLastError(), "launch cbc_decode_blocks_kernel");
     HIPCHK(hipEventRecord(ctx->ev1, s), "hipEventRecord");
@@ -1075,7 +1102,8 @@ API int cbc_gpu_decode_blocks_device(cbc_gpu_ctx *ctx, const cbc_dec_device_batc
 
 static bool post_is_covx(post_kind k) { return k == POST_COVX || k == POST_COVQ; }
 static bool post_is_cov(post_kind k) { return k == POST_COV || post_is_covx(k); }
-static bool post_is_depth(post_kind k) { return k == POST_DEPTH || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST; }
+/* PILEUP shares the depth kinds' arenas, counters and text fetch; it has no change points and its text tiles are the position tiles */
+static bool post_is_depth(post_kind k) { return k == POST_DEPTH || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || k == POST_PILEUP; }
 static bool post_is_sam(post_kind k) { return k == POST_SAM || k == POST_TG_SAM; }
 static bool post_is_targets(post_kind k) { return k == POST_TG_READS || k == POST_TG_SAM || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || k == POST_TG_STATS; }
 static bool post_is_stats(post_kind k) { return k == POST_STATS || k == POST_TG_STATS; }
@@ -1111,6 +1139,10 @@ struct post_req {
     hist_req hist;                 /* HIST */
     /* STATS, TG_STATS (with `exclude`): where the tables go, the record groups of the largest block */
     cbc_gpu_stats *stats; uint32_t stats_gmax;
+    /* edits_per_read > 0 (with smax > 0): the edit-reporting decoder.  PILEUP: the line rule and the contig's first reference
+     * byte; NONE (cbc_gpu_decode_blocks_edits): where the side array (2 words per record) and the arena go */
+    uint32_t edits_per_read, min_alt; uint64_t ref_c0;
+    uint32_t *edit_side; uint16_t *edit_arena;
 };
 
 /* sizes derived from the request: tiles of the difference array (d_words = W + 1 words), change points (two per read at most,
@@ -1129,6 +1161,7 @@ static post_sizes post_sizes_of(const post_req *rg, uint32_t n_blocks, uint64_t 
     z.n_tiles = (uint32_t)((z.d_words + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
     z.cp_cap = (uint32_t)(2u * n_recs + (tg ? 2u * (uint64_t)rg->n_iv : 0u));
     z.n_ttiles = (z.cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
+    if (rg->kind == POST_PILEUP) { z.cp_cap = 0; z.n_ttiles = z.n_tiles; }
     z.n_sized = z.n_ttiles;
     /* start points: a piece starts where its read starts or on an interval's first slot */
     if (post_is_covx(rg->kind)) z.sp_cap = (uint32_t)(n_recs + rg->n_iv);
@@ -1205,6 +1238,10 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
         NEED(A_HTILE, (uint64_t)z.n_btiles * sizeof(cbc_block_result) + ((uint64_t)z.n_btiles + 1) * 8, "hipMalloc histogram tiles");
     }
     if (post_is_stats(k)) NEED(A_STATS, (uint64_t)CBC_STATS_WORDS * 4, "hipMalloc statistics tables");
+    if (k == POST_PILEUP && arena_need(ctx, A_PTAB, (uint64_t)z.n_tiles * CBC_DEPTH_TILE * 4 * CBC_PILEUP_PLANES, "hipMalloc pileup counters")) {
+        (void)hipGetLastError();
+        return set_err(ctx, CBC_E_NOMEM, "no device memory for the window's allele counters (28 bytes per position)", hipSuccess);
+    }
 done:
     return rc;
 }
@@ -1300,10 +1337,8 @@ static int launch_targets_text(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req 
     return CBC_OK;
 }
 
-/* the front of every depth kind: mark, tile sums, their two scans, the change points.  `da` and `ta` (filled for the targets
- * kinds, whose mark kernel reads the interval table) are what the tails go on with. */
-static int launch_depth_front(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const post_sizes &z, const cbc_region_args &ra,
-                              cbc_depth_args *da, cbc_tdepth_args *ta)
+/* what every depth kind's kernels take, out of the context's arenas, with the difference array and the counters zeroed */
+static int depth_args_zeroed(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const post_sizes &z, const cbc_region_args &ra, cbc_depth_args *da)
 {
     const uint32_t n_tiles = z.n_tiles;
     memset(da, 0, sizeof *da);
@@ -1317,6 +1352,18 @@ static int launch_depth_front(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *
     da->name_len = rg->names_bytes; da->exclude = rg->exclude; da->n_tiles = n_tiles; da->n_ttiles = z.n_ttiles;
     HIPCHK(hipMemsetAsync(da->diff, 0, da->diff_words * 4, ks), "memset depth window");
     HIPCHK(hipMemsetAsync(da->ctr, 0, 16, ks), "memset depth counters");
+    return CBC_OK;
+}
+
+/* the front of every depth kind: mark, tile sums, their two scans, the change points.  `da` and `ta` (filled for the targets
+ * kinds, whose mark kernel reads the interval table) are what the tails go on with. */
+static int launch_depth_front(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const post_sizes &z, const cbc_region_args &ra,
+                              cbc_depth_args *da, cbc_tdepth_args *ta)
+{
+    const uint32_t n_tiles = z.n_tiles;
+    uint64_t *toff = (uint64_t *)ctx->arena[A_DTOFF].p;
+    int rc = depth_args_zeroed(ctx, ks, rg, z, ra, da);
+    if (rc) return rc;
     memset(ta, 0, sizeof *ta);
     if (post_is_targets(rg->kind)) {
         ta->D = *da; ta->iv = (const uint32_t *)ctx->arena[A_TIV].p; ta->iv_off = (const uint32_t *)ctx->arena[A_TOFF].p;
@@ -1487,6 +1534,39 @@ static int launch_hist(cbc_gpu_ctx *ctx, hipStream_t ks, const hist_req *hist, c
     return CBC_OK;
 }
 
+/* per-position allele counts: zero, the depth's mark pass and the events; the depth's tile sums and their scan; lines per tile
+ * of positions, scan, write */
+static int launch_pileup(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const post_sizes &z, const cbc_region_args &ra, uint64_t n_recs)
+{
+    const uint32_t n_tiles = z.n_tiles;
+    cbc_pileup_args pa;
+    memset(&pa, 0, sizeof pa);
+    int rc = depth_args_zeroed(ctx, ks, rg, z, ra, &pa.D);
+    if (rc) return rc;
+    pa.side = (const uint32_t *)ctx->arena[A_ESIDE].p; pa.arena = (const uint16_t *)ctx->arena[A_EARENA].p;
+    pa.arena_entries = n_recs * rg->edits_per_read; pa.per_read = rg->edits_per_read;
+    pa.ref = ctx->d_ref; pa.ref_bytes = ctx->ref_bytes; pa.ref_c0 = rg->ref_c0; pa.min_alt = rg->min_alt;
+    pa.tab = (uint32_t *)ctx->arena[A_PTAB].p; pa.plane = pa.D.diff_words;
+    HIPCHK(hipMemsetAsync(pa.tab, 0, pa.plane * 4 * CBC_PILEUP_PLANES, ks), "memset pileup counters");
+    hipLaunchKernelGGL(cbc_depth_mark_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, pa.D);
+    HIPCHK(hipGetLastError(), "launch cbc_depth_mark_kernel");
+    hipLaunchKernelGGL(cbc_pileup_events_kernel, dim3(ra.n_blocks), dim3(64 * CBC_PILEUP_WAVES), 0, ks, pa);
+    HIPCHK(hipGetLastError(), "launch cbc_pileup_events_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+    hipLaunchKernelGGL(cbc_depth_tile_kernel, dim3(n_tiles), dim3(64), 0, ks, pa.D);
+    HIPCHK(hipGetLastError(), "launch cbc_depth_tile_kernel");
+    launch_scan_sizes(ks, pa.D.tile_sum, (uint64_t *)ctx->arena[A_DTOFF].p, n_tiles);
+    hipLaunchKernelGGL(cbc_pileup_count_kernel, dim3(n_tiles), dim3(64), 0, ks, pa);
+    HIPCHK(hipGetLastError(), "launch cbc_pileup_count_kernel");
+    launch_scan_sizes(ks, ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_tiles);
+    HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+    hipLaunchKernelGGL(cbc_pileup_write_kernel, dim3(n_tiles), dim3(64), 0, ks, pa);
+    HIPCHK(hipGetLastError(), "launch cbc_pileup_write_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[4], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
 /* read statistics: zero the tables, one pass over the records and rows: no text */
 static int launch_stats(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const cbc_region_args &ra)
 {
@@ -1562,7 +1642,7 @@ static int post_fetch_output(cbc_gpu_ctx *ctx, const post_req *rg, const post_si
     else for (uint32_t b = 0; b < n_blocks; b++) kept += g->cnt[b].n_symbols;
     *rg->text_bytes = g->total; *rg->n_selected = kept;
     if (g->total > rg->text_cap)
-        return set_err(ctx, CBC_E_ARG, depth ? "text_cap too small for the depth text" : post_is_sam(rg->kind) ? "text_cap too small for the SAM text" : "text_cap too small for the region's text", hipSuccess);
+        return set_err(ctx, CBC_E_ARG, rg->kind == POST_PILEUP ? "text_cap too small for the pileup text" : depth ? "text_cap too small for the depth text" : post_is_sam(rg->kind) ? "text_cap too small for the SAM text" : "text_cap too small for the region's text", hipSuccess);
     if (g->total) {
         HIPCHK(hipMemcpyAsync(rg->text, ctx->arena[A_TEXT].p, g->total, hipMemcpyDeviceToHost, sc), "D2H region text");
         HIPCHK(hipStreamSynchronize(sc), "D2H region text");
@@ -1601,7 +1681,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     const double T0 = wall_now();
     cbc_e2e_times tm; memset(&tm, 0, sizeof tm);
-    const bool two_bit = codes_out != NULL, post = rg && rg->kind != POST_NONE;
+    const bool two_bit = codes_out != NULL, post = rg && rg->kind != POST_NONE, edits = rg && rg->smax && rg->edits_per_read;
     const post_sizes z = post_sizes_of(rg, n_blocks, n_recs);
     post_got pg; memset(&pg, 0, sizeof pg);
     const uint32_t stride = blocks[0].seq_stride;
@@ -1621,6 +1701,14 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         NEED(A_EXC_V, (exc_cap ? exc_cap : 1), "hipMalloc exceptions");
         NEED(A_CNT, 8, "hipMalloc counter");
     }
+    if (edits) {
+        NEED(A_ESIDE, n_recs * 8 + 16, "hipMalloc edit side array");
+        if (arena_need(ctx, A_EARENA, n_recs * rg->edits_per_read * 2 + 16, "hipMalloc edit arena")) {
+            (void)hipGetLastError();
+            rc = set_err(ctx, CBC_E_NOMEM, "no device memory for the edit arena (2 bytes per read and entry of edits_per_read)", hipSuccess);
+            goto done;
+        }
+    }
     if (post && (rc = post_arenas(ctx, rg, z, n_blocks)) != CBC_OK) goto done;
     tm.alloc_s = wall_now() - T0;
     {
@@ -1634,6 +1722,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         GO(hipMemcpyAsync(d_blocks, blocks, (uint64_t)n_blocks * sizeof(cbc_dec_block_desc), hipMemcpyHostToDevice, sc), "H2D blocks");
         GO(hipMemsetAsync(d_res, 0xff, (uint64_t)n_blocks * sizeof(cbc_block_result), sc), "memset results");
         if (two_bit) GO(hipMemsetAsync(ctx->arena[A_CNT].p, 0, 8, sc), "memset counter");
+        if (edits) GO(hipMemsetAsync(ctx->arena[A_ESIDE].p, 0, n_recs * 8, sc), "memset edit side array");
         if (post && (rc = post_h2d(ctx, rg, n_blocks, sc)) != CBC_OK) goto done;
         GO(hipEventRecord(ctx->ev_done[0], sc), "hipEventRecord");       /* inputs are on the device */
         tm.h2d_bytes = in_bytes + (uint64_t)n_blocks * sizeof(cbc_dec_block_desc);
@@ -1658,7 +1747,13 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 db.seq_bytes = seq_bytes + 32;
                 db.d_var_scratch = (uint32_t *)ctx->arena[A_VS].p + (uint64_t)k.b0 * caps->cap_var;
                 db.var_scratch_words = (uint64_t)(k.b1 - k.b0) * caps->cap_var;
-                rc = decode_blocks_launch(ctx, &db, ks, rg ? rg->smax : 0u);
+                cbc_dec_edits de;
+                memset(&de, 0, sizeof de);
+                if (edits) {
+                    de.side = (uint32_t *)ctx->arena[A_ESIDE].p; de.arena = (uint16_t *)ctx->arena[A_EARENA].p;
+                    de.arena_entries = n_recs * rg->edits_per_read; de.per_read = rg->edits_per_read;
+                }
+                rc = decode_blocks_launch(ctx, &db, ks, rg ? rg->smax : 0u, edits ? &de : NULL);
             }
             if (rc) goto done;
             if (post) {                                        /* one chunk: the stage's launches on the decode's stream */
@@ -1696,6 +1791,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     if (!rc) rc = launch_hist(ctx, ks, &rg->hist, z, da);
                     break;
                 case POST_STATS: case POST_TG_STATS: rc = launch_stats(ctx, ks, rg, ra); break;
+                case POST_PILEUP: rc = launch_pileup(ctx, ks, rg, z, ra, n_recs); break;
                 }
                 if (rc) goto done;
                 ctx->last_post = rg->kind;                     /* the events now hold this call's times */
@@ -1723,6 +1819,11 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 GO(hipMemcpyAsync(seq + k.s0, d_seq + k.s0, k.s1 - k.s0, hipMemcpyDeviceToHost, sc), "D2H seq");
                 tm.d2h_bytes += k.s1 - k.s0;
             }
+        }
+        if (edits && !post) {                                  /* cbc_gpu_decode_blocks_edits: behind the last chunk's records and rows */
+            GO(hipMemcpyAsync(rg->edit_side, ctx->arena[A_ESIDE].p, n_recs * 8, hipMemcpyDeviceToHost, sc), "D2H edit side array");
+            GO(hipMemcpyAsync(rg->edit_arena, ctx->arena[A_EARENA].p, n_recs * rg->edits_per_read * 2, hipMemcpyDeviceToHost, sc), "D2H edit arena");
+            tm.d2h_bytes += n_recs * (8 + 2ull * rg->edits_per_read);
         }
         res = results ? results : (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
         if (!res) { rc = CBC_E_NOMEM; goto done; }
@@ -1955,6 +2056,70 @@ API int cbc_gpu_last_depth_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms
     if (!ctx || ctx->last_post != POST_DEPTH) return CBC_E_ARG;
     float *const out[] = { decode_ms, mark_ms, scan_ms, text_ms };
     return last_ms(ctx, ctx->ev_rg, out, 4);
+}
+
+/* per-position allele counts: the window's blocks laid out afresh as for the depth, then edits decode +
+ * mark + events + scans + text on the device (cbc_pileup_body.h) */
+API int cbc_gpu_decode_pileup(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                              uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const char *name,
+                              uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax, uint32_t exclude_flags, uint32_t min_alt,
+                              uint32_t edits_per_read, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_lines,
+                              uint64_t *n_reads_kept, cbc_block_result *results)
+{
+    if (!ctx || !blocks || !caps || !window_start || !name || !text_bytes || !n_lines || !n_reads_kept || (text_cap && !text)) return CBC_E_ARG;
+    *text_bytes = 0; *n_lines = 0; *n_reads_kept = 0;
+    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (n_blocks == 0) return CBC_OK;
+    if (!in) return CBC_E_ARG;
+    if (smax == 0 || beg < 1 || beg > end || end > CBC_SAM_MAX_POS)
+        return set_err(ctx, CBC_E_ARG, "pileup wants 1 <= beg <= end <= 2^31 - 1 and smax > 0", hipSuccess);
+    if (min_alt < 1) return set_err(ctx, CBC_E_ARG, "pileup wants min_alt >= 1", hipSuccess);
+    if (edits_per_read == 0) edits_per_read = CBC_EDITS_PER_READ;
+    if (edits_per_read > CBC_EDITS_MAX) return set_err(ctx, CBC_E_ARG, "pileup wants edits_per_read in 1..510 (0: the default)", hipSuccess);
+    if (name_bytes < 1 || name_bytes > CBC_SAM_MAX_NAME || memchr(name, '\t', name_bytes) || memchr(name, '\n', name_bytes) || memchr(name, 0, name_bytes))
+        return set_err(ctx, CBC_E_ARG, "pileup: the contig name is empty, longer than 255 bytes or holds a tab, a newline or a NUL", hipSuccess);
+    /* one contig: every block's window lies at the same place of the reference */
+    for (uint32_t b = 0; b < n_blocks; b++)
+        if (blocks[b].ref_off < window_start[b] || blocks[b].ref_off - window_start[b] != blocks[0].ref_off - window_start[0])
+            return set_err(ctx, CBC_E_ARG, "pileup takes the blocks of one contig", hipSuccess);
+    block_layout L;
+    int rc = relayout_blocks(ctx, "pileup", in_bytes, blocks, n_blocks, NULL, &L);
+    if (rc) return rc;
+    if (L.nrec > 0x3fffffffull) rc = set_err(ctx, CBC_E_ARG, "pileup: more than 2^30 - 1 reads in one call", hipSuccess);
+    else if (L.nrec) {                                         /* blocks without reads: no line */
+        /* a line per position of the window at most, and per reference base a kept read spans (span <= smax) */
+        const uint64_t w = end - beg + 1u, by_reads = L.nrec * smax;
+        post_req rg;
+        post_req_init(&rg, POST_PILEUP, smax, window_start, text, text_cap, (w < by_reads ? w : by_reads) * (name_bytes + 102ull), text_bytes, n_reads_kept);
+        rg.beg = beg; rg.end = end;
+        rg.names = (const uint8_t *)name; rg.names_bytes = name_bytes; rg.exclude = exclude_flags; rg.n_runs = n_lines;
+        rg.edits_per_read = edits_per_read; rg.min_alt = min_alt; rg.ref_c0 = blocks[0].ref_off - window_start[0];
+        rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
+    }
+    layout_free(&L);
+    return rc;
+}
+
+API int cbc_gpu_last_pileup_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *events_ms, float *scan_ms, float *text_ms)
+{
+    if (!ctx || ctx->last_post != POST_PILEUP) return CBC_E_ARG;
+    float *const out[] = { decode_ms, events_ms, scan_ms, text_ms };
+    return last_ms(ctx, ctx->ev_rg, out, 4);
+}
+
+/* cbc_gpu_decode_blocks_span with the edits reported too: the decoder the pileup runs, with everything it leaves returned */
+API int cbc_gpu_decode_blocks_edits(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, cbc_dec_block_desc *blocks,
+                                    uint32_t n_blocks, const cbc_lds_caps *caps, uint32_t smax, uint32_t edits_per_read,
+                                    cbc_read_rec *recs, uint64_t n_recs, uint8_t *seq, uint64_t seq_bytes, uint32_t *side,
+                                    uint16_t *arena, cbc_block_result *results)
+{
+    if (!ctx || !in || !blocks || !caps || !recs || !seq || !side || !arena || smax == 0) return CBC_E_ARG;
+    if (edits_per_read == 0) edits_per_read = CBC_EDITS_PER_READ;
+    if (edits_per_read > CBC_EDITS_MAX) return set_err(ctx, CBC_E_ARG, "edits_per_read in 1..510 (0: the default)", hipSuccess);
+    post_req rg;
+    memset(&rg, 0, sizeof rg);
+    rg.kind = POST_NONE; rg.smax = smax; rg.edits_per_read = edits_per_read; rg.edit_side = side; rg.edit_arena = arena;
+    return decode_blocks_impl(ctx, in, in_bytes, blocks, n_blocks, caps, recs, n_recs, seq, seq_bytes, NULL, NULL, NULL, 0, NULL, results, &rg);
 }
 
 /* a set of regions: the selected blocks laid out afresh as for a region decode, the tables checked

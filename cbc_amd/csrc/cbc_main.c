@@ -74,6 +74,11 @@ static void usage(const char *p)
             "                  A, C, G, T, other per sequencing cycle; the whole file, or the reads --region / --regions-file select,\n"
             "                  each once; counted on the device; not with --sam, --depth, --bedcov or --depth-hist)\n"
             "         --stats-exclude-flags N (with --stats: reads with FLAG & N != 0 are counted as excluded only; default 0)\n"
+            "         --pileup (what the reads show where they disagree with the reference, one line per such position:\n"
+            "                   NAME, pos, ref, depth, A, C, G, T, N, del, ins; the whole file or one --region; counted on the device;\n"
+            "                   with --depth-exclude-flags; not with --sam, --depth, --bedcov, --depth-hist or --stats)\n"
+            "         --min-alt K (with --pileup: only positions with K or more non-reference observations; default 1)\n"
+            "         --max-edits-per-read N (with --pileup: deleted + inserted bases kept per read of a block, 1..510; default 16)\n"
             "options: -l (header read length = longest read)  --block-reads N (default 4096)  --device N (default 0)\n"
             "         --threads N (SAM parser threads, default one per CPU)  --verbose (stage times)\n"
             "         --compat (write the reference's own single-stream format; slow: one stream = one wavefront)\n"
@@ -491,6 +496,8 @@ int main(int argc, char **argv)
     uint32_t hist_max = 0;
     int stats_out = 0, stats_excl_given = 0;
     uint32_t stats_exclude = 0;
+    int pileup = 0, min_alt_given = 0, max_edits_given = 0;
+    uint32_t min_alt = 1, max_edits = 0;
     g_main_t0 = now_s();
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
@@ -550,6 +557,9 @@ int main(int argc, char **argv)
         }
         if (!strcmp(a, "--depth-hist")) { depth_hist = 1; continue; }
         if (!strcmp(a, "--stats")) { stats_out = 1; continue; }
+        if (!strcmp(a, "--pileup")) { pileup = 1; continue; }
+        if (!strcmp(a, "--min-alt") && i + 1 < argc) { if (!parse_count(a, argv[++i], 0xffffffffull, "a count in 1..4294967295", &n)) return 1; min_alt = (uint32_t)n; min_alt_given = 1; continue; }
+        if (!strcmp(a, "--max-edits-per-read") && i + 1 < argc) { if (!parse_count(a, argv[++i], 510, "a number of deleted and inserted bases in 1..510", &n)) return 1; max_edits = (uint32_t)n; max_edits_given = 1; continue; }
         if (!strcmp(a, "--compat")) { compat = 1; continue; }
         if (!strcmp(a, "--long")) { long_reads = 1; continue; }
         if (!strcmp(a, "--device-parse")) { device_parse = 1; continue; }
@@ -601,6 +611,8 @@ int main(int argc, char **argv)
           quant_given ? "--quantiles" : NULL },
         { "--depth-hist", depth_hist, "--depth-hist, --bedcov, --depth and --sam are different outputs", hist_max_given ? "--hist-max" : NULL },
         { "--stats", stats_out, "--stats, --depth-hist, --bedcov, --depth and --sam are different outputs", stats_excl_given ? "--stats-exclude-flags" : NULL },
+        { "--pileup", pileup, "--pileup, --stats, --depth-hist, --bedcov, --depth and --sam are different outputs",
+          min_alt_given ? "--min-alt" : max_edits_given ? "--max-edits-per-read" : NULL },
     };
     for (size_t k = 0; k < sizeof opts / sizeof opts[0]; k++) {
         if (opts[k].owned && !opts[k].given) { fprintf(stderr, "cbc: %s applies to %s\n", opts[k].owned, opts[k].name); return 1; }
@@ -609,9 +621,13 @@ int main(int argc, char **argv)
         for (size_t j = 2; j < k; j++) if (opts[j].given) { fprintf(stderr, "cbc: %s; give one of them\n", opts[k].clash); return 1; }
         if (ndev > 1) { fprintf(stderr, "cbc: %s decodes on one device; give a single --devices ordinal\n", opts[k].name); return 1; }
     }
+    if (pileup) {                                                 /* one window or every contig: a target set is left for later */
+        if (regions_file || n_regions > 1) { fprintf(stderr, "cbc: --pileup takes at most one --region and no --regions-file\n"); return 1; }
+        return cbc_cli_decompress_pileup(files[0], files[1], files[2], device, region, depth_exclude, min_alt, max_edits, verbose);
+    }
     if (depth_hist)
         return cbc_cli_decompress_hist(files[0], files[1], files[2], device, regions, n_regions, regions_file, hist_max, depth_exclude, verbose);
-    if (depth_excl_given && !depth_out && !bedcov) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
+    if (depth_excl_given && !depth_out && !bedcov && !pileup) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
     if (stats_out) return cbc_cli_decompress_stats(files[0], files[1], files[2], device, regions, n_regions, regions_file, stats_exclude, verbose);
     if (bedcov)                                                   /* no --thresholds, --count-reads, --quantiles: the plain summary */
         return cbc_cli_decompress_bedcov(files[0], files[1], files[2], device, regions, n_regions, regions_file, cov_window, cov_min_depth,

@@ -1938,6 +1938,26 @@ API uint64_t cbc_unpack_depth_text_cap(const cbc_unpack_plan *u, uint32_t b0, ui
     return k ? (2u * k - 1u) * ((uint64_t)nl + 34u) : 0u;
 }
 
+/* ---- per-position allele counts (include/cbc_host.h) ----
+ * Proof of the bound.  A line stands for a position p of the window [beg, end] with nonref(p) >= 1, so lines <= end - beg + 1.
+ * nonref(p) >= 1 needs a kept read with an aligned base of another class at p, a deleted base at p, or an insertion anchored
+ * at p; all three lie inside that read's span [POS, POS + span - 1] (what falls outside is not counted), the decoder fails the
+ * block of a read with span > smax (CBC_ST_SPAN), and a failed block contributes nothing: so lines <= reads * smax as well.
+ * A line is the name, ten tabs, the reference byte, '\n' and nine numbers below 2^32 -- pos1 <= 2^31 - 1 has at most 10
+ * digits, the eight counts at most 10 each --: name + 12 + 90 = name + 2 + 10 + 2 + 8 * 11 bytes. */
+API uint64_t cbc_unpack_pileup_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg, uint64_t end,
+                                        uint32_t smax)
+{
+    if (!u || u->long_reads || !u->names || !u->contig_name_off || b0 > b1 || b1 > u->n_blocks || contig >= u->n_contigs || beg < 1 ||
+        beg > end || end > 0x7fffffffull) return 0;
+    const int64_t nl = sam_name_len(u, contig);
+    if (nl < 0) return 0;
+    uint64_t k = 0;
+    for (uint32_t b = b0; b < b1; b++) k += u->blocks[b].n_reads;
+    const uint64_t w = end - beg + 1u, by_reads = k * smax;          /* k < 2^32 blocks * 2^14 reads, smax < 2^32: no wrap */
+    return (w < by_reads ? w : by_reads) * ((uint64_t)nl + 102u);
+}
+
 /* ---- a set of regions (include/cbc_host.h) ---- */
 typedef struct { uint32_t contig, beg, end; } target_raw;
 

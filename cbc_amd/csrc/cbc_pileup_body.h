@@ -1,0 +1,302 @@
+/*
+ * cbc_pileup_body.h -- per-position allele counts on the device, after the edit-reporting decode of one contig window's blocks
+ * (cbc_gpu_decode_pileup, include/cbc_gpu.h).
+ *
+ * The decoder (cbc_decode_body.h, EDITS = true) has left, beside the records, rows and spans, the alignment of every read with
+ * indels: nDel matched coordinates dc[] and nIns read indices oi[] (cbc_dec_edits).  With T = rl - nIns:
+ *   read index q with q == oi[i] for some i is inserted;
+ *   any other q has matched coordinate m = q - #{i : oi[i] < q} and is aligned to POS + m + #{d : dc[d] <= m};
+ *   deleted base d is reference position POS + dc[d] + d
+ * -- the counting form edits_indel() rebuilds the read with, not restated with other edge cases: `#{oi < q}` is its `nb`,
+ * `#{dc <= m}` its `sh`.  A read without indels (coded as perfect, or SNPs only) has q aligned to POS + q.  Whatever this maps
+ * outside the read's span [POS, POS + span - 1] is not counted (only a crafted file does that).
+ *
+ * Per position p of the window [beg, end], seven 32-bit counters in seven planes of `plane` words (28 bytes per position):
+ *   0..4   aligned read bases whose class (A, C, G, T, other: byte & 0xDF) DIFFERS from the class of the reference byte
+ *   5      deleted bases
+ *   6      insertion events: maximal runs of inserted read indices, anchored at the reference position of the nearest aligned
+ *          base before the run, or at POS when there is none
+ * A matching base costs no atomic: the line pass has the span depth (the prefix sum of cbc_depth_mark's difference array), and
+ * cnt[class(ref)] = depth - del - the five mismatch counters.
+ *
+ *   events   CBC_PILEUP_WAVES wavefronts per block share its kept reads (the keep rule of cbc_depth_mark); a read is taken by
+ *            the whole wavefront, 64 read indices a turn, one lane per index; then its deleted bases, one lane per base.
+ *   count    one wavefront per tile of CBC_DEPTH_TILE positions, one lane per position: depth from the tile's carry
+ *            (cbc_depth_tile + cbc_scan_sizes_kernel), the line rule nonref = mismatches + del + ins >= min_alt, lines and bytes
+ *            into a cbc_block_result for the size scan (64-bit text offsets).
+ *   write    the same tile again, one lane per line:  <name> <pos1> <ref> <depth> <A> <C> <G> <T> <N> <del> <ins>  tab-separated,
+ *            made four bytes at a time (cbc_depth_digit) and written as dwords at the line's own offset; a dword never leaves
+ *            its line, the last 1..3 bytes are byte stores.
+ * Range tests are written without base + length sums.  Written against the wave policy (W = WaveGPU in cbc_gpu.hip, the
+ * lock-step emulation in tests/pileup_emu).
+ */
+#ifndef CBC_PILEUP_BODY_H
+#define CBC_PILEUP_BODY_H
+
+#include <stdint.h>
+#include "../../include/cbc_gpu.h"
+#include "cbc_region_body.h"
+#include "cbc_depth_body.h"
+
+#define CBC_PILEUP_WAVES  4u       /* wavefronts that share one block's reads in the events pass */
+#define CBC_PILEUP_PLANES 7u
+#define CBC_PILEUP_DEL    5u
+#define CBC_PILEUP_INS    6u
+
+struct cbc_pileup_args {
+    cbc_depth_args D;             /* records, blocks, window, diff, tile sums and their scan, counters ([0] reads kept by the mark
+                                   * pass, [1] lines), name; R.counts / R.offsets / R.text: the position tiles' sizes, offsets, text */
+    const uint32_t *side;         /* the EDITS decoder's side array and arena (cbc_dec_edits)                                    */
+    const uint16_t *arena;
+    const uint8_t  *ref;          /* the device reference                                                                        */
+    uint32_t *tab;                /* CBC_PILEUP_PLANES planes of `plane` words, zeroed before                                    */
+    uint64_t arena_entries, ref_bytes, plane;
+    uint64_t ref_c0;              /* reference byte of window position p (1-based) = ref[ref_c0 + p - 1]                         */
+    uint32_t per_read, min_alt;
+};
+
+/* class of a base byte: 0..3 = A, C, G, T in either case, 4 = anything else */
+template <class W>
+CBC_FN typename W::V32 cbc_pileup_class(const typename W::V32 &b)
+{
+    const typename W::V32 c = b & 0xdfu;
+    return W::select(c == 0x41u, W::splat(0u), W::select(c == 0x43u, W::splat(1u), W::select(c == 0x47u, W::splat(2u),
+           W::select(c == 0x54u, W::splat(3u), W::splat(4u)))));
+}
+
+/* where the local coordinates of a block sit in the planes: local x is plane word fwd + (x - sub), inside the window when
+ * x >= sub and x - sub <= rem (the arithmetic of cbc_depth_mark) */
+struct cbc_pileup_win { uint64_t fwd; uint32_t sub, rem; bool ok; };
+
+CBC_FN cbc_pileup_win cbc_pileup_window(const cbc_pileup_args &A, uint32_t blk)
+{
+    cbc_pileup_win w;
+    const uint64_t ws = A.D.R.window_start[blk], beg = A.D.R.beg;
+    const uint64_t nw = A.D.R.end - beg;                             /* the window's last index */
+    w.ok = A.plane != 0u && nw < A.plane;
+    w.fwd = ws >= beg ? ws - beg : 0u;
+    w.sub = ws >= beg ? 0u : (uint32_t)(beg - ws);                   /* cbc_region_block: beg + 1 - ws < 2^32 */
+    w.ok = w.ok && w.fwd <= nw;
+    const uint64_t rem64 = w.ok ? nw - w.fwd : 0u;
+    w.rem = rem64 > 0xffffffffull ? 0xffffffffu : (uint32_t)rem64;
+    return w;
+}
+
+/* ---- events ------------------------------------------------------------------------------------------------------------ */
+template <class W>
+CBC_FN void cbc_pileup_events(const cbc_pileup_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
+{
+    typedef typename W::V32 V32;
+    typedef typename W::Mask Mask;
+    const cbc_region_blk B = cbc_region_block(A.D.R, blk);           /* ok: decoded, 1 <= beg <= end, end > window start */
+    if (!B.ok || n_waves == 0u || wave >= n_waves) return;
+    const cbc_pileup_win Wn = cbc_pileup_window(A, blk);
+    if (!Wn.ok) return;
+    const cbc_dec_block_desc *bd = A.D.R.blocks + blk;
+    const uint64_t rec_base = bd->rec_base, ref_off = bd->ref_off;
+    /* the block's part of the arena, by the decoder's own test; the side array runs beside the records (B.ok: inside n_recs) */
+    const uint64_t cap64 = (uint64_t)B.n * A.per_read, base64 = rec_base * A.per_read;
+    if (A.per_read < 1u || A.per_read > 510u || base64 > A.arena_entries || cap64 > A.arena_entries - base64) return;
+    const uint32_t cap = (uint32_t)cap64;
+    const uint16_t *arena = A.arena + base64;
+    const uint32_t *side = A.side + 2u * rec_base;
+    if (ref_off > A.ref_bytes) return;
+    const uint64_t ref_avail = A.ref_bytes - ref_off;
+    const uint32_t ref_lim = ref_avail > 0xffffffffull ? 0xffffffffu : (uint32_t)ref_avail;
+    const uint8_t *refb = A.ref + ref_off;
+    uint32_t *p = A.tab + Wn.fwd;
+    const V32 ln = W::lane();
+    uint32_t nq = 0;                                                 /* kept reads of the block so far */
+    for (uint32_t r0 = 0; r0 < B.n; r0 += 64u) {
+        V32 rlv, lp, fl, off, span;
+        Mask k = cbc_region_keep<W>(B, r0, rlv);
+        W::load_rec(B.recs4, ln + r0, k, lp, fl, off, span);
+        k = k & ((fl & (A.D.exclude & 0xffffu)) == 0u) & (span >= 1u);
+        const V32 sd0 = W::load32(side, (ln + r0) * 2u, k, 0u), sd1 = W::load32(side, (ln + r0) * 2u + 1u, k, 0u);
+        uint64_t bits = W::ballot(k);
+        while (bits) {
+            const uint32_t j = W::ctz64(bits);
+            bits &= bits - 1u;
+            if ((nq++ % n_waves) != wave) continue;
+            const uint32_t rl = W::readlane(rlv, j), lpj = W::readlane(lp, j), sp = W::readlane(span, j);
+            const uint32_t e0 = W::readlane(sd0, j), cnt = W::readlane(sd1, j), nd = cnt & 0xffffu, ni = cnt >> 16;
+            if (nd > 255u || ni > 255u || e0 > cap || nd + ni > cap - e0) continue;     /* not what the decoder writes */
+            const uint16_t *ar = arena + e0;                         /* dc = ar[0 .. nd), oi = ar[nd .. nd + ni) */
+            const uint8_t *row = B.rows + (uint64_t)(r0 + j) * B.stride;
+            /* the first 64 entries of each list in a register; later ones (rare) are read one by one */
+            const V32 dcv = W::load16(ar, ln, ln < nd), oiv = W::load16(ar, ln + nd, ln < ni);
+            for (uint32_t b = 0; b < rl; b += 64u) {
+                const V32 q = ln + b;
+                const Mask inr = q < rl;
+                V32 nb = W::splat(0u), ii = W::splat(0u), pi = W::splat(0u);
+                for (uint32_t i = 0; i < ni; i++) {
+                    const uint32_t oi = i < 64u ? W::readlane(oiv, i) : W::read_uni16(ar, nd + i);
+                    nb = nb + W::select(q > oi, W::splat(1u), W::splat(0u));
+                    ii = W::select(q == oi, W::splat(1u), ii);
+                    pi = W::select(q == oi + 1u, W::splat(1u), pi);
+                }
+                const Mask isins = ii != 0u;
+                const Mask al = inr & !isins;                        /* an aligned base */
+                const Mask st = inr & isins & (pi == 0u);            /* the first index of an insertion run */
+                const V32 m = q - nb;                                /* matched coordinate; of an inserted q: that of the next aligned base */
+                const Mask none = isins & (m == 0u);                 /* no aligned base before the run: the anchor is POS */
+                const V32 mm = W::select(isins & !none, m - 1u, m);  /* the run's anchor is the aligned base before it */
+                V32 sh = W::splat(0u);
+                for (uint32_t d = 0; d < nd; d++) {
+                    const uint32_t dc = d < 64u ? W::readlane(dcv, d) : W::read_uni16(ar, d);
+                    sh = sh + W::select(mm >= dc, W::splat(1u), W::splat(0u));
+                }
+                const V32 xo = W::select(none, W::splat(0u), mm + sh);     /* offset from POS; below rl + 255 */
+                const V32 x = xo + lpj;                              /* decoded record: local POS + span < 2^32 */
+                const Mask in = (al | st) & (xo < sp) & (x >= Wn.sub) & ((x - Wn.sub) <= Wn.rem);
+                const V32 idx = x - Wn.sub;
+                const Mask ab = al & in & ((x - 1u) < ref_lim);      /* local POS >= 1 */
+                const V32 cb = cbc_pileup_class<W>(W::load8(row, q, ab)), cr = cbc_pileup_class<W>(W::load8(refb, x - 1u, ab));
+                const Mask mis = ab & (cb != cr);
+                if (W::ballot(mis) != 0ull)
+                    for (uint32_t c = 0; c < 5u; c++) W::list_add(p + (uint64_t)c * A.plane, idx, W::splat(1u), mis & (cb == c));
+                W::list_add(p + (uint64_t)CBC_PILEUP_INS * A.plane, idx, W::splat(1u), st & in);
+            }
+            for (uint32_t b = 0; b < nd; b += 64u) {                 /* deleted base d: POS + dc[d] + d */
+                const V32 d = ln + b;
+                const Mask md = d < nd;
+                const V32 xo = W::load16(ar, d, md) + d;
+                const V32 x = xo + lpj;
+                const Mask in = md & (xo < sp) & (x >= Wn.sub) & ((x - Wn.sub) <= Wn.rem);
+                W::list_add(p + (uint64_t)CBC_PILEUP_DEL * A.plane, x - Wn.sub, W::splat(1u), in);
+            }
+        }
+    }
+}
+
+/* ---- lines ------------------------------------------------------------------------------------------------------------- */
+/* positions [i0, i0 + 64) of the window, `run` = the depth in front of them (advanced): the nine numbers of the line in
+ * v[] = pos1, depth, A, C, G, T, N, del, ins, the reference byte, the line's length (0: no line) */
+template <class W>
+CBC_FN typename W::Mask cbc_pileup_line(const cbc_pileup_args &A, uint32_t i0, uint32_t &run, typename W::V32 *v,
+                                        typename W::V32 &rb, typename W::V32 &len)
+{
+    typedef typename W::V32 V32;
+    typedef typename W::Mask Mask;
+    const V32 idx = W::lane() + i0;
+    const uint64_t nw = A.D.R.end - A.D.R.beg;
+    const Mask m = idx <= (nw > 0xffffffffull ? 0xffffffffu : (uint32_t)nw);
+    const V32 d = W::load32(A.D.diff, idx, W::all(), 0u);            /* whole tiles behind diff */
+    const V32 incl = W::scan_incl_add(d);
+    const V32 depth = incl + run;
+    run += W::readlane(incl, 63u);
+    V32 c[CBC_PILEUP_PLANES], nonref = W::splat(0u);
+    for (uint32_t k = 0; k < CBC_PILEUP_PLANES; k++) {
+        c[k] = W::load32(A.tab + (uint64_t)k * A.plane, idx, m, 0u);
+        nonref = nonref + c[k];
+    }
+    const Mask k = m & (nonref >= A.min_alt) & (A.min_alt >= 1u);
+    len = W::splat(0u);
+    if (W::ballot(k) == 0ull) return k;
+    const uint64_t at = A.ref_c0 + (A.D.R.beg - 1u);                 /* the reference byte of index 0 */
+    const uint64_t avail = at <= A.ref_bytes ? A.ref_bytes - at : 0u;
+    const Mask rok = k & (idx < (avail > 0xffffffffull ? 0xffffffffu : (uint32_t)avail));
+    rb = W::select(rok, W::load8(A.ref + (at <= A.ref_bytes ? at : 0u), idx, rok), W::splat((uint32_t)'N'));
+    const V32 cr = cbc_pileup_class<W>(rb);
+    const V32 mis = c[0] + c[1] + c[2] + c[3] + c[4];
+    const V32 same = depth - c[CBC_PILEUP_DEL] - mis;                /* the bases of the reference's class */
+    v[0] = idx + (uint32_t)A.D.R.beg;                                /* end <= CBC_SAM_MAX_POS */
+    v[1] = depth;
+    for (uint32_t s = 0; s < 5u; s++) v[2u + s] = W::select(cr == s, same, c[s]);
+    v[7] = c[CBC_PILEUP_DEL]; v[8] = c[CBC_PILEUP_INS];
+    V32 l = W::splat(A.D.name_len + 12u);                            /* name, ten '\t', the reference byte, '\n' */
+    for (uint32_t s = 0; s < 9u; s++) l = l + cbc_sam_ndig_v<W>(v[s], 1000000000u);
+    len = W::select(k, l, W::splat(0u));
+    return k;
+}
+
+CBC_FN bool cbc_pileup_text_ok(const cbc_pileup_args &A, uint32_t t)
+{
+    return t < A.D.n_tiles && A.D.diff_words / CBC_DEPTH_TILE >= A.D.n_tiles && A.plane >= A.D.diff_words &&
+           A.D.name_len <= CBC_SAM_MAX_NAME && A.D.R.beg >= 1u && A.D.R.beg <= A.D.R.end && A.D.R.end <= CBC_SAM_MAX_POS;
+}
+
+template <class W>
+CBC_FN void cbc_pileup_count(const cbc_pileup_args &A, uint32_t t)
+{
+    typedef typename W::V32 V32;
+    typedef typename W::Mask Mask;
+    uint32_t lines = 0, bytes = 0;
+    if (cbc_pileup_text_ok(A, t)) {
+        uint32_t run = (uint32_t)A.D.sum_off[t];                     /* depth in front of the tile, mod 2^32 */
+        for (uint32_t r = 0; r < CBC_DEPTH_TILE / 64u; r++) {
+            V32 v[9], rb, len;
+            const Mask k = cbc_pileup_line<W>(A, t * CBC_DEPTH_TILE + r * 64u, run, v, rb, len);
+            if (W::ballot(k) == 0ull) continue;
+            lines += W::popc64(W::ballot(k));
+            bytes += W::reduce_add(len);
+        }
+    }
+    if (t >= A.D.n_tiles) return;
+    uint32_t *c = (uint32_t *)(A.D.R.counts + t);
+    W::write_uni(c, 0u, bytes); W::write_uni(c, 1u, CBC_ST_OK); W::write_uni(c, 2u, lines); W::write_uni(c, 3u, 0u);
+    if (lines) W::list_add(A.D.ctr, W::splat(1u), W::splat(lines), W::lane() == 0u);
+}
+
+template <class W>
+CBC_FN void cbc_pileup_write(const cbc_pileup_args &A, uint32_t t)
+{
+    typedef typename W::V32 V32;
+    typedef typename W::Mask Mask;
+    if (!cbc_pileup_text_ok(A, t)) return;
+    const uint32_t bytes = A.D.R.counts[t].nbytes, nl = A.D.name_len;
+    const uint64_t o0 = A.D.R.offsets[t];
+    if (bytes == 0u || o0 > A.D.R.text_cap || bytes > A.D.R.text_cap - o0) return;
+    uint64_t o = o0;
+    uint32_t run = (uint32_t)A.D.sum_off[t];
+    for (uint32_t r = 0; r < CBC_DEPTH_TILE / 64u; r++) {
+        V32 v[9], rb, len;
+        const Mask k = cbc_pileup_line<W>(A, t * CBC_DEPTH_TILE + r * 64u, run, v, rb, len);
+        if (W::ballot(k) == 0ull) continue;
+        const V32 incl = W::scan_incl_add(len);
+        const uint32_t chunk = W::readlane(incl, 63u);
+        if (chunk > (o0 + bytes) - o) return;                        /* the counters moved under the count pass */
+        const V32 at = incl - len;
+        /* the line: name, '\t' at nl, pos1, '\t' at e[0], the reference byte, '\t' at e[0] + 2, then the eight counts, number s
+         * ending at e[s] with a '\t' there; e[8] = len - 1 holds the '\n' */
+        V32 e[9], hi[9], lo[9];
+        e[0] = cbc_sam_ndig_v<W>(v[0], 1000000000u) + (nl + 1u);
+        e[1] = e[0] + cbc_sam_ndig_v<W>(v[1], 1000000000u) + 3u;
+        for (uint32_t s = 2; s < 9u; s++) e[s] = e[s - 1u] + cbc_sam_ndig_v<W>(v[s], 1000000000u) + 1u;
+        for (uint32_t s = 0; s < 9u; s++) cbc_depth_split<W>(v[s], hi[s], lo[s]);
+        uint8_t *dst = A.D.R.text + o;
+        const uint32_t maxlen = W::readlane(W::scan_incl_max(len), 63u);
+        for (uint32_t q = 0; q < maxlen; q += 4u) {
+            V32 out = W::splat(0u);
+            for (uint32_t tt = 0; tt < 4u; tt++) {
+                const uint32_t i = q + tt;
+                V32 by;
+                if (i < nl) by = W::splat(W::read_uni8(A.D.name, i));
+                else {
+                    const V32 iv = W::splat(i);
+                    V32 h = hi[8], l = lo[8], ee = e[8];
+                    Mask tab = iv == nl;
+                    for (int s = 7; s >= 0; s--) {                   /* the first number that ends behind byte i */
+                        const Mask lt = iv < e[s];
+                        h = W::select(lt, hi[s], h); l = W::select(lt, lo[s], l); ee = W::select(lt, e[s], ee);
+                        tab = tab | (iv == e[s]);
+                    }
+                    by = cbc_depth_digit<W>(h, l, (ee - 1u) - iv);
+                    by = W::select(tab | (iv == e[0] + 2u), W::splat(9u), by);
+                    by = W::select(iv == e[0] + 1u, rb, by);
+                    by = W::select(iv == e[8], W::splat(10u), by);
+                }
+                out = out | (by << (8u * tt));
+            }
+            const Mask full = k & (W::splat(q + 4u) <= len);
+            W::store32_bytes(dst, at + q, out, full);
+            const Mask part = k & !full & (W::splat(q) < len);
+            if (W::ballot(part) != 0ull)
+                for (uint32_t tt = 0; tt < 3u; tt++)
+                    W::store8(dst, at + (q + tt), (out >> (8u * tt)) & 0xffu, part & (W::splat(q + tt) < len));
+        }
+        o += chunk;
+    }
+}
+
+#endif /* CBC_PILEUP_BODY_H */

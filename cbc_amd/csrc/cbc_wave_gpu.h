@@ -195,6 +195,10 @@ struct WaveGPU {
     static CBC_FN V32 load8(const uint8_t *p, V32 byteoff, Mask m) { return m ? (uint32_t)p[byteoff] : 0u; }
     static CBC_FN void store8(uint8_t *p, V32 byteoff, V32 val, Mask m) { if (m) p[byteoff] = (uint8_t)val; }
     static CBC_FN void store32_bytes(uint8_t *p, V32 byteoff, V32 val, Mask m) { if (m) *(u32_unaligned *)(p + byteoff) = val; }
+    /* 16-bit entries (the edit arena of the EDITS decoder, cbc_decode_body.h, and its reader, cbc_pileup_body.h) */
+    static CBC_FN void store16(uint16_t *p, V32 idx, V32 val, Mask m) { if (m) p[idx] = (uint16_t)val; }
+    static CBC_FN V32 load16(const uint16_t *p, V32 idx, Mask m) { return m ? (uint32_t)p[idx] : 0u; }
+    static CBC_FN uint32_t read_uni16(const uint16_t *p, uint32_t idx) { return uni((uint32_t)p[idx]); }
     static CBC_FN void store_rec(uint4 *p, V32 idx, Mask m, V32 a, V32 b, V32 c, V32 d) { if (m) p[idx] = make_uint4(a, b, c, d); }
     /* 16-byte record gather (cbc_read_rec) */
     static CBC_FN void load_rec(const uint4 *p, V32 idx, Mask m, V32 &a, V32 &b, V32 &c, V32 &d)

@@ -276,6 +276,19 @@ def lib():
         L.cbc_gpu_last_stats_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 2
         L.cbc_gpu_last_depth_ms.restype = ctypes.c_int
         L.cbc_gpu_last_depth_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
+        L.cbc_gpu_decode_pileup.restype = ctypes.c_int
+        L.cbc_gpu_decode_pileup.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                            ctypes.POINTER(host.LdsCaps), ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32,
+                                            ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                            ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.cbc_gpu_last_pileup_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_pileup_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
+        L.cbc_gpu_decode_blocks_edits.restype = ctypes.c_int
+        L.cbc_gpu_decode_blocks_edits.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                                  ctypes.POINTER(host.LdsCaps), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                  ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p]
         if L.cbc_gpu_abi_version() != 1:
             raise CbcGpuError("libcbc_gpu.so ABI version mismatch")
         _lib = L
@@ -300,7 +313,10 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_decode_coverage", "cbc_gpu_last_coverage_ms", "cbc_gpu_decode_depth_hist", "cbc_gpu_last_hist_ms", "cbc_gpu_decode_stats",
            "cbc_gpu_last_stats_ms",
            "cbc_gpu_decode_coverage_ext", "cbc_gpu_last_coverage_ext_ms",
-           "cbc_gpu_decode_coverage_quant", "cbc_gpu_last_coverage_quant_ms"]
+           "cbc_gpu_decode_coverage_quant", "cbc_gpu_last_coverage_quant_ms",
+           "cbc_gpu_decode_pileup", "cbc_gpu_last_pileup_ms", "cbc_gpu_decode_blocks_edits"]
+
+EDITS_PER_READ = 16           # CBC_EDITS_PER_READ: the library's default arena size, entries per read of a block
 
 
 class Encoder:
@@ -618,6 +634,80 @@ class Encoder:
         if results:
             return text, n_runs, n_kept, self._cat(allres)
         return text
+
+    def decode_pileup(self, plan: "host.UnpackPlan", region=None, exclude_flags=0, min_alt=1, edits_per_read=None, results=False,
+                      text_cap=None):
+        """What the container's reads show at the positions where they disagree with the reference (cbc_gpu_decode_pileup):
+        per position with at least min_alt non-reference observations `NAME\\tpos1\\tref\\tdepth\\tA\\tC\\tG\\tT\\tN\\tdel\\tins\\n`,
+        in the codec's view of the alignment; reads with FLAG & exclude_flags != 0 are left out.  region=None: every contig that
+        has blocks, as a whole, in the order of the contig table; otherwise (NAME, NAME:BEG or NAME:BEG-END) only the window.  The
+        reference must have been uploaded (upload_reference(plan.ref)).  A selection without blocks gives b"" and runs nothing
+        on the device.  edits_per_read (1..510, default 16) sizes the arena the decoder keeps the alignment in: a block that
+        needs more fails with status 9 (CBC_ST_EDITS).  With results=True returns (text, n_lines, n_reads_kept, per-block decode
+        results of the blocks used) and lets a failed block pass (it contributes nothing); text_cap: size of the buffer of one
+        call (default: plan.pileup_text_cap of its blocks and window)."""
+        plan.sam_header()                                     # refuses what the text cannot carry, and long-read containers
+        if int(min_alt) < 1:
+            raise ValueError("min_alt is 1 or more")
+        epr = EDITS_PER_READ if edits_per_read is None else int(edits_per_read)
+        if not 1 <= epr <= 510:
+            raise ValueError("edits_per_read is in 1..510")
+        sels = [plan.region(region)] if region is not None else [plan.contig_blocks(c) for c in range(plan.n_contigs)]
+        out, n_lines, n_kept, allres = [], 0, 0, []
+        self.last_pileup_text_bytes = 0
+        self._pileup_ms = None
+        caps, pay, _, _ = self._plan_args(plan)
+        for sel in sels:
+            nb = sel.b1 - sel.b0
+            if nb == 0:
+                continue
+            blocks, ws, _ = self._gather(plan, slice(sel.b0, sel.b1))
+            off = int(plan.contig_name_off[sel.contig])
+            name = plan.names[off:].tobytes().split(b"\0", 1)[0]
+            cap = plan.pileup_text_cap(sel.b0, sel.b1, sel.contig, sel.beg, sel.end, sel.smax) if text_cap is None else int(text_cap)
+            text = np.zeros(max(cap, 1), dtype=np.uint8)
+            res = np.zeros(nb, dtype=host.RESULT_DTYPE)
+            nbytes, nl, nk = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+            rc = lib().cbc_gpu_decode_pileup(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
+                                             ws.ctypes.data, name, len(name), sel.beg, sel.end, sel.smax, int(exclude_flags),
+                                             int(min_alt), epr, text.ctypes.data, cap, ctypes.byref(nbytes), ctypes.byref(nl),
+                                             ctypes.byref(nk), res.ctypes.data)
+            self.last_pileup_text_bytes += int(nbytes.value)
+            self._check_blocks(rc, "cbc_gpu_decode_pileup", results)
+            self._add_ms("_pileup_ms", "cbc_gpu_last_pileup_ms", 4, must=True)
+            out.append(text[:int(nbytes.value)].tobytes())
+            n_lines += int(nl.value); n_kept += int(nk.value); allres.append(res)
+        text = b"".join(out)
+        if results:
+            return text, n_lines, n_kept, self._cat(allres)
+        return text
+
+    def last_pileup_ms(self):
+        """(edits decode, zero + mark + events, scans, text) kernel milliseconds of the last decode_pileup, summed over its calls."""
+        if getattr(self, "_pileup_ms", None) is None:
+            raise CbcGpuError("no decode_pileup has run on the device")
+        return self._pileup_ms
+
+    def decode_blocks_edits(self, plan: "host.UnpackPlan", smax, edits_per_read=None):
+        """decode_blocks_span with the alignment of the reads with indels kept as well (cbc_gpu_decode_blocks_edits).  Returns
+        (recs, seq, results, side, arena): side[r] = (first arena entry of record r relative to its block's, nDel | nIns << 16),
+        arena = uint16 entries, block b owning [rec_base * edits_per_read, (rec_base + n_reads) * edits_per_read)."""
+        nb = plan.n_blocks
+        epr = EDITS_PER_READ if edits_per_read is None else int(edits_per_read)
+        blocks = plan.blocks.copy()
+        recs = np.zeros(plan.n_recs, dtype=host.REC_DTYPE)
+        seq = np.zeros(plan.n_recs * plan.seq_stride + 8, dtype=np.uint8)
+        res = np.zeros(nb, dtype=host.RESULT_DTYPE)
+        side = np.zeros((max(plan.n_recs, 1), 2), dtype=np.uint32)
+        arena = np.zeros(max(plan.n_recs * epr, 1), dtype=np.uint16)
+        caps = host.LdsCaps(plan.cap_pos, plan.cap_var)
+        pay = np.ascontiguousarray(plan.payloads)
+        rc = lib().cbc_gpu_decode_blocks_edits(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps), smax, epr,
+                                               recs.ctypes.data, plan.n_recs, seq.ctypes.data, seq.size, side.ctypes.data,
+                                               arena.ctypes.data, res.ctypes.data)
+        if rc != 0 and rc != -4:
+            self._check(rc, "cbc_gpu_decode_blocks_edits")
+        return recs, seq, res, side[:plan.n_recs], arena[:plan.n_recs * epr]
 
     def decode_targets(self, plan: "host.UnpackPlan", targets, output="reads", exclude_flags=0, results=False, text_cap=None):
         """The reads that overlap at least one interval of `targets` (a host.TargetSet of plan.targets()), in one decode of the

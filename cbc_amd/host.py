@@ -205,6 +205,9 @@ def lib():
         L.cbc_unpack_contig_blocks.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.POINTER(RegionSelC), ctypes.c_char_p, ctypes.c_size_t]
         L.cbc_unpack_depth_text_cap.restype = ctypes.c_uint64
         L.cbc_unpack_depth_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+        L.cbc_unpack_pileup_text_cap.restype = ctypes.c_uint64
+        L.cbc_unpack_pileup_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                 ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
         L.cbc_unpack_targets.restype = ctypes.c_int
         L.cbc_unpack_targets.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.c_void_p,
                                          ctypes.c_size_t, ctypes.POINTER(ctypes.POINTER(TargetsC)), ctypes.c_char_p, ctypes.c_size_t]
@@ -690,6 +693,11 @@ class UnpackPlan:
     def depth_text_cap(self, b0, b1, contig) -> int:
         """Bytes that always hold the bedGraph of blocks [b0, b1) of contig `contig` (cbc_unpack_depth_text_cap)."""
         return int(lib().cbc_unpack_depth_text_cap(self._ptr, b0, b1, contig))
+
+    def pileup_text_cap(self, b0, b1, contig, beg, end, smax) -> int:
+        """Bytes that always hold the pileup lines of blocks [b0, b1) of contig `contig` for the window [beg, end] and the span
+        bound smax (cbc_unpack_pileup_text_cap)."""
+        return int(lib().cbc_unpack_pileup_text_cap(self._ptr, b0, b1, contig, beg, end, smax))
 
     def sam_header(self) -> bytes:
         """@HD and one @SQ line per contig of the container's table (cbc_unpack_sam_header): what precedes the alignment

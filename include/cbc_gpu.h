@@ -60,6 +60,8 @@ extern "C" {
                                 /* of more than CBC_MAX_BLOCK_READS records; a LOSSY stream         */
 #define CBC_ST_SPAN         8   /* region decode: a read covers more reference bases than the bound */
                                 /* the block selection assumed (cbc_gpu_decode_region, smax)        */
+#define CBC_ST_EDITS        9   /* edit-reporting decode: the block's reads with indels hold more   */
+                                /* deleted and inserted bases than its arena (edits_per_read)       */
 
 /* ---- packed record layout (device and host share it) ---------------------------------------- */
 
@@ -338,8 +340,8 @@ int  cbc_gpu_last_sam_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *count_ms, fl
  *     <name>\t<start0>\t<end0>\t<depth>\n
  * Depth at position p = the kept reads with POS <= p <= POS + span - 1, POS = window_start[b] + the block-local POS and span
  * the reference bases the codec's reconstruction covers (rlen for a read coded as perfect, rlen + nDel - nIns otherwise; 0
- * covers nothing).  This is a SPAN coverage: deleted bases count as covered (the file does not say where in the read they
- * lie) -- for ordinary CIGARs the interval M + D + N, what `bedtools genomecov -bg` and `samtools depth -J` count.  Kept =
+ * covers nothing).  This is a SPAN coverage: deleted bases count as covered (this pass reads only the span; where they lie
+ * is what cbc_gpu_decode_pileup keeps) -- for ordinary CIGARs the interval M + D + N, what `bedtools genomecov -bg` and `samtools depth -J` count.  Kept =
  * every read cbc_gpu_decode_region keeps for [beg, end] with (FLAG & exclude_flags) == 0.  Reads are clipped to the window and
  * runs that reach its edge end there.  `name` (name_bytes of it, 1..CBC_SAM_MAX_NAME, no tab / newline / NUL) is the text of
  * the first column.  A block that fails to decode marks nothing and the call returns CBC_E_BLOCK, as cbc_gpu_decode_region
@@ -354,6 +356,51 @@ int  cbc_gpu_decode_depth(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes
 /* Kernel times of the most recent cbc_gpu_decode_depth (HIP events on its stream): the span decode; zeroing + mark; tile
  * sums, scans and change points; line count, scan and the text. */
 int  cbc_gpu_last_depth_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *text_ms);
+
+/* ---- per-position allele counts of a decode -------------------------------------------------------
+ * Decode `blocks` -- a selection of cbc_unpack_region or cbc_unpack_contig_blocks on ONE contig -- with the decoder that keeps
+ * the alignment it reconstructs with, and write what the kept reads show at the positions of the window [beg, end] (1-based,
+ * inclusive, end <= CBC_SAM_MAX_POS) where they disagree with the reference; computed and formatted on the device, tab-separated,
+ * no header, in position order:
+ *     <name>\t<pos1>\t<ref>\t<depth>\t<A>\t<C>\t<G>\t<T>\t<N>\t<del>\t<ins>\n
+ * ref = the byte of the uploaded reference; every other column a decimal integer.  Kept = the reads cbc_gpu_decode_depth keeps
+ * under the same exclude_flags.  The alignment is the codec's: a read without indels (coded as perfect, or SNPs only) has read
+ * base q at POS + q.  A read with nDel deleted bases at matched coordinates dc[] and nIns inserted bases at read indices oi[]
+ * (both as the decoder holds them): q == oi[i] is inserted; any other q has m = q - #{i : oi[i] < q} and is aligned to
+ * POS + m + #{d : dc[d] <= m}; deleted base d (decode order) is POS + dc[d] + d.  Whatever that maps outside the read's span
+ * [POS, POS + span - 1] is not counted.  The class of a byte is byte & 0xDF: A, C, G, T, anything else is N.  A..N = the aligned
+ * read bases of the class; del = deleted bases; ins = insertion events, an event being a maximal run of inserted read indices,
+ * anchored at the position of the nearest aligned base before it, or at POS when there is none (a trailing soft clip is stored
+ * as insertions and shows as one event at the read's last aligned base).  depth = A + C + G + T + N + del, which is the depth
+ * cbc_gpu_decode_depth reports.  Position p gets a line when depth - (count of ref's class) + ins >= min_alt (>= 1).  Reads are
+ * clipped to the window; an event whose anchor lies outside it is not counted.
+ * edits_per_read (1..CBC_EDITS_MAX, 0 = CBC_EDITS_PER_READ) sizes the arena the alignment is kept in: a block of n reads has
+ * room for n * edits_per_read deleted and inserted bases of its reads with indels, 2 bytes each; a block that needs more fails
+ * with CBC_ST_EDITS, nothing is truncated.  A block that fails to decode contributes nothing and the call returns CBC_E_BLOCK.
+ * *text_bytes = bytes of text (also when text_cap is too small: CBC_E_ARG, nothing copied), *n_lines = lines, *n_reads_kept =
+ * reads counted.  text_cap = min(window, reads * smax) * (name_bytes + 102) always suffices (cbc_unpack_pileup_text_cap).  The
+ * window costs 4 + 28 bytes of device memory per position: CBC_E_NOMEM when that cannot be had.  One chunk, one stream, no host
+ * round trip between the kernels. */
+#define CBC_EDITS_PER_READ 16u
+#define CBC_EDITS_MAX      510u
+int  cbc_gpu_decode_pileup(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                           uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                           const char *name, uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax,
+                           uint32_t exclude_flags, uint32_t min_alt, uint32_t edits_per_read, uint8_t *text, uint64_t text_cap,
+                           uint64_t *text_bytes, uint64_t *n_lines, uint64_t *n_reads_kept,
+                           cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_pileup (HIP events on its stream): the edits decode; zeroing + mark + events;
+ * tile sums, their scan, the line count and its scan; the text. */
+int  cbc_gpu_last_pileup_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *events_ms, float *scan_ms, float *text_ms);
+/* cbc_gpu_decode_blocks_span with the edits reported as well (the decoder the pileup runs, with everything it leaves returned;
+ * what the tests check it with): side[2 r] = the first arena entry of record r relative to its block's, side[2 r + 1] =
+ * nDel | nIns << 16 (both 0 for a read without indels); block b owns arena entries [rec_base * edits_per_read, (rec_base +
+ * n_reads) * edits_per_read); a record's entries are its nDel matched coordinates, then its nIns read indices.  side holds
+ * 2 * n_recs words, arena n_recs * edits_per_read entries. */
+int  cbc_gpu_decode_blocks_edits(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, cbc_dec_block_desc *blocks,
+                                 uint32_t n_blocks, const cbc_lds_caps *caps, uint32_t smax, uint32_t edits_per_read,
+                                 cbc_read_rec *recs, uint64_t n_recs, uint8_t *seq, uint64_t seq_bytes, uint32_t *side,
+                                 uint16_t *arena, cbc_block_result *results /* n_blocks or NULL */);
 
 /* ---- decode of a set of regions -------------------------------------------------------------------
  * `blocks` are the blocks a target set selects (cbc_unpack_targets of libcbc_host: the union of the single-region selections

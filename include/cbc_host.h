@@ -223,6 +223,13 @@ uint64_t cbc_unpack_sam_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t
 int      cbc_unpack_contig_blocks(const cbc_unpack_plan *u, uint32_t contig, cbc_region_sel *sel, char *errbuf, size_t errlen);
 uint64_t cbc_unpack_depth_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig);
 
+/* Per-position allele counts (the text comes from cbc_gpu_decode_pileup).  A text_cap that always holds
+ * the lines of blocks [b0, b1) of contig `contig` for the window [beg, end] and the span bound smax of their selection: a line
+ * per position of the window at most, and per reference base a kept read spans, of at most len(name) + 102 bytes each (0 for a
+ * plan cbc_unpack_sam_header refuses, a bad range or a bad window).  The proof stands at the function. */
+uint64_t cbc_unpack_pileup_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg, uint64_t end,
+                                    uint32_t smax);
+
 /* Decode of a set of regions (the text comes from cbc_gpu_decode_targets).  The set is every string of
  * `regions` (parsed, clamped and refused exactly as cbc_unpack_region does) plus the lines of the BED text `bed` (bed_len bytes,
  * need not end in a newline or a NUL; NULL: none).  BED: fields separated by tabs or runs of spaces, at least `chrom start0 end0`
