@@ -43,24 +43,13 @@ struct cbc_cov_args {
     uint32_t slots;                                      /* slots of the compressed coordinate: no query reaches past them      */
 };
 
-/* change points of the call: what the compact pass counted, never more than the tables hold */
-CBC_FN uint32_t cbc_cov_points(const cbc_cov_args &A)
-{
-    const uint64_t n = A.cnt_off[A.n_tiles];
-    return n > A.cp_cap ? A.cp_cap : (uint32_t)n;
-}
-
 /* runs [j0, j0 + 64): weight (two words) and covered slots; a lane whose run does not exist (j + 1 >= ncp) gets zeros */
 template <class W>
 CBC_FN void cbc_cov_runs(const cbc_cov_args &A, uint32_t j0, uint32_t ncp, typename W::V32 &wlo, typename W::V32 &whi,
                          typename W::V32 &cov)
 {
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const V32 j = W::lane() + j0;
-    const Mask m = (j + 1u) < ncp;                                   /* ncp <= cp_cap < 2^32 - 64: no wrap */
-    const V32 p = W::load32(A.cp_pos, j, m, 0u), q = W::load32(A.cp_pos, j + 1u, m, 0u), d = W::load32(A.cp_dep, j, m, 0u);
-    const V32 len = q - p;
+    typename W::V32 d, len;
+    const typename W::Mask m = cbc_depth_run_load<W>(A.cp_pos, A.cp_dep, j0, ncp, d, len);
     wlo = d * len;
     whi = W::mulhi(d, len);
     cov = W::select(m & (d >= A.min_depth), len, W::splat(0u));
@@ -76,7 +65,7 @@ template <class W>
 CBC_FN void cbc_cov_weights(const cbc_cov_args &A, uint32_t tt)
 {
     typedef typename W::V32 V32;
-    const uint32_t ncp = cbc_cov_points(A);
+    const uint32_t ncp = cbc_depth_points(A.cnt_off, A.n_tiles, A.cp_cap);
     V32 alo = W::splat(0u), ahi = W::splat(0u), ac = W::splat(0u);
     if (tt < A.n_ttiles)
         for (uint32_t r = 0; r < CBC_DEPTH_LINES / 64u; r++) {
@@ -90,10 +79,9 @@ CBC_FN void cbc_cov_weights(const cbc_cov_args &A, uint32_t tt)
         }
     const uint64_t tot = (uint64_t)W::reduce_add(alo & 0xffffu) + ((uint64_t)W::reduce_add(alo >> 16) << 16) +
                          ((uint64_t)W::reduce_add(ahi) << 32);
-    uint32_t *tl = (uint32_t *)(A.tile_wlo + tt), *th = (uint32_t *)(A.tile_whi + tt), *tc = (uint32_t *)(A.tile_cov + tt);
-    W::write_uni(tl, 0u, (uint32_t)tot); W::write_uni(tl, 1u, CBC_ST_OK); W::write_uni(tl, 2u, 0u); W::write_uni(tl, 3u, 0u);
-    W::write_uni(th, 0u, (uint32_t)(tot >> 32)); W::write_uni(th, 1u, CBC_ST_OK); W::write_uni(th, 2u, 0u); W::write_uni(th, 3u, 0u);
-    W::write_uni(tc, 0u, W::reduce_add(ac)); W::write_uni(tc, 1u, CBC_ST_OK); W::write_uni(tc, 2u, 0u); W::write_uni(tc, 3u, 0u);
+    cbc_store_result<W>(A.tile_wlo + tt, (uint32_t)tot, 0u);
+    cbc_store_result<W>(A.tile_whi + tt, (uint32_t)(tot >> 32), 0u);
+    cbc_store_result<W>(A.tile_cov + tt, W::reduce_add(ac), 0u);
 }
 
 template <class W>
@@ -102,7 +90,7 @@ CBC_FN void cbc_cov_apply(const cbc_cov_args &A, uint32_t tt)
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
     if (tt >= A.n_ttiles) return;
-    const uint32_t ncp = cbc_cov_points(A);
+    const uint32_t ncp = cbc_depth_points(A.cnt_off, A.n_tiles, A.cp_cap);
     uint64_t run = A.wlo_off[tt] + (A.whi_off[tt] << 32);           /* S in front of the tile */
     uint32_t crun = (uint32_t)A.cov_off[tt];
     for (uint32_t r = 0; r < CBC_DEPTH_LINES / 64u; r++) {
@@ -156,7 +144,7 @@ CBC_FN void cbc_cov_lookup(const cbc_cov_args &A, uint32_t w)
     const Mask m = i < A.n_q;
     const V32 slot = W::load32(A.q, i * 2u, m, 0u), len = W::load32(A.q, i * 2u + 1u, m, 0u);
     const Mask ok = m & (slot <= A.slots) & (len <= A.slots - slot);
-    const uint32_t ncp = cbc_cov_points(A);
+    const uint32_t ncp = cbc_depth_points(A.cnt_off, A.n_tiles, A.cp_cap);
     V32 alo, ahi, ac, blo, bhi, bc;
     cbc_cov_prefix<W>(A, ncp, slot, ok, alo, ahi, ac);
     cbc_cov_prefix<W>(A, ncp, slot + len, ok, blo, bhi, bc);        /* <= A.slots under ok */

@@ -51,29 +51,12 @@ struct cbc_covx_args {
     uint32_t slots, reserved;
 };
 
-CBC_FN uint32_t cbc_covx_points(const cbc_covx_args &A)
-{
-    const uint64_t n = A.cnt_off[A.n_tiles];
-    return n > A.cp_cap ? A.cp_cap : (uint32_t)n;
-}
-
-CBC_FN uint32_t cbc_covx_starts(const cbc_covx_args &A)
-{
-    const uint64_t n = A.sp_off[A.n_tiles];
-    return n > A.sp_cap ? A.sp_cap : (uint32_t)n;
-}
-
 /* runs [j0, j0 + 64): depth and length; a lane whose run does not exist (j + 1 >= ncp) gets length 0 */
 template <class W>
 CBC_FN void cbc_covx_runs(const cbc_covx_args &A, uint32_t j0, uint32_t ncp, typename W::V32 &d, typename W::V32 &len)
 {
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const V32 j = W::lane() + j0;
-    const Mask m = (j + 1u) < ncp;                                   /* ncp <= cp_cap < 2^32 - 64: no wrap */
-    const V32 p = W::load32(A.cp_pos, j, m, 0u), q = W::load32(A.cp_pos, j + 1u, m, 0u);
-    d = W::load32(A.cp_dep, j, m, 0u);
-    len = W::select(m, q - p, W::splat(0u));
+    const typename W::Mask m = cbc_depth_run_load<W>(A.cp_pos, A.cp_dep, j0, ncp, d, len);
+    len = W::select(m, len, W::splat(0u));
 }
 
 template <class W>
@@ -81,7 +64,7 @@ CBC_FN void cbc_covx_weights(const cbc_covx_args &A, uint32_t tt)
 {
     typedef typename W::V32 V32;
     if (tt >= A.n_ttiles || A.n_thr > CBC_COVX_MAX_THR) return;
-    const uint32_t ncp = cbc_covx_points(A);
+    const uint32_t ncp = cbc_depth_points(A.cnt_off, A.n_tiles, A.cp_cap);
     V32 ac[CBC_COVX_MAX_THR];
 CBC_COVX_UNROLL
     for (uint32_t t = 0; t < CBC_COVX_MAX_THR; t++) ac[t] = W::splat(0u);
@@ -96,10 +79,8 @@ CBC_COVX_UNROLL
     }
 CBC_COVX_UNROLL
     for (uint32_t t = 0; t < CBC_COVX_MAX_THR; t++)
-        if (t < A.n_thr) {
-            uint32_t *tc = (uint32_t *)(A.tile_thr + ((uint64_t)t * A.n_ttiles + tt));
-            W::write_uni(tc, 0u, W::reduce_add(ac[t])); W::write_uni(tc, 1u, CBC_ST_OK); W::write_uni(tc, 2u, 0u); W::write_uni(tc, 3u, 0u);
-        }
+        if (t < A.n_thr)
+            cbc_store_result<W>(A.tile_thr + ((uint64_t)t * A.n_ttiles + tt), W::reduce_add(ac[t]), 0u);
 }
 
 template <class W>
@@ -108,7 +89,7 @@ CBC_FN void cbc_covx_apply(const cbc_covx_args &A, uint32_t tt)
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
     if (tt >= A.n_ttiles || A.n_thr > CBC_COVX_MAX_THR) return;
-    const uint32_t ncp = cbc_covx_points(A);
+    const uint32_t ncp = cbc_depth_points(A.cnt_off, A.n_tiles, A.cp_cap);
     uint32_t crun[CBC_COVX_MAX_THR];
 CBC_COVX_UNROLL
     for (uint32_t t = 0; t < CBC_COVX_MAX_THR; t++)
@@ -142,7 +123,7 @@ CBC_FN void cbc_covx_lookup(const cbc_covx_args &A, uint32_t w)
     const Mask m = i < A.n_q;
     const V32 slot = W::load32(A.q, i * 2u, m, 0u), len = W::load32(A.q, i * 2u + 1u, m, 0u);
     const Mask ok = m & (slot <= A.slots) & (len <= A.slots - slot);
-    const uint32_t ncp = cbc_covx_points(A);
+    const uint32_t ncp = cbc_depth_points(A.cnt_off, A.n_tiles, A.cp_cap);
     /* the last change point at or below x = slot (a) and x = slot + len (b): k = change points with cp_pos <= x */
     const V32 end = slot + len;                                      /* <= A.slots under ok */
     const V32 ka = cbc_targets_find<W>(A.cp_pos, 1u, ncp, slot + 1u, ok), kb = cbc_targets_find<W>(A.cp_pos, 1u, ncp, end + 1u, ok);
@@ -160,7 +141,7 @@ CBC_COVX_UNROLL
             W::store32(A.thr_covered, i * A.n_thr + t, cb - ca, m);
         }
     if (A.reads) {
-        const uint32_t nsp = cbc_covx_starts(A);
+        const uint32_t nsp = cbc_depth_points(A.sp_off, A.n_tiles, A.sp_cap);
         const Mask one = ok & (len != 0u);
         /* CS(y) = sp_cnt of the last start point with sp_pos <= y, 0 in front of the first one */
         const V32 sa = cbc_targets_find<W>(A.sp_pos, 1u, nsp, slot + 1u, one), sb = cbc_targets_find<W>(A.sp_pos, 1u, nsp, end, one);

@@ -21,9 +21,10 @@
  *   count    run j = [cp[j].pos, cp[j + 1].pos) with depth cp[j].depth, a line when that depth is not 0.  One wavefront
  *            per CBC_DEPTH_LINES runs: line lengths (digit counts by compares), lines and bytes into a cbc_block_result
  *            for the size scan (64-bit text offsets).
- *   write    the same runs, one lane per line: the line is made four bytes at a time (digits by the multiply-shift
- *            scheme of cbc_sam_body.h) and written as dwords at the line's own byte offset; a dword never leaves its line,
- *            the last 1..3 bytes are byte stores.
+ *   write    the same runs, one lane per line (digits by the multiply-shift scheme of cbc_sam_body.h), through the
+ *            line-per-lane writer cbc_lines_store, which cbc_pileup_body.h uses too.
+ * count and write are the run-text skeleton below (cbc_runs_count / cbc_runs_write); cbc_targets_body.h instantiates it with
+ * its own line function.  cbc_depth_points and cbc_depth_run_load serve every pass that reads the change points.
  * Range tests are written without base + length sums.  Written against the wave policy (W = WaveGPU in cbc_gpu.hip, the
  * lock-step emulation in tests/depth_emu).
  */
@@ -106,9 +107,8 @@ CBC_FN void cbc_depth_tile(const cbc_depth_args &A, uint32_t t)
         s = s + a + b + cc + d;
         c = c + cbc_depth_nz<W>(a) + cbc_depth_nz<W>(b) + cbc_depth_nz<W>(cc) + cbc_depth_nz<W>(d);
     }
-    uint32_t *ts = (uint32_t *)(A.tile_sum + t), *tc = (uint32_t *)(A.tile_cnt + t);
-    W::write_uni(ts, 0u, W::reduce_add(s)); W::write_uni(ts, 1u, CBC_ST_OK); W::write_uni(ts, 2u, 0u); W::write_uni(ts, 3u, 0u);
-    W::write_uni(tc, 0u, W::reduce_add(c)); W::write_uni(tc, 1u, CBC_ST_OK); W::write_uni(tc, 2u, 0u); W::write_uni(tc, 3u, 0u);
+    cbc_store_result<W>(A.tile_sum + t, W::reduce_add(s), 0u);
+    cbc_store_result<W>(A.tile_cnt + t, W::reduce_add(c), 0u);
 }
 
 template <class W>
@@ -172,33 +172,35 @@ CBC_FN typename W::Mask cbc_depth_line(const cbc_depth_args &A, uint32_t j0, uin
     return k;
 }
 
+/* the run text of cbc_depth_line as it stands: the window's first position is a POS */
+CBC_FN bool cbc_depth_line_ok(const cbc_depth_args &A) { return A.R.beg >= 1u && A.R.beg <= CBC_SAM_MAX_POS; }
+
+/* change points of a call: what the compact pass counted (cnt_off[n_tiles]), never more than the tables hold */
+CBC_FN uint32_t cbc_depth_points(const uint64_t *cnt_off, uint32_t n_tiles, uint32_t cp_cap)
+{
+    const uint64_t n = cnt_off[n_tiles];
+    return n > cp_cap ? cp_cap : (uint32_t)n;
+}
+
 /* runs of the window: the change points less one (the last one ends the last run) */
 CBC_FN uint32_t cbc_depth_runs(const cbc_depth_args &A)
 {
-    const uint64_t n = A.cnt_off[A.n_tiles];
-    const uint32_t ncp = n > A.cp_cap ? A.cp_cap : (uint32_t)n;
+    const uint32_t ncp = cbc_depth_points(A.cnt_off, A.n_tiles, A.cp_cap);
     return ncp ? ncp - 1u : 0u;
 }
 
+/* runs [j0, j0 + 64) of ncp change points: depth and length under the mask returned (the run exists: j + 1 < ncp), zeros
+ * in the other lanes */
 template <class W>
-CBC_FN void cbc_depth_count(const cbc_depth_args &A, uint32_t tt)
+CBC_FN typename W::Mask cbc_depth_run_load(const uint32_t *cp_pos, const uint32_t *cp_dep, uint32_t j0, uint32_t ncp,
+                                           typename W::V32 &d, typename W::V32 &len)
 {
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const uint32_t nr = cbc_depth_runs(A);
-    uint32_t lines = 0, bytes = 0;
-    if (A.name_len <= CBC_SAM_MAX_NAME && A.R.beg >= 1u && A.R.beg <= CBC_SAM_MAX_POS && tt < A.n_ttiles)
-        for (uint32_t r = 0; r < CBC_DEPTH_LINES / 64u; r++) {
-            const uint32_t j0 = tt * CBC_DEPTH_LINES + r * 64u;
-            if (j0 >= nr) break;
-            V32 st, en, dp, len;
-            const Mask k = cbc_depth_line<W>(A, j0, nr, st, en, dp, len);
-            lines += W::popc64(W::ballot(k));
-            bytes += W::reduce_add(len);
-        }
-    uint32_t *c = (uint32_t *)(A.R.counts + tt);
-    W::write_uni(c, 0u, bytes); W::write_uni(c, 1u, CBC_ST_OK); W::write_uni(c, 2u, lines); W::write_uni(c, 3u, 0u);
-    if (lines) W::list_add(A.ctr, W::splat(1u), W::splat(lines), W::lane() == 0u);
+    const typename W::V32 j = W::lane() + j0;
+    const typename W::Mask m = (j + 1u) < ncp;                       /* ncp <= cp_cap < 2^32 - 64: no wrap */
+    const typename W::V32 p = W::load32(cp_pos, j, m, 0u), q = W::load32(cp_pos, j + 1u, m, 0u);
+    d = W::load32(cp_dep, j, m, 0u);
+    len = q - p;
+    return m;
 }
 
 /* v = hi * 10^5 + lo for any 32-bit v: floor(v / 10^5) = floor((v >> 5) / 3125) = ((v >> 5) * M) >> 39 with
@@ -225,16 +227,85 @@ CBC_FN typename W::V32 cbc_depth_digit(const typename W::V32 &hi, const typename
     return (q - W::mulhi(q, W::splat(429496730u)) * 10u) + 48u;
 }
 
-template <class W>
-CBC_FN void cbc_depth_write(const cbc_depth_args &A, uint32_t tt)
+/* ---- the line-per-lane writer ------------------------------------------------------------------------------------------
+ * Lane l under k writes its line of len bytes at dst[at ..]: `name` (nl bytes) and then, for i >= nl, byte i as
+ * cbc_line_byte(L, i) gives it per lane -- overloaded on the line state L (cbc_depth_ln here, cbc_pileup_ln in
+ * cbc_pileup_body.h).  The line is made four bytes at a time and written as dwords at its own byte offset; a dword never
+ * leaves its line, the last 1..3 bytes are byte stores. */
+template <class W, class L>
+CBC_FN void cbc_lines_store(uint8_t *dst, const typename W::V32 &at, const typename W::V32 &len, const typename W::Mask &k,
+                            const uint8_t *name, uint32_t nl, const L &ls)
 {
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
-    if (tt >= A.n_ttiles || A.name_len > CBC_SAM_MAX_NAME || A.R.beg < 1u || A.R.beg > CBC_SAM_MAX_POS) return;
-    const uint32_t nr = cbc_depth_runs(A);
-    const uint32_t bytes = A.R.counts[tt].nbytes, nl = A.name_len;
-    const uint64_t o0 = A.R.offsets[tt];
-    if (bytes == 0u || o0 > A.R.text_cap || bytes > A.R.text_cap - o0) return;
+    const uint32_t maxlen = W::readlane(W::scan_incl_max(len), 63u);
+    for (uint32_t q = 0; q < maxlen; q += 4u) {
+        V32 out = W::splat(0u);
+        for (uint32_t t = 0; t < 4u; t++) {
+            const uint32_t i = q + t;
+            out = out | ((i < nl ? W::splat(W::read_uni8(name, i)) : cbc_line_byte(ls, i)) << (8u * t));
+        }
+        const Mask full = k & (W::splat(q + 4u) <= len);
+        W::store32_bytes(dst, at + q, out, full);
+        const Mask part = k & !full & (W::splat(q) < len);
+        if (W::ballot(part) != 0ull)
+            for (uint32_t t = 0; t < 3u; t++)
+                W::store8(dst, at + (q + t), (out >> (8u * t)) & 0xffu, part & (W::splat(q + t) < len));
+    }
+}
+
+/* a run's line: name, '\t' at nl, start0, '\t' at e1, end0, '\t' at e2, depth, '\n' at e3 = len - 1; the numbers split */
+template <class W>
+struct cbc_depth_ln { typename W::V32 e1, e2, e3, sh, sl, eh, el, dh, dl; uint32_t nl; };
+
+template <class W>
+CBC_FN typename W::V32 cbc_line_byte(const cbc_depth_ln<W> &L, uint32_t i)
+{
+    typedef typename W::V32 V32;
+    typedef typename W::Mask Mask;
+    const V32 iv = W::splat(i);
+    const Mask f1 = iv < L.e1, f2 = iv < L.e2;
+    const V32 hi = W::select(f1, L.sh, W::select(f2, L.eh, L.dh)), lo = W::select(f1, L.sl, W::select(f2, L.el, L.dl));
+    const V32 j = (W::select(f1, L.e1, W::select(f2, L.e2, L.e3)) - 1u) - iv;
+    V32 by = cbc_depth_digit<W>(hi, lo, j);
+    by = W::select((iv == L.nl) | (iv == L.e1) | (iv == L.e2), W::splat(9u), by);
+    return W::select(iv == L.e3, W::splat(10u), by);
+}
+
+/* ---- the run-text skeleton ---------------------------------------------------------------------------------------------
+ * count and write for one line per run of non-zero depth, one wavefront per CBC_DEPTH_LINES runs.  A member is its argument
+ * struct A (D = the cbc_depth_args inside) with two functions overloaded on it: cbc_depth_line<W>(A, j0, nr, st, en, dp, len)
+ * and its guard cbc_depth_line_ok(A).  The members: the window (above), the target set (cbc_targets_body.h). */
+template <class W, class Args>
+CBC_FN void cbc_runs_count(const Args &A, const cbc_depth_args &D, uint32_t tt)
+{
+    typedef typename W::V32 V32;
+    typedef typename W::Mask Mask;
+    const uint32_t nr = cbc_depth_runs(D);
+    uint32_t lines = 0, bytes = 0;
+    if (D.name_len <= CBC_SAM_MAX_NAME && cbc_depth_line_ok(A) && tt < D.n_ttiles)
+        for (uint32_t r = 0; r < CBC_DEPTH_LINES / 64u; r++) {
+            const uint32_t j0 = tt * CBC_DEPTH_LINES + r * 64u;
+            if (j0 >= nr) break;
+            V32 st, en, dp, len;
+            const Mask k = cbc_depth_line<W>(A, j0, nr, st, en, dp, len);
+            lines += W::popc64(W::ballot(k));
+            bytes += W::reduce_add(len);
+        }
+    cbc_store_result<W>(D.R.counts + tt, bytes, lines);
+    if (lines) W::list_add(D.ctr, W::splat(1u), W::splat(lines), W::lane() == 0u);
+}
+
+template <class W, class Args>
+CBC_FN void cbc_runs_write(const Args &A, const cbc_depth_args &D, uint32_t tt)
+{
+    typedef typename W::V32 V32;
+    typedef typename W::Mask Mask;
+    if (tt >= D.n_ttiles || D.name_len > CBC_SAM_MAX_NAME || !cbc_depth_line_ok(A)) return;
+    const uint32_t nr = cbc_depth_runs(D);
+    const uint32_t bytes = D.R.counts[tt].nbytes;
+    const uint64_t o0 = D.R.offsets[tt];
+    if (bytes == 0u || o0 > D.R.text_cap || bytes > D.R.text_cap - o0) return;
     uint64_t o = o0;
     for (uint32_t r = 0; r < CBC_DEPTH_LINES / 64u; r++) {
         const uint32_t j0 = tt * CBC_DEPTH_LINES + r * 64u;
@@ -245,41 +316,20 @@ CBC_FN void cbc_depth_write(const cbc_depth_args &A, uint32_t tt)
         const uint32_t chunk = W::readlane(incl, 63u);
         if (chunk > (o0 + bytes) - o) return;                        /* the change points moved under the count pass */
         if (chunk == 0u) continue;
-        const V32 at = incl - len;
-        /* the line: name, '\t' at nl, start0, '\t' at e1, end0, '\t' at e2, depth, '\n' at e3 = len - 1 */
-        const V32 e1 = cbc_sam_ndig_v<W>(st, 1000000000u) + (nl + 1u);
-        const V32 e2 = e1 + cbc_sam_ndig_v<W>(en, 1000000000u) + 1u;
-        const V32 e3 = len - 1u;
-        V32 sh, sl, eh, el, dh, dl;
-        cbc_depth_split<W>(st, sh, sl); cbc_depth_split<W>(en, eh, el); cbc_depth_split<W>(dp, dh, dl);
-        uint8_t *dst = A.R.text + o;
-        const uint32_t maxlen = W::readlane(W::scan_incl_max(len), 63u);
-        for (uint32_t q = 0; q < maxlen; q += 4u) {
-            V32 out = W::splat(0u);
-            for (uint32_t t = 0; t < 4u; t++) {
-                const uint32_t i = q + t;
-                V32 by;
-                if (i < nl) by = W::splat(W::read_uni8(A.name, i));
-                else {
-                    const V32 iv = W::splat(i);
-                    const Mask f1 = iv < e1, f2 = iv < e2;
-                    const V32 hi = W::select(f1, sh, W::select(f2, eh, dh)), lo = W::select(f1, sl, W::select(f2, el, dl));
-                    const V32 j = (W::select(f1, e1, W::select(f2, e2, e3)) - 1u) - iv;
-                    by = cbc_depth_digit<W>(hi, lo, j);
-                    by = W::select((iv == nl) | (iv == e1) | (iv == e2), W::splat(9u), by);
-                    by = W::select(iv == e3, W::splat(10u), by);
-                }
-                out = out | (by << (8u * t));
-            }
-            const Mask full = k & (W::splat(q + 4u) <= len);
-            W::store32_bytes(dst, at + q, out, full);
-            const Mask part = k & !full & (W::splat(q) < len);
-            if (W::ballot(part) != 0ull)
-                for (uint32_t t = 0; t < 3u; t++)
-                    W::store8(dst, at + (q + t), (out >> (8u * t)) & 0xffu, part & (W::splat(q + t) < len));
-        }
+        cbc_depth_ln<W> L;
+        L.nl = D.name_len;
+        L.e1 = cbc_sam_ndig_v<W>(st, 1000000000u) + (L.nl + 1u);
+        L.e2 = L.e1 + cbc_sam_ndig_v<W>(en, 1000000000u) + 1u;
+        L.e3 = len - 1u;
+        cbc_depth_split<W>(st, L.sh, L.sl); cbc_depth_split<W>(en, L.eh, L.el); cbc_depth_split<W>(dp, L.dh, L.dl);
+        cbc_lines_store<W>(D.R.text + o, incl - len, len, k, D.name, L.nl, L);
         o += chunk;
     }
 }
+
+template <class W>
+CBC_FN void cbc_depth_count(const cbc_depth_args &A, uint32_t tt) { cbc_runs_count<W>(A, A, tt); }
+template <class W>
+CBC_FN void cbc_depth_write(const cbc_depth_args &A, uint32_t tt) { cbc_runs_write<W>(A, A, tt); }
 
 #endif /* CBC_DEPTH_BODY_H */

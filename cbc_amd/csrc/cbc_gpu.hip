@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(64 * CBC_REGION_WAVES)
 cbc_region_write_kernel(cbc_region_args A)
 {
     if (blockIdx.x >= A.n_blocks) return;
-    cbc_region_write<WaveGPU>(A, blockIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), CBC_REGION_WAVES);
+    cbc_region_write<WaveGPU>(A, blockIdx.x, WaveGPU::uni(threadIdx.x >> 6), CBC_REGION_WAVES);
 }
 
 /* SAM output (cbc_gpu_decode_sam, cbc_sam_body.h): line lengths per block (one wavefront per block), then the lines
@@ -132,7 +132,7 @@ __global__ void __launch_bounds__(64 * CBC_SAM_WAVES)
 cbc_sam_write_kernel(cbc_sam_args A)
 {
     if (blockIdx.x >= A.R.n_blocks) return;
-    cbc_sam_write<WaveGPU>(A, blockIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), CBC_SAM_WAVES);
+    cbc_sam_write<WaveGPU>(A, blockIdx.x, WaveGPU::uni(threadIdx.x >> 6), CBC_SAM_WAVES);
 }
 
 /* Coverage (cbc_gpu_decode_depth, cbc_depth_body.h): one wavefront per block marks the reads in the difference array, one
@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(64 * CBC_REGION_WAVES)
 cbc_targets_write_kernel(cbc_targets_args A)
 {
     if (blockIdx.x >= A.S.R.n_blocks) return;
-    cbc_targets_write<WaveGPU>(A, blockIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), CBC_REGION_WAVES);
+    cbc_targets_write<WaveGPU>(A, blockIdx.x, WaveGPU::uni(threadIdx.x >> 6), CBC_REGION_WAVES);
 }
 __global__ void __launch_bounds__(64)
 cbc_targets_sam_count_kernel(cbc_targets_args A) { if (blockIdx.x < A.S.R.n_blocks) cbc_targets_sam_count<WaveGPU>(A, blockIdx.x); }
@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(64 * CBC_SAM_WAVES)
 cbc_targets_sam_write_kernel(cbc_targets_args A)
 {
     if (blockIdx.x >= A.S.R.n_blocks) return;
-    cbc_targets_sam_write<WaveGPU>(A, blockIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), CBC_SAM_WAVES);
+    cbc_targets_sam_write<WaveGPU>(A, blockIdx.x, WaveGPU::uni(threadIdx.x >> 6), CBC_SAM_WAVES);
 }
 __global__ void __launch_bounds__(64)
 cbc_targets_mark_kernel(cbc_tdepth_args A) { if (blockIdx.x < A.D.R.n_blocks) cbc_targets_mark<WaveGPU>(A, blockIdx.x); }

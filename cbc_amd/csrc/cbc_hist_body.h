@@ -43,20 +43,13 @@ struct cbc_hist_args {
     uint32_t cp_cap, n_tiles, n_ttiles, fold, n_bins, n_btiles, out_cap, grid;
 };
 
-/* change points of the call: what the compact pass counted, never more than the tables hold */
-CBC_FN uint32_t cbc_hist_points(const cbc_hist_args &A)
-{
-    const uint64_t n = A.cnt_off[A.n_tiles];
-    return n > A.cp_cap ? A.cp_cap : (uint32_t)n;
-}
-
 /* workgroup wg of A.grid: run tiles wg, wg + grid, ...; lds: CBC_HIST_LDS words of this workgroup (unused with CBC_HIST_NO_LDS) */
 template <class W>
 CBC_FN void cbc_hist_accum(const cbc_hist_args &A, uint32_t wg, uint32_t *lds)
 {
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
-    const uint32_t ncp = cbc_hist_points(A);
+    const uint32_t ncp = cbc_depth_points(A.cnt_off, A.n_tiles, A.cp_cap);
     const V32 ln = W::lane();
     if (A.grid == 0u || wg >= A.grid) return;
 #ifndef CBC_HIST_NO_LDS
@@ -67,10 +60,8 @@ CBC_FN void cbc_hist_accum(const cbc_hist_args &A, uint32_t wg, uint32_t *lds)
         for (uint32_t r = 0; r < CBC_DEPTH_LINES / 64u; r++) {
             const uint32_t j0 = tt * CBC_DEPTH_LINES + r * 64u;
             if (j0 >= ncp || ncp - j0 < 2u) break;                   /* no run from j0 on */
-            const V32 j = ln + j0;
-            const Mask m = (j + 1u) < ncp;                           /* ncp <= cp_cap < 2^32 - 64: no wrap */
-            const V32 p = W::load32(A.cp_pos, j, m, 0u), q = W::load32(A.cp_pos, j + 1u, m, 0u), d = W::load32(A.cp_dep, j, m, 0u);
-            const V32 len = q - p;
+            V32 d, len;
+            const Mask m = cbc_depth_run_load<W>(A.cp_pos, A.cp_dep, j0, ncp, d, len);
             const V32 bin = W::select(d < A.fold, d, W::splat(A.fold));
             const Mask k = m & (d != 0u) & (bin < A.n_bins);         /* a depth past the reads of the call: not from these passes */
 #ifndef CBC_HIST_NO_LDS
@@ -104,8 +95,7 @@ CBC_FN void cbc_hist_count(const cbc_hist_args &A, uint32_t t)
         W::load_rec(b4, ln + r * 64u, W::all(), a, b, cc, d);
         c = c + cbc_depth_nz<W>(a) + cbc_depth_nz<W>(b) + cbc_depth_nz<W>(cc) + cbc_depth_nz<W>(d);
     }
-    uint32_t *tc = (uint32_t *)(A.tile_nz + t);
-    W::write_uni(tc, 0u, W::reduce_add(c)); W::write_uni(tc, 1u, CBC_ST_OK); W::write_uni(tc, 2u, 0u); W::write_uni(tc, 3u, 0u);
+    cbc_store_result<W>(A.tile_nz + t, W::reduce_add(c), 0u);
 }
 
 template <class W>

@@ -25,8 +25,7 @@
  *            (cbc_depth_tile + cbc_scan_sizes_kernel), the line rule nonref = mismatches + del + ins >= min_alt, lines and bytes
  *            into a cbc_block_result for the size scan (64-bit text offsets).
  *   write    the same tile again, one lane per line:  <name> <pos1> <ref> <depth> <A> <C> <G> <T> <N> <del> <ins>  tab-separated,
- *            made four bytes at a time (cbc_depth_digit) and written as dwords at the line's own offset; a dword never leaves
- *            its line, the last 1..3 bytes are byte stores.
+ *            through the line-per-lane writer of cbc_depth_body.h (cbc_lines_store) with the line bytes of cbc_pileup_ln.
  * Range tests are written without base + length sums.  Written against the wave policy (W = WaveGPU in cbc_gpu.hip, the
  * lock-step emulation in tests/pileup_emu).
  */
@@ -233,11 +232,36 @@ CBC_FN void cbc_pileup_count(const cbc_pileup_args &A, uint32_t t)
         }
     }
     if (t >= A.D.n_tiles) return;
-    uint32_t *c = (uint32_t *)(A.D.R.counts + t);
-    W::write_uni(c, 0u, bytes); W::write_uni(c, 1u, CBC_ST_OK); W::write_uni(c, 2u, lines); W::write_uni(c, 3u, 0u);
+    cbc_store_result<W>(A.D.R.counts + t, bytes, lines);
     if (lines) W::list_add(A.D.ctr, W::splat(1u), W::splat(lines), W::lane() == 0u);
 }
 
+/* the line for cbc_lines_store (cbc_depth_body.h): name, '\t' at nl, pos1, '\t' at e[0], the reference byte, '\t' at e[0] + 2, then
+ * the eight counts, number s ending at e[s] with a '\t' there; e[8] = len - 1 holds the '\n'; hi / lo: the numbers split */
+template <class W>
+struct cbc_pileup_ln { typename W::V32 e[9], hi[9], lo[9], rb; uint32_t nl; };
+
+template <class W>
+CBC_FN typename W::V32 cbc_line_byte(const cbc_pileup_ln<W> &L, uint32_t i)
+{
+    typedef typename W::V32 V32;
+    typedef typename W::Mask Mask;
+    const V32 iv = W::splat(i);
+    V32 h = L.hi[8], l = L.lo[8], ee = L.e[8];
+    Mask tab = iv == L.nl;
+    for (int s = 7; s >= 0; s--) {                                   /* the first number that ends behind byte i */
+        const Mask lt = iv < L.e[s];
+        h = W::select(lt, L.hi[s], h); l = W::select(lt, L.lo[s], l); ee = W::select(lt, L.e[s], ee);
+        tab = tab | (iv == L.e[s]);
+    }
+    V32 by = cbc_depth_digit<W>(h, l, (ee - 1u) - iv);
+    by = W::select(tab | (iv == L.e[0] + 2u), W::splat(9u), by);
+    by = W::select(iv == L.e[0] + 1u, L.rb, by);
+    return W::select(iv == L.e[8], W::splat(10u), by);
+}
+
+/* count and write iterate positions, carry `run` and skip empty rounds: they share the writer with the run-text skeleton of
+ * cbc_depth_body.h, not its loops */
 template <class W>
 CBC_FN void cbc_pileup_write(const cbc_pileup_args &A, uint32_t t)
 {
@@ -256,45 +280,13 @@ CBC_FN void cbc_pileup_write(const cbc_pileup_args &A, uint32_t t)
         const V32 incl = W::scan_incl_add(len);
         const uint32_t chunk = W::readlane(incl, 63u);
         if (chunk > (o0 + bytes) - o) return;                        /* the counters moved under the count pass */
-        const V32 at = incl - len;
-        /* the line: name, '\t' at nl, pos1, '\t' at e[0], the reference byte, '\t' at e[0] + 2, then the eight counts, number s
-         * ending at e[s] with a '\t' there; e[8] = len - 1 holds the '\n' */
-        V32 e[9], hi[9], lo[9];
-        e[0] = cbc_sam_ndig_v<W>(v[0], 1000000000u) + (nl + 1u);
-        e[1] = e[0] + cbc_sam_ndig_v<W>(v[1], 1000000000u) + 3u;
-        for (uint32_t s = 2; s < 9u; s++) e[s] = e[s - 1u] + cbc_sam_ndig_v<W>(v[s], 1000000000u) + 1u;
-        for (uint32_t s = 0; s < 9u; s++) cbc_depth_split<W>(v[s], hi[s], lo[s]);
-        uint8_t *dst = A.D.R.text + o;
-        const uint32_t maxlen = W::readlane(W::scan_incl_max(len), 63u);
-        for (uint32_t q = 0; q < maxlen; q += 4u) {
-            V32 out = W::splat(0u);
-            for (uint32_t tt = 0; tt < 4u; tt++) {
-                const uint32_t i = q + tt;
-                V32 by;
-                if (i < nl) by = W::splat(W::read_uni8(A.D.name, i));
-                else {
-                    const V32 iv = W::splat(i);
-                    V32 h = hi[8], l = lo[8], ee = e[8];
-                    Mask tab = iv == nl;
-                    for (int s = 7; s >= 0; s--) {                   /* the first number that ends behind byte i */
-                        const Mask lt = iv < e[s];
-                        h = W::select(lt, hi[s], h); l = W::select(lt, lo[s], l); ee = W::select(lt, e[s], ee);
-                        tab = tab | (iv == e[s]);
-                    }
-                    by = cbc_depth_digit<W>(h, l, (ee - 1u) - iv);
-                    by = W::select(tab | (iv == e[0] + 2u), W::splat(9u), by);
-                    by = W::select(iv == e[0] + 1u, rb, by);
-                    by = W::select(iv == e[8], W::splat(10u), by);
-                }
-                out = out | (by << (8u * tt));
-            }
-            const Mask full = k & (W::splat(q + 4u) <= len);
-            W::store32_bytes(dst, at + q, out, full);
-            const Mask part = k & !full & (W::splat(q) < len);
-            if (W::ballot(part) != 0ull)
-                for (uint32_t tt = 0; tt < 3u; tt++)
-                    W::store8(dst, at + (q + tt), (out >> (8u * tt)) & 0xffu, part & (W::splat(q + tt) < len));
-        }
+        cbc_pileup_ln<W> L;
+        L.nl = nl; L.rb = rb;
+        L.e[0] = cbc_sam_ndig_v<W>(v[0], 1000000000u) + (nl + 1u);
+        L.e[1] = L.e[0] + cbc_sam_ndig_v<W>(v[1], 1000000000u) + 3u;
+        for (uint32_t s = 2; s < 9u; s++) L.e[s] = L.e[s - 1u] + cbc_sam_ndig_v<W>(v[s], 1000000000u) + 1u;
+        for (uint32_t s = 0; s < 9u; s++) cbc_depth_split<W>(v[s], L.hi[s], L.lo[s]);
+        cbc_lines_store<W>(A.D.R.text + o, incl - len, len, k, A.D.name, nl, L);
         o += chunk;
     }
 }

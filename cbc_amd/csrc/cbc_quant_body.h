@@ -50,12 +50,6 @@ struct cbc_quant_args {
     uint32_t n_quant, cp_cap, n_tiles, n_q, slots, reserved;
 };
 
-CBC_FN uint32_t cbc_quant_points(const cbc_quant_args &A)
-{
-    const uint64_t n = A.cnt_off[A.n_tiles];
-    return n > A.cp_cap ? A.cp_cap : (uint32_t)n;
-}
-
 /* the rank of percentage p among len >= 1 values: max(1, ceil(p len / 100)) without a 32-bit overflow (p <= 100) */
 CBC_FN uint32_t cbc_quant_rank(uint32_t p, uint32_t len)
 {
@@ -93,7 +87,7 @@ CBC_FN void cbc_quant_select(const cbc_quant_args &A, uint32_t i, uint32_t *lds)
 CBC_QUANT_UNROLL
     for (uint32_t t = 0; t < CBC_QUANT_MAX; t++) { res[t] = 0u; k[t] = 1u; }
     const bool ok = slot <= A.slots && len <= A.slots - slot && len != 0u;
-    const uint32_t ncp = cbc_quant_points(A);
+    const uint32_t ncp = cbc_depth_points(A.cnt_off, A.n_tiles, A.cp_cap);
     uint32_t j0 = 0u, j1 = 0u;
     const uint32_t end = slot + len;                                 /* <= A.slots under ok */
     if (ok && ncp >= 2u) {

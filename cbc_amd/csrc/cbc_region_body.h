@@ -11,6 +11,8 @@
  *   write  `n_waves` wavefronts per block share its kept reads; a read is written by the whole wavefront: the dwords of the
  *          OUTPUT that lie inside the read's text are one aligned 4-byte store per lane (source bytes funnel-shifted out of
  *          two row words), the at most 3 + 3 bytes it shares with its neighbours are byte stores.
+ * Both passes are the reads-text skeleton below (cbc_text_count / cbc_text_write), which cbc_sam_body.h and cbc_targets_body.h
+ * instantiate too; cbc_store_result, the one place a wavefront stores a cbc_block_result, lives here as well.
  * Overlap rule: POS <= end and POS + span - 1 >= beg with POS = window_start + local POS, evaluated in local coordinates
  * (32-bit lanes, no 64-bit sums): local POS <= end - window_start and local POS + span >= beg + 1 - window_start.
  * Written against the wave policy (W = WaveGPU in cbc_gpu.hip, the lock-step emulation in the tests).
@@ -79,25 +81,6 @@ CBC_FN typename W::Mask cbc_region_keep(const cbc_region_blk &B, uint32_t r0, ty
     return m & (lp <= B.hi) & ((lp >= B.lo) | (span >= B.lo - lp)) & (rlv <= B.stride);
 }
 
-template <class W>
-CBC_FN void cbc_region_count(const cbc_region_args &A, uint32_t blk)
-{
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const cbc_region_blk B = cbc_region_block(A, blk);
-    uint32_t kept = 0, bytes = 0;
-    if (B.ok) {
-        for (uint32_t r0 = 0; r0 < B.n; r0 += 64u) {
-            V32 rlv;
-            const Mask k = cbc_region_keep<W>(B, r0, rlv);
-            kept += W::reduce_add(W::select(k, W::splat(1u), W::splat(0u)));
-            bytes += W::reduce_add(W::select(k, rlv + 1u, W::splat(0u)));
-        }
-    }
-    uint32_t *c = (uint32_t *)(A.counts + blk);
-    W::write_uni(c, 0u, bytes); W::write_uni(c, 1u, CBC_ST_OK); W::write_uni(c, 2u, kept); W::write_uni(c, 3u, 0u);
-}
-
 /* one read's text (rl bases + '\n') at dst[0 ..]: the whole wavefront, lane-parallel */
 template <class W>
 CBC_FN void cbc_region_emit(uint8_t *dst, uint64_t o, const uint8_t *row, uint32_t rl)
@@ -125,35 +108,100 @@ CBC_FN void cbc_region_emit(uint8_t *dst, uint64_t o, const uint8_t *row, uint32
     W::store8(dst + o, idx, W::select(idx == rl, W::splat(10u), b), mb);
 }
 
-/* wavefront `wave` of `n_waves` writes every n_waves-th kept read of block blk */
+/* a cbc_block_result from a wavefront, as cbc_scan_sizes_kernel reads it */
 template <class W>
-CBC_FN void cbc_region_write(const cbc_region_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
+CBC_FN void cbc_store_result(cbc_block_result *r, uint32_t nbytes, uint32_t n_symbols)
 {
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const cbc_region_blk B = cbc_region_block(A, blk);
-    const uint32_t bytes = A.counts[blk].nbytes;
-    const uint64_t o0 = A.offsets[blk];
-    if (!B.ok || bytes == 0u || o0 > A.text_cap || bytes > A.text_cap - o0) return;
+    uint32_t *c = (uint32_t *)r;
+    W::write_uni(c, 0u, nbytes); W::write_uni(c, 1u, CBC_ST_OK); W::write_uni(c, 2u, n_symbols); W::write_uni(c, 3u, 0u);
+}
+
+/* ---- the reads-text skeleton ---------------------------------------------------------------------------------------------
+ * The count and the write pass of every output that is one line per kept read: region and SAM text, and the two of a target
+ * set (cbc_sam_body.h, cbc_targets_body.h).  A member is its argument struct A (R = the cbc_region_args inside: counts,
+ * offsets, text) and SAM, which picks the line.  It supplies, overloaded on A and found when the skeleton is instantiated:
+ *   cbc_text_block<SAM>(A, blk)       the block set-up X; X.B is its cbc_region_blk
+ *   cbc_text_keep<W>(A, X, r0, G)     keep flags of records [r0, r0 + 64); fills G.rlv, and G.lp, G.fl for a SAM line
+ * The line is overloaded on cbc_line<SAM>: the bases here, the SAM line in cbc_sam_body.h (its X is a cbc_sam_blk). */
+template <class W>
+struct cbc_text_grp { typename W::V32 rlv, lp, fl, tl, incl; };      /* 64 records: length, local POS, FLAG, line length, its scan */
+template <bool SAM>
+struct cbc_line {};
+
+template <class W, class X>
+CBC_FN typename W::V32 cbc_line_len(cbc_line<false>, const X &, const cbc_text_grp<W> &G) { return G.rlv + 1u; }
+
+/* the line of record r0 + j = lane j of the group whose text begins at o */
+template <class W, class X>
+CBC_FN void cbc_line_emit(cbc_line<false>, uint8_t *text, uint64_t o, const X &x, uint32_t r0, uint32_t j, const cbc_text_grp<W> &G)
+{
+    const uint32_t rl = W::readlane(G.rlv, j), at = W::readlane(G.incl, j) - (rl + 1u);
+    cbc_region_emit<W>(text, o + at, x.B.rows + (uint64_t)(r0 + j) * x.B.stride, rl);
+}
+
+struct cbc_region_tblk { cbc_region_blk B; };
+template <bool SAM>
+CBC_FN cbc_region_tblk cbc_text_block(const cbc_region_args &A, uint32_t blk) { return cbc_region_tblk{cbc_region_block(A, blk)}; }
+
+template <class W>
+CBC_FN typename W::Mask cbc_text_keep(const cbc_region_args &, const cbc_region_tblk &X, uint32_t r0, cbc_text_grp<W> &G)
+{
+    return cbc_region_keep<W>(X.B, r0, G.rlv);
+}
+
+/* one wavefront per block: its kept reads and text bytes into counts[blk] for the size scan */
+template <class W, bool SAM, class Args>
+CBC_FN void cbc_text_count(const Args &A, const cbc_region_args &R, uint32_t blk)
+{
+    const auto X = cbc_text_block<SAM>(A, blk);
+    uint32_t kept = 0, bytes = 0;
+    if (X.B.ok) {
+        for (uint32_t r0 = 0; r0 < X.B.n; r0 += 64u) {
+            cbc_text_grp<W> G;
+            const typename W::Mask k = cbc_text_keep<W>(A, X, r0, G);
+            kept += W::reduce_add(W::select(k, W::splat(1u), W::splat(0u)));
+            bytes += W::reduce_add(W::select(k, cbc_line_len<W>(cbc_line<SAM>(), X, G), W::splat(0u)));
+        }
+    }
+    cbc_store_result<W>(R.counts + blk, bytes, kept);
+}
+
+/* wavefront `wave` of `n_waves` writes every n_waves-th kept read of block blk.  The line length is asked for behind the keep
+ * flags (in the count pass: behind their reduction, so that the two DPP ladders do not interleave) and r0, j go to the line
+ * apart (the row address is formed behind the readlanes): profiles/text_bodies_isa.md */
+template <class W, bool SAM, class Args>
+CBC_FN void cbc_text_write(const Args &A, const cbc_region_args &R, uint32_t blk, uint32_t wave, uint32_t n_waves)
+{
+    const auto X = cbc_text_block<SAM>(A, blk);
+    const uint32_t bytes = R.counts[blk].nbytes;
+    const uint64_t o0 = R.offsets[blk];
+    if (!X.B.ok || bytes == 0u || o0 > R.text_cap || bytes > R.text_cap - o0) return;
     uint64_t o = o0;
     uint32_t q = 0;                                                    /* kept reads of the block so far */
-    for (uint32_t r0 = 0; r0 < B.n; r0 += 64u) {
-        V32 rlv;
-        const Mask k = cbc_region_keep<W>(B, r0, rlv);
-        const V32 tl = W::select(k, rlv + 1u, W::splat(0u));
-        const V32 incl = W::scan_incl_add(tl);
-        const uint32_t chunk = W::readlane(incl, 63u);
+    for (uint32_t r0 = 0; r0 < X.B.n; r0 += 64u) {
+        cbc_text_grp<W> G;
+        const typename W::Mask k = cbc_text_keep<W>(A, X, r0, G);
+        G.tl = W::select(k, cbc_line_len<W>(cbc_line<SAM>(), X, G), W::splat(0u));
+        G.incl = W::scan_incl_add(G.tl);
+        const uint32_t chunk = W::readlane(G.incl, 63u);
         if (chunk > (o0 + bytes) - o) return;                          /* the records changed under the count pass */
         uint64_t bits = W::ballot(k);
         while (bits) {
-            const uint32_t j = (uint32_t)__builtin_ctzll(bits);
+            const uint32_t j = W::ctz64(bits);
             bits &= bits - 1u;
             if ((q++ % n_waves) != wave) continue;
-            const uint32_t rl = W::readlane(rlv, j), at = W::readlane(incl, j) - (rl + 1u);
-            cbc_region_emit<W>(A.text, o + at, B.rows + (uint64_t)(r0 + j) * B.stride, rl);
+            cbc_line_emit<W>(cbc_line<SAM>(), R.text, o, X, r0, j, G);
         }
         o += chunk;
     }
+}
+
+template <class W>
+CBC_FN void cbc_region_count(const cbc_region_args &A, uint32_t blk) { cbc_text_count<W, false>(A, A, blk); }
+template <class W>
+CBC_FN void cbc_region_write(const cbc_region_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
+{
+    cbc_text_write<W, false>(A, A, blk, wave, n_waves);
 }
 
 #endif /* CBC_REGION_BODY_H */

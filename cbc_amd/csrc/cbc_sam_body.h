@@ -3,7 +3,8 @@
  * DESIGN.md section 4.12).
  *
  * The decode kernel has left every record of the blocks in the context's arenas (plain decoder for a full decode, the
- * span-reporting one for a region).  Two passes, the shape of cbc_region_body.h, turn them into one line per read:
+ * span-reporting one for a region).  Two passes, the reads-text skeleton of cbc_region_body.h with the keep rule, the line length
+ * and the line of this file, turn them into one line per read:
  *     *\t<FLAG>\t<RNAME>\t<POS>\t255\t*\t*\t0\t0\t<SEQ>\t*\n          20 + digits(FLAG) + len(RNAME) + digits(POS) + rlen bytes
  *   count  one wavefront per block, one lane per record: keep flag (every record; with a region the rule of
  *          cbc_region_keep), line length (digit counts by compares), kept reads and text bytes by wave reductions into a
@@ -102,25 +103,6 @@ CBC_FN typename W::V32 cbc_sam_line_len(const cbc_sam_blk &S, const typename W::
                                         const typename W::V32 &fl)
 {
     return rlv + (20u + S.nl) + cbc_sam_ndig_v<W>(fl, 10000u) + cbc_sam_ndig_v<W>(lp + S.ws, 1000000000u);
-}
-
-template <class W>
-CBC_FN void cbc_sam_count(const cbc_sam_args &A, uint32_t blk)
-{
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const cbc_sam_blk S = cbc_sam_block(A, blk);
-    uint32_t kept = 0, bytes = 0;
-    if (S.B.ok) {
-        for (uint32_t r0 = 0; r0 < S.B.n; r0 += 64u) {
-            V32 rlv, lp, fl;
-            const Mask k = cbc_sam_keep<W>(A, S, r0, rlv, lp, fl);
-            kept += W::reduce_add(W::select(k, W::splat(1u), W::splat(0u)));
-            bytes += W::reduce_add(W::select(k, cbc_sam_line_len<W>(S, rlv, lp, fl), W::splat(0u)));
-        }
-    }
-    uint32_t *c = (uint32_t *)(A.R.counts + blk);
-    W::write_uni(c, 0u, bytes); W::write_uni(c, 1u, CBC_ST_OK); W::write_uni(c, 2u, kept); W::write_uni(c, 3u, 0u);
 }
 
 /* The table of the bytes around NAME and SEQ, one entry per lane:
@@ -230,37 +212,37 @@ CBC_FN void cbc_sam_emit(uint8_t *text, uint64_t o, const uint8_t *row, uint32_t
     }
 }
 
-/* wavefront `wave` of `n_waves` writes every n_waves-th kept read of block blk */
+/* ---- the SAM line and the SAM member of the reads-text skeleton (cbc_region_body.h) ------------------------------------- */
+template <class W>
+CBC_FN typename W::V32 cbc_line_len(cbc_line<true>, const cbc_sam_blk &S, const cbc_text_grp<W> &G)
+{
+    return cbc_sam_line_len<W>(S, G.rlv, G.lp, G.fl);
+}
+
+/* the constant table is the same for every line: the compiler makes it once, in front of the loops */
+template <class W>
+CBC_FN void cbc_line_emit(cbc_line<true>, uint8_t *text, uint64_t o, const cbc_sam_blk &S, uint32_t r0, uint32_t j, const cbc_text_grp<W> &G)
+{
+    const uint32_t len = W::readlane(G.tl, j), at = W::readlane(G.incl, j) - len;
+    cbc_sam_emit<W>(text, o + at, S.B.rows + (uint64_t)(r0 + j) * S.B.stride, W::readlane(G.rlv, j), S.ws + W::readlane(G.lp, j),
+                    W::readlane(G.fl, j), S.name, S.nl, len, cbc_sam_const_tab<W>());
+}
+
+template <bool SAM>
+CBC_FN cbc_sam_blk cbc_text_block(const cbc_sam_args &A, uint32_t blk) { return cbc_sam_block(A, blk); }
+
+template <class W>
+CBC_FN typename W::Mask cbc_text_keep(const cbc_sam_args &A, const cbc_sam_blk &S, uint32_t r0, cbc_text_grp<W> &G)
+{
+    return cbc_sam_keep<W>(A, S, r0, G.rlv, G.lp, G.fl);
+}
+
+template <class W>
+CBC_FN void cbc_sam_count(const cbc_sam_args &A, uint32_t blk) { cbc_text_count<W, true>(A, A.R, blk); }
 template <class W>
 CBC_FN void cbc_sam_write(const cbc_sam_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
 {
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const cbc_sam_blk S = cbc_sam_block(A, blk);
-    const uint32_t bytes = A.R.counts[blk].nbytes;
-    const uint64_t o0 = A.R.offsets[blk];
-    if (!S.B.ok || bytes == 0u || o0 > A.R.text_cap || bytes > A.R.text_cap - o0) return;
-    const V32 tabc = cbc_sam_const_tab<W>();
-    uint64_t o = o0;
-    uint32_t q = 0;                                                    /* kept reads of the block so far */
-    for (uint32_t r0 = 0; r0 < S.B.n; r0 += 64u) {
-        V32 rlv, lp, fl;
-        const Mask k = cbc_sam_keep<W>(A, S, r0, rlv, lp, fl);
-        const V32 tl = W::select(k, cbc_sam_line_len<W>(S, rlv, lp, fl), W::splat(0u));
-        const V32 incl = W::scan_incl_add(tl);
-        const uint32_t chunk = W::readlane(incl, 63u);
-        if (chunk > (o0 + bytes) - o) return;                          /* the records changed under the count pass */
-        uint64_t bits = W::ballot(k);
-        while (bits) {
-            const uint32_t j = W::ctz64(bits);
-            bits &= bits - 1u;
-            if ((q++ % n_waves) != wave) continue;
-            const uint32_t len = W::readlane(tl, j), at = W::readlane(incl, j) - len;
-            cbc_sam_emit<W>(A.R.text, o + at, S.B.rows + (uint64_t)(r0 + j) * S.B.stride, W::readlane(rlv, j),
-                            S.ws + W::readlane(lp, j), W::readlane(fl, j), S.name, S.nl, len, tabc);
-        }
-        o += chunk;
-    }
+    cbc_text_write<W, true>(A, A.R, blk, wave, n_waves);
 }
 
 #endif /* CBC_SAM_BODY_H */

@@ -9,18 +9,18 @@
  * trip count).  The comparisons carry no sum that can wrap: POS = window start + local POS is formed only for records with
  * local POS <= 2^31 - 1 - window start, and beg <= POS + span - 1 is taken as beg < POS or span > beg - POS.
  *
- *   reads, SAM   count and write passes in the shape of cbc_region_body.h / cbc_sam_body.h with the keep rule above; the
- *                bytes come from cbc_region_emit and cbc_sam_emit, which are called.
+ *   reads, SAM   two members of the reads-text skeleton of cbc_region_body.h: the keep rule above, the lines of the region and of
+ *                the SAM member.
  *   depth        one contig per call.  The difference array lives in a COMPRESSED coordinate: the contig's intervals laid
  *                end to end with one spare slot behind each (sum of len + 1 words), `iv_off` the exclusive prefix of the
  *                slots.  mark: a lane walks the intervals its read overlaps (from the search result while beg <= the read's
  *                last base), clips the read to each and adds +1 at the piece's first slot, -1 at the slot behind its last
  *                one.  The spare slot therefore always has depth 0: no run crosses a gap, and intervals that were merged
  *                are one interval, so no run is cut inside them.  The tile, scan and compact passes of cbc_depth_body.h run
- *                on that array unchanged.  count / write: a change point is mapped back to its reference position by a
- *                binary search in iv_off; a run of non-zero depth lies inside one interval (or ends on its spare slot =
- *                the interval's end), so its end is start + the distance of the two change points.  Digit counts and
- *                digits are cbc_sam_ndig_v and cbc_depth_digit.
+ *                on that array unchanged.  count / write: the run-text skeleton of cbc_depth_body.h with the line function of
+ *                this file: a change point is mapped back to its reference position by a binary search in iv_off; a run of
+ *                non-zero depth lies inside one interval (or ends on its spare slot = the interval's end), so its end is
+ *                start + the distance of the two change points.
  * Written against the wave policy (W = WaveGPU in cbc_gpu.hip, the lock-step emulation in tests/targets_emu).
  */
 #ifndef CBC_TARGETS_BODY_H
@@ -108,110 +108,39 @@ CBC_FN typename W::Mask cbc_targets_keep(const cbc_targets_blk &T, uint32_t r0, 
     return ex & ((bj < pos) | (span > bj - pos));                    /* beg <= POS + span - 1 */
 }
 
-/* ---- reads ------------------------------------------------------------------------------------------------------------ */
-template <class W>
-CBC_FN void cbc_targets_count(const cbc_targets_args &A, uint32_t blk)
+/* ---- reads, SAM: the two target-set members of the reads-text skeleton (cbc_region_body.h) ------------------------------- */
+struct cbc_targets_tblk : cbc_sam_blk { cbc_targets_blk T; };        /* B = T.B; name, ws, nl are set up for a SAM line alone */
+
+template <bool SAM>
+CBC_FN cbc_targets_tblk cbc_text_block(const cbc_targets_args &A, uint32_t blk)
 {
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const cbc_targets_blk T = cbc_targets_block(cbc_region_block(A.S.R, blk), A.S.R.window_start[blk], A.iv, A.block_iv, A.n_iv, blk);
-    uint32_t kept = 0, bytes = 0;
-    if (T.B.ok) {
-        for (uint32_t r0 = 0; r0 < T.B.n; r0 += 64u) {
-            V32 rlv, lp, fl, span, j;
-            const Mask k = cbc_targets_keep<W>(T, r0, rlv, lp, fl, span, j);
-            kept += W::reduce_add(W::select(k, W::splat(1u), W::splat(0u)));
-            bytes += W::reduce_add(W::select(k, rlv + 1u, W::splat(0u)));
-        }
-    }
-    uint32_t *c = (uint32_t *)(A.S.R.counts + blk);
-    W::write_uni(c, 0u, bytes); W::write_uni(c, 1u, CBC_ST_OK); W::write_uni(c, 2u, kept); W::write_uni(c, 3u, 0u);
+    cbc_targets_tblk X = {};
+    if (SAM) static_cast<cbc_sam_blk &>(X) = cbc_sam_block(A.S, blk); else X.B = cbc_region_block(A.S.R, blk);
+    X.T = cbc_targets_block(X.B, A.S.R.window_start[blk], A.iv, A.block_iv, A.n_iv, blk);
+    X.B = X.T.B;
+    return X;
 }
 
-/* wavefront `wave` of `n_waves` writes every n_waves-th kept read of block blk (cbc_region_emit) */
+template <class W>
+CBC_FN typename W::Mask cbc_text_keep(const cbc_targets_args &, const cbc_targets_tblk &X, uint32_t r0, cbc_text_grp<W> &G)
+{
+    typename W::V32 span, j;
+    return cbc_targets_keep<W>(X.T, r0, G.rlv, G.lp, G.fl, span, j);
+}
+
+template <class W>
+CBC_FN void cbc_targets_count(const cbc_targets_args &A, uint32_t blk) { cbc_text_count<W, false>(A, A.S.R, blk); }
 template <class W>
 CBC_FN void cbc_targets_write(const cbc_targets_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
 {
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const cbc_targets_blk T = cbc_targets_block(cbc_region_block(A.S.R, blk), A.S.R.window_start[blk], A.iv, A.block_iv, A.n_iv, blk);
-    const uint32_t bytes = A.S.R.counts[blk].nbytes;
-    const uint64_t o0 = A.S.R.offsets[blk];
-    if (!T.B.ok || bytes == 0u || o0 > A.S.R.text_cap || bytes > A.S.R.text_cap - o0) return;
-    uint64_t o = o0;
-    uint32_t q = 0;                                                    /* kept reads of the block so far */
-    for (uint32_t r0 = 0; r0 < T.B.n; r0 += 64u) {
-        V32 rlv, lp, fl, span, j;
-        const Mask k = cbc_targets_keep<W>(T, r0, rlv, lp, fl, span, j);
-        const V32 tl = W::select(k, rlv + 1u, W::splat(0u));
-        const V32 incl = W::scan_incl_add(tl);
-        const uint32_t chunk = W::readlane(incl, 63u);
-        if (chunk > (o0 + bytes) - o) return;                          /* the records changed under the count pass */
-        uint64_t bits = W::ballot(k);
-        while (bits) {
-            const uint32_t i = W::ctz64(bits);
-            bits &= bits - 1u;
-            if ((q++ % n_waves) != wave) continue;
-            const uint32_t rl = W::readlane(rlv, i), at = W::readlane(incl, i) - (rl + 1u);
-            cbc_region_emit<W>(A.S.R.text, o + at, T.B.rows + (uint64_t)(r0 + i) * T.B.stride, rl);
-        }
-        o += chunk;
-    }
+    cbc_text_write<W, false>(A, A.S.R, blk, wave, n_waves);
 }
-
-/* ---- SAM --------------------------------------------------------------------------------------------------------------- */
 template <class W>
-CBC_FN void cbc_targets_sam_count(const cbc_targets_args &A, uint32_t blk)
-{
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const cbc_sam_blk S = cbc_sam_block(A.S, blk);
-    const cbc_targets_blk T = cbc_targets_block(S.B, A.S.R.window_start[blk], A.iv, A.block_iv, A.n_iv, blk);
-    uint32_t kept = 0, bytes = 0;
-    if (T.B.ok) {
-        for (uint32_t r0 = 0; r0 < T.B.n; r0 += 64u) {
-            V32 rlv, lp, fl, span, j;
-            const Mask k = cbc_targets_keep<W>(T, r0, rlv, lp, fl, span, j);
-            kept += W::reduce_add(W::select(k, W::splat(1u), W::splat(0u)));
-            bytes += W::reduce_add(W::select(k, cbc_sam_line_len<W>(S, rlv, lp, fl), W::splat(0u)));
-        }
-    }
-    uint32_t *c = (uint32_t *)(A.S.R.counts + blk);
-    W::write_uni(c, 0u, bytes); W::write_uni(c, 1u, CBC_ST_OK); W::write_uni(c, 2u, kept); W::write_uni(c, 3u, 0u);
-}
-
-/* wavefront `wave` of `n_waves` writes every n_waves-th kept read of block blk (cbc_sam_emit) */
+CBC_FN void cbc_targets_sam_count(const cbc_targets_args &A, uint32_t blk) { cbc_text_count<W, true>(A, A.S.R, blk); }
 template <class W>
 CBC_FN void cbc_targets_sam_write(const cbc_targets_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
 {
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const cbc_sam_blk S = cbc_sam_block(A.S, blk);
-    const cbc_targets_blk T = cbc_targets_block(S.B, A.S.R.window_start[blk], A.iv, A.block_iv, A.n_iv, blk);
-    const uint32_t bytes = A.S.R.counts[blk].nbytes;
-    const uint64_t o0 = A.S.R.offsets[blk];
-    if (!T.B.ok || bytes == 0u || o0 > A.S.R.text_cap || bytes > A.S.R.text_cap - o0) return;
-    const V32 tabc = cbc_sam_const_tab<W>();
-    uint64_t o = o0;
-    uint32_t q = 0;                                                    /* kept reads of the block so far */
-    for (uint32_t r0 = 0; r0 < T.B.n; r0 += 64u) {
-        V32 rlv, lp, fl, span, j;
-        const Mask k = cbc_targets_keep<W>(T, r0, rlv, lp, fl, span, j);
-        const V32 tl = W::select(k, cbc_sam_line_len<W>(S, rlv, lp, fl), W::splat(0u));
-        const V32 incl = W::scan_incl_add(tl);
-        const uint32_t chunk = W::readlane(incl, 63u);
-        if (chunk > (o0 + bytes) - o) return;                          /* the records changed under the count pass */
-        uint64_t bits = W::ballot(k);
-        while (bits) {
-            const uint32_t i = W::ctz64(bits);
-            bits &= bits - 1u;
-            if ((q++ % n_waves) != wave) continue;
-            const uint32_t len = W::readlane(tl, i), at = W::readlane(incl, i) - len;
-            cbc_sam_emit<W>(A.S.R.text, o + at, T.B.rows + (uint64_t)(r0 + i) * T.B.stride, W::readlane(rlv, i),
-                            S.ws + W::readlane(lp, i), W::readlane(fl, i), S.name, S.nl, len, tabc);
-        }
-        o += chunk;
-    }
+    cbc_text_write<W, true>(A, A.S.R, blk, wave, n_waves);
 }
 
 /* ---- depth: mark ------------------------------------------------------------------------------------------------------- */
@@ -255,10 +184,13 @@ CBC_FN void cbc_targets_mark(const cbc_tdepth_args &A, uint32_t blk, uint32_t *s
 }
 
 /* ---- depth: text ------------------------------------------------------------------------------------------------------- */
-/* runs [j0, j0 + 64) of the contig's `nr` runs: start0, end0, depth and the line's length (0: no line) */
+/* the target-set member of the run-text skeleton (cbc_depth_body.h): runs [j0, j0 + 64) of the contig's `nr` runs: start0, end0,
+ * depth and the line's length (0: no line); no guard of its own */
+CBC_FN bool cbc_depth_line_ok(const cbc_tdepth_args &) { return true; }
+
 template <class W>
-CBC_FN typename W::Mask cbc_targets_line(const cbc_tdepth_args &A, uint32_t j0, uint32_t nr, typename W::V32 &st,
-                                         typename W::V32 &en, typename W::V32 &dp, typename W::V32 &len)
+CBC_FN typename W::Mask cbc_depth_line(const cbc_tdepth_args &A, uint32_t j0, uint32_t nr, typename W::V32 &st,
+                                       typename W::V32 &en, typename W::V32 &dp, typename W::V32 &len)
 {
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
@@ -280,82 +212,8 @@ CBC_FN typename W::Mask cbc_targets_line(const cbc_tdepth_args &A, uint32_t j0, 
 }
 
 template <class W>
-CBC_FN void cbc_targets_depth_count(const cbc_tdepth_args &A, uint32_t tt)
-{
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    const uint32_t nr = cbc_depth_runs(A.D);
-    uint32_t lines = 0, bytes = 0;
-    if (A.D.name_len <= CBC_SAM_MAX_NAME && tt < A.D.n_ttiles)
-        for (uint32_t r = 0; r < CBC_DEPTH_LINES / 64u; r++) {
-            const uint32_t j0 = tt * CBC_DEPTH_LINES + r * 64u;
-            if (j0 >= nr) break;
-            V32 st, en, dp, len;
-            const Mask k = cbc_targets_line<W>(A, j0, nr, st, en, dp, len);
-            lines += W::popc64(W::ballot(k));
-            bytes += W::reduce_add(len);
-        }
-    uint32_t *c = (uint32_t *)(A.D.R.counts + tt);
-    W::write_uni(c, 0u, bytes); W::write_uni(c, 1u, CBC_ST_OK); W::write_uni(c, 2u, lines); W::write_uni(c, 3u, 0u);
-    if (lines) W::list_add(A.D.ctr, W::splat(1u), W::splat(lines), W::lane() == 0u);
-}
-
-/* the lines of text tile tt, one lane per line, four bytes at a time: the scheme of cbc_depth_write */
+CBC_FN void cbc_targets_depth_count(const cbc_tdepth_args &A, uint32_t tt) { cbc_runs_count<W>(A, A.D, tt); }
 template <class W>
-CBC_FN void cbc_targets_depth_write(const cbc_tdepth_args &A, uint32_t tt)
-{
-    typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
-    if (tt >= A.D.n_ttiles || A.D.name_len > CBC_SAM_MAX_NAME) return;
-    const uint32_t nr = cbc_depth_runs(A.D);
-    const uint32_t bytes = A.D.R.counts[tt].nbytes, nl = A.D.name_len;
-    const uint64_t o0 = A.D.R.offsets[tt];
-    if (bytes == 0u || o0 > A.D.R.text_cap || bytes > A.D.R.text_cap - o0) return;
-    uint64_t o = o0;
-    for (uint32_t r = 0; r < CBC_DEPTH_LINES / 64u; r++) {
-        const uint32_t j0 = tt * CBC_DEPTH_LINES + r * 64u;
-        if (j0 >= nr) break;
-        V32 st, en, dp, len;
-        const Mask k = cbc_targets_line<W>(A, j0, nr, st, en, dp, len);
-        const V32 incl = W::scan_incl_add(len);
-        const uint32_t chunk = W::readlane(incl, 63u);
-        if (chunk > (o0 + bytes) - o) return;                        /* the change points moved under the count pass */
-        if (chunk == 0u) continue;
-        const V32 at = incl - len;
-        /* the line: name, '\t' at nl, start0, '\t' at e1, end0, '\t' at e2, depth, '\n' at e3 = len - 1 */
-        const V32 e1 = cbc_sam_ndig_v<W>(st, 1000000000u) + (nl + 1u);
-        const V32 e2 = e1 + cbc_sam_ndig_v<W>(en, 1000000000u) + 1u;
-        const V32 e3 = len - 1u;
-        V32 sh, sl, eh, el, dh, dl;
-        cbc_depth_split<W>(st, sh, sl); cbc_depth_split<W>(en, eh, el); cbc_depth_split<W>(dp, dh, dl);
-        uint8_t *dst = A.D.R.text + o;
-        const uint32_t maxlen = W::readlane(W::scan_incl_max(len), 63u);
-        for (uint32_t q = 0; q < maxlen; q += 4u) {
-            V32 out = W::splat(0u);
-            for (uint32_t t = 0; t < 4u; t++) {
-                const uint32_t i = q + t;
-                V32 by;
-                if (i < nl) by = W::splat(W::read_uni8(A.D.name, i));
-                else {
-                    const V32 iv = W::splat(i);
-                    const Mask f1 = iv < e1, f2 = iv < e2;
-                    const V32 hi = W::select(f1, sh, W::select(f2, eh, dh)), lo = W::select(f1, sl, W::select(f2, el, dl));
-                    const V32 d = (W::select(f1, e1, W::select(f2, e2, e3)) - 1u) - iv;
-                    by = cbc_depth_digit<W>(hi, lo, d);
-                    by = W::select((iv == nl) | (iv == e1) | (iv == e2), W::splat(9u), by);
-                    by = W::select(iv == e3, W::splat(10u), by);
-                }
-                out = out | (by << (8u * t));
-            }
-            const Mask full = k & (W::splat(q + 4u) <= len);
-            W::store32_bytes(dst, at + q, out, full);
-            const Mask part = k & !full & (W::splat(q) < len);
-            if (W::ballot(part) != 0ull)
-                for (uint32_t t = 0; t < 3u; t++)
-                    W::store8(dst, at + (q + t), (out >> (8u * t)) & 0xffu, part & (W::splat(q + t) < len));
-        }
-        o += chunk;
-    }
-}
+CBC_FN void cbc_targets_depth_write(const cbc_tdepth_args &A, uint32_t tt) { cbc_runs_write<W>(A, A.D, tt); }
 
 #endif /* CBC_TARGETS_BODY_H */

@@ -188,7 +188,7 @@ def emu_decode(L, plan, b0, b1, smax):
     return bl, recs, seq, res, nrec
 
 
-def emu_call(L, plan, sel, exclude=0, cap=None, fail_blocks=(), dec=None):
+def emu_call(L, plan, sel, exclude=0, cap=None, fail_blocks=(), dec=None, name=None):
     """One cbc_gpu_decode_depth on the emulation: span decode of the selection, then every pass.  Returns (rc, text, lines,
     reads kept, text bytes); the guard bytes behind the text (all of it when rc != 0) must be untouched.  fail_blocks: blocks
     of the selection whose decode status is set to a failure before the passes run."""
@@ -200,7 +200,7 @@ def emu_call(L, plan, sel, exclude=0, cap=None, fail_blocks=(), dec=None):
         res[b]["status"] = 2
     ws = np.ascontiguousarray(plan.window_start[sel.b0:sel.b1], dtype=np.uint64)
     off = int(plan.contig_name_off[sel.contig])
-    name = plan.names[off:].tobytes().split(b"\0", 1)[0]
+    name = plan.names[off:].tobytes().split(b"\0", 1)[0] if name is None else name
     cap = plan.depth_text_cap(sel.b0, sel.b1, sel.contig) if cap is None else cap
     text = np.full(cap + 16, 0xEE, dtype=np.uint8)
     out = np.zeros(4, dtype=np.uint64)

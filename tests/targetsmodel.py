@@ -183,7 +183,7 @@ def emu_text(L, plan, dec, ts, sam, n_waves=4, cap=None, fail_blocks=()):
     return rc, (text[:total].tobytes() if rc == 0 else b""), int(out[1]), total
 
 
-def emu_depth(L, plan, dec, ts, exclude=0, fail_blocks=()):
+def emu_depth(L, plan, dec, ts, exclude=0, fail_blocks=(), name=None):
     """The depth calls of cbc_gpu_decode_targets on the emulation, one per contig with intervals and blocks, texts appended.
     Returns (text, lines, reads counted, words of the difference arrays)."""
     text, lines, kept, words = [], 0, 0, 0
@@ -202,12 +202,12 @@ def emu_depth(L, plan, dec, ts, exclude=0, fail_blocks=()):
         iv = np.ascontiguousarray(ts.iv[f:f + n], dtype=np.uint32)
         biv = np.ascontiguousarray(ts.block_iv[k0:k0 + nb], dtype=np.uint32).copy()
         biv[:, 0] -= np.uint32(f)
-        name = _name(plan, c)[1]
+        nm = _name(plan, c)[1] if name is None else name
         cap = ts.depth_cap[c]
         buf = np.full(cap + 16, 0xEE, dtype=np.uint8)
         out = np.zeros(5, dtype=np.uint64)
         rc = L.emu_targets_depth(dec["recs"].ctypes.data, dec["nrec"], dec["seq"].ctypes.data, dec["seq"].size, bl.ctypes.data,
-                                 ws.ctypes.data, res.ctypes.data, nb, name, len(name), iv.ctypes.data, n, biv.ctypes.data, exclude,
+                                 ws.ctypes.data, res.ctypes.data, nb, nm, len(nm), iv.ctypes.data, n, biv.ctypes.data, exclude,
                                  buf.ctypes.data, cap, out.ctypes.data)
         assert rc == 0, rc
         assert (buf[int(out[0]):] == 0xEE).all(), "bytes written outside the text"

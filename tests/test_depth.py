@@ -151,6 +151,20 @@ def test_failed_block_marks_nothing(emu, data):
     assert kept == sum(1 for x in iv if x[0] == 0 and x[4] != 1)
 
 
+def test_name_longer_than_the_limit_writes_nothing(emu, data):
+    """The name_len guard of the run-text skeleton through the window member: no line is counted, nothing is written (the
+    helper checks every byte of the buffer), while the mark pass still counts the reads."""
+    plan = data["plan"]
+    sel = plan.contig_blocks(0)
+    rc, text, lines, kept, total = dm.emu_call(emu, plan, sel, name=b"n" * 256)               # CBC_SAM_MAX_NAME + 1
+    assert (rc, text, lines, total) == (0, b"", 0, 0) and kept > 0
+    cap = plan.depth_text_cap(sel.b0, sel.b1, 0) // 34 * (255 + 34)                             # the cap counts the real name
+    rc, text, lines, kept2, total = dm.emu_call(emu, plan, sel, name=b"n" * 255, cap=cap)
+    assert rc == 0 and lines > 0 and kept2 == kept and text.startswith(b"n" * 255 + b"\t") and total == len(text)
+    # zero bytes: no block marks anything, so there is no run; every text tile counts 0 bytes and its write pass ends there
+    assert dm.emu_call(emu, plan, sel, fail_blocks=range(sel.b1 - sel.b0)) == (0, b"", 0, 0, 0)
+
+
 def test_text_cap(emu, data, ramp):
     for d in (data, ramp):
         plan, iv = d["plan"], d["iv"]

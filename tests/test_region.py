@@ -208,6 +208,46 @@ def test_emulated_region_text_matches_the_model(data, n_waves):
         assert _emu_region_text(plan, sel, n_waves) == rm.expected_text(recs, c, beg, end), s
 
 
+def test_emulated_region_write_guards(data):
+    """The guards of the write pass through the region member of the reads-text skeleton: a failed block, a block that keeps
+    nothing and a block whose text would end past text_cap write nothing; the other blocks' bytes stay where the scan put them."""
+    plan, recs = data["plan"], data["recs"]
+    sel = plan.region("chr1")
+    nb = sel.b1 - sel.b0
+    assert nb >= 3
+    bl, rr, seq, res, nrec = _emu_span_decode(plan, sel.b0, sel.b1, sel.smax)
+    assert (res["status"] == 0).all()
+    ws = np.ascontiguousarray(plan.window_start[sel.b0:sel.b1], dtype=np.uint64)
+    full = nrec * (plan.seq_stride + 1)
+
+    def passes(res, beg, end, cap):
+        text = np.full(full + 16, 0xEE, dtype=np.uint8)
+        counts = np.zeros(nb, dtype=host.RESULT_DTYPE)
+        offs = np.zeros(nb + 1, dtype=np.uint64)
+        assert _emu_lib().emu_region(rr.ctypes.data, nrec, seq.ctypes.data, seq.size, bl.ctypes.data, ws.ctypes.data,
+                                     res.ctypes.data, nb, beg, end, text.ctypes.data, cap, counts.ctypes.data, offs.ctypes.data, 4) == 0
+        return text, counts, offs
+
+    whole = rm.expected_text(recs, 0, sel.beg, sel.end)
+    text, counts, offs = passes(res, sel.beg, sel.end, full)
+    assert text[:int(offs[nb])].tobytes() == whole and (counts["nbytes"] > 0).all()
+    # block not ok: its count is 0 and the text is that of the other blocks
+    bad = res.copy()
+    bad[1]["status"] = 8
+    text, counts, offs = passes(bad, sel.beg, sel.end, full)
+    without = [r for r in recs if r[0] != sel.b0 + 1]
+    assert int(counts[1]["nbytes"]) == 0 and text[:int(offs[nb])].tobytes() == rm.expected_text(without, 0, sel.beg, sel.end)
+    assert (text[int(offs[nb]):] == 0xEE).all()
+    # zero bytes: every block decoded and in reach of the window, no read overlaps the contig's tail
+    tail = int(data["pb"].contigs[0]["length"]) - 1000
+    text, counts, offs = passes(res, tail, tail, full)
+    assert int(offs[nb]) == 0 and (counts["status"] == 0).all() and (text == 0xEE).all()
+    # the text one byte short: the last block would end past text_cap and is not written, the others are
+    text, counts, offs = passes(res, sel.beg, sel.end, len(whole) - 1)
+    cut = int(offs[nb - 1])
+    assert int(offs[nb]) == len(whole) and text[:cut].tobytes() == whole[:cut] and (text[cut:] == 0xEE).all()
+
+
 # ---- refusals and hostile containers -------------------------------------------------------------------------------------
 def test_long_read_container_is_refused(built):
     pb, sam, fa = host.synth_long(5, 200_000, 40, read_len=2000, want_text=True)

@@ -205,6 +205,27 @@ def test_empty_selection_and_failed_block(emu, data, dec):
     assert (text, lines) == tm.expected_depth(d["iv"], NAMES, d["lens"], merged, 0, (blk,))
 
 
+def test_sam_failed_block_and_name_longer_than_the_limit(emu, data, dec):
+    """Through the target-set members of the shared passes: a failed block contributes no SAM line; with a name of
+    CBC_SAM_MAX_NAME + 1 bytes the run text counts no line and writes nothing (the helper checks every byte of the buffers)."""
+    d, plan = data, data["plan"]
+    ivs = _sets(d)["random200"]
+    merged = tm.merge(ivs)
+    ts = plan.targets(tm.region_strings(ivs, NAMES))
+    blk = int(ts.blocks[1])
+    rc, text, _, _ = tm.emu_text(emu, plan, dec, ts, 1, fail_blocks=(1,))
+    recs_wo = [r for r in d["recs"] if r[0] != blk]
+    flags_wo = [f for r, f in zip(d["recs"], d["flags"]) if r[0] != blk]
+    assert rc == 0 and text == tm.expected_sam(recs_wo, flags_wo, NAMES, merged)
+    assert text != tm.expected_sam(d["recs"], d["flags"], NAMES, merged)
+    text, lines, kept, _ = tm.emu_depth(emu, plan, dec, ts, name=b"n" * 256)
+    assert (text, lines) == (b"", 0) and kept > 0
+    text, lines, kept2, _ = tm.emu_depth(emu, plan, dec, ts)
+    assert lines > 0 and kept2 == kept and text
+    # zero bytes: no block marks anything, so there is no run; every text tile counts 0 bytes and its write pass ends there
+    assert tm.emu_depth(emu, plan, dec, ts, fail_blocks=range(ts.n_blocks))[:3] == (b"", 0, 0)
+
+
 def test_text_caps(emu, data, dec):
     d, plan = data, data["plan"]
     ts = plan.targets(tm.region_strings(_sets(d)["special"], NAMES))
