@@ -11,7 +11,8 @@ int cbc_cli_decompress(const char *in, const char *out, const char *ref, const i
 
 /* exactly one region (for --sam and --depth: at most one, NULL = the whole file) */
 int cbc_cli_decompress_region(const char *in, const char *out, const char *ref, int device, const char *region, int verbose);
-int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int verbose);
+int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int cigar,
+                           uint32_t edits_per_read, int verbose);
 int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude, int verbose);
 /* --pileup: at most one region; min_alt >= 1; edits_per_read 1..510, 0 = the library's default */
 int cbc_cli_decompress_pileup(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,

@@ -282,7 +282,11 @@ int cbc_cli_decompress_region(const char *in, const char *out, const char *ref, 
 /* `cbc -d|-x ... --sam [--region NAME[:BEG[-END]]]`: the same reads as without --sam, as SAM: the
  * header from the container's contig table (host), one alignment line per read assembled on the device
  * (cbc_gpu_decode_sam); only the text crosses PCIe. */
-int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int verbose)
+/* --cigar: the lines with CIGAR, NM and MD (cbc_gpu_decode_sam_cigar) behind the edit-reporting decoder
+ * with an arena of edits_per_read entries per read (0: the default); the buffer is the plain lines' bound plus 64 bytes per read,
+ * and the call is repeated once at the text's own size when that is too small */
+int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int cigar,
+                           uint32_t edits_per_read, int verbose)
 {
     cli_run r;
     if (cli_open(&r, in, ref, NULL, device, "--sam", "stores no contig table")) return 1;
@@ -296,22 +300,41 @@ int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int
     int rc = region ? cbc_unpack_region(u, region, &sel, err, sizeof err) : 0;
     if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT ? err : "region selection failed"); return 1; }
     const uint32_t nb = sel.b1 - sel.b0;
-    const uint64_t cap = cbc_unpack_sam_text_cap(u, sel.b0, sel.b1);
+    uint64_t cap = cbc_unpack_sam_text_cap(u, sel.b0, sel.b1);
+    const uint64_t bound = cigar ? cbc_unpack_sam_cigar_text_cap(u, sel.b0, sel.b1, edits_per_read) : cap;
+    if (cigar) {
+        for (uint32_t q = sel.b0; q < sel.b1; q++) cap += 64ull * u->blocks[q].n_reads;
+        if (cap > bound) cap = bound;
+    }
     char *text = (char *)malloc((size_t)hdr + (size_t)cap + 1);
     if (!text || cbc_unpack_sam_header(u, text, (uint64_t)hdr, err, sizeof err) != hdr) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
     r.t1 = now2();
     uint64_t text_bytes = 0, n_reads = 0;
-    float ms[3] = { 0, 0, 0 };
+    float ms[4] = { 0, 0, 0, 0 };
     if (nb) {                                            /* no block to decode: the header alone, no device needed */
         if (cli_device(&r)) return 1;
         const double b = now2();
         cbc_sam_region rg = { sel.beg, sel.end, sel.smax, 0 };
-        rc = cbc_gpu_decode_sam(r.ctx, u->payloads, u->payload_bytes, u->blocks + sel.b0, nb, &u->caps, u->window_start + sel.b0,
-                                u->block_contig + sel.b0, u->names, u->names_bytes, u->contig_name_off, u->n_contigs,
-                                region ? &rg : NULL, (uint8_t *)text + hdr, cap, &text_bytes, &n_reads, NULL);
+        for (int attempt = 0; attempt < 2; attempt++) {
+            if (cigar)
+                rc = cbc_gpu_decode_sam_cigar(r.ctx, u->payloads, u->payload_bytes, u->blocks + sel.b0, nb, &u->caps, u->window_start + sel.b0,
+                                              u->block_contig + sel.b0, u->names, u->names_bytes, u->contig_name_off, u->n_contigs,
+                                              region ? &rg : NULL, u->max_read_len + u->read_length - 1u, edits_per_read,
+                                              (uint8_t *)text + hdr, cap, &text_bytes, &n_reads, NULL);
+            else
+                rc = cbc_gpu_decode_sam(r.ctx, u->payloads, u->payload_bytes, u->blocks + sel.b0, nb, &u->caps, u->window_start + sel.b0,
+                                        u->block_contig + sel.b0, u->names, u->names_bytes, u->contig_name_off, u->n_contigs,
+                                        region ? &rg : NULL, (uint8_t *)text + hdr, cap, &text_bytes, &n_reads, NULL);
+            if (!(cigar && rc == CBC_E_ARG && text_bytes > cap && text_bytes <= bound)) break;
+            cap = text_bytes;                            /* the text's own size */
+            char *t2 = (char *)realloc(text, (size_t)hdr + (size_t)cap + 1);
+            if (!t2) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+            text = t2;
+        }
         if (rc) { fprintf(stderr, "cbc: SAM decode failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
         r.t_dev = now2() - b;
-        if (verbose) (void)cbc_gpu_last_sam_ms(r.ctx, &ms[0], &ms[1], &ms[2]);
+        if (verbose && cigar) (void)cbc_gpu_last_sam_cigar_ms(r.ctx, &ms[0], &ms[1], &ms[2], &ms[3]);
+        else if (verbose) (void)cbc_gpu_last_sam_ms(r.ctx, &ms[0], &ms[1], &ms[2]);
     }
     const double t3 = now2();
     const size_t total = (size_t)hdr + (size_t)text_bytes;
@@ -326,7 +349,8 @@ int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int
                (unsigned long long)n_reads, (long long)hdr, (unsigned long long)text_bytes);
         printf("time: read + plan + header %.3f s, device init + reference upload %.3f s, decode + count + text %.3f s, write %.3f s\n",
                r.t1 - r.t0, r.t_init, r.t_dev, now2() - t3);
-        if (r.used) printf("kernels: decode %.3f ms, count + scan %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2]);
+        if (r.used && cigar) printf("kernels: edits decode %.3f ms, measure %.3f ms, count + scan %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
+        else if (r.used) printf("kernels: decode %.3f ms, count + scan %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2]);
     }
     free(text);
     cli_close(&r);

@@ -29,6 +29,7 @@
 #include "cbc_hist_body.h"
 #include "cbc_stats_body.h"
 #include "cbc_pileup_body.h"
+#include "cbc_cigar_body.h"
 #include "cbc_plan.h"
 #include "cbc_stream_body.h"
 #include "cbc_long_body.h"
@@ -111,6 +112,17 @@ cbc_pileup_count_kernel(cbc_pileup_args A) { cbc_pileup_count<WaveGPU>(A, blockI
 __global__ void __launch_bounds__(64)
 cbc_pileup_write_kernel(cbc_pileup_args A) { cbc_pileup_write<WaveGPU>(A, blockIdx.x); }
 
+/* SAM text with CIGAR, NM and MD (cbc_gpu_decode_sam_cigar, cbc_cigar_body.h): behind the edits decoder CBC_CIGAR_WAVES wavefronts
+ * per block measure every kept read's CIGAR, NM and MD; then the count (one wavefront per block) and the text assembly
+ * (CBC_SAM_WAVES wavefronts per block) of the SAM text with the longer line */
+__global__ void __launch_bounds__(64 * CBC_CIGAR_WAVES)
+cbc_sam_cigar_measure_kernel(cbc_cigar_args A)
+{
+    if (blockIdx.x < A.S.R.n_blocks) cbc_cigar_measure<WaveGPU>(A, blockIdx.x, WaveGPU::uni(threadIdx.x >> 6), CBC_CIGAR_WAVES);
+}
+__global__ void __launch_bounds__(64)
+cbc_sam_cigar_count_kernel(cbc_cigar_args A) { if (blockIdx.x < A.S.R.n_blocks) cbc_sam_cigar_count<WaveGPU>(A, blockIdx.x); }
+
 __global__ void __launch_bounds__(64)
 cbc_region_count_kernel(cbc_region_args A) { if (blockIdx.x < A.n_blocks) cbc_region_count<WaveGPU>(A, blockIdx.x); }
 
@@ -133,6 +145,12 @@ cbc_sam_write_kernel(cbc_sam_args A)
 {
     if (blockIdx.x >= A.R.n_blocks) return;
     cbc_sam_write<WaveGPU>(A, blockIdx.x, WaveGPU::uni(threadIdx.x >> 6), CBC_SAM_WAVES);
+}
+__global__ void __launch_bounds__(64 * CBC_SAM_WAVES)
+cbc_sam_cigar_write_kernel(cbc_cigar_args A)
+{
+    if (blockIdx.x >= A.S.R.n_blocks) return;
+    cbc_sam_cigar_write<WaveGPU>(A, blockIdx.x, WaveGPU::uni(threadIdx.x >> 6), CBC_SAM_WAVES);
 }
 
 /* Coverage (cbc_gpu_decode_depth, cbc_depth_body.h): one wavefront per block marks the reads in the difference array, one
@@ -396,14 +414,14 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
 /* grow-only device buffer owned by the context: the host-buffer entry points keep their device arrays between calls
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
-enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_XSTARTS, A_XTILE, A_XSP, A_XTHR, A_XPRE, A_XOUT, A_STATS, A_ESIDE, A_EARENA, A_PTAB, A_COUNT };
+enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_XSTARTS, A_XTILE, A_XSP, A_XTHR, A_XPRE, A_XOUT, A_STATS, A_ESIDE, A_EARENA, A_PTAB, A_CIGAR, A_COUNT };
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
 /* what decode_blocks_impl runs behind the decode (its post-decode stage): nothing (plain, 2-bit, span, long reads), or the
  * stage of cbc_gpu_decode_region, _sam, _depth, _targets (reads, SAM, depth), _coverage, _depth_hist, _coverage_ext, _stats (whole
- * file, target set) */
+ * file, target set), _pileup, _sam_cigar */
 enum post_kind { POST_NONE, POST_REGION, POST_SAM, POST_DEPTH, POST_TG_READS, POST_TG_SAM, POST_TG_DEPTH, POST_COV, POST_HIST, POST_COVX,
-                 POST_STATS, POST_TG_STATS, POST_COVQ, POST_PILEUP };
+                 POST_STATS, POST_TG_STATS, POST_COVQ, POST_PILEUP, POST_SAM_CIGAR };
 
 struct cbc_gpu_ctx {
     int device;
@@ -1104,7 +1122,7 @@ static bool post_is_covx(post_kind k) { return k == POST_COVX || k == POST_COVQ;
 static bool post_is_cov(post_kind k) { return k == POST_COV || post_is_covx(k); }
 /* PILEUP shares the depth kinds' arenas, counters and text fetch; it has no change points and its text tiles are the position tiles */
 static bool post_is_depth(post_kind k) { return k == POST_DEPTH || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || k == POST_PILEUP; }
-static bool post_is_sam(post_kind k) { return k == POST_SAM || k == POST_TG_SAM; }
+static bool post_is_sam(post_kind k) { return k == POST_SAM || k == POST_TG_SAM || k == POST_SAM_CIGAR; }
 static bool post_is_targets(post_kind k) { return k == POST_TG_READS || k == POST_TG_SAM || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || k == POST_TG_STATS; }
 static bool post_is_stats(post_kind k) { return k == POST_STATS || k == POST_TG_STATS; }
 
@@ -1126,7 +1144,8 @@ struct post_req {
      * histogram: text_cap = 0); n_selected = reads kept */
     const uint64_t *window_start;
     uint8_t *text; uint64_t text_cap; uint64_t *text_bytes, *n_selected;
-    /* REGION, SAM, DEPTH: keep by [beg, end]; SAM with region == 0 keeps every read (smax = 0).  Targets kinds: 1, 2^64 - 1 */
+    /* REGION, SAM, SAM_CIGAR, DEPTH: keep by [beg, end]; SAM with region == 0 keeps every read (smax = 0; SAM_CIGAR: the
+     * container's span bound, its decoder reports spans).  Targets kinds: 1, 2^64 - 1 */
     uint64_t beg, end; int region;
     /* SAM, TG_SAM: the contig-name table and per block the (offset, length) of its name; depth kinds: the one contig name */
     const uint8_t *names; uint32_t names_bytes; const uint32_t *block_name;
@@ -1139,8 +1158,8 @@ struct post_req {
     hist_req hist;                 /* HIST */
     /* STATS, TG_STATS (with `exclude`): where the tables go, the record groups of the largest block */
     cbc_gpu_stats *stats; uint32_t stats_gmax;
-    /* edits_per_read > 0 (with smax > 0): the edit-reporting decoder.  PILEUP: the line rule and the contig's first reference
-     * byte; NONE (cbc_gpu_decode_blocks_edits): where the side array (2 words per record) and the arena go */
+    /* edits_per_read > 0 (with smax > 0): the edit-reporting decoder.  SAM_CIGAR: nothing more; PILEUP: the line rule and the
+     * contig's first reference byte; NONE (cbc_gpu_decode_blocks_edits): where the side array (2 words per record) and the arena go */
     uint32_t edits_per_read, min_alt; uint64_t ref_c0;
     uint32_t *edit_side; uint16_t *edit_arena;
 };
@@ -1173,7 +1192,7 @@ static post_sizes post_sizes_of(const post_req *rg, uint32_t n_blocks, uint64_t 
 }
 
 /* post stage, step 1: its arenas */
-static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z, uint32_t n_blocks)
+static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z, uint32_t n_blocks, uint64_t n_recs)
 {
     const post_kind k = rg->kind;
     int rc = CBC_OK;
@@ -1242,6 +1261,7 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
         (void)hipGetLastError();
         return set_err(ctx, CBC_E_NOMEM, "no device memory for the window's allele counters (28 bytes per position)", hipSuccess);
     }
+    if (k == POST_SAM_CIGAR) NEED(A_CIGAR, n_recs * 8 + 16, "hipMalloc measured CIGAR, NM and MD sizes");
 done:
     return rc;
 }
@@ -1311,6 +1331,30 @@ static int launch_sam_text(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg,
     hipLaunchKernelGGL(cbc_sam_write_kernel, dim3(ra.n_blocks), dim3(64 * CBC_SAM_WAVES), 0, ks, sa);
     HIPCHK(hipGetLastError(), "launch cbc_sam_write_kernel");
     HIPCHK(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
+/* SAM text with CIGAR, NM and MD: the measure pass over the edits the decoder kept, then the same three steps with the longer line */
+static int launch_sam_cigar_text(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const cbc_region_args &ra, uint64_t n_recs)
+{
+    cbc_cigar_args ca;
+    memset(&ca, 0, sizeof ca);
+    ca.S.R = ra; ca.S.block_name = (const uint32_t *)ctx->arena[A_SBN].p; ca.S.names = (const uint8_t *)ctx->arena[A_SNAMES].p;
+    ca.S.names_bytes = rg->names_bytes; ca.S.region = rg->region ? 1u : 0u;
+    ca.side = (const uint32_t *)ctx->arena[A_ESIDE].p; ca.arena = (const uint16_t *)ctx->arena[A_EARENA].p;
+    ca.arena_entries = n_recs * rg->edits_per_read; ca.per_read = rg->edits_per_read;
+    ca.ref = ctx->d_ref; ca.ref_bytes = ctx->ref_bytes; ca.meas = (uint32_t *)ctx->arena[A_CIGAR].p;
+    hipLaunchKernelGGL(cbc_sam_cigar_measure_kernel, dim3(ra.n_blocks), dim3(64 * CBC_CIGAR_WAVES), 0, ks, ca);
+    HIPCHK(hipGetLastError(), "launch cbc_sam_cigar_measure_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+    hipLaunchKernelGGL(cbc_sam_cigar_count_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, ca);
+    HIPCHK(hipGetLastError(), "launch cbc_sam_cigar_count_kernel");
+    launch_scan_sizes(ks, ra.counts, (uint64_t *)ctx->arena[A_OFF].p, ra.n_blocks);
+    HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+    hipLaunchKernelGGL(cbc_sam_cigar_write_kernel, dim3(ra.n_blocks), dim3(64 * CBC_SAM_WAVES), 0, ks, ca);
+    HIPCHK(hipGetLastError(), "launch cbc_sam_cigar_write_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[4], ks), "hipEventRecord");
     return CBC_OK;
 }
 
@@ -1709,7 +1753,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
             goto done;
         }
     }
-    if (post && (rc = post_arenas(ctx, rg, z, n_blocks)) != CBC_OK) goto done;
+    if (post && (rc = post_arenas(ctx, rg, z, n_blocks, n_recs)) != CBC_OK) goto done;
     tm.alloc_s = wall_now() - T0;
     {
         uint8_t *d_in = (uint8_t *)ctx->arena[A_IN].p, *d_seq = (uint8_t *)ctx->arena[A_SEQ].p;
@@ -1792,6 +1836,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     break;
                 case POST_STATS: case POST_TG_STATS: rc = launch_stats(ctx, ks, rg, ra); break;
                 case POST_PILEUP: rc = launch_pileup(ctx, ks, rg, z, ra, n_recs); break;
+                case POST_SAM_CIGAR: rc = launch_sam_cigar_text(ctx, ks, rg, ra, n_recs); break;
                 }
                 if (rc) goto done;
                 ctx->last_post = rg->kind;                     /* the events now hold this call's times */
@@ -2017,6 +2062,51 @@ API int cbc_gpu_last_sam_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *count_ms,
     if (!ctx || ctx->last_post != POST_SAM) return CBC_E_ARG;
     float *const out[] = { decode_ms, count_ms, text_ms };
     return last_ms(ctx, ctx->ev_rg, out, 3);
+}
+
+/* SAM output with CIGAR, NM and MD: cbc_gpu_decode_sam behind the edits decoder, with the measure pass
+ * in front of the count (cbc_cigar_body.h).  The bound on the text is cbc_unpack_sam_cigar_text_cap's. */
+API int cbc_gpu_decode_sam_cigar(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                 uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                                 const uint32_t *block_contig, const char *names, uint32_t names_bytes,
+                                 const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_sam_region *region, uint32_t smax,
+                                 uint32_t edits_per_read, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_reads,
+                                 cbc_block_result *results)
+{
+    if (!ctx || !blocks || !caps || !window_start || !block_contig || !names || !contig_name_off || !text_bytes || !n_reads ||
+        (text_cap && !text)) return CBC_E_ARG;
+    *text_bytes = 0; *n_reads = 0;
+    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (n_blocks == 0) return CBC_OK;
+    if (!in) return CBC_E_ARG;
+    if (region && (region->smax == 0 || region->beg < 1 || region->beg > region->end))
+        return set_err(ctx, CBC_E_ARG, "SAM region decode wants 1 <= beg <= end and smax > 0", hipSuccess);
+    if (!region && smax == 0) return set_err(ctx, CBC_E_ARG, "SAM decode with CIGAR wants smax > 0 (the container's span bound)", hipSuccess);
+    if (edits_per_read == 0) edits_per_read = CBC_EDITS_PER_READ;
+    if (edits_per_read > CBC_EDITS_MAX) return set_err(ctx, CBC_E_ARG, "SAM decode with CIGAR wants edits_per_read in 1..510 (0: the default)", hipSuccess);
+    const name_tables nt = { window_start, block_contig, names, names_bytes, contig_name_off, n_contigs };
+    block_layout L;
+    int rc = relayout_blocks(ctx, "SAM decode", in_bytes, blocks, n_blocks, &nt, &L);
+    if (rc) return rc;
+    if (L.nrec > 0x3fffffffull) rc = set_err(ctx, CBC_E_ARG, "SAM decode with CIGAR: more than 2^30 - 1 reads in one call", hipSuccess);
+    else {
+        post_req rg;                                           /* every read kept, every field and token at its longest */
+        post_req_init(&rg, POST_SAM_CIGAR, region ? region->smax : smax, window_start, text, text_cap,
+                      L.nrec * (56ull + 3ull * blocks[0].seq_stride + 16ull * edits_per_read) + L.name_sum, text_bytes, n_reads);
+        rg.beg = region ? region->beg : 1u; rg.end = region ? region->end : UINT64_MAX; rg.region = region != NULL;
+        rg.names = (const uint8_t *)names; rg.names_bytes = names_bytes; rg.block_name = L.bn;
+        rg.edits_per_read = edits_per_read;
+        rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
+    }
+    layout_free(&L);
+    return rc;
+}
+
+API int cbc_gpu_last_sam_cigar_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *measure_ms, float *count_ms, float *text_ms)
+{
+    if (!ctx || ctx->last_post != POST_SAM_CIGAR) return CBC_E_ARG;
+    float *const out[] = { decode_ms, measure_ms, count_ms, text_ms };
+    return last_ms(ctx, ctx->ev_rg, out, 4);
 }
 
 /* coverage: the window's blocks laid out afresh as for a region decode, then span decode + mark + scan + text on the device

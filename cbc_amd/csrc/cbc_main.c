@@ -78,7 +78,12 @@ static void usage(const char *p)
             "                   NAME, pos, ref, depth, A, C, G, T, N, del, ins; the whole file or one --region; counted on the device;\n"
             "                   with --depth-exclude-flags; not with --sam, --depth, --bedcov, --depth-hist or --stats)\n"
             "         --min-alt K (with --pileup: only positions with K or more non-reference observations; default 1)\n"
-            "         --max-edits-per-read N (with --pileup: deleted + inserted bases kept per read of a block, 1..510; default 16)\n"
+            "         --max-edits-per-read N (with --pileup or --sam --cigar: deleted + inserted bases kept per read of a block, 1..510;\n"
+            "                  default 16)\n"
+            "         --cigar (with --sam: CIGAR, NM:i and MD:Z on every line, in the codec's view of the alignment: M, I, D and S only,\n"
+            "                  an insertion in front of a deletion at the same place, an inserted run at a read's end as S, a mismatch\n"
+            "                  = the read byte differs from the reference byte, so N over N matches; at most one --region, no\n"
+            "                  --regions-file)\n"
             "options: -l (header read length = longest read)  --block-reads N (default 4096)  --device N (default 0)\n"
             "         --threads N (SAM parser threads, default one per CPU)  --verbose (stage times)\n"
             "         --compat (write the reference's own single-stream format; slow: one stream = one wavefront)\n"
@@ -496,7 +501,7 @@ int main(int argc, char **argv)
     uint32_t hist_max = 0;
     int stats_out = 0, stats_excl_given = 0;
     uint32_t stats_exclude = 0;
-    int pileup = 0, min_alt_given = 0, max_edits_given = 0;
+    int pileup = 0, min_alt_given = 0, max_edits_given = 0, sam_cigar = 0;
     uint32_t min_alt = 1, max_edits = 0;
     g_main_t0 = now_s();
     for (int i = 1; i < argc; i++) {
@@ -519,6 +524,7 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--region") && i + 1 < argc) { region = regions[n_regions++] = argv[++i]; continue; }
         if (!strcmp(a, "--regions-file") && i + 1 < argc) { regions_file = argv[++i]; continue; }
         if (!strcmp(a, "--sam")) { sam_out = 1; continue; }
+        if (!strcmp(a, "--cigar")) { sam_cigar = 1; continue; }
         if (!strcmp(a, "--depth")) { depth_out = 1; continue; }
         if (!strcmp(a, "--depth-exclude-flags") && i + 1 < argc) { if (!parse_flag_mask(a, argv[++i], &depth_exclude)) return 1; depth_excl_given = 1; continue; }
         if (!strcmp(a, "--stats-exclude-flags") && i + 1 < argc) { if (!parse_flag_mask(a, argv[++i], &stats_exclude)) return 1; stats_excl_given = 1; continue; }
@@ -604,7 +610,7 @@ int main(int argc, char **argv)
     const struct { const char *name; int given; const char *clash, *owned; } opts[] = {
         { "--regions-file", regions_file != NULL, NULL, NULL },
         { "--region", region != NULL, NULL, NULL },
-        { "--sam", sam_out, NULL, NULL },
+        { "--sam", sam_out, NULL, sam_cigar ? "--cigar" : NULL },
         { "--depth", depth_out, "--depth and --sam are two different outputs", NULL },
         { "--bedcov", bedcov, "--bedcov, --depth and --sam are different outputs",
           window_given ? "--window" : min_depth_given ? "--min-depth" : thr_given ? "--thresholds" : count_reads ? "--count-reads" :
@@ -612,7 +618,7 @@ int main(int argc, char **argv)
         { "--depth-hist", depth_hist, "--depth-hist, --bedcov, --depth and --sam are different outputs", hist_max_given ? "--hist-max" : NULL },
         { "--stats", stats_out, "--stats, --depth-hist, --bedcov, --depth and --sam are different outputs", stats_excl_given ? "--stats-exclude-flags" : NULL },
         { "--pileup", pileup, "--pileup, --stats, --depth-hist, --bedcov, --depth and --sam are different outputs",
-          min_alt_given ? "--min-alt" : max_edits_given ? "--max-edits-per-read" : NULL },
+          min_alt_given ? "--min-alt" : max_edits_given && !sam_cigar ? "--max-edits-per-read" : NULL },
     };
     for (size_t k = 0; k < sizeof opts / sizeof opts[0]; k++) {
         if (opts[k].owned && !opts[k].given) { fprintf(stderr, "cbc: %s applies to %s\n", opts[k].owned, opts[k].name); return 1; }
@@ -624,6 +630,9 @@ int main(int argc, char **argv)
     if (pileup) {                                                 /* one window or every contig: a target set is left for later */
         if (regions_file || n_regions > 1) { fprintf(stderr, "cbc: --pileup takes at most one --region and no --regions-file\n"); return 1; }
         return cbc_cli_decompress_pileup(files[0], files[1], files[2], device, region, depth_exclude, min_alt, max_edits, verbose);
+    }
+    if (sam_cigar && (regions_file || n_regions > 1)) {            /* as for --pileup */
+        fprintf(stderr, "cbc: --sam --cigar takes at most one --region and no --regions-file\n"); return 1;
     }
     if (depth_hist)
         return cbc_cli_decompress_hist(files[0], files[1], files[2], device, regions, n_regions, regions_file, hist_max, depth_exclude, verbose);
@@ -637,7 +646,7 @@ int main(int argc, char **argv)
         return cbc_cli_decompress_targets(files[0], files[1], files[2], device, regions, n_regions, regions_file,
                                           depth_out ? CBC_TARGETS_DEPTH : sam_out ? CBC_TARGETS_SAM : CBC_TARGETS_READS, depth_exclude, verbose);
     if (depth_out) return cbc_cli_decompress_depth(files[0], files[1], files[2], device, region, depth_exclude, verbose);
-    if (sam_out) return cbc_cli_decompress_sam(files[0], files[1], files[2], device, region, verbose);
+    if (sam_out) return cbc_cli_decompress_sam(files[0], files[1], files[2], device, region, sam_cigar, max_edits, verbose);
     if (region) return cbc_cli_decompress_region(files[0], files[1], files[2], device, region, verbose);
     if (ndev == 0) { devs[0] = device; ndev = 1; }
     return mode == 1 ? do_compress(files[0], files[1], files[2], block_reads, device, var_length, threads, verbose, compat, devs, ndev, long_reads, device_parse, want_rccl)

@@ -1915,6 +1915,36 @@ API uint64_t cbc_unpack_sam_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint
     return n;
 }
 
+/* Bytes that always hold the lines of blocks [b0, b1) with CIGAR, NM and MD (cbc_gpu_decode_sam_cigar).  Per block of n reads
+ * on a contig whose name has nl bytes, with the arena of n * edits_per_read entries its reads with indels share:
+ *   every read: the SAM line at its longest, 35 + nl + seq_stride (cbc_unpack_sam_text_cap), whose '*' the CIGAR replaces;
+ *     rl <= seq_stride <= 256 and the counts are <= 255, so every number of CIGAR and MD has at most 3 digits and NM
+ *     (<= rl + nDel) has 3; "\tNM:i:" and "\tMD:Z:" are 12 bytes: + 15;
+ *     a read with e arena entries (deleted and inserted bases) has at most 1 + 2e runs of read indices and deleted runs (an
+ *     inserted run adds itself and the aligned run behind it, a deleted run itself and the aligned run behind it), 4 bytes
+ *     each: 4 - 1 + 8e for the CIGAR;
+ *     MD: a mismatch's token is digits(n) + 1 <= 2 (n + 1) bytes for the n + 1 aligned bases it covers, so the aligned bases
+ *     cost at most 2 seq_stride; a deleted run costs digits(n) + 1 + its bases <= 5 per deleted entry (the '0' of a mismatch
+ *     behind it is that mismatch's); the last count 3;
+ *   in all n * (35 + nl + seq_stride + 15 + 3 + 2 seq_stride + 3) + 13 * (entries in use) <= n * (56 + nl + 3 seq_stride +
+ *   16 edits_per_read), the constant per entry rounded up.  A read whose entries are not the decoder's gets the plain line.
+ * edits_per_read: 0 = CBC_EDITS_PER_READ.  0 for a plan cbc_unpack_sam_header refuses, a bad range or edits_per_read above
+ * CBC_EDITS_MAX.  About three times cbc_unpack_sam_text_cap: callers try less first (include/cbc_gpu.h). */
+API uint64_t cbc_unpack_sam_cigar_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t edits_per_read)
+{
+    if (!u || u->long_reads || !u->block_contig || !u->names || !u->contig_name_off || b0 > b1 || b1 > u->n_blocks) return 0;
+    if (edits_per_read == 0) edits_per_read = CBC_EDITS_PER_READ;
+    if (edits_per_read > CBC_EDITS_MAX) return 0;
+    uint64_t n = 0;
+    for (uint32_t b = b0; b < b1; b++) {
+        const uint32_t c = u->block_contig[b];
+        const int64_t nl = c < u->n_contigs ? sam_name_len(u, c) : -1;
+        if (nl < 0) return 0;
+        n += (uint64_t)u->blocks[b].n_reads * (56ull + (uint64_t)nl + 3ull * u->seq_stride + 16ull * edits_per_read);
+    }
+    return n;
+}
+
 /* ---- coverage output (include/cbc_host.h) ---- */
 API int cbc_unpack_contig_blocks(const cbc_unpack_plan *u, uint32_t contig, cbc_region_sel *sel, char *errbuf, size_t errlen)
 {

@@ -118,29 +118,33 @@ CBC_FN void cbc_store_result(cbc_block_result *r, uint32_t nbytes, uint32_t n_sy
 
 /* ---- the reads-text skeleton ---------------------------------------------------------------------------------------------
  * The count and the write pass of every output that is one line per kept read: region and SAM text, and the two of a target
- * set (cbc_sam_body.h, cbc_targets_body.h).  A member is its argument struct A (R = the cbc_region_args inside: counts,
- * offsets, text) and SAM, which picks the line.  It supplies, overloaded on A and found when the skeleton is instantiated:
- *   cbc_text_block<SAM>(A, blk)       the block set-up X; X.B is its cbc_region_blk
- *   cbc_text_keep<W>(A, X, r0, G)     keep flags of records [r0, r0 + 64); fills G.rlv, and G.lp, G.fl for a SAM line
- * The line is overloaded on cbc_line<SAM>: the bases here, the SAM line in cbc_sam_body.h (its X is a cbc_sam_blk). */
+ * set (cbc_sam_body.h, cbc_targets_body.h), and the SAM text with CIGAR and tags (cbc_cigar_body.h).  A member is its argument
+ * struct A (R = the cbc_region_args inside: counts, offsets, text) and LINE, which picks the line.  It supplies, overloaded on A
+ * and found when the skeleton is instantiated:
+ *   cbc_text_block<LINE>(A, blk)      the block set-up X; X.B is its cbc_region_blk
+ *   cbc_text_keep<W>(A, X, r0, G)     keep flags of records [r0, r0 + 64); fills G.rlv, and G.lp, G.fl for a SAM line, and
+ *                                     G.xa, G.xb where its line wants two more words per record
+ * The line is overloaded on cbc_line<LINE>: the bases here, the SAM line in cbc_sam_body.h (its X is a cbc_sam_blk), the SAM
+ * line with CIGAR, NM and MD in cbc_cigar_body.h (its X is a cbc_cigar_blk). */
+enum { CBC_LINE_BASES = 0, CBC_LINE_SAM = 1, CBC_LINE_SAM_CIGAR = 2 };
 template <class W>
-struct cbc_text_grp { typename W::V32 rlv, lp, fl, tl, incl; };      /* 64 records: length, local POS, FLAG, line length, its scan */
-template <bool SAM>
+struct cbc_text_grp { typename W::V32 rlv, lp, fl, tl, incl, xa, xb; };   /* 64 records: length, local POS, FLAG, line length, its scan; the line's own */
+template <int LINE>
 struct cbc_line {};
 
 template <class W, class X>
-CBC_FN typename W::V32 cbc_line_len(cbc_line<false>, const X &, const cbc_text_grp<W> &G) { return G.rlv + 1u; }
+CBC_FN typename W::V32 cbc_line_len(cbc_line<CBC_LINE_BASES>, const X &, const cbc_text_grp<W> &G) { return G.rlv + 1u; }
 
 /* the line of record r0 + j = lane j of the group whose text begins at o */
 template <class W, class X>
-CBC_FN void cbc_line_emit(cbc_line<false>, uint8_t *text, uint64_t o, const X &x, uint32_t r0, uint32_t j, const cbc_text_grp<W> &G)
+CBC_FN void cbc_line_emit(cbc_line<CBC_LINE_BASES>, uint8_t *text, uint64_t o, const X &x, uint32_t r0, uint32_t j, const cbc_text_grp<W> &G)
 {
     const uint32_t rl = W::readlane(G.rlv, j), at = W::readlane(G.incl, j) - (rl + 1u);
     cbc_region_emit<W>(text, o + at, x.B.rows + (uint64_t)(r0 + j) * x.B.stride, rl);
 }
 
 struct cbc_region_tblk { cbc_region_blk B; };
-template <bool SAM>
+template <int LINE>
 CBC_FN cbc_region_tblk cbc_text_block(const cbc_region_args &A, uint32_t blk) { return cbc_region_tblk{cbc_region_block(A, blk)}; }
 
 template <class W>
@@ -150,17 +154,17 @@ CBC_FN typename W::Mask cbc_text_keep(const cbc_region_args &, const cbc_region_
 }
 
 /* one wavefront per block: its kept reads and text bytes into counts[blk] for the size scan */
-template <class W, bool SAM, class Args>
+template <class W, int LINE, class Args>
 CBC_FN void cbc_text_count(const Args &A, const cbc_region_args &R, uint32_t blk)
 {
-    const auto X = cbc_text_block<SAM>(A, blk);
+    const auto X = cbc_text_block<LINE>(A, blk);
     uint32_t kept = 0, bytes = 0;
     if (X.B.ok) {
         for (uint32_t r0 = 0; r0 < X.B.n; r0 += 64u) {
             cbc_text_grp<W> G;
             const typename W::Mask k = cbc_text_keep<W>(A, X, r0, G);
             kept += W::reduce_add(W::select(k, W::splat(1u), W::splat(0u)));
-            bytes += W::reduce_add(W::select(k, cbc_line_len<W>(cbc_line<SAM>(), X, G), W::splat(0u)));
+            bytes += W::reduce_add(W::select(k, cbc_line_len<W>(cbc_line<LINE>(), X, G), W::splat(0u)));
         }
     }
     cbc_store_result<W>(R.counts + blk, bytes, kept);
@@ -169,10 +173,10 @@ CBC_FN void cbc_text_count(const Args &A, const cbc_region_args &R, uint32_t blk
 /* wavefront `wave` of `n_waves` writes every n_waves-th kept read of block blk.  The line length is asked for behind the keep
  * flags (in the count pass: behind their reduction, so that the two DPP ladders do not interleave) and r0, j go to the line
  * apart (the row address is formed behind the readlanes): profiles/text_bodies_isa.md */
-template <class W, bool SAM, class Args>
+template <class W, int LINE, class Args>
 CBC_FN void cbc_text_write(const Args &A, const cbc_region_args &R, uint32_t blk, uint32_t wave, uint32_t n_waves)
 {
-    const auto X = cbc_text_block<SAM>(A, blk);
+    const auto X = cbc_text_block<LINE>(A, blk);
     const uint32_t bytes = R.counts[blk].nbytes;
     const uint64_t o0 = R.offsets[blk];
     if (!X.B.ok || bytes == 0u || o0 > R.text_cap || bytes > R.text_cap - o0) return;
@@ -181,7 +185,7 @@ CBC_FN void cbc_text_write(const Args &A, const cbc_region_args &R, uint32_t blk
     for (uint32_t r0 = 0; r0 < X.B.n; r0 += 64u) {
         cbc_text_grp<W> G;
         const typename W::Mask k = cbc_text_keep<W>(A, X, r0, G);
-        G.tl = W::select(k, cbc_line_len<W>(cbc_line<SAM>(), X, G), W::splat(0u));
+        G.tl = W::select(k, cbc_line_len<W>(cbc_line<LINE>(), X, G), W::splat(0u));
         G.incl = W::scan_incl_add(G.tl);
         const uint32_t chunk = W::readlane(G.incl, 63u);
         if (chunk > (o0 + bytes) - o) return;                          /* the records changed under the count pass */
@@ -190,18 +194,18 @@ CBC_FN void cbc_text_write(const Args &A, const cbc_region_args &R, uint32_t blk
             const uint32_t j = W::ctz64(bits);
             bits &= bits - 1u;
             if ((q++ % n_waves) != wave) continue;
-            cbc_line_emit<W>(cbc_line<SAM>(), R.text, o, X, r0, j, G);
+            cbc_line_emit<W>(cbc_line<LINE>(), R.text, o, X, r0, j, G);
         }
         o += chunk;
     }
 }
 
 template <class W>
-CBC_FN void cbc_region_count(const cbc_region_args &A, uint32_t blk) { cbc_text_count<W, false>(A, A, blk); }
+CBC_FN void cbc_region_count(const cbc_region_args &A, uint32_t blk) { cbc_text_count<W, CBC_LINE_BASES>(A, A, blk); }
 template <class W>
 CBC_FN void cbc_region_write(const cbc_region_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
 {
-    cbc_text_write<W, false>(A, A, blk, wave, n_waves);
+    cbc_text_write<W, CBC_LINE_BASES>(A, A, blk, wave, n_waves);
 }
 
 #endif /* CBC_REGION_BODY_H */

@@ -214,21 +214,21 @@ CBC_FN void cbc_sam_emit(uint8_t *text, uint64_t o, const uint8_t *row, uint32_t
 
 /* ---- the SAM line and the SAM member of the reads-text skeleton (cbc_region_body.h) ------------------------------------- */
 template <class W>
-CBC_FN typename W::V32 cbc_line_len(cbc_line<true>, const cbc_sam_blk &S, const cbc_text_grp<W> &G)
+CBC_FN typename W::V32 cbc_line_len(cbc_line<CBC_LINE_SAM>, const cbc_sam_blk &S, const cbc_text_grp<W> &G)
 {
     return cbc_sam_line_len<W>(S, G.rlv, G.lp, G.fl);
 }
 
 /* the constant table is the same for every line: the compiler makes it once, in front of the loops */
 template <class W>
-CBC_FN void cbc_line_emit(cbc_line<true>, uint8_t *text, uint64_t o, const cbc_sam_blk &S, uint32_t r0, uint32_t j, const cbc_text_grp<W> &G)
+CBC_FN void cbc_line_emit(cbc_line<CBC_LINE_SAM>, uint8_t *text, uint64_t o, const cbc_sam_blk &S, uint32_t r0, uint32_t j, const cbc_text_grp<W> &G)
 {
     const uint32_t len = W::readlane(G.tl, j), at = W::readlane(G.incl, j) - len;
     cbc_sam_emit<W>(text, o + at, S.B.rows + (uint64_t)(r0 + j) * S.B.stride, W::readlane(G.rlv, j), S.ws + W::readlane(G.lp, j),
                     W::readlane(G.fl, j), S.name, S.nl, len, cbc_sam_const_tab<W>());
 }
 
-template <bool SAM>
+template <int LINE>
 CBC_FN cbc_sam_blk cbc_text_block(const cbc_sam_args &A, uint32_t blk) { return cbc_sam_block(A, blk); }
 
 template <class W>
@@ -238,11 +238,11 @@ CBC_FN typename W::Mask cbc_text_keep(const cbc_sam_args &A, const cbc_sam_blk &
 }
 
 template <class W>
-CBC_FN void cbc_sam_count(const cbc_sam_args &A, uint32_t blk) { cbc_text_count<W, true>(A, A.R, blk); }
+CBC_FN void cbc_sam_count(const cbc_sam_args &A, uint32_t blk) { cbc_text_count<W, CBC_LINE_SAM>(A, A.R, blk); }
 template <class W>
 CBC_FN void cbc_sam_write(const cbc_sam_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
 {
-    cbc_text_write<W, true>(A, A.R, blk, wave, n_waves);
+    cbc_text_write<W, CBC_LINE_SAM>(A, A.R, blk, wave, n_waves);
 }
 
 #endif /* CBC_SAM_BODY_H */

@@ -111,11 +111,11 @@ CBC_FN typename W::Mask cbc_targets_keep(const cbc_targets_blk &T, uint32_t r0, 
 /* ---- reads, SAM: the two target-set members of the reads-text skeleton (cbc_region_body.h) ------------------------------- */
 struct cbc_targets_tblk : cbc_sam_blk { cbc_targets_blk T; };        /* B = T.B; name, ws, nl are set up for a SAM line alone */
 
-template <bool SAM>
+template <int LINE>
 CBC_FN cbc_targets_tblk cbc_text_block(const cbc_targets_args &A, uint32_t blk)
 {
     cbc_targets_tblk X = {};
-    if (SAM) static_cast<cbc_sam_blk &>(X) = cbc_sam_block(A.S, blk); else X.B = cbc_region_block(A.S.R, blk);
+    if (LINE == CBC_LINE_SAM) static_cast<cbc_sam_blk &>(X) = cbc_sam_block(A.S, blk); else X.B = cbc_region_block(A.S.R, blk);
     X.T = cbc_targets_block(X.B, A.S.R.window_start[blk], A.iv, A.block_iv, A.n_iv, blk);
     X.B = X.T.B;
     return X;
@@ -129,18 +129,18 @@ CBC_FN typename W::Mask cbc_text_keep(const cbc_targets_args &, const cbc_target
 }
 
 template <class W>
-CBC_FN void cbc_targets_count(const cbc_targets_args &A, uint32_t blk) { cbc_text_count<W, false>(A, A.S.R, blk); }
+CBC_FN void cbc_targets_count(const cbc_targets_args &A, uint32_t blk) { cbc_text_count<W, CBC_LINE_BASES>(A, A.S.R, blk); }
 template <class W>
 CBC_FN void cbc_targets_write(const cbc_targets_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
 {
-    cbc_text_write<W, false>(A, A.S.R, blk, wave, n_waves);
+    cbc_text_write<W, CBC_LINE_BASES>(A, A.S.R, blk, wave, n_waves);
 }
 template <class W>
-CBC_FN void cbc_targets_sam_count(const cbc_targets_args &A, uint32_t blk) { cbc_text_count<W, true>(A, A.S.R, blk); }
+CBC_FN void cbc_targets_sam_count(const cbc_targets_args &A, uint32_t blk) { cbc_text_count<W, CBC_LINE_SAM>(A, A.S.R, blk); }
 template <class W>
 CBC_FN void cbc_targets_sam_write(const cbc_targets_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
 {
-    cbc_text_write<W, true>(A, A.S.R, blk, wave, n_waves);
+    cbc_text_write<W, CBC_LINE_SAM>(A, A.S.R, blk, wave, n_waves);
 }
 
 /* ---- depth: mark ------------------------------------------------------------------------------------------------------- */

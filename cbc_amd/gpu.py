@@ -226,6 +226,14 @@ def lib():
                                          ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
         L.cbc_gpu_last_sam_ms.restype = ctypes.c_int
         L.cbc_gpu_last_sam_ms.argtypes = L.cbc_gpu_last_region_ms.argtypes
+        L.cbc_gpu_decode_sam_cigar.restype = ctypes.c_int
+        L.cbc_gpu_decode_sam_cigar.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                               ctypes.POINTER(host.LdsCaps), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(SamRegion),
+                                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.cbc_gpu_last_sam_cigar_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_sam_cigar_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         L.cbc_gpu_decode_depth.restype = ctypes.c_int
         L.cbc_gpu_decode_depth.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
                                            ctypes.POINTER(host.LdsCaps), ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32,
@@ -314,7 +322,8 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_last_stats_ms",
            "cbc_gpu_decode_coverage_ext", "cbc_gpu_last_coverage_ext_ms",
            "cbc_gpu_decode_coverage_quant", "cbc_gpu_last_coverage_quant_ms",
-           "cbc_gpu_decode_pileup", "cbc_gpu_last_pileup_ms", "cbc_gpu_decode_blocks_edits"]
+           "cbc_gpu_decode_pileup", "cbc_gpu_last_pileup_ms", "cbc_gpu_decode_blocks_edits",
+           "cbc_gpu_decode_sam_cigar", "cbc_gpu_last_sam_cigar_ms"]
 
 EDITS_PER_READ = 16           # CBC_EDITS_PER_READ: the library's default arena size, entries per read of a block
 
@@ -566,12 +575,21 @@ class Encoder:
         out = text[:int(nbytes.value)].tobytes()
         return (out, int(nsel.value), sel, res[:nb]) if results else out
 
-    def decode_sam(self, plan: "host.UnpackPlan", region=None, results=False, text_cap=None):
+    def decode_sam(self, plan: "host.UnpackPlan", region=None, results=False, text_cap=None, cigar=False, edits_per_read=None):
         """The reads of the container, or with `region` (NAME, NAME:BEG or NAME:BEG-END) the reads decode_region selects, as
         SAM text: plan.sam_header() + one alignment line per read, assembled on the device (cbc_gpu_decode_sam).  The
         reference must have been uploaded (upload_reference(plan.ref)).  An empty selection gives the header alone and runs
         nothing on the device.  With results=True returns (text, n_reads, selection or None, per-block decode results).
-        text_cap: size of the buffer for the lines (default: plan.sam_text_cap of the blocks)."""
+        text_cap: size of the buffer for the lines (default: plan.sam_text_cap of the blocks).
+        cigar=True: every line carries CIGAR, NM:i and MD:Z in the codec's view of the alignment (cbc_gpu_decode_sam_cigar: an
+        insertion run is written in front of a deletion at the same place, an inserted run at a read's end is S, a mismatch is
+        a plain byte compare with the uploaded reference); edits_per_read sizes the arena as for decode_pileup (a block that
+        needs more fails, the error names the option).  Its default buffer is plan.sam_text_cap plus 64 bytes per read, and the
+        call is repeated once at the text's own size when that is too small; plan.sam_cigar_text_cap always suffices."""
+        if cigar:
+            return self._decode_sam_cigar(plan, region, results, text_cap, edits_per_read)
+        if edits_per_read is not None:
+            raise ValueError("edits_per_read applies to decode_sam(cigar=True)")
         hdr = plan.sam_header()
         sel = plan.region(region) if region is not None else None
         b0, b1 = (sel.b0, sel.b1) if sel is not None else (0, plan.n_blocks)
@@ -591,6 +609,40 @@ class Encoder:
                                       ctypes.byref(nbytes), ctypes.byref(nrd), res.ctypes.data)
         self.last_sam_text_bytes = int(nbytes.value)
         self._check_blocks(rc, "cbc_gpu_decode_sam", results)
+        out = hdr + text[:int(nbytes.value)].tobytes()
+        return (out, int(nrd.value), sel, res[:nb]) if results else out
+
+    def _decode_sam_cigar(self, plan, region, results, text_cap, edits_per_read):
+        hdr = plan.sam_header()
+        epr = 0 if edits_per_read is None else int(edits_per_read)
+        if edits_per_read is not None and not 1 <= epr <= 510:
+            raise ValueError("edits_per_read in 1..510")
+        sel = plan.region(region) if region is not None else None
+        b0, b1 = (sel.b0, sel.b1) if sel is not None else (0, plan.n_blocks)
+        nb = b1 - b0
+        res = np.zeros(max(nb, 1), dtype=host.RESULT_DTYPE)
+        self.last_sam_text_bytes = 0
+        if nb == 0:
+            return (hdr, 0, sel, res[:0]) if results else hdr
+        blocks, ws, bc = self._gather(plan, slice(b0, b1))
+        caps, pay, names, noff = self._plan_args(plan)
+        bound = plan.sam_cigar_text_cap(b0, b1, epr)
+        first = plan.sam_text_cap(b0, b1) + 64 * int(plan.blocks[b0:b1]["n_reads"].sum())
+        cap = min(first, bound) if text_cap is None else int(text_cap)
+        nbytes, nrd = ctypes.c_uint64(), ctypes.c_uint64()
+        rg = SamRegion(sel.beg, sel.end, sel.smax, 0) if sel is not None else None
+        smax = plan.max_read_len + plan.read_length - 1       # the container's span bound, the one every selection carries
+        for _ in range(2):
+            text = np.zeros(max(cap, 1), dtype=np.uint8)
+            rc = lib().cbc_gpu_decode_sam_cigar(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
+                                                ws.ctypes.data, bc.ctypes.data, names.ctypes.data, names.size, noff.ctypes.data,
+                                                plan.n_contigs, ctypes.byref(rg) if rg is not None else None, smax, epr,
+                                                text.ctypes.data, cap, ctypes.byref(nbytes), ctypes.byref(nrd), res.ctypes.data)
+            if not (text_cap is None and rc == -1 and cap < int(nbytes.value) <= bound):
+                break
+            cap = int(nbytes.value)                           # the text's own size
+        self.last_sam_text_bytes = int(nbytes.value)
+        self._check_blocks(rc, "cbc_gpu_decode_sam_cigar", results)
         out = hdr + text[:int(nbytes.value)].tobytes()
         return (out, int(nrd.value), sel, res[:nb]) if results else out
 
@@ -991,6 +1043,10 @@ class Encoder:
     def last_sam_ms(self):
         """(decode, count + scan, text) kernel milliseconds of the last decode_sam."""
         return self._last_ms("cbc_gpu_last_sam_ms", 3, must=True)
+
+    def last_sam_cigar_ms(self):
+        """(edits decode, measure, count + scan, text) kernel milliseconds of the last decode_sam(cigar=True)."""
+        return self._last_ms("cbc_gpu_last_sam_cigar_ms", 4, must=True)
 
     def last_region_ms(self):
         """(decode, filter + scan, text) kernel milliseconds of the last decode_region."""

@@ -205,6 +205,8 @@ def lib():
         L.cbc_unpack_contig_blocks.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.POINTER(RegionSelC), ctypes.c_char_p, ctypes.c_size_t]
         L.cbc_unpack_depth_text_cap.restype = ctypes.c_uint64
         L.cbc_unpack_depth_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+        L.cbc_unpack_sam_cigar_text_cap.restype = ctypes.c_uint64
+        L.cbc_unpack_sam_cigar_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
         L.cbc_unpack_pileup_text_cap.restype = ctypes.c_uint64
         L.cbc_unpack_pileup_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
@@ -716,6 +718,11 @@ class UnpackPlan:
     def sam_text_cap(self, b0=0, b1=None) -> int:
         """Bytes that always hold the alignment lines of blocks [b0, b1) (cbc_unpack_sam_text_cap)."""
         return int(lib().cbc_unpack_sam_text_cap(self._ptr, b0, self.n_blocks if b1 is None else b1))
+
+    def sam_cigar_text_cap(self, b0=0, b1=None, edits_per_read=0) -> int:
+        """Bytes that always hold the alignment lines of blocks [b0, b1) with CIGAR, NM and MD, for an arena of edits_per_read
+        entries per read (0: the default) (cbc_unpack_sam_cigar_text_cap)."""
+        return int(lib().cbc_unpack_sam_cigar_text_cap(self._ptr, b0, self.n_blocks if b1 is None else b1, edits_per_read))
 
     def text(self, recs: np.ndarray, seq: np.ndarray) -> bytes:
         """One reconstructed read per line (what `cbc -d` writes)."""

@@ -332,6 +332,37 @@ int  cbc_gpu_decode_sam(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, 
 /* Kernel times of the most recent cbc_gpu_decode_sam (HIP events on its stream): the decode, the count pass + block scan,
  * and the text assembly. */
 int  cbc_gpu_last_sam_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *count_ms, float *text_ms);
+/* cbc_gpu_decode_sam with CIGAR, NM and MD: the same selection, order, FLAG, RNAME, POS and SEQ, the
+ * line
+ *     *\t<FLAG>\t<RNAME>\t<POS>\t255\t<CIGAR>\t*\t0\t0\t<SEQ>\t*\tNM:i:<n>\tMD:Z:<md>\n
+ * from the alignment the edit-reporting decoder keeps (cbc_gpu_decode_blocks_edits below): per read with indels nDel matched
+ * coordinates dc[] and nIns read indices oi[]; T = rl - nIns.  The read's elements in order, for m = 0 .. T: the inserted read
+ * indices in front of aligned base m (those q in oi with q - #{oi < q} = m), then the deleted bases with dc = m, then aligned
+ * base m (m < T): an insertion run is anchored at the aligned base before it, and an input that had the deletion first comes back
+ * with the insertion first.  CIGAR = maximal runs of one kind: M (never = or X), D, I; an inserted run with no aligned base
+ * before it or none after it in the read is S (a leading or trailing I of the input comes back as S).  A mismatch is an aligned
+ * read byte that differs from the byte of the uploaded reference (a plain byte compare: N over N is a match, which samtools
+ * calmd counts as a mismatch).  NM = mismatches + bases of I runs + deleted bases.  MD: the standard grammar over the aligned and
+ * deleted elements (n matches; a mismatch: n, the reference byte; a deleted run: n, '^', its reference bytes; n at the end).  A
+ * read coded as perfect is <rl>M, NM:i:0, MD:Z:<rl>.  A record whose side / arena entries are not what the decoder writes
+ * (counts above 255, entries outside the block's arena, dc not ascending or above T, oi not strictly ascending or >= rl, rl = 0,
+ * reference bytes outside the upload) is written as cbc_gpu_decode_sam writes it, CIGAR '*' and no tags.
+ * region = NULL: every read, decoded against smax (> 0: the container's span bound, as cbc_gpu_decode_blocks_span takes it);
+ * otherwise smax is not read and region->smax is the bound.  edits_per_read (1..CBC_EDITS_MAX, 0 = CBC_EDITS_PER_READ) sizes the
+ * arena as for cbc_gpu_decode_pileup: a block that needs more fails with CBC_ST_EDITS.  A failed block writes nothing and the
+ * call returns CBC_E_BLOCK.  *text_bytes is also set when text_cap is too small (CBC_E_ARG, nothing copied):
+ * cbc_unpack_sam_cigar_text_cap always suffices but is about three times the text, so a caller may try less and repeat once at
+ * *text_bytes.  One chunk, one stream, no host round trip between the kernels. */
+int  cbc_gpu_decode_sam_cigar(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                              uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                              const uint32_t *block_contig /* n_blocks */, const char *names, uint32_t names_bytes,
+                              const uint32_t *contig_name_off /* n_contigs */, uint32_t n_contigs,
+                              const cbc_sam_region *region /* or NULL */, uint32_t smax, uint32_t edits_per_read,
+                              uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_reads,
+                              cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_sam_cigar: the edits decode, the measure pass, the count pass + block scan,
+ * and the text assembly. */
+int  cbc_gpu_last_sam_cigar_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *measure_ms, float *count_ms, float *text_ms);
 
 /* ---- coverage of a decode -------------------------------------------------------------------------
  * Decode `blocks` -- a selection of cbc_unpack_region on ONE contig, decoded by the span-reporting decoder against smax --

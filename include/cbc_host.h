@@ -214,6 +214,10 @@ int     cbc_unpack_region(const cbc_unpack_plan *u, const char *region, cbc_regi
  * blocks [b0, b1) (0 for a plan the header function refuses or a bad range). */
 int64_t  cbc_unpack_sam_header(const cbc_unpack_plan *u, char *dst, uint64_t cap, char *errbuf, size_t errlen);
 uint64_t cbc_unpack_sam_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1);
+/* The same for the lines with CIGAR, NM and MD (cbc_gpu_decode_sam_cigar) and an arena of edits_per_read
+ * entries per read (0: CBC_EDITS_PER_READ): per block n_reads * (56 + len(RNAME) + 3 seq_stride + 16 edits_per_read); the proof
+ * stands at the function.  0 also for edits_per_read above CBC_EDITS_MAX. */
+uint64_t cbc_unpack_sam_cigar_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t edits_per_read);
 
 /* Coverage output (the text comes from cbc_gpu_decode_depth).  cbc_unpack_contig_blocks: the
  * selection of contig `contig` as a whole -- its blocks [b0, b1) (b0 == b1: the contig has none), beg = 1, end = its length,
