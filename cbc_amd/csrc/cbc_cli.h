@@ -28,6 +28,6 @@ int cbc_cli_decompress_bedcov(const char *in, const char *out, const char *ref, 
 int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                             const char *bed_path, uint32_t max_depth, uint32_t exclude, int verbose);
 int cbc_cli_decompress_stats(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
-                             const char *bed_path, uint32_t exclude, int verbose);
+                             const char *bed_path, uint32_t exclude, int alignment, uint32_t edits_per_read, int verbose);
 
 #endif

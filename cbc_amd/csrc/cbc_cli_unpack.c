@@ -787,9 +787,12 @@ int cbc_cli_decompress_hist(const char *in, const char *out, const char *ref, in
 /* `cbc -d|-x ... --stats [--region A ...] [--regions-file FILE] [--stats-exclude-flags N]`: the tables of a first look at the reads
  *  instead of the reads.  Without regions every block is decoded by the plain decoder; with them the
  * selected blocks of the target set by the span decoder, each selected read counted once.  One cbc_gpu_decode_stats; the tables
- * (about 270 KB) cross PCIe and cbc_stats_text makes the text. */
+ * (about 270 KB) cross PCIe and cbc_stats_text makes the text.
+ * alignment (--alignment): one cbc_gpu_decode_stats_aln instead -- the edits decoder against the
+ * container's span bound or the target set's, with an arena of edits_per_read entries per read (0: the default) -- and the
+ * sections of cbc_stats_aln_text behind the same text. */
 int cbc_cli_decompress_stats(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
-                             const char *bed_path, uint32_t exclude, int verbose)
+                             const char *bed_path, uint32_t exclude, int alignment, uint32_t edits_per_read, int verbose)
 {
     cli_run r;
     if (cli_open(&r, in, ref, bed_path, device, "--stats", "has no block index")) return 1;
@@ -803,22 +806,31 @@ int cbc_cli_decompress_stats(const char *in, const char *out, const char *ref, i
     const uint32_t nb = T ? T->n_blocks : u->n_blocks;
     cbc_dec_block_desc *bl; uint64_t *ws;
     cbc_gpu_stats *st = (cbc_gpu_stats *)calloc(1, sizeof *st);
-    const uint64_t cap = cbc_stats_text_cap();
-    char *text = (char *)malloc((size_t)cap);
-    if (!st || !text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+    cbc_gpu_stats_aln *al = (cbc_gpu_stats_aln *)calloc(1, sizeof *al);
+    const uint64_t cap = cbc_stats_text_cap(), acap = alignment ? cbc_stats_aln_text_cap() : 0u;
+    char *text = (char *)malloc((size_t)(cap + acap));
+    if (!st || !al || !text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
     if (cli_gather(u, T ? T->blocks : NULL, nb, &bl, &ws, NULL)) return 1;
     r.t1 = now2();
-    float ms[2] = { 0, 0 };
+    float ms[3] = { 0, 0, 0 };
     if (nb) {                                                /* else nothing runs: all-zero tables */
         if (cli_device(&r)) return 1;
         const double b = now2();
         const cbc_gpu_targets gt = { T ? (const uint32_t *)T->iv : NULL, T ? T->block_iv : NULL, T ? T->n_iv : 0u, T ? T->smax : 0u };
-        rc = cbc_gpu_decode_stats(r.ctx, u->payloads, u->payload_bytes, bl, nb, &u->caps, ws, T ? &gt : NULL, exclude, st, NULL);
+        if (alignment)
+            rc = cbc_gpu_decode_stats_aln(r.ctx, u->payloads, u->payload_bytes, bl, nb, &u->caps, ws, T ? &gt : NULL,
+                                          u->max_read_len + u->read_length - 1u, exclude, edits_per_read, st, al, NULL);
+        else rc = cbc_gpu_decode_stats(r.ctx, u->payloads, u->payload_bytes, bl, nb, &u->caps, ws, T ? &gt : NULL, exclude, st, NULL);
         if (rc) { fprintf(stderr, "cbc: statistics failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
         r.t_dev = now2() - b;
-        if (verbose) (void)cbc_gpu_last_stats_ms(r.ctx, &ms[0], &ms[1]);
+        if (verbose && alignment) (void)cbc_gpu_last_stats_aln_ms(r.ctx, &ms[0], &ms[1], &ms[2]);
+        else if (verbose) (void)cbc_gpu_last_stats_ms(r.ctx, &ms[0], &ms[1]);
     }
-    const int64_t n = cbc_stats_text(st, text, cap);
+    int64_t n = cbc_stats_text(st, text, cap);
+    if (n >= 0 && alignment) {
+        const int64_t m = cbc_stats_aln_text(al, text + n, acap);
+        n = m < 0 ? m : n + m;
+    }
     FILE *fo = n < 0 ? NULL : fopen(out, "wb");
     if (!fo || fwrite(text, 1, (size_t)n, fo) != (size_t)n || fclose(fo) != 0) return cannot_write(out);
     printf("statistics of %llu reads (%llu excluded) from %u of %u blocks\n", (unsigned long long)st->reads, (unsigned long long)st->excluded, nb, u->n_blocks);
@@ -827,9 +839,11 @@ int cbc_cli_decompress_stats(const char *in, const char *out, const char *ref, i
                       T->n_iv, nb, (unsigned long long)T->bed_unselected, exclude);
         else printf("stats: the whole file, exclude flags 0x%x\n", exclude);
         printf("time: read + plan + select %.3f s, device init + reference upload %.3f s, decode + statistics %.3f s\n", r.t1 - r.t0, r.t_init, r.t_dev);
-        if (r.used) printf("kernels: decode %.3f ms, statistics %.3f ms\n", ms[0], ms[1]);
+        if (alignment) printf("alignment: %llu reads, %llu without alignment\n", (unsigned long long)al->reads, (unsigned long long)al->invalid);
+        if (r.used && alignment) printf("kernels: edits decode %.3f ms, statistics %.3f ms, alignment %.3f ms\n", ms[0], ms[1], ms[2]);
+        else if (r.used) printf("kernels: decode %.3f ms, statistics %.3f ms\n", ms[0], ms[1]);
     }
-    free(text); free(st); free(bl); free(ws);
+    free(text); free(st); free(al); free(bl); free(ws);
     if (T) cbc_targets_free(T);
     cli_close(&r);
     return 0;

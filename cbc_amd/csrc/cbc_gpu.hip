@@ -30,6 +30,7 @@
 #include "cbc_stats_body.h"
 #include "cbc_pileup_body.h"
 #include "cbc_cigar_body.h"
+#include "cbc_stats_aln_body.h"
 #include "cbc_plan.h"
 #include "cbc_stream_body.h"
 #include "cbc_long_body.h"
@@ -259,6 +260,24 @@ cbc_stats_kernel(cbc_stats_args A) { cbc_stats_workgroup<false>(A); }
 __global__ void __launch_bounds__(64 * CBC_STATS_WAVES)
 cbc_targets_stats_kernel(cbc_stats_args A) { cbc_stats_workgroup<true>(A); }
 
+/* The alignment tables of the statistics (cbc_gpu_decode_stats_aln, cbc_stats_aln_body.h), behind the edits decode and the
+ * statistics kernel above: the same grid and workgroup shape over the same units, with its own count tables in LDS */
+template <bool TG>
+static __device__ __forceinline__ void cbc_stats_aln_workgroup(const cbc_stats_aln_args &A)
+{
+    __shared__ uint32_t tab[CBC_SALN_LDS];
+    const uint32_t wave = WaveGPU::uni(threadIdx.x >> 6);
+    cbc_stats_aln_zero<WaveGPU>(tab, wave, CBC_STATS_WAVES);
+    __syncthreads();
+    cbc_stats_aln_accum<WaveGPU, TG>(A, blockIdx.x, wave, CBC_STATS_WAVES, tab);
+    __syncthreads();
+    cbc_stats_aln_flush<WaveGPU>(A, tab, wave, CBC_STATS_WAVES);
+}
+__global__ void __launch_bounds__(64 * CBC_STATS_WAVES)
+cbc_stats_aln_kernel(cbc_stats_aln_args A) { cbc_stats_aln_workgroup<false>(A); }
+__global__ void __launch_bounds__(64 * CBC_STATS_WAVES)
+cbc_targets_stats_aln_kernel(cbc_stats_aln_args A) { cbc_stats_aln_workgroup<true>(A); }
+
 /* Whole-file stream / general-form fallback (cbc_stream_body.h): one wavefront per stream.  Workgroup w codes streams
  * w, w + gridDim, ... with var table w of the pool, which it re-zeroes between streams. */
 __global__ void __launch_bounds__(64)
@@ -414,14 +433,14 @@ cbc_checksum_kernel(const uint8_t *__restrict__ p, uint64_t n, unsigned long lon
 /* grow-only device buffer owned by the context: the host-buffer entry points keep their device arrays between calls
  * (a hipMalloc / hipFree pair per array and call cost more than the copies they framed: profiles/r02_final_pcie.log) */
 struct cbc_arena { void *p; uint64_t cap; };
-enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_XSTARTS, A_XTILE, A_XSP, A_XTHR, A_XPRE, A_XOUT, A_STATS, A_ESIDE, A_EARENA, A_PTAB, A_CIGAR, A_COUNT };
+enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A_CODES, A_RUNS, A_VS, A_IN, A_EXC_I, A_EXC_V, A_CNT, A_LSCR, A_STASH, A_GATHER, A_TEXT, A_RWS, A_RCNT, A_SNAMES, A_SBN, A_DDIFF, A_DTILE, A_DTOFF, A_DCP, A_DCTR, A_TIV, A_TBIV, A_TOFF, A_CVTILE, A_CVPRE, A_CVQ, A_CVOUT, A_HBINS, A_HTILE, A_HOUT, A_XSTARTS, A_XTILE, A_XSP, A_XTHR, A_XPRE, A_XOUT, A_STATS, A_ESIDE, A_EARENA, A_PTAB, A_CIGAR, A_SALN, A_COUNT };
 #define CBC_N_KSTREAMS 8           /* every chunk's launch on a stream of its own: launches of different chunks share the chip */
 
 /* what decode_blocks_impl runs behind the decode (its post-decode stage): nothing (plain, 2-bit, span, long reads), or the
  * stage of cbc_gpu_decode_region, _sam, _depth, _targets (reads, SAM, depth), _coverage, _depth_hist, _coverage_ext, _stats (whole
- * file, target set), _pileup, _sam_cigar */
+ * file, target set), _pileup, _sam_cigar, _stats_aln (whole file, target set) */
 enum post_kind { POST_NONE, POST_REGION, POST_SAM, POST_DEPTH, POST_TG_READS, POST_TG_SAM, POST_TG_DEPTH, POST_COV, POST_HIST, POST_COVX,
-                 POST_STATS, POST_TG_STATS, POST_COVQ, POST_PILEUP, POST_SAM_CIGAR };
+                 POST_STATS, POST_TG_STATS, POST_COVQ, POST_PILEUP, POST_SAM_CIGAR, POST_STATS_ALN, POST_TG_STATS_ALN };
 
 struct cbc_gpu_ctx {
     int device;
@@ -1123,8 +1142,10 @@ static bool post_is_cov(post_kind k) { return k == POST_COV || post_is_covx(k); 
 /* PILEUP shares the depth kinds' arenas, counters and text fetch; it has no change points and its text tiles are the position tiles */
 static bool post_is_depth(post_kind k) { return k == POST_DEPTH || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || k == POST_PILEUP; }
 static bool post_is_sam(post_kind k) { return k == POST_SAM || k == POST_TG_SAM || k == POST_SAM_CIGAR; }
-static bool post_is_targets(post_kind k) { return k == POST_TG_READS || k == POST_TG_SAM || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || k == POST_TG_STATS; }
-static bool post_is_stats(post_kind k) { return k == POST_STATS || k == POST_TG_STATS; }
+static bool post_is_targets(post_kind k) { return k == POST_TG_READS || k == POST_TG_SAM || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || k == POST_TG_STATS || k == POST_TG_STATS_ALN; }
+/* STATS_ALN is STATS behind the edits decoder with one more table and one more kernel */
+static bool post_is_stats_aln(post_kind k) { return k == POST_STATS_ALN || k == POST_TG_STATS_ALN; }
+static bool post_is_stats(post_kind k) { return k == POST_STATS || k == POST_TG_STATS || post_is_stats_aln(k); }
 
 /* the queries (n_q pairs slot, len in the compressed coordinate), the depth that counts as covered, where the results go */
 struct cov_req { const uint32_t *q; uint32_t n_q, min_depth; uint64_t *sum; uint32_t *covered;
@@ -1158,7 +1179,8 @@ struct post_req {
     hist_req hist;                 /* HIST */
     /* STATS, TG_STATS (with `exclude`): where the tables go, the record groups of the largest block */
     cbc_gpu_stats *stats; uint32_t stats_gmax;
-    /* edits_per_read > 0 (with smax > 0): the edit-reporting decoder.  SAM_CIGAR: nothing more; PILEUP: the line rule and the
+    cbc_gpu_stats_aln *stats_aln;  /* STATS_ALN, TG_STATS_ALN (with edits_per_read): where the alignment tables go */
+    /* edits_per_read > 0 (with smax > 0): the edit-reporting decoder.  SAM_CIGAR, STATS_ALN: nothing more; PILEUP: the line rule and the
      * contig's first reference byte; NONE (cbc_gpu_decode_blocks_edits): where the side array (2 words per record) and the arena go */
     uint32_t edits_per_read, min_alt; uint64_t ref_c0;
     uint32_t *edit_side; uint16_t *edit_arena;
@@ -1257,6 +1279,7 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
         NEED(A_HTILE, (uint64_t)z.n_btiles * sizeof(cbc_block_result) + ((uint64_t)z.n_btiles + 1) * 8, "hipMalloc histogram tiles");
     }
     if (post_is_stats(k)) NEED(A_STATS, (uint64_t)CBC_STATS_WORDS * 4, "hipMalloc statistics tables");
+    if (post_is_stats_aln(k)) NEED(A_SALN, (uint64_t)CBC_SALN_WORDS * 4, "hipMalloc alignment tables");
     if (k == POST_PILEUP && arena_need(ctx, A_PTAB, (uint64_t)z.n_tiles * CBC_DEPTH_TILE * 4 * CBC_PILEUP_PLANES, "hipMalloc pileup counters")) {
         (void)hipGetLastError();
         return set_err(ctx, CBC_E_NOMEM, "no device memory for the window's allele counters (28 bytes per position)", hipSuccess);
@@ -1620,21 +1643,36 @@ static int launch_stats(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, co
     const uint64_t units = (uint64_t)ra.n_blocks * sa.gmax, wgs = (units + CBC_STATS_WAVES - 1u) / CBC_STATS_WAVES;
     sa.grid = wgs < CBC_STATS_GRID ? (uint32_t)wgs : CBC_STATS_GRID;
     HIPCHK(hipMemsetAsync(sa.tab, 0, (uint64_t)CBC_STATS_WORDS * 4, ks), "memset statistics tables");
+    if (post_is_stats_aln(rg->kind)) HIPCHK(hipMemsetAsync(ctx->arena[A_SALN].p, 0, (uint64_t)CBC_SALN_WORDS * 4, ks), "memset alignment tables");
     if (sa.grid) {
-        if (rg->kind == POST_TG_STATS) {
+        if (post_is_targets(rg->kind)) {
             sa.iv = (const uint32_t *)ctx->arena[A_TIV].p; sa.block_iv = (const uint32_t *)ctx->arena[A_TBIV].p; sa.n_iv = rg->n_iv;
             hipLaunchKernelGGL(cbc_targets_stats_kernel, dim3(sa.grid), dim3(64 * CBC_STATS_WAVES), 0, ks, sa);
         } else hipLaunchKernelGGL(cbc_stats_kernel, dim3(sa.grid), dim3(64 * CBC_STATS_WAVES), 0, ks, sa);
         HIPCHK(hipGetLastError(), "launch cbc_stats_kernel");
     }
     HIPCHK(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
+    if (!post_is_stats_aln(rg->kind)) return CBC_OK;
+    /* the alignment pass over the same units: the side array and arena the edits decoder has left, the device reference */
+    cbc_stats_aln_args aa;
+    memset(&aa, 0, sizeof aa);
+    aa.S = sa; aa.tab = (uint32_t *)ctx->arena[A_SALN].p;
+    aa.side = (const uint32_t *)ctx->arena[A_ESIDE].p; aa.arena = (const uint16_t *)ctx->arena[A_EARENA].p;
+    aa.arena_entries = ra.n_recs * rg->edits_per_read; aa.per_read = rg->edits_per_read;
+    aa.ref = ctx->d_ref; aa.ref_bytes = ctx->ref_bytes;
+    if (sa.grid) {
+        if (post_is_targets(rg->kind)) hipLaunchKernelGGL(cbc_targets_stats_aln_kernel, dim3(sa.grid), dim3(64 * CBC_STATS_WAVES), 0, ks, aa);
+        else hipLaunchKernelGGL(cbc_stats_aln_kernel, dim3(sa.grid), dim3(64 * CBC_STATS_WAVES), 0, ks, aa);
+        HIPCHK(hipGetLastError(), "launch cbc_stats_aln_kernel");
+    }
+    HIPCHK(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
     return CBC_OK;
 }
 
 /* post stage, step 4: its results.  First the small ones, queued behind the block results and ahead of the call's one wait:
  * the counters, the size of the text or of the histogram, the coverage numbers. */
 struct post_got { uint32_t dctr[4]; uint64_t total, h_count; cbc_block_result *cnt; /* region / SAM / reads: the filter's per-block counts */
-                  uint32_t *stats; /* STATS: the device's tables, CBC_STATS_WORDS */ };
+                  uint32_t *stats; /* STATS: the device's tables, CBC_STATS_WORDS; STATS_ALN: CBC_SALN_WORDS more behind them */ };
 
 static int post_fetch_sizes(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z, uint32_t n_blocks, hipStream_t sc, post_got *g)
 {
@@ -1657,9 +1695,11 @@ static int post_fetch_sizes(cbc_gpu_ctx *ctx, const post_req *rg, const post_siz
         return CBC_OK;
     }
     if (post_is_stats(rg->kind)) {                             /* the tables are the output: about 270 KB, no second wait */
-        g->stats = (uint32_t *)malloc((size_t)CBC_STATS_WORDS * 4);
+        g->stats = (uint32_t *)malloc((size_t)(CBC_STATS_WORDS + CBC_SALN_WORDS) * 4);
         if (!g->stats) return CBC_E_NOMEM;
         HIPCHK(hipMemcpyAsync(g->stats, ctx->arena[A_STATS].p, (uint64_t)CBC_STATS_WORDS * 4, hipMemcpyDeviceToHost, sc), "D2H statistics tables");
+        if (post_is_stats_aln(rg->kind))
+            HIPCHK(hipMemcpyAsync(g->stats + CBC_STATS_WORDS, ctx->arena[A_SALN].p, (uint64_t)CBC_SALN_WORDS * 4, hipMemcpyDeviceToHost, sc), "D2H alignment tables");
         return CBC_OK;
     }
     g->cnt = (cbc_block_result *)malloc((size_t)n_blocks * sizeof(cbc_block_result));
@@ -1680,6 +1720,10 @@ static int post_fetch_output(cbc_gpu_ctx *ctx, const post_req *rg, const post_si
         for (uint32_t b = 0; b < n_blocks; b++) if (res[b].status != CBC_ST_OK) return CBC_OK;
         cbc_stats_finish(g->stats, rg->stats);
         *d2h_bytes = (uint64_t)CBC_STATS_WORDS * 4;
+        if (post_is_stats_aln(rg->kind)) {
+            cbc_stats_aln_finish(g->stats + CBC_STATS_WORDS, rg->stats_aln);
+            *d2h_bytes += (uint64_t)CBC_SALN_WORDS * 4;
+        }
         return CBC_OK;
     }
     if (depth) { kept = g->dctr[0]; *rg->n_runs = g->dctr[1]; }
@@ -1834,7 +1878,7 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                     rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
                     if (!rc) rc = launch_hist(ctx, ks, &rg->hist, z, da);
                     break;
-                case POST_STATS: case POST_TG_STATS: rc = launch_stats(ctx, ks, rg, ra); break;
+                case POST_STATS: case POST_TG_STATS: case POST_STATS_ALN: case POST_TG_STATS_ALN: rc = launch_stats(ctx, ks, rg, ra); break;
                 case POST_PILEUP: rc = launch_pileup(ctx, ks, rg, z, ra, n_recs); break;
                 case POST_SAM_CIGAR: rc = launch_sam_cigar_text(ctx, ks, rg, ra, n_recs); break;
                 }
@@ -2500,9 +2544,68 @@ API int cbc_gpu_decode_stats(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_by
 /* kernel times of the most recent cbc_gpu_decode_stats */
 API int cbc_gpu_last_stats_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *stats_ms)
 {
-    if (!ctx || !post_is_stats(ctx->last_post)) return CBC_E_ARG;
+    if (!ctx || !post_is_stats(ctx->last_post) || post_is_stats_aln(ctx->last_post)) return CBC_E_ARG;
     float *const out[] = { decode_ms, stats_ms };
     return last_ms(ctx, ctx->ev_rg, out, 2);
+}
+
+/* read statistics with the alignment tables: cbc_gpu_decode_stats behind the edits decoder, with the
+ * alignment pass (cbc_stats_aln_body.h) behind the statistics pass; both tables come back in the one small-results fetch */
+API int cbc_gpu_decode_stats_aln(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                 uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const cbc_gpu_targets *t,
+                                 uint32_t smax, uint32_t exclude_flags, uint32_t edits_per_read, cbc_gpu_stats *out,
+                                 cbc_gpu_stats_aln *aln, cbc_block_result *results)
+{
+    if (!ctx || !out || !aln) return CBC_E_ARG;
+    memset(out, 0, sizeof *out); memset(aln, 0, sizeof *aln);
+    if (!blocks || !caps || !window_start) return CBC_E_ARG;
+    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (n_blocks == 0) return CBC_OK;
+    if (!in || (t && (!t->iv || !t->block_iv))) return CBC_E_ARG;
+    if (t && (t->smax == 0 || t->n_iv == 0 || t->n_iv > (1u << 24)))
+        return set_err(ctx, CBC_E_ARG, "statistics of a target set want smax > 0 and 1 .. 2^24 intervals", hipSuccess);
+    if (!t && smax == 0) return set_err(ctx, CBC_E_ARG, "statistics with alignment tables want smax > 0 (the container's span bound)", hipSuccess);
+    if (edits_per_read == 0) edits_per_read = CBC_EDITS_PER_READ;
+    if (edits_per_read > CBC_EDITS_MAX) return set_err(ctx, CBC_E_ARG, "statistics with alignment tables want edits_per_read in 1..510 (0: the default)", hipSuccess);
+    for (uint32_t i = 0; t && i < t->n_iv; i++)
+        if (t->iv[2 * i] < 1 || t->iv[2 * i] > t->iv[2 * i + 1] || t->iv[2 * i + 1] > CBC_SAM_MAX_POS)
+            return set_err(ctx, CBC_E_ARG, "statistics: an interval is not 1 <= beg <= end <= 2^31 - 1", hipSuccess);
+    uint32_t most = 0;
+    for (uint32_t b = 0; b < n_blocks; b++) {
+        if (blocks[b].n_reads > most) most = blocks[b].n_reads;
+        if (!t) continue;
+        const uint32_t f = t->block_iv[2 * b], c = t->block_iv[2 * b + 1];
+        if (f > t->n_iv || c > t->n_iv - f) return set_err(ctx, CBC_E_ARG, "statistics: a block's interval range lies outside the table", hipSuccess);
+        if (window_start[b] > CBC_SAM_MAX_POS) return set_err(ctx, CBC_E_ARG, "statistics: a block starts past POS 2^31 - 1", hipSuccess);
+    }
+    /* the bound on a workgroup's run-length counts (cbc_stats_aln_body.h) */
+    if ((uint64_t)n_blocks * ((most + 63u) / 64u) > CBC_SALN_MAX_UNITS)
+        return set_err(ctx, CBC_E_ARG, "statistics with alignment tables: blocks x record groups of the largest block pass 2^29", hipSuccess);
+    block_layout L;
+    int rc = relayout_blocks(ctx, "statistics", in_bytes, blocks, n_blocks, NULL, &L);
+    if (rc) return rc;
+    if (L.nrec > 0xffffffffull) { layout_free(&L); return set_err(ctx, CBC_E_ARG, "statistics: more than 2^32 - 1 reads in one call", hipSuccess); }
+    if (L.nrec) {
+        uint64_t text_bytes = 0, n_sel = 0;
+        post_req rg;
+        post_req_init(&rg, t ? POST_TG_STATS_ALN : POST_STATS_ALN, t ? t->smax : smax, window_start, NULL, 0, 0, &text_bytes, &n_sel);
+        rg.beg = 1u; rg.end = UINT64_MAX;
+        if (t) { rg.iv = t->iv; rg.n_iv = t->n_iv; rg.block_iv = t->block_iv; }
+        rg.exclude = exclude_flags; rg.stats = out; rg.stats_gmax = (most + 63u) / 64u;
+        rg.stats_aln = aln; rg.edits_per_read = edits_per_read;
+        rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
+        if (rc) { memset(out, 0, sizeof *out); memset(aln, 0, sizeof *aln); }
+    }
+    layout_free(&L);
+    return rc;
+}
+
+/* kernel times of the most recent cbc_gpu_decode_stats_aln */
+API int cbc_gpu_last_stats_aln_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *stats_ms, float *aln_ms)
+{
+    if (!ctx || !post_is_stats_aln(ctx->last_post)) return CBC_E_ARG;
+    float *const out[] = { decode_ms, stats_ms, aln_ms };
+    return last_ms(ctx, ctx->ev_rg, out, 3);
 }
 
 /* kernel times of the most recent cbc_gpu_decode_depth_hist */

@@ -74,11 +74,15 @@ static void usage(const char *p)
             "                  A, C, G, T, other per sequencing cycle; the whole file, or the reads --region / --regions-file select,\n"
             "                  each once; counted on the device; not with --sam, --depth, --bedcov or --depth-hist)\n"
             "         --stats-exclude-flags N (with --stats: reads with FLAG & N != 0 are counted as excluded only; default 0)\n"
+            "         --alignment (with --stats: behind the same text, how the counted reads agree with the reference, in the view of\n"
+            "                  --sam --cigar: AS summary numbers with the mismatch rate, MC aligned bases and mismatches per cycle,\n"
+            "                  IC insertions and deletions per cycle, ID insertions and deletions per length, NM reads per edit\n"
+            "                  distance; takes --max-edits-per-read)\n"
             "         --pileup (what the reads show where they disagree with the reference, one line per such position:\n"
             "                   NAME, pos, ref, depth, A, C, G, T, N, del, ins; the whole file or one --region; counted on the device;\n"
             "                   with --depth-exclude-flags; not with --sam, --depth, --bedcov, --depth-hist or --stats)\n"
             "         --min-alt K (with --pileup: only positions with K or more non-reference observations; default 1)\n"
-            "         --max-edits-per-read N (with --pileup or --sam --cigar: deleted + inserted bases kept per read of a block, 1..510;\n"
+            "         --max-edits-per-read N (with --pileup, --sam --cigar or --stats --alignment: deleted + inserted bases kept per read of a block, 1..510;\n"
             "                  default 16)\n"
             "         --cigar (with --sam: CIGAR, NM:i and MD:Z on every line, in the codec's view of the alignment: M, I, D and S only,\n"
             "                  an insertion in front of a deletion at the same place, an inserted run at a read's end as S, a mismatch\n"
@@ -499,7 +503,7 @@ int main(int argc, char **argv)
     uint32_t pct[8], n_pct = 0;
     int depth_hist = 0, hist_max_given = 0;
     uint32_t hist_max = 0;
-    int stats_out = 0, stats_excl_given = 0;
+    int stats_out = 0, stats_excl_given = 0, stats_aln = 0;
     uint32_t stats_exclude = 0;
     int pileup = 0, min_alt_given = 0, max_edits_given = 0, sam_cigar = 0;
     uint32_t min_alt = 1, max_edits = 0;
@@ -563,6 +567,7 @@ int main(int argc, char **argv)
         }
         if (!strcmp(a, "--depth-hist")) { depth_hist = 1; continue; }
         if (!strcmp(a, "--stats")) { stats_out = 1; continue; }
+        if (!strcmp(a, "--alignment")) { stats_aln = 1; continue; }
         if (!strcmp(a, "--pileup")) { pileup = 1; continue; }
         if (!strcmp(a, "--min-alt") && i + 1 < argc) { if (!parse_count(a, argv[++i], 0xffffffffull, "a count in 1..4294967295", &n)) return 1; min_alt = (uint32_t)n; min_alt_given = 1; continue; }
         if (!strcmp(a, "--max-edits-per-read") && i + 1 < argc) { if (!parse_count(a, argv[++i], 510, "a number of deleted and inserted bases in 1..510", &n)) return 1; max_edits = (uint32_t)n; max_edits_given = 1; continue; }
@@ -616,9 +621,9 @@ int main(int argc, char **argv)
           window_given ? "--window" : min_depth_given ? "--min-depth" : thr_given ? "--thresholds" : count_reads ? "--count-reads" :
           quant_given ? "--quantiles" : NULL },
         { "--depth-hist", depth_hist, "--depth-hist, --bedcov, --depth and --sam are different outputs", hist_max_given ? "--hist-max" : NULL },
-        { "--stats", stats_out, "--stats, --depth-hist, --bedcov, --depth and --sam are different outputs", stats_excl_given ? "--stats-exclude-flags" : NULL },
+        { "--stats", stats_out, "--stats, --depth-hist, --bedcov, --depth and --sam are different outputs", stats_excl_given ? "--stats-exclude-flags" : stats_aln ? "--alignment" : NULL },
         { "--pileup", pileup, "--pileup, --stats, --depth-hist, --bedcov, --depth and --sam are different outputs",
-          min_alt_given ? "--min-alt" : max_edits_given && !sam_cigar ? "--max-edits-per-read" : NULL },
+          min_alt_given ? "--min-alt" : max_edits_given && !sam_cigar && !(stats_out && stats_aln) ? "--max-edits-per-read" : NULL },
     };
     for (size_t k = 0; k < sizeof opts / sizeof opts[0]; k++) {
         if (opts[k].owned && !opts[k].given) { fprintf(stderr, "cbc: %s applies to %s\n", opts[k].owned, opts[k].name); return 1; }
@@ -637,7 +642,7 @@ int main(int argc, char **argv)
     if (depth_hist)
         return cbc_cli_decompress_hist(files[0], files[1], files[2], device, regions, n_regions, regions_file, hist_max, depth_exclude, verbose);
     if (depth_excl_given && !depth_out && !bedcov && !pileup) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
-    if (stats_out) return cbc_cli_decompress_stats(files[0], files[1], files[2], device, regions, n_regions, regions_file, stats_exclude, verbose);
+    if (stats_out) return cbc_cli_decompress_stats(files[0], files[1], files[2], device, regions, n_regions, regions_file, stats_exclude, stats_aln, max_edits, verbose);
     if (bedcov)                                                   /* no --thresholds, --count-reads, --quantiles: the plain summary */
         return cbc_cli_decompress_bedcov(files[0], files[1], files[2], device, regions, n_regions, regions_file, cov_window, cov_min_depth,
                                          depth_exclude, verbose, thr, n_thr, count_reads, pct, n_pct);

@@ -2286,6 +2286,45 @@ API int64_t cbc_stats_text(const cbc_gpu_stats *s, char *dst, uint64_t cap)
     return (int64_t)(p - dst);
 }
 
+/* ---- alignment tables of the read statistics (include/cbc_host.h) ---- */
+API uint64_t cbc_stats_aln_text_cap(void)
+{
+    /* per line: the tag and its tab, the longest name or key, a tab and the longest number per column, the newline */
+    return 11u * (3u + 23u + 1u + 21u + 1u) + (CBC_STATS_ALN_CYC - 1u) * (3u + 3u + 2u * (1u + 20u) + 1u) + CBC_STATS_ALN_CYC * (3u + 3u + 2u * (1u + 10u) + 1u) +
+           (CBC_STATS_ALN_LEN - 1u) * (3u + 3u + 2u * (1u + 20u) + 1u) + CBC_STATS_ALN_NM * (3u + 3u + 1u + 10u + 1u);
+}
+
+API int64_t cbc_stats_aln_text(const cbc_gpu_stats_aln *a, char *dst, uint64_t cap)
+{
+    if (!a || !dst || cap < cbc_stats_aln_text_cap()) return CBC_E_ARG;
+    char *p = dst;
+    uint64_t aligned[CBC_STATS_ALN_CYC], al = 0, mm = 0, unal = 0, ins = 0, del = 0, bi = 0, bd = 0, reach = 0;
+    uint32_t lmax = 0;
+    for (uint32_t l = 1; l < CBC_STATS_ALN_CYC; l++) { reach += a->len[l]; if (a->len[l]) lmax = l; }
+    aligned[0] = 0;
+    for (uint32_t c = 1; c < CBC_STATS_ALN_CYC; c++) {               /* reach: the valid reads of length >= c */
+        aligned[c] = reach - a->unal[c];
+        al += aligned[c]; mm += a->mm[c]; unal += a->unal[c];
+        reach -= a->len[c];
+    }
+    for (uint32_t l = 1; l < CBC_STATS_ALN_LEN; l++) {
+        ins += a->ins_len[l]; del += a->del_len[l]; bi += (uint64_t)l * a->ins_len[l]; bd += (uint64_t)l * a->del_len[l];
+    }
+    char rate[40];
+    (void)cbc_hist_fraction(mm, al, rate);
+    p += sprintf(p, "AS\treads\t%llu\nAS\treads without alignment\t%llu\nAS\tbases aligned\t%llu\nAS\tmismatches\t%llu\nAS\tmismatch rate\t%s\n",
+                 (unsigned long long)a->reads, (unsigned long long)a->invalid, (unsigned long long)al, (unsigned long long)mm, rate);
+    p += sprintf(p, "AS\tinsertions\t%llu\nAS\tdeletions\t%llu\nAS\tbases inserted\t%llu\nAS\tbases deleted\t%llu\nAS\tbases soft-clipped\t%llu\n",
+                 (unsigned long long)ins, (unsigned long long)del, (unsigned long long)bi, (unsigned long long)bd, (unsigned long long)(unal - bi));
+    p += sprintf(p, "AS\treads with NM 0\t%u\n", a->nm[0]);
+    for (uint32_t c = 1; c <= lmax; c++) p += sprintf(p, "MC\t%u\t%llu\t%u\n", c, (unsigned long long)aligned[c], a->mm[c]);
+    for (uint32_t c = 0; c < CBC_STATS_ALN_CYC; c++) if (a->ins_cyc[c] | a->del_cyc[c]) p += sprintf(p, "IC\t%u\t%u\t%u\n", c, a->ins_cyc[c], a->del_cyc[c]);
+    for (uint32_t l = 1; l < CBC_STATS_ALN_LEN; l++)
+        if (a->ins_len[l] | a->del_len[l]) p += sprintf(p, "ID\t%u\t%llu\t%llu\n", l, (unsigned long long)a->ins_len[l], (unsigned long long)a->del_len[l]);
+    for (uint32_t n = 0; n < CBC_STATS_ALN_NM; n++) if (a->nm[n]) p += sprintf(p, "NM\t%u\t%u\n", n, a->nm[n]);
+    return (int64_t)(p - dst);
+}
+
 /* ---- depth histogram (include/cbc_host.h) ---- */
 API uint64_t cbc_unpack_targets_size(const cbc_targets *t, uint32_t contig)
 {

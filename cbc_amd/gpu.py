@@ -282,6 +282,12 @@ def lib():
                                            ctypes.POINTER(host.GpuStats), ctypes.c_void_p]
         L.cbc_gpu_last_stats_ms.restype = ctypes.c_int
         L.cbc_gpu_last_stats_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 2
+        L.cbc_gpu_decode_stats_aln.restype = ctypes.c_int
+        L.cbc_gpu_decode_stats_aln.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.cbc_gpu_last_stats_aln_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_stats_aln_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 3
         L.cbc_gpu_last_depth_ms.restype = ctypes.c_int
         L.cbc_gpu_last_depth_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         L.cbc_gpu_decode_pileup.restype = ctypes.c_int
@@ -319,7 +325,7 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_decode_blocks_span", "cbc_gpu_last_region_ms", "cbc_gpu_decode_sam", "cbc_gpu_last_sam_ms",
            "cbc_gpu_decode_depth", "cbc_gpu_last_depth_ms", "cbc_gpu_decode_targets", "cbc_gpu_last_targets_ms",
            "cbc_gpu_decode_coverage", "cbc_gpu_last_coverage_ms", "cbc_gpu_decode_depth_hist", "cbc_gpu_last_hist_ms", "cbc_gpu_decode_stats",
-           "cbc_gpu_last_stats_ms",
+           "cbc_gpu_last_stats_ms", "cbc_gpu_decode_stats_aln", "cbc_gpu_last_stats_aln_ms",
            "cbc_gpu_decode_coverage_ext", "cbc_gpu_last_coverage_ext_ms",
            "cbc_gpu_decode_coverage_quant", "cbc_gpu_last_coverage_quant_ms",
            "cbc_gpu_decode_pileup", "cbc_gpu_last_pileup_ms", "cbc_gpu_decode_blocks_edits",
@@ -1018,6 +1024,51 @@ class Encoder:
                    len=np.ctypeslib.as_array(st.len).copy(), gc=np.ctypeslib.as_array(st.gc).copy(),
                    cyc=np.ctypeslib.as_array(st.cyc).copy().reshape(5, 256))
         return (out, res) if results else out
+
+    def decode_stats_aln(self, plan: "host.UnpackPlan", targets=None, exclude_flags=0, edits_per_read=None, results=False):
+        """Read statistics with the alignment tables (cbc_gpu_decode_stats_aln): decode_stats behind the edit-reporting decoder and
+        one more pass that counts how the counted reads agree with the reference, in the view of decode_sam(cigar=True).  Returns
+        (the dict of decode_stats, the alignment dict): reads, invalid (int), len, mm, unal, ins_cyc, del_cyc (257,), nm (767,)
+        uint32 and ins_len, del_len (256,) uint64 -- the cycle tables indexed by the 1-based sequencing cycle.  edits_per_read as
+        for decode_pileup (None: the default).  A selection without blocks runs nothing and gives all-zero tables.  With
+        results=True returns (stats, aln, the per-block decode results) and lets a failed block pass (all tables zero then);
+        otherwise it raises CbcGpuError."""
+        plan.sam_header()
+        if not 0 <= int(exclude_flags) <= 0xffff:
+            raise ValueError("exclude_flags is a FLAG mask in 0 .. 65535")
+        per_read = 0 if edits_per_read is None else int(edits_per_read)
+        if edits_per_read is not None and not 1 <= per_read <= 510:
+            raise ValueError("edits_per_read is in 1 .. 510")
+        self._stats_aln_ms = None
+        st, al = host.GpuStats(), host.GpuStatsAln()
+        nb = plan.n_blocks if targets is None else len(targets.blocks)
+        res = np.zeros(nb, dtype=host.RESULT_DTYPE)
+        if nb:
+            caps, pay, _, _ = self._plan_args(plan)
+            tg = None
+            if targets is None:
+                blocks, ws, _ = self._gather(plan, slice(0, nb))
+            else:
+                blocks, ws, _, biv = self._gather(plan, targets.blocks, targets.block_iv)
+                iv = np.ascontiguousarray(targets.iv, dtype=np.uint32)
+                tg = GpuTargets(iv.ctypes.data, biv.ctypes.data, targets.n_iv, targets.smax)
+            rc = lib().cbc_gpu_decode_stats_aln(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
+                                                ws.ctypes.data, ctypes.byref(tg) if tg is not None else None,
+                                                plan.max_read_len + plan.read_length - 1, int(exclude_flags), per_read,
+                                                ctypes.byref(st), ctypes.byref(al), res.ctypes.data)
+            self._check_blocks(rc, "cbc_gpu_decode_stats_aln", results)
+            self._add_ms("_stats_aln_ms", "cbc_gpu_last_stats_aln_ms", 3)
+        out = dict(reads=int(st.reads), excluded=int(st.excluded), flag=np.ctypeslib.as_array(st.flag).copy(),
+                   len=np.ctypeslib.as_array(st.len).copy(), gc=np.ctypeslib.as_array(st.gc).copy(),
+                   cyc=np.ctypeslib.as_array(st.cyc).copy().reshape(5, 256))
+        aln = host.stats_aln_dict(al)
+        return (out, aln, res) if results else (out, aln)
+
+    def last_stats_aln_ms(self):
+        """(edits decode, zeroing + statistics pass, alignment pass) kernel milliseconds of the last decode_stats_aln."""
+        if getattr(self, "_stats_aln_ms", None) is None:
+            raise CbcGpuError("no decode_stats_aln has run on the device")
+        return self._stats_aln_ms
 
     def last_stats_ms(self):
         """(decode, zeroing + statistics pass) kernel milliseconds of the last decode_stats."""

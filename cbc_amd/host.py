@@ -235,6 +235,10 @@ def lib():
         L.cbc_stats_text_cap.argtypes = []
         L.cbc_stats_text.restype = ctypes.c_int64
         L.cbc_stats_text.argtypes = [ctypes.POINTER(GpuStats), ctypes.c_char_p, ctypes.c_uint64]
+        L.cbc_stats_aln_text_cap.restype = ctypes.c_uint64
+        L.cbc_stats_aln_text_cap.argtypes = []
+        L.cbc_stats_aln_text.restype = ctypes.c_int64
+        L.cbc_stats_aln_text.argtypes = [ctypes.POINTER(GpuStatsAln), ctypes.c_char_p, ctypes.c_uint64]
         _lib = L
     return _lib
 
@@ -262,6 +266,46 @@ def stats_text(stats) -> bytes:
     n = lib().cbc_stats_text(ctypes.byref(stats), buf, cap)
     if n < 0:
         raise ValueError("cbc_stats_text failed (%d)" % n)
+    return buf.raw[:n]
+
+
+class GpuStatsAln(ctypes.Structure):
+    """cbc_gpu_stats_aln (include/cbc_gpu.h): the alignment tables of cbc_gpu_decode_stats_aln."""
+    _fields_ = [("reads", ctypes.c_uint64), ("invalid", ctypes.c_uint64), ("len", ctypes.c_uint32 * 257), ("mm", ctypes.c_uint32 * 257),
+                ("unal", ctypes.c_uint32 * 257), ("ins_cyc", ctypes.c_uint32 * 257), ("del_cyc", ctypes.c_uint32 * 257),
+                ("nm", ctypes.c_uint32 * 767), ("ins_len", ctypes.c_uint64 * 256), ("del_len", ctypes.c_uint64 * 256)]
+
+
+STATS_ALN_TABLES = (("len", 257, np.uint32), ("mm", 257, np.uint32), ("unal", 257, np.uint32), ("ins_cyc", 257, np.uint32),
+                    ("del_cyc", 257, np.uint32), ("nm", 767, np.uint32), ("ins_len", 256, np.uint64), ("del_len", 256, np.uint64))
+
+
+def stats_aln_dict(st: "GpuStatsAln") -> dict:
+    """A GpuStatsAln as the dict Encoder.decode_stats_aln returns: reads, invalid (int) and the tables as arrays."""
+    out = dict(reads=int(st.reads), invalid=int(st.invalid))
+    for name, _, _ in STATS_ALN_TABLES:
+        out[name] = np.ctypeslib.as_array(getattr(st, name)).copy()
+    return out
+
+
+def stats_aln_text(aln) -> bytes:
+    """The sections `cbc -x --stats --alignment` writes behind the text of stats_text (cbc_stats_aln_text).  aln: the second dict
+    of Encoder.decode_stats_aln -- reads, invalid, len, mm, unal, ins_cyc, del_cyc (257), nm (767), ins_len, del_len (256, 64
+    bits) -- or a GpuStatsAln."""
+    if not isinstance(aln, GpuStatsAln):
+        st = GpuStatsAln()
+        st.reads, st.invalid = int(aln["reads"]), int(aln["invalid"])
+        for name, n, dt in STATS_ALN_TABLES:
+            a = np.ascontiguousarray(aln[name], dtype=dt).reshape(-1)
+            if a.size != n:
+                raise ValueError("aln[%r] wants %d counters" % (name, n))
+            ctypes.memmove(getattr(st, name), a.ctypes.data, a.nbytes)
+        aln = st
+    cap = int(lib().cbc_stats_aln_text_cap())
+    buf = ctypes.create_string_buffer(cap)
+    n = lib().cbc_stats_aln_text(ctypes.byref(aln), buf, cap)
+    if n < 0:
+        raise ValueError("cbc_stats_aln_text failed (%d)" % n)
     return buf.raw[:n]
 
 

@@ -603,6 +603,45 @@ int  cbc_gpu_decode_stats(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes
 /* Kernel times of the most recent cbc_gpu_decode_stats: the decode; zeroing the tables + the statistics pass. */
 int  cbc_gpu_last_stats_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *stats_ms);
 
+/* ---- read statistics with the alignment tables --------------------------------------------------------
+ * cbc_gpu_decode_stats behind the edit-reporting decoder (cbc_gpu_decode_blocks_edits), with one more pass that counts how the
+ * reads agree with the reference.  *out is what cbc_gpu_decode_stats returns for the same selection.  The alignment is that of
+ * cbc_gpu_decode_sam_cigar above: its element order, its S rule (an inserted run with no aligned base before it, or none after
+ * it, in the read), its mismatch (a plain byte compare of the aligned read byte with the uploaded reference byte) and its valid
+ * record; a counted read -- kept and not excluded -- that cbc_gpu_decode_sam_cigar would write with CIGAR '*' is counted in
+ * `invalid` and in no table below.  The cycle of read index q is q + 1 for FLAG & 16 == 0, else rl - q (1-based, the
+ * orientation of cbc_gpu_stats.cyc).
+ *   reads, invalid   the counted reads that are valid, and those that are not; reads = the sum of len[]
+ *   len[l]           valid counted reads of length l
+ *   mm[c]            mismatches in cycle c
+ *   unal[c]          inserted bases (I and S) in cycle c: the aligned bases of cycle c are the reads of length >= c less unal[c]
+ *   ins_cyc[c]       I runs whose first-sequenced base has cycle c: index q0 + 1 forward, rl - q1 reverse for a run over q0 .. q1
+ *   del_cyc[c]       D runs behind the base of cycle c: with k the read index of the aligned base behind the run (rl for the
+ *                    run that ends the read), c = k forward and rl - k reverse; c = 0 is in front of the first sequenced base
+ *   nm[n]            reads with NM = mismatches + I bases + D bases = n, the NM:i: of cbc_gpu_decode_sam_cigar
+ *   ins_len[l], del_len[l]   I runs and D runs of l bases
+ * Index 0 of the cycle tables is used by del_cyc alone.  smax > 0 is the span bound the decoder checks (t == NULL; otherwise
+ * t->smax); edits_per_read sizes the arena as for cbc_gpu_decode_pileup (CBC_ST_EDITS).  Every 32-bit counter is bounded by the
+ * reads of the call (2^32 - 1 at most, as for cbc_gpu_decode_stats); ins_len and del_len are exact in 64 bits; a call whose
+ * blocks x record groups of the largest block pass 2^29 is CBC_E_ARG.  One call, one chunk, one stream, no host round trip
+ * between the kernels.  A failed block contributes nothing; the call returns CBC_E_BLOCK with both structs all zero. */
+#define CBC_STATS_ALN_CYC 257u
+#define CBC_STATS_ALN_NM  767u
+#define CBC_STATS_ALN_LEN 256u
+typedef struct cbc_gpu_stats_aln {
+    uint64_t reads, invalid;
+    uint32_t len[CBC_STATS_ALN_CYC], mm[CBC_STATS_ALN_CYC], unal[CBC_STATS_ALN_CYC], ins_cyc[CBC_STATS_ALN_CYC], del_cyc[CBC_STATS_ALN_CYC];
+    uint32_t nm[CBC_STATS_ALN_NM];
+    uint64_t ins_len[CBC_STATS_ALN_LEN], del_len[CBC_STATS_ALN_LEN];
+} cbc_gpu_stats_aln;
+int  cbc_gpu_decode_stats_aln(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                              uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                              const cbc_gpu_targets *t /* or NULL */, uint32_t smax, uint32_t exclude_flags, uint32_t edits_per_read,
+                              cbc_gpu_stats *out, cbc_gpu_stats_aln *aln, cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_stats_aln: the edits decode; zeroing the tables + the statistics pass; the
+ * alignment pass. */
+int  cbc_gpu_last_stats_aln_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *stats_ms, float *aln_ms);
+
 /* ---- whole-file stream ("compat" mode): the reference's own file format --------------------------------------
  * compress() / decompress(), src/compression.c:112-216: ONE arithmetic stream per file, models never reset.
  * `batch` is a cbc_host_batch packed with cbc_pack_opts.whole_file = 1: its `blocks` are SEGMENTS of the one

@@ -330,6 +330,19 @@ int      cbc_hist_fraction(uint64_t bases, uint64_t size, char *dst);
 uint64_t cbc_stats_text_cap(void);
 int64_t  cbc_stats_text(const cbc_gpu_stats *s, char *dst, uint64_t cap);
 
+/* The alignment tables of the read statistics (the tables come from cbc_gpu_decode_stats_aln).
+ * cbc_stats_aln_text writes the sections `cbc -x --stats --alignment` appends to the text of cbc_stats_text, tab-separated, in
+ * this order: 11 AS lines (reads, reads without alignment, bases aligned, mismatches, mismatch rate, insertions, deletions,
+ * bases inserted, bases deleted, bases soft-clipped, reads with NM 0), one MC line `cycle, aligned, mismatches` per cycle
+ * 1 .. the longest counted valid read, one IC line `cycle, insertions, deletions` per cycle 0 .. 256 where either is non-zero,
+ * one ID line `length, insertions, deletions` per length 1 .. 255 where either is non-zero, one NM line `value, reads` per value
+ * that occurs.  Every number is an integer derived from the tables in 64 bits -- aligned[c] = the reads of length >= c less
+ * unal[c], bases soft-clipped = the sum of unal[] less bases inserted -- except the mismatch rate, which is
+ * cbc_hist_fraction(mismatches, bases aligned).  Returns the bytes written, or CBC_E_ARG when cap is below
+ * cbc_stats_aln_text_cap(). */
+uint64_t cbc_stats_aln_text_cap(void);
+int64_t  cbc_stats_aln_text(const cbc_gpu_stats_aln *a, char *dst, uint64_t cap);
+
 int     cbc_unpack_plan_create(const uint8_t *blob, uint64_t len, const char *fasta, size_t fasta_len,
                                cbc_unpack_plan **out, char *errbuf, size_t errlen);
 void    cbc_unpack_plan_free(cbc_unpack_plan *u);
