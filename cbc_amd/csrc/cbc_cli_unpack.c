@@ -159,7 +159,7 @@ int cbc_cli_decompress(const char *in, const char *out, const char *ref, const i
     return 0;
 }
 
-/* ---- the decode modes that write something other than every read (DESIGN.md sections 4.10 - 4.18).  The steps they share are
+/* ---- the decode modes that write something other than every read (DESIGN.md sections 4.10 - 4.22).  The steps they share are
  * written once, cli_open .. cli_close; each mode function below is what it selects, its call loop and what it prints. ---- */
 static double now2(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
@@ -359,81 +359,25 @@ int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int
 
 /* `cbc -d|-x ... --depth [--region NAME[:BEG[-END]]]`: the coverage of the reads instead of the reads,
  * bedGraph computed and formatted on the device (cbc_gpu_decode_depth): one call for the region's window, or one per contig
- * that has blocks, in the order of the contig table, the texts appended.  Only the track crosses PCIe. */
-int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude, int verbose)
-{
-    cli_run r;
-    if (cli_open(&r, in, ref, NULL, device, "--depth", "stores no contig table")) return 1;
-    const cbc_unpack_plan *u = r.u;
-    char err[512];
-    /* what SAM output refuses, depth refuses: a long-read container, names and lengths the text cannot carry */
-    if (cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) < 0) { fprintf(stderr, "cbc: --depth: %s\n", err[0] ? err : "the contig table is not usable"); return 1; }
-    /* the calls: the region's selection, or every contig as a whole */
-    const uint32_t n_calls = region ? 1u : u->n_contigs;
-    cbc_region_sel *sels = (cbc_region_sel *)calloc(n_calls ? n_calls : 1u, sizeof(cbc_region_sel));
-    if (!sels) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    uint64_t max_cap = 0;
-    int rc;
-    for (uint32_t k = 0; k < n_calls; k++) {
-        rc = region ? cbc_unpack_region(u, region, &sels[k], err, sizeof err) : cbc_unpack_contig_blocks(u, k, &sels[k], err, sizeof err);
-        if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT ? err : "block selection failed"); return 1; }
-        const uint64_t c = cbc_unpack_depth_text_cap(u, sels[k].b0, sels[k].b1, sels[k].contig);
-        if (c > max_cap) max_cap = c;
-    }
-    r.t1 = now2();
-    FILE *fo = fopen(out, "wb");
-    if (!fo) return cannot_write(out);
-    char *text = (char *)malloc((size_t)max_cap + 1);
-    if (!text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-    uint64_t total = 0, runs = 0, kept = 0;
-    uint32_t blocks_used = 0;
-    float ms[4] = { 0, 0, 0, 0 }, m[4];
-    for (uint32_t k = 0; k < n_calls; k++) {
-        const cbc_region_sel *s = &sels[k];
-        const uint32_t nb = s->b1 - s->b0;
-        if (!nb) continue;                              /* no block can hold a read of the window: no line, no device needed */
-        if (cli_device(&r)) return 1;
-        const double b = now2();
-        const char *nm = u->names + u->contig_name_off[s->contig];
-        uint64_t tb = 0, nr = 0, nk = 0;
-        rc = cbc_gpu_decode_depth(r.ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
-                                  nm, (uint32_t)strlen(nm), s->beg, s->end, s->smax, exclude, (uint8_t *)text,
-                                  cbc_unpack_depth_text_cap(u, s->b0, s->b1, s->contig), &tb, &nr, &nk, NULL);
-        if (rc) { fprintf(stderr, "cbc: depth failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
-        r.t_dev += now2() - b;
-        if (verbose && cbc_gpu_last_depth_ms(r.ctx, &m[0], &m[1], &m[2], &m[3]) == 0) add_ms(ms, m, 4);
-        if (tb && fwrite(text, 1, (size_t)tb, fo) != (size_t)tb) return cannot_write(out);
-        total += tb; runs += nr; kept += nk; blocks_used += nb;
-    }
-    if (fclose(fo) != 0) return cannot_write(out);
-    if (region)
-        printf("depth of %s:%llu-%llu: %llu runs from %llu reads in %u of %u blocks\n", u->names + u->contig_name_off[sels[0].contig],
-               (unsigned long long)sels[0].beg, (unsigned long long)sels[0].end, (unsigned long long)runs, (unsigned long long)kept,
-               blocks_used, u->n_blocks);
-    else printf("depth: %llu runs from %llu reads in %u blocks\n", (unsigned long long)runs, (unsigned long long)kept, blocks_used);
-    if (verbose) {
-        printf("depth: %llu text bytes, exclude flags 0x%x\n", (unsigned long long)total, exclude);
-        printf("time: read + plan %.3f s, device init + reference upload %.3f s, decode + depth + write %.3f s\n", r.t1 - r.t0, r.t_init, r.t_dev);
-        if (r.used) printf("kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
-    }
-    free(text); free(sels);
-    cli_close(&r);
-    return 0;
-}
+ * that has blocks, in the order of the contig table, the texts appended.  Only the track crosses PCIe.  A call's buffer is the
+ * bound of its blocks.
+ * pu != NULL, `--pileup`: what the reads show at the positions where they disagree with the reference,
+ * counted and formatted on the device (cbc_gpu_decode_pileup), the calls as for --depth.  A call starts with a buffer of 64 MiB
+ * + 64 bytes per read of its blocks (or the bound, if that is less); the library reports the size of a text that does not fit,
+ * and the call is made once more with exactly that. */
+typedef struct cli_pileup { uint32_t min_alt, edits_per_read; } cli_pileup;
 
-/* `cbc -d|-x ... --pileup [--region NAME[:BEG[-END]]]`: what the reads show at the positions where they disagree with the
- * reference, counted and formatted on the device (cbc_gpu_decode_pileup): one call for the region's
- * window, or one per contig that has blocks, in the order of the contig table, the texts appended.  Only the lines cross PCIe.
- * A call starts with a buffer of 64 MiB + 64 bytes per read of its blocks (or the bound, if that is less); the library reports
- * the size of a text that does not fit, and the call is made once more with exactly that. */
-int cbc_cli_decompress_pileup(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,
-                              uint32_t min_alt, uint32_t edits_per_read, int verbose)
+static int decompress_window(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,
+                             const cli_pileup *pu, int verbose)
 {
+    const char *opt = pu ? "--pileup" : "--depth", *mode = opt + 2, *noun = pu ? "positions" : "runs";
     cli_run r;
-    if (cli_open(&r, in, ref, NULL, device, "--pileup", "stores no contig table")) return 1;
+    if (cli_open(&r, in, ref, NULL, device, opt, "stores no contig table")) return 1;
     const cbc_unpack_plan *u = r.u;
     char err[512];
-    if (cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) < 0) { fprintf(stderr, "cbc: --pileup: %s\n", err[0] ? err : "the contig table is not usable"); return 1; }
+    /* what SAM output refuses, these refuse: a long-read container, names and lengths the text cannot carry */
+    if (cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) < 0) { fprintf(stderr, "cbc: %s: %s\n", opt, err[0] ? err : "the contig table is not usable"); return 1; }
+    /* the calls: the region's selection, or every contig as a whole */
     const uint32_t n_calls = region ? 1u : u->n_contigs;
     cbc_region_sel *sels = (cbc_region_sel *)calloc(n_calls ? n_calls : 1u, sizeof(cbc_region_sel));
     if (!sels) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
@@ -456,40 +400,56 @@ int cbc_cli_decompress_pileup(const char *in, const char *out, const char *ref, 
         if (cli_device(&r)) return 1;
         const double b = now2();
         const char *nm = u->names + u->contig_name_off[s->contig];
-        const uint64_t bound = cbc_unpack_pileup_text_cap(u, s->b0, s->b1, s->contig, s->beg, s->end, s->smax);
-        uint64_t first = 64ull << 20, tb = 0, nl = 0, nk = 0;
+        const uint64_t bound = pu ? cbc_unpack_pileup_text_cap(u, s->b0, s->b1, s->contig, s->beg, s->end, s->smax)
+                                  : cbc_unpack_depth_text_cap(u, s->b0, s->b1, s->contig);
+        uint64_t cap = bound, first = 64ull << 20, tb = 0, nl = 0, nk = 0;
         for (uint32_t q = s->b0; q < s->b1; q++) first += 64ull * u->blocks[q].n_reads;
-        uint64_t cap = bound < first ? bound : first;
-        for (int attempt = 0; attempt < 2; attempt++) {
-            if (cap > have) { free(text); text = (char *)malloc((size_t)cap + 1); have = cap; }
+        if (pu && first < cap) cap = first;
+        for (int attempt = 0; attempt < (pu ? 2 : 1); attempt++) {
+            if (cap > have || !text) { free(text); text = (char *)malloc((size_t)cap + 1); have = cap; }
             if (!text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-            rc = cbc_gpu_decode_pileup(r.ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
-                                       nm, (uint32_t)strlen(nm), s->beg, s->end, s->smax, exclude, min_alt, edits_per_read,
-                                       (uint8_t *)text, cap, &tb, &nl, &nk, NULL);
+            rc = pu ? cbc_gpu_decode_pileup(r.ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
+                                            nm, (uint32_t)strlen(nm), s->beg, s->end, s->smax, exclude, pu->min_alt, pu->edits_per_read,
+                                            (uint8_t *)text, cap, &tb, &nl, &nk, NULL)
+                    : cbc_gpu_decode_depth(r.ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
+                                           nm, (uint32_t)strlen(nm), s->beg, s->end, s->smax, exclude, (uint8_t *)text, cap, &tb, &nl, &nk, NULL);
             if (!(rc == CBC_E_ARG && tb > cap && tb <= bound)) break;
             cap = tb;                                   /* the text's own size */
         }
-        if (rc) { fprintf(stderr, "cbc: pileup failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
+        if (rc) { fprintf(stderr, "cbc: %s failed: %s\n", mode, cbc_gpu_last_error(r.ctx)); return 1; }
         r.t_dev += now2() - b;
-        if (verbose && cbc_gpu_last_pileup_ms(r.ctx, &m[0], &m[1], &m[2], &m[3]) == 0) add_ms(ms, m, 4);
+        if (verbose && (pu ? cbc_gpu_last_pileup_ms : cbc_gpu_last_depth_ms)(r.ctx, &m[0], &m[1], &m[2], &m[3]) == 0) add_ms(ms, m, 4);
         if (tb && fwrite(text, 1, (size_t)tb, fo) != (size_t)tb) return cannot_write(out);
         total += tb; lines += nl; kept += nk; blocks_used += nb;
     }
     if (fclose(fo) != 0) return cannot_write(out);
     if (region)
-        printf("pileup of %s:%llu-%llu: %llu positions from %llu reads in %u of %u blocks\n", u->names + u->contig_name_off[sels[0].contig],
-               (unsigned long long)sels[0].beg, (unsigned long long)sels[0].end, (unsigned long long)lines, (unsigned long long)kept,
+        printf("%s of %s:%llu-%llu: %llu %s from %llu reads in %u of %u blocks\n", mode, u->names + u->contig_name_off[sels[0].contig],
+               (unsigned long long)sels[0].beg, (unsigned long long)sels[0].end, (unsigned long long)lines, noun, (unsigned long long)kept,
                blocks_used, u->n_blocks);
-    else printf("pileup: %llu positions from %llu reads in %u blocks\n", (unsigned long long)lines, (unsigned long long)kept, blocks_used);
+    else printf("%s: %llu %s from %llu reads in %u blocks\n", mode, (unsigned long long)lines, noun, (unsigned long long)kept, blocks_used);
     if (verbose) {
-        printf("pileup: %llu text bytes, exclude flags 0x%x, min alt %u, edits per read %u\n", (unsigned long long)total, exclude, min_alt,
-               edits_per_read ? edits_per_read : CBC_EDITS_PER_READ);
-        printf("time: read + plan %.3f s, device init + reference upload %.3f s, decode + pileup + write %.3f s\n", r.t1 - r.t0, r.t_init, r.t_dev);
-        if (r.used) printf("kernels: edits decode %.3f ms, mark + events %.3f ms, scans %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
+        printf("%s: %llu text bytes, exclude flags 0x%x", mode, (unsigned long long)total, exclude);
+        if (pu) printf(", min alt %u, edits per read %u", pu->min_alt, pu->edits_per_read ? pu->edits_per_read : CBC_EDITS_PER_READ);
+        printf("\ntime: read + plan %.3f s, device init + reference upload %.3f s, decode + %s + write %.3f s\n", r.t1 - r.t0, r.t_init, mode, r.t_dev);
+        if (r.used) printf(pu ? "kernels: edits decode %.3f ms, mark + events %.3f ms, scans %.3f ms, text %.3f ms\n"
+                              : "kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
     }
     free(text); free(sels);
     cli_close(&r);
     return 0;
+}
+
+int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude, int verbose)
+{
+    return decompress_window(in, out, ref, device, region, exclude, NULL, verbose);
+}
+
+int cbc_cli_decompress_pileup(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,
+                              uint32_t min_alt, uint32_t edits_per_read, int verbose)
+{
+    const cli_pileup pu = { min_alt, edits_per_read };
+    return decompress_window(in, out, ref, device, region, exclude, &pu, verbose);
 }
 
 /* `cbc -d|-x ... --region A --region B ... [--regions-file FILE]`: the union of the loci in one pass.

@@ -2026,13 +2026,80 @@ static int decode_laid_out(cbc_gpu_ctx *ctx, const uint8_t *in, const block_layo
                               L->nrec * L->bl[0].seq_stride + 8, NULL, NULL, NULL, 0, NULL, results, rg);
 }
 
-/* Kernel times of the most recent call with a post-decode stage: out[i] = the time from ev[i] to ev[i + 1], for the n
- * stretches between n + 1 consecutive events of that call. */
-static int last_ms(cbc_gpu_ctx *ctx, const hipEvent_t *ev, float *const *out, int n)
+/* Kernel times of the most recent call with a post-decode stage, for the entry point that call belongs to (`mine`): out[i] =
+ * the time between the i-th and the next of the call's events, for its first n stretches.  The events in the order the call
+ * recorded them: ev_rg[0..3], then the histogram's two, or the coverage's four, the extension's five and the quantiles' one, or
+ * ev_rg[4]. */
+static int last_ms(cbc_gpu_ctx *ctx, bool mine, float *const *out, int n)
 {
+    if (!mine) return CBC_E_ARG;
     for (int i = 0; i < n; i++) if (!out[i]) return CBC_E_ARG;
+    hipEvent_t ev[14];
+    int k = 0;
+    for (int i = 0; i < 4; i++) ev[k++] = ctx->ev_rg[i];
+    if (ctx->last_post == POST_HIST) { ev[k++] = ctx->ev_hist[0]; ev[k++] = ctx->ev_hist[1]; }
+    else if (post_is_cov(ctx->last_post)) {
+        for (int i = 0; i < 4; i++) ev[k++] = ctx->ev_cov[i];
+        for (int i = 0; i < 5; i++) ev[k++] = ctx->ev_covx[i];
+        ev[k++] = ctx->ev_quant;
+    } else ev[k++] = ctx->ev_rg[4];
     HIPCHK(hipEventSynchronize(ev[n]), "hipEventSynchronize");
     for (int i = 0; i < n; i++) HIPCHK(hipEventElapsedTime(out[i], ev[i], ev[i + 1]), "hipEventElapsedTime");
+    return CBC_OK;
+}
+#define LAST_IS(test) (ctx && (test))                          /* `mine` of last_ms: no context, no kind */
+
+/* The checks the decode entry points share.  `who` opens the message as for relayout_blocks; each returns CBC_OK or the
+ * refusal, with the message set. */
+
+/* after the NULL checks and the zeroing of the out-parameters: > 0 go on, otherwise the call's return code (no reference: a
+ * refusal; no blocks: CBC_OK; `ptrs`, the pointers a call with blocks needs, not all there: CBC_E_ARG) */
+static int call_ready(cbc_gpu_ctx *ctx, uint32_t n_blocks, bool ptrs)
+{
+    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
+    if (n_blocks == 0) return CBC_OK;
+    return ptrs ? 1 : CBC_E_ARG;
+}
+
+/* the window of a region, SAM region (pos_max false), depth or pileup call (true: end <= 2^31 - 1 too) */
+static int check_window(cbc_gpu_ctx *ctx, const char *who, uint64_t beg, uint64_t end, uint32_t smax, bool pos_max)
+{
+    if (smax == 0 || beg < 1 || beg > end || (pos_max && end > CBC_SAM_MAX_POS))
+        return layout_err(ctx, who, pos_max ? " wants 1 <= beg <= end <= 2^31 - 1 and smax > 0" : " wants 1 <= beg <= end and smax > 0");
+    return CBC_OK;
+}
+
+/* the contig name of a depth or pileup call */
+static int check_window_name(cbc_gpu_ctx *ctx, const char *who, const char *name, uint32_t name_bytes)
+{
+    if (name_bytes < 1 || name_bytes > CBC_SAM_MAX_NAME || memchr(name, '\t', name_bytes) || memchr(name, '\n', name_bytes) || memchr(name, 0, name_bytes))
+        return layout_err(ctx, who, ": the contig name is empty, longer than 255 bytes or holds a tab, a newline or a NUL");
+    return CBC_OK;
+}
+
+/* the arena size of a call behind the edits decoder, 0 replaced by the default; who_wants: "pileup wants ", or "" */
+static int check_edits(cbc_gpu_ctx *ctx, const char *who_wants, uint32_t *edits_per_read)
+{
+    if (*edits_per_read == 0) *edits_per_read = CBC_EDITS_PER_READ;
+    if (*edits_per_read > CBC_EDITS_MAX) return layout_err(ctx, who_wants, "edits_per_read in 1..510 (0: the default)");
+    return CBC_OK;
+}
+
+/* the interval table of a target set */
+static int check_intervals(cbc_gpu_ctx *ctx, const char *who, const cbc_gpu_targets *t)
+{
+    for (uint32_t i = 0; i < t->n_iv; i++)
+        if (t->iv[2 * i] < 1 || t->iv[2 * i] > t->iv[2 * i + 1] || t->iv[2 * i + 1] > CBC_SAM_MAX_POS)
+            return layout_err(ctx, who, ": an interval is not 1 <= beg <= end <= 2^31 - 1");
+    return CBC_OK;
+}
+
+/* block b's range of the interval table, and (window_start != NULL; with the name tables relayout_blocks looks) its window start */
+static int check_block_iv(cbc_gpu_ctx *ctx, const char *who, const cbc_gpu_targets *t, uint32_t b, const uint64_t *window_start)
+{
+    const uint32_t f = t->block_iv[2 * b], c = t->block_iv[2 * b + 1];
+    if (f > t->n_iv || c > t->n_iv - f) return layout_err(ctx, who, ": a block's interval range lies outside the table");
+    if (window_start && window_start[b] > CBC_SAM_MAX_POS) return layout_err(ctx, who, ": a block starts past POS 2^31 - 1");
     return CBC_OK;
 }
 
@@ -2045,12 +2112,11 @@ API int cbc_gpu_decode_region(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
 {
     if (!ctx || !blocks || !caps || !window_start || !text_bytes || !n_selected || (text_cap && !text)) return CBC_E_ARG;
     *text_bytes = 0; *n_selected = 0;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
-    if (n_blocks == 0) return CBC_OK;
-    if (!in) return CBC_E_ARG;
-    if (smax == 0 || beg < 1 || beg > end) return set_err(ctx, CBC_E_ARG, "region decode wants 1 <= beg <= end and smax > 0", hipSuccess);
+    int rc = call_ready(ctx, n_blocks, in != NULL);
+    if (rc <= 0) return rc;
+    if ((rc = check_window(ctx, "region decode", beg, end, smax, false))) return rc;
     block_layout L;
-    int rc = relayout_blocks(ctx, "region decode", in_bytes, blocks, n_blocks, NULL, &L);
+    rc = relayout_blocks(ctx, "region decode", in_bytes, blocks, n_blocks, NULL, &L);
     if (rc) return rc;
     post_req rg;                                               /* every read kept: rl + 1 <= stride + 1 bytes each */
     post_req_init(&rg, POST_REGION, smax, window_start, text, text_cap, L.nrec * (blocks[0].seq_stride + 1ull), text_bytes, n_selected);
@@ -2072,71 +2138,38 @@ API int cbc_gpu_decode_blocks_span(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t
 }
 
 /* SAM output: the blocks laid out afresh as for a region decode, the per-block name table made and checked on the host,
- * then decode + count + scan + write on the device (cbc_sam_body.h) */
-API int cbc_gpu_decode_sam(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+ * then decode + count + scan + write on the device (cbc_sam_body.h).  cg != NULL: with CIGAR, NM and MD (DESIGN.md section
+ * 4.21) -- the edits decoder, and the measure pass in front of the count (cbc_cigar_body.h); the bound on the text is
+ * cbc_unpack_sam_cigar_text_cap's. */
+struct sam_cigar_opt { uint32_t smax, edits_per_read; };
+static int decode_sam_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                            uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
                            const uint32_t *block_contig, const char *names, uint32_t names_bytes,
-                           const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_sam_region *region,
+                           const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_sam_region *region, const sam_cigar_opt *cg,
                            uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_reads, cbc_block_result *results)
 {
     if (!ctx || !blocks || !caps || !window_start || !block_contig || !names || !contig_name_off || !text_bytes || !n_reads ||
         (text_cap && !text)) return CBC_E_ARG;
     *text_bytes = 0; *n_reads = 0;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
-    if (n_blocks == 0) return CBC_OK;
-    if (!in) return CBC_E_ARG;
-    if (region && (region->smax == 0 || region->beg < 1 || region->beg > region->end))
-        return set_err(ctx, CBC_E_ARG, "SAM region decode wants 1 <= beg <= end and smax > 0", hipSuccess);
+    int rc = call_ready(ctx, n_blocks, in != NULL);
+    if (rc <= 0) return rc;
+    if (region && (rc = check_window(ctx, "SAM region decode", region->beg, region->end, region->smax, false))) return rc;
+    uint32_t edits_per_read = 0;
+    if (cg) {
+        if (!region && cg->smax == 0) return set_err(ctx, CBC_E_ARG, "SAM decode with CIGAR wants smax > 0 (the container's span bound)", hipSuccess);
+        edits_per_read = cg->edits_per_read;
+        if ((rc = check_edits(ctx, "SAM decode with CIGAR wants ", &edits_per_read))) return rc;
+    }
     const name_tables nt = { window_start, block_contig, names, names_bytes, contig_name_off, n_contigs };
     block_layout L;
-    int rc = relayout_blocks(ctx, "SAM decode", in_bytes, blocks, n_blocks, &nt, &L);
+    rc = relayout_blocks(ctx, "SAM decode", in_bytes, blocks, n_blocks, &nt, &L);
     if (rc) return rc;
-    post_req rg;                                               /* every read kept, every field at its longest */
-    post_req_init(&rg, POST_SAM, region ? region->smax : 0u, window_start, text, text_cap,
-                  L.nrec * (35ull + blocks[0].seq_stride) + L.name_sum, text_bytes, n_reads);
-    rg.beg = region ? region->beg : 1u; rg.end = region ? region->end : UINT64_MAX; rg.region = region != NULL;
-    rg.names = (const uint8_t *)names; rg.names_bytes = names_bytes; rg.block_name = L.bn;
-    rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
-    layout_free(&L);
-    return rc;
-}
-
-API int cbc_gpu_last_sam_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *count_ms, float *text_ms)
-{
-    if (!ctx || ctx->last_post != POST_SAM) return CBC_E_ARG;
-    float *const out[] = { decode_ms, count_ms, text_ms };
-    return last_ms(ctx, ctx->ev_rg, out, 3);
-}
-
-/* SAM output with CIGAR, NM and MD: cbc_gpu_decode_sam behind the edits decoder, with the measure pass
- * in front of the count (cbc_cigar_body.h).  The bound on the text is cbc_unpack_sam_cigar_text_cap's. */
-API int cbc_gpu_decode_sam_cigar(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
-                                 uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
-                                 const uint32_t *block_contig, const char *names, uint32_t names_bytes,
-                                 const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_sam_region *region, uint32_t smax,
-                                 uint32_t edits_per_read, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_reads,
-                                 cbc_block_result *results)
-{
-    if (!ctx || !blocks || !caps || !window_start || !block_contig || !names || !contig_name_off || !text_bytes || !n_reads ||
-        (text_cap && !text)) return CBC_E_ARG;
-    *text_bytes = 0; *n_reads = 0;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
-    if (n_blocks == 0) return CBC_OK;
-    if (!in) return CBC_E_ARG;
-    if (region && (region->smax == 0 || region->beg < 1 || region->beg > region->end))
-        return set_err(ctx, CBC_E_ARG, "SAM region decode wants 1 <= beg <= end and smax > 0", hipSuccess);
-    if (!region && smax == 0) return set_err(ctx, CBC_E_ARG, "SAM decode with CIGAR wants smax > 0 (the container's span bound)", hipSuccess);
-    if (edits_per_read == 0) edits_per_read = CBC_EDITS_PER_READ;
-    if (edits_per_read > CBC_EDITS_MAX) return set_err(ctx, CBC_E_ARG, "SAM decode with CIGAR wants edits_per_read in 1..510 (0: the default)", hipSuccess);
-    const name_tables nt = { window_start, block_contig, names, names_bytes, contig_name_off, n_contigs };
-    block_layout L;
-    int rc = relayout_blocks(ctx, "SAM decode", in_bytes, blocks, n_blocks, &nt, &L);
-    if (rc) return rc;
-    if (L.nrec > 0x3fffffffull) rc = set_err(ctx, CBC_E_ARG, "SAM decode with CIGAR: more than 2^30 - 1 reads in one call", hipSuccess);
+    if (cg && L.nrec > 0x3fffffffull) rc = set_err(ctx, CBC_E_ARG, "SAM decode with CIGAR: more than 2^30 - 1 reads in one call", hipSuccess);
     else {
-        post_req rg;                                           /* every read kept, every field and token at its longest */
-        post_req_init(&rg, POST_SAM_CIGAR, region ? region->smax : smax, window_start, text, text_cap,
-                      L.nrec * (56ull + 3ull * blocks[0].seq_stride + 16ull * edits_per_read) + L.name_sum, text_bytes, n_reads);
+        post_req rg;                                           /* every read kept, every field (and token) at its longest */
+        const uint64_t per_read = cg ? 56ull + 3ull * blocks[0].seq_stride + 16ull * edits_per_read : 35ull + blocks[0].seq_stride;
+        post_req_init(&rg, cg ? POST_SAM_CIGAR : POST_SAM, region ? region->smax : cg ? cg->smax : 0u, window_start, text, text_cap,
+                      L.nrec * per_read + L.name_sum, text_bytes, n_reads);
         rg.beg = region ? region->beg : 1u; rg.end = region ? region->end : UINT64_MAX; rg.region = region != NULL;
         rg.names = (const uint8_t *)names; rg.names_bytes = names_bytes; rg.block_name = L.bn;
         rg.edits_per_read = edits_per_read;
@@ -2146,99 +2179,94 @@ API int cbc_gpu_decode_sam_cigar(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t i
     return rc;
 }
 
-API int cbc_gpu_last_sam_cigar_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *measure_ms, float *count_ms, float *text_ms)
+API int cbc_gpu_decode_sam(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                           uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                           const uint32_t *block_contig, const char *names, uint32_t names_bytes,
+                           const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_sam_region *region,
+                           uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_reads, cbc_block_result *results)
 {
-    if (!ctx || ctx->last_post != POST_SAM_CIGAR) return CBC_E_ARG;
-    float *const out[] = { decode_ms, measure_ms, count_ms, text_ms };
-    return last_ms(ctx, ctx->ev_rg, out, 4);
+    return decode_sam_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
+                           n_contigs, region, NULL, text, text_cap, text_bytes, n_reads, results);
+}
+
+API int cbc_gpu_decode_sam_cigar(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                 uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
+                                 const uint32_t *block_contig, const char *names, uint32_t names_bytes,
+                                 const uint32_t *contig_name_off, uint32_t n_contigs, const cbc_sam_region *region, uint32_t smax,
+                                 uint32_t edits_per_read, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_reads,
+                                 cbc_block_result *results)
+{
+    const sam_cigar_opt cg = { smax, edits_per_read };
+    return decode_sam_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
+                           n_contigs, region, &cg, text, text_cap, text_bytes, n_reads, results);
 }
 
 /* coverage: the window's blocks laid out afresh as for a region decode, then span decode + mark + scan + text on the device
- * (cbc_depth_body.h) */
+ * (cbc_depth_body.h).  pu != NULL: per-position allele counts -- the edits decoder, then mark + events +
+ * scans + text (cbc_pileup_body.h), for the blocks of one contig. */
+struct pileup_opt { uint32_t min_alt, edits_per_read; };
+static int decode_window_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                              uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const char *name,
+                              uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax, uint32_t exclude_flags, const pileup_opt *pu,
+                              uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_runs, uint64_t *n_reads_kept,
+                              cbc_block_result *results)
+{
+    const char *who = pu ? "pileup" : "depth";
+    if (!ctx || !blocks || !caps || !window_start || !name || !text_bytes || !n_runs || !n_reads_kept || (text_cap && !text)) return CBC_E_ARG;
+    *text_bytes = 0; *n_runs = 0; *n_reads_kept = 0;
+    int rc = call_ready(ctx, n_blocks, in != NULL);
+    if (rc <= 0) return rc;
+    if ((rc = check_window(ctx, who, beg, end, smax, true))) return rc;
+    uint32_t edits_per_read = 0;
+    if (pu) {
+        if (pu->min_alt < 1) return set_err(ctx, CBC_E_ARG, "pileup wants min_alt >= 1", hipSuccess);
+        edits_per_read = pu->edits_per_read;
+        if ((rc = check_edits(ctx, "pileup wants ", &edits_per_read))) return rc;
+    }
+    if ((rc = check_window_name(ctx, who, name, name_bytes))) return rc;
+    /* one contig: every block's window lies at the same place of the reference */
+    for (uint32_t b = 0; pu && b < n_blocks; b++)
+        if (blocks[b].ref_off < window_start[b] || blocks[b].ref_off - window_start[b] != blocks[0].ref_off - window_start[0])
+            return set_err(ctx, CBC_E_ARG, "pileup takes the blocks of one contig", hipSuccess);
+    block_layout L;
+    rc = relayout_blocks(ctx, who, in_bytes, blocks, n_blocks, NULL, &L);
+    if (rc) return rc;
+    if (L.nrec > 0x3fffffffull) rc = layout_err(ctx, who, ": more than 2^30 - 1 reads in one call");
+    else if (L.nrec) {                                         /* blocks without reads: no line */
+        /* depth: K reads give at most 2K - 1 runs; pileup: a line per position of the window at most, and per reference base a
+         * kept read spans (span <= smax) */
+        const uint64_t w = end - beg + 1u, by_reads = L.nrec * smax;
+        post_req rg;
+        post_req_init(&rg, pu ? POST_PILEUP : POST_DEPTH, smax, window_start, text, text_cap,
+                      pu ? (w < by_reads ? w : by_reads) * (name_bytes + 102ull) : (2u * L.nrec - 1u) * (name_bytes + 34ull), text_bytes, n_reads_kept);
+        rg.beg = beg; rg.end = end;
+        rg.names = (const uint8_t *)name; rg.names_bytes = name_bytes; rg.exclude = exclude_flags; rg.n_runs = n_runs;
+        if (pu) { rg.edits_per_read = edits_per_read; rg.min_alt = pu->min_alt; rg.ref_c0 = blocks[0].ref_off - window_start[0]; }
+        rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
+    }
+    layout_free(&L);
+    return rc;
+}
+
 API int cbc_gpu_decode_depth(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                              uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const char *name,
                              uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax, uint32_t exclude_flags,
                              uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_runs, uint64_t *n_reads_kept,
                              cbc_block_result *results)
 {
-    if (!ctx || !blocks || !caps || !window_start || !name || !text_bytes || !n_runs || !n_reads_kept || (text_cap && !text)) return CBC_E_ARG;
-    *text_bytes = 0; *n_runs = 0; *n_reads_kept = 0;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
-    if (n_blocks == 0) return CBC_OK;
-    if (!in) return CBC_E_ARG;
-    if (smax == 0 || beg < 1 || beg > end || end > CBC_SAM_MAX_POS)
-        return set_err(ctx, CBC_E_ARG, "depth wants 1 <= beg <= end <= 2^31 - 1 and smax > 0", hipSuccess);
-    if (name_bytes < 1 || name_bytes > CBC_SAM_MAX_NAME || memchr(name, '\t', name_bytes) || memchr(name, '\n', name_bytes) || memchr(name, 0, name_bytes))
-        return set_err(ctx, CBC_E_ARG, "depth: the contig name is empty, longer than 255 bytes or holds a tab, a newline or a NUL", hipSuccess);
-    block_layout L;
-    int rc = relayout_blocks(ctx, "depth", in_bytes, blocks, n_blocks, NULL, &L);
-    if (rc) return rc;
-    if (L.nrec > 0x3fffffffull) rc = set_err(ctx, CBC_E_ARG, "depth: more than 2^30 - 1 reads in one call", hipSuccess);
-    else if (L.nrec) {                                         /* blocks without reads: no line */
-        post_req rg;                                           /* K reads: at most 2K - 1 runs */
-        post_req_init(&rg, POST_DEPTH, smax, window_start, text, text_cap, (2u * L.nrec - 1u) * (name_bytes + 34ull), text_bytes, n_reads_kept);
-        rg.beg = beg; rg.end = end;
-        rg.names = (const uint8_t *)name; rg.names_bytes = name_bytes; rg.exclude = exclude_flags; rg.n_runs = n_runs;
-        rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
-    }
-    layout_free(&L);
-    return rc;
+    return decode_window_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, name, name_bytes, beg, end, smax, exclude_flags, NULL,
+                              text, text_cap, text_bytes, n_runs, n_reads_kept, results);
 }
 
-API int cbc_gpu_last_depth_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *text_ms)
-{
-    if (!ctx || ctx->last_post != POST_DEPTH) return CBC_E_ARG;
-    float *const out[] = { decode_ms, mark_ms, scan_ms, text_ms };
-    return last_ms(ctx, ctx->ev_rg, out, 4);
-}
-
-/* per-position allele counts: the window's blocks laid out afresh as for the depth, then edits decode +
- * mark + events + scans + text on the device (cbc_pileup_body.h) */
 API int cbc_gpu_decode_pileup(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                               uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const char *name,
                               uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax, uint32_t exclude_flags, uint32_t min_alt,
                               uint32_t edits_per_read, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_lines,
                               uint64_t *n_reads_kept, cbc_block_result *results)
 {
-    if (!ctx || !blocks || !caps || !window_start || !name || !text_bytes || !n_lines || !n_reads_kept || (text_cap && !text)) return CBC_E_ARG;
-    *text_bytes = 0; *n_lines = 0; *n_reads_kept = 0;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
-    if (n_blocks == 0) return CBC_OK;
-    if (!in) return CBC_E_ARG;
-    if (smax == 0 || beg < 1 || beg > end || end > CBC_SAM_MAX_POS)
-        return set_err(ctx, CBC_E_ARG, "pileup wants 1 <= beg <= end <= 2^31 - 1 and smax > 0", hipSuccess);
-    if (min_alt < 1) return set_err(ctx, CBC_E_ARG, "pileup wants min_alt >= 1", hipSuccess);
-    if (edits_per_read == 0) edits_per_read = CBC_EDITS_PER_READ;
-    if (edits_per_read > CBC_EDITS_MAX) return set_err(ctx, CBC_E_ARG, "pileup wants edits_per_read in 1..510 (0: the default)", hipSuccess);
-    if (name_bytes < 1 || name_bytes > CBC_SAM_MAX_NAME || memchr(name, '\t', name_bytes) || memchr(name, '\n', name_bytes) || memchr(name, 0, name_bytes))
-        return set_err(ctx, CBC_E_ARG, "pileup: the contig name is empty, longer than 255 bytes or holds a tab, a newline or a NUL", hipSuccess);
-    /* one contig: every block's window lies at the same place of the reference */
-    for (uint32_t b = 0; b < n_blocks; b++)
-        if (blocks[b].ref_off < window_start[b] || blocks[b].ref_off - window_start[b] != blocks[0].ref_off - window_start[0])
-            return set_err(ctx, CBC_E_ARG, "pileup takes the blocks of one contig", hipSuccess);
-    block_layout L;
-    int rc = relayout_blocks(ctx, "pileup", in_bytes, blocks, n_blocks, NULL, &L);
-    if (rc) return rc;
-    if (L.nrec > 0x3fffffffull) rc = set_err(ctx, CBC_E_ARG, "pileup: more than 2^30 - 1 reads in one call", hipSuccess);
-    else if (L.nrec) {                                         /* blocks without reads: no line */
-        /* a line per position of the window at most, and per reference base a kept read spans (span <= smax) */
-        const uint64_t w = end - beg + 1u, by_reads = L.nrec * smax;
-        post_req rg;
-        post_req_init(&rg, POST_PILEUP, smax, window_start, text, text_cap, (w < by_reads ? w : by_reads) * (name_bytes + 102ull), text_bytes, n_reads_kept);
-        rg.beg = beg; rg.end = end;
-        rg.names = (const uint8_t *)name; rg.names_bytes = name_bytes; rg.exclude = exclude_flags; rg.n_runs = n_lines;
-        rg.edits_per_read = edits_per_read; rg.min_alt = min_alt; rg.ref_c0 = blocks[0].ref_off - window_start[0];
-        rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
-    }
-    layout_free(&L);
-    return rc;
-}
-
-API int cbc_gpu_last_pileup_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *events_ms, float *scan_ms, float *text_ms)
-{
-    if (!ctx || ctx->last_post != POST_PILEUP) return CBC_E_ARG;
-    float *const out[] = { decode_ms, events_ms, scan_ms, text_ms };
-    return last_ms(ctx, ctx->ev_rg, out, 4);
+    const pileup_opt pu = { min_alt, edits_per_read };
+    return decode_window_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, name, name_bytes, beg, end, smax, exclude_flags, &pu,
+                              text, text_cap, text_bytes, n_lines, n_reads_kept, results);
 }
 
 /* cbc_gpu_decode_blocks_span with the edits reported too: the decoder the pileup runs, with everything it leaves returned */
@@ -2248,8 +2276,7 @@ API int cbc_gpu_decode_blocks_edits(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_
                                     uint16_t *arena, cbc_block_result *results)
 {
     if (!ctx || !in || !blocks || !caps || !recs || !seq || !side || !arena || smax == 0) return CBC_E_ARG;
-    if (edits_per_read == 0) edits_per_read = CBC_EDITS_PER_READ;
-    if (edits_per_read > CBC_EDITS_MAX) return set_err(ctx, CBC_E_ARG, "edits_per_read in 1..510 (0: the default)", hipSuccess);
+    if (check_edits(ctx, "", &edits_per_read)) return CBC_E_ARG;
     post_req rg;
     memset(&rg, 0, sizeof rg);
     rg.kind = POST_NONE; rg.smax = smax; rg.edits_per_read = edits_per_read; rg.edit_side = side; rg.edit_arena = arena;
@@ -2273,18 +2300,15 @@ static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
     if (!ctx || !blocks || !caps || !window_start || !block_contig || !names || !contig_name_off || !t || !text_bytes || !n_reads ||
         !n_runs || (text_cap && !text) || output > CBC_TARGETS_DEPTH) return CBC_E_ARG;
     *text_bytes = 0; *n_reads = 0; *n_runs = 0;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
-    if (n_blocks == 0) return CBC_OK;
-    if (!in || !t->iv || !t->block_iv) return CBC_E_ARG;
+    int rc = call_ready(ctx, n_blocks, in && t->iv && t->block_iv);
+    if (rc <= 0) return rc;
     if (t->smax == 0 || t->n_iv == 0 || t->n_iv > (1u << 24))
         return set_err(ctx, CBC_E_ARG, "targets decode wants smax > 0 and 1 .. 2^24 intervals", hipSuccess);
     const bool depth = output == CBC_TARGETS_DEPTH, sam = output == CBC_TARGETS_SAM;
-    for (uint32_t i = 0; i < t->n_iv; i++)
-        if (t->iv[2 * i] < 1 || t->iv[2 * i] > t->iv[2 * i + 1] || t->iv[2 * i + 1] > CBC_SAM_MAX_POS)
-            return set_err(ctx, CBC_E_ARG, "targets decode: an interval is not 1 <= beg <= end <= 2^31 - 1", hipSuccess);
+    if ((rc = check_intervals(ctx, "targets decode", t))) return rc;
     const name_tables nt = { window_start, block_contig, names, names_bytes, contig_name_off, n_contigs };
     block_layout L;
-    int rc = relayout_blocks(ctx, "targets decode", in_bytes, blocks, n_blocks, &nt, &L);
+    rc = relayout_blocks(ctx, "targets decode", in_bytes, blocks, n_blocks, &nt, &L);
     if (rc) return rc;
     uint32_t *biv = NULL, *ioff = NULL;
     uint32_t lo = UINT32_MAX, hi = 0;                           /* depth: the intervals the call's blocks reach */
@@ -2293,7 +2317,7 @@ static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
     post_req rg;
     for (uint32_t b = 0; b < n_blocks; b++) {
         const uint32_t f = t->block_iv[2 * b], c = t->block_iv[2 * b + 1];
-        if (f > t->n_iv || c > t->n_iv - f) { bad = "targets decode: a block's interval range lies outside the table"; goto out; }
+        if ((rc = check_block_iv(ctx, "targets decode", t, b, NULL))) goto out;
         if (depth && block_contig[b] != block_contig[0]) { bad = "targets decode: a depth call takes the blocks of one contig"; goto out; }
         if (whole && c && (f < iv_first || f - iv_first > iv_count || c > iv_count - (f - iv_first))) {
             bad = "coverage: a block's interval range lies outside the contig's intervals"; goto out; }
@@ -2434,19 +2458,6 @@ API int cbc_gpu_decode_coverage_ext(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_
                                    n_thr, thr_covered, reads, NULL, 0u, NULL);
 }
 
-/* kernel times of the most recent cbc_gpu_decode_coverage_ext: cov_ms[7] as cbc_gpu_last_coverage_ms gives them (the mark is
- * the one that also notes the starts), ext_ms[5] the added passes */
-API int cbc_gpu_last_coverage_ext_ms(cbc_gpu_ctx *ctx, float *cov_ms, float *ext_ms)
-{
-    if (!ctx || !cov_ms || !ext_ms || ctx->last_post != POST_COVX) return CBC_E_ARG;
-    const hipEvent_t ev[] = { ctx->ev_rg[0], ctx->ev_rg[1], ctx->ev_rg[2], ctx->ev_rg[3], ctx->ev_cov[0], ctx->ev_cov[1], ctx->ev_cov[2], ctx->ev_cov[3],
-                              ctx->ev_covx[0], ctx->ev_covx[1], ctx->ev_covx[2], ctx->ev_covx[3], ctx->ev_covx[4] };
-    float *out[12];
-    for (int i = 0; i < 7; i++) out[i] = cov_ms + i;
-    for (int i = 0; i < 5; i++) out[7 + i] = ext_ms + i;
-    return last_ms(ctx, ev, out, 12);
-}
-
 /* depth quantiles per query; n_quant == 0: the call above */
 API int cbc_gpu_decode_coverage_quant(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                                       uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start,
@@ -2460,20 +2471,6 @@ API int cbc_gpu_decode_coverage_quant(cbc_gpu_ctx *ctx, const uint8_t *in, uint6
     return decode_coverage_ext_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, block_contig, names, names_bytes, contig_name_off,
                                    n_contigs, t, iv_first, iv_count, q, n_q, exclude_flags, min_depth, sum, covered, n_reads, results, thresholds,
                                    n_thr, thr_covered, reads, quantiles, n_quant, quant_depth);
-}
-
-/* kernel times of the most recent cbc_gpu_decode_coverage_quant: cov_ms[7] and ext_ms[5] as cbc_gpu_last_coverage_ext_ms gives
- * them, quant_ms[1] the selection */
-API int cbc_gpu_last_coverage_quant_ms(cbc_gpu_ctx *ctx, float *cov_ms, float *ext_ms, float *quant_ms)
-{
-    if (!ctx || !cov_ms || !ext_ms || !quant_ms || ctx->last_post != POST_COVQ) return CBC_E_ARG;
-    const hipEvent_t ev[] = { ctx->ev_rg[0], ctx->ev_rg[1], ctx->ev_rg[2], ctx->ev_rg[3], ctx->ev_cov[0], ctx->ev_cov[1], ctx->ev_cov[2], ctx->ev_cov[3],
-                              ctx->ev_covx[0], ctx->ev_covx[1], ctx->ev_covx[2], ctx->ev_covx[3], ctx->ev_covx[4], ctx->ev_quant };
-    float *out[13];
-    for (int i = 0; i < 7; i++) out[i] = cov_ms + i;
-    for (int i = 0; i < 5; i++) out[7 + i] = ext_ms + i;
-    out[12] = quant_ms;
-    return last_ms(ctx, ev, out, 13);
 }
 
 /* depth histogram: the depth form of cbc_gpu_decode_targets up to the change points, laid over all the
@@ -2500,149 +2497,135 @@ API int cbc_gpu_decode_depth_hist(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t 
 
 /* read statistics: the blocks laid out afresh as for a region decode, the plain decode (t == NULL) or the
  * span decode and the keep rule of a target set, then one pass over the records and rows (cbc_stats_body.h); only the tables
- * come back */
-API int cbc_gpu_decode_stats(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+ * come back.  aln != NULL: with the alignment tables -- the edits decoder (smax, edits_per_read), and the
+ * alignment pass (cbc_stats_aln_body.h) behind the statistics pass; both tables come back in the one small-results fetch, and
+ * both are zero after any refusal or failure. */
+static int decode_stats_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                              uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const cbc_gpu_targets *t,
-                             uint32_t exclude_flags, cbc_gpu_stats *out, cbc_block_result *results)
+                             uint32_t smax, uint32_t exclude_flags, uint32_t edits_per_read, cbc_gpu_stats *out, cbc_gpu_stats_aln *aln,
+                             cbc_block_result *results)
 {
     if (!ctx || !out) return CBC_E_ARG;
     memset(out, 0, sizeof *out);
+    if (aln) memset(aln, 0, sizeof *aln);
     if (!blocks || !caps || !window_start) return CBC_E_ARG;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
-    if (n_blocks == 0) return CBC_OK;
-    if (!in || (t && (!t->iv || !t->block_iv))) return CBC_E_ARG;
+    int rc = call_ready(ctx, n_blocks, in && (!t || (t->iv && t->block_iv)));
+    if (rc <= 0) return rc;
     if (t && (t->smax == 0 || t->n_iv == 0 || t->n_iv > (1u << 24)))
         return set_err(ctx, CBC_E_ARG, "statistics of a target set want smax > 0 and 1 .. 2^24 intervals", hipSuccess);
-    for (uint32_t i = 0; t && i < t->n_iv; i++)
-        if (t->iv[2 * i] < 1 || t->iv[2 * i] > t->iv[2 * i + 1] || t->iv[2 * i + 1] > CBC_SAM_MAX_POS)
-            return set_err(ctx, CBC_E_ARG, "statistics: an interval is not 1 <= beg <= end <= 2^31 - 1", hipSuccess);
+    if (aln) {
+        if (!t && smax == 0) return set_err(ctx, CBC_E_ARG, "statistics with alignment tables want smax > 0 (the container's span bound)", hipSuccess);
+        if ((rc = check_edits(ctx, "statistics with alignment tables want ", &edits_per_read))) return rc;
+    }
+    if (t && (rc = check_intervals(ctx, "statistics", t))) return rc;
     uint32_t most = 0;
     for (uint32_t b = 0; b < n_blocks; b++) {
         if (blocks[b].n_reads > most) most = blocks[b].n_reads;
-        if (!t) continue;
-        const uint32_t f = t->block_iv[2 * b], c = t->block_iv[2 * b + 1];
-        if (f > t->n_iv || c > t->n_iv - f) return set_err(ctx, CBC_E_ARG, "statistics: a block's interval range lies outside the table", hipSuccess);
-        if (window_start[b] > CBC_SAM_MAX_POS) return set_err(ctx, CBC_E_ARG, "statistics: a block starts past POS 2^31 - 1", hipSuccess);
+        if (t && (rc = check_block_iv(ctx, "statistics", t, b, window_start))) return rc;
     }
+    /* the bound on a workgroup's run-length counts (cbc_stats_aln_body.h) */
+    if (aln && (uint64_t)n_blocks * ((most + 63u) / 64u) > CBC_SALN_MAX_UNITS)
+        return set_err(ctx, CBC_E_ARG, "statistics with alignment tables: blocks x record groups of the largest block pass 2^29", hipSuccess);
     block_layout L;
-    int rc = relayout_blocks(ctx, "statistics", in_bytes, blocks, n_blocks, NULL, &L);
+    rc = relayout_blocks(ctx, "statistics", in_bytes, blocks, n_blocks, NULL, &L);
     if (rc) return rc;
     if (L.nrec > 0xffffffffull) { layout_free(&L); return set_err(ctx, CBC_E_ARG, "statistics: more than 2^32 - 1 reads in one call", hipSuccess); }
     if (L.nrec) {
         uint64_t text_bytes = 0, n_sel = 0;
         post_req rg;
-        post_req_init(&rg, t ? POST_TG_STATS : POST_STATS, t ? t->smax : 0u, window_start, NULL, 0, 0, &text_bytes, &n_sel);
+        post_req_init(&rg, aln ? (t ? POST_TG_STATS_ALN : POST_STATS_ALN) : (t ? POST_TG_STATS : POST_STATS), t ? t->smax : aln ? smax : 0u,
+                      window_start, NULL, 0, 0, &text_bytes, &n_sel);
         rg.beg = 1u; rg.end = UINT64_MAX;
         if (t) { rg.iv = t->iv; rg.n_iv = t->n_iv; rg.block_iv = t->block_iv; }
         rg.exclude = exclude_flags; rg.stats = out; rg.stats_gmax = (most + 63u) / 64u;
+        if (aln) { rg.stats_aln = aln; rg.edits_per_read = edits_per_read; }
         rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
+        if (rc && aln) { memset(out, 0, sizeof *out); memset(aln, 0, sizeof *aln); }
     }
     layout_free(&L);
     return rc;
 }
 
-/* kernel times of the most recent cbc_gpu_decode_stats */
-API int cbc_gpu_last_stats_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *stats_ms)
+API int cbc_gpu_decode_stats(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                             uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const cbc_gpu_targets *t,
+                             uint32_t exclude_flags, cbc_gpu_stats *out, cbc_block_result *results)
 {
-    if (!ctx || !post_is_stats(ctx->last_post) || post_is_stats_aln(ctx->last_post)) return CBC_E_ARG;
-    float *const out[] = { decode_ms, stats_ms };
-    return last_ms(ctx, ctx->ev_rg, out, 2);
+    return decode_stats_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, t, 0u, exclude_flags, 0u, out, NULL, results);
 }
 
-/* read statistics with the alignment tables: cbc_gpu_decode_stats behind the edits decoder, with the
- * alignment pass (cbc_stats_aln_body.h) behind the statistics pass; both tables come back in the one small-results fetch */
 API int cbc_gpu_decode_stats_aln(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                                  uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const cbc_gpu_targets *t,
                                  uint32_t smax, uint32_t exclude_flags, uint32_t edits_per_read, cbc_gpu_stats *out,
                                  cbc_gpu_stats_aln *aln, cbc_block_result *results)
 {
-    if (!ctx || !out || !aln) return CBC_E_ARG;
-    memset(out, 0, sizeof *out); memset(aln, 0, sizeof *aln);
-    if (!blocks || !caps || !window_start) return CBC_E_ARG;
-    if (!ctx->d_ref) return set_err(ctx, CBC_E_ARG, "cbc_gpu_upload_reference has not been called", hipSuccess);
-    if (n_blocks == 0) return CBC_OK;
-    if (!in || (t && (!t->iv || !t->block_iv))) return CBC_E_ARG;
-    if (t && (t->smax == 0 || t->n_iv == 0 || t->n_iv > (1u << 24)))
-        return set_err(ctx, CBC_E_ARG, "statistics of a target set want smax > 0 and 1 .. 2^24 intervals", hipSuccess);
-    if (!t && smax == 0) return set_err(ctx, CBC_E_ARG, "statistics with alignment tables want smax > 0 (the container's span bound)", hipSuccess);
-    if (edits_per_read == 0) edits_per_read = CBC_EDITS_PER_READ;
-    if (edits_per_read > CBC_EDITS_MAX) return set_err(ctx, CBC_E_ARG, "statistics with alignment tables want edits_per_read in 1..510 (0: the default)", hipSuccess);
-    for (uint32_t i = 0; t && i < t->n_iv; i++)
-        if (t->iv[2 * i] < 1 || t->iv[2 * i] > t->iv[2 * i + 1] || t->iv[2 * i + 1] > CBC_SAM_MAX_POS)
-            return set_err(ctx, CBC_E_ARG, "statistics: an interval is not 1 <= beg <= end <= 2^31 - 1", hipSuccess);
-    uint32_t most = 0;
-    for (uint32_t b = 0; b < n_blocks; b++) {
-        if (blocks[b].n_reads > most) most = blocks[b].n_reads;
-        if (!t) continue;
-        const uint32_t f = t->block_iv[2 * b], c = t->block_iv[2 * b + 1];
-        if (f > t->n_iv || c > t->n_iv - f) return set_err(ctx, CBC_E_ARG, "statistics: a block's interval range lies outside the table", hipSuccess);
-        if (window_start[b] > CBC_SAM_MAX_POS) return set_err(ctx, CBC_E_ARG, "statistics: a block starts past POS 2^31 - 1", hipSuccess);
-    }
-    /* the bound on a workgroup's run-length counts (cbc_stats_aln_body.h) */
-    if ((uint64_t)n_blocks * ((most + 63u) / 64u) > CBC_SALN_MAX_UNITS)
-        return set_err(ctx, CBC_E_ARG, "statistics with alignment tables: blocks x record groups of the largest block pass 2^29", hipSuccess);
-    block_layout L;
-    int rc = relayout_blocks(ctx, "statistics", in_bytes, blocks, n_blocks, NULL, &L);
-    if (rc) return rc;
-    if (L.nrec > 0xffffffffull) { layout_free(&L); return set_err(ctx, CBC_E_ARG, "statistics: more than 2^32 - 1 reads in one call", hipSuccess); }
-    if (L.nrec) {
-        uint64_t text_bytes = 0, n_sel = 0;
-        post_req rg;
-        post_req_init(&rg, t ? POST_TG_STATS_ALN : POST_STATS_ALN, t ? t->smax : smax, window_start, NULL, 0, 0, &text_bytes, &n_sel);
-        rg.beg = 1u; rg.end = UINT64_MAX;
-        if (t) { rg.iv = t->iv; rg.n_iv = t->n_iv; rg.block_iv = t->block_iv; }
-        rg.exclude = exclude_flags; rg.stats = out; rg.stats_gmax = (most + 63u) / 64u;
-        rg.stats_aln = aln; rg.edits_per_read = edits_per_read;
-        rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
-        if (rc) { memset(out, 0, sizeof *out); memset(aln, 0, sizeof *aln); }
-    }
-    layout_free(&L);
-    return rc;
+    if (!aln) return CBC_E_ARG;
+    return decode_stats_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, t, smax, exclude_flags, edits_per_read, out, aln, results);
 }
 
-/* kernel times of the most recent cbc_gpu_decode_stats_aln */
+/* Kernel times of the most recent call, per entry point (last_ms): the kinds it answers for and the stretches it reports.  A
+ * NULL out-pointer is CBC_E_ARG before anything waits. */
+#define LAST_MS(kinds, ...) do { float *const out[] = { __VA_ARGS__ }; \
+                                 return last_ms(ctx, LAST_IS(kinds), out, (int)(sizeof out / sizeof out[0])); } while (0)
+
+API int cbc_gpu_last_region_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *text_ms)
+{ LAST_MS(ctx->last_post == POST_REGION, decode_ms, filter_ms, text_ms); }
+
+API int cbc_gpu_last_sam_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *count_ms, float *text_ms)
+{ LAST_MS(ctx->last_post == POST_SAM, decode_ms, count_ms, text_ms); }
+
+API int cbc_gpu_last_sam_cigar_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *measure_ms, float *count_ms, float *text_ms)
+{ LAST_MS(ctx->last_post == POST_SAM_CIGAR, decode_ms, measure_ms, count_ms, text_ms); }
+
+API int cbc_gpu_last_depth_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *text_ms)
+{ LAST_MS(ctx->last_post == POST_DEPTH, decode_ms, mark_ms, scan_ms, text_ms); }
+
+API int cbc_gpu_last_pileup_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *events_ms, float *scan_ms, float *text_ms)
+{ LAST_MS(ctx->last_post == POST_PILEUP, decode_ms, events_ms, scan_ms, text_ms); }
+
+/* not after a call with the alignment tables: that one has a third stretch, and an entry point of its own */
+API int cbc_gpu_last_stats_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *stats_ms)
+{ LAST_MS(post_is_stats(ctx->last_post) && !post_is_stats_aln(ctx->last_post), decode_ms, stats_ms); }
+
 API int cbc_gpu_last_stats_aln_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *stats_ms, float *aln_ms)
-{
-    if (!ctx || !post_is_stats_aln(ctx->last_post)) return CBC_E_ARG;
-    float *const out[] = { decode_ms, stats_ms, aln_ms };
-    return last_ms(ctx, ctx->ev_rg, out, 3);
-}
+{ LAST_MS(post_is_stats_aln(ctx->last_post), decode_ms, stats_ms, aln_ms); }
 
-/* kernel times of the most recent cbc_gpu_decode_depth_hist */
 API int cbc_gpu_last_hist_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *accum_ms, float *compact_ms)
-{
-    if (!ctx || ctx->last_post != POST_HIST) return CBC_E_ARG;
-    const hipEvent_t ev[] = { ctx->ev_rg[0], ctx->ev_rg[1], ctx->ev_rg[2], ctx->ev_rg[3], ctx->ev_hist[0], ctx->ev_hist[1] };
-    float *const out[] = { decode_ms, mark_ms, scan_ms, accum_ms, compact_ms };
-    return last_ms(ctx, ev, out, 5);
-}
+{ LAST_MS(ctx->last_post == POST_HIST, decode_ms, mark_ms, scan_ms, accum_ms, compact_ms); }
 
-/* kernel times of the most recent cbc_gpu_decode_coverage */
 API int cbc_gpu_last_coverage_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms, float *scan_ms, float *weights_ms,
                                  float *wscan_ms, float *apply_ms, float *lookup_ms)
+{ LAST_MS(ctx->last_post == POST_COV, decode_ms, mark_ms, scan_ms, weights_ms, wscan_ms, apply_ms, lookup_ms); }
+
+/* cov_ms[7] as cbc_gpu_last_coverage_ms gives them (the mark is the one that also notes the starts), ext_ms[5] the added
+ * passes, and after a call with quantiles quant_ms[1], the selection */
+static int last_coverage_ext_ms(cbc_gpu_ctx *ctx, post_kind kind, float *cov_ms, float *ext_ms, float *quant_ms)
 {
-    if (!ctx || ctx->last_post != POST_COV) return CBC_E_ARG;
-    const hipEvent_t ev[] = { ctx->ev_rg[0], ctx->ev_rg[1], ctx->ev_rg[2], ctx->ev_rg[3], ctx->ev_cov[0], ctx->ev_cov[1], ctx->ev_cov[2], ctx->ev_cov[3] };
-    float *const out[] = { decode_ms, mark_ms, scan_ms, weights_ms, wscan_ms, apply_ms, lookup_ms };
-    return last_ms(ctx, ev, out, 7);
+    if (!cov_ms || !ext_ms) return CBC_E_ARG;
+    float *out[13];
+    for (int i = 0; i < 7; i++) out[i] = cov_ms + i;
+    for (int i = 0; i < 5; i++) out[7 + i] = ext_ms + i;
+    out[12] = quant_ms;
+    return last_ms(ctx, LAST_IS(ctx->last_post == kind), out, kind == POST_COVQ ? 13 : 12);
+}
+
+API int cbc_gpu_last_coverage_ext_ms(cbc_gpu_ctx *ctx, float *cov_ms, float *ext_ms)
+{
+    return last_coverage_ext_ms(ctx, POST_COVX, cov_ms, ext_ms, NULL);
+}
+
+API int cbc_gpu_last_coverage_quant_ms(cbc_gpu_ctx *ctx, float *cov_ms, float *ext_ms, float *quant_ms)
+{
+    return last_coverage_ext_ms(ctx, POST_COVQ, cov_ms, ext_ms, quant_ms);
 }
 
 /* a reads / SAM call has no scan stretch of its own: scan_ms = 0 */
 API int cbc_gpu_last_targets_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *scan_ms, float *text_ms)
 {
     if (!ctx || !decode_ms || !filter_ms || !scan_ms || !text_ms) return CBC_E_ARG;
-    float *const out4[] = { decode_ms, filter_ms, scan_ms, text_ms }, *const out3[] = { decode_ms, filter_ms, text_ms };
-    if (ctx->last_post == POST_TG_DEPTH) return last_ms(ctx, ctx->ev_rg, out4, 4);
+    if (ctx->last_post == POST_TG_DEPTH) LAST_MS(true, decode_ms, filter_ms, scan_ms, text_ms);
     if (ctx->last_post != POST_TG_READS && ctx->last_post != POST_TG_SAM) return CBC_E_ARG;
     *scan_ms = 0.0f;
-    return last_ms(ctx, ctx->ev_rg, out3, 3);
-}
-
-API int cbc_gpu_last_region_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *filter_ms, float *text_ms)
-{
-    if (!ctx || ctx->last_post != POST_REGION) return CBC_E_ARG;
-    float *const out[] = { decode_ms, filter_ms, text_ms };
-    return last_ms(ctx, ctx->ev_rg, out, 3);
+    LAST_MS(true, decode_ms, filter_ms, text_ms);
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -592,33 +592,8 @@ class Encoder:
         a plain byte compare with the uploaded reference); edits_per_read sizes the arena as for decode_pileup (a block that
         needs more fails, the error names the option).  Its default buffer is plan.sam_text_cap plus 64 bytes per read, and the
         call is repeated once at the text's own size when that is too small; plan.sam_cigar_text_cap always suffices."""
-        if cigar:
-            return self._decode_sam_cigar(plan, region, results, text_cap, edits_per_read)
-        if edits_per_read is not None:
+        if not cigar and edits_per_read is not None:
             raise ValueError("edits_per_read applies to decode_sam(cigar=True)")
-        hdr = plan.sam_header()
-        sel = plan.region(region) if region is not None else None
-        b0, b1 = (sel.b0, sel.b1) if sel is not None else (0, plan.n_blocks)
-        nb = b1 - b0
-        res = np.zeros(max(nb, 1), dtype=host.RESULT_DTYPE)
-        if nb == 0:
-            return (hdr, 0, sel, res[:0]) if results else hdr
-        blocks, ws, bc = self._gather(plan, slice(b0, b1))
-        caps, pay, names, noff = self._plan_args(plan)
-        cap = plan.sam_text_cap(b0, b1) if text_cap is None else int(text_cap)
-        text = np.zeros(max(cap, 1), dtype=np.uint8)
-        nbytes, nrd = ctypes.c_uint64(), ctypes.c_uint64()
-        rg = SamRegion(sel.beg, sel.end, sel.smax, 0) if sel is not None else None
-        rc = lib().cbc_gpu_decode_sam(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps), ws.ctypes.data,
-                                      bc.ctypes.data, names.ctypes.data, names.size, noff.ctypes.data, plan.n_contigs,
-                                      ctypes.byref(rg) if rg is not None else None, text.ctypes.data, cap,
-                                      ctypes.byref(nbytes), ctypes.byref(nrd), res.ctypes.data)
-        self.last_sam_text_bytes = int(nbytes.value)
-        self._check_blocks(rc, "cbc_gpu_decode_sam", results)
-        out = hdr + text[:int(nbytes.value)].tobytes()
-        return (out, int(nrd.value), sel, res[:nb]) if results else out
-
-    def _decode_sam_cigar(self, plan, region, results, text_cap, edits_per_read):
         hdr = plan.sam_header()
         epr = 0 if edits_per_read is None else int(edits_per_read)
         if edits_per_read is not None and not 1 <= epr <= 510:
@@ -627,30 +602,71 @@ class Encoder:
         b0, b1 = (sel.b0, sel.b1) if sel is not None else (0, plan.n_blocks)
         nb = b1 - b0
         res = np.zeros(max(nb, 1), dtype=host.RESULT_DTYPE)
-        self.last_sam_text_bytes = 0
+        if cigar:
+            self.last_sam_text_bytes = 0
         if nb == 0:
             return (hdr, 0, sel, res[:0]) if results else hdr
         blocks, ws, bc = self._gather(plan, slice(b0, b1))
         caps, pay, names, noff = self._plan_args(plan)
-        bound = plan.sam_cigar_text_cap(b0, b1, epr)
-        first = plan.sam_text_cap(b0, b1) + 64 * int(plan.blocks[b0:b1]["n_reads"].sum())
-        cap = min(first, bound) if text_cap is None else int(text_cap)
+        # the plain text starts at its bound, so nothing is ever repeated for it; with CIGAR the first buffer is a guess
+        bound = cap = plan.sam_text_cap(b0, b1)
+        fn, extra = "cbc_gpu_decode_sam", ()
+        if cigar:
+            bound = plan.sam_cigar_text_cap(b0, b1, epr)
+            cap = min(cap + 64 * int(plan.blocks[b0:b1]["n_reads"].sum()), bound)
+            # the container's span bound, the one every selection carries
+            fn, extra = "cbc_gpu_decode_sam_cigar", (plan.max_read_len + plan.read_length - 1, epr)
+        if text_cap is not None:
+            cap = int(text_cap)
         nbytes, nrd = ctypes.c_uint64(), ctypes.c_uint64()
         rg = SamRegion(sel.beg, sel.end, sel.smax, 0) if sel is not None else None
-        smax = plan.max_read_len + plan.read_length - 1       # the container's span bound, the one every selection carries
         for _ in range(2):
             text = np.zeros(max(cap, 1), dtype=np.uint8)
-            rc = lib().cbc_gpu_decode_sam_cigar(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
-                                                ws.ctypes.data, bc.ctypes.data, names.ctypes.data, names.size, noff.ctypes.data,
-                                                plan.n_contigs, ctypes.byref(rg) if rg is not None else None, smax, epr,
-                                                text.ctypes.data, cap, ctypes.byref(nbytes), ctypes.byref(nrd), res.ctypes.data)
+            rc = getattr(lib(), fn)(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps), ws.ctypes.data,
+                                    bc.ctypes.data, names.ctypes.data, names.size, noff.ctypes.data, plan.n_contigs,
+                                    ctypes.byref(rg) if rg is not None else None, *extra, text.ctypes.data, cap,
+                                    ctypes.byref(nbytes), ctypes.byref(nrd), res.ctypes.data)
             if not (text_cap is None and rc == -1 and cap < int(nbytes.value) <= bound):
                 break
             cap = int(nbytes.value)                           # the text's own size
         self.last_sam_text_bytes = int(nbytes.value)
-        self._check_blocks(rc, "cbc_gpu_decode_sam_cigar", results)
+        self._check_blocks(rc, fn, results)
         out = hdr + text[:int(nbytes.value)].tobytes()
         return (out, int(nrd.value), sel, res[:nb]) if results else out
+
+    def _decode_windows(self, plan, region, results, text_cap, fn, rest, cap_of, bytes_attr, ms_attr, ms_fn):
+        """What decode_depth and decode_pileup share: one call of lib().<fn> per selection -- the region's, or every contig's that
+        has blocks -- with rest(sel), the arguments between the window's end and the text buffer; the buffer is cap_of(sel) or
+        text_cap bytes and the call is never repeated.  The texts' bytes are summed in self.<bytes_attr>, the kernel times of
+        lib().<ms_fn> in self.<ms_attr>.  Returns (text, n_runs or n_lines, n_reads_kept, per-block results), or the text."""
+        sels = [plan.region(region)] if region is not None else [plan.contig_blocks(c) for c in range(plan.n_contigs)]
+        out, n_out, n_kept, allres = [], 0, 0, []
+        setattr(self, bytes_attr, 0)
+        setattr(self, ms_attr, None)
+        caps, pay, _, _ = self._plan_args(plan)
+        for sel in sels:
+            nb = sel.b1 - sel.b0
+            if nb == 0:
+                continue
+            blocks, ws, _ = self._gather(plan, slice(sel.b0, sel.b1))
+            off = int(plan.contig_name_off[sel.contig])
+            name = plan.names[off:].tobytes().split(b"\0", 1)[0]
+            cap = cap_of(sel) if text_cap is None else int(text_cap)
+            text = np.zeros(max(cap, 1), dtype=np.uint8)
+            res = np.zeros(nb, dtype=host.RESULT_DTYPE)
+            nbytes, no, nk = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+            rc = getattr(lib(), fn)(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps), ws.ctypes.data,
+                                    name, len(name), sel.beg, sel.end, *rest(sel), text.ctypes.data, cap, ctypes.byref(nbytes),
+                                    ctypes.byref(no), ctypes.byref(nk), res.ctypes.data)
+            setattr(self, bytes_attr, getattr(self, bytes_attr) + int(nbytes.value))
+            self._check_blocks(rc, fn, results)
+            self._add_ms(ms_attr, ms_fn, 4, must=True)
+            out.append(text[:int(nbytes.value)].tobytes())
+            n_out += int(no.value); n_kept += int(nk.value); allres.append(res)
+        text = b"".join(out)
+        if results:
+            return text, n_out, n_kept, self._cat(allres)
+        return text
 
     def decode_depth(self, plan: "host.UnpackPlan", region=None, exclude_flags=0, results=False, text_cap=None, smax=None):
         """Coverage of the container's reads as bedGraph bytes (cbc_gpu_decode_depth): per maximal run of equal non-zero
@@ -662,36 +678,10 @@ class Encoder:
         of the blocks used) and lets a failed block pass (it marks nothing); text_cap: size of the buffer of one call (default:
         plan.depth_text_cap of its blocks); smax: the span bound the decode checks (default: the selection's)."""
         plan.sam_header()                                     # refuses what the text cannot carry, and long-read containers
-        sels = [plan.region(region)] if region is not None else [plan.contig_blocks(c) for c in range(plan.n_contigs)]
-        out, n_runs, n_kept, allres = [], 0, 0, []
-        self.last_depth_text_bytes = 0
-        self._depth_ms = None
-        caps, pay, _, _ = self._plan_args(plan)
-        for sel in sels:
-            nb = sel.b1 - sel.b0
-            if nb == 0:
-                continue
-            blocks, ws, _ = self._gather(plan, slice(sel.b0, sel.b1))
-            off = int(plan.contig_name_off[sel.contig])
-            name = plan.names[off:].tobytes().split(b"\0", 1)[0]
-            cap = plan.depth_text_cap(sel.b0, sel.b1, sel.contig) if text_cap is None else int(text_cap)
-            text = np.zeros(max(cap, 1), dtype=np.uint8)
-            res = np.zeros(nb, dtype=host.RESULT_DTYPE)
-            nbytes, nr, nk = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-            rc = lib().cbc_gpu_decode_depth(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
-                                            ws.ctypes.data, name, len(name), sel.beg, sel.end, sel.smax if smax is None else int(smax),
-                                            int(exclude_flags),
-                                            text.ctypes.data, cap, ctypes.byref(nbytes), ctypes.byref(nr), ctypes.byref(nk),
-                                            res.ctypes.data)
-            self.last_depth_text_bytes += int(nbytes.value)
-            self._check_blocks(rc, "cbc_gpu_decode_depth", results)
-            self._add_ms("_depth_ms", "cbc_gpu_last_depth_ms", 4, must=True)
-            out.append(text[:int(nbytes.value)].tobytes())
-            n_runs += int(nr.value); n_kept += int(nk.value); allres.append(res)
-        text = b"".join(out)
-        if results:
-            return text, n_runs, n_kept, self._cat(allres)
-        return text
+        return self._decode_windows(plan, region, results, text_cap, "cbc_gpu_decode_depth",
+                                    lambda sel: (sel.smax if smax is None else int(smax), int(exclude_flags)),
+                                    lambda sel: plan.depth_text_cap(sel.b0, sel.b1, sel.contig),
+                                    "last_depth_text_bytes", "_depth_ms", "cbc_gpu_last_depth_ms")
 
     def decode_pileup(self, plan: "host.UnpackPlan", region=None, exclude_flags=0, min_alt=1, edits_per_read=None, results=False,
                       text_cap=None):
@@ -710,41 +700,21 @@ class Encoder:
         epr = EDITS_PER_READ if edits_per_read is None else int(edits_per_read)
         if not 1 <= epr <= 510:
             raise ValueError("edits_per_read is in 1..510")
-        sels = [plan.region(region)] if region is not None else [plan.contig_blocks(c) for c in range(plan.n_contigs)]
-        out, n_lines, n_kept, allres = [], 0, 0, []
-        self.last_pileup_text_bytes = 0
-        self._pileup_ms = None
-        caps, pay, _, _ = self._plan_args(plan)
-        for sel in sels:
-            nb = sel.b1 - sel.b0
-            if nb == 0:
-                continue
-            blocks, ws, _ = self._gather(plan, slice(sel.b0, sel.b1))
-            off = int(plan.contig_name_off[sel.contig])
-            name = plan.names[off:].tobytes().split(b"\0", 1)[0]
-            cap = plan.pileup_text_cap(sel.b0, sel.b1, sel.contig, sel.beg, sel.end, sel.smax) if text_cap is None else int(text_cap)
-            text = np.zeros(max(cap, 1), dtype=np.uint8)
-            res = np.zeros(nb, dtype=host.RESULT_DTYPE)
-            nbytes, nl, nk = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-            rc = lib().cbc_gpu_decode_pileup(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
-                                             ws.ctypes.data, name, len(name), sel.beg, sel.end, sel.smax, int(exclude_flags),
-                                             int(min_alt), epr, text.ctypes.data, cap, ctypes.byref(nbytes), ctypes.byref(nl),
-                                             ctypes.byref(nk), res.ctypes.data)
-            self.last_pileup_text_bytes += int(nbytes.value)
-            self._check_blocks(rc, "cbc_gpu_decode_pileup", results)
-            self._add_ms("_pileup_ms", "cbc_gpu_last_pileup_ms", 4, must=True)
-            out.append(text[:int(nbytes.value)].tobytes())
-            n_lines += int(nl.value); n_kept += int(nk.value); allres.append(res)
-        text = b"".join(out)
-        if results:
-            return text, n_lines, n_kept, self._cat(allres)
-        return text
+        return self._decode_windows(plan, region, results, text_cap, "cbc_gpu_decode_pileup",
+                                    lambda sel: (sel.smax, int(exclude_flags), int(min_alt), epr),
+                                    lambda sel: plan.pileup_text_cap(sel.b0, sel.b1, sel.contig, sel.beg, sel.end, sel.smax),
+                                    "last_pileup_text_bytes", "_pileup_ms", "cbc_gpu_last_pileup_ms")
+
+    def _summed_ms(self, attr, what):
+        """The kernel milliseconds _add_ms summed in self.<attr>; CbcGpuError while no <what> has run."""
+        ms = getattr(self, attr, None)
+        if ms is None:
+            raise CbcGpuError("no %s has run on the device" % what)
+        return ms
 
     def last_pileup_ms(self):
         """(edits decode, zero + mark + events, scans, text) kernel milliseconds of the last decode_pileup, summed over its calls."""
-        if getattr(self, "_pileup_ms", None) is None:
-            raise CbcGpuError("no decode_pileup has run on the device")
-        return self._pileup_ms
+        return self._summed_ms("_pileup_ms", "decode_pileup")
 
     def decode_blocks_edits(self, plan: "host.UnpackPlan", smax, edits_per_read=None):
         """decode_blocks_span with the alignment of the reads with indels kept as well (cbc_gpu_decode_blocks_edits).  Returns
@@ -915,24 +885,18 @@ class Encoder:
     def last_coverage_ms(self):
         """(decode, mark, scan + compact, weights, weight scans, prefixes, lookup) kernel milliseconds of the last
         decode_coverage, summed over its calls."""
-        if getattr(self, "_coverage_ms", None) is None:
-            raise CbcGpuError("no decode_coverage has run on the device")
-        return self._coverage_ms
+        return self._summed_ms("_coverage_ms", "decode_coverage")
 
     def last_coverage_ext_ms(self):
         """Kernel milliseconds of the last decode_coverage with thresholds or count_reads, summed over its calls: the seven of
         last_coverage_ms (the mark also notes where the pieces start), then the start points (tile sums, scans, compact), the
         thresholds' weights, their scans, their prefixes, the lookup."""
-        if getattr(self, "_coverage_ext_ms", None) is None:
-            raise CbcGpuError("no decode_coverage with thresholds or count_reads has run on the device")
-        return self._coverage_ext_ms
+        return self._summed_ms("_coverage_ext_ms", "decode_coverage with thresholds or count_reads")
 
     def last_coverage_quant_ms(self):
         """Kernel milliseconds of the last decode_coverage_quant, summed over its calls: the twelve of
         last_coverage_ext_ms, then the selection pass."""
-        if getattr(self, "_coverage_quant_ms", None) is None:
-            raise CbcGpuError("no decode_coverage_quant has run on the device")
-        return self._coverage_quant_ms
+        return self._summed_ms("_coverage_quant_ms", "decode_coverage_quant")
 
     def decode_depth_hist(self, plan: "host.UnpackPlan", targets=None, exclude_flags=0, max_depth=0, results=False):
         """Depth histogram (cbc_gpu_decode_depth_hist): per contig how many positions have each depth; depth as decode_depth
@@ -987,9 +951,7 @@ class Encoder:
     def last_hist_ms(self):
         """(decode, mark, scan + compact, zero + accumulate, bin compaction) kernel milliseconds of the last decode_depth_hist,
         summed over its calls."""
-        if getattr(self, "_hist_ms", None) is None:
-            raise CbcGpuError("no decode_depth_hist has run on the device")
-        return self._hist_ms
+        return self._summed_ms("_hist_ms", "decode_depth_hist")
 
     def decode_stats(self, plan: "host.UnpackPlan", targets=None, exclude_flags=0, results=False):
         """Read statistics (cbc_gpu_decode_stats): the count tables of a first look at the reads, filled on the device in one pass
@@ -999,47 +961,18 @@ class Encoder:
         rows A, C, G, T, other by sequencing cycle), uint32 arrays.  A selection without blocks runs nothing and gives all-zero
         tables.  With results=True returns (that dict, the per-block decode results) and lets a failed block pass (the tables are
         all zero then); otherwise it raises CbcGpuError."""
-        plan.sam_header()                                     # refuses what the coordinates cannot carry, and long-read containers
-        if not 0 <= int(exclude_flags) <= 0xffff:
-            raise ValueError("exclude_flags is a FLAG mask in 0 .. 65535")
-        self._stats_ms = None
-        st = host.GpuStats()
-        nb = plan.n_blocks if targets is None else len(targets.blocks)
-        res = np.zeros(nb, dtype=host.RESULT_DTYPE)
-        if nb:
-            caps, pay, _, _ = self._plan_args(plan)
-            tg = None
-            if targets is None:
-                blocks, ws, _ = self._gather(plan, slice(0, nb))
-            else:
-                blocks, ws, _, biv = self._gather(plan, targets.blocks, targets.block_iv)
-                iv = np.ascontiguousarray(targets.iv, dtype=np.uint32)
-                tg = GpuTargets(iv.ctypes.data, biv.ctypes.data, targets.n_iv, targets.smax)
-            rc = lib().cbc_gpu_decode_stats(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps), ws.ctypes.data,
-                                            ctypes.byref(tg) if tg is not None else None, int(exclude_flags), ctypes.byref(st),
-                                            res.ctypes.data)
-            self._check_blocks(rc, "cbc_gpu_decode_stats", results)
-            self._add_ms("_stats_ms", "cbc_gpu_last_stats_ms", 2)
-        out = dict(reads=int(st.reads), excluded=int(st.excluded), flag=np.ctypeslib.as_array(st.flag).copy(),
-                   len=np.ctypeslib.as_array(st.len).copy(), gc=np.ctypeslib.as_array(st.gc).copy(),
-                   cyc=np.ctypeslib.as_array(st.cyc).copy().reshape(5, 256))
-        return (out, res) if results else out
+        return self._decode_stats(plan, targets, exclude_flags, results, False, None)
 
-    def decode_stats_aln(self, plan: "host.UnpackPlan", targets=None, exclude_flags=0, edits_per_read=None, results=False):
-        """Read statistics with the alignment tables (cbc_gpu_decode_stats_aln): decode_stats behind the edit-reporting decoder and
-        one more pass that counts how the counted reads agree with the reference, in the view of decode_sam(cigar=True).  Returns
-        (the dict of decode_stats, the alignment dict): reads, invalid (int), len, mm, unal, ins_cyc, del_cyc (257,), nm (767,)
-        uint32 and ins_len, del_len (256,) uint64 -- the cycle tables indexed by the 1-based sequencing cycle.  edits_per_read as
-        for decode_pileup (None: the default).  A selection without blocks runs nothing and gives all-zero tables.  With
-        results=True returns (stats, aln, the per-block decode results) and lets a failed block pass (all tables zero then);
-        otherwise it raises CbcGpuError."""
-        plan.sam_header()
+    def _decode_stats(self, plan, targets, exclude_flags, results, aln, edits_per_read):
+        """decode_stats, and with aln=True decode_stats_aln."""
+        plan.sam_header()                                     # refuses what the coordinates cannot carry, and long-read containers
         if not 0 <= int(exclude_flags) <= 0xffff:
             raise ValueError("exclude_flags is a FLAG mask in 0 .. 65535")
         per_read = 0 if edits_per_read is None else int(edits_per_read)
         if edits_per_read is not None and not 1 <= per_read <= 510:
             raise ValueError("edits_per_read is in 1 .. 510")
-        self._stats_aln_ms = None
+        ms_attr = "_stats_aln_ms" if aln else "_stats_ms"
+        setattr(self, ms_attr, None)
         st, al = host.GpuStats(), host.GpuStatsAln()
         nb = plan.n_blocks if targets is None else len(targets.blocks)
         res = np.zeros(nb, dtype=host.RESULT_DTYPE)
@@ -1052,43 +985,51 @@ class Encoder:
                 blocks, ws, _, biv = self._gather(plan, targets.blocks, targets.block_iv)
                 iv = np.ascontiguousarray(targets.iv, dtype=np.uint32)
                 tg = GpuTargets(iv.ctypes.data, biv.ctypes.data, targets.n_iv, targets.smax)
-            rc = lib().cbc_gpu_decode_stats_aln(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
-                                                ws.ctypes.data, ctypes.byref(tg) if tg is not None else None,
-                                                plan.max_read_len + plan.read_length - 1, int(exclude_flags), per_read,
-                                                ctypes.byref(st), ctypes.byref(al), res.ctypes.data)
-            self._check_blocks(rc, "cbc_gpu_decode_stats_aln", results)
-            self._add_ms("_stats_aln_ms", "cbc_gpu_last_stats_aln_ms", 3)
-        out = dict(reads=int(st.reads), excluded=int(st.excluded), flag=np.ctypeslib.as_array(st.flag).copy(),
-                   len=np.ctypeslib.as_array(st.len).copy(), gc=np.ctypeslib.as_array(st.gc).copy(),
-                   cyc=np.ctypeslib.as_array(st.cyc).copy().reshape(5, 256))
-        aln = host.stats_aln_dict(al)
-        return (out, aln, res) if results else (out, aln)
+            head = (self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps), ws.ctypes.data,
+                    ctypes.byref(tg) if tg is not None else None)
+            if aln:
+                rc = lib().cbc_gpu_decode_stats_aln(*head, plan.max_read_len + plan.read_length - 1, int(exclude_flags), per_read,
+                                                    ctypes.byref(st), ctypes.byref(al), res.ctypes.data)
+            else:
+                rc = lib().cbc_gpu_decode_stats(*head, int(exclude_flags), ctypes.byref(st), res.ctypes.data)
+            self._check_blocks(rc, "cbc_gpu_decode_stats_aln" if aln else "cbc_gpu_decode_stats", results)
+            self._add_ms(ms_attr, "cbc_gpu_last_stats_aln_ms" if aln else "cbc_gpu_last_stats_ms", 3 if aln else 2)
+        out = (dict(reads=int(st.reads), excluded=int(st.excluded), flag=np.ctypeslib.as_array(st.flag).copy(),
+                    len=np.ctypeslib.as_array(st.len).copy(), gc=np.ctypeslib.as_array(st.gc).copy(),
+                    cyc=np.ctypeslib.as_array(st.cyc).copy().reshape(5, 256)),)
+        if aln:
+            out += (host.stats_aln_dict(al),)
+        if results:
+            return out + (res,)
+        return out if aln else out[0]
+
+    def decode_stats_aln(self, plan: "host.UnpackPlan", targets=None, exclude_flags=0, edits_per_read=None, results=False):
+        """Read statistics with the alignment tables (cbc_gpu_decode_stats_aln): decode_stats behind the edit-reporting decoder and
+        one more pass that counts how the counted reads agree with the reference, in the view of decode_sam(cigar=True).  Returns
+        (the dict of decode_stats, the alignment dict): reads, invalid (int), len, mm, unal, ins_cyc, del_cyc (257,), nm (767,)
+        uint32 and ins_len, del_len (256,) uint64 -- the cycle tables indexed by the 1-based sequencing cycle.  edits_per_read as
+        for decode_pileup (None: the default).  A selection without blocks runs nothing and gives all-zero tables.  With
+        results=True returns (stats, aln, the per-block decode results) and lets a failed block pass (all tables zero then);
+        otherwise it raises CbcGpuError."""
+        return self._decode_stats(plan, targets, exclude_flags, results, True, edits_per_read)
 
     def last_stats_aln_ms(self):
         """(edits decode, zeroing + statistics pass, alignment pass) kernel milliseconds of the last decode_stats_aln."""
-        if getattr(self, "_stats_aln_ms", None) is None:
-            raise CbcGpuError("no decode_stats_aln has run on the device")
-        return self._stats_aln_ms
+        return self._summed_ms("_stats_aln_ms", "decode_stats_aln")
 
     def last_stats_ms(self):
         """(decode, zeroing + statistics pass) kernel milliseconds of the last decode_stats."""
-        if getattr(self, "_stats_ms", None) is None:
-            raise CbcGpuError("no decode_stats has run on the device")
-        return self._stats_ms
+        return self._summed_ms("_stats_ms", "decode_stats")
 
     def last_targets_ms(self):
         """(decode, count + scan or mark, depth scan + compact or 0, text) kernel milliseconds of the last decode_targets,
         summed over its calls."""
-        if getattr(self, "_targets_ms", None) is None:
-            raise CbcGpuError("no decode_targets has run on the device")
-        return self._targets_ms
+        return self._summed_ms("_targets_ms", "decode_targets")
 
     def last_depth_ms(self, _one=False):
         """(decode, mark, scan + compact, text) kernel milliseconds of the last decode_depth, summed over its calls."""
         if not _one:
-            if getattr(self, "_depth_ms", None) is None:
-                raise CbcGpuError("no decode_depth has run on the device")
-            return self._depth_ms
+            return self._summed_ms("_depth_ms", "decode_depth")
         return self._last_ms("cbc_gpu_last_depth_ms", 4, must=True)
 
     def last_sam_ms(self):

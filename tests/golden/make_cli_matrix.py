@@ -47,6 +47,7 @@ VALUES = ["", "x", "0", "1", "0x10", "-1", "65535", "65536", "4294967295", "4294
 # the decode modes that take several regions or a BED file, as the options that select them
 SEVERAL = [[], ["--sam"], ["--depth"], ["--bedcov"], ["--depth-hist"], ["--stats"]]
 ALL_MODES = SEVERAL                                          # with a single --region: the single-region functions too
+EDITS_MODES = [["--pileup"], ["--sam", "--cigar"], ["--stats", "--alignment"]]
 NOT_A_CONTAINER = ["stream.bin", "out.txt", "ref.fa"]
 CONTAINER = ["reads.cbc", "out.txt", "ref.fa"]
 
@@ -73,13 +74,10 @@ def cpu_cases():
         for v in VALUES:
             add("value", ["-x", owner, opt, v] + NOT_A_CONTAINER)
     run = ["-x", "--verbose"]
-    for mode in SEVERAL:
+    def beds(mode):
         for bed in ("empty.bed", "unknown.bed", "missing.bed"):
             add("run", run + mode + ["--regions-file", bed] + CONTAINER)
-    for bed in ("empty.bed", "unknown.bed"):
-        add("run", run + ["--bedcov", "--window", "100", "--regions-file", bed] + CONTAINER)
-        add("run", run + ["--bedcov", "--thresholds", "1,5", "--count-reads", "--regions-file", bed] + CONTAINER)
-    for mode in ALL_MODES:
+    def regions(mode):
         for region in ("chrX", "chrX:5-9", "chr1:5-x", "chr1:9-5", "chr1:0-5", "chr1:1-1"):
             add("run", run + mode + ["--region", region] + CONTAINER)
         add("run", run + mode + ["--region", "chrX", "--region", "chr1:5-x"] + CONTAINER)
@@ -88,6 +86,18 @@ def cpu_cases():
             add("run", run + mode + sel + ["missing.cbc", "out.txt", "ref.fa"])
             add("run", run + mode + sel + ["reads.cbc", "out.txt", "missing.fa"])
             add("run", run + mode + sel + ["reads.cbc", "no_such_dir/out.txt", "ref.fa"])
+    for mode in SEVERAL:
+        beds(mode)
+    for bed in ("empty.bed", "unknown.bed"):
+        add("run", run + ["--bedcov", "--window", "100", "--regions-file", bed] + CONTAINER)
+        add("run", run + ["--bedcov", "--thresholds", "1,5", "--count-reads", "--regions-file", bed] + CONTAINER)
+    for mode in ALL_MODES:
+        regions(mode)
+    # the modes behind the edits decoder came later: their cases stand behind the older ones, whose ids and order stay
+    for mode in EDITS_MODES:
+        beds(mode)
+    for mode in EDITS_MODES:
+        regions(mode)
     return out
 
 
@@ -113,6 +123,12 @@ def gpu_cases():
                  ["--depth-hist", "--regions-file", "mixed.bed", "--hist-max", "3", "--depth-exclude-flags", "16"]],
         "stats": [["--stats"], ["--stats", "--region", "chr1:100-400"], ["--stats", "--regions-file", "late.bed"],
                   ["--stats", "--regions-file", "mixed.bed", "--stats-exclude-flags", "16"]],
+        "pileup": [["--pileup"], ["--pileup", "--region", "chr1:100-400"],
+                   ["--pileup", "--min-alt", "2", "--max-edits-per-read", "32", "--depth-exclude-flags", "16"]],
+        "sam_cigar": [["--sam", "--cigar"], ["--sam", "--cigar", "--region", "chr1:100-400"], ["--sam", "--cigar", "--region", "chr2:50-300"]],
+        "stats_aln": [["--stats", "--alignment"], ["--stats", "--alignment", "--region", "chr1:100-400"],
+                      ["--stats", "--alignment", "--regions-file", "late.bed"],
+                      ["--stats", "--alignment", "--regions-file", "mixed.bed", "--stats-exclude-flags", "16"]],
     }
     return {m: [("%s/%d %s" % (m, i, " ".join(a)), run + a + CONTAINER) for i, a in enumerate(v)] for m, v in modes.items()}
 
