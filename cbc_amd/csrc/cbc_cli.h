@@ -6,6 +6,10 @@
 #define CBC_CLI_H
 #include <stdint.h>
 
+/* --skip-deletions: from here on --depth, --bedcov and --depth-hist count aligned bases only (cbc_gpu_set_depth_skip_deletions on
+ * every device they open) with edits_per_read arena entries per read, 1..510; 0: off, the default */
+void cbc_cli_skip_deletions(uint32_t edits_per_read);
+
 /* every read, one per line; either file format; contiguous block ranges over the listed devices */
 int cbc_cli_decompress(const char *in, const char *out, const char *ref, const int *devs, int ndev);
 

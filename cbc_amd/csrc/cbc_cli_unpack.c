@@ -195,6 +195,11 @@ static int cli_open(cli_run *r, const char *in, const char *ref, const char *bed
     return 0;
 }
 
+/* --skip-deletions: a setting of the run, as the library has it a setting of the context; the depth
+ * modes read it for their text bounds and their messages, cli_device hands it to the device it opens */
+static uint32_t g_skip_edits = 0;
+void cbc_cli_skip_deletions(uint32_t edits_per_read) { g_skip_edits = edits_per_read; }
+
 /* the device, opened and given the reference when the first call needs it: a selection without blocks needs none */
 static int cli_device(cli_run *r)
 {
@@ -203,6 +208,7 @@ static int cli_device(cli_run *r)
     const int rc = cbc_gpu_init(r->device, &r->ctx);
     if (rc) { fprintf(stderr, "cbc: no usable MI355X (cbc_gpu_init = %d); there is no CPU fallback\n", rc); return 1; }
     if (cbc_gpu_upload_reference(r->ctx, r->u->ref, r->u->ref_bytes)) { fprintf(stderr, "cbc: %s\n", cbc_gpu_last_error(r->ctx)); return 1; }
+    if (g_skip_edits && cbc_gpu_set_depth_skip_deletions(r->ctx, g_skip_edits)) { fprintf(stderr, "cbc: --skip-deletions: %s\n", cbc_gpu_last_error(r->ctx)); return 1; }
     r->used = 1;
     r->t_init = now2() - a;
     return 0;
@@ -364,7 +370,9 @@ int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int
  * pu != NULL, `--pileup`: what the reads show at the positions where they disagree with the reference,
  * counted and formatted on the device (cbc_gpu_decode_pileup), the calls as for --depth.  A call starts with a buffer of 64 MiB
  * + 64 bytes per read of its blocks (or the bound, if that is less); the library reports the size of a text that does not fit,
- * and the call is made once more with exactly that. */
+ * and the call is made once more with exactly that.
+ * --skip-deletions: the depth of the aligned bases alone; its bound is a line per position, not two per
+ * read, so its buffer is handled as the pileup's. */
 typedef struct cli_pileup { uint32_t min_alt, edits_per_read; } cli_pileup;
 
 static int decompress_window(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,
@@ -400,12 +408,14 @@ static int decompress_window(const char *in, const char *out, const char *ref, i
         if (cli_device(&r)) return 1;
         const double b = now2();
         const char *nm = u->names + u->contig_name_off[s->contig];
+        const int capped = pu || g_skip_edits;            /* a bound per position: start smaller, repeat once at the text's size */
         const uint64_t bound = pu ? cbc_unpack_pileup_text_cap(u, s->b0, s->b1, s->contig, s->beg, s->end, s->smax)
-                                  : cbc_unpack_depth_text_cap(u, s->b0, s->b1, s->contig);
+                             : g_skip_edits ? cbc_unpack_depth_skipdel_text_cap(u, s->b0, s->b1, s->contig, s->beg, s->end, s->smax)
+                                            : cbc_unpack_depth_text_cap(u, s->b0, s->b1, s->contig);
         uint64_t cap = bound, first = 64ull << 20, tb = 0, nl = 0, nk = 0;
         for (uint32_t q = s->b0; q < s->b1; q++) first += 64ull * u->blocks[q].n_reads;
-        if (pu && first < cap) cap = first;
-        for (int attempt = 0; attempt < (pu ? 2 : 1); attempt++) {
+        if (capped && first < cap) cap = first;
+        for (int attempt = 0; attempt < (capped ? 2 : 1); attempt++) {
             if (cap > have || !text) { free(text); text = (char *)malloc((size_t)cap + 1); have = cap; }
             if (!text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
             rc = pu ? cbc_gpu_decode_pileup(r.ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
@@ -431,8 +441,10 @@ static int decompress_window(const char *in, const char *out, const char *ref, i
     if (verbose) {
         printf("%s: %llu text bytes, exclude flags 0x%x", mode, (unsigned long long)total, exclude);
         if (pu) printf(", min alt %u, edits per read %u", pu->min_alt, pu->edits_per_read ? pu->edits_per_read : CBC_EDITS_PER_READ);
+        else if (g_skip_edits) printf(", deleted bases not counted, edits per read %u", g_skip_edits);
         printf("\ntime: read + plan %.3f s, device init + reference upload %.3f s, decode + %s + write %.3f s\n", r.t1 - r.t0, r.t_init, mode, r.t_dev);
         if (r.used) printf(pu ? "kernels: edits decode %.3f ms, mark + events %.3f ms, scans %.3f ms, text %.3f ms\n"
+                              : g_skip_edits ? "kernels: edits decode %.3f ms, mark + unmark %.3f ms, scan + compact %.3f ms, text %.3f ms\n"
                               : "kernels: decode %.3f ms, mark %.3f ms, scan + compact %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
     }
     free(text); free(sels);
@@ -471,9 +483,22 @@ int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref,
     const uint32_t nb = T->n_blocks;
     cbc_dec_block_desc *bl; uint64_t *ws; uint32_t *bc;
     if (cli_gather(u, T->blocks, nb, &bl, &ws, &bc)) return 1;
-    uint64_t cap = 0;
-    if (depth) { for (uint32_t c = 0; c < u->n_contigs; c++) { const uint64_t x = cbc_unpack_targets_depth_cap(u, T, c); if (x > cap) cap = x; } }
-    else cap = cbc_unpack_targets_text_cap(u, T, sam);
+    /* --depth --skip-deletions: the bound is a line per position of the intervals; the buffer starts at 64 MiB + 64 bytes per read,
+     * and a call whose text does not fit is made once more with exactly its size (as decompress_window does) */
+    const int capped = depth && g_skip_edits;
+    uint64_t cap = 0, bound = 0;
+    if (depth) {
+        for (uint32_t c = 0; c < u->n_contigs; c++) {
+            const uint64_t x = capped ? cbc_unpack_targets_depth_skipdel_cap(u, T, c) : cbc_unpack_targets_depth_cap(u, T, c);
+            if (x > cap) cap = x;
+        }
+    } else cap = cbc_unpack_targets_text_cap(u, T, sam);
+    bound = cap;
+    if (capped) {
+        uint64_t first = 64ull << 20;
+        for (uint32_t k = 0; k < nb; k++) first += 64ull * bl[k].n_reads;
+        if (first < cap) cap = first;
+    }
     char *text = (char *)malloc((size_t)hdr + (size_t)cap + 1);
     if (!text || (hdr && cbc_unpack_sam_header(u, text, (uint64_t)hdr, err, sizeof err) != hdr)) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
     r.t1 = now2();
@@ -489,8 +514,15 @@ int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref,
         const double b = now2();
         const cbc_gpu_targets g = { (const uint32_t *)T->iv, T->block_iv + 2 * (size_t)k0, T->n_iv, T->smax };
         uint64_t tb = 0, nr = 0, nn = 0;
-        rc = cbc_gpu_decode_targets(r.ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
-                                    u->contig_name_off, u->n_contigs, &g, output, exclude, (uint8_t *)text, cap, &tb, &nr, &nn, NULL);
+        for (int attempt = 0; attempt < (capped ? 2 : 1); attempt++) {
+            rc = cbc_gpu_decode_targets(r.ctx, u->payloads, u->payload_bytes, bl + k0, kn, &u->caps, ws + k0, bc + k0, u->names, u->names_bytes,
+                                        u->contig_name_off, u->n_contigs, &g, output, exclude, (uint8_t *)text, cap, &tb, &nr, &nn, NULL);
+            if (!(rc == CBC_E_ARG && tb > cap && tb <= bound)) break;
+            cap = tb;                                   /* the text's own size; no header in front of a depth text */
+            char *t2 = (char *)realloc(text, (size_t)cap + 1);
+            if (!t2) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
+            text = t2;
+        }
         if (rc) { fprintf(stderr, "cbc: targets decode failed: %s\n", cbc_gpu_last_error(r.ctx)); return 1; }
         r.t_dev += now2() - b;
         if (verbose && cbc_gpu_last_targets_ms(r.ctx, &m[0], &m[1], &m[2], &m[3]) == 0) add_ms(ms, m, 4);

@@ -53,8 +53,14 @@ struct cbc_depth_args {
 };
 
 /* ---- mark ------------------------------------------------------------------------------------------------------------ */
-template <class W>
-CBC_FN void cbc_depth_mark(const cbc_depth_args &A, uint32_t blk)
+/* U: what is done with the kept reads.  cbc_mark_only (the default, the mark pass): +1 / -1 at the ends of every kept read's
+ * piece, and the count of the kept.  A U with unmark = true (the unmark pass of cbc_skipdel_body.h) is handed the same reads
+ * instead -- U::reads<W>(p, sub, r0, k, lp, span, i0, i1): group r0's keep flags, local POS, span and pieces [i0, i1) behind p --
+ * and neither marks nor counts: the keep rule and the clipping are this one text for both passes, so they cannot drift apart. */
+struct cbc_mark_only { static const bool unmark = false; template <class W, class... T> CBC_MFN void reads(const T &...) {} };
+
+template <class W, class U = cbc_mark_only>
+CBC_FN void cbc_depth_mark(const cbc_depth_args &A, uint32_t blk, U *u = NULL)
 {
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
@@ -82,10 +88,12 @@ CBC_FN void cbc_depth_mark(const cbc_depth_args &A, uint32_t blk)
         const V32 e = W::select((span - 1u) >= (W::splat(B.hi) - lp), W::splat(B.hi), lp + (span - 1u));
         const V32 i0 = s - sub, i1 = (e - sub) + 1u;
         k = k & (i1 > i0) & (i1 <= rem);
+        if (U::unmark) { u->template reads<W>(p, sub, r0, k, lp, span, i0, i1); continue; }
         W::list_add(p, i0, W::splat(1u), k);
         W::list_add(p, i1, W::splat(0xffffffffu), k);
         kept += W::popc64(W::ballot(k));
     }
+    if (U::unmark) return;
     W::list_add(A.ctr, W::splat(0u), W::splat(kept), ln == 0u);
 }
 

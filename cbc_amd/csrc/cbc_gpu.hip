@@ -29,6 +29,7 @@
 #include "cbc_hist_body.h"
 #include "cbc_stats_body.h"
 #include "cbc_pileup_body.h"
+#include "cbc_skipdel_body.h"
 #include "cbc_cigar_body.h"
 #include "cbc_stats_aln_body.h"
 #include "cbc_plan.h"
@@ -102,6 +103,16 @@ cbc_decode_blocks_edits_kernel(cbc_dec_args A, uint32_t smax, cbc_dec_edits E)
     uint32_t blk = blockIdx.x;
     if (blk >= A.n_blocks) return;
     cbc_decode_stream<WaveGPU, true, true>(A, blk, cbc_lds, smax, &E);
+}
+__global__ void __launch_bounds__(64 * CBC_SKIPDEL_WAVES)
+cbc_skipdel_unmark_kernel(cbc_skipdel_args A)
+{
+    if (blockIdx.x < A.D.R.n_blocks) cbc_skipdel_unmark<WaveGPU>(A, blockIdx.x, WaveGPU::uni(threadIdx.x >> 6), CBC_SKIPDEL_WAVES);
+}
+__global__ void __launch_bounds__(64 * CBC_SKIPDEL_WAVES)
+cbc_skipdel_targets_unmark_kernel(cbc_tskipdel_args A)
+{
+    if (blockIdx.x < A.T.D.R.n_blocks) cbc_skipdel_targets_unmark<WaveGPU>(A, blockIdx.x, WaveGPU::uni(threadIdx.x >> 6), CBC_SKIPDEL_WAVES);
 }
 __global__ void __launch_bounds__(64 * CBC_PILEUP_WAVES)
 cbc_pileup_events_kernel(cbc_pileup_args A)
@@ -456,6 +467,8 @@ struct cbc_gpu_ctx {
                                     * weights, their scans, their prefixes and the lookup */
     hipEvent_t ev_hist[2];         /* cbc_gpu_decode_depth_hist: behind ev_rg[3], after zeroing + accumulate and after the bin compaction */
     hipEvent_t ev_quant;           /* cbc_gpu_decode_coverage_quant: behind ev_covx[4], after the selection */
+    uint32_t skipdel_edits;        /* cbc_gpu_set_depth_skip_deletions: > 0, the depth kinds count aligned bases only, behind the edits
+                                    * decoder with that many arena entries per read; 0 (the default): the span depth */
     post_kind last_post;           /* whose times those events hold: the kind of the most recent call with a post-decode stage
                                     * (POST_NONE: none yet), set by decode_blocks_impl and asked by the cbc_gpu_last_*_ms */
     int have_timing;
@@ -1184,10 +1197,13 @@ struct post_req {
      * contig's first reference byte; NONE (cbc_gpu_decode_blocks_edits): where the side array (2 words per record) and the arena go */
     uint32_t edits_per_read, min_alt; uint64_t ref_c0;
     uint32_t *edit_side; uint16_t *edit_arena;
+    /* the depth kinds but PILEUP, under cbc_gpu_set_depth_skip_deletions: deleted bases do not count -- the
+     * edits decoder (edits_per_read is set with it) and the unmark stage behind the mark kernel */
+    bool skip_del;
 };
 
 /* sizes derived from the request: tiles of the difference array (d_words = W + 1 words), change points (two per read at most,
- * two per interval edge; start points: one per read and interval), text tiles of the runs, entries the text's size scan runs over; histogram: min(fold, reads) + 1 bins
+ * two per interval edge -- more under skip_del, see post_sizes_of; start points: one per read and interval), text tiles of the runs, entries the text's size scan runs over; histogram: min(fold, reads) + 1 bins
  * in whole tiles, the non-zero ones are fewer than the bins and than the runs */
 struct post_sizes { uint64_t d_words, h_bins; uint32_t n_tiles, cp_cap, n_ttiles, n_sized, n_btiles, h_out_cap, sp_cap; };
 
@@ -1201,6 +1217,20 @@ static post_sizes post_sizes_of(const post_req *rg, uint32_t n_blocks, uint64_t 
     z.d_words = tg ? rg->iv_off[rg->n_iv] : rg->end - rg->beg + 2u;
     z.n_tiles = (uint32_t)((z.d_words + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
     z.cp_cap = (uint32_t)(2u * n_recs + (tg ? 2u * (uint64_t)rg->n_iv : 0u));
+    if (rg->skip_del) {
+        /* Change points under skip_del.  A change point is a non-zero word of the difference array, and a word is non-zero only
+         * where somebody added to it.  The mark pass adds at two words per kept piece: at most 2 * n_recs (+ 2 * n_iv in the
+         * compressed coordinate: the bound the span depth has).  The unmark pass adds at two words per deleted base it counts
+         * (x and x + 1; neighbours share one, which only lowers the number), and it counts no base that has no arena entry.  A
+         * block's arena holds at most n * edits_per_read entries -- a block that needs more has failed with CBC_ST_EDITS and
+         * contributes nothing (cbc_region_block), and a hostile side array is held to the block's part of the arena by
+         * cbc_edits_read_ok -- so the deleted bases of a call are at most n_recs * edits_per_read and the words at most
+         * 2 * n_recs * (1 + edits_per_read) (+ 2 * n_iv).  No more words than the array has can be non-zero: min with d_words.
+         * n_recs < 2^30 and edits_per_read <= 510: the product stays inside 64 bits, and d_words <= 2^31 + 2^24 + 1 fits the
+         * 32-bit tables.  The compact pass refuses a tile that would write past cp_cap (cbc_depth_compact). */
+        const uint64_t by_edits = 2u * n_recs * (1u + (uint64_t)rg->edits_per_read) + (tg ? 2u * (uint64_t)rg->n_iv : 0u);
+        z.cp_cap = (uint32_t)(by_edits < z.d_words ? by_edits : z.d_words);
+    }
     z.n_ttiles = (z.cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
     if (rg->kind == POST_PILEUP) { z.cp_cap = 0; z.n_ttiles = z.n_tiles; }
     z.n_sized = z.n_ttiles;
@@ -1211,6 +1241,16 @@ static post_sizes post_sizes_of(const post_req *rg, uint32_t n_blocks, uint64_t 
     z.n_btiles = (uint32_t)((z.h_bins + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
     z.h_out_cap = (uint32_t)(z.h_bins - 1u < z.cp_cap ? z.h_bins - 1u : z.cp_cap);
     return z;
+}
+
+/* no device memory for an arena that grows with the change points: under skip_del the message names the option that grew it */
+static int nomem_points(cbc_gpu_ctx *ctx, const post_req *rg, const char *what)
+{
+    char msg[256];
+    (void)hipGetLastError();
+    snprintf(msg, sizeof msg, "%s%s", what, rg->skip_del ? "; skip_deletions (--skip-deletions) sizes the change points by edits_per_read: "
+             "lower edits_per_read (--max-edits-per-read) or take a smaller window" : "");
+    return set_err(ctx, CBC_E_NOMEM, msg, hipSuccess);
 }
 
 /* post stage, step 1: its arenas */
@@ -1229,7 +1269,8 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
         }
         NEED(A_DTILE, (uint64_t)z.n_tiles * 2 * sizeof(cbc_block_result), "hipMalloc depth tiles");
         NEED(A_DTOFF, ((uint64_t)z.n_tiles + 1) * 2 * 8, "hipMalloc depth tile offsets");
-        NEED(A_DCP, (uint64_t)z.cp_cap * 2 * 4 + 16, "hipMalloc depth change points");
+        if (arena_need(ctx, A_DCP, (uint64_t)z.cp_cap * 2 * 4 + 16, "hipMalloc depth change points"))
+            return nomem_points(ctx, rg, "no device memory for the depth's change points (8 bytes each)");
         NEED(A_DCTR, 16, "hipMalloc depth counters");
         NEED(A_SNAMES, (uint64_t)rg->names_bytes + 16, "hipMalloc contig name");
     }
@@ -1244,10 +1285,8 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
     }
     if (post_is_cov(k)) {
         NEED(A_CVTILE, (uint64_t)z.n_ttiles * 3 * sizeof(cbc_block_result) + ((uint64_t)z.n_ttiles + 1) * 3 * 8, "hipMalloc coverage tiles");
-        if (arena_need(ctx, A_CVPRE, (uint64_t)z.cp_cap * 12 + 16, "hipMalloc coverage prefixes")) {
-            (void)hipGetLastError();
-            return set_err(ctx, CBC_E_NOMEM, "no device memory for the coverage prefixes (12 bytes per change point)", hipSuccess);
-        }
+        if (arena_need(ctx, A_CVPRE, (uint64_t)z.cp_cap * 12 + 16, "hipMalloc coverage prefixes"))
+            return nomem_points(ctx, rg, "no device memory for the coverage prefixes (12 bytes per change point)");
         NEED(A_CVQ, (uint64_t)rg->cov.n_q * 8 + 16, "hipMalloc coverage queries");
         NEED(A_CVOUT, (uint64_t)rg->cov.n_q * 12 + 16, "hipMalloc coverage results");
     }
@@ -1263,10 +1302,8 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
         }
         if (cv->n_thr) {
             NEED(A_XTHR, (uint64_t)cv->n_thr * (z.n_ttiles * sizeof(cbc_block_result) + ((uint64_t)z.n_ttiles + 1) * 8), "hipMalloc threshold tiles");
-            if (arena_need(ctx, A_XPRE, (uint64_t)z.cp_cap * 4 * cv->n_thr + 16, "hipMalloc threshold prefixes")) {
-                (void)hipGetLastError();
-                return set_err(ctx, CBC_E_NOMEM, "no device memory for the threshold prefixes (4 bytes per threshold and change point)", hipSuccess);
-            }
+            if (arena_need(ctx, A_XPRE, (uint64_t)z.cp_cap * 4 * cv->n_thr + 16, "hipMalloc threshold prefixes"))
+                return nomem_points(ctx, rg, "no device memory for the threshold prefixes (4 bytes per threshold and change point)");
         }
         NEED(A_XOUT, (uint64_t)cv->n_q * 4 * (cv->n_thr + 1ull + (k == POST_COVQ ? cv->n_quant : 0u)) + 16, "hipMalloc threshold and read counts");
     }
@@ -1422,8 +1459,15 @@ static int depth_args_zeroed(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *r
     return CBC_OK;
 }
 
-/* the front of every depth kind: mark, tile sums, their two scans, the change points.  `da` and `ta` (filled for the targets
- * kinds, whose mark kernel reads the interval table) are what the tails go on with. */
+static int launch_coverage_ext(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *cov, const post_sizes &z, const cbc_depth_args &da, int reads_phase);
+
+/* the front of every depth kind: mark, (skip_del: unmark,) tile sums, their two scans, the change points.  `da` and `ta` (filled
+ * for the targets kinds, whose mark kernel reads the interval table) are what the tails go on with.  The unmark stage
+ * (cbc_skipdel_body.h) takes the deleted bases of the kept reads off the difference array, on the same stream and inside the
+ * mark stretch of the events.  The read counts of the coverage calls keep their span meaning under skip_del, and their formula
+ * reads the depth at a query's first slot (cbc_covx_body.h): so they are taken from the SPAN depth, by a first run of the passes
+ * behind the mark -- tile sums, scans, change points, then the start points and the lookup (launch_coverage_ext, phase 1) -- in
+ * front of the unmark; the passes then run again over the unmarked array. */
 static int launch_depth_front(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const post_sizes &z, const cbc_region_args &ra,
                               cbc_depth_args *da, cbc_tdepth_args *ta)
 {
@@ -1442,6 +1486,30 @@ static int launch_depth_front(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *
         } else hipLaunchKernelGGL(cbc_targets_mark_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, *ta);
     } else hipLaunchKernelGGL(cbc_depth_mark_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, *da);
     HIPCHK(hipGetLastError(), "launch cbc_depth_mark_kernel");
+    if (rg->skip_del && post_is_covx(rg->kind) && rg->cov.reads) {
+        hipLaunchKernelGGL(cbc_depth_tile_kernel, dim3(n_tiles), dim3(64), 0, ks, *da);
+        launch_scan_sizes(ks, da->tile_sum, toff, n_tiles);
+        launch_scan_sizes(ks, da->tile_cnt, toff + n_tiles + 1, n_tiles);
+        hipLaunchKernelGGL(cbc_depth_compact_kernel, dim3(n_tiles), dim3(64), 0, ks, *da);
+        HIPCHK(hipGetLastError(), "launch the span depth's change points");
+        if ((rc = launch_coverage_ext(ctx, ks, &rg->cov, z, *da, 1))) return rc;
+    }
+    if (rg->skip_del) {
+        cbc_skipdel_edits se;
+        memset(&se, 0, sizeof se);
+        se.side = (const uint32_t *)ctx->arena[A_ESIDE].p; se.arena = (const uint16_t *)ctx->arena[A_EARENA].p;
+        se.arena_entries = ra.n_recs * rg->edits_per_read; se.per_read = rg->edits_per_read;
+        if (post_is_targets(rg->kind)) {
+            cbc_tskipdel_args xa;
+            xa.T = *ta; xa.E = se;
+            hipLaunchKernelGGL(cbc_skipdel_targets_unmark_kernel, dim3(ra.n_blocks), dim3(64 * CBC_SKIPDEL_WAVES), 0, ks, xa);
+        } else {
+            cbc_skipdel_args xa;
+            xa.D = *da; xa.E = se;
+            hipLaunchKernelGGL(cbc_skipdel_unmark_kernel, dim3(ra.n_blocks), dim3(64 * CBC_SKIPDEL_WAVES), 0, ks, xa);
+        }
+        HIPCHK(hipGetLastError(), "launch cbc_skipdel_unmark_kernel");
+    }
     HIPCHK(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
     hipLaunchKernelGGL(cbc_depth_tile_kernel, dim3(n_tiles), dim3(64), 0, ks, *da);
     HIPCHK(hipGetLastError(), "launch cbc_depth_tile_kernel");
@@ -1502,10 +1570,13 @@ static int launch_coverage(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *cov,
 }
 
 /* read counts and thresholds, behind launch_coverage: the start points (tile sums, scans, compact over the starts), the
- * thresholds' weights, their scans and prefixes, the lookup.  A pass nobody asked for is not launched; its event still is. */
-static int launch_coverage_ext(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *cov, const post_sizes &z, const cbc_depth_args &da)
+ * thresholds' weights, their scans and prefixes, the lookup.  A pass nobody asked for is not launched; its event still is.
+ * reads_phase 0: all of it.  Under skip_del (launch_depth_front): 1 = the read counts alone, over the span depth's change points,
+ * in front of the unmark; 2 = everything but the read counts, which are done. */
+static int launch_coverage_ext(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *cov, const post_sizes &z, const cbc_depth_args &da, int reads_phase)
 {
-    const uint32_t n_tiles = z.n_tiles, n_ttiles = z.n_ttiles, n_thr = cov->n_thr;
+    const uint32_t n_tiles = z.n_tiles, n_ttiles = z.n_ttiles, n_thr = reads_phase == 1 ? 0u : cov->n_thr;
+    const bool want_reads = cov->reads && reads_phase != 2;
     cbc_covx_args xa;
     memset(&xa, 0, sizeof xa);
     xa.cp_pos = da.cp_pos; xa.cp_dep = da.cp_dep; xa.cnt_off = da.cnt_off;
@@ -1514,7 +1585,7 @@ static int launch_coverage_ext(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *
     xa.n_thr = n_thr; xa.cp_cap = z.cp_cap; xa.sp_cap = z.sp_cap; xa.n_tiles = n_tiles; xa.n_ttiles = n_ttiles; xa.n_q = cov->n_q;
     xa.slots = (uint32_t)z.d_words;
     for (uint32_t t = 0; t < n_thr; t++) xa.thr[t] = cov->thr[t];
-    if (cov->reads) {
+    if (want_reads) {
         cbc_depth_args sa = da;                                /* the depth passes over the starts: CS in the place of the depth */
         sa.diff = (uint32_t *)ctx->arena[A_XSTARTS].p;
         sa.tile_sum = (cbc_block_result *)ctx->arena[A_XTILE].p; sa.tile_cnt = sa.tile_sum + n_tiles;
@@ -1529,7 +1600,7 @@ static int launch_coverage_ext(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *
         hipLaunchKernelGGL(cbc_depth_compact_kernel, dim3(n_tiles), dim3(64), 0, ks, sa);
         HIPCHK(hipGetLastError(), "launch cbc_depth_compact_kernel");
         xa.sp_pos = sa.cp_pos; xa.sp_cnt = sa.cp_dep; xa.sp_off = sa.cnt_off;
-        xa.reads = xa.thr_covered + (uint64_t)cov->n_q * n_thr;
+        xa.reads = xa.thr_covered + (uint64_t)cov->n_q * cov->n_thr;
     }
     HIPCHK(hipEventRecord(ctx->ev_covx[0], ks), "hipEventRecord");
     if (n_thr) {
@@ -1548,7 +1619,7 @@ static int launch_coverage_ext(cbc_gpu_ctx *ctx, hipStream_t ks, const cov_req *
         HIPCHK(hipEventRecord(ctx->ev_covx[3], ks), "hipEventRecord");
     } else
         for (int k = 1; k < 4; k++) HIPCHK(hipEventRecord(ctx->ev_covx[k], ks), "hipEventRecord");
-    if (n_thr || cov->reads) {
+    if (n_thr || want_reads) {
         hipLaunchKernelGGL(cbc_covx_lookup_kernel, dim3((cov->n_q + 63u) / 64u), dim3(64), 0, ks, xa);
         HIPCHK(hipGetLastError(), "launch cbc_covx_lookup_kernel");
     }
@@ -1866,12 +1937,12 @@ static int decode_blocks_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                 case POST_COVX:
                     rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
                     if (!rc) rc = launch_coverage(ctx, ks, &rg->cov, z, da);
-                    if (!rc) rc = launch_coverage_ext(ctx, ks, &rg->cov, z, da);
+                    if (!rc) rc = launch_coverage_ext(ctx, ks, &rg->cov, z, da, rg->skip_del && rg->cov.reads ? 2 : 0);
                     break;
                 case POST_COVQ:
                     rc = launch_depth_front(ctx, ks, rg, z, ra, &da, &ta);
                     if (!rc) rc = launch_coverage(ctx, ks, &rg->cov, z, da);
-                    if (!rc) rc = launch_coverage_ext(ctx, ks, &rg->cov, z, da);
+                    if (!rc) rc = launch_coverage_ext(ctx, ks, &rg->cov, z, da, rg->skip_del && rg->cov.reads ? 2 : 0);
                     if (!rc) rc = launch_coverage_quant(ctx, ks, &rg->cov, z, da);
                     break;
                 case POST_HIST:
@@ -2223,6 +2294,7 @@ static int decode_window_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         edits_per_read = pu->edits_per_read;
         if ((rc = check_edits(ctx, "pileup wants ", &edits_per_read))) return rc;
     }
+    const bool skip_del = !pu && ctx->skipdel_edits != 0u;            /* cbc_gpu_set_depth_skip_deletions */
     if ((rc = check_window_name(ctx, who, name, name_bytes))) return rc;
     /* one contig: every block's window lies at the same place of the reference */
     for (uint32_t b = 0; pu && b < n_blocks; b++)
@@ -2233,15 +2305,17 @@ static int decode_window_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     if (rc) return rc;
     if (L.nrec > 0x3fffffffull) rc = layout_err(ctx, who, ": more than 2^30 - 1 reads in one call");
     else if (L.nrec) {                                         /* blocks without reads: no line */
-        /* depth: K reads give at most 2K - 1 runs; pileup: a line per position of the window at most, and per reference base a
-         * kept read spans (span <= smax) */
-        const uint64_t w = end - beg + 1u, by_reads = L.nrec * smax;
+        /* depth: K reads give at most 2K - 1 runs; pileup, and the depth under skip_del (cbc_unpack_depth_skipdel_text_cap): a line
+         * per position of the window at most, and per reference base a kept read spans (span <= smax) */
+        const uint64_t w = end - beg + 1u, by_reads = L.nrec * smax, by_pos = w < by_reads ? w : by_reads;
         post_req rg;
         post_req_init(&rg, pu ? POST_PILEUP : POST_DEPTH, smax, window_start, text, text_cap,
-                      pu ? (w < by_reads ? w : by_reads) * (name_bytes + 102ull) : (2u * L.nrec - 1u) * (name_bytes + 34ull), text_bytes, n_reads_kept);
+                      pu ? by_pos * (name_bytes + 102ull) : skip_del ? by_pos * (name_bytes + 34ull) : (2u * L.nrec - 1u) * (name_bytes + 34ull),
+                      text_bytes, n_reads_kept);
         rg.beg = beg; rg.end = end;
         rg.names = (const uint8_t *)name; rg.names_bytes = name_bytes; rg.exclude = exclude_flags; rg.n_runs = n_runs;
         if (pu) { rg.edits_per_read = edits_per_read; rg.min_alt = pu->min_alt; rg.ref_c0 = blocks[0].ref_off - window_start[0]; }
+        if (skip_del) { rg.skip_del = true; rg.edits_per_read = ctx->skipdel_edits; }
         rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
     }
     layout_free(&L);
@@ -2281,6 +2355,16 @@ API int cbc_gpu_decode_blocks_edits(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_
     memset(&rg, 0, sizeof rg);
     rg.kind = POST_NONE; rg.smax = smax; rg.edits_per_read = edits_per_read; rg.edit_side = side; rg.edit_arena = arena;
     return decode_blocks_impl(ctx, in, in_bytes, blocks, n_blocks, caps, recs, n_recs, seq, seq_bytes, NULL, NULL, NULL, 0, NULL, results, &rg);
+}
+
+/* deletion-aware coverage: a setting of the context, read by every depth kind but the pileup when its
+ * request is made (decode_window_impl, decode_targets_impl) */
+API int cbc_gpu_set_depth_skip_deletions(cbc_gpu_ctx *ctx, uint32_t edits_per_read)
+{
+    if (!ctx) return CBC_E_ARG;
+    if (edits_per_read > CBC_EDITS_MAX) return layout_err(ctx, "skip_deletions wants ", "edits_per_read in 1..510 (0: off)");
+    ctx->skipdel_edits = edits_per_read;
+    return CBC_OK;
 }
 
 /* a set of regions: the selected blocks laid out afresh as for a region decode, the tables checked
@@ -2357,7 +2441,13 @@ static int decode_targets_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
         rg.names = (const uint8_t *)names + L.bn[0]; rg.names_bytes = nl0; rg.exclude = exclude_flags; rg.n_runs = n_runs;
         if (cov) rg.cov = *cov;
         if (hist) rg.hist = *hist;
-        const uint64_t need = (2u * L.nrec + 2ull * n - 1u) * (nl0 + 34ull);   /* K reads, n intervals: at most 2K + 2n - 1 runs */
+        uint64_t need = (2u * L.nrec + 2ull * n - 1u) * (nl0 + 34ull);   /* K reads, n intervals: at most 2K + 2n - 1 runs */
+        if (ctx->skipdel_edits) {                               /* cbc_gpu_set_depth_skip_deletions: every depth kind of a target set */
+            /* a run per position of the intervals at most, and per reference base a read spans (cbc_unpack_targets_depth_skipdel_cap) */
+            const uint64_t w = run - n, by_reads = L.nrec * t->smax;
+            need = (w < by_reads ? w : by_reads) * (nl0 + 34ull);
+            rg.skip_del = true; rg.edits_per_read = ctx->skipdel_edits;
+        }
         rg.text_cap = text_cap < need ? text_cap : need;
     }
     rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);

@@ -82,8 +82,11 @@ static void usage(const char *p)
             "                   NAME, pos, ref, depth, A, C, G, T, N, del, ins; the whole file or one --region; counted on the device;\n"
             "                   with --depth-exclude-flags; not with --sam, --depth, --bedcov, --depth-hist or --stats)\n"
             "         --min-alt K (with --pileup: only positions with K or more non-reference observations; default 1)\n"
-            "         --max-edits-per-read N (with --pileup, --sam --cigar or --stats --alignment: deleted + inserted bases kept per read of a block, 1..510;\n"
-            "                  default 16)\n"
+            "         --max-edits-per-read N (with --pileup, --sam --cigar, --stats --alignment or --skip-deletions: deleted + inserted bases\n"
+            "                  kept per read of a block, 1..510; default 16)\n"
+            "         --skip-deletions (with --depth, --bedcov or --depth-hist: the depth at a position is the reads with an aligned base\n"
+            "                  there; the bases a read deletes do not count, as in samtools depth without -J, mosdepth and bedtools\n"
+            "                  genomecov -split; the reads counted and the --count-reads column keep their span meaning)\n"
             "         --cigar (with --sam: CIGAR, NM:i and MD:Z on every line, in the codec's view of the alignment: M, I, D and S only,\n"
             "                  an insertion in front of a deletion at the same place, an inserted run at a read's end as S, a mismatch\n"
             "                  = the read byte differs from the reference byte, so N over N matches; at most one --region, no\n"
@@ -505,7 +508,7 @@ int main(int argc, char **argv)
     uint32_t hist_max = 0;
     int stats_out = 0, stats_excl_given = 0, stats_aln = 0;
     uint32_t stats_exclude = 0;
-    int pileup = 0, min_alt_given = 0, max_edits_given = 0, sam_cigar = 0;
+    int pileup = 0, min_alt_given = 0, max_edits_given = 0, sam_cigar = 0, skip_del = 0;
     uint32_t min_alt = 1, max_edits = 0;
     g_main_t0 = now_s();
     for (int i = 1; i < argc; i++) {
@@ -571,6 +574,7 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--pileup")) { pileup = 1; continue; }
         if (!strcmp(a, "--min-alt") && i + 1 < argc) { if (!parse_count(a, argv[++i], 0xffffffffull, "a count in 1..4294967295", &n)) return 1; min_alt = (uint32_t)n; min_alt_given = 1; continue; }
         if (!strcmp(a, "--max-edits-per-read") && i + 1 < argc) { if (!parse_count(a, argv[++i], 510, "a number of deleted and inserted bases in 1..510", &n)) return 1; max_edits = (uint32_t)n; max_edits_given = 1; continue; }
+        if (!strcmp(a, "--skip-deletions")) { skip_del = 1; continue; }
         if (!strcmp(a, "--compat")) { compat = 1; continue; }
         if (!strcmp(a, "--long")) { long_reads = 1; continue; }
         if (!strcmp(a, "--device-parse")) { device_parse = 1; continue; }
@@ -623,8 +627,14 @@ int main(int argc, char **argv)
         { "--depth-hist", depth_hist, "--depth-hist, --bedcov, --depth and --sam are different outputs", hist_max_given ? "--hist-max" : NULL },
         { "--stats", stats_out, "--stats, --depth-hist, --bedcov, --depth and --sam are different outputs", stats_excl_given ? "--stats-exclude-flags" : stats_aln ? "--alignment" : NULL },
         { "--pileup", pileup, "--pileup, --stats, --depth-hist, --bedcov, --depth and --sam are different outputs",
-          min_alt_given ? "--min-alt" : max_edits_given && !sam_cigar && !(stats_out && stats_aln) ? "--max-edits-per-read" : NULL },
+          min_alt_given ? "--min-alt" : max_edits_given && !sam_cigar && !(stats_out && stats_aln) && !skip_del ? "--max-edits-per-read" : NULL },
     };
+    /* --skip-deletions changes what the three depth outputs count; anywhere else it means nothing and is refused */
+    if (skip_del) {
+        if (mode != 2) { fprintf(stderr, "cbc: --skip-deletions applies to decompression (-d / -x)\n"); return 1; }
+        if (pileup) { fprintf(stderr, "cbc: --skip-deletions applies to --depth, --bedcov or --depth-hist; the del column of --pileup already says it\n"); return 1; }
+        if (!depth_out && !bedcov && !depth_hist) { fprintf(stderr, "cbc: --skip-deletions applies to --depth, --bedcov or --depth-hist\n"); return 1; }
+    }
     for (size_t k = 0; k < sizeof opts / sizeof opts[0]; k++) {
         if (opts[k].owned && !opts[k].given) { fprintf(stderr, "cbc: %s applies to %s\n", opts[k].owned, opts[k].name); return 1; }
         if (!opts[k].given) continue;
@@ -632,6 +642,7 @@ int main(int argc, char **argv)
         for (size_t j = 2; j < k; j++) if (opts[j].given) { fprintf(stderr, "cbc: %s; give one of them\n", opts[k].clash); return 1; }
         if (ndev > 1) { fprintf(stderr, "cbc: %s decodes on one device; give a single --devices ordinal\n", opts[k].name); return 1; }
     }
+    if (skip_del) cbc_cli_skip_deletions(max_edits ? max_edits : CBC_EDITS_PER_READ);
     if (pileup) {                                                 /* one window or every contig: a target set is left for later */
         if (regions_file || n_regions > 1) { fprintf(stderr, "cbc: --pileup takes at most one --region and no --regions-file\n"); return 1; }
         return cbc_cli_decompress_pileup(files[0], files[1], files[2], device, region, depth_exclude, min_alt, max_edits, verbose);

@@ -1988,6 +1988,27 @@ API uint64_t cbc_unpack_pileup_text_cap(const cbc_unpack_plan *u, uint32_t b0, u
     return (w < by_reads ? w : by_reads) * ((uint64_t)nl + 102u);
 }
 
+/* ---- deletion-aware coverage (include/cbc_host.h) ----
+ * Proof of the bound.  Under skip_deletions a read's deletion cuts its cover, so "K reads give at most 2K - 1 runs" no longer
+ * holds.  A line stands for a maximal run of equal non-zero depth inside the window [beg, end]; runs are disjoint and each
+ * holds at least one position of the window, so lines <= end - beg + 1.  A position of non-zero depth carries an aligned base
+ * of a kept read; those lie inside the read's span [POS, POS + span - 1], the decoder fails the block of a read with
+ * span > smax (CBC_ST_SPAN), and a failed block contributes nothing: so such positions, and with them the lines, are
+ * <= reads * smax as well.  A line is the name, three tabs, '\n' and three numbers below 2^32 of at most 10 digits: name + 34
+ * bytes, as for cbc_unpack_depth_text_cap. */
+API uint64_t cbc_unpack_depth_skipdel_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg,
+                                               uint64_t end, uint32_t smax)
+{
+    if (!u || u->long_reads || !u->names || !u->contig_name_off || b0 > b1 || b1 > u->n_blocks || contig >= u->n_contigs || beg < 1 ||
+        beg > end || end > 0x7fffffffull) return 0;
+    const int64_t nl = sam_name_len(u, contig);
+    if (nl < 0) return 0;
+    uint64_t k = 0;
+    for (uint32_t b = b0; b < b1; b++) k += u->blocks[b].n_reads;
+    const uint64_t w = end - beg + 1u, by_reads = k * smax;          /* k < 2^32 blocks * 2^14 reads, smax < 2^32: no wrap */
+    return (w < by_reads ? w : by_reads) * ((uint64_t)nl + 34u);
+}
+
 /* ---- a set of regions (include/cbc_host.h) ---- */
 typedef struct { uint32_t contig, beg, end; } target_raw;
 
@@ -2218,6 +2239,27 @@ API uint64_t cbc_unpack_targets_depth_cap(const cbc_unpack_plan *u, const cbc_ta
         k += u->blocks[b].n_reads;
     }
     return (2u * k + 2ull * t->contig_count[contig] - 1u) * ((uint64_t)nl + 34u);
+}
+
+/* the same under skip_deletions: the proof of cbc_unpack_depth_skipdel_text_cap with the positions of
+ * the contig's merged intervals in the window's place -- a run lies inside one interval */
+API uint64_t cbc_unpack_targets_depth_skipdel_cap(const cbc_unpack_plan *u, const cbc_targets *t, uint32_t contig)
+{
+    if (!u || !t || u->long_reads || !u->names || !u->contig_name_off || contig >= u->n_contigs || contig >= t->n_contigs) return 0;
+    const int64_t nl = sam_name_len(u, contig);
+    if (nl < 0 || !t->contig_count[contig] || !t->contig_blk_count[contig]) return 0;
+    uint64_t k = 0, w = 0;
+    for (uint32_t i = 0; i < t->contig_blk_count[contig]; i++) {
+        const uint32_t b = t->blocks[t->contig_blk_first[contig] + i];
+        if (b >= u->n_blocks) return 0;
+        k += u->blocks[b].n_reads;
+    }
+    for (uint32_t i = 0; i < t->contig_count[contig]; i++) {
+        const cbc_target_iv *v = &t->iv[t->contig_first[contig] + i];
+        w += (uint64_t)(v->end - v->beg) + 1u;
+    }
+    const uint64_t by_reads = k * t->smax;
+    return (w < by_reads ? w : by_reads) * ((uint64_t)nl + 34u);
 }
 
 /* ---- per-target coverage summary (include/cbc_host.h) ---- */

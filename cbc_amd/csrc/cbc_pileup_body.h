@@ -81,6 +81,37 @@ CBC_FN cbc_pileup_win cbc_pileup_window(const cbc_pileup_args &A, uint32_t blk)
     return w;
 }
 
+/* ---- what every reader of the kept alignment shares (the events pass here, the unmark pass of cbc_skipdel_body.h) ---------- */
+/* a block's part of the side array and of the arena, by the decoder's own test; the side array runs beside the records
+ * (cbc_region_block's ok: inside n_recs).  ok = false (a per_read outside 1..510, a range outside the arena): the block's
+ * alignment is not read */
+struct cbc_edits_blk { const uint32_t *side; const uint16_t *arena; uint32_t cap; bool ok; };
+
+CBC_FN cbc_edits_blk cbc_edits_block(const uint32_t *side, const uint16_t *arena, uint64_t arena_entries, uint32_t per_read,
+                                     uint64_t rec_base, uint32_t n)
+{
+    cbc_edits_blk E;
+    const uint64_t cap64 = (uint64_t)n * per_read, base64 = rec_base * per_read;
+    E.ok = !(per_read < 1u || per_read > 510u || base64 > arena_entries || cap64 > arena_entries - base64);
+    E.cap = (uint32_t)cap64;
+    E.arena = arena + (E.ok ? base64 : 0u);
+    E.side = side + 2u * rec_base;
+    return E;
+}
+
+/* a read's entries [e0, e0 + nd + ni) of its block's `cap`: false is not what the decoder writes, and the read is skipped */
+CBC_FN bool cbc_edits_read_ok(uint32_t e0, uint32_t nd, uint32_t ni, uint32_t cap)
+{
+    return !(nd > 255u || ni > 255u || e0 > cap || nd + ni > cap - e0);
+}
+
+/* deleted base d of a read with the matched coordinates dc[] = ar[0 .. nd): its offset from POS, dc[d] + d */
+template <class W>
+CBC_FN typename W::V32 cbc_edits_del_offset(const uint16_t *ar, const typename W::V32 &d, const typename W::Mask &md)
+{
+    return W::load16(ar, d, md) + d;
+}
+
 /* ---- events ------------------------------------------------------------------------------------------------------------ */
 template <class W>
 CBC_FN void cbc_pileup_events(const cbc_pileup_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
@@ -93,12 +124,10 @@ CBC_FN void cbc_pileup_events(const cbc_pileup_args &A, uint32_t blk, uint32_t w
     if (!Wn.ok) return;
     const cbc_dec_block_desc *bd = A.D.R.blocks + blk;
     const uint64_t rec_base = bd->rec_base, ref_off = bd->ref_off;
-    /* the block's part of the arena, by the decoder's own test; the side array runs beside the records (B.ok: inside n_recs) */
-    const uint64_t cap64 = (uint64_t)B.n * A.per_read, base64 = rec_base * A.per_read;
-    if (A.per_read < 1u || A.per_read > 510u || base64 > A.arena_entries || cap64 > A.arena_entries - base64) return;
-    const uint32_t cap = (uint32_t)cap64;
-    const uint16_t *arena = A.arena + base64;
-    const uint32_t *side = A.side + 2u * rec_base;
+    const cbc_edits_blk E = cbc_edits_block(A.side, A.arena, A.arena_entries, A.per_read, rec_base, B.n);
+    if (!E.ok) return;
+    const uint16_t *arena = E.arena;
+    const uint32_t *side = E.side;
     if (ref_off > A.ref_bytes) return;
     const uint64_t ref_avail = A.ref_bytes - ref_off;
     const uint32_t ref_lim = ref_avail > 0xffffffffull ? 0xffffffffu : (uint32_t)ref_avail;
@@ -119,7 +148,7 @@ CBC_FN void cbc_pileup_events(const cbc_pileup_args &A, uint32_t blk, uint32_t w
             if ((nq++ % n_waves) != wave) continue;
             const uint32_t rl = W::readlane(rlv, j), lpj = W::readlane(lp, j), sp = W::readlane(span, j);
             const uint32_t e0 = W::readlane(sd0, j), cnt = W::readlane(sd1, j), nd = cnt & 0xffffu, ni = cnt >> 16;
-            if (nd > 255u || ni > 255u || e0 > cap || nd + ni > cap - e0) continue;     /* not what the decoder writes */
+            if (!cbc_edits_read_ok(e0, nd, ni, E.cap)) continue;
             const uint16_t *ar = arena + e0;                         /* dc = ar[0 .. nd), oi = ar[nd .. nd + ni) */
             const uint8_t *row = B.rows + (uint64_t)(r0 + j) * B.stride;
             /* the first 64 entries of each list in a register; later ones (rare) are read one by one */
@@ -159,7 +188,7 @@ CBC_FN void cbc_pileup_events(const cbc_pileup_args &A, uint32_t blk, uint32_t w
             for (uint32_t b = 0; b < nd; b += 64u) {                 /* deleted base d: POS + dc[d] + d */
                 const V32 d = ln + b;
                 const Mask md = d < nd;
-                const V32 xo = W::load16(ar, d, md) + d;
+                const V32 xo = cbc_edits_del_offset<W>(ar, d, md);
                 const V32 x = xo + lpj;
                 const Mask in = md & (xo < sp) & (x >= Wn.sub) & ((x - Wn.sub) <= Wn.rem);
                 W::list_add(p + (uint64_t)CBC_PILEUP_DEL * A.plane, x - Wn.sub, W::splat(1u), in);

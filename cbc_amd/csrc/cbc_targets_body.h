@@ -146,8 +146,10 @@ CBC_FN void cbc_targets_sam_write(const cbc_targets_args &A, uint32_t blk, uint3
 /* ---- depth: mark ------------------------------------------------------------------------------------------------------- */
 /* STARTS (cbc_gpu_decode_coverage_ext, cbc_covx_body.h): per piece also +1 at its first slot in `starts`, an array as long as
  * the difference array */
-template <class W, bool STARTS = false>
-CBC_FN void cbc_targets_mark(const cbc_tdepth_args &A, uint32_t blk, uint32_t *starts = NULL)
+/* U as for cbc_depth_mark (cbc_depth_body.h): a U with unmark = true is handed the kept reads of every group instead --
+ * U::reads<W>(T, off, lim, r0, k, pos, last): keep flags, POS and the read's last base -- and nothing is marked or counted */
+template <class W, bool STARTS = false, class U = cbc_mark_only>
+CBC_FN void cbc_targets_mark(const cbc_tdepth_args &A, uint32_t blk, uint32_t *starts = NULL, U *u = NULL)
 {
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
@@ -165,6 +167,7 @@ CBC_FN void cbc_targets_mark(const cbc_tdepth_args &A, uint32_t blk, uint32_t *s
         /* the read's last base, not as a sum that wraps (POS <= 2^31 - 1 under k; no interval ends past that) */
         const V32 pos = lp + T.ws;
         const V32 last = W::select((span - 1u) >= (W::splat(CBC_SAM_MAX_POS) - pos), W::splat(CBC_SAM_MAX_POS), pos + (span - 1u));
+        if (U::unmark) { u->template reads<W>(T, off, lim, r0, k, pos, last); continue; }
         Mask act = k;                                                /* interval i: end >= POS, and beg <= last by the keep rule */
         while (W::ballot(act) != 0ull) {
             const V32 b = W::load32(T.iv, i * 2u, act, 0u), e = W::load32(T.iv, i * 2u + 1u, act, 0u), o = W::load32(off, i, act, 0u);
@@ -180,6 +183,7 @@ CBC_FN void cbc_targets_mark(const cbc_tdepth_args &A, uint32_t blk, uint32_t *s
             act = act & (i < T.cnt);
         }
     }
+    if (U::unmark) return;
     W::list_add(A.D.ctr, W::splat(0u), W::splat(kept), ln == 0u);
 }
 

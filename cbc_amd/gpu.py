@@ -4,6 +4,7 @@ There is no CPU fallback: if the library is not built or no MI355X is visible, e
 raises.  Python here only moves pointers; `torch` (when used by bench.py / the multi-GPU host) only
 owns device memory and process groups.
 """
+import contextlib
 import ctypes
 import os
 
@@ -296,6 +297,8 @@ def lib():
                                             ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.cbc_gpu_set_depth_skip_deletions.restype = ctypes.c_int
+        L.cbc_gpu_set_depth_skip_deletions.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         L.cbc_gpu_last_pileup_ms.restype = ctypes.c_int
         L.cbc_gpu_last_pileup_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         L.cbc_gpu_decode_blocks_edits.restype = ctypes.c_int
@@ -329,7 +332,7 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_decode_coverage_ext", "cbc_gpu_last_coverage_ext_ms",
            "cbc_gpu_decode_coverage_quant", "cbc_gpu_last_coverage_quant_ms",
            "cbc_gpu_decode_pileup", "cbc_gpu_last_pileup_ms", "cbc_gpu_decode_blocks_edits",
-           "cbc_gpu_decode_sam_cigar", "cbc_gpu_last_sam_cigar_ms"]
+           "cbc_gpu_decode_sam_cigar", "cbc_gpu_last_sam_cigar_ms", "cbc_gpu_set_depth_skip_deletions"]
 
 EDITS_PER_READ = 16           # CBC_EDITS_PER_READ: the library's default arena size, entries per read of a block
 
@@ -353,6 +356,29 @@ class Encoder:
             raise CbcGpuError("%s failed (%d): %s" % (what, rc, msg.decode(errors="replace") if msg else ""))
 
     # ---- what the decode_* wrappers below share ----
+
+    @contextlib.contextmanager
+    def skip_deletions(self, max_edits_per_read=EDITS_PER_READ, on=True):
+        """`with enc.skip_deletions():` -- every depth call made inside (decode_depth, decode_targets(output="depth"),
+        decode_coverage, decode_coverage_quant, decode_depth_hist; not decode_pileup) counts ALIGNED bases only: the bases a read
+        deletes do not count, as in samtools depth without -J, mosdepth and bedtools genomecov -split
+        (cbc_gpu_set_depth_skip_deletions).  The reads counted, and the `reads` of decode_coverage(count_reads=True), keep their
+        span meaning: a read whose only bases inside a query are deleted still overlaps it (samtools bedcov -c counts it too).
+        The calls run the decoder that keeps the alignment, with max_edits_per_read (1..510) arena entries per read as for
+        decode_pileup: a block that needs more fails with status 9.  The encoder is back at the span depth afterwards, whatever
+        happened.  decode_depth, decode_targets and decode_depth_hist take the same as keywords; decode_coverage and
+        decode_coverage_quant, whose parameter lists are fixed, are used inside this block.  on=False: nothing is set."""
+        if not on:
+            yield
+            return
+        epr = int(max_edits_per_read)
+        if not 1 <= epr <= 510:
+            raise ValueError("max_edits_per_read is in 1..510")
+        self._check(lib().cbc_gpu_set_depth_skip_deletions(self._ctx, epr), "cbc_gpu_set_depth_skip_deletions")
+        try:
+            yield
+        finally:
+            lib().cbc_gpu_set_depth_skip_deletions(self._ctx, 0)
 
     def _check_blocks(self, rc, what, results):
         """_check, except that with results=True a failed block (rc -4) passes: the caller hands out the per-block results."""
@@ -668,7 +694,8 @@ class Encoder:
             return text, n_out, n_kept, self._cat(allres)
         return text
 
-    def decode_depth(self, plan: "host.UnpackPlan", region=None, exclude_flags=0, results=False, text_cap=None, smax=None):
+    def decode_depth(self, plan: "host.UnpackPlan", region=None, exclude_flags=0, results=False, text_cap=None, smax=None,
+                     skip_deletions=False, max_edits_per_read=EDITS_PER_READ):
         """Coverage of the container's reads as bedGraph bytes (cbc_gpu_decode_depth): per maximal run of equal non-zero
         depth `NAME\\tstart\\tend\\tdepth\\n`, 0-based half-open.  A read covers POS .. POS + span - 1, the bases it deletes
         included (a span coverage); reads with FLAG & exclude_flags != 0 are left out.  region=None: every contig that has
@@ -676,12 +703,20 @@ class Encoder:
         clipped to it.  The reference must have been uploaded (upload_reference(plan.ref)).  A selection without blocks gives
         b"" and runs nothing on the device.  With results=True returns (text, n_runs, n_reads_kept, per-block decode results
         of the blocks used) and lets a failed block pass (it marks nothing); text_cap: size of the buffer of one call (default:
-        plan.depth_text_cap of its blocks); smax: the span bound the decode checks (default: the selection's)."""
+        plan.depth_text_cap of its blocks); smax: the span bound the decode checks (default: the selection's).
+        skip_deletions=True: the depth at a position is the kept reads with an ALIGNED base there -- the bases a read deletes do
+        not count, as in samtools depth without -J, mosdepth and bedtools genomecov -split; inserted bases and soft clips change
+        nothing, and n_reads_kept keeps its span meaning.  The calls then run the decoder that keeps the alignment, with
+        max_edits_per_read (1..510) arena entries per read as for decode_pileup (a block that needs more fails with status 9),
+        and text_cap defaults to plan.depth_skipdel_text_cap.  False (the default): every byte as without the keyword."""
         plan.sam_header()                                     # refuses what the text cannot carry, and long-read containers
-        return self._decode_windows(plan, region, results, text_cap, "cbc_gpu_decode_depth",
-                                    lambda sel: (sel.smax if smax is None else int(smax), int(exclude_flags)),
-                                    lambda sel: plan.depth_text_cap(sel.b0, sel.b1, sel.contig),
-                                    "last_depth_text_bytes", "_depth_ms", "cbc_gpu_last_depth_ms")
+        cap_of = (lambda sel: plan.depth_skipdel_text_cap(sel.b0, sel.b1, sel.contig, sel.beg, sel.end,
+                                                          sel.smax if smax is None else int(smax))) if skip_deletions else \
+                 (lambda sel: plan.depth_text_cap(sel.b0, sel.b1, sel.contig))
+        with self.skip_deletions(max_edits_per_read, skip_deletions):
+            return self._decode_windows(plan, region, results, text_cap, "cbc_gpu_decode_depth",
+                                        lambda sel: (sel.smax if smax is None else int(smax), int(exclude_flags)), cap_of,
+                                        "last_depth_text_bytes", "_depth_ms", "cbc_gpu_last_depth_ms")
 
     def decode_pileup(self, plan: "host.UnpackPlan", region=None, exclude_flags=0, min_alt=1, edits_per_read=None, results=False,
                       text_cap=None):
@@ -737,22 +772,31 @@ class Encoder:
             self._check(rc, "cbc_gpu_decode_blocks_edits")
         return recs, seq, res, side[:plan.n_recs], arena[:plan.n_recs * epr]
 
-    def decode_targets(self, plan: "host.UnpackPlan", targets, output="reads", exclude_flags=0, results=False, text_cap=None):
+    def decode_targets(self, plan: "host.UnpackPlan", targets, output="reads", exclude_flags=0, results=False, text_cap=None,
+                       skip_deletions=False, max_edits_per_read=EDITS_PER_READ):
         """The reads that overlap at least one interval of `targets` (a host.TargetSet of plan.targets()), in one decode of the
         selected blocks (cbc_gpu_decode_targets).  output="reads": the text `cbc -x` writes for them, each read once, in
         container order; "sam": plan.sam_header() + their alignment lines; "depth": the bedGraph of decode_depth restricted to
         the set -- per merged interval what decode_depth(region=...) gives, appended in contig-table and position order, one
         call and one decode per contig (reads with FLAG & exclude_flags != 0 left out).  An empty selection runs nothing on
         the device.  With results=True returns (text, n_reads, n_runs, per-block decode results of the blocks decoded) and
-        lets a failed block pass (it contributes nothing); text_cap: size of the buffer of one call (default: the set's)."""
+        lets a failed block pass (it contributes nothing); text_cap: size of the buffer of one call (default: the set's).
+        skip_deletions / max_edits_per_read: with output="depth" as for decode_depth (ValueError with another output)."""
         kind = {"reads": 0, "sam": 1, "depth": 2}[output]
+        if skip_deletions and kind != 2:
+            raise ValueError("skip_deletions applies to output=\"depth\"")
+        with self.skip_deletions(max_edits_per_read, skip_deletions):
+            return self._decode_targets(plan, targets, kind, exclude_flags, results, text_cap, bool(skip_deletions))
+
+    def _decode_targets(self, plan, targets, kind, exclude_flags, results, text_cap, skip_deletions):
         hdr = plan.sam_header()                               # refuses what the text cannot carry, and long-read containers
         self._targets_ms = None
         self.last_targets_text_bytes = 0
         caps, pay, names, noff = self._plan_args(plan)
         iv = np.ascontiguousarray(targets.iv, dtype=np.uint32)
         if kind == 2:
-            calls = [(int(targets.contig_blk_first[c]), int(targets.contig_blk_count[c]), targets.depth_cap[c])
+            caps_of = targets.depth_skipdel_cap if skip_deletions else targets.depth_cap
+            calls = [(int(targets.contig_blk_first[c]), int(targets.contig_blk_count[c]), caps_of[c])
                      for c in range(targets.n_contigs) if targets.contig_blk_count[c]]
         else:
             calls = [(0, targets.n_blocks, targets.text_cap_sam if kind == 1 else targets.text_cap_reads)] if targets.n_blocks else []
@@ -789,7 +833,8 @@ class Encoder:
         cbc_gpu_decode_coverage_ext: then thr (uint32, shape [n_q, T]: the positions with depth >= thresholds[t]) and / or reads
         (uint32: the kept reads with at least one covered base in the query) follow covered, in that order.  With
         results=True the per-block decode results of the blocks decoded are appended and a failed block passes (it contributes
-        nothing); otherwise it raises CbcGpuError."""
+        nothing); otherwise it raises CbcGpuError.  Inside `with enc.skip_deletions():` the depth is decode_depth's with
+        skip_deletions=True -- sum, covered and thr lose the deleted bases; `reads` does not change."""
         return self._coverage(plan, queries, exclude_flags, min_depth, results, thresholds, count_reads, ())
 
     def decode_coverage_quant(self, plan: "host.UnpackPlan", queries, quantiles, exclude_flags=0, min_depth=1, results=False,
@@ -898,7 +943,8 @@ class Encoder:
         last_coverage_ext_ms, then the selection pass."""
         return self._summed_ms("_coverage_quant_ms", "decode_coverage_quant")
 
-    def decode_depth_hist(self, plan: "host.UnpackPlan", targets=None, exclude_flags=0, max_depth=0, results=False):
+    def decode_depth_hist(self, plan: "host.UnpackPlan", targets=None, exclude_flags=0, max_depth=0, results=False,
+                          skip_deletions=False, max_edits_per_read=EDITS_PER_READ):
         """Depth histogram (cbc_gpu_decode_depth_hist): per contig how many positions have each depth; depth as decode_depth
         counts it (reads with FLAG & exclude_flags != 0 left out).  targets=None: every contig of the container's table, whole;
         a host.TargetSet of plan.targets(): the positions of its merged intervals, every position once, and a contig is listed
@@ -906,7 +952,12 @@ class Encoder:
         decode per contig that has blocks; only the non-zero bins cross PCIe, and the depth-0 bin is size less their sum.
         Returns a list, in table order, of (contig, depth (uint32, ascending), bases (uint64, all > 0), size) with
         bases.sum() == size.  With results=True returns (that list, the per-block decode results of the blocks decoded) and
-        lets a failed block pass (its contig's call gives no bins: everything in depth 0); otherwise it raises CbcGpuError."""
+        lets a failed block pass (its contig's call gives no bins: everything in depth 0); otherwise it raises CbcGpuError.
+        skip_deletions / max_edits_per_read: the depth as decode_depth counts it with them."""
+        with self.skip_deletions(max_edits_per_read, skip_deletions):
+            return self._depth_hist(plan, targets, exclude_flags, max_depth, results)
+
+    def _depth_hist(self, plan, targets, exclude_flags, max_depth, results):
         plan.sam_header()                                     # refuses what the coordinates cannot carry, and long-read containers
         ts = plan.queries().targets if targets is None else targets
         if not 0 <= int(max_depth) <= 0xffffffff:

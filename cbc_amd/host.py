@@ -210,6 +210,9 @@ def lib():
         L.cbc_unpack_pileup_text_cap.restype = ctypes.c_uint64
         L.cbc_unpack_pileup_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
+        L.cbc_unpack_depth_skipdel_text_cap.restype = ctypes.c_uint64
+        L.cbc_unpack_depth_skipdel_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
         L.cbc_unpack_targets.restype = ctypes.c_int
         L.cbc_unpack_targets.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.c_void_p,
                                          ctypes.c_size_t, ctypes.POINTER(ctypes.POINTER(TargetsC)), ctypes.c_char_p, ctypes.c_size_t]
@@ -219,6 +222,8 @@ def lib():
         L.cbc_unpack_targets_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(TargetsC), ctypes.c_int]
         L.cbc_unpack_targets_depth_cap.restype = ctypes.c_uint64
         L.cbc_unpack_targets_depth_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(TargetsC), ctypes.c_uint32]
+        L.cbc_unpack_targets_depth_skipdel_cap.restype = ctypes.c_uint64
+        L.cbc_unpack_targets_depth_skipdel_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(TargetsC), ctypes.c_uint32]
         L.cbc_unpack_queries.restype = ctypes.c_int
         L.cbc_unpack_queries.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.c_void_p,
                                          ctypes.c_size_t, ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(QueriesC)), ctypes.c_char_p,
@@ -593,6 +598,7 @@ class TargetSet:
         self.text_cap_reads = int(lib().cbc_unpack_targets_text_cap(plan._ptr, ptr, 0))
         self.text_cap_sam = int(lib().cbc_unpack_targets_text_cap(plan._ptr, ptr, 1))
         self.depth_cap = [int(lib().cbc_unpack_targets_depth_cap(plan._ptr, ptr, c)) for c in range(nc)]
+        self.depth_skipdel_cap = [int(lib().cbc_unpack_targets_depth_skipdel_cap(plan._ptr, ptr, c)) for c in range(nc)]
         self.size = [int(lib().cbc_unpack_targets_size(ptr, c)) for c in range(nc)]
 
     def intervals(self):
@@ -739,6 +745,11 @@ class UnpackPlan:
     def depth_text_cap(self, b0, b1, contig) -> int:
         """Bytes that always hold the bedGraph of blocks [b0, b1) of contig `contig` (cbc_unpack_depth_text_cap)."""
         return int(lib().cbc_unpack_depth_text_cap(self._ptr, b0, b1, contig))
+
+    def depth_skipdel_text_cap(self, b0, b1, contig, beg, end, smax) -> int:
+        """Bytes that always hold the bedGraph of blocks [b0, b1) of contig `contig` for the window [beg, end] and the span bound
+        smax when deleted bases do not count (Encoder.decode_depth(skip_deletions=True); cbc_unpack_depth_skipdel_text_cap)."""
+        return int(lib().cbc_unpack_depth_skipdel_text_cap(self._ptr, b0, b1, contig, beg, end, smax))
 
     def pileup_text_cap(self, b0, b1, contig, beg, end, smax) -> int:
         """Bytes that always hold the pileup lines of blocks [b0, b1) of contig `contig` for the window [beg, end] and the span

@@ -433,6 +433,27 @@ int  cbc_gpu_decode_blocks_edits(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t i
                                  cbc_read_rec *recs, uint64_t n_recs, uint8_t *seq, uint64_t seq_bytes, uint32_t *side,
                                  uint16_t *arena, cbc_block_result *results /* n_blocks or NULL */);
 
+/* ---- deletion-aware coverage ----------------------------------------------------------------------
+ * A setting of the context.  edits_per_read = 0 (the default) leaves every call as it is: the depth is the SPAN depth, a read
+ * covers POS .. POS + span - 1, the bases it deletes included.  edits_per_read in 1..510 (CBC_EDITS_PER_READ is the usual
+ * choice; more is CBC_E_ARG and changes nothing): from then on the depth at position p, in every call that reports a depth
+ * but the pileup -- cbc_gpu_decode_depth, cbc_gpu_decode_targets with the depth output, cbc_gpu_decode_coverage, _ext and _quant,
+ * cbc_gpu_decode_depth_hist --, is the kept reads with an ALIGNED base at p: the span depth less the deleted bases of the kept
+ * reads at p (the `depth - del` of cbc_gpu_decode_pileup; what samtools depth without -J, mosdepth and bedtools genomecov -split
+ * count).  Inserted bases and soft clips change nothing; a deleted base outside its read's span, the window or the intervals is
+ * not counted.  "Kept" keeps its meaning, and so do n_reads_kept / n_reads and the `reads` of cbc_gpu_decode_coverage_ext: a
+ * read whose only bases inside a query are deleted still overlaps it (samtools bedcov -c counts it too).
+ * These calls then run the decoder that keeps the alignment, with an arena of edits_per_read entries per read as for the pileup
+ * (2 bytes each; a block whose reads hold more deleted and inserted bases fails with CBC_ST_EDITS and the call returns
+ * CBC_E_BLOCK), and one more stage behind the mark kernel that takes the deleted bases off the difference array.  The change
+ * points -- two per read before -- are sized min(difference-array words, 2 * reads * (1 + edits_per_read) (+ 2 per interval)),
+ * 8 bytes each (and 12 + 4 per threshold more in the coverage calls): CBC_E_NOMEM, with a message that names the setting, when
+ * that cannot be had.  text_cap of cbc_gpu_decode_depth: min(window, reads * smax) * (name_bytes + 34) always suffices
+ * (cbc_unpack_depth_skipdel_text_cap; cbc_unpack_targets_depth_skipdel_cap for a target set); the 2K - 1 runs of the span depth
+ * no longer hold.  The cbc_gpu_last_*_ms of these calls keep their meaning: the new stage's time falls into the mark stretch
+ * ("zeroing + mark"), the decode stretch is the edits decode. */
+int  cbc_gpu_set_depth_skip_deletions(cbc_gpu_ctx *ctx, uint32_t edits_per_read);
+
 /* ---- decode of a set of regions -------------------------------------------------------------------
  * `blocks` are the blocks a target set selects (cbc_unpack_targets of libcbc_host: the union of the single-region selections
  * of its merged intervals), gathered by the caller with their window starts and contigs; they are decoded ONCE by the

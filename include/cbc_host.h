@@ -234,6 +234,15 @@ uint64_t cbc_unpack_depth_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32
 uint64_t cbc_unpack_pileup_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg, uint64_t end,
                                     uint32_t smax);
 
+/* Deletion-aware coverage (the text comes from cbc_gpu_decode_depth after
+ * cbc_gpu_set_depth_skip_deletions).  A deletion cuts a read's cover in two, so the 2K - 1 runs of cbc_unpack_depth_text_cap no
+ * longer hold.  A text_cap that always holds the bedGraph of blocks [b0, b1) of contig `contig` for the window [beg, end] and the
+ * span bound smax of their selection: a line per position of the window at most, and per reference base a kept read spans, of
+ * at most len(name) + 34 bytes each (0 for a plan cbc_unpack_sam_header refuses, a bad range or a bad window).  The proof
+ * stands at the function. */
+uint64_t cbc_unpack_depth_skipdel_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg,
+                                           uint64_t end, uint32_t smax);
+
 /* Decode of a set of regions (the text comes from cbc_gpu_decode_targets).  The set is every string of
  * `regions` (parsed, clamped and refused exactly as cbc_unpack_region does) plus the lines of the BED text `bed` (bed_len bytes,
  * need not end in a newline or a NUL; NULL: none).  BED: fields separated by tabs or runs of spaces, at least `chrom start0 end0`
@@ -275,6 +284,9 @@ void     cbc_targets_free(cbc_targets *t);
  * intervals or no blocks there, or a bad argument) */
 uint64_t cbc_unpack_targets_text_cap(const cbc_unpack_plan *u, const cbc_targets *t, int sam);
 uint64_t cbc_unpack_targets_depth_cap(const cbc_unpack_plan *u, const cbc_targets *t, uint32_t contig);
+/* the depth of contig c under cbc_gpu_set_depth_skip_deletions: a line per position of the contig's merged intervals at most,
+ * and per reference base a read of its selected blocks spans (t->smax), of len(name) + 34 bytes */
+uint64_t cbc_unpack_targets_depth_skipdel_cap(const cbc_unpack_plan *u, const cbc_targets *t, uint32_t contig);
 
 /* Per-target coverage summary (the numbers come from cbc_gpu_decode_coverage).  The QUERY list, in this
  * order and never merged or de-duplicated: every string of `regions` (parsed, clamped and refused as cbc_unpack_region does),
