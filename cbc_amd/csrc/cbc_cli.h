@@ -18,9 +18,10 @@ int cbc_cli_decompress_region(const char *in, const char *out, const char *ref, 
 int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int device, const char *region, int cigar,
                            uint32_t edits_per_read, int verbose);
 int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude, int verbose);
-/* --pileup: at most one region; min_alt >= 1; edits_per_read 1..510, 0 = the library's default */
+/* --pileup: at most one region; min_alt >= 1; edits_per_read 1..510, 0 = the library's default; min_alt_ppm 0 (no fraction rule)
+ * ..1000000 (--min-alt-frac); by_strand 0 or 1 (--by-strand) */
 int cbc_cli_decompress_pileup(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,
-                              uint32_t min_alt, uint32_t edits_per_read, int verbose);
+                              uint32_t min_alt, uint32_t edits_per_read, uint32_t min_alt_ppm, int by_strand, int verbose);
 
 /* any number of regions and / or a BED file (bed_path NULL: none); output: CBC_TARGETS_READS, _SAM or _DEPTH */
 int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,

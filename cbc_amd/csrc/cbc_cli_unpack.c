@@ -372,8 +372,10 @@ int cbc_cli_decompress_sam(const char *in, const char *out, const char *ref, int
  * + 64 bytes per read of its blocks (or the bound, if that is less); the library reports the size of a text that does not fit,
  * and the call is made once more with exactly that.
  * --skip-deletions: the depth of the aligned bases alone; its bound is a line per position, not two per
- * read, so its buffer is handled as the pileup's. */
-typedef struct cli_pileup { uint32_t min_alt, edits_per_read; } cli_pileup;
+ * read, so its buffer is handled as the pileup's.
+ * --by-strand, --min-alt-frac: the same calls through cbc_gpu_decode_pileup_ext with the longer line's
+ * bound; without either option the call is cbc_gpu_decode_pileup as before. */
+typedef struct cli_pileup { uint32_t min_alt, edits_per_read, min_alt_ppm, by_strand; } cli_pileup;
 
 static int decompress_window(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,
                              const cli_pileup *pu, int verbose)
@@ -409,7 +411,8 @@ static int decompress_window(const char *in, const char *out, const char *ref, i
         const double b = now2();
         const char *nm = u->names + u->contig_name_off[s->contig];
         const int capped = pu || g_skip_edits;            /* a bound per position: start smaller, repeat once at the text's size */
-        const uint64_t bound = pu ? cbc_unpack_pileup_text_cap(u, s->b0, s->b1, s->contig, s->beg, s->end, s->smax)
+        const int ext = pu && (pu->by_strand || pu->min_alt_ppm);
+        const uint64_t bound = pu ? cbc_unpack_pileup_ext_text_cap(u, s->b0, s->b1, s->contig, s->beg, s->end, s->smax, pu->by_strand)
                              : g_skip_edits ? cbc_unpack_depth_skipdel_text_cap(u, s->b0, s->b1, s->contig, s->beg, s->end, s->smax)
                                             : cbc_unpack_depth_text_cap(u, s->b0, s->b1, s->contig);
         uint64_t cap = bound, first = 64ull << 20, tb = 0, nl = 0, nk = 0;
@@ -418,7 +421,10 @@ static int decompress_window(const char *in, const char *out, const char *ref, i
         for (int attempt = 0; attempt < (capped ? 2 : 1); attempt++) {
             if (cap > have || !text) { free(text); text = (char *)malloc((size_t)cap + 1); have = cap; }
             if (!text) { fprintf(stderr, "cbc: out of memory\n"); return 1; }
-            rc = pu ? cbc_gpu_decode_pileup(r.ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
+            rc = ext ? cbc_gpu_decode_pileup_ext(r.ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
+                                                 nm, (uint32_t)strlen(nm), s->beg, s->end, s->smax, exclude, pu->min_alt, pu->edits_per_read,
+                                                 pu->min_alt_ppm, pu->by_strand, (uint8_t *)text, cap, &tb, &nl, &nk, NULL)
+               : pu ? cbc_gpu_decode_pileup(r.ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
                                             nm, (uint32_t)strlen(nm), s->beg, s->end, s->smax, exclude, pu->min_alt, pu->edits_per_read,
                                             (uint8_t *)text, cap, &tb, &nl, &nk, NULL)
                     : cbc_gpu_decode_depth(r.ctx, u->payloads, u->payload_bytes, u->blocks + s->b0, nb, &u->caps, u->window_start + s->b0,
@@ -458,9 +464,9 @@ int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, i
 }
 
 int cbc_cli_decompress_pileup(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,
-                              uint32_t min_alt, uint32_t edits_per_read, int verbose)
+                              uint32_t min_alt, uint32_t edits_per_read, uint32_t min_alt_ppm, int by_strand, int verbose)
 {
-    const cli_pileup pu = { min_alt, edits_per_read };
+    const cli_pileup pu = { min_alt, edits_per_read, min_alt_ppm, by_strand ? 1u : 0u };
     return decompress_window(in, out, ref, device, region, exclude, &pu, verbose);
 }
 

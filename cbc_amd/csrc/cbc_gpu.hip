@@ -123,6 +123,18 @@ __global__ void __launch_bounds__(64)
 cbc_pileup_count_kernel(cbc_pileup_args A) { cbc_pileup_count<WaveGPU>(A, blockIdx.x); }
 __global__ void __launch_bounds__(64)
 cbc_pileup_write_kernel(cbc_pileup_args A) { cbc_pileup_write<WaveGPU>(A, blockIdx.x); }
+/* cbc_gpu_decode_pileup_ext: the events into the planes of the read's strand, and the line passes with
+ * the fraction rule (M = CBC_PILEUP_FRAC) or with it and the per-strand columns (CBC_PILEUP_STRAND); the kernels above are the
+ * plain call's and are not touched by it */
+__global__ void __launch_bounds__(64 * CBC_PILEUP_WAVES)
+cbc_pileup_events_strand_kernel(cbc_pileup_args A)
+{
+    if (blockIdx.x < A.D.R.n_blocks) cbc_pileup_events<WaveGPU, true>(A, blockIdx.x, WaveGPU::uni(threadIdx.x >> 6), CBC_PILEUP_WAVES);
+}
+template <int M> __global__ void __launch_bounds__(64)
+cbc_pileup_count_ext_kernel(cbc_pileup_args A, cbc_pileup_sx X) { cbc_pileup_count<WaveGPU, M>(A, blockIdx.x, &X); }
+template <int M> __global__ void __launch_bounds__(64)
+cbc_pileup_write_ext_kernel(cbc_pileup_args A, cbc_pileup_sx X) { cbc_pileup_write<WaveGPU, M>(A, blockIdx.x, &X); }
 
 /* SAM text with CIGAR, NM and MD (cbc_gpu_decode_sam_cigar, cbc_cigar_body.h): behind the edits decoder CBC_CIGAR_WAVES wavefronts
  * per block measure every kept read's CIGAR, NM and MD; then the count (one wavefront per block) and the text assembly
@@ -1196,6 +1208,9 @@ struct post_req {
     /* edits_per_read > 0 (with smax > 0): the edit-reporting decoder.  SAM_CIGAR, STATS_ALN: nothing more; PILEUP: the line rule and the
      * contig's first reference byte; NONE (cbc_gpu_decode_blocks_edits): where the side array (2 words per record) and the arena go */
     uint32_t edits_per_read, min_alt; uint64_t ref_c0;
+    /* PILEUP through cbc_gpu_decode_pileup_ext: the least alternative fraction in parts per million (0:
+     * none) and whether the line carries the per-strand columns -- then the window holds two difference arrays and 14 planes */
+    uint32_t min_alt_ppm; bool by_strand;
     uint32_t *edit_side; uint16_t *edit_arena;
     /* the depth kinds but PILEUP, under cbc_gpu_set_depth_skip_deletions: deleted bases do not count -- the
      * edits decoder (edits_per_read is set with it) and the unmark stage behind the mark kernel */
@@ -1241,6 +1256,15 @@ static post_sizes post_sizes_of(const post_req *rg, uint32_t n_blocks, uint64_t 
     z.n_btiles = (uint32_t)((z.h_bins + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
     z.h_out_cap = (uint32_t)(z.h_bins - 1u < z.cp_cap ? z.h_bins - 1u : z.cp_cap);
     return z;
+}
+
+/* PILEUP's counter arena: seven planes of the difference array's size; by_strand: fourteen, behind them the forward reads'
+ * difference array, its tile sums and non-zero counts and the scan of the sums (the second half of the 8 + 56 bytes per position) */
+static uint64_t pileup_tab_bytes(const post_req *rg, const post_sizes &z)
+{
+    const uint64_t plane = (uint64_t)z.n_tiles * CBC_DEPTH_TILE * 4;
+    if (!rg->by_strand) return plane * CBC_PILEUP_PLANES;
+    return plane * (2u * CBC_PILEUP_PLANES + 1u) + (uint64_t)z.n_tiles * 2 * sizeof(cbc_block_result) + ((uint64_t)z.n_tiles + 1) * 8;
 }
 
 /* no device memory for an arena that grows with the change points: under skip_del the message names the option that grew it */
@@ -1317,9 +1341,10 @@ static int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z
     }
     if (post_is_stats(k)) NEED(A_STATS, (uint64_t)CBC_STATS_WORDS * 4, "hipMalloc statistics tables");
     if (post_is_stats_aln(k)) NEED(A_SALN, (uint64_t)CBC_SALN_WORDS * 4, "hipMalloc alignment tables");
-    if (k == POST_PILEUP && arena_need(ctx, A_PTAB, (uint64_t)z.n_tiles * CBC_DEPTH_TILE * 4 * CBC_PILEUP_PLANES, "hipMalloc pileup counters")) {
+    if (k == POST_PILEUP && arena_need(ctx, A_PTAB, pileup_tab_bytes(rg, z), "hipMalloc pileup counters")) {
         (void)hipGetLastError();
-        return set_err(ctx, CBC_E_NOMEM, "no device memory for the window's allele counters (28 bytes per position)", hipSuccess);
+        return set_err(ctx, CBC_E_NOMEM, rg->by_strand ? "no device memory for the window's per-strand allele counters and forward difference array (56 + 4 bytes per position)"
+                                                       : "no device memory for the window's allele counters (28 bytes per position)", hipSuccess);
     }
     if (k == POST_SAM_CIGAR) NEED(A_CIGAR, n_recs * 8 + 16, "hipMalloc measured CIGAR, NM and MD sizes");
 done:
@@ -1685,21 +1710,48 @@ static int launch_pileup(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, c
     pa.arena_entries = n_recs * rg->edits_per_read; pa.per_read = rg->edits_per_read;
     pa.ref = ctx->d_ref; pa.ref_bytes = ctx->ref_bytes; pa.ref_c0 = rg->ref_c0; pa.min_alt = rg->min_alt;
     pa.tab = (uint32_t *)ctx->arena[A_PTAB].p; pa.plane = pa.D.diff_words;
-    HIPCHK(hipMemsetAsync(pa.tab, 0, pa.plane * 4 * CBC_PILEUP_PLANES, ks), "memset pileup counters");
+    const bool bs = rg->by_strand, ext = bs || rg->min_alt_ppm != 0u;
+    const uint32_t planes = bs ? 2u * CBC_PILEUP_PLANES : CBC_PILEUP_PLANES;
+    /* by_strand: behind the planes the forward reads' difference array, marked by the mark kernel under exclude | 16 with the
+     * spare counter word [2] for its count, and the tile sums of that array with their scan */
+    cbc_depth_args df = pa.D;
+    cbc_pileup_sx sx;
+    memset(&sx, 0, sizeof sx);
+    sx.ppm = rg->min_alt_ppm;
+    if (bs) {
+        df.diff = pa.tab + pa.plane * planes; df.exclude = rg->exclude | 16u; df.ctr = pa.D.ctr + 2;
+        df.tile_sum = (cbc_block_result *)(df.diff + pa.plane); df.tile_cnt = df.tile_sum + n_tiles;
+        df.sum_off = (const uint64_t *)(df.tile_cnt + n_tiles);
+        sx.diff_f = df.diff; sx.sum_off_f = df.sum_off;
+    }
+    HIPCHK(hipMemsetAsync(pa.tab, 0, pa.plane * 4 * (planes + (bs ? 1u : 0u)), ks), "memset pileup counters");
     hipLaunchKernelGGL(cbc_depth_mark_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, pa.D);
     HIPCHK(hipGetLastError(), "launch cbc_depth_mark_kernel");
-    hipLaunchKernelGGL(cbc_pileup_events_kernel, dim3(ra.n_blocks), dim3(64 * CBC_PILEUP_WAVES), 0, ks, pa);
+    if (bs) {
+        hipLaunchKernelGGL(cbc_depth_mark_kernel, dim3(ra.n_blocks), dim3(64), 0, ks, df);
+        HIPCHK(hipGetLastError(), "launch cbc_depth_mark_kernel");
+        hipLaunchKernelGGL(cbc_pileup_events_strand_kernel, dim3(ra.n_blocks), dim3(64 * CBC_PILEUP_WAVES), 0, ks, pa);
+    } else hipLaunchKernelGGL(cbc_pileup_events_kernel, dim3(ra.n_blocks), dim3(64 * CBC_PILEUP_WAVES), 0, ks, pa);
     HIPCHK(hipGetLastError(), "launch cbc_pileup_events_kernel");
     HIPCHK(hipEventRecord(ctx->ev_rg[2], ks), "hipEventRecord");
     hipLaunchKernelGGL(cbc_depth_tile_kernel, dim3(n_tiles), dim3(64), 0, ks, pa.D);
     HIPCHK(hipGetLastError(), "launch cbc_depth_tile_kernel");
     launch_scan_sizes(ks, pa.D.tile_sum, (uint64_t *)ctx->arena[A_DTOFF].p, n_tiles);
-    hipLaunchKernelGGL(cbc_pileup_count_kernel, dim3(n_tiles), dim3(64), 0, ks, pa);
+    if (bs) {
+        hipLaunchKernelGGL(cbc_depth_tile_kernel, dim3(n_tiles), dim3(64), 0, ks, df);
+        HIPCHK(hipGetLastError(), "launch cbc_depth_tile_kernel");
+        launch_scan_sizes(ks, df.tile_sum, (uint64_t *)df.sum_off, n_tiles);
+    }
+    if (bs) hipLaunchKernelGGL(cbc_pileup_count_ext_kernel<CBC_PILEUP_STRAND>, dim3(n_tiles), dim3(64), 0, ks, pa, sx);
+    else if (ext) hipLaunchKernelGGL(cbc_pileup_count_ext_kernel<CBC_PILEUP_FRAC>, dim3(n_tiles), dim3(64), 0, ks, pa, sx);
+    else hipLaunchKernelGGL(cbc_pileup_count_kernel, dim3(n_tiles), dim3(64), 0, ks, pa);
     HIPCHK(hipGetLastError(), "launch cbc_pileup_count_kernel");
     launch_scan_sizes(ks, ra.counts, (uint64_t *)ctx->arena[A_OFF].p, n_tiles);
     HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
     HIPCHK(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
-    hipLaunchKernelGGL(cbc_pileup_write_kernel, dim3(n_tiles), dim3(64), 0, ks, pa);
+    if (bs) hipLaunchKernelGGL(cbc_pileup_write_ext_kernel<CBC_PILEUP_STRAND>, dim3(n_tiles), dim3(64), 0, ks, pa, sx);
+    else if (ext) hipLaunchKernelGGL(cbc_pileup_write_ext_kernel<CBC_PILEUP_FRAC>, dim3(n_tiles), dim3(64), 0, ks, pa, sx);
+    else hipLaunchKernelGGL(cbc_pileup_write_kernel, dim3(n_tiles), dim3(64), 0, ks, pa);
     HIPCHK(hipGetLastError(), "launch cbc_pileup_write_kernel");
     HIPCHK(hipEventRecord(ctx->ev_rg[4], ks), "hipEventRecord");
     return CBC_OK;
@@ -2275,7 +2327,7 @@ API int cbc_gpu_decode_sam_cigar(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t i
 /* coverage: the window's blocks laid out afresh as for a region decode, then span decode + mark + scan + text on the device
  * (cbc_depth_body.h).  pu != NULL: per-position allele counts -- the edits decoder, then mark + events +
  * scans + text (cbc_pileup_body.h), for the blocks of one contig. */
-struct pileup_opt { uint32_t min_alt, edits_per_read; };
+struct pileup_opt { uint32_t min_alt, edits_per_read, min_alt_ppm, by_strand; };
 static int decode_window_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                               uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const char *name,
                               uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax, uint32_t exclude_flags, const pileup_opt *pu,
@@ -2291,6 +2343,8 @@ static int decode_window_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
     uint32_t edits_per_read = 0;
     if (pu) {
         if (pu->min_alt < 1) return set_err(ctx, CBC_E_ARG, "pileup wants min_alt >= 1", hipSuccess);
+        if (pu->min_alt_ppm > 1000000u || pu->by_strand > 1u)
+            return set_err(ctx, CBC_E_ARG, "pileup wants min_alt_ppm in 0..1000000 (0: no fraction rule) and by_strand 0 or 1", hipSuccess);
         edits_per_read = pu->edits_per_read;
         if ((rc = check_edits(ctx, "pileup wants ", &edits_per_read))) return rc;
     }
@@ -2310,11 +2364,12 @@ static int decode_window_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         const uint64_t w = end - beg + 1u, by_reads = L.nrec * smax, by_pos = w < by_reads ? w : by_reads;
         post_req rg;
         post_req_init(&rg, pu ? POST_PILEUP : POST_DEPTH, smax, window_start, text, text_cap,
-                      pu ? by_pos * (name_bytes + 102ull) : skip_del ? by_pos * (name_bytes + 34ull) : (2u * L.nrec - 1u) * (name_bytes + 34ull),
+                      pu ? by_pos * (name_bytes + 102ull + (pu->by_strand ? 77ull : 0ull)) : skip_del ? by_pos * (name_bytes + 34ull) : (2u * L.nrec - 1u) * (name_bytes + 34ull),
                       text_bytes, n_reads_kept);
         rg.beg = beg; rg.end = end;
         rg.names = (const uint8_t *)name; rg.names_bytes = name_bytes; rg.exclude = exclude_flags; rg.n_runs = n_runs;
-        if (pu) { rg.edits_per_read = edits_per_read; rg.min_alt = pu->min_alt; rg.ref_c0 = blocks[0].ref_off - window_start[0]; }
+        if (pu) { rg.edits_per_read = edits_per_read; rg.min_alt = pu->min_alt; rg.ref_c0 = blocks[0].ref_off - window_start[0];
+                  rg.min_alt_ppm = pu->min_alt_ppm; rg.by_strand = pu->by_strand != 0u; }
         if (skip_del) { rg.skip_del = true; rg.edits_per_read = ctx->skipdel_edits; }
         rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
     }
@@ -2338,7 +2393,19 @@ API int cbc_gpu_decode_pileup(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
                               uint32_t edits_per_read, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_lines,
                               uint64_t *n_reads_kept, cbc_block_result *results)
 {
-    const pileup_opt pu = { min_alt, edits_per_read };
+    const pileup_opt pu = { min_alt, edits_per_read, 0u, 0u };
+    return decode_window_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, name, name_bytes, beg, end, smax, exclude_flags, &pu,
+                              text, text_cap, text_bytes, n_lines, n_reads_kept, results);
+}
+
+/* the pileup with a least alternative fraction and the per-strand columns; 0, 0 is the call above */
+API int cbc_gpu_decode_pileup_ext(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                  uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const char *name,
+                                  uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax, uint32_t exclude_flags, uint32_t min_alt,
+                                  uint32_t edits_per_read, uint32_t min_alt_ppm, uint32_t by_strand, uint8_t *text, uint64_t text_cap,
+                                  uint64_t *text_bytes, uint64_t *n_lines, uint64_t *n_reads_kept, cbc_block_result *results)
+{
+    const pileup_opt pu = { min_alt, edits_per_read, min_alt_ppm, by_strand };
     return decode_window_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, name, name_bytes, beg, end, smax, exclude_flags, &pu,
                               text, text_cap, text_bytes, n_lines, n_reads_kept, results);
 }

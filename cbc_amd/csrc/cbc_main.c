@@ -82,6 +82,11 @@ static void usage(const char *p)
             "                   NAME, pos, ref, depth, A, C, G, T, N, del, ins; the whole file or one --region; counted on the device;\n"
             "                   with --depth-exclude-flags; not with --sam, --depth, --bedcov, --depth-hist or --stats)\n"
             "         --min-alt K (with --pileup: only positions with K or more non-reference observations; default 1)\n"
+            "         --by-strand (with --pileup: seven more columns behind the eleven, A+, C+, G+, T+, N+, del+, ins+ -- the same counts\n"
+            "                  over the reads with FLAG & 16 == 0 only; the reverse strand's are the difference; which positions get a\n"
+            "                  line is decided on the totals)\n"
+            "         --min-alt-frac F (with --pileup: only positions whose non-reference observations are at least the fraction F of\n"
+            "                  the depth, beside --min-alt; F in (0, 1] with at most six decimals, e.g. 0.02; compared in exact integers)\n"
             "         --max-edits-per-read N (with --pileup, --sam --cigar, --stats --alignment or --skip-deletions: deleted + inserted bases\n"
             "                  kept per read of a block, 1..510; default 16)\n"
             "         --skip-deletions (with --depth, --bedcov or --depth-hist: the depth at a position is the reads with an aligned base\n"
@@ -486,6 +491,26 @@ static int do_compress(const char *in, const char *out, const char *ref, uint32_
     return 0;
 }
 
+/* --min-alt-frac F: [0-9]+(\.[0-9]{1,6})? with a value in (0, 1], to parts per million by digit arithmetic (no strtod: 0.07 is
+ * 70000 whatever the nearest double says) */
+static int parse_alt_frac(const char *name, const char *v, uint32_t *ppm)
+{
+    const char *c = v;
+    uint64_t whole = 0, frac = 0;
+    int nd = 0, nf = 0, ok;
+    for (; *c >= '0' && *c <= '9'; c++, nd++) if (whole < 10) whole = whole * 10 + (uint64_t)(*c - '0');
+    ok = nd > 0;
+    if (ok && *c == '.') {
+        for (c++; *c >= '0' && *c <= '9' && nf < 7; c++, nf++) frac = frac * 10 + (uint64_t)(*c - '0');
+        ok = nf >= 1 && nf <= 6;
+        for (int k = nf; k < 6; k++) frac *= 10;
+    }
+    ok = ok && *c == 0 && whole <= 1 && whole * 1000000u + frac >= 1 && whole * 1000000u + frac <= 1000000u;
+    if (!ok) { fprintf(stderr, "cbc: %s wants a fraction in (0, 1] with at most six decimals, such as 0.02, not \"%s\"\n", name, v); return 0; }
+    *ppm = (uint32_t)(whole * 1000000u + frac);
+    return 1;
+}
+
 int main(int argc, char **argv)
 {
     const char *files[3] = { 0, 0, 0 };
@@ -510,6 +535,8 @@ int main(int argc, char **argv)
     uint32_t stats_exclude = 0;
     int pileup = 0, min_alt_given = 0, max_edits_given = 0, sam_cigar = 0, skip_del = 0;
     uint32_t min_alt = 1, max_edits = 0;
+    int by_strand = 0, alt_frac_given = 0;
+    uint32_t alt_frac_ppm = 0;
     g_main_t0 = now_s();
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
@@ -573,6 +600,8 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--alignment")) { stats_aln = 1; continue; }
         if (!strcmp(a, "--pileup")) { pileup = 1; continue; }
         if (!strcmp(a, "--min-alt") && i + 1 < argc) { if (!parse_count(a, argv[++i], 0xffffffffull, "a count in 1..4294967295", &n)) return 1; min_alt = (uint32_t)n; min_alt_given = 1; continue; }
+        if (!strcmp(a, "--by-strand")) { by_strand = 1; continue; }
+        if (!strcmp(a, "--min-alt-frac") && i + 1 < argc) { if (!parse_alt_frac(a, argv[++i], &alt_frac_ppm)) return 1; alt_frac_given = 1; continue; }
         if (!strcmp(a, "--max-edits-per-read") && i + 1 < argc) { if (!parse_count(a, argv[++i], 510, "a number of deleted and inserted bases in 1..510", &n)) return 1; max_edits = (uint32_t)n; max_edits_given = 1; continue; }
         if (!strcmp(a, "--skip-deletions")) { skip_del = 1; continue; }
         if (!strcmp(a, "--compat")) { compat = 1; continue; }
@@ -627,7 +656,8 @@ int main(int argc, char **argv)
         { "--depth-hist", depth_hist, "--depth-hist, --bedcov, --depth and --sam are different outputs", hist_max_given ? "--hist-max" : NULL },
         { "--stats", stats_out, "--stats, --depth-hist, --bedcov, --depth and --sam are different outputs", stats_excl_given ? "--stats-exclude-flags" : stats_aln ? "--alignment" : NULL },
         { "--pileup", pileup, "--pileup, --stats, --depth-hist, --bedcov, --depth and --sam are different outputs",
-          min_alt_given ? "--min-alt" : max_edits_given && !sam_cigar && !(stats_out && stats_aln) && !skip_del ? "--max-edits-per-read" : NULL },
+          min_alt_given ? "--min-alt" : max_edits_given && !sam_cigar && !(stats_out && stats_aln) && !skip_del ? "--max-edits-per-read" :
+          by_strand ? "--by-strand" : alt_frac_given ? "--min-alt-frac" : NULL },
     };
     /* --skip-deletions changes what the three depth outputs count; anywhere else it means nothing and is refused */
     if (skip_del) {
@@ -645,7 +675,7 @@ int main(int argc, char **argv)
     if (skip_del) cbc_cli_skip_deletions(max_edits ? max_edits : CBC_EDITS_PER_READ);
     if (pileup) {                                                 /* one window or every contig: a target set is left for later */
         if (regions_file || n_regions > 1) { fprintf(stderr, "cbc: --pileup takes at most one --region and no --regions-file\n"); return 1; }
-        return cbc_cli_decompress_pileup(files[0], files[1], files[2], device, region, depth_exclude, min_alt, max_edits, verbose);
+        return cbc_cli_decompress_pileup(files[0], files[1], files[2], device, region, depth_exclude, min_alt, max_edits, alt_frac_ppm, by_strand, verbose);
     }
     if (sam_cigar && (regions_file || n_regions > 1)) {            /* as for --pileup */
         fprintf(stderr, "cbc: --sam --cigar takes at most one --region and no --regions-file\n"); return 1;

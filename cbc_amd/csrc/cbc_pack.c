@@ -1975,8 +1975,8 @@ API uint64_t cbc_unpack_depth_text_cap(const cbc_unpack_plan *u, uint32_t b0, ui
  * block of a read with span > smax (CBC_ST_SPAN), and a failed block contributes nothing: so lines <= reads * smax as well.
  * A line is the name, ten tabs, the reference byte, '\n' and nine numbers below 2^32 -- pos1 <= 2^31 - 1 has at most 10
  * digits, the eight counts at most 10 each --: name + 12 + 90 = name + 2 + 10 + 2 + 8 * 11 bytes. */
-API uint64_t cbc_unpack_pileup_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg, uint64_t end,
-                                        uint32_t smax)
+static uint64_t pileup_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg, uint64_t end,
+                                uint32_t smax, uint32_t line)        /* line: the bytes of a line beside the name */
 {
     if (!u || u->long_reads || !u->names || !u->contig_name_off || b0 > b1 || b1 > u->n_blocks || contig >= u->n_contigs || beg < 1 ||
         beg > end || end > 0x7fffffffull) return 0;
@@ -1985,7 +1985,24 @@ API uint64_t cbc_unpack_pileup_text_cap(const cbc_unpack_plan *u, uint32_t b0, u
     uint64_t k = 0;
     for (uint32_t b = b0; b < b1; b++) k += u->blocks[b].n_reads;
     const uint64_t w = end - beg + 1u, by_reads = k * smax;          /* k < 2^32 blocks * 2^14 reads, smax < 2^32: no wrap */
-    return (w < by_reads ? w : by_reads) * ((uint64_t)nl + 102u);
+    return (w < by_reads ? w : by_reads) * ((uint64_t)nl + line);
+}
+
+API uint64_t cbc_unpack_pileup_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg, uint64_t end,
+                                        uint32_t smax)
+{
+    return pileup_text_cap(u, b0, b1, contig, beg, end, smax, 102u);
+}
+
+/* ---- per-strand counts and the fraction rule (include/cbc_host.h) ----
+ * The proof above, extended.  The fraction rule only takes lines away, and which positions get a line is decided on the totals, so
+ * the two bounds on the number of lines stand as they are.  With by_strand a line carries seven more columns, each a tab and a
+ * number below 2^32 of at most 10 digits (X+ counts a subset of what X counts; the reference class's X+ is depth+ - del+ -
+ * mismatches+, a 32-bit value whatever the tables hold): 7 * 11 bytes more, name + 179.  Lines < 2^31 and a line < 2^9: no wrap. */
+API uint64_t cbc_unpack_pileup_ext_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg, uint64_t end,
+                                            uint32_t smax, uint32_t by_strand)
+{
+    return by_strand > 1u ? 0u : pileup_text_cap(u, b0, b1, contig, beg, end, smax, by_strand ? 102u + 7u * 11u : 102u);
 }
 
 /* ---- deletion-aware coverage (include/cbc_host.h) ----

@@ -26,13 +26,17 @@
  *            into a cbc_block_result for the size scan (64-bit text offsets).
  *   write    the same tile again, one lane per line:  <name> <pos1> <ref> <depth> <A> <C> <G> <T> <N> <del> <ins>  tab-separated,
  *            through the line-per-lane writer of cbc_depth_body.h (cbc_lines_store) with the line bytes of cbc_pileup_ln.
+ * cbc_gpu_decode_pileup_ext runs the same passes with a template parameter each: the events into the
+ * planes of the read's strand (14 planes), the line rule with the fraction, the line with seven per-strand columns; the plain
+ * call's instantiations are the bodies as they were.
  * Range tests are written without base + length sums.  Written against the wave policy (W = WaveGPU in cbc_gpu.hip, the
- * lock-step emulation in tests/pileup_emu).
+ * lock-step emulation in tests/pileup_emu and tests/pileup_strand_emu).
  */
 #ifndef CBC_PILEUP_BODY_H
 #define CBC_PILEUP_BODY_H
 
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/cbc_gpu.h"
 #include "cbc_region_body.h"
 #include "cbc_depth_body.h"
@@ -113,7 +117,10 @@ CBC_FN typename W::V32 cbc_edits_del_offset(const uint16_t *ar, const typename W
 }
 
 /* ---- events ------------------------------------------------------------------------------------------------------------ */
-template <class W>
+/* STRAND (cbc_gpu_decode_pileup_ext with by_strand): tab holds 2 * CBC_PILEUP_PLANES planes, the seven of
+ * the reads with FLAG & 16 == 0 and behind them the seven of the others; an observation still costs one list_add, into the
+ * planes of its read's strand, which is uniform over the wavefront's turn.  Without it the body is the text it was. */
+template <class W, bool STRAND = false>
 CBC_FN void cbc_pileup_events(const cbc_pileup_args &A, uint32_t blk, uint32_t wave, uint32_t n_waves)
 {
     typedef typename W::V32 V32;
@@ -151,6 +158,8 @@ CBC_FN void cbc_pileup_events(const cbc_pileup_args &A, uint32_t blk, uint32_t w
             if (!cbc_edits_read_ok(e0, nd, ni, E.cap)) continue;
             const uint16_t *ar = arena + e0;                         /* dc = ar[0 .. nd), oi = ar[nd .. nd + ni) */
             const uint8_t *row = B.rows + (uint64_t)(r0 + j) * B.stride;
+            uint32_t *ps = p;                                        /* the planes of the read's strand */
+            if constexpr (STRAND) ps = p + (uint64_t)(((W::readlane(fl, j) >> 4) & 1u) * CBC_PILEUP_PLANES) * A.plane;
             /* the first 64 entries of each list in a register; later ones (rare) are read one by one */
             const V32 dcv = W::load16(ar, ln, ln < nd), oiv = W::load16(ar, ln + nd, ln < ni);
             for (uint32_t b = 0; b < rl; b += 64u) {
@@ -182,8 +191,8 @@ CBC_FN void cbc_pileup_events(const cbc_pileup_args &A, uint32_t blk, uint32_t w
                 const V32 cb = cbc_pileup_class<W>(W::load8(row, q, ab)), cr = cbc_pileup_class<W>(W::load8(refb, x - 1u, ab));
                 const Mask mis = ab & (cb != cr);
                 if (W::ballot(mis) != 0ull)
-                    for (uint32_t c = 0; c < 5u; c++) W::list_add(p + (uint64_t)c * A.plane, idx, W::splat(1u), mis & (cb == c));
-                W::list_add(p + (uint64_t)CBC_PILEUP_INS * A.plane, idx, W::splat(1u), st & in);
+                    for (uint32_t c = 0; c < 5u; c++) W::list_add(ps + (uint64_t)c * A.plane, idx, W::splat(1u), mis & (cb == c));
+                W::list_add(ps + (uint64_t)CBC_PILEUP_INS * A.plane, idx, W::splat(1u), st & in);
             }
             for (uint32_t b = 0; b < nd; b += 64u) {                 /* deleted base d: POS + dc[d] + d */
                 const V32 d = ln + b;
@@ -191,7 +200,7 @@ CBC_FN void cbc_pileup_events(const cbc_pileup_args &A, uint32_t blk, uint32_t w
                 const V32 xo = cbc_edits_del_offset<W>(ar, d, md);
                 const V32 x = xo + lpj;
                 const Mask in = md & (xo < sp) & (x >= Wn.sub) & ((x - Wn.sub) <= Wn.rem);
-                W::list_add(p + (uint64_t)CBC_PILEUP_DEL * A.plane, x - Wn.sub, W::splat(1u), in);
+                W::list_add(ps + (uint64_t)CBC_PILEUP_DEL * A.plane, x - Wn.sub, W::splat(1u), in);
             }
         }
     }
@@ -200,9 +209,29 @@ CBC_FN void cbc_pileup_events(const cbc_pileup_args &A, uint32_t blk, uint32_t w
 /* ---- lines ------------------------------------------------------------------------------------------------------------- */
 /* positions [i0, i0 + 64) of the window, `run` = the depth in front of them (advanced): the nine numbers of the line in
  * v[] = pos1, depth, A, C, G, T, N, del, ins, the reference byte, the line's length (0: no line) */
-template <class W>
+/* What cbc_gpu_decode_pileup_ext adds, as the mode M of the line, count and write bodies: 0 the plain
+ * call, whose bodies are the text they were; CBC_PILEUP_FRAC the fraction rule; CBC_PILEUP_STRAND the fraction rule and the
+ * seven per-strand columns.  X is read by the modes above 0 only.
+ *   fraction   a line needs nonref * 10^6 >= ppm * depth beside nonref >= min_alt, both products in 64 bits as (mulhi, low word)
+ *              pairs: nonref, depth < 2^32 and ppm <= 10^6 < 2^20 keep them below 2^52.  ppm = 0 passes everything.
+ *   strand     tab holds the forward planes and behind them the reverse planes (cbc_pileup_events<W, true>), a total is their
+ *              sum; diff_f is a second difference array, marked by cbc_depth_mark with the forward reads only, with its own
+ *              tile sums and their scan sum_off_f: its carry `runf` runs beside `run`, and the forward bases of the reference's
+ *              class are depth+ - del+ - mismatches+ as for the totals.  v[9 .. 15] = A+, C+, G+, T+, N+, del+, ins+; len2 = the
+ *              bytes of these seven columns, the tail of the line's len. */
+#define CBC_PILEUP_FRAC   1
+#define CBC_PILEUP_STRAND 2
+
+struct cbc_pileup_sx {
+    const uint32_t *diff_f;       /* STRAND: the forward reads' difference array, whole tiles like diff                        */
+    const uint64_t *sum_off_f;    /* STRAND: the exclusive scan of its tile sums (n_tiles + 1)                                  */
+    uint32_t ppm, reserved;       /* the least alternative fraction in parts per million, 0: none                              */
+};
+
+template <class W, int M = 0>
 CBC_FN typename W::Mask cbc_pileup_line(const cbc_pileup_args &A, uint32_t i0, uint32_t &run, typename W::V32 *v,
-                                        typename W::V32 &rb, typename W::V32 &len)
+                                        typename W::V32 &rb, typename W::V32 &len, const cbc_pileup_sx *X = NULL,
+                                        uint32_t *runf = NULL, typename W::V32 *len2 = NULL)
 {
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
@@ -214,12 +243,28 @@ CBC_FN typename W::Mask cbc_pileup_line(const cbc_pileup_args &A, uint32_t i0, u
     const V32 depth = incl + run;
     run += W::readlane(incl, 63u);
     V32 c[CBC_PILEUP_PLANES], nonref = W::splat(0u);
+    V32 cf[M == CBC_PILEUP_STRAND ? CBC_PILEUP_PLANES : 1u], depthf = W::splat(0u);
+    if constexpr (M == CBC_PILEUP_STRAND) {
+        const V32 inclf = W::scan_incl_add(W::load32(X->diff_f, idx, W::all(), 0u));
+        depthf = inclf + *runf;
+        *runf += W::readlane(inclf, 63u);
+    }
     for (uint32_t k = 0; k < CBC_PILEUP_PLANES; k++) {
         c[k] = W::load32(A.tab + (uint64_t)k * A.plane, idx, m, 0u);
+        if constexpr (M == CBC_PILEUP_STRAND) {
+            cf[k] = c[k];
+            c[k] = c[k] + W::load32(A.tab + (uint64_t)(CBC_PILEUP_PLANES + k) * A.plane, idx, m, 0u);
+        }
         nonref = nonref + c[k];
     }
-    const Mask k = m & (nonref >= A.min_alt) & (A.min_alt >= 1u);
+    Mask k = m & (nonref >= A.min_alt) & (A.min_alt >= 1u);
+    if constexpr (M != 0) {
+        const V32 mil = W::splat(1000000u), ppm = W::splat(X->ppm);
+        const V32 nh = W::mulhi(nonref, mil), nl = nonref * 1000000u, dh = W::mulhi(depth, ppm), dl = depth * X->ppm;
+        k = k & ((nh > dh) | ((nh == dh) & (nl >= dl)));
+    }
     len = W::splat(0u);
+    if constexpr (M == CBC_PILEUP_STRAND) *len2 = W::splat(0u);
     if (W::ballot(k) == 0ull) return k;
     const uint64_t at = A.ref_c0 + (A.D.R.beg - 1u);                 /* the reference byte of index 0 */
     const uint64_t avail = at <= A.ref_bytes ? A.ref_bytes - at : 0u;
@@ -234,6 +279,16 @@ CBC_FN typename W::Mask cbc_pileup_line(const cbc_pileup_args &A, uint32_t i0, u
     v[7] = c[CBC_PILEUP_DEL]; v[8] = c[CBC_PILEUP_INS];
     V32 l = W::splat(A.D.name_len + 12u);                            /* name, ten '\t', the reference byte, '\n' */
     for (uint32_t s = 0; s < 9u; s++) l = l + cbc_sam_ndig_v<W>(v[s], 1000000000u);
+    if constexpr (M == CBC_PILEUP_STRAND) {
+        const V32 misf = cf[0] + cf[1] + cf[2] + cf[3] + cf[4];
+        const V32 samef = depthf - cf[CBC_PILEUP_DEL] - misf;        /* the forward bases of the reference's class */
+        for (uint32_t s = 0; s < 5u; s++) v[9u + s] = W::select(cr == s, samef, cf[s]);
+        v[14] = cf[CBC_PILEUP_DEL]; v[15] = cf[CBC_PILEUP_INS];
+        V32 l2 = W::splat(7u);                                       /* seven '\t'; the '\n' of the first part becomes one */
+        for (uint32_t s = 9; s < 16u; s++) l2 = l2 + cbc_sam_ndig_v<W>(v[s], 1000000000u);
+        *len2 = W::select(k, l2, W::splat(0u));
+        l = l + l2;
+    }
     len = W::select(k, l, W::splat(0u));
     return k;
 }
@@ -244,17 +299,19 @@ CBC_FN bool cbc_pileup_text_ok(const cbc_pileup_args &A, uint32_t t)
            A.D.name_len <= CBC_SAM_MAX_NAME && A.D.R.beg >= 1u && A.D.R.beg <= A.D.R.end && A.D.R.end <= CBC_SAM_MAX_POS;
 }
 
-template <class W>
-CBC_FN void cbc_pileup_count(const cbc_pileup_args &A, uint32_t t)
+template <class W, int M = 0>
+CBC_FN void cbc_pileup_count(const cbc_pileup_args &A, uint32_t t, const cbc_pileup_sx *X = NULL)
 {
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
     uint32_t lines = 0, bytes = 0;
     if (cbc_pileup_text_ok(A, t)) {
         uint32_t run = (uint32_t)A.D.sum_off[t];                     /* depth in front of the tile, mod 2^32 */
+        uint32_t runf = 0;
+        if constexpr (M == CBC_PILEUP_STRAND) runf = (uint32_t)X->sum_off_f[t];
         for (uint32_t r = 0; r < CBC_DEPTH_TILE / 64u; r++) {
-            V32 v[9], rb, len;
-            const Mask k = cbc_pileup_line<W>(A, t * CBC_DEPTH_TILE + r * 64u, run, v, rb, len);
+            V32 v[M == CBC_PILEUP_STRAND ? 16 : 9], rb, len, len2;
+            const Mask k = cbc_pileup_line<W, M>(A, t * CBC_DEPTH_TILE + r * 64u, run, v, rb, len, X, &runf, &len2);
             if (W::ballot(k) == 0ull) continue;
             lines += W::popc64(W::ballot(k));
             bytes += W::reduce_add(len);
@@ -289,10 +346,43 @@ CBC_FN typename W::V32 cbc_line_byte(const cbc_pileup_ln<W> &L, uint32_t i)
     return W::select(iv == L.e[8], W::splat(10u), by);
 }
 
+/* STRAND: the line goes out in two parts, so that no more numbers are held at once than the plain line holds.  The first is the
+ * plain line with a '\t' where its '\n' stood; the second, written behind it, is the seven per-strand numbers: number s ends at
+ * e[s] with a '\t' there, e[6] holds the '\n'.  The second part keeps its numbers whole and splits the one a byte belongs to. */
+template <class W>
+struct cbc_pileup_ln_tab : cbc_pileup_ln<W> {};
+
+template <class W>
+CBC_FN typename W::V32 cbc_line_byte(const cbc_pileup_ln_tab<W> &L, uint32_t i)
+{
+    return W::select(W::splat(i) == L.e[8], W::splat(9u), cbc_line_byte(static_cast<const cbc_pileup_ln<W> &>(L), i));
+}
+
+template <class W>
+struct cbc_pileup_ln2 { typename W::V32 e[7], v[7]; };
+
+template <class W>
+CBC_FN typename W::V32 cbc_line_byte(const cbc_pileup_ln2<W> &L, uint32_t i)
+{
+    typedef typename W::V32 V32;
+    typedef typename W::Mask Mask;
+    const V32 iv = W::splat(i);
+    V32 x = L.v[6], ee = L.e[6], hi, lo;
+    Mask tab = iv != iv;
+    for (int s = 5; s >= 0; s--) {                                   /* the first number that ends behind byte i */
+        const Mask lt = iv < L.e[s];
+        x = W::select(lt, L.v[s], x); ee = W::select(lt, L.e[s], ee);
+        tab = tab | (iv == L.e[s]);
+    }
+    cbc_depth_split<W>(x, hi, lo);
+    const V32 by = W::select(tab, W::splat(9u), cbc_depth_digit<W>(hi, lo, (ee - 1u) - iv));
+    return W::select(iv == L.e[6], W::splat(10u), by);
+}
+
 /* count and write iterate positions, carry `run` and skip empty rounds: they share the writer with the run-text skeleton of
  * cbc_depth_body.h, not its loops */
-template <class W>
-CBC_FN void cbc_pileup_write(const cbc_pileup_args &A, uint32_t t)
+template <class W, int M = 0>
+CBC_FN void cbc_pileup_write(const cbc_pileup_args &A, uint32_t t, const cbc_pileup_sx *X = NULL)
 {
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
@@ -302,19 +392,30 @@ CBC_FN void cbc_pileup_write(const cbc_pileup_args &A, uint32_t t)
     if (bytes == 0u || o0 > A.D.R.text_cap || bytes > A.D.R.text_cap - o0) return;
     uint64_t o = o0;
     uint32_t run = (uint32_t)A.D.sum_off[t];
+    uint32_t runf = 0;
+    if constexpr (M == CBC_PILEUP_STRAND) runf = (uint32_t)X->sum_off_f[t];
     for (uint32_t r = 0; r < CBC_DEPTH_TILE / 64u; r++) {
-        V32 v[9], rb, len;
-        const Mask k = cbc_pileup_line<W>(A, t * CBC_DEPTH_TILE + r * 64u, run, v, rb, len);
+        V32 v[M == CBC_PILEUP_STRAND ? 16 : 9], rb, len, len2;
+        const Mask k = cbc_pileup_line<W, M>(A, t * CBC_DEPTH_TILE + r * 64u, run, v, rb, len, X, &runf, &len2);
         if (W::ballot(k) == 0ull) continue;
         const V32 incl = W::scan_incl_add(len);
         const uint32_t chunk = W::readlane(incl, 63u);
         if (chunk > (o0 + bytes) - o) return;                        /* the counters moved under the count pass */
-        cbc_pileup_ln<W> L;
+        typename std::conditional<M == CBC_PILEUP_STRAND, cbc_pileup_ln_tab<W>, cbc_pileup_ln<W> >::type L;
         L.nl = nl; L.rb = rb;
         L.e[0] = cbc_sam_ndig_v<W>(v[0], 1000000000u) + (nl + 1u);
         L.e[1] = L.e[0] + cbc_sam_ndig_v<W>(v[1], 1000000000u) + 3u;
         for (uint32_t s = 2; s < 9u; s++) L.e[s] = L.e[s - 1u] + cbc_sam_ndig_v<W>(v[s], 1000000000u) + 1u;
         for (uint32_t s = 0; s < 9u; s++) cbc_depth_split<W>(v[s], L.hi[s], L.lo[s]);
+        if constexpr (M == CBC_PILEUP_STRAND) {
+            cbc_lines_store<W>(A.D.R.text + o, incl - len, len - len2, k, A.D.name, nl, L);
+            cbc_pileup_ln2<W> L2;
+            for (uint32_t s = 0; s < 7u; s++) {
+                L2.v[s] = v[9u + s];
+                L2.e[s] = (s ? L2.e[s - 1u] + 1u : W::splat(0u)) + cbc_sam_ndig_v<W>(v[9u + s], 1000000000u);
+            }
+            cbc_lines_store<W>(A.D.R.text + o, incl - len2, len2, k, A.D.name, 0u, L2);
+        } else
         cbc_lines_store<W>(A.D.R.text + o, incl - len, len, k, A.D.name, nl, L);
         o += chunk;
     }

@@ -7,6 +7,7 @@ owns device memory and process groups.
 import contextlib
 import ctypes
 import os
+import re
 
 import numpy as np
 
@@ -297,6 +298,9 @@ def lib():
                                             ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.cbc_gpu_decode_pileup_ext.restype = ctypes.c_int
+        L.cbc_gpu_decode_pileup_ext.argtypes = L.cbc_gpu_decode_pileup.argtypes[:15] + [ctypes.c_uint32, ctypes.c_uint32] + \
+                                                L.cbc_gpu_decode_pileup.argtypes[15:]
         L.cbc_gpu_set_depth_skip_deletions.restype = ctypes.c_int
         L.cbc_gpu_set_depth_skip_deletions.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         L.cbc_gpu_last_pileup_ms.restype = ctypes.c_int
@@ -331,10 +335,24 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_last_stats_ms", "cbc_gpu_decode_stats_aln", "cbc_gpu_last_stats_aln_ms",
            "cbc_gpu_decode_coverage_ext", "cbc_gpu_last_coverage_ext_ms",
            "cbc_gpu_decode_coverage_quant", "cbc_gpu_last_coverage_quant_ms",
-           "cbc_gpu_decode_pileup", "cbc_gpu_last_pileup_ms", "cbc_gpu_decode_blocks_edits",
+           "cbc_gpu_decode_pileup", "cbc_gpu_decode_pileup_ext", "cbc_gpu_last_pileup_ms", "cbc_gpu_decode_blocks_edits",
            "cbc_gpu_decode_sam_cigar", "cbc_gpu_last_sam_cigar_ms", "cbc_gpu_set_depth_skip_deletions"]
 
 EDITS_PER_READ = 16           # CBC_EDITS_PER_READ: the library's default arena size, entries per read of a block
+
+_ALT_FRAC = re.compile(r"[0-9]+(\.[0-9]{1,6})?\Z")
+
+
+def alt_frac_ppm(text) -> int:
+    """The value of `cbc -x --pileup --min-alt-frac F` in parts per million, by digit arithmetic: F is [0-9]+(\\.[0-9]{1,6})? with
+    a value in (0, 1] -- "0.000001" gives 1, "1" and "1.0" give 1 000 000.  ValueError for exactly the strings the CLI refuses."""
+    if not isinstance(text, str) or not _ALT_FRAC.match(text):
+        raise ValueError("min_alt_frac wants a decimal fraction in (0, 1] with at most six decimals, not %r" % (text,))
+    whole, _, frac = text.partition(".")
+    ppm = int(whole) * 1_000_000 + int((frac + "000000")[:6])
+    if not 1 <= ppm <= 1_000_000:
+        raise ValueError("min_alt_frac wants a decimal fraction in (0, 1] with at most six decimals, not %r" % (text,))
+    return ppm
 
 
 class Encoder:
@@ -719,7 +737,7 @@ class Encoder:
                                         "last_depth_text_bytes", "_depth_ms", "cbc_gpu_last_depth_ms")
 
     def decode_pileup(self, plan: "host.UnpackPlan", region=None, exclude_flags=0, min_alt=1, edits_per_read=None, results=False,
-                      text_cap=None):
+                      text_cap=None, by_strand=False, min_alt_ppm=0):
         """What the container's reads show at the positions where they disagree with the reference (cbc_gpu_decode_pileup):
         per position with at least min_alt non-reference observations `NAME\\tpos1\\tref\\tdepth\\tA\\tC\\tG\\tT\\tN\\tdel\\tins\\n`,
         in the codec's view of the alignment; reads with FLAG & exclude_flags != 0 are left out.  region=None: every contig that
@@ -728,13 +746,25 @@ class Encoder:
         on the device.  edits_per_read (1..510, default 16) sizes the arena the decoder keeps the alignment in: a block that
         needs more fails with status 9 (CBC_ST_EDITS).  With results=True returns (text, n_lines, n_reads_kept, per-block decode
         results of the blocks used) and lets a failed block pass (it contributes nothing); text_cap: size of the buffer of one
-        call (default: plan.pileup_text_cap of its blocks and window)."""
+        call (default: plan.pileup_text_cap of its blocks and window).
+        by_strand=True or min_alt_ppm > 0 (cbc_gpu_decode_pileup_ext; the defaults give the call as it was): min_alt_ppm in
+        1..1 000 000 (alt_frac_ppm("0.02") = 20 000) also asks nonref * 10^6 >= min_alt_ppm * depth of a position, nonref = depth
+        - count(class(ref)) + ins, in exact integers; by_strand appends `\\tA+\\tC+\\tG+\\tT+\\tN+\\tdel+\\tins+` to every line, the
+        same columns counted over the kept reads with FLAG & 16 == 0 only."""
         plan.sam_header()                                     # refuses what the text cannot carry, and long-read containers
         if int(min_alt) < 1:
             raise ValueError("min_alt is 1 or more")
+        if not 0 <= int(min_alt_ppm) <= 1_000_000:
+            raise ValueError("min_alt_ppm is in 0..1000000")
         epr = EDITS_PER_READ if edits_per_read is None else int(edits_per_read)
         if not 1 <= epr <= 510:
             raise ValueError("edits_per_read is in 1..510")
+        if by_strand or int(min_alt_ppm):
+            bs = bool(by_strand)
+            return self._decode_windows(plan, region, results, text_cap, "cbc_gpu_decode_pileup_ext",
+                                        lambda sel: (sel.smax, int(exclude_flags), int(min_alt), epr, int(min_alt_ppm), int(bs)),
+                                        lambda sel: plan.pileup_text_cap(sel.b0, sel.b1, sel.contig, sel.beg, sel.end, sel.smax, bs),
+                                        "last_pileup_text_bytes", "_pileup_ms", "cbc_gpu_last_pileup_ms")
         return self._decode_windows(plan, region, results, text_cap, "cbc_gpu_decode_pileup",
                                     lambda sel: (sel.smax, int(exclude_flags), int(min_alt), epr),
                                     lambda sel: plan.pileup_text_cap(sel.b0, sel.b1, sel.contig, sel.beg, sel.end, sel.smax),

@@ -210,6 +210,9 @@ def lib():
         L.cbc_unpack_pileup_text_cap.restype = ctypes.c_uint64
         L.cbc_unpack_pileup_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
+        L.cbc_unpack_pileup_ext_text_cap.restype = ctypes.c_uint64
+        L.cbc_unpack_pileup_ext_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                     ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]
         L.cbc_unpack_depth_skipdel_text_cap.restype = ctypes.c_uint64
         L.cbc_unpack_depth_skipdel_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
@@ -751,9 +754,12 @@ class UnpackPlan:
         smax when deleted bases do not count (Encoder.decode_depth(skip_deletions=True); cbc_unpack_depth_skipdel_text_cap)."""
         return int(lib().cbc_unpack_depth_skipdel_text_cap(self._ptr, b0, b1, contig, beg, end, smax))
 
-    def pileup_text_cap(self, b0, b1, contig, beg, end, smax) -> int:
+    def pileup_text_cap(self, b0, b1, contig, beg, end, smax, by_strand=False) -> int:
         """Bytes that always hold the pileup lines of blocks [b0, b1) of contig `contig` for the window [beg, end] and the span
-        bound smax (cbc_unpack_pileup_text_cap)."""
+        bound smax (cbc_unpack_pileup_text_cap); by_strand=True: the lines with the seven per-strand columns
+        (cbc_unpack_pileup_ext_text_cap)."""
+        if by_strand:
+            return int(lib().cbc_unpack_pileup_ext_text_cap(self._ptr, b0, b1, contig, beg, end, smax, 1))
         return int(lib().cbc_unpack_pileup_text_cap(self._ptr, b0, b1, contig, beg, end, smax))
 
     def sam_header(self) -> bytes:

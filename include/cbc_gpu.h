@@ -420,8 +420,27 @@ int  cbc_gpu_decode_pileup(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_byte
                            uint32_t exclude_flags, uint32_t min_alt, uint32_t edits_per_read, uint8_t *text, uint64_t text_cap,
                            uint64_t *text_bytes, uint64_t *n_lines, uint64_t *n_reads_kept,
                            cbc_block_result *results /* n_blocks or NULL */);
-/* Kernel times of the most recent cbc_gpu_decode_pileup (HIP events on its stream): the edits decode; zeroing + mark + events;
- * tile sums, their scan, the line count and its scan; the text. */
+/* cbc_gpu_decode_pileup with a least alternative fraction and per-strand counts.  With min_alt_ppm = 0
+ * and by_strand = 0 it writes the bytes of cbc_gpu_decode_pileup; any other value than min_alt_ppm in 0..1 000 000 and by_strand
+ * in 0..1 is CBC_E_ARG.
+ * min_alt_ppm > 0: with nonref = depth - (count of ref's class) + ins, position p gets a line when nonref >= min_alt AND
+ * nonref * 10^6 >= min_alt_ppm * depth, in exact integer arithmetic (both products are below 2^52).  Insertion events are not part
+ * of depth, so nonref can exceed it; such a position passes every fraction.
+ * by_strand = 1: every line keeps its eleven columns and seven more follow, tab-separated:
+ *     ... <del>\t<ins>\t<A+>\t<C+>\t<G+>\t<T+>\t<N+>\t<del+>\t<ins+>\n
+ * X+ = column X counted over the kept reads with FLAG & 16 == 0 only (the reverse strand's count is X - X+).  Which positions get
+ * a line is decided on the totals.  exclude_flags applies first: with bit 16 in it every X+ equals X.
+ * text_cap = min(window, reads * smax) * (name_bytes + 102 + 77 * by_strand) always suffices (cbc_unpack_pileup_ext_text_cap).
+ * With by_strand the window costs 8 + 56 bytes of device memory per position, otherwise 4 + 28: CBC_E_NOMEM when that cannot be
+ * had.  Everything else is as for cbc_gpu_decode_pileup. */
+int  cbc_gpu_decode_pileup_ext(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                               uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                               const char *name, uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax,
+                               uint32_t exclude_flags, uint32_t min_alt, uint32_t edits_per_read, uint32_t min_alt_ppm,
+                               uint32_t by_strand, uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_lines,
+                               uint64_t *n_reads_kept, cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_pileup or _ext (HIP events on its stream): the edits decode; zeroing + mark(s) +
+ * events; tile sums, their scan(s), the line count and its scan; the text. */
 int  cbc_gpu_last_pileup_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *events_ms, float *scan_ms, float *text_ms);
 /* cbc_gpu_decode_blocks_span with the edits reported as well (the decoder the pileup runs, with everything it leaves returned;
  * what the tests check it with): side[2 r] = the first arena entry of record r relative to its block's, side[2 r + 1] =

@@ -233,6 +233,11 @@ uint64_t cbc_unpack_depth_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32
  * plan cbc_unpack_sam_header refuses, a bad range or a bad window).  The proof stands at the function. */
 uint64_t cbc_unpack_pileup_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg, uint64_t end,
                                     uint32_t smax);
+/* The same for cbc_gpu_decode_pileup_ext: by_strand = 1 adds seven columns of at most 11 bytes to every
+ * line, len(name) + 102 + 7 * 11; the number of lines is bounded as above, and the fraction rule only takes lines away.
+ * by_strand = 0 gives cbc_unpack_pileup_text_cap; anything but 0 or 1 gives 0. */
+uint64_t cbc_unpack_pileup_ext_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg, uint64_t end,
+                                        uint32_t smax, uint32_t by_strand);
 
 /* Deletion-aware coverage (the text comes from cbc_gpu_decode_depth after
  * cbc_gpu_set_depth_skip_deletions).  A deletion cuts a read's cover in two, so the 2K - 1 runs of cbc_unpack_depth_text_cap no
