@@ -7,42 +7,13 @@
  * so an index past one is a finding.  With -DALNSTATS_EMU_MAIN the file is a stand-alone program that builds fabricated cases
  * itself, compares them with an element-by-element host loop and exits non-zero on a mismatch (make asan_check).
  */
-#include <vector>
-#include <string>
-#include "wave_emu_aln.h"
-#include "../../cbc_amd/csrc/cbc_encode_body.h"
-#include "../../cbc_amd/csrc/cbc_decode_body.h"
-#include "../../cbc_amd/csrc/cbc_plan.h"
+#include "../emu/post_emu.h"
 #include "../../cbc_amd/csrc/cbc_stats_aln_body.h"
-
-typedef WaveEmuAln WA;
-
-static int g_emu_errors = 0;
-extern "C" void emu_oob(const char *what) { fprintf(stderr, "[emu] invariant violated: %s\n", what); g_emu_errors++; }
 
 /* the edit-reporting decoder over every block of the batch: side = 2 * n_recs words, arena = n_recs * per_read entries exactly */
 extern "C" __attribute__((visibility("default")))
 int emu_aln_decode(const cbc_dec_device_batch *b, uint32_t smax, uint32_t per_read, uint32_t *side, uint16_t *arena)
-{
-    cbc_dec_args A;
-    memset(&A, 0, sizeof A);
-    A.in = b->d_in; A.blocks = b->d_blocks; A.ref = b->d_ref; A.recs = b->d_recs; A.seq = b->d_seq; A.results = b->d_results;
-    A.in_bytes = b->in_bytes; A.ref_bytes = b->ref_bytes; A.n_recs = b->n_recs; A.seq_bytes = b->seq_bytes;
-    A.n_blocks = b->n_blocks; A.cap_pos = b->caps.cap_pos; A.cap_var = b->caps.cap_var;
-    A.var_scratch = b->d_var_scratch; A.var_scratch_words = b->var_scratch_words;
-    cbc_dec_edits E;
-    memset(&E, 0, sizeof E);
-    E.side = side; E.arena = arena; E.arena_entries = b->n_recs * per_read; E.per_read = per_read;
-    g_emu_errors = 0;
-    WA::edit_arena(arena, E.arena_entries);
-    uint32_t words = cbc_plan_dec_lds_bytes(&b->caps) / 4;
-    for (uint32_t blk = 0; blk < b->n_blocks; blk++) {
-        std::vector<uint32_t> lds(words, 0xdeadbeefu);
-        cbc_decode_stream<WA, true, true>(A, blk, lds.data(), smax, &E);
-    }
-    WA::edit_arena(nullptr, 0);
-    return g_emu_errors ? -100 : 0;
-}
+{ return emu_decode_blocks<WP, true, true>(b, smax, per_read, side, arena); }
 
 extern "C" __attribute__((visibility("default")))
 uint32_t emu_aln_words(uint32_t what) { return what == 0u ? CBC_SALN_WORDS : what == 1u ? CBC_SALN_LDS : what == 2u ? CBC_SALN_T_LO : CBC_SALN_T_HI; }
@@ -75,34 +46,34 @@ int emu_stats_aln(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq,
     S.grid = grid ? grid : (wgs < CBC_STATS_GRID ? (uint32_t)wgs : CBC_STATS_GRID);
     A.side = side; A.arena = arena; A.ref = ref; A.tab = atab.data();
     A.arena_entries = n_recs * per_read; A.ref_bytes = ref_bytes; A.per_read = per_read;
-    WA::clear_ranges();
-    WA::add_range(tab.data(), CBC_STATS_WORDS);
-    WA::add_range(atab.data(), CBC_SALN_WORDS);
-    WA::edit_arena(arena, A.arena_entries);
+    WP::clear_ranges();
+    WP::add_range(tab.data(), CBC_STATS_WORDS); WP::add_uni_range(tab.data(), CBC_STATS_WORDS);
+    WP::add_range(atab.data(), CBC_SALN_WORDS); WP::add_uni_range(atab.data(), CBC_SALN_WORDS);
+    WP::edit_arena(arena, A.arena_entries);
     for (uint32_t wg = 0; wg < S.grid; wg++) {                       /* the statistics kernel */
         std::vector<uint32_t> lds(CBC_STATS_LDS, 0xdeadbeefu);
-        WA::wg_table(lds.data(), CBC_STATS_LDS);
-        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_zero<WA>(lds.data(), w, n_waves);
+        WP::wg_table(lds.data(), CBC_STATS_LDS);
+        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_zero<WP>(lds.data(), w, n_waves);
         for (uint32_t w = 0; w < n_waves; w++) {
-            if (iv) cbc_stats_accum<WA, true>(S, wg, w, n_waves, lds.data());
-            else cbc_stats_accum<WA, false>(S, wg, w, n_waves, lds.data());
+            if (iv) cbc_stats_accum<WP, true>(S, wg, w, n_waves, lds.data());
+            else cbc_stats_accum<WP, false>(S, wg, w, n_waves, lds.data());
         }
-        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_flush<WA>(S, lds.data(), w, n_waves);
-        WA::wg_table(nullptr, 0u);
+        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_flush<WP>(S, lds.data(), w, n_waves);
+        WP::wg_table(nullptr, 0u);
     }
     for (uint32_t wg = 0; wg < S.grid; wg++) {                       /* the alignment kernel */
         std::vector<uint32_t> lds(CBC_SALN_LDS, 0xdeadbeefu);        /* one table per workgroup, exactly CBC_SALN_LDS words */
-        WA::wg_table(lds.data(), CBC_SALN_LDS);
-        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_aln_zero<WA>(lds.data(), w, n_waves);
+        WP::wg_table(lds.data(), CBC_SALN_LDS);
+        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_aln_zero<WP>(lds.data(), w, n_waves);
         for (uint32_t w = 0; w < n_waves; w++) {
-            if (iv) cbc_stats_aln_accum<WA, true>(A, wg, w, n_waves, lds.data());
-            else cbc_stats_aln_accum<WA, false>(A, wg, w, n_waves, lds.data());
+            if (iv) cbc_stats_aln_accum<WP, true>(A, wg, w, n_waves, lds.data());
+            else cbc_stats_aln_accum<WP, false>(A, wg, w, n_waves, lds.data());
         }
-        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_aln_flush<WA>(A, lds.data(), w, n_waves);
-        WA::wg_table(nullptr, 0u);
+        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_aln_flush<WP>(A, lds.data(), w, n_waves);
+        WP::wg_table(nullptr, 0u);
     }
-    WA::clear_ranges();
-    WA::edit_arena(nullptr, 0);
+    WP::clear_ranges();
+    WP::edit_arena(nullptr, 0);
     if (tab[CBC_STATS_T_CTR + 1u] || atab[CBC_SALN_T_CTR + 1u] != (preload ? preload[CBC_SALN_T_CTR + 1u] : 0u)) emu_oob("a spare counter was written");
     if (g_emu_errors) return -100;
     for (uint32_t b = 0; b < n_blocks; b++) if (dec_results[b].status != CBC_ST_OK) return CBC_E_BLOCK;   /* all zero */
@@ -112,23 +83,8 @@ int emu_stats_aln(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq,
 }
 
 #ifdef ALNSTATS_EMU_MAIN
+#include "../emu/fab_reads.h"
 /* ---- the stand-alone check: fabricated records, rows and arena entries against an element-by-element host loop --------------- */
-struct fread_ {
-    uint32_t pos, flag; std::string seq; std::vector<uint32_t> dc, oi;
-    int raw_cnt, raw_e0;                                              /* >= 0: the side words as given, whatever the lists hold */
-    int want_valid;                                                   /* -1: whatever the host loop says */
-};
-struct fab {
-    uint32_t stride, per_read;
-    std::vector<fread_> reads;
-    std::vector<uint32_t> block_n;
-    std::vector<uint8_t> ref;                                         /* window start 0: position p is ref[p - 1] */
-};
-typedef std::vector<uint32_t> vu;
-
-static uint32_t g_rng = 2463534242u;
-static uint32_t rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 17; g_rng ^= g_rng << 5; return g_rng; }
-
 /* the semantics of include/cbc_gpu.h, one element at a time, into *a; false: not a valid record */
 static bool host_count(const fab &f, const fread_ &r, cbc_gpu_stats_aln *a)
 {
@@ -176,27 +132,6 @@ static bool host_count(const fab &f, const fread_ &r, cbc_gpu_stats_aln *a)
     return true;
 }
 
-/* a read of `len` bases at `pos` with the given edits: the reference's bytes at its aligned indices, but for those in `mis` */
-static fread_ &fab_read(fab &f, uint32_t pos, uint32_t flag, uint32_t len, vu dc, vu oi, vu mis = vu())
-{
-    fread_ r;
-    r.pos = pos; r.flag = flag; r.dc = dc; r.oi = oi; r.raw_cnt = r.raw_e0 = -1; r.want_valid = -1;
-    for (uint32_t i = 0; i < len; i++) r.seq.push_back("ACGTNacgtRn"[rnd() % 11u]);
-    uint32_t nb = 0;
-    for (uint32_t q = 0; q < len; q++) {
-        bool ins = false;
-        for (uint32_t o : oi) ins |= o == q;
-        if (ins) { nb++; continue; }
-        uint32_t m = q - nb, sh = 0;
-        for (uint32_t d : dc) sh += d <= m;
-        const uint64_t at = (uint64_t)pos - 1u + m + sh;
-        if (at < f.ref.size()) r.seq[q] = (char)f.ref[at];
-    }
-    for (uint32_t q : mis) if (q < len) r.seq[q] = (char)(r.seq[q] == 'A' ? 'C' : 'A');
-    f.reads.push_back(r);
-    return f.reads.back();
-}
-
 static bool same_aln(const cbc_gpu_stats_aln &a, const cbc_gpu_stats_aln &b, const char **which)
 {
 #define CMP(m) if (memcmp(a.m, b.m, sizeof a.m) != 0) { *which = #m; return false; }
@@ -211,49 +146,28 @@ static bool same_aln(const cbc_gpu_stats_aln &a, const cbc_gpu_stats_aln &b, con
 static int fab_check(const char *what, fab &f, uint32_t exclude, uint32_t grid, uint32_t n_waves, const vu *iv = NULL, int fail_block = -1,
                      uint32_t pre_lo = 0u, uint32_t pre_hi = 0u)
 {
-    const size_t n = f.reads.size(), nb = f.block_n.size();
-    std::vector<cbc_read_rec> recs(n ? n : 1);
-    std::vector<uint8_t> rows(n * f.stride + 8u, 0xEEu);            /* exactly the spare bytes cbc_region_block asks for */
-    std::vector<uint32_t> side(2u * (n ? n : 1), 0u), biv;
-    std::vector<uint16_t> arena(n * f.per_read, 0xEEEEu);
-    std::vector<cbc_dec_block_desc> blocks(nb);
-    std::vector<uint64_t> ws(nb, 0u);
-    std::vector<cbc_block_result> res(nb);
+    const size_t nb = f.block_n.size();
+    fab_arrays a;
+    if (!fab_build(f, a, fail_block, 2u)) { printf("%-66s BAD FIXTURE\n", what); return 1; }
+    vu biv;
+    for (size_t b = 0; b < nb; b++) { biv.push_back(0u); biv.push_back(iv ? (uint32_t)(iv->size() / 2u) : 0u); }
     std::vector<cbc_gpu_stats_aln> want(1), got(1);
     std::vector<cbc_gpu_stats> out(1);
     memset(&want[0], 0, sizeof want[0]);
     uint64_t counted = 0, excluded = 0;
-    size_t at = 0;
-    for (size_t b = 0; b < nb; b++) {
-        memset(&blocks[b], 0, sizeof blocks[b]); memset(&res[b], 0, sizeof res[b]);
-        blocks[b].rec_base = at; blocks[b].seq_base = (uint64_t)at * f.stride; blocks[b].n_reads = f.block_n[b]; blocks[b].seq_stride = f.stride;
-        biv.push_back(0u); biv.push_back(iv ? (uint32_t)(iv->size() / 2u) : 0u);
-        if ((int)b == fail_block) res[b].status = 2u;
-        uint32_t used = 0;
-        for (uint32_t k = 0; k < f.block_n[b]; k++, at++) {
-            fread_ &r = f.reads[at];
-            const uint32_t rl = (uint32_t)r.seq.size(), span = rl + (uint32_t)r.dc.size() - (r.oi.size() < rl ? (uint32_t)r.oi.size() : rl);
-            uint32_t *w = (uint32_t *)&recs[at];
-            w[0] = r.pos; w[1] = r.flag | (rl << 16); w[2] = k * f.stride; w[3] = span;
-            for (uint32_t i = 0; i < f.stride; i++) rows[at * f.stride + i] = i < rl ? (uint8_t)r.seq[i] : (uint8_t)"GCN"[i % 3u];   /* never zero */
-            side[2 * at] = r.raw_e0 >= 0 ? (uint32_t)r.raw_e0 : (r.dc.size() + r.oi.size()) ? used : 0u;
-            side[2 * at + 1] = r.raw_cnt >= 0 ? (uint32_t)r.raw_cnt : (uint32_t)r.dc.size() | ((uint32_t)r.oi.size() << 16);
-            if (r.raw_cnt < 0 && r.raw_e0 < 0) {
-                if (used + r.dc.size() + r.oi.size() > (size_t)f.block_n[b] * f.per_read) { printf("%-66s BAD FIXTURE\n", what); return 1; }
-                for (uint32_t d : r.dc) arena[blocks[b].rec_base * f.per_read + used++] = (uint16_t)d;
-                for (uint32_t o : r.oi) arena[blocks[b].rec_base * f.per_read + used++] = (uint16_t)o;
-            }
-            if (iv) {
-                bool hit = false;
-                for (size_t q = 0; q + 1u < iv->size() && !hit; q += 2u) hit = r.pos <= (*iv)[q + 1u] && r.pos + span - 1u >= (*iv)[q];
-                if (!hit) continue;
-            }
-            if (r.flag & exclude) { excluded++; continue; }
-            counted++;
-            const bool ok = host_count(f, r, &want[0]);
-            if (!ok) want[0].invalid++;
-            if (r.want_valid >= 0 && (r.want_valid != 0) != ok) { printf("%-66s BAD FIXTURE: read %zu validity\n", what, at); return 1; }
+    for (size_t at = 0; at < f.reads.size(); at++) {
+        const fread_ &r = f.reads[at];
+        for (uint32_t i = r.len; i < f.stride; i++) a.rows[at * f.stride + i] = (uint8_t)"GCN"[i % 3u];   /* behind the bases: never zero */
+        if (iv) {
+            bool hit = false;
+            for (size_t q = 0; q + 1u < iv->size() && !hit; q += 2u) hit = r.pos <= (*iv)[q + 1u] && r.pos + r.span - 1u >= (*iv)[q];
+            if (!hit) continue;
         }
+        if (r.flag & exclude) { excluded++; continue; }
+        counted++;
+        const bool ok = host_count(f, r, &want[0]);
+        if (!ok) want[0].invalid++;
+        if (r.want_valid >= 0 && (r.want_valid != 0) != ok) { printf("%-66s BAD FIXTURE: read %zu validity\n", what, at); return 1; }
     }
     std::vector<uint32_t> pre;
     if (pre_lo | pre_hi) {
@@ -261,8 +175,8 @@ static int fab_check(const char *what, fab &f, uint32_t exclude, uint32_t grid, 
         pre[emu_aln_words(2u) + 1u] = pre_lo; pre[emu_aln_words(3u) + 1u] = pre_hi;
         want[0].ins_len[1] += (uint64_t)pre_lo + ((uint64_t)pre_hi << 16);
     }
-    const int rc = emu_stats_aln(recs.data(), n, rows.data(), rows.size(), blocks.data(), ws.data(), res.data(), (uint32_t)nb,
-                                 iv ? iv->data() : NULL, iv ? (uint32_t)(iv->size() / 2u) : 0u, biv.data(), exclude, side.data(), arena.data(),
+    const int rc = emu_stats_aln(a.recs.data(), f.reads.size(), a.rows.data(), a.rows.size(), a.blocks.data(), a.ws.data(), a.res.data(), (uint32_t)nb,
+                                 iv ? iv->data() : NULL, iv ? (uint32_t)(iv->size() / 2u) : 0u, biv.data(), exclude, a.side.data(), a.arena.data(),
                                  f.per_read, f.ref.data(), f.ref.size(), grid, n_waves, pre.empty() ? NULL : pre.data(), &out[0], &got[0]);
     const char *which = "";
     int bad;
@@ -289,7 +203,7 @@ int main()
         /* reads without indels: every length the stride holds on both strands; perfect, a mismatch at the first base, at the last,
          * in the dword that straddles the read's end, at all three; at reference offset 0 and ending on the last uploaded byte
          * (valid), one byte further (not valid, and not read) */
-        fab f; f.stride = stride; f.per_read = 1u; f.ref = ref;
+        fab f; f.stride = stride; f.per_read = 1u; f.on_ref = true; f.ref = ref;
         uint32_t pos = 1u;
         for (size_t i = 0; i < n_lens; i++) {
             const uint32_t L = lens[i];
@@ -327,7 +241,7 @@ int main()
         bad |= fab_check(what, f, 0u, 0u, 4u, &iv);
     }
     {   /* reads with indels, stride 256 */
-        fab f; f.stride = 256u; f.per_read = 24u; f.ref = ref;
+        fab f; f.stride = 256u; f.per_read = 24u; f.on_ref = true; f.ref = ref;
         static const uint32_t ilens[] = { 1, 63, 64, 65, 127, 128, 129, 150, 256 };
         uint32_t pos = 5;
         for (size_t i = 0; i < sizeof ilens / sizeof ilens[0]; i++) {
@@ -390,7 +304,7 @@ int main()
         }
     }
     {   /* long lists: nDel and nIns above 64, 127 one-base I runs, an arena of exactly the needed size */
-        fab g; g.stride = 256u; g.per_read = 135u; g.ref = ref;                   /* 70 + 70 + 245 + 88 + 127 + 210 = 6 * 135 entries */
+        fab g; g.stride = 256u; g.per_read = 135u; g.on_ref = true; g.ref = ref;                   /* 70 + 70 + 245 + 88 + 127 + 210 = 6 * 135 entries */
         vu d70(70u, 100u), d200, i70, i40, i127, d210;
         for (uint32_t i = 0; i < 200u; i++) d200.push_back(10u + i / 2u);
         for (uint32_t i = 0; i < 70u; i++) i70.push_back(60u + i);

@@ -7,42 +7,13 @@
  * -DCIGAR_EMU_MAIN the file is a stand-alone program that builds the fabricated cases itself, compares them with an
  * element-by-element host loop and exits non-zero on a mismatch (make asan_check).
  */
-#include <vector>
-#include <string>
-#include "wave_emu_cigar.h"
-#include "../../cbc_amd/csrc/cbc_encode_body.h"
-#include "../../cbc_amd/csrc/cbc_decode_body.h"
-#include "../../cbc_amd/csrc/cbc_plan.h"
+#include "../emu/post_emu.h"
 #include "../../cbc_amd/csrc/cbc_cigar_body.h"
-
-typedef WaveEmuCigar WC;
-
-static int g_emu_errors = 0;
-extern "C" void emu_oob(const char *what) { fprintf(stderr, "[emu] invariant violated: %s\n", what); g_emu_errors++; }
 
 /* the edit-reporting decoder over every block of the batch: side = 2 * n_recs words, arena = n_recs * per_read entries exactly */
 extern "C" __attribute__((visibility("default")))
 int emu_cigar_decode(const cbc_dec_device_batch *b, uint32_t smax, uint32_t per_read, uint32_t *side, uint16_t *arena)
-{
-    cbc_dec_args A;
-    memset(&A, 0, sizeof A);
-    A.in = b->d_in; A.blocks = b->d_blocks; A.ref = b->d_ref; A.recs = b->d_recs; A.seq = b->d_seq; A.results = b->d_results;
-    A.in_bytes = b->in_bytes; A.ref_bytes = b->ref_bytes; A.n_recs = b->n_recs; A.seq_bytes = b->seq_bytes;
-    A.n_blocks = b->n_blocks; A.cap_pos = b->caps.cap_pos; A.cap_var = b->caps.cap_var;
-    A.var_scratch = b->d_var_scratch; A.var_scratch_words = b->var_scratch_words;
-    cbc_dec_edits E;
-    memset(&E, 0, sizeof E);
-    E.side = side; E.arena = arena; E.arena_entries = b->n_recs * per_read; E.per_read = per_read;
-    g_emu_errors = 0;
-    WC::edit_arena(arena, E.arena_entries);
-    uint32_t words = cbc_plan_dec_lds_bytes(&b->caps) / 4;
-    for (uint32_t blk = 0; blk < b->n_blocks; blk++) {
-        std::vector<uint32_t> lds(words, 0xdeadbeefu);
-        cbc_decode_stream<WC, true, true>(A, blk, lds.data(), smax, &E);
-    }
-    WC::edit_arena(nullptr, 0);
-    return g_emu_errors ? -100 : 0;
-}
+{ return emu_decode_blocks<WP, true, true>(b, smax, per_read, side, arena); }
 
 /* ONE cbc_gpu_decode_sam_cigar behind the decode.  out[0] = text bytes (also when text_cap is too small: CBC_E_ARG, nothing
  * written), out[1] = reads.  CBC_E_BLOCK (after the text of the other blocks) when a block of the call failed.  n_waves
@@ -69,26 +40,26 @@ int emu_sam_cigar(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq,
     A.S.block_name = block_name; A.S.names = names; A.S.names_bytes = names_bytes; A.S.region = region ? 1u : 0u;
     A.side = side; A.arena = arena; A.ref = ref; A.meas = meas.data();
     A.arena_entries = n_recs * per_read; A.ref_bytes = ref_bytes; A.per_read = per_read;
-    WC::clear_ranges();
-    WC::add_range(meas.data(), n_recs * 2u);
-    WC::add_range((const uint32_t *)counts.data(), (uint64_t)n_blocks * 4u);
-    WC::edit_arena(arena, A.arena_entries);
+    WP::clear_ranges();
+    WP::add_range(meas.data(), n_recs * 2u); WP::add_uni_range(meas.data(), n_recs * 2u);
+    WP::add_range((const uint32_t *)counts.data(), (uint64_t)n_blocks * 4u); WP::add_uni_range((const uint32_t *)counts.data(), (uint64_t)n_blocks * 4u);
+    WP::edit_arena(arena, A.arena_entries);
     for (uint32_t b = 0; b < n_blocks; b++)
-        for (uint32_t w = 0; w < n_waves; w++) cbc_cigar_measure<WC>(A, b, w, n_waves);
-    for (uint32_t b = 0; b < n_blocks; b++) cbc_sam_cigar_count<WC>(A, b);
+        for (uint32_t w = 0; w < n_waves; w++) cbc_cigar_measure<WP>(A, b, w, n_waves);
+    for (uint32_t b = 0; b < n_blocks; b++) cbc_sam_cigar_count<WP>(A, b);
     for (uint32_t b = 0; b < n_blocks; b++) { offsets[b + 1u] = offsets[b] + counts[b].nbytes; out[1] += counts[b].n_symbols; }
     out[0] = offsets[n_blocks];
     int rc = 0;
     if (out[0] > text_cap) rc = CBC_E_ARG;
     else {
-        WC::text_range(text, out[0]);
+        WP::text_range(text, out[0]);
         for (uint32_t b = 0; b < n_blocks; b++)
-            for (uint32_t w = 0; w < n_waves; w++) cbc_sam_cigar_write<WC>(A, b, w, n_waves);
-        for (size_t i = 0; i < WC::tx_seen().size(); i++) if (!WC::tx_seen()[i]) { emu_oob("a byte of the text is not written"); break; }
-        WC::text_range(nullptr, 0);
+            for (uint32_t w = 0; w < n_waves; w++) cbc_sam_cigar_write<WP>(A, b, w, n_waves);
+        for (size_t i = 0; i < WP::tx_seen().size(); i++) if (!WP::tx_seen()[i]) { emu_oob("a byte of the text is not written"); break; }
+        WP::text_range(nullptr, 0);
     }
-    WC::clear_ranges();
-    WC::edit_arena(nullptr, 0);
+    WP::clear_ranges();
+    WP::edit_arena(nullptr, 0);
     if (g_emu_errors) return -100;
     if (rc) return rc;
     for (uint32_t b = 0; b < n_blocks; b++) if (dec_results[b].status != CBC_ST_OK) return CBC_E_BLOCK;
@@ -96,22 +67,8 @@ int emu_sam_cigar(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq,
 }
 
 #ifdef CIGAR_EMU_MAIN
+#include "../emu/fab_reads.h"
 /* ---- the stand-alone check: fabricated records, rows and arena entries against an element-by-element host loop --------------- */
-struct fread_ {
-    uint32_t pos, flag; std::string seq; std::vector<uint32_t> dc, oi;
-    int raw_cnt, raw_e0;                                              /* >= 0: the side words as given, whatever the lists hold */
-    std::string want;                                                 /* "" = the plain line; else CIGAR \t NM \t MD */
-};
-struct fab {
-    uint32_t stride, per_read;
-    std::vector<fread_> reads;
-    std::vector<uint32_t> block_n;
-    std::vector<uint8_t> ref;                                         /* window start 0: position p is ref[p - 1] */
-};
-
-static uint32_t g_rng = 2463534242u;
-static uint32_t rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 17; g_rng ^= g_rng << 5; return g_rng; }
-
 /* the semantics of include/cbc_gpu.h, one element at a time; false: not what the decoder writes */
 static bool host_tags(const fab &f, const fread_ &r, std::string &out)
 {
@@ -162,28 +119,6 @@ static bool host_tags(const fab &f, const fread_ &r, std::string &out)
     return true;
 }
 
-/* a read of `len` bases at `pos` with the given edits: the reference's bytes at its aligned indices, but for those in `mis` */
-static fread_ &fab_read(fab &f, uint32_t pos, uint32_t flag, uint32_t len, std::vector<uint32_t> dc, std::vector<uint32_t> oi,
-                        std::vector<uint32_t> mis = std::vector<uint32_t>())
-{
-    fread_ r;
-    r.pos = pos; r.flag = flag; r.dc = dc; r.oi = oi; r.raw_cnt = r.raw_e0 = -1;
-    for (uint32_t i = 0; i < len; i++) r.seq.push_back("ACGTNacgtRn"[rnd() % 11u]);
-    uint32_t nb = 0;
-    for (uint32_t q = 0; q < len; q++) {
-        bool ins = false;
-        for (uint32_t o : oi) ins |= o == q;
-        if (ins) { nb++; continue; }
-        uint32_t m = q - nb, sh = 0;
-        for (uint32_t d : dc) sh += d <= m;
-        const uint64_t at = (uint64_t)pos - 1u + m + sh;
-        if (at < f.ref.size()) r.seq[q] = (char)f.ref[at];
-    }
-    for (uint32_t q : mis) if (q < len) r.seq[q] = (char)(r.seq[q] == 'A' ? 'C' : 'A');
-    f.reads.push_back(r);
-    return f.reads.back();
-}
-
 static std::string sam_line(const fread_ &r, const std::string &name, const std::string &tags)
 {
     std::string s = "*\t" + std::to_string(r.flag) + "\t" + name + "\t" + std::to_string(r.pos) + "\t255\t";
@@ -196,49 +131,32 @@ static int fab_check(const char *what, fab &f, int region, uint64_t beg, uint64_
                      uint32_t fail_status = 2u)
 {
     const std::string name = "ctg";
-    const size_t n = f.reads.size(), nb = f.block_n.size();
-    std::vector<cbc_read_rec> recs(n ? n : 1);
-    std::vector<uint8_t> rows(n * f.stride + 8u, 0xEEu);            /* exactly the spare bytes cbc_region_block asks for */
-    std::vector<uint32_t> side(2u * (n ? n : 1), 0u), bn(2u * nb, 0u);
-    std::vector<uint16_t> arena(n * f.per_read, 0xEEEEu);
-    std::vector<cbc_dec_block_desc> blocks(nb);
-    std::vector<uint64_t> ws(nb, 0u);
-    std::vector<cbc_block_result> res(nb);
+    const size_t nb = f.block_n.size();
+    fab_arrays a;
+    if (!fab_build(f, a, fail_block, fail_status)) { printf("%-66s BAD FIXTURE\n", what); return 1; }
+    vu bn;
+    for (size_t b = 0; b < nb; b++) { bn.push_back(0u); bn.push_back((uint32_t)name.size()); }
     std::string want;
     uint64_t kept = 0;
     size_t at = 0;
-    for (size_t b = 0; b < nb; b++) {
-        memset(&blocks[b], 0, sizeof blocks[b]); memset(&res[b], 0, sizeof res[b]);
-        blocks[b].rec_base = at; blocks[b].seq_base = (uint64_t)at * f.stride; blocks[b].n_reads = f.block_n[b]; blocks[b].seq_stride = f.stride;
-        bn[2u * b] = 0u; bn[2u * b + 1u] = (uint32_t)name.size();
-        if ((int)b == fail_block) res[b].status = fail_status;
-        uint32_t used = 0;
+    for (size_t b = 0; b < nb; b++)
         for (uint32_t k = 0; k < f.block_n[b]; k++, at++) {
-            fread_ &r = f.reads[at];
-            const uint32_t rl = (uint32_t)r.seq.size(), span = rl + (uint32_t)r.dc.size() - (r.oi.size() < rl ? (uint32_t)r.oi.size() : rl);
-            uint32_t *w = (uint32_t *)&recs[at];
-            w[0] = r.pos; w[1] = r.flag | (rl << 16); w[2] = k * f.stride; w[3] = span;
-            memcpy(rows.data() + at * f.stride, r.seq.data(), r.seq.size());
-            side[2 * at] = r.raw_e0 >= 0 ? (uint32_t)r.raw_e0 : (r.dc.size() + r.oi.size()) ? used : 0u;
-            side[2 * at + 1] = r.raw_cnt >= 0 ? (uint32_t)r.raw_cnt : (uint32_t)r.dc.size() | ((uint32_t)r.oi.size() << 16);
-            if (r.raw_cnt < 0 && r.raw_e0 < 0) {
-                if (used + r.dc.size() + r.oi.size() > (size_t)f.block_n[b] * f.per_read) { printf("%-66s BAD FIXTURE\n", what); return 1; }
-                for (uint32_t d : r.dc) arena[blocks[b].rec_base * f.per_read + used++] = (uint16_t)d;
-                for (uint32_t o : r.oi) arena[blocks[b].rec_base * f.per_read + used++] = (uint16_t)o;
-            }
+            const fread_ &r = f.reads[at];
             if ((int)b == fail_block) continue;
-            if (region && (r.pos > end || (uint64_t)r.pos + span < beg + 1u)) continue;
+            if (region && (r.pos > end || (uint64_t)r.pos + r.span < beg + 1u)) continue;
             std::string tags;
             if (r.raw_cnt >= 0 || r.raw_e0 >= 0 || !host_tags(f, r, tags)) tags.clear();
             if (!r.want.empty() && r.want != tags) { printf("%-66s BAD FIXTURE: read %zu is %s, meant %s\n", what, at, tags.c_str(), r.want.c_str()); return 1; }
             want += sam_line(r, name, tags); kept++;
         }
-    }
     std::vector<uint8_t> text(want.size() + 16u, 0xEEu);
     uint64_t out[2] = { 0, 0 };
-    const int rc = emu_sam_cigar(recs.data(), n, rows.data(), rows.size(), blocks.data(), ws.data(), res.data(), (uint32_t)nb, bn.data(),
-                                 (const uint8_t *)name.data(), (uint32_t)name.size(), region, beg, end, side.data(), arena.data(), f.per_read,
-                                 f.ref.data(), f.ref.size(), n_waves, text.data(), want.size(), out);
+    auto call = [&](uint8_t *t, uint64_t cap) {
+        return emu_sam_cigar(a.recs.data(), f.reads.size(), a.rows.data(), a.rows.size(), a.blocks.data(), a.ws.data(), a.res.data(), (uint32_t)nb, bn.data(),
+                             (const uint8_t *)name.data(), (uint32_t)name.size(), region, beg, end, a.side.data(), a.arena.data(), f.per_read,
+                             f.ref.data(), f.ref.size(), n_waves, t, cap, out);
+    };
+    const int rc = call(text.data(), want.size());
     int bad = rc != (fail_block >= 0 ? CBC_E_BLOCK : 0) || out[0] != want.size() || out[1] != kept || memcmp(text.data(), want.data(), want.size()) != 0;
     for (size_t i = want.size(); i < text.size(); i++) bad |= text[i] != 0xEEu;
     printf("%-66s %s (rc %d, %llu bytes, %llu reads)\n", what, bad ? "MISMATCH" : "ok", rc, (unsigned long long)out[0], (unsigned long long)out[1]);
@@ -249,26 +167,17 @@ static int fab_check(const char *what, fab &f, int region, uint64_t beg, uint64_
         size_t e = want.find('\n', i);
         printf("  want: %s\n  got:  %.*s\n", want.substr(a, e - a).c_str(), (int)(e - a), (const char *)text.data() + a);
     }
-    if (!bad && want.size() > 0) {                                   /* one byte short: the size, CBC_E_ARG, nothing written */
-        std::vector<uint8_t> t2(want.size() + 16u, 0xEEu);
-        const int rc2 = emu_sam_cigar(recs.data(), n, rows.data(), rows.size(), blocks.data(), ws.data(), res.data(), (uint32_t)nb, bn.data(),
-                                      (const uint8_t *)name.data(), (uint32_t)name.size(), region, beg, end, side.data(), arena.data(), f.per_read,
-                                      f.ref.data(), f.ref.size(), n_waves, t2.data(), want.size() - 1u, out);
-        bad |= rc2 != CBC_E_ARG || out[0] != want.size();
-        for (size_t i = 0; i < t2.size(); i++) bad |= t2[i] != 0xEEu;
-        if (bad) printf("%-66s MISMATCH (text_cap one byte short: rc %d)\n", what, rc2);
-    }
+    if (!bad && want.size() > 0) bad |= fab_short_probe(what, 66, call, want.size(), out);
     return bad;
 }
 
 int main()
 {
     int bad = 0;
-    fab f; f.stride = 256u; f.per_read = 16u;
+    fab f; f.stride = 256u; f.per_read = 16u; f.on_ref = true;
     for (uint32_t i = 0; i < 9000u; i++) f.ref.push_back("ACGTNacgtnRYk"[rnd() % 13u]);    /* lower-case and IUPAC reference bytes */
     static const uint32_t lens[] = { 1, 63, 64, 65, 127, 128, 129, 150, 256 };
     uint32_t pos = 5;
-    typedef std::vector<uint32_t> vu;
     for (size_t i = 0; i < sizeof lens / sizeof lens[0]; i++) {
         const uint32_t L = lens[i];
         fab_read(f, pos += 7u, 0u, L, vu(), vu()).want = std::to_string(L) + "M\t0\t" + std::to_string(L);      /* perfect */
@@ -331,7 +240,7 @@ int main()
         if (!r.dc.empty()) { snprintf(what, sizeof what, "region on the deleted bases of read %zu", i); bad |= fab_check(what, f, 1, r.pos + r.dc[0], r.pos + r.dc[0], 4u); }
     }
     {   /* long lists: a deletion run of 70 bases, 70 inserted bases, 200 + 40 entries in one read; an arena of exactly the needed size */
-        fab g; g.stride = 256u; g.per_read = 117u; g.ref = f.ref;               /* 70 + 70 + 240 + 88 = 4 * 117 entries */
+        fab g; g.stride = 256u; g.per_read = 117u; g.on_ref = true; g.ref = f.ref;               /* 70 + 70 + 240 + 88 = 4 * 117 entries */
         vu d70(70u, 100u), d200, i70, i40;
         for (uint32_t i = 0; i < 200u; i++) d200.push_back(10u + i / 2u);
         for (uint32_t i = 0; i < 70u; i++) i70.push_back(60u + i);

@@ -2,44 +2,14 @@
  * depth_emu.cpp -- the coverage bodies (cbc_amd/csrc/cbc_depth_body.h) on the CPU through the lock-step wave emulation.
  * TEST AID ONLY: mark, tile sums, change points, line count and text are checked against the Python model
  * (tests/depthmodel.py) under ASan-able host code before anything runs on a GPU.  The records come from the emulated span
- * decoder or from arrays the test builds.  The scans between the passes are the host loops below (on the device:
- * cbc_scan_sizes_kernel).
+ * decoder or from arrays the test builds.  The scans between the passes are the host loop of tests/emu/post_emu.h (on the
+ * device: cbc_scan_sizes_kernel).
  */
-#include <vector>
-#include "wave_emu_depth.h"
-#include "../../cbc_amd/csrc/cbc_encode_body.h"
-#include "../../cbc_amd/csrc/cbc_decode_body.h"
-#include "../../cbc_amd/csrc/cbc_plan.h"
-#include "../../cbc_amd/csrc/cbc_depth_body.h"
-
-static int g_emu_errors = 0;
-extern "C" void emu_oob(const char *what) { fprintf(stderr, "[emu] invariant violated: %s\n", what); g_emu_errors++; }
+#include "../emu/post_emu.h"
 
 /* the span-reporting decoder over every block of the batch */
 extern "C" __attribute__((visibility("default")))
-int emu_depth_decode(const cbc_dec_device_batch *b, uint32_t smax)
-{
-    cbc_dec_args A;
-    memset(&A, 0, sizeof A);
-    A.in = b->d_in; A.blocks = b->d_blocks; A.ref = b->d_ref; A.recs = b->d_recs; A.seq = b->d_seq; A.results = b->d_results;
-    A.in_bytes = b->in_bytes; A.ref_bytes = b->ref_bytes; A.n_recs = b->n_recs; A.seq_bytes = b->seq_bytes;
-    A.n_blocks = b->n_blocks; A.cap_pos = b->caps.cap_pos; A.cap_var = b->caps.cap_var;
-    A.var_scratch = b->d_var_scratch; A.var_scratch_words = b->var_scratch_words;
-    g_emu_errors = 0;
-    uint32_t words = cbc_plan_dec_lds_bytes(&b->caps) / 4;
-    for (uint32_t blk = 0; blk < b->n_blocks; blk++) {
-        std::vector<uint32_t> lds(words, 0xdeadbeefu);
-        cbc_decode_stream<WaveEmuDepth, true>(A, blk, lds.data(), smax);
-    }
-    return g_emu_errors ? -100 : 0;
-}
-
-static void scan(const cbc_block_result *r, uint64_t *off, uint32_t n)
-{
-    uint64_t run = 0;
-    for (uint32_t i = 0; i < n; i++) { off[i] = run; run += r[i].status == CBC_ST_OK ? r[i].nbytes : 0u; }
-    off[n] = run;
-}
+int emu_depth_decode(const cbc_dec_device_batch *b, uint32_t smax) { return emu_decode_blocks<WP, true>(b, smax); }
 
 /* every pass in the order of cbc_gpu_decode_depth.  out[0] = text bytes, out[1] = lines, out[2] = reads kept, out[3] = change
  * points.  Returns -1 (CBC_E_ARG) with out[] set and nothing written when the text does not fit text_cap.  Every array is
@@ -68,16 +38,13 @@ int emu_depth(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq, uin
     A.diff = diff.data(); A.diff_words = diff.size(); A.tile_sum = tsum.data(); A.tile_cnt = tcnt.data();
     A.sum_off = soff.data(); A.cnt_off = coff.data(); A.cp_pos = cp_pos.data(); A.cp_dep = cp_dep.data(); A.cp_cap = cp_cap;
     A.ctr = ctr; A.name = nm.data(); A.name_len = name_len; A.exclude = exclude; A.n_tiles = n_tiles; A.n_ttiles = n_ttiles;
-    for (uint32_t b = 0; b < n_blocks; b++) cbc_depth_mark<WaveEmuDepth>(A, b);
-    for (uint32_t t = 0; t < n_tiles; t++) cbc_depth_tile<WaveEmuDepth>(A, t);
-    scan(tsum.data(), soff.data(), n_tiles);
-    scan(tcnt.data(), coff.data(), n_tiles);
-    for (uint32_t t = 0; t < n_tiles; t++) cbc_depth_compact<WaveEmuDepth>(A, t);
-    if (cp_pos[cp_cap] != 0xEEEEEEEEu || cp_dep[cp_cap] != 0xEEEEEEEEu) emu_oob("change point written past the table");
-    for (uint32_t t = 0; t < n_ttiles; t++) cbc_depth_count<WaveEmuDepth>(A, t);
+    for (uint32_t b = 0; b < n_blocks; b++) cbc_depth_mark<WP>(A, b);
+    uint32_t ncp = 0;
+    emu_depth_points<WP>(A, soff.data(), coff.data(), "change point", &ncp);
+    for (uint32_t t = 0; t < n_ttiles; t++) cbc_depth_count<WP>(A, t);
     scan(counts.data(), toff.data(), n_ttiles);
     out[0] = toff[n_ttiles]; out[1] = ctr[1]; out[2] = ctr[0]; out[3] = coff[n_tiles];
     if (out[0] > text_cap) return CBC_E_ARG;
-    for (uint32_t t = 0; t < n_ttiles; t++) cbc_depth_write<WaveEmuDepth>(A, t);
+    for (uint32_t t = 0; t < n_ttiles; t++) cbc_depth_write<WP>(A, t);
     return g_emu_errors ? -100 : 0;
 }

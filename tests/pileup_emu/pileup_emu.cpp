@@ -7,46 +7,16 @@
  * past one is a finding.  With -DPILEUP_EMU_MAIN the file is a stand-alone program that builds the fabricated cases itself,
  * compares them with a base-by-base host loop and exits non-zero on a mismatch (make asan_check).
  */
-#include <vector>
-#include <string>
-#include "wave_emu_pileup.h"
-#include "../../cbc_amd/csrc/cbc_encode_body.h"
-#include "../../cbc_amd/csrc/cbc_decode_body.h"
-#include "../../cbc_amd/csrc/cbc_plan.h"
-#include "../../cbc_amd/csrc/cbc_pileup_body.h"
-
-typedef WaveEmuPileup WP;
-
-static int g_emu_errors = 0;
-extern "C" void emu_oob(const char *what) { fprintf(stderr, "[emu] invariant violated: %s\n", what); g_emu_errors++; }
+#include "../emu/post_emu.h"
 
 /* the edit-reporting decoder over every block of the batch: side = 2 * n_recs words, arena = n_recs * per_read entries exactly */
 extern "C" __attribute__((visibility("default")))
 int emu_pileup_decode(const cbc_dec_device_batch *b, uint32_t smax, uint32_t per_read, uint32_t *side, uint16_t *arena)
-{
-    cbc_dec_args A;
-    memset(&A, 0, sizeof A);
-    A.in = b->d_in; A.blocks = b->d_blocks; A.ref = b->d_ref; A.recs = b->d_recs; A.seq = b->d_seq; A.results = b->d_results;
-    A.in_bytes = b->in_bytes; A.ref_bytes = b->ref_bytes; A.n_recs = b->n_recs; A.seq_bytes = b->seq_bytes;
-    A.n_blocks = b->n_blocks; A.cap_pos = b->caps.cap_pos; A.cap_var = b->caps.cap_var;
-    A.var_scratch = b->d_var_scratch; A.var_scratch_words = b->var_scratch_words;
-    cbc_dec_edits E;
-    memset(&E, 0, sizeof E);
-    E.side = side; E.arena = arena; E.arena_entries = b->n_recs * per_read; E.per_read = per_read;
-    g_emu_errors = 0;
-    WP::edit_arena(arena, E.arena_entries);
-    uint32_t words = cbc_plan_dec_lds_bytes(&b->caps) / 4;
-    for (uint32_t blk = 0; blk < b->n_blocks; blk++) {
-        std::vector<uint32_t> lds(words, 0xdeadbeefu);
-        cbc_decode_stream<WP, true, true>(A, blk, lds.data(), smax, &E);
-    }
-    WP::edit_arena(nullptr, 0);
-    return g_emu_errors ? -100 : 0;
-}
+{ return emu_decode_blocks<WP, true, true>(b, smax, per_read, side, arena); }
 
-/* ONE cbc_gpu_decode_pileup behind the decode.  out[0] = text bytes (also when text_cap is too small: CBC_E_ARG, nothing
- * written), out[1] = lines, out[2] = reads kept.  CBC_E_BLOCK (after the text of the other blocks) when a block of the call
- * failed.  n_waves wavefronts share a block in the events pass. */
+/* ONE cbc_gpu_decode_pileup behind the decode: the plain bodies through the driver of tests/emu/post_emu.h.  out[0] = text bytes
+ * (also when text_cap is too small: CBC_E_ARG, nothing written), out[1] = lines, out[2] = reads kept.  CBC_E_BLOCK (after the
+ * text of the other blocks) when a block of the call failed.  n_waves wavefronts share a block in the events pass. */
 extern "C" __attribute__((visibility("default")))
 int emu_pileup(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq, uint64_t seq_bytes, const cbc_dec_block_desc *blocks,
                const uint64_t *window_start, const cbc_block_result *dec_results, uint32_t n_blocks, const uint32_t *side,
@@ -54,118 +24,13 @@ int emu_pileup(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq, ui
                uint32_t name_len, uint64_t beg, uint64_t end, uint32_t exclude, uint32_t min_alt, uint32_t n_waves, uint8_t *text,
                uint64_t text_cap, uint64_t *out)
 {
-    g_emu_errors = 0;
-    out[0] = out[1] = out[2] = 0;
-    if (beg < 1 || beg > end || end > CBC_SAM_MAX_POS || n_waves < 1u || n_waves > 16u || min_alt < 1u) return CBC_E_ARG;
-    const uint64_t d_words = end - beg + 2u;
-    const uint32_t n_tiles = (uint32_t)((d_words + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
-    std::vector<uint32_t> diff((size_t)n_tiles * CBC_DEPTH_TILE, 0u), tab((size_t)n_tiles * CBC_DEPTH_TILE * CBC_PILEUP_PLANES, 0u), ctr(4, 0u);
-    std::vector<cbc_block_result> tile_sum(n_tiles), tile_cnt(n_tiles), counts(n_tiles);
-    std::vector<uint64_t> sum_off(n_tiles + 1u, 0u), offsets(n_tiles + 1u, 0u);
-    std::vector<uint8_t> dname(name, name + name_len);
-    cbc_pileup_args A;
-    memset(&A, 0, sizeof A);
-    cbc_region_args &R = A.D.R;
-    R.recs = recs; R.seq = seq; R.blocks = blocks; R.window_start = window_start; R.dec_results = dec_results;
-    R.counts = counts.data(); R.offsets = offsets.data(); R.text = text; R.text_cap = text_cap;
-    R.n_recs = n_recs; R.seq_bytes = seq_bytes; R.beg = beg; R.end = end; R.n_blocks = n_blocks;
-    A.D.diff = diff.data(); A.D.diff_words = diff.size(); A.D.tile_sum = tile_sum.data(); A.D.tile_cnt = tile_cnt.data();
-    A.D.sum_off = sum_off.data(); A.D.cnt_off = sum_off.data(); A.D.ctr = ctr.data(); A.D.name = dname.data();
-    A.D.name_len = name_len; A.D.exclude = exclude; A.D.n_tiles = n_tiles; A.D.n_ttiles = n_tiles;
-    A.side = side; A.arena = arena; A.arena_entries = n_recs * per_read; A.per_read = per_read;
-    A.ref = ref; A.ref_bytes = ref_bytes; A.ref_c0 = ref_c0; A.tab = tab.data(); A.plane = diff.size(); A.min_alt = min_alt;
-    WP::clear_ranges();
-    /* the window's own words only: W + 1 of the difference array, W of every plane */
-    WP::add_range(diff.data(), d_words);
-    for (uint32_t k = 0; k < CBC_PILEUP_PLANES; k++) WP::add_range(tab.data() + (size_t)k * A.plane, d_words - 1u);
-    WP::add_range(ctr.data(), 2);
-    WP::edit_arena(arena, A.arena_entries);
-    for (uint32_t b = 0; b < n_blocks; b++) cbc_depth_mark<WP>(A.D, b);
-    for (uint32_t b = 0; b < n_blocks; b++)
-        for (uint32_t w = 0; w < n_waves; w++) cbc_pileup_events<WP>(A, b, w, n_waves);
-    for (uint32_t t = 0; t < n_tiles; t++) cbc_depth_tile<WP>(A.D, t);
-    for (uint32_t t = 0; t < n_tiles; t++) sum_off[t + 1u] = sum_off[t] + tile_sum[t].nbytes;
-    for (uint32_t t = 0; t < n_tiles; t++) cbc_pileup_count<WP>(A, t);
-    for (uint32_t t = 0; t < n_tiles; t++) offsets[t + 1u] = offsets[t] + counts[t].nbytes;
-    out[0] = offsets[n_tiles]; out[1] = ctr[1]; out[2] = ctr[0];
-    int rc = 0;
-    if (out[0] > text_cap) rc = CBC_E_ARG;
-    else for (uint32_t t = 0; t < n_tiles; t++) cbc_pileup_write<WP>(A, t);
-    WP::clear_ranges();
-    WP::edit_arena(nullptr, 0);
-    if (g_emu_errors) return -100;
-    if (rc) return rc;
-    for (uint32_t b = 0; b < n_blocks; b++) if (dec_results[b].status != CBC_ST_OK) return CBC_E_BLOCK;
-    return 0;
+    return emu_pileup_call(recs, n_recs, seq, seq_bytes, blocks, window_start, dec_results, n_blocks, side, arena, per_read, ref, ref_bytes, ref_c0,
+                           name, name_len, beg, end, exclude, min_alt, 0u, 0u, n_waves, 0u, 0u, text, text_cap, out);
 }
 
 #ifdef PILEUP_EMU_MAIN
+#include "../emu/fab_reads.h"
 /* ---- the stand-alone check: fabricated records, rows and arena entries against a base-by-base host loop ---------------------- */
-struct fread_ { uint32_t pos, flag, span; std::string seq; std::vector<uint32_t> dc, oi; };
-struct fab {
-    uint32_t stride, per_read;
-    std::vector<fread_> reads;
-    std::vector<uint32_t> block_n;                                    /* reads per block */
-    std::vector<uint8_t> ref;                                         /* window start 0: position p is ref[p - 1] */
-};
-
-static uint32_t g_rng = 2463534242u;
-static uint32_t rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 17; g_rng ^= g_rng << 5; return g_rng; }
-
-static uint32_t klass(uint8_t b) { b &= 0xdfu; return b == 'A' ? 0u : b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 4u; }
-
-/* a read of `len` bases at `pos` with the given edits; span < 0: the honest one */
-static void fab_read(fab &f, uint32_t pos, uint32_t flag, uint32_t len, std::vector<uint32_t> dc, std::vector<uint32_t> oi, int span = -1)
-{
-    fread_ r;
-    r.pos = pos; r.flag = flag; r.dc = dc; r.oi = oi;
-    r.span = span >= 0 ? (uint32_t)span : len + (uint32_t)dc.size() - (uint32_t)oi.size();
-    for (uint32_t i = 0; i < len; i++) r.seq.push_back("ACGTNacgtRn"[rnd() % 11u]);
-    f.reads.push_back(r);
-}
-
-struct tables { std::vector<uint64_t> cnt[5], del, ins, depth; uint64_t kept; };
-
-/* the definitions of include/cbc_gpu.h, one base at a time */
-static void want_tables(const fab &f, uint64_t beg, uint64_t end, uint32_t exclude, const std::vector<int> &failed, tables &T)
-{
-    const size_t W = (size_t)(end - beg + 1u);
-    for (int k = 0; k < 5; k++) T.cnt[k].assign(W, 0);
-    T.del.assign(W, 0); T.ins.assign(W, 0); T.depth.assign(W, 0); T.kept = 0;
-    size_t at = 0;
-    for (size_t b = 0; b < f.block_n.size(); b++)
-        for (uint32_t k = 0; k < f.block_n[b]; k++, at++) {
-            const fread_ &r = f.reads[at];
-            if (failed[b] || r.span < 1u || (r.flag & exclude) || r.pos > end || (uint64_t)r.pos + r.span - 1u < beg) continue;
-            T.kept++;
-            for (uint64_t p = r.pos; p < (uint64_t)r.pos + r.span; p++) if (p >= beg && p <= end) T.depth[p - beg]++;
-            const uint32_t rl = (uint32_t)r.seq.size();
-            bool prev_ins = false;
-            int64_t last = -1;                                       /* offset of the nearest aligned base before q */
-            for (uint32_t q = 0; q < rl; q++) {
-                uint32_t nb = 0; bool isins = false;
-                for (uint32_t o : r.oi) { nb += o < q; isins |= o == q; }
-                const uint32_t m = q - nb;
-                uint32_t sh = 0;
-                for (uint32_t d : r.dc) sh += d <= m;
-                if (!isins) {
-                    last = (int64_t)m + sh;
-                    const uint64_t p = (uint64_t)r.pos + m + sh;
-                    if ((uint64_t)m + sh < r.span && p >= beg && p <= end) T.cnt[klass((uint8_t)r.seq[q])][p - beg]++;
-                } else if (!prev_ins) {
-                    /* `last` is the aligned base in front of the run whether or not it fell inside the span */
-                    const uint64_t off = m == 0u ? 0u : (uint64_t)last, p = r.pos + off;
-                    if (off < r.span && p >= beg && p <= end) T.ins[p - beg]++;
-                }
-                prev_ins = isins;
-            }
-            for (size_t d = 0; d < r.dc.size(); d++) {
-                const uint64_t off = (uint64_t)r.dc[d] + d, p = r.pos + off;
-                if (off < r.span && p >= beg && p <= end) T.del[p - beg]++;
-            }
-        }
-}
-
 static std::string want_text(const fab &f, const std::string &name, uint64_t beg, uint64_t end, uint32_t min_alt, const tables &T, uint64_t &lines)
 {
     std::string out;
@@ -192,93 +57,34 @@ static int fab_check(const char *what, const fab &f, uint64_t beg, uint64_t end,
                      int fail_block = -1)
 {
     const std::string name = "ctg";
-    const size_t n = f.reads.size();
-    std::vector<cbc_read_rec> recs(n ? n : 1);
-    std::vector<uint8_t> rows(n * f.stride + 8u, 0xEEu);            /* exactly the spare bytes cbc_region_block asks for */
-    std::vector<uint32_t> side(2u * (n ? n : 1), 0u);
-    std::vector<uint16_t> arena(n * f.per_read, 0xEEEEu);
-    std::vector<cbc_dec_block_desc> blocks(f.block_n.size());
-    std::vector<uint64_t> ws(f.block_n.size(), 0u);
-    std::vector<cbc_block_result> res(f.block_n.size());
-    std::vector<int> failed(f.block_n.size(), 0);
-    size_t at = 0;
-    for (size_t b = 0; b < f.block_n.size(); b++) {
-        memset(&blocks[b], 0, sizeof blocks[b]); memset(&res[b], 0, sizeof res[b]);
-        blocks[b].rec_base = at; blocks[b].seq_base = (uint64_t)at * f.stride; blocks[b].n_reads = f.block_n[b]; blocks[b].seq_stride = f.stride;
-        uint32_t used = 0;
-        for (uint32_t k = 0; k < f.block_n[b]; k++, at++) {
-            const fread_ &r = f.reads[at];
-            uint32_t *w = (uint32_t *)&recs[at];
-            w[0] = r.pos; w[1] = r.flag | ((uint32_t)r.seq.size() << 16); w[2] = k * f.stride; w[3] = r.span;
-            memcpy(rows.data() + at * f.stride, r.seq.data(), r.seq.size());
-            side[2 * at] = (r.dc.size() + r.oi.size()) ? used : 0u;
-            side[2 * at + 1] = (uint32_t)r.dc.size() | ((uint32_t)r.oi.size() << 16);
-            for (uint32_t d : r.dc) arena[blocks[b].rec_base * f.per_read + used++] = (uint16_t)d;
-            for (uint32_t o : r.oi) arena[blocks[b].rec_base * f.per_read + used++] = (uint16_t)o;
-            if (used > f.block_n[b] * f.per_read) { printf("%-66s BAD FIXTURE\n", what); return 1; }
-        }
-        if ((int)b == fail_block) { res[b].status = CBC_ST_EDITS; failed[b] = 1; }
-    }
+    fab_arrays a;
+    if (!fab_build(f, a, fail_block)) { printf("%-66s BAD FIXTURE\n", what); return 1; }
     tables T;
-    want_tables(f, beg, end, exclude, failed, T);
+    want_tables(f, beg, end, exclude, a.failed, T);
     uint64_t lines = 0;
     const std::string want = want_text(f, name, beg, end, min_alt, T, lines);
     std::vector<uint8_t> text(want.size() + 16u, 0xEEu);
     uint64_t out[4] = { 0, 0, 0, 0 };
-    const int rc = emu_pileup(recs.data(), n, rows.data(), rows.size(), blocks.data(), ws.data(), res.data(), (uint32_t)blocks.size(), side.data(),
-                              arena.data(), f.per_read, f.ref.data(), f.ref.size(), 0u, name.c_str(), (uint32_t)name.size(), beg, end, exclude,
-                              min_alt, n_waves, text.data(), want.size(), out);
+    auto call = [&](uint8_t *t, uint64_t cap) {
+        return emu_pileup(a.recs.data(), f.reads.size(), a.rows.data(), a.rows.size(), a.blocks.data(), a.ws.data(), a.res.data(), (uint32_t)a.blocks.size(),
+                          a.side.data(), a.arena.data(), f.per_read, f.ref.data(), f.ref.size(), 0u, name.c_str(), (uint32_t)name.size(), beg, end,
+                          exclude, min_alt, n_waves, t, cap, out);
+    };
+    const int rc = call(text.data(), want.size());
     int bad = rc != (fail_block >= 0 ? CBC_E_BLOCK : 0) || out[0] != want.size() || out[1] != lines || out[2] != T.kept ||
               memcmp(text.data(), want.data(), want.size()) != 0;
     for (size_t i = want.size(); i < text.size(); i++) bad |= text[i] != 0xEEu;
     printf("%-66s %s (rc %d, %llu lines, %llu reads)\n", what, bad ? "MISMATCH" : "ok", rc, (unsigned long long)out[1], (unsigned long long)out[2]);
-    if (!bad && want.size() > 0) {                                   /* one byte short: the size, CBC_E_ARG, nothing written */
-        std::vector<uint8_t> t2(want.size() + 16u, 0xEEu);
-        const int rc2 = emu_pileup(recs.data(), n, rows.data(), rows.size(), blocks.data(), ws.data(), res.data(), (uint32_t)blocks.size(),
-                                   side.data(), arena.data(), f.per_read, f.ref.data(), f.ref.size(), 0u, name.c_str(), (uint32_t)name.size(),
-                                   beg, end, exclude, min_alt, n_waves, t2.data(), want.size() - 1u, out);
-        bad |= rc2 != CBC_E_ARG || out[0] != want.size();
-        for (size_t i = 0; i < t2.size(); i++) bad |= t2[i] != 0xEEu;
-        if (bad) printf("%-66s MISMATCH (text_cap one byte short: rc %d)\n", what, rc2);
-    }
+    if (!bad && want.size() > 0) bad |= fab_short_probe(what, 66, call, want.size(), out);
     return bad;
 }
 
 int main()
 {
     int bad = 0;
-    fab f; f.stride = 152u; f.per_read = 16u;
-    for (uint32_t i = 0; i < 6000u; i++) f.ref.push_back("ACGTNacgtnRYk"[rnd() % 13u]);    /* lower-case and IUPAC reference bytes */
-    static const uint32_t lens[] = { 1, 3, 4, 5, 63, 64, 65, 100, 150 };
-    uint32_t pos = 5;
-    typedef std::vector<uint32_t> vu;
-    for (size_t i = 0; i < sizeof lens / sizeof lens[0]; i++) {
-        const uint32_t L = lens[i];
-        fab_read(f, pos += 7u, 0u, L, vu(), vu());                                /* no edits */
-        fab_read(f, pos += 1u, 16u, L, vu{ 0u }, vu());                           /* a deletion before the first base */
-        fab_read(f, pos += 1u, 0u, L, vu{ L }, vu());                             /* one after the last, at matched coordinate T */
-        fab_read(f, pos += 1u, 16u, L, vu{ L / 2u, L / 2u }, vu());               /* two deletions at one coordinate */
-        fab_read(f, pos += 1u, 0u, L, vu(), vu{ 0u });                            /* an insertion run at read index 0 */
-        fab_read(f, pos += 1u, 1024u, L, vu(), vu{ L - 1u });                     /* and one at rl - 1 */
-        if (L >= 5u) {
-            fab_read(f, pos += 1u, 0u, L, vu{ 2u }, vu{ 2u, 3u });                /* an insertion run directly after a deletion */
-            fab_read(f, pos += 1u, 16u, L, vu{ 1u, 3u, 3u }, vu{ 0u, 1u, L - 2u, L - 1u });
-        }
-        vu all; for (uint32_t q = 0; q < L; q++) all.push_back(q);
-        if (L <= 65u) {
-            fab_read(f, pos += 1u, 0u, L, vu{ 0u, 0u }, all);                     /* nothing but insertions over two deleted bases */
-            fab_read(f, pos += 1u, 0u, L, vu(), all);                             /* span 0: not kept */
-        }
-        fab_read(f, pos += 1u, 0u, L, vu{ 70000u % 65536u, 60000u }, vu(), (int)L);   /* hostile entries that map past the span: ignored */
-        fab_read(f, pos += 1u, 0u, L, vu(), vu{ 0u }, (int)(L > 1u ? L - 1u : 1u));
-    }
-    while (f.reads.size() < 0u + 1u + 63u + 64u + 65u + 40u) fab_read(f, pos += 3u, (rnd() & 1u) * 16u, 100u, rnd() % 3u ? vu() : vu{ 40u, 40u, 41u }, rnd() % 4u ? vu() : vu{ 10u, 11u, 50u });
-    {
-        const uint32_t sizes[] = { 0, 1, 63, 64, 65 };
-        uint32_t at = 0;
-        for (int i = 0; i < 5; i++) { f.block_n.push_back(sizes[i]); at += sizes[i]; }
-        f.block_n.push_back((uint32_t)f.reads.size() - at);
-    }
+    fab f;
+    uint32_t pos;
+    fab_pileup_cases(f, pos);
     const uint64_t last = pos + 160u;
     if (last > f.ref.size()) { printf("BAD FIXTURE: the reference is too short\n"); return 1; }
     bad |= fab_check("every case, whole window, one wavefront per block", f, 1u, last, 0u, 1u, 1u);

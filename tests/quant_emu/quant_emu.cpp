@@ -1,51 +1,21 @@
 /*
  * quant_emu.cpp -- the quantile selection body (cbc_amd/csrc/cbc_quant_body.h) on the CPU through the lock-step wave emulation.
  * TEST AID ONLY: the body is run behind the emulated span decoder, the mark pass and the tile / compact passes over the
- * difference array (the order of cbc_gpu_decode_coverage_quant), or straight on change points the test fabricates.  The scans
- * between the passes are the host loop below (on the device: cbc_scan_sizes_kernel).  The wavefront's LDS table is a plain array
- * of exactly CBC_QUANT_LDS words that the emulation checks every zero / add / read against (tests/hist_emu/wave_emu_hist.h), and
+ * difference array (the order of cbc_gpu_decode_coverage_quant), or straight on change points the test fabricates.  The front
+ * of the call and the scans between the passes are those of tests/emu/post_emu.h.  The wavefront's LDS table is a plain array
+ * of exactly CBC_QUANT_LDS words that the emulation checks every zero / add / read against (tests/emu/wave_emu_post.h), and
  * every other table the body touches is an allocation of its exact size, so an index past it is an ASan finding.  With
  * -DQUANT_EMU_MAIN the file is a stand-alone program that builds fabricated cases itself, compares them with a sort on the host
  * and exits non-zero on a mismatch (make asan_check).
  */
 #include <algorithm>
 #include <utility>
-#include <vector>
-#include "../hist_emu/wave_emu_hist.h"
-#include "../../cbc_amd/csrc/cbc_encode_body.h"
-#include "../../cbc_amd/csrc/cbc_decode_body.h"
-#include "../../cbc_amd/csrc/cbc_plan.h"
+#include "../emu/post_emu.h"
 #include "../../cbc_amd/csrc/cbc_quant_body.h"
-
-static int g_emu_errors = 0;
-extern "C" void emu_oob(const char *what) { fprintf(stderr, "[emu] invariant violated: %s\n", what); g_emu_errors++; }
 
 /* the span-reporting decoder over every block of the batch */
 extern "C" __attribute__((visibility("default")))
-int emu_quant_decode(const cbc_dec_device_batch *b, uint32_t smax)
-{
-    cbc_dec_args A;
-    memset(&A, 0, sizeof A);
-    A.in = b->d_in; A.blocks = b->d_blocks; A.ref = b->d_ref; A.recs = b->d_recs; A.seq = b->d_seq; A.results = b->d_results;
-    A.in_bytes = b->in_bytes; A.ref_bytes = b->ref_bytes; A.n_recs = b->n_recs; A.seq_bytes = b->seq_bytes;
-    A.n_blocks = b->n_blocks; A.cap_pos = b->caps.cap_pos; A.cap_var = b->caps.cap_var;
-    A.var_scratch = b->d_var_scratch; A.var_scratch_words = b->var_scratch_words;
-    g_emu_errors = 0;
-    WaveEmuHist::wg_table(nullptr, 0u);
-    uint32_t words = cbc_plan_dec_lds_bytes(&b->caps) / 4;
-    for (uint32_t blk = 0; blk < b->n_blocks; blk++) {
-        std::vector<uint32_t> lds(words, 0xdeadbeefu);
-        cbc_decode_stream<WaveEmuHist, true>(A, blk, lds.data(), smax);
-    }
-    return g_emu_errors ? -100 : 0;
-}
-
-static void scan(const cbc_block_result *r, uint64_t *off, uint32_t n)
-{
-    uint64_t run = 0;
-    for (uint32_t i = 0; i < n; i++) { off[i] = run; run += r[i].status == CBC_ST_OK ? r[i].nbytes : 0u; }
-    off[n] = run;
-}
+int emu_quant_decode(const cbc_dec_device_batch *b, uint32_t smax) { WP::wg_table(nullptr, 0u); return emu_decode_blocks<WP, true>(b, smax); }
 
 /* the selection over the first ncp change points: one emulated wavefront per query, each with a fresh table of garbage */
 static void quant_pass(const uint32_t *cp_pos, const uint32_t *cp_dep, uint32_t ncp, uint32_t cp_cap, uint32_t slots, const uint32_t *pct,
@@ -62,9 +32,9 @@ static void quant_pass(const uint32_t *cp_pos, const uint32_t *cp_dep, uint32_t 
     A.n_quant = n_quant; A.cp_cap = cp_cap; A.n_q = n_q; A.slots = slots;
     for (uint32_t i = 0; i < n_q; i++) {
         std::vector<uint32_t> lds(CBC_QUANT_LDS, 0xdeadbeefu);
-        WaveEmuHist::wg_table(lds.data(), CBC_QUANT_LDS);
-        cbc_quant_select<WaveEmuHist>(A, i, lds.data());
-        WaveEmuHist::wg_table(nullptr, 0u);
+        WP::wg_table(lds.data(), CBC_QUANT_LDS);
+        cbc_quant_select<WP>(A, i, lds.data());
+        WP::wg_table(nullptr, 0u);
     }
     for (size_t i = 0; i < out.size(); i++) { if (out[i] == 0xEEEEEEEEu) emu_oob("a quantile was not written"); quant[i] = out[i]; }
 }
@@ -98,40 +68,18 @@ int emu_quant(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq, uin
     for (uint64_t i = 0; i < (uint64_t)n_q * n_quant; i++) quant[i] = 0;
     for (uint32_t t = 0; t < n_quant; t++) if (pct[t] > 100u || (t && pct[t] <= pct[t - 1])) return CBC_E_ARG;
     if (n_recs > 0x3fffffffull || n_iv == 0) return CBC_E_ARG;
-    std::vector<uint32_t> ivv(iv, iv + 2u * (size_t)n_iv), biv(block_iv, block_iv + 2u * (size_t)n_blocks), ioff(n_iv + 1u);
-    uint64_t run = 0;
-    for (uint32_t i = 0; i < n_iv; i++) {
-        if (iv[2 * i] < 1 || iv[2 * i] > iv[2 * i + 1] || iv[2 * i + 1] > CBC_SAM_MAX_POS || (i && iv[2 * i] <= iv[2 * i - 1] + 1u)) return CBC_E_ARG;
-        ioff[i] = (uint32_t)run; run += (uint64_t)(iv[2 * i + 1] - iv[2 * i]) + 2u;
-    }
-    ioff[n_iv] = (uint32_t)run;
-    const uint64_t d_words = run;
+    emu_depth_front F;
+    if (F.intervals(iv, n_iv, block_iv, n_blocks)) return CBC_E_ARG;
+    const uint64_t d_words = F.d_words;
     for (uint32_t i = 0; i < n_q; i++) if (q[2 * i] > d_words || q[2 * i + 1] > d_words - q[2 * i]) return CBC_E_ARG;
-    const uint32_t n_tiles = (uint32_t)((d_words + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
-    const uint32_t cp_cap = (uint32_t)(2u * n_recs + 2u * (uint64_t)n_iv), n_ttiles = (cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
-    std::vector<uint32_t> diff((size_t)n_tiles * CBC_DEPTH_TILE, 0u), cp_pos(cp_cap + 1u, 0xEEEEEEEEu), cp_dep(cp_cap + 1u, 0xEEEEEEEEu);
-    std::vector<cbc_block_result> tsum(n_tiles), tcnt(n_tiles);
-    std::vector<uint64_t> soff(n_tiles + 1u), coff(n_tiles + 1u);
-    uint32_t ctr[4] = { 0, 0, 0, 0 };
-    cbc_tdepth_args A;
-    memset(&A, 0, sizeof A);
-    A.D.R.recs = recs; A.D.R.seq = seq; A.D.R.blocks = blocks; A.D.R.window_start = window_start; A.D.R.dec_results = dec_results;
-    A.D.R.n_recs = n_recs; A.D.R.seq_bytes = seq_bytes; A.D.R.beg = 1u; A.D.R.end = UINT64_MAX; A.D.R.n_blocks = n_blocks;
-    A.D.diff = diff.data(); A.D.diff_words = diff.size(); A.D.tile_sum = tsum.data(); A.D.tile_cnt = tcnt.data();
-    A.D.sum_off = soff.data(); A.D.cnt_off = coff.data(); A.D.cp_pos = cp_pos.data(); A.D.cp_dep = cp_dep.data(); A.D.cp_cap = cp_cap;
-    A.D.ctr = ctr; A.D.exclude = exclude; A.D.n_tiles = n_tiles; A.D.n_ttiles = n_ttiles;
-    A.iv = ivv.data(); A.iv_off = ioff.data(); A.block_iv = biv.data(); A.n_iv = n_iv;
-    WaveEmuHist::wg_table(nullptr, 0u);
-    for (uint32_t b = 0; b < n_blocks; b++) cbc_targets_mark<WaveEmuHist>(A, b);
-    for (uint32_t t = 0; t < n_tiles; t++) cbc_depth_tile<WaveEmuHist>(A.D, t);
-    scan(tsum.data(), soff.data(), n_tiles);
-    scan(tcnt.data(), coff.data(), n_tiles);
-    for (uint32_t t = 0; t < n_tiles; t++) cbc_depth_compact<WaveEmuHist>(A.D, t);
-    if (cp_pos[cp_cap] != 0xEEEEEEEEu || cp_dep[cp_cap] != 0xEEEEEEEEu) emu_oob("change point written past the table");
-    if (coff[n_tiles] > cp_cap) { emu_oob("more change points than 2K + 2n"); return -100; }
-    const uint32_t ncp = (uint32_t)coff[n_tiles];
-    quant_pass(cp_pos.data(), cp_dep.data(), ncp, cp_cap, (uint32_t)d_words, pct, n_quant, q, n_q, quant);
-    out[0] = ctr[0]; out[1] = ncp; out[2] = d_words;
+    const uint32_t cp_cap = (uint32_t)(2u * n_recs + 2u * (uint64_t)n_iv);
+    F.tables(recs, n_recs, seq, seq_bytes, blocks, window_start, dec_results, n_blocks, exclude, cp_cap);
+    WP::wg_table(nullptr, 0u);
+    F.mark();
+    if (F.points()) return -100;
+    const uint32_t ncp = F.ncp;
+    quant_pass(F.cp_pos.data(), F.cp_dep.data(), ncp, cp_cap, (uint32_t)d_words, pct, n_quant, q, n_q, quant);
+    out[0] = F.ctr[0]; out[1] = ncp; out[2] = d_words;
     if (g_emu_errors) return -100;
     for (uint32_t b = 0; b < n_blocks; b++) if (dec_results[b].status != CBC_ST_OK) return CBC_E_BLOCK;
     return 0;

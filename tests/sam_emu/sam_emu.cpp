@@ -2,37 +2,15 @@
  * sam_emu.cpp -- the SAM text bodies (cbc_amd/csrc/cbc_sam_body.h) on the CPU through the lock-step wave emulation.
  * TEST AID ONLY: the count and the write pass are checked against the Python model (tests/sammodel.py) under ASan-able host
  * code before anything runs on a GPU.  The records come from the emulated decoders (plain, or span-reporting for a region) or
- * from arrays the test builds.  The scan between the passes is the host loop below (on the device: cbc_scan_sizes_kernel).
+ * from arrays the test builds.  The scan between the passes is the host loop of tests/emu/post_emu.h (on the device:
+ * cbc_scan_sizes_kernel).
  */
-#include <vector>
-#include "wave_emu_sam.h"
-#include "../../cbc_amd/csrc/cbc_encode_body.h"
-#include "../../cbc_amd/csrc/cbc_decode_body.h"
-#include "../../cbc_amd/csrc/cbc_plan.h"
+#include "../emu/post_emu.h"
 #include "../../cbc_amd/csrc/cbc_sam_body.h"
-
-static int g_emu_errors = 0;
-extern "C" void emu_oob(const char *what) { fprintf(stderr, "[emu] invariant violated: %s\n", what); g_emu_errors++; }
 
 /* the decoder over every block of the batch: smax = 0 the plain one, otherwise the span-reporting one */
 extern "C" __attribute__((visibility("default")))
-int emu_sam_decode(const cbc_dec_device_batch *b, uint32_t smax)
-{
-    cbc_dec_args A;
-    memset(&A, 0, sizeof A);
-    A.in = b->d_in; A.blocks = b->d_blocks; A.ref = b->d_ref; A.recs = b->d_recs; A.seq = b->d_seq; A.results = b->d_results;
-    A.in_bytes = b->in_bytes; A.ref_bytes = b->ref_bytes; A.n_recs = b->n_recs; A.seq_bytes = b->seq_bytes;
-    A.n_blocks = b->n_blocks; A.cap_pos = b->caps.cap_pos; A.cap_var = b->caps.cap_var;
-    A.var_scratch = b->d_var_scratch; A.var_scratch_words = b->var_scratch_words;
-    g_emu_errors = 0;
-    uint32_t words = cbc_plan_dec_lds_bytes(&b->caps) / 4;
-    for (uint32_t blk = 0; blk < b->n_blocks; blk++) {
-        std::vector<uint32_t> lds(words, 0xdeadbeefu);
-        if (smax) cbc_decode_stream<WaveEmuSam, true>(A, blk, lds.data(), smax);
-        else cbc_decode_stream<WaveEmuSam>(A, blk, lds.data());
-    }
-    return g_emu_errors ? -100 : 0;
-}
+int emu_sam_decode(const cbc_dec_device_batch *b, uint32_t smax) { return smax ? emu_decode_blocks<WP, true>(b, smax) : emu_decode_blocks<WP, false>(b, 0u); }
 
 /* count pass, exclusive scan, write pass (n_waves wavefronts per block, run one after the other).  region != 0: keep by
  * [beg, end].  Returns -1 (CBC_E_ARG) with offsets[n_blocks] set and nothing written when the text does not fit text_cap,
@@ -50,12 +28,10 @@ int emu_sam(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq, uint6
     A.R.beg = region ? beg : 1u; A.R.end = region ? end : UINT64_MAX; A.R.n_blocks = n_blocks;
     A.block_name = block_name; A.names = names; A.names_bytes = names_bytes; A.region = region ? 1u : 0u;
     g_emu_errors = 0;
-    for (uint32_t b = 0; b < n_blocks; b++) cbc_sam_count<WaveEmuSam>(A, b);
-    uint64_t run = 0;
-    for (uint32_t b = 0; b < n_blocks; b++) { offsets[b] = run; run += counts[b].status == CBC_ST_OK ? counts[b].nbytes : 0u; }
-    offsets[n_blocks] = run;
-    if (run > text_cap) return CBC_E_ARG;
+    for (uint32_t b = 0; b < n_blocks; b++) cbc_sam_count<WP>(A, b);
+    scan(counts, offsets, n_blocks);
+    if (offsets[n_blocks] > text_cap) return CBC_E_ARG;
     for (uint32_t b = 0; b < n_blocks; b++)
-        for (uint32_t w = 0; w < n_waves; w++) cbc_sam_write<WaveEmuSam>(A, b, w, n_waves);
+        for (uint32_t w = 0; w < n_waves; w++) cbc_sam_write<WP>(A, b, w, n_waves);
     return g_emu_errors ? -100 : 0;
 }

@@ -9,49 +9,13 @@
  * them is a finding.  With -DSKIPDEL_EMU_MAIN the file is a stand-alone program that builds the fabricated cases itself,
  * compares them with a base-by-base host loop and exits non-zero on a mismatch (make asan_check).
  */
-#include <vector>
-#include <string>
-#include "../pileup_emu/wave_emu_pileup.h"
-#include "../../cbc_amd/csrc/cbc_encode_body.h"
-#include "../../cbc_amd/csrc/cbc_decode_body.h"
-#include "../../cbc_amd/csrc/cbc_plan.h"
+#include "../emu/post_emu.h"
 #include "../../cbc_amd/csrc/cbc_skipdel_body.h"
-
-typedef WaveEmuPileup WP;
-
-static int g_emu_errors = 0;
-extern "C" void emu_oob(const char *what) { fprintf(stderr, "[emu] invariant violated: %s\n", what); g_emu_errors++; }
 
 /* the edit-reporting decoder over every block of the batch: side = 2 * n_recs words, arena = n_recs * per_read entries exactly */
 extern "C" __attribute__((visibility("default")))
 int emu_skipdel_decode(const cbc_dec_device_batch *b, uint32_t smax, uint32_t per_read, uint32_t *side, uint16_t *arena)
-{
-    cbc_dec_args A;
-    memset(&A, 0, sizeof A);
-    A.in = b->d_in; A.blocks = b->d_blocks; A.ref = b->d_ref; A.recs = b->d_recs; A.seq = b->d_seq; A.results = b->d_results;
-    A.in_bytes = b->in_bytes; A.ref_bytes = b->ref_bytes; A.n_recs = b->n_recs; A.seq_bytes = b->seq_bytes;
-    A.n_blocks = b->n_blocks; A.cap_pos = b->caps.cap_pos; A.cap_var = b->caps.cap_var;
-    A.var_scratch = b->d_var_scratch; A.var_scratch_words = b->var_scratch_words;
-    cbc_dec_edits E;
-    memset(&E, 0, sizeof E);
-    E.side = side; E.arena = arena; E.arena_entries = b->n_recs * per_read; E.per_read = per_read;
-    g_emu_errors = 0;
-    WP::edit_arena(arena, E.arena_entries);
-    uint32_t words = cbc_plan_dec_lds_bytes(&b->caps) / 4;
-    for (uint32_t blk = 0; blk < b->n_blocks; blk++) {
-        std::vector<uint32_t> lds(words, 0xdeadbeefu);
-        cbc_decode_stream<WP, true, true>(A, blk, lds.data(), smax, &E);
-    }
-    WP::edit_arena(nullptr, 0);
-    return g_emu_errors ? -100 : 0;
-}
-
-static void scan(const cbc_block_result *r, uint64_t *off, uint32_t n)
-{
-    uint64_t run = 0;
-    for (uint32_t i = 0; i < n; i++) { off[i] = run; run += r[i].status == CBC_ST_OK ? r[i].nbytes : 0u; }
-    off[n] = run;
-}
+{ return emu_decode_blocks<WP, true, true>(b, smax, per_read, side, arena); }
 
 /* the library's bound on the change points (post_sizes_of in cbc_gpu.hip): per_read == 0 is the span depth's */
 extern "C" __attribute__((visibility("default")))
@@ -80,58 +44,44 @@ int emu_skipdel(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq, u
     const bool tg = n_iv != 0u;
     if (n_recs > 0x3fffffffull || n_waves < 1u || n_waves > 16u || per_read > 510u) return CBC_E_ARG;
     if (!tg && (beg < 1 || beg > end || end > CBC_SAM_MAX_POS)) return CBC_E_ARG;
-    std::vector<uint32_t> ivv, biv, ioff(n_iv + 1u, 0u);
-    uint64_t d_words = end - beg + 2u;
-    if (tg) {
-        ivv.assign(iv, iv + 2u * (size_t)n_iv); biv.assign(block_iv, block_iv + 2u * (size_t)n_blocks);
-        uint64_t run = 0;
-        for (uint32_t i = 0; i < n_iv; i++) {
-            if (iv[2 * i] < 1 || iv[2 * i] > iv[2 * i + 1] || iv[2 * i + 1] > CBC_SAM_MAX_POS || (i && iv[2 * i] <= iv[2 * i - 1] + 1u)) return CBC_E_ARG;
-            ioff[i] = (uint32_t)run; run += (uint64_t)(iv[2 * i + 1] - iv[2 * i]) + 2u;
-        }
-        ioff[n_iv] = (uint32_t)run;
-        d_words = run;
-    }
-    const uint32_t n_tiles = (uint32_t)((d_words + CBC_DEPTH_TILE - 1u) / CBC_DEPTH_TILE);
+    emu_depth_front F;
+    F.d_words = end - beg + 2u;
+    if (tg && F.intervals(iv, n_iv, block_iv, n_blocks)) return CBC_E_ARG;
+    const uint64_t d_words = F.d_words;
     const uint32_t cp_cap = (uint32_t)emu_skipdel_cp_cap(d_words, n_recs, n_iv, per_read);
     const uint32_t n_ttiles = (cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
-    std::vector<uint32_t> diff((size_t)n_tiles * CBC_DEPTH_TILE, 0u), cp_pos(cp_cap + 1u, 0xEEEEEEEEu), cp_dep(cp_cap + 1u, 0xEEEEEEEEu), ctr(4, 0u);
-    std::vector<cbc_block_result> tsum(n_tiles), tcnt(n_tiles), counts(n_ttiles + 1u);
-    std::vector<uint64_t> soff(n_tiles + 1u), coff(n_tiles + 1u), toff(n_ttiles + 1u);
+    std::vector<cbc_block_result> counts(n_ttiles + 1u);
+    std::vector<uint64_t> toff(n_ttiles + 1u);
     std::vector<uint8_t> nm(name, name + name_len);
+    F.tables(recs, n_recs, seq, seq_bytes, blocks, window_start, dec_results, n_blocks, exclude, cp_cap);
+    const uint32_t n_tiles = F.n_tiles;
+    uint32_t *const ctr = F.ctr;
     cbc_tskipdel_args X;
     memset(&X, 0, sizeof X);
+    X.T = F.A;
     cbc_tdepth_args &A = X.T;
-    A.D.R.recs = recs; A.D.R.seq = seq; A.D.R.blocks = blocks; A.D.R.window_start = window_start; A.D.R.dec_results = dec_results;
-    A.D.R.counts = counts.data(); A.D.R.offsets = toff.data(); A.D.R.text = text; A.D.R.text_cap = text_cap; A.D.R.n_recs = n_recs;
-    A.D.R.seq_bytes = seq_bytes; A.D.R.beg = tg ? 1u : beg; A.D.R.end = tg ? UINT64_MAX : end; A.D.R.n_blocks = n_blocks;
-    A.D.diff = diff.data(); A.D.diff_words = diff.size(); A.D.tile_sum = tsum.data(); A.D.tile_cnt = tcnt.data();
-    A.D.sum_off = soff.data(); A.D.cnt_off = coff.data(); A.D.cp_pos = cp_pos.data(); A.D.cp_dep = cp_dep.data(); A.D.cp_cap = cp_cap;
-    A.D.ctr = ctr.data(); A.D.name = nm.data(); A.D.name_len = name_len; A.D.exclude = exclude; A.D.n_tiles = n_tiles; A.D.n_ttiles = n_ttiles;
-    A.iv = ivv.data(); A.iv_off = ioff.data(); A.block_iv = biv.data(); A.n_iv = n_iv;
+    A.D.R.counts = counts.data(); A.D.R.offsets = toff.data(); A.D.R.text = text; A.D.R.text_cap = text_cap;
+    if (!tg) { A.D.R.beg = beg; A.D.R.end = end; }
+    A.D.name = nm.data(); A.D.name_len = name_len;
     X.E.side = side; X.E.arena = arena; X.E.arena_entries = n_recs * per_read; X.E.per_read = per_read;
     cbc_skipdel_args Wd;
     Wd.D = A.D; Wd.E = X.E;
     WP::clear_ranges();
-    WP::add_range(diff.data(), d_words);                              /* the array's own words only, not the tile's padding */
-    WP::add_range(ctr.data(), 2);
+    WP::add_range(F.diff.data(), d_words);                              /* the array's own words only, not the tile's padding */
+    WP::add_range(ctr, 2);
     WP::edit_arena(arena, X.E.arena_entries);
     for (uint32_t b = 0; b < n_blocks; b++) { if (tg) cbc_targets_mark<WP>(A, b); else cbc_depth_mark<WP>(A.D, b); }
     const uint32_t kept = ctr[0];
     for (uint32_t b = 0; b < n_blocks && per_read; b++)
         for (uint32_t w = 0; w < n_waves; w++) { if (tg) cbc_skipdel_targets_unmark<WP>(X, b, w, n_waves); else cbc_skipdel_unmark<WP>(Wd, b, w, n_waves); }
     if (ctr[0] != kept) emu_oob("the unmark pass changed the count of the kept reads");
-    for (uint32_t t = 0; t < n_tiles; t++) cbc_depth_tile<WP>(A.D, t);
-    scan(tsum.data(), soff.data(), n_tiles);
-    scan(tcnt.data(), coff.data(), n_tiles);
-    for (uint32_t t = 0; t < n_tiles; t++) cbc_depth_compact<WP>(A.D, t);
-    if (cp_pos[cp_cap] != 0xEEEEEEEEu || cp_dep[cp_cap] != 0xEEEEEEEEu) emu_oob("change point written past the table");
-    if (coff[n_tiles] > cp_cap) emu_oob("more change points than the bound");
-    if ((uint32_t)soff[n_tiles] != 0u) emu_oob("the depth behind the last word is not 0");
+    uint32_t ncp = 0;
+    emu_depth_points<WP>(A.D, F.soff.data(), F.coff.data(), "change point", &ncp);   /* a finding is counted; the text passes still run */
+    if ((uint32_t)F.soff[n_tiles] != 0u) emu_oob("the depth behind the last word is not 0");
     for (uint32_t t = 0; t < n_ttiles; t++) { if (tg) cbc_targets_depth_count<WP>(A, t); else cbc_depth_count<WP>(A.D, t); }
     scan(counts.data(), toff.data(), n_ttiles);
-    out[0] = toff[n_ttiles]; out[1] = ctr[1]; out[2] = ctr[0]; out[3] = coff[n_tiles]; out[4] = d_words; out[5] = cp_cap;
-    for (uint64_t i = 0; cp && i < out[3] && i < cp_cap; i++) { cp[2 * i] = cp_pos[i]; cp[2 * i + 1] = cp_dep[i]; }
+    out[0] = toff[n_ttiles]; out[1] = ctr[1]; out[2] = ctr[0]; out[3] = F.coff[n_tiles]; out[4] = d_words; out[5] = cp_cap;
+    for (uint64_t i = 0; cp && i < out[3] && i < cp_cap; i++) { cp[2 * i] = F.cp_pos[i]; cp[2 * i + 1] = F.cp_dep[i]; }
     int rc = 0;
     if (out[0] > text_cap) rc = CBC_E_ARG;
     else for (uint32_t t = 0; t < n_ttiles; t++) { if (tg) cbc_targets_depth_write<WP>(A, t); else cbc_depth_write<WP>(A.D, t); }
@@ -144,26 +94,8 @@ int emu_skipdel(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq, u
 }
 
 #ifdef SKIPDEL_EMU_MAIN
+#include "../emu/fab_reads.h"
 /* ---- the stand-alone check: fabricated records and arena entries against a base-by-base host loop ------------------------------ */
-struct fread_ { uint32_t pos, flag, len, span; std::vector<uint32_t> dc, oi; };
-struct fab {
-    uint32_t stride, per_read;
-    std::vector<fread_> reads;
-    std::vector<uint32_t> block_n;                                    /* reads per block */
-};
-
-static uint32_t g_rng = 2463534242u;
-static uint32_t rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 17; g_rng ^= g_rng << 5; return g_rng; }
-
-/* a read of `len` bases at `pos` with the given edits; span < 0: the honest one */
-static void fab_read(fab &f, uint32_t pos, uint32_t flag, uint32_t len, std::vector<uint32_t> dc, std::vector<uint32_t> oi, int span = -1)
-{
-    fread_ r;
-    r.pos = pos; r.flag = flag; r.len = len; r.dc = dc; r.oi = oi;
-    r.span = span >= 0 ? (uint32_t)span : len + (uint32_t)dc.size() - (uint32_t)oi.size();
-    f.reads.push_back(r);
-}
-
 /* the definition of include/cbc_gpu.h, one base at a time: depth[p] of positions 1 .. top, and the reads kept by `keep` */
 static void want_depth(const fab &f, uint32_t exclude, const std::vector<int> &failed, uint64_t top, std::vector<int64_t> &depth)
 {
@@ -204,35 +136,13 @@ static int fab_check(const char *what, const fab &f, uint64_t beg, uint64_t end,
                      uint32_t n_waves, int fail_block = -1)
 {
     const std::string name = "ctg";
-    const size_t n = f.reads.size();
     const uint32_t n_iv = (uint32_t)(iv.size() / 2u);
-    std::vector<cbc_read_rec> recs(n ? n : 1);
-    std::vector<uint8_t> rows(n * f.stride + 8u, 0xEEu);            /* exactly the spare bytes cbc_region_block asks for */
-    std::vector<uint32_t> side(2u * (n ? n : 1), 0u), biv;
-    std::vector<uint16_t> arena(n * f.per_read, 0xEEEEu);
-    std::vector<cbc_dec_block_desc> blocks(f.block_n.size());
-    std::vector<uint64_t> ws(f.block_n.size(), 0u);
-    std::vector<cbc_block_result> res(f.block_n.size());
-    std::vector<int> failed(f.block_n.size(), 0);
-    size_t at = 0;
+    fab_arrays a;
+    if (!fab_build(f, a, fail_block)) { printf("%-70s BAD FIXTURE\n", what); return 1; }
+    const std::vector<int> &failed = a.failed;
+    vu biv;
+    for (size_t b = 0; b < f.block_n.size(); b++) { biv.push_back(0u); biv.push_back(n_iv); }   /* every block may reach every interval */
     uint64_t top = end;
-    for (size_t b = 0; b < f.block_n.size(); b++) {
-        memset(&blocks[b], 0, sizeof blocks[b]); memset(&res[b], 0, sizeof res[b]);
-        blocks[b].rec_base = at; blocks[b].seq_base = (uint64_t)at * f.stride; blocks[b].n_reads = f.block_n[b]; blocks[b].seq_stride = f.stride;
-        uint32_t used = 0;
-        for (uint32_t k = 0; k < f.block_n[b]; k++, at++) {
-            const fread_ &r = f.reads[at];
-            uint32_t *w = (uint32_t *)&recs[at];
-            w[0] = r.pos; w[1] = r.flag | (r.len << 16); w[2] = k * f.stride; w[3] = r.span;
-            side[2 * at] = (r.dc.size() + r.oi.size()) ? used : 0u;
-            side[2 * at + 1] = (uint32_t)r.dc.size() | ((uint32_t)r.oi.size() << 16);
-            for (uint32_t d : r.dc) arena[blocks[b].rec_base * f.per_read + used++] = (uint16_t)d;
-            for (uint32_t o : r.oi) arena[blocks[b].rec_base * f.per_read + used++] = (uint16_t)o;
-            if (used > f.block_n[b] * f.per_read) { printf("%-70s BAD FIXTURE\n", what); return 1; }
-        }
-        if ((int)b == fail_block) { res[b].status = CBC_ST_EDITS; failed[b] = 1; }
-        biv.push_back(0u); biv.push_back(n_iv);                       /* every block may reach every interval */
-    }
     for (uint32_t i = 0; i < n_iv; i++) if (iv[2 * i + 1] > top) top = iv[2 * i + 1];
     std::vector<int64_t> depth;
     want_depth(f, exclude, failed, top, depth);
@@ -241,7 +151,7 @@ static int fab_check(const char *what, const fab &f, uint64_t beg, uint64_t end,
     uint64_t lines = 0, points = 0, kept = 0;
     if (n_iv) for (uint32_t i = 0; i < n_iv; i++) want_runs(name, depth, iv[2 * i], iv[2 * i + 1], want, lines, points);
     else want_runs(name, depth, beg, end, want, lines, points);
-    at = 0;
+    size_t at = 0;
     for (size_t b = 0; b < f.block_n.size(); b++)
         for (uint32_t k = 0; k < f.block_n[b]; k++, at++) {
             const fread_ &r = f.reads[at];
@@ -253,32 +163,26 @@ static int fab_check(const char *what, const fab &f, uint64_t beg, uint64_t end,
         }
     std::vector<uint8_t> text(want.size() + 16u, 0xEEu);
     uint64_t out[6] = { 0, 0, 0, 0, 0, 0 };
-    const int rc = emu_skipdel(recs.data(), n, rows.data(), rows.size(), blocks.data(), ws.data(), res.data(), (uint32_t)blocks.size(), side.data(),
-                               arena.data(), f.per_read, name.c_str(), (uint32_t)name.size(), beg, end, iv.data(), n_iv, biv.data(), exclude,
-                               n_waves, text.data(), want.size(), NULL, out);
+    auto call = [&](uint8_t *t, uint64_t cap) {
+        return emu_skipdel(a.recs.data(), f.reads.size(), a.rows.data(), a.rows.size(), a.blocks.data(), a.ws.data(), a.res.data(), (uint32_t)a.blocks.size(),
+                           a.side.data(), a.arena.data(), f.per_read, name.c_str(), (uint32_t)name.size(), beg, end, iv.data(), n_iv, biv.data(), exclude,
+                           n_waves, t, cap, NULL, out);
+    };
+    const int rc = call(text.data(), want.size());
     int bad = rc != (fail_block >= 0 ? CBC_E_BLOCK : 0) || out[0] != want.size() || out[1] != lines || out[2] != kept || out[3] != points ||
               memcmp(text.data(), want.data(), want.size()) != 0;
     for (size_t i = want.size(); i < text.size(); i++) bad |= text[i] != 0xEEu;
     printf("%-70s %s (rc %d, %llu lines, %llu reads, %llu of %llu change points)\n", what, bad ? "MISMATCH" : "ok", rc, (unsigned long long)out[1],
            (unsigned long long)out[2], (unsigned long long)out[3], (unsigned long long)out[5]);
-    if (!bad && want.size() > 0) {                                   /* one byte short: the size, CBC_E_ARG, nothing written */
-        std::vector<uint8_t> t2(want.size() + 16u, 0xEEu);
-        const int rc2 = emu_skipdel(recs.data(), n, rows.data(), rows.size(), blocks.data(), ws.data(), res.data(), (uint32_t)blocks.size(),
-                                    side.data(), arena.data(), f.per_read, name.c_str(), (uint32_t)name.size(), beg, end, iv.data(), n_iv,
-                                    biv.data(), exclude, n_waves, t2.data(), want.size() - 1u, NULL, out);
-        bad |= rc2 != CBC_E_ARG || out[0] != want.size();
-        for (size_t i = 0; i < t2.size(); i++) bad |= t2[i] != 0xEEu;
-        if (bad) printf("%-70s MISMATCH (text_cap one byte short: rc %d)\n", what, rc2);
-    }
+    if (!bad && want.size() > 0) bad |= fab_short_probe(what, 70, call, want.size(), out);
     return bad;
 }
 
 int main()
 {
     int bad = 0;
-    typedef std::vector<uint32_t> vu;
     const vu none;
-    fab f; f.stride = 152u; f.per_read = 80u;
+    fab f; f.stride = 152u; f.per_read = 80u; f.bases = false;
     static const uint32_t lens[] = { 1, 3, 4, 5, 63, 64, 65, 100, 150 };
     uint32_t pos = 5;
     for (size_t i = 0; i < sizeof lens / sizeof lens[0]; i++) {
@@ -335,14 +239,14 @@ int main()
     bad |= fab_check("intervals, a failed block", f, 1u, 1u, vu{ 20u, 300u, 500u, 4200u }, 0u, 4u, 2);
     {   /* 64 reads apart, three separate deletion runs each: 8 change points per read, at exactly two arena entries per read too few
          * to waste: the bound is met with per_read = 3 */
-        fab g; g.stride = 104u; g.per_read = 3u;
+        fab g; g.stride = 104u; g.per_read = 3u; g.bases = false;
         for (uint32_t i = 0; i < 64u; i++) fab_read(g, 10u + 200u * i, 0u, 100u, vu{ 20u, 40u, 60u }, vu());
         g.block_n.push_back(64u);
         bad |= fab_check("64 reads apart with three deletion runs each", g, 1u, 13000u, none, 0u, 4u);
         bad |= fab_check("the same over two intervals", g, 1u, 1u, vu{ 1u, 6000u, 6002u, 13000u }, 0u, 4u);
     }
     {   /* 300 reads deleting the same two positions: the words cancel to two change points of weight 300 */
-        fab g; g.stride = 8u; g.per_read = 2u;
+        fab g; g.stride = 8u; g.per_read = 2u; g.bases = false;
         for (uint32_t i = 0; i < 300u; i++) fab_read(g, 3u, 0u, 6u, vu{ 2u, 2u }, vu());
         g.block_n.push_back(300u);
         bad |= fab_check("300 reads deleting the same positions: an arena of exactly the needed size", g, 1u, 40u, none, 0u, 4u);

@@ -8,35 +8,12 @@
  * finding.  With -DSTATS_EMU_MAIN the file is a stand-alone program that builds the fabricated cases itself, compares them with
  * a byte-by-byte host loop and exits non-zero on a mismatch (make asan_check).
  */
-#include <vector>
-#include "wave_emu_stats.h"
-#include "../../cbc_amd/csrc/cbc_encode_body.h"
-#include "../../cbc_amd/csrc/cbc_decode_body.h"
-#include "../../cbc_amd/csrc/cbc_plan.h"
-#include "../../cbc_amd/csrc/cbc_targets_body.h"
+#include "../emu/post_emu.h"
 #include "../../cbc_amd/csrc/cbc_stats_body.h"
-
-static int g_emu_errors = 0;
-extern "C" void emu_oob(const char *what) { fprintf(stderr, "[emu] invariant violated: %s\n", what); g_emu_errors++; }
 
 /* the span-reporting decoder over every block of the batch */
 extern "C" __attribute__((visibility("default")))
-int emu_stats_decode(const cbc_dec_device_batch *b, uint32_t smax)
-{
-    cbc_dec_args A;
-    memset(&A, 0, sizeof A);
-    A.in = b->d_in; A.blocks = b->d_blocks; A.ref = b->d_ref; A.recs = b->d_recs; A.seq = b->d_seq; A.results = b->d_results;
-    A.in_bytes = b->in_bytes; A.ref_bytes = b->ref_bytes; A.n_recs = b->n_recs; A.seq_bytes = b->seq_bytes;
-    A.n_blocks = b->n_blocks; A.cap_pos = b->caps.cap_pos; A.cap_var = b->caps.cap_var;
-    A.var_scratch = b->d_var_scratch; A.var_scratch_words = b->var_scratch_words;
-    g_emu_errors = 0;
-    uint32_t words = cbc_plan_dec_lds_bytes(&b->caps) / 4;
-    for (uint32_t blk = 0; blk < b->n_blocks; blk++) {
-        std::vector<uint32_t> lds(words, 0xdeadbeefu);
-        cbc_decode_stream<WaveEmuStats, true>(A, blk, lds.data(), smax);
-    }
-    return g_emu_errors ? -100 : 0;
-}
+int emu_stats_decode(const cbc_dec_device_batch *b, uint32_t smax) { return emu_decode_blocks<WP, true>(b, smax); }
 
 extern "C" __attribute__((visibility("default")))
 uint32_t emu_stats_lds_flags(void) { return CBC_STATS_FLAGS_LDS; }
@@ -61,19 +38,19 @@ int emu_stats(const cbc_read_rec *recs, uint64_t n_recs, const uint8_t *seq, uin
     A.iv = iv; A.block_iv = block_iv; A.n_iv = n_iv; A.tab = tab.data(); A.exclude = exclude; A.gmax = (most + 63u) / 64u;
     const uint64_t units = (uint64_t)n_blocks * A.gmax, wgs = (units + n_waves - 1u) / n_waves;
     A.grid = grid ? grid : (wgs < CBC_STATS_GRID ? (uint32_t)wgs : CBC_STATS_GRID);
-    WaveEmuStats::global_table(tab.data(), CBC_STATS_WORDS);
+    WP::global_table(tab.data(), CBC_STATS_WORDS);
     for (uint32_t wg = 0; wg < A.grid; wg++) {
         std::vector<uint32_t> lds(CBC_STATS_LDS, 0xdeadbeefu);      /* one table per workgroup, exactly CBC_STATS_LDS words */
-        WaveEmuStats::wg_table(lds.data(), CBC_STATS_LDS);
-        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_zero<WaveEmuStats>(lds.data(), w, n_waves);
+        WP::wg_table(lds.data(), CBC_STATS_LDS);
+        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_zero<WP>(lds.data(), w, n_waves);
         for (uint32_t w = 0; w < n_waves; w++) {
-            if (iv) cbc_stats_accum<WaveEmuStats, true>(A, wg, w, n_waves, lds.data());
-            else cbc_stats_accum<WaveEmuStats, false>(A, wg, w, n_waves, lds.data());
+            if (iv) cbc_stats_accum<WP, true>(A, wg, w, n_waves, lds.data());
+            else cbc_stats_accum<WP, false>(A, wg, w, n_waves, lds.data());
         }
-        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_flush<WaveEmuStats>(A, lds.data(), w, n_waves);
-        WaveEmuStats::wg_table(nullptr, 0u);
+        for (uint32_t w = 0; w < n_waves; w++) cbc_stats_flush<WP>(A, lds.data(), w, n_waves);
+        WP::wg_table(nullptr, 0u);
     }
-    WaveEmuStats::global_table(nullptr, 0u);
+    WP::global_table(nullptr, 0u);
     if (tab[CBC_STATS_T_CTR + 1u]) emu_oob("the spare counter was written");
     if (g_emu_errors) return -100;
     for (uint32_t b = 0; b < n_blocks; b++) if (dec_results[b].status != CBC_ST_OK) return CBC_E_BLOCK;   /* all zero */
