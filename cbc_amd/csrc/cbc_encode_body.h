@@ -83,6 +83,30 @@
 extern "C" void cbc_emu_trace(uint32_t read, uint32_t lo, uint32_t cnt, uint32_t n);
 #endif
 
+/* CBC_PATH_COUNTS: host (emulation) build only -- how often the coder took each path of its per-record steps, read
+ * through emu_path_counts() of tests/emu/emu_paths.cpp.  Two rows: records below 512 of their block, and the rest.  The
+ * device code carries no counter. */
+enum {
+    CBC_PC_CODE1, CBC_PC_CODE1_REM, CBC_PC_CODE1_REM_EXACT,    /* two-bound steps through code1_lazy(); those that took the
+                                                                * remainder branch; those with a low word at the bound */
+    CBC_PC_QUIET, CBC_PC_QUIET_REM, CBC_PC_QUIET_REM_EXACT,    /* the same for step_fixed_quiet() */
+    CBC_PC_KNOWN0, CBC_PC_KNOWN0_REM,                          /* step_known0() and its single-word test */
+    CBC_PC_X3, CBC_PC_X3_EXIT, CBC_PC_X3_FB_SHIFT, CBC_PC_X3_FB_REM,   /* step_known0_x3(): calls, fused exits, fallbacks */
+    CBC_PC_SR, CBC_PC_SR_EXIT, CBC_PC_SR_FB_SHIFT, CBC_PC_SR_FB_REM,   /* step_sameref_rl0(): the same */
+    CBC_PC_N
+};
+#if defined(CBC_PATH_COUNTS) && !defined(__HIP_DEVICE_COMPILE__)
+extern "C" void cbc_path_count(uint32_t what, uint32_t read);
+extern "C" void cbc_path_mute(int on);                         /* the cross-checks re-run steps on a copy of the state */
+#define CBC_COUNT(what, read) cbc_path_count((what), (read))
+#define CBC_COUNT_IF(cond, what, read) do { if (cond) cbc_path_count((what), (read)); } while (0)
+#define CBC_COUNT_MUTE(on) cbc_path_mute(on)
+#else
+#define CBC_COUNT(what, read) do {} while (0)
+#define CBC_COUNT_IF(cond, what, read) do {} while (0)
+#define CBC_COUNT_MUTE(on) do {} while (0)
+#endif
+
 struct cbc_enc_args {
     const cbc_read_rec   *recs;
     const uint8_t        *seq;
@@ -248,6 +272,20 @@ struct CbcEnc {
     {
         lm1 = W::uv_opaque(l - 1u);
         thr0 = ((l & (1u << 24)) | (1u << 25)) - l;
+    }
+    /* The remainder test of a two-bound step: does either low word reach 2^32 - 2^26 (see code1_lazy())?  The larger of
+     * the two against the bound is exact for that (v_max_u32 where the OR form has v_or_b32).  The OR of the two never
+     * misses one either, but has its top six bits set far more often (17.8 % against 3.2 % of steps on random operands) and
+     * sends all those steps through the remainder branch, whose quotients are right either way: about 13 instructions
+     * with four quarter-rate multiplies, on the coder's chain and on a SIMD it shares with model wavefronts (measured: DESIGN.md
+     * section 4.1).  The GEN kernels and the long-read encoder (CbcEnc<W, true>) keep the OR form: they were not measured
+     * with the other.  -DCBC_REM_OR: A/B build, the OR form everywhere. */
+    static CBC_MFN bool rem_flag2(Uv tl, Uv th)
+    {
+#ifndef CBC_REM_OR
+        if constexpr (!GEN) return W::uv_ge(tl > th ? tl : th, 0xfc000000u);
+#endif
+        return W::uv_ge(tl | th, 0xfc000000u);
     }
     uint32_t scale3;                         /* E3 count pending after the steps packed so far      */
     uint32_t bitpos, flushed;               /* bits produced; words already stored (multiple of 64)  */
@@ -512,7 +550,10 @@ struct CbcEnc {
 #endif
         Uv ql, qh, tl, th;
         W::mul64(rng, flo, ql, tl); W::mul64(rng, fhi, qh, th);
-        if (W::uv_ge(tl | th, 0xfc000000u)) {                 /* the remainder test of code1_lazy() */
+        CBC_COUNT(CBC_PC_QUIET, cur_read);
+        CBC_COUNT_IF(W::uv_scalar(tl) >= 0xfc000000u || W::uv_scalar(th) >= 0xfc000000u, CBC_PC_QUIET_REM_EXACT, cur_read);
+        if (rem_flag2(tl, th)) {                              /* the remainder test of code1_lazy() */
+            CBC_COUNT(CBC_PC_QUIET_REM, cur_read);
             const uint32_t lo = lo_of(), hi = hi_of(), n = n_of();
             ql += (rng * lo - ql * n >= n) ? 1u : 0u;
             qh += (rng * hi - qh * n >= n) ? 1u : 0u;
@@ -685,8 +726,9 @@ struct CbcEnc {
     {
         code1_lazy(flo, fhi, [&]() { return lo; }, [&]() { return hi; }, [&]() { return n; }, rec, k3);
     }
-    /* the same step with cum / cum + count / total fetched only where they are needed: the remainder test that one step
-     * in 64 takes (and the emulation's cross-check).  The fixed symbols keep their operands in lanes of vector registers
+    /* the same step with cum / cum + count / total fetched only where they are needed: the remainder branch, which about
+     * one step in 32 takes on random operands (one in 64 per low word: rem_flag2()) and every step with
+     * cum + count = n, and the emulation's cross-check.  The fixed symbols keep their operands in lanes of vector registers
      * (one lane per record), so every operand costs a v_readlane: two per step on the usual path instead of five. */
     template <class FLO, class FHI, class FN>
     CBC_MFN void code1_lazy(uint32_t flo, uint32_t fhi, FLO lo_of, FHI hi_of, FN n_of, Uv &rec, Uv &k3)
@@ -698,12 +740,16 @@ struct CbcEnc {
         /* floor(range * c / n) for c = lo and c = hi, given f = floor(c * 2^32 / n) (clamped to 2^32 - 1
          * when c == n).  range * f = q * 2^32 + t: the true quotient is q + (t + range * g / n) / 2^32
          * with g < n the remainder of f's own division, and range <= 2^26, so q is final unless
-         * t >= 2^32 - 2^26 (one step in 64 for a random t, and always when cum + count = n).  Only then
+         * t >= 2^32 - 2^26 (one in 64 for a random t, so one step in 32 for its two words, and always when
+         * cum + count = n).  Only then
          * is the remainder formed (it is < 2n < 2^22, so its low 32 bits are all of it): one 32x32->64
          * multiply per division on the usual path instead of three quarter-rate ones. */
         Uv ql, qh, tl, th;
         W::mul64(range, flo, ql, tl); W::mul64(range, fhi, qh, th);
-        if (W::uv_ge(tl | th, 0xfc000000u)) {
+        CBC_COUNT(CBC_PC_CODE1, cur_read);
+        CBC_COUNT_IF(W::uv_scalar(tl) >= 0xfc000000u || W::uv_scalar(th) >= 0xfc000000u, CBC_PC_CODE1_REM_EXACT, cur_read);
+        if (rem_flag2(tl, th)) {
+            CBC_COUNT(CBC_PC_CODE1_REM, cur_read);
             const uint32_t lo = lo_of(), hi = hi_of(), n = n_of();
             ql += (range * lo - ql * n >= n) ? 1u : 0u;
             qh += (range * hi - qh * n >= n) ? 1u : 0u;
@@ -763,7 +809,9 @@ struct CbcEnc {
 #endif
         Uv qh, th;
         W::mul64(rng, fhi, qh, th);
+        CBC_COUNT(CBC_PC_KNOWN0, cur_read);
         if (W::uv_ge(th, 0xfc000000u)) {
+            CBC_COUNT(CBC_PC_KNOWN0_REM, cur_read);
             const uint32_t hi = hi_of(), n = n_of();
             qh += (rng * hi - qh * n >= n) ? 1u : 0u;
         }
@@ -784,6 +832,107 @@ struct CbcEnc {
         code_tail(W::uv(0u), qh, rec, k3);
         rec_put(rec, k3);
         rec_n++;
+    }
+    /* ---- fused quiet steps: A/B BUILDS ONLY (-DCBC_FUSE_SR, -DCBC_FUSE_X3; the default build codes these steps one at a
+     * time, and the emulation with the path counters, tests/emu/emu_paths.cpp, defines both).  Five of a record's eight
+     * fixed symbols (same_ref, rlength[0..3]) usually only move (l, range): nothing shifts, nothing is recorded, no lane is
+     * taken.  Coded one at a time they cost a remainder test and a "nothing shifts" test each -- ten v_cmp -> vcc -> branch
+     * turn-rounds on the coder's serial chain.  The two forms below run the multiplies of a group of them back to back on
+     * the assumption that every step of the group is quiet, fold all its tests into ONE word compared once, and commit only
+     * then; otherwise they leave the state as it was and the steps are coded one at a time as before (with cfg2's reads,
+     * of one length: DESIGN.md section 4.1 has the rates).  A test word is "bad" when it is at or above 2^32 - 2^26: a low
+     * word that needs the remainder; q + ~thr0 = q - thr0 - 1, which is below 2^26 when q > thr0 and wraps to at least
+     * 2^32 - 2^25 - 1 otherwise (q <= 2^26, 2^24 < thr0 <= 2^25); all ones.  The largest of the words decides.
+     * They shorten the coder's chain by ~145 cycles per record and make launches of a few blocks per CU 9 % shorter, but a
+     * whole cfg2 launch, where the model wavefront is the block's chain and the fallbacks' repeated multiplies take issue
+     * slots from it, 0.5 - 2 % LONGER (profiles/fused_steps_ab.log): hence not in the default build.
+     * They are kept as switches, with their cross-checks, because that verdict belongs to today's balance of the two
+     * wavefronts: whatever shortens the model wavefront's chain at cfg2 makes the coder the chain again, as it already is
+     * with fewer blocks per CU, and these are then the next 145 cycles to take off it. ---- */
+    static CBC_MFN Uv uv_max(Uv a, Uv b) { return a > b ? a : b; }
+    /* rlength[1..3]: three times symbol 0 of a model with the same (count0, n), so one f.  While nothing shifts l and
+     * thr0 stay, and q1 >= q2 >= q3, so q3 > thr0 covers all three; with no low word at the bound each quotient is exact
+     * given the one before. */
+    template <class FHI, class FN>
+    CBC_MFN void step_known0_x3(FHI hi_of, FN n_of, uint32_t f)
+    {
+#if !defined(CBC_ABLATE_CODER) && defined(CBC_FUSE_X3)
+        Uv q1, q2, q3, t1, t2, t3;
+        W::mul64(rng, f, q1, t1); W::mul64(q1, f, q2, t2); W::mul64(q2, f, q3, t3);
+        const Uv tm = uv_max(uv_max(t1, t2), t3);
+        CBC_COUNT(CBC_PC_X3, cur_read);
+        if (!W::uv_ge(uv_max(tm, q3 + ~thr0), 0xfc000000u)) {
+#ifndef __HIP_DEVICE_COMPILE__     /* emulation: the quotients, the full recurrence, and the three single steps on a copy */
+            const uint32_t hi = hi_of(), n = n_of(), lf = W::uv_scalar(l);
+            const uint32_t q[4] = { W::uv_scalar(rng), W::uv_scalar(q1), W::uv_scalar(q2), W::uv_scalar(q3) };
+            for (int k = 1; k <= 3; k++) {
+                W::expect_eq(q[k], (uint32_t)((uint64_t)q[k - 1] * hi / n), "step_known0_x3: scaled_div(count0)");
+                const uint32_t uf = lf + q[k] - 1u;
+                W::expect_eq(((lf ^ uf) >> 25) & 1u, 1u, "step_known0_x3: E1/E2 would shift");
+                W::expect_eq((lf >> 24) & (~uf >> 24) & 1u, 0u, "step_known0_x3: E3 would shift");
+            }
+            CbcEnc one = *this;
+            CBC_COUNT_MUTE(1);
+            one.step_known0(hi_of, n_of, f); one.step_known0(hi_of, n_of, f); one.step_known0(hi_of, n_of, f);
+            CBC_COUNT_MUTE(0);
+            W::expect_eq(W::uv_scalar(one.l), lf, "step_known0_x3: l of the single steps");
+            W::expect_eq(W::uv_scalar(one.rng), q[3], "step_known0_x3: range of the single steps");
+            W::expect_eq(one.nsym, nsym + 3u, "step_known0_x3: nsym of the single steps");
+            W::expect_eq(one.rec_n, rec_n, "step_known0_x3: the single steps record something");
+#endif
+            CBC_COUNT(CBC_PC_X3_EXIT, cur_read);
+            rng = q3; nsym += 3u;
+            return;
+        }
+        CBC_COUNT(W::uv_scalar(tm) >= 0xfc000000u ? CBC_PC_X3_FB_REM : CBC_PC_X3_FB_SHIFT, cur_read);
+#endif
+        step_known0(hi_of, n_of, f); step_known0(hi_of, n_of, f); step_known0(hi_of, n_of, f);
+    }
+    /* same_ref (symbol 0: step_known0()) and then rlength[0] (step_fixed_quiet()) of a record other than a block's first:
+     * qa is same_ref's new range, which rlength[0]'s two bounds are then cut from.  "Nothing shifts" is qa > thr0 for the
+     * first and step_fixed_quiet()'s own test on l + ql and l - 1 + qh for the second, here as a word with bit 25 set
+     * when something WOULD shift, spread to all ones. */
+    template <class FH0, class FN0, class FLO, class FHI, class FN>
+    CBC_MFN void step_sameref_rl0(FH0 sr_hi_of, FN0 sr_n_of, uint32_t sr_fh, FLO lo_of, FHI hi_of, FN n_of, uint32_t flo, uint32_t fhi)
+    {
+#if !defined(CBC_ABLATE_CODER) && defined(CBC_FUSE_SR)
+        Uv qa, ql, qh, ta, tl, th;
+        W::mul64(rng, sr_fh, qa, ta); W::mul64(qa, flo, ql, tl); W::mul64(qa, fhi, qh, th);
+        const Uv tm = uv_max(uv_max(ta, tl), th);
+        const Uv l1 = l + ql, u = lm1 + qh;
+        const Uv shifts = ~(l1 ^ u) | ((l1 & ~u) << 1);              /* bit 25: E1/E2 or E3 */
+        const Uv bad = (Uv)((int32_t)(shifts << 6) >> 31);           /* all ones if so */
+        CBC_COUNT(CBC_PC_SR, cur_read);
+        if (!W::uv_ge(uv_max(uv_max(tm, qa + ~thr0), bad), 0xfc000000u)) {
+#ifndef __HIP_DEVICE_COMPILE__     /* emulation: the quotients, the full recurrence, and the two single steps on a copy */
+            const uint32_t r0 = W::uv_scalar(rng), ra = W::uv_scalar(qa), l0 = W::uv_scalar(l);
+            W::expect_eq(ra, (uint32_t)((uint64_t)r0 * sr_hi_of() / sr_n_of()), "step_sameref_rl0: scaled_div(count0)");
+            W::expect_eq(W::uv_scalar(ql), (uint32_t)((uint64_t)ra * lo_of() / n_of()), "step_sameref_rl0: scaled_div(cum)");
+            W::expect_eq(W::uv_scalar(qh), (uint32_t)((uint64_t)ra * hi_of() / n_of()), "step_sameref_rl0: scaled_div(cum + count)");
+            const uint32_t ua = l0 + ra - 1u, lf = W::uv_scalar(l1), uf = W::uv_scalar(u);
+            W::expect_eq(((l0 ^ ua) >> 25) & 1u, 1u, "step_sameref_rl0: same_ref, E1/E2 would shift");
+            W::expect_eq((l0 >> 24) & (~ua >> 24) & 1u, 0u, "step_sameref_rl0: same_ref, E3 would shift");
+            W::expect_eq(W::clz32((((lf ^ uf) & CBC_M26) << 6) | 32u), 0u, "step_sameref_rl0: rlength[0], E1/E2 would shift");
+            W::expect_eq(W::clz32(((((~lf | uf) << 7) | 127u))), 0u, "step_sameref_rl0: rlength[0], E3 would shift");
+            CbcEnc one = *this;
+            CBC_COUNT_MUTE(1);
+            one.step_known0(sr_hi_of, sr_n_of, sr_fh); one.step_fixed_quiet(lo_of, hi_of, n_of, flo, fhi);
+            CBC_COUNT_MUTE(0);
+            W::expect_eq(W::uv_scalar(one.l), lf, "step_sameref_rl0: l of the single steps");
+            W::expect_eq(W::uv_scalar(one.rng), W::uv_scalar(qh - ql), "step_sameref_rl0: range of the single steps");
+            W::expect_eq(one.nsym, nsym + 2u, "step_sameref_rl0: nsym of the single steps");
+            W::expect_eq(one.rec_n, rec_n, "step_sameref_rl0: the single steps record something");
+#endif
+            CBC_COUNT(CBC_PC_SR_EXIT, cur_read);
+            l = l1; rng = qh - ql;
+            set_l_forms();
+            nsym += 2u;
+            return;
+        }
+        CBC_COUNT(W::uv_scalar(tm) >= 0xfc000000u ? CBC_PC_SR_FB_REM : CBC_PC_SR_FB_SHIFT, cur_read);
+#endif
+        step_known0(sr_hi_of, sr_n_of, sr_fh);
+        step_fixed_quiet(lo_of, hi_of, n_of, flo, fhi);
     }
     CBC_MFN uint32_t finish()                        /* encoder_last_step :348-363 + stream_finish_byte */
     {
@@ -2085,19 +2234,25 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
             /* -- compress_rname (id_compression.c:39-65): same_ref is (1,1) until record 0 codes symbol 1,
              *    after which only symbol 0 is coded; the name itself is the model wave's segment -- */
             E.room(8u);                                       /* same_ref, rlength x 4, pos, flag, match */
-            if (!CBC_ENC_FIRST(first, r)) E.step_known0(CBC_LZ(W::readlane(sr_hi, j)), CBC_LZ(10u * r + 2u), W::readlane(sr_fh, j));
-            else {
+            const uint32_t tn = 255u + 10u * r;
+            if (CBC_ENC_FIRST(first, r)) {
                 E.encode(1u, 1u, 2u); E.drain_q();
                 if (fused) { gen_rname(); E.seg_end(); } else E.seg_consume();
             }
             /* -- read length, 4 "bytes" (read_compression.c:29-33, quirk Q1): rlength[0] from the group
-             *    pass; contexts 1..3 only ever code symbol 0, each once per record -- */
-            {
-                const uint32_t tn = 255u + 10u * r, tf = W::readlane(t_fh, j);
+             *    pass; contexts 1..3 only ever code symbol 0, each once per record.  same_ref + rlength[0] and
+             *    rlength[1..3] go through the two fused quiet steps, which code them one at a time unless an A/B build
+             *    asks for the fused forms; record 0, whose same_ref is not symbol 0, calls the single steps -- */
+            if (CBC_ENC_FIRST(first, r)) {
+                const uint32_t tf = W::readlane(t_fh, j);
                 E.step_fixed_quiet(CBC_LZ(W::readlane(F.rl_lo, j)), CBC_LZ(W::readlane(rl_hi, j)), CBC_LZ(tn), W::readlane(rl_fl, j), W::readlane(rl_fh, j));
                 E.step_known0(CBC_LZ(W::readlane(t_hi, j)), CBC_LZ(tn), tf);
                 E.step_known0(CBC_LZ(W::readlane(t_hi, j)), CBC_LZ(tn), tf);
                 E.step_known0(CBC_LZ(W::readlane(t_hi, j)), CBC_LZ(tn), tf);
+            } else {
+                E.step_sameref_rl0(CBC_LZ(W::readlane(sr_hi, j)), CBC_LZ(10u * r + 2u), W::readlane(sr_fh, j),
+                                   CBC_LZ(W::readlane(F.rl_lo, j)), CBC_LZ(W::readlane(rl_hi, j)), CBC_LZ(tn), W::readlane(rl_fl, j), W::readlane(rl_fh, j));
+                E.step_known0_x3(CBC_LZ(W::readlane(t_hi, j)), CBC_LZ(tn), W::readlane(t_fh, j));
             }
             /* -- compress_pos: hit, or escape + the four bytes of the new delta -- */
             E.step_fixed(CBC_LZ(W::readlane(F.p_lo, j)), CBC_LZ(W::readlane(p_hi, j)), CBC_LZ(W::readlane(p_n, j)), W::readlane(p_fl, j), W::readlane(p_fh, j));
