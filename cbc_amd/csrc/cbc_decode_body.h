@@ -113,6 +113,29 @@ struct CbcDec {
 #endif
 
     CBC_MFN void fail(uint32_t st) { if (status == CBC_ST_OK) { status = st; fail_read = cur_read; } }
+    /* ---- the start of a stream: the mirror of CbcEnc::start_coder / start_models ---- */
+    CBC_MFN void start_coder()
+    {
+        status = CBC_ST_OK; nsym = 0; fail_read = 0; cur_read = 0;
+        l = W::dv(0u); rng = W::dv(CBC_M26 + 1u); d = W::dv(0u); acc = 0; navail = 0; widx = 0; wordv = W::splat(0u);
+    }
+    /* the tag: first 26 bits (alloc_arithmetic_stream, Arithmetic_stream.c:260-263); after inb / nwords_in / tail_valid are set,
+     * and only for arguments that passed their checks -- that test stays with the callers (inside this member it changes the
+     * decode kernels' branch layout) */
+    CBC_MFN void start_tag() { d = W::dv(take(26u)); }
+    /* what every form's models start from; the tables, the lane table (cbc_small_start) and the totals rlen_n, rl123_*, snps_n,
+     * indels_n stay with the callers */
+    CBC_MFN void start_models()
+    {
+        rn_count = 0; pos_card = 1u; pos_n = 1u; nev = 0; nev1 = 0;
+        pval = W::splat(0xffffffffu); pcnt = W::select(W::lane() == 0u, W::splat(1u), W::splat(0u));
+        fkey = W::splat(0u); fexc = W::splat(0u); fcount = 0; fn = 65536u;
+        hkey = W::splat(0u); hexc = W::splat(0u);
+        hc0 = hc1 = hc2 = hc3 = 0; hn0 = hn1 = hn2 = hn3 = 256u;
+        prevPos = 0; prevM = 0; prevChar = 0; win_clear();
+        rl_memo_x = CBC_NOMEMO; rl_memo_lo = 0; rl_memo_cnt = 0; rl_last_x = 0;
+        p0cnt = W::splat(0u); p0over = 0;
+    }
     CBC_MFN uint32_t *tab(uint32_t off) { return lds + off; }
     CBC_MFN uint32_t *pos_val_p() { return pos_valp; }
     CBC_MFN uint32_t *pos_cnt_p() { return pos_cntp; }
@@ -306,7 +329,8 @@ struct CbcDec {
         }
         const V32 qlv = W::muldiv_v(rng, W::select(live, A, W::splat(0u)), n);
         const V32 qhv = W::muldiv_v(rng, W::select(live, A + 1u + exc, W::splat(0u)), n);
-        const uint64_t hb = W::ballot(live & (qlv <= W::dvv(d)) & (W::dvv(d) < qhv));
+        const V32 dvec = W::dvv(d);                           /* read once: no call among the operands of the mask's & */
+        const uint64_t hb = W::ballot(live & (qlv <= dvec) & (dvec < qhv));
         if (!hb) return false;
         const uint32_t hl = W::ctz64(hb);
         x = W::readlane(key, hl);
@@ -331,7 +355,8 @@ struct CbcDec {
         const uint32_t range = rng;
         const V32 qlv = W::muldiv_v(range, W::select(live, A, W::splat(0u)), n);
         const V32 qhv = W::muldiv_v(range, W::select(live, A + 1u + exc, W::splat(0u)), n);
-        const uint64_t hb = W::ballot(live & (qlv <= W::dvv(d)) & (W::dvv(d) < qhv));
+        const V32 dvec = W::dvv(d);                           /* read once: no call among the operands of the mask's & */
+        const uint64_t hb = W::ballot(live & (qlv <= dvec) & (dvec < qhv));
         uint32_t x, hl = 0; const bool hit = hb != 0ull;
         if (hit) {
             hl = W::ctz64(hb); x = W::readlane(key, hl);
@@ -1032,8 +1057,7 @@ CBC_FN void cbc_decode_stream(const cbc_dec_args &A, uint32_t blk, uint32_t *lds
     const uint64_t in_off = bd->in_off, ref_off = bd->ref_off, rec_base = bd->rec_base, seq_base = bd->seq_base;
     const uint32_t in_bytes = bd->in_bytes, n_reads = bd->n_reads, L0 = bd->read_length, stride = bd->seq_stride;
 
-    D.status = CBC_ST_OK; D.nsym = 0; D.fail_read = 0; D.cur_read = 0;
-    D.l = W::dv(0u); D.rng = W::dv(CBC_M26 + 1u); D.d = W::dv(0u); D.acc = 0; D.navail = 0; D.widx = 0; D.wordv = W::splat(0u);
+    D.start_coder();
     D.inb = A.in + in_off;
     D.lds = lds; D.cap_pos = A.cap_pos; D.cap_var = A.cap_var; D.L0 = L0;
     D.evp = A.var_scratch + (uint64_t)blk * A.cap_var;
@@ -1062,29 +1086,10 @@ CBC_FN void cbc_decode_stream(const cbc_dec_args &A, uint32_t blk, uint32_t *lds
     }
 
     for (uint32_t b = 0; b < CBC_DLDS_FIXED; b += 64u) W::store32(lds, ln + b, W::splat(0u), (ln + b) < CBC_DLDS_FIXED);
-    D.rlen_n = 255u; D.rl123_c0 = 1u; D.rl123_n = 255u; D.snps_n = L0; D.indels_n = L0; D.rn_count = 0;
-    D.pos_card = 1u; D.pos_n = 1u; D.nev = 0; D.nev1 = 0;
-    D.pval = W::splat(0xffffffffu); D.pcnt = W::select(ln == 0u, W::splat(1u), W::splat(0u));
-    D.fkey = W::splat(0u); D.fexc = W::splat(0u); D.fcount = 0; D.fn = 65536u;
-    D.hkey = W::splat(0u); D.hexc = W::splat(0u);
-    D.hc0 = D.hc1 = D.hc2 = D.hc3 = 0; D.hn0 = D.hn1 = D.hn2 = D.hn3 = 256u;
-    {
-        V32 s = W::select(ln < 10u, W::splat(1u), W::splat(0u));
-        V32 r = (ln - CBC_LT_CHARS) >> 3, c = (ln - CBC_LT_CHARS) & 7u;
-        Mask inch = (ln >= CBC_LT_CHARS) & (r < 6u) & (c < 5u);
-        V32 cv = W::select(c == 4u, W::splat(1u), W::select(c == r, W::splat(0u), W::splat(8u)));
-        Mask bump = ((r == 0u) & ((c == 1u) | (c == 2u))) | ((r == 1u) & ((c == 0u) | (c == 3u))) |
-                    ((r == 2u) & ((c == 0u) | (c == 3u))) | ((r == 3u) & ((c == 1u) | (c == 2u)));
-        cv = W::select(bump, cv + 8u, cv);
-        D.small = W::select(inch, cv, s);
-    }
-    D.prevPos = 0; D.prevM = 0; D.prevChar = 0; D.win_clear();
-    D.rl_memo_x = CBC_NOMEMO; D.rl_memo_lo = 0; D.rl_memo_cnt = 0; D.rl_last_x = 0;
-    D.p0cnt = W::splat(0u); D.p0over = 0;
-
-    /* the tag: first 26 bits (alloc_arithmetic_stream, Arithmetic_stream.c:260-263) */
-    if (D.status == CBC_ST_OK) D.d = W::dv(D.take(26u));
-
+    D.rlen_n = 255u; D.rl123_c0 = 1u; D.rl123_n = 255u; D.snps_n = L0; D.indels_n = L0;
+    D.start_models();
+    D.small = cbc_small_start<W>(10u);
+    if (D.status == CBC_ST_OK) D.start_tag();
     /* stream header: int(L0), 32 x int(WELL), int(8) */
     for (uint32_t k = 0; k < 34u && D.status == CBC_ST_OK; k++) {
         uint32_t v = D.regsparse_dec(D.hkey, D.hexc, 0u, 8u, D.hc0, D.hn0, 256u, 1u, CBC_ST_ASSERT) << 24;

@@ -168,11 +168,10 @@ CBC_FN uint32_t cbc_basepair(uint32_t c)            /* char2basepair sam_models.
  * Kept in ONE vector register, 32 bits in each of lanes 0..7 (the other lanes hold 0): sliding it is two lane gathers and a
  * funnel shift, the first mark at or after p is one ballot and two count-trailing-zeros, setting a mark is a compare and an
  * OR.  (Round 1 kept it in four 64-bit scalars: ~30 scalar instructions per slide or search, on the unit that is these
- * kernels' busiest port; -DCBC_WIN_SCALAR restores that form for A/B.) */
+ * kernels' busiest port; that form is in the history before its A/B switch was retired.) */
 template <class W>
 struct CbcWin {
     typedef typename W::V32 V32;
-#ifndef CBC_WIN_SCALAR
     V32 w;
     CBC_MFN void clear() { w = W::splat(0u); }
     CBC_MFN void shift(uint32_t d)                      /* drop the d lowest positions */
@@ -204,54 +203,31 @@ struct CbcWin {
     {
         if (k < 256u) w = w | W::select(W::lane() == (k >> 5), W::splat(1u << (k & 31u)), W::splat(0u));
     }
-#else
-    uint64_t w0, w1, w2, w3;
-    CBC_MFN void clear() { w0 = w1 = w2 = w3 = 0; }
-    CBC_MFN void shift(uint32_t d)
-    {
-        if (d == 0u) return;
-        if (d >= 256u) { clear(); return; }
-        uint32_t wsh = d >> 6, bsh = d & 63u;
-        if (wsh == 1u) { w0 = w1; w1 = w2; w2 = w3; w3 = 0; }
-        else if (wsh == 2u) { w0 = w2; w1 = w3; w2 = 0; w3 = 0; }
-        else if (wsh == 3u) { w0 = w3; w1 = 0; w2 = 0; w3 = 0; }
-        if (bsh) {
-            uint32_t inv = 64u - bsh;
-            w0 = (w0 >> bsh) | (w1 << inv);
-            w1 = (w1 >> bsh) | (w2 << inv);
-            w2 = (w2 >> bsh) | (w3 << inv);
-            w3 = w3 >> bsh;
-        }
-    }
-    CBC_MFN uint32_t first(uint32_t p, uint32_t rl)
-    {
-        uint32_t out = rl + 2u;
-        if (p >= rl) return out;
-        uint32_t pw = p >> 6; uint64_t pm = ~0ull << (p & 63u);
-        uint64_t a0 = pw == 0u ? (w0 & pm) : 0ull;
-        uint64_t a1 = pw == 1u ? (w1 & pm) : (pw < 1u ? w1 : 0ull);
-        uint64_t a2 = pw == 2u ? (w2 & pm) : (pw < 2u ? w2 : 0ull);
-        uint64_t a3 = pw == 3u ? (w3 & pm) : w3;
-        uint32_t pos = 0xffffffffu;
-        if (a0) pos = W::ctz64(a0);
-        else if (a1) pos = 64u + W::ctz64(a1);
-        else if (a2) pos = 128u + W::ctz64(a2);
-        else if (a3) pos = 192u + W::ctz64(a3);
-        if (pos < rl) out = pos - p;
-        return out;
-    }
-    CBC_MFN void set(uint32_t k)
-    {
-        /* selects, not an if-chain: an if-chain over adjacent members is turned back into a
-         * runtime-indexed access by the optimiser, which forces the window into scratch memory */
-        uint64_t bit = 1ull << (k & 63u); uint32_t kw = k >> 6;
-        w0 |= (kw == 0u) ? bit : 0ull;
-        w1 |= (kw == 1u) ? bit : 0ull;
-        w2 |= (kw == 2u) ? bit : 0ull;
-        w3 |= (kw == 3u) ? bit : 0ull;
-    }
-#endif
 };
+
+/* ---- the start of a stream, stated once for the three encoders and the three decoders (CbcEnc / CbcDec: start_coder,
+ * start_handoff, start_models, code_int; start_tag): this state decides every byte of the output.  The loop over the 34 words
+ * of the stream header stays with each of its four callers, and the long-read kernels keep their own code_int / dec_int: as
+ * members they change the gfx950 code of those kernels (profiles/start_state_isa.log) ---- */
+/* The lane table `small` at the start: lanes [0, ones) hold 1 -- match 1,1 per context (n = 2) and same_ref 1,1 (lanes 8, 9)
+ * in the short-read kernels, ones = 10; the long-read kernels keep their kind contexts in lanes 0-5 and 10-15 (1,1,1), ones =
+ * 16 -- and lanes 16..63 the chars rows (sam_models.c:372-401). */
+template <class W>
+CBC_FN typename W::V32 cbc_small_start(uint32_t ones)
+{
+    typedef typename W::V32 V32;
+    typedef typename W::Mask Mask;
+    const V32 ln = W::lane();
+    V32 sm = W::select(ln < ones, W::splat(1u), W::splat(0u));
+    V32 r = (ln - CBC_LT_CHARS) >> 3, c = (ln - CBC_LT_CHARS) & 7u;
+    Mask inch = (ln >= CBC_LT_CHARS) & (r < 6u) & (c < 5u);
+    V32 cv = W::select(c == 4u, W::splat(1u), W::select(c == r, W::splat(0u), W::splat(8u)));
+    /* +8 on two entries per row: A:{C,G} C:{A,T} G:{A,T} T:{C,G} */
+    Mask bump = ((r == 0u) & ((c == 1u) | (c == 2u))) | ((r == 1u) & ((c == 0u) | (c == 3u))) |
+                ((r == 2u) & ((c == 0u) | (c == 3u))) | ((r == 3u) & ((c == 1u) | (c == 2u)));
+    cv = W::select(bump, cv + 8u, cv);
+    return W::select(inch, cv, sm);
+}
 
 /* does the wave policy supply the lane writes under one mask (W::set_lane2_uv / W::set_lane3: cbc_wave_gpu.h)?  The
  * CPU lock-step emulation's policy does not and gets the plain form, which writes the same lanes. */
@@ -295,7 +271,8 @@ struct CbcEnc {
     V32 q_lo, q_cnt, q_n; uint32_t q_len;   /* pending symbols: lane k = k-th queued (lo, cnt, n)      */
     uint32_t role, batch_i; uint32_t *batch, *ctl;  /* CBC_ROLE_*; hand-off ring and its two counters in LDS */
     /* coder wave: the batch taken from the model wave (lane k = its k-th symbol) and the read cursor */
-    V32 b_lo, b_hi, b_n, b_fl, b_fh; uint32_t b_len, b_pos, b_stop, b_flags, seen_last; uint64_t b_neq;
+    V32 b_lo, b_hi, b_n, b_fl, b_fh; uint32_t b_len, b_pos, b_stop, b_flags, seen_last;
+    uint64_t b_neq;                         /* words 4, 5 of a batch header: the match mask of the retired GROUP batches; nothing sends or reads it */
     V32 rec_a, rec_s; uint32_t rec_n;       /* output of the coder steps not packed yet (see pack())   */
 #ifdef CBC_STAMP
     unsigned long long t_last, t_sum[16];
@@ -329,6 +306,42 @@ struct CbcEnc {
 
     /* ======================================================================================= */
     CBC_MFN void fail(uint32_t st) { if (status == CBC_ST_OK) { status = st; fail_read = cur_read; } }
+
+    /* ---- the start of a stream (alloc_arithmetic_stream, Arithmetic_stream.c:246-263, and the models' initial counts) ---- */
+    /* the coder, its bit writer over `ring_` (CBC_RING_WORDS of LDS, zeroed by the caller), the symbol queue, the registers
+     * of the batch in hand and the recorded steps.  pulls = false: the whole-file form, which never pulls a batch, leaves the
+     * five batch registers unset (they are dead there, but setting them changes that kernel's register allocation). */
+    CBC_MFN void start_coder(uint32_t *ring_, bool pulls)
+    {
+        status = CBC_ST_OK; nsym = 0; fail_read = 0; cur_read = 0;
+        l = W::uv(0u); set_l_forms(); rng = W::uv(CBC_M26 + 1u); scale3 = 0u; bitpos = 0; flushed = 0;
+        ring = ring_;
+        q_lo = W::splat(0u); q_cnt = W::splat(0u); q_n = W::splat(0u); q_len = 0;
+        if (pulls) { b_lo = W::splat(0u); b_hi = W::splat(0u); b_n = W::splat(1u); b_fl = W::splat(0u); b_fh = W::splat(0u); }
+        b_len = 0; b_pos = 0; b_stop = 64u; b_flags = 0; seen_last = 0; b_neq = 0;
+        rec_a = W::splat(0u); rec_s = W::splat(0u); rec_n = 0;
+    }
+    /* the hand-off: this wavefront's role, the batch ring and its counters in LDS (nullptr where one wavefront does it all) */
+    CBC_MFN void start_handoff(uint32_t role_, uint32_t *batch_, uint32_t *ctl_) { role = role_; batch_i = 0; batch = batch_; ctl = ctl_; }
+    /* the models' state that every form starts from; the tables and their pointers, the lane table (cbc_small_start), the totals
+     * snps_n / indels_n and the escape's count pos_occ[0] differ between the forms and stay with their callers */
+    CBC_MFN void start_models()
+    {
+        fkey = W::splat(0u); fexc = W::splat(0u); fcount = 0;
+        hkey = W::splat(0u); hexc = W::splat(0u);
+        hc0 = hc1 = hc2 = hc3 = 0; hn0 = hn1 = hn2 = hn3 = 256u;
+        p0cnt = W::splat(0u); p0over = 0;
+        prevPos = 0; prevM = 0; prevChar = 0; win_pos = 0;
+        win_clear();
+    }
+    /* compress_int (qv_codebook.c:14-50): four bytes, MSB first, through the four header models (the words of the stream header) */
+    CBC_MFN void code_int(uint32_t v)
+    {
+        regsparse_code(hkey, hexc, 0u, 8u, hc0, hn0, 256u, 1u, v >> 24, CBC_ST_ASSERT);
+        regsparse_code(hkey, hexc, 8u, 8u, hc1, hn1, 256u, 1u, (v >> 16) & 0xffu, CBC_ST_ASSERT);
+        regsparse_code(hkey, hexc, 16u, 8u, hc2, hn2, 256u, 1u, (v >> 8) & 0xffu, CBC_ST_ASSERT);
+        regsparse_code(hkey, hexc, 24u, 8u, hc3, hn3, 256u, 1u, v & 0xffu, CBC_ST_ASSERT);
+    }
 
     /* ---- bit writer (stream_write_bits / stream_write_bit, io_functions.c; MSB first).  The stream is
      * assembled in a ring of LDS words: a piece of <= 32 bits at bit offset `off` is OR-ed into one or two
@@ -376,9 +389,6 @@ struct CbcEnc {
      * the previous batch when no step of this batch has emitted yet. */
     CBC_MFN void pack(const V32 &rec_a, const V32 &rec_k3, uint32_t m)
     {
-#ifdef CBC_ABLATE_PACK            /* timing experiments only (tools/README.md): the stream is wrong */
-        bitpos += m; return;
-#endif
         const V32 ln = W::lane();
         const Mask in = ln < m;
         const V32 k1 = rec_a >> 26, bits = (rec_a & CBC_M26) >> ((W::splat(26u) - k1) & 31u);   /* k1 = 0: l >> 26 = 0 */
@@ -469,19 +479,19 @@ struct CbcEnc {
      * `produced` with release order; the coder waits for produced > consumed, copies the slot into
      * registers and bumps `consumed`.  The ring lets the model wave run several batches ahead, which
      * absorbs the burstiness of the two sides (a run of perfect records costs the coder time and the
-     * model wave none; an imperfect record the reverse).  Per group of 64 records the model wave also
-     * sends one empty batch flagged GROUP that carries the group's match-test mask.  The model wave
+     * model wave none; an imperfect record the reverse).  The match-test mask of a group of 64 records
+     * goes the other way, through the mailbox of post_group() / wait_group() below.  The model wave
      * always ends with a batch flagged LAST (which carries its status) and never waits after it;
      * whatever happens, the coder takes batches until it has seen LAST, so both waves run to their end. */
 #define CBC_FRAC(c, n) W::frac32(c, n)
 #define CBC_BF_LAST  1u
-#define CBC_BF_GROUP 2u
+#define CBC_BF_GROUP 2u                              /* no sender left: see seg_consume() */
 #define CBC_END_N    0xffffffffu                     /* n of an END entry */
-    CBC_MFN void drain() { if (role == CBC_ROLE_MODEL) publish(0u, 0ull); else drain_q(); }
+    CBC_MFN void drain() { if (role == CBC_ROLE_MODEL) publish(0u); else drain_q(); }
     CBC_MFN void seg_end()
     {
         if (role != CBC_ROLE_MODEL) { drain_q(); return; }
-        if (q_len >= 64u) publish(0u, 0ull);
+        if (q_len >= 64u) publish(0u);
         q_put(0u, 1u, CBC_END_N);
     }
     /* seg_end() of the model wavefront where the caller knows the END entry fits (edits() drains at 56 entries and adds at
@@ -491,7 +501,7 @@ struct CbcEnc {
         W::expect_eq(q_len < 64u ? 1u : 0u, 1u, "seg_end_fits: queue full");
         q_put(0u, 1u, CBC_END_N);
     }
-    CBC_MFN void publish(uint32_t flags, uint64_t neq)
+    CBC_MFN void publish(uint32_t flags)
     {
         V32 ln = W::lane();
         CBC_TSM(5);
@@ -502,7 +512,7 @@ struct CbcEnc {
         W::store32(buf, ln, q_lo, m); W::store32(buf + 64u, ln, q_cnt, m); W::store32(buf + 128u, ln, q_n, m);
         V32 hdr = W::select(ln == 0u, W::splat(q_len), W::select(ln == 1u, W::splat(flags),
                   W::select(ln == 2u, W::splat(status), W::select(ln == 3u, W::splat(status == CBC_ST_OK ? cur_read : fail_read),
-                  W::select(ln == 4u, W::splat((uint32_t)neq), W::splat((uint32_t)(neq >> 32)))))));
+                  W::splat(0u)))));              /* words 4, 5: the match mask of the retired GROUP batches, nothing sends one */
         W::store32(buf + 192u, ln, hdr, ln < 6u);
         batch_i++;
         W::ctl_store(ctl, batch_i);                          /* release: the slot's words are in LDS before the count */
@@ -529,11 +539,7 @@ struct CbcEnc {
     {
         Uv rec, k3;
         code1_lazy(flo, fhi, lo_of, hi_of, n_of, rec, k3);
-#ifdef CBC_ABLATE_SETLANE         /* timing experiments only */
-        rec_a ^= rec; rec_s ^= k3;
-#else
         rec_put(rec, k3);
-#endif
         nsym++; rec_n++;
     }
     /* step_fixed() for a symbol that usually shifts nothing although its cum is not 0: rlength[0] with reads of one
@@ -545,9 +551,6 @@ struct CbcEnc {
     template <class FLO, class FHI, class FN>
     CBC_MFN void step_fixed_quiet(FLO lo_of, FHI hi_of, FN n_of, uint32_t flo, uint32_t fhi)
     {
-#ifdef CBC_ABLATE_CODER         /* timing experiments only */
-        step_fixed(lo_of, hi_of, n_of, flo, fhi); return;
-#endif
         Uv ql, qh, tl, th;
         W::mul64(rng, flo, ql, tl); W::mul64(rng, fhi, qh, th);
         CBC_COUNT(CBC_PC_QUIET, cur_read);
@@ -634,7 +637,7 @@ struct CbcEnc {
         while ((done | status) == 0u) {
             if (b_pos == b_len) {
                 if (seen_last) fail(CBC_ST_ASSERT);                            /* stream ended inside a segment */
-                else { pull(); if (b_flags & CBC_BF_GROUP) fail(CBC_ST_ASSERT); }   /* protocol: group mark inside a segment */
+                else { pull(); if (b_flags & CBC_BF_GROUP) fail(CBC_ST_ASSERT); }   /* nothing sends a GROUP batch any more; the test stays with the device code */
             } else {
                 const uint64_t em = W::ballot((b_n == CBC_END_N) & (ln >= b_pos) & (ln < b_len));
                 uint32_t kend = em ? W::ctz64(em) : b_len;
@@ -703,15 +706,6 @@ struct CbcEnc {
         neq = (uint64_t)W::read_uni(ctl, 4u + 2u * (g & 1u)) | ((uint64_t)W::read_uni(ctl, 5u + 2u * (g & 1u)) << 32);
         return W::read_uni(ctl, 3u) == 0u;
     }
-    /* coder wave: the next group's match mask (an empty batch flagged GROUP) */
-    CBC_MFN uint64_t pull_group()
-    {
-        if (status != CBC_ST_OK) return 0ull;
-        if (b_pos != b_len || seen_last) { fail(CBC_ST_ASSERT); return 0ull; }
-        pull();
-        if (status == CBC_ST_OK && !(b_flags & CBC_BF_GROUP)) fail(CBC_ST_ASSERT);
-        return b_neq;
-    }
     /* coder wave: before leaving, take every batch the model wave still sends */
     CBC_MFN void pull_rest() { while (!seen_last) pull(); }
     /* one coder step without its output: the range update (Arithmetic_stream.c:274-295) and the E1/E2
@@ -733,9 +727,6 @@ struct CbcEnc {
     template <class FLO, class FHI, class FN>
     CBC_MFN void code1_lazy(uint32_t flo, uint32_t fhi, FLO lo_of, FHI hi_of, FN n_of, Uv &rec, Uv &k3)
     {
-#ifdef CBC_ABLATE_CODER          /* timing experiments only: keeps the operands live, skips the coder */
-        l ^= flo; rng ^= fhi; rec = W::uv(0u); k3 = rec; return;
-#endif
         const Uv range = rng;
         /* floor(range * c / n) for c = lo and c = hi, given f = floor(c * 2^32 / n) (clamped to 2^32 - 1
          * when c == n).  range * f = q * 2^32 + t: the true quotient is q + (t + range * g / n) / 2^32
@@ -804,9 +795,6 @@ struct CbcEnc {
     template <class FHI, class FN>
     CBC_MFN void step_known0(FHI hi_of, FN n_of, uint32_t fhi)
     {
-#ifdef CBC_ABLATE_CODER
-        rng ^= fhi; nsym++; return;
-#endif
         Uv qh, th;
         W::mul64(rng, fhi, qh, th);
         CBC_COUNT(CBC_PC_KNOWN0, cur_read);
@@ -856,7 +844,7 @@ struct CbcEnc {
     template <class FHI, class FN>
     CBC_MFN void step_known0_x3(FHI hi_of, FN n_of, uint32_t f)
     {
-#if !defined(CBC_ABLATE_CODER) && defined(CBC_FUSE_X3)
+#ifdef CBC_FUSE_X3
         Uv q1, q2, q3, t1, t2, t3;
         W::mul64(rng, f, q1, t1); W::mul64(q1, f, q2, t2); W::mul64(q2, f, q3, t3);
         const Uv tm = uv_max(uv_max(t1, t2), t3);
@@ -895,7 +883,7 @@ struct CbcEnc {
     template <class FH0, class FN0, class FLO, class FHI, class FN>
     CBC_MFN void step_sameref_rl0(FH0 sr_hi_of, FN0 sr_n_of, uint32_t sr_fh, FLO lo_of, FHI hi_of, FN n_of, uint32_t flo, uint32_t fhi)
     {
-#if !defined(CBC_ABLATE_CODER) && defined(CBC_FUSE_SR)
+#ifdef CBC_FUSE_SR
         Uv qa, ql, qh, ta, tl, th;
         W::mul64(rng, sr_fh, qa, ta); W::mul64(qa, flo, ql, tl); W::mul64(qa, fhi, qh, th);
         const Uv tm = uv_max(uv_max(ta, tl), th);
@@ -1353,8 +1341,8 @@ struct CbcEnc {
         /* deltas below CBC_POS_IDX_WORDS (nearly all: they are gaps between neighbouring reads) find their alphabet index
          * with one LDS load per lane; 0 there = not registered yet.  Only a group that holds a larger delta walks the alphabet. */
         const Mask small_dx = live & (dxv < CBC_POS_IDX_WORDS);
-        if (CBC_POS_IDX_WORDS) kv = W::load32(pos_idx, dxv, small_dx, 0u);
-        if (!CBC_POS_IDX_WORDS || W::ballot(live & !small_dx) != 0ull) {
+        kv = W::load32(pos_idx, dxv, small_dx, 0u);
+        if (W::ballot(live & !small_dx) != 0ull) {
             const uint32_t cb = W::uni(card0);
             for (uint32_t b = 0; b < cb; b += 64u) {
                 const V32 av = W::load32(pos_val, ln + b, (ln + b) < card0, 0xffffffffu);
@@ -1664,9 +1652,6 @@ struct CbcEnc {
         const uint32_t last = (uint32_t)(rm >> 32) ? 63u - W::clz32((uint32_t)(rm >> 32)) : 31u - W::clz32((uint32_t)rm);
         const uint32_t total = W::readlane(incl, last);
         R.rm = rm; R.s = 0u;
-#ifdef CBC_WIN_SCALAR                                        /* A/B form of the window: no lane form to read, every run goes through edits() */
-        return false;
-#else
         /* owner of every SNP lane */
         const Mask head = inrun & (cntv != 0u);
         W::store32(runs, ln & 15u, zero, W::all());            /* one byte per SNP lane: record + 1 at the lane its SNPs start at */
@@ -1741,7 +1726,6 @@ struct CbcEnc {
         W::lds_or(runs, W::select(keep, mk >> 5, zero), W::select(keep, W::splat(1u) << (mk & 31u), zero), W::all());
         win.w = W::select(ln < 8u, W::load32(runs, ln & 7u, W::all(), 0u), zero);
         return true;
-#endif
     }
     /* one record of the run: its SNP-count symbol (counted by prep_group()), then var and chars of its n SNPs from the lanes */
     CBC_MFN void run_record(Run &R, uint32_t n, uint32_t lo, uint32_t cnt)
@@ -1913,14 +1897,8 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
     const uint32_t out_cap = bd->out_cap, n_reads = bd->n_reads, name_off = bd->name_off;
     const uint32_t L0 = bd->read_length, n_tok_blk = bd->n_tok;
 
-    E.status = CBC_ST_OK; E.nsym = 0; E.fail_read = 0; E.cur_read = 0;
-    E.l = W::uv(0u); E.set_l_forms(); E.rng = W::uv(CBC_M26 + 1u); E.scale3 = 0u; E.bitpos = 0; E.flushed = 0;
-    E.ring = lds + CBC_LDS_RING;
-    E.q_lo = W::splat(0u); E.q_cnt = W::splat(0u); E.q_n = W::splat(0u); E.q_len = 0;
-    E.b_lo = W::splat(0u); E.b_hi = W::splat(0u); E.b_n = W::splat(1u); E.b_fl = W::splat(0u); E.b_fh = W::splat(0u);
-    E.b_len = 0; E.b_pos = 0; E.b_stop = 64u; E.b_flags = 0; E.seen_last = 0; E.b_neq = 0;
-    E.rec_a = W::splat(0u); E.rec_s = W::splat(0u); E.rec_n = 0;
-    E.role = role; E.batch_i = 0; E.batch = lds + CBC_LDS_BATCH; E.ctl = lds + CBC_LDS_CTL;
+    E.start_coder(lds + CBC_LDS_RING, true);
+    E.start_handoff(role, lds + CBC_LDS_BATCH, lds + CBC_LDS_CTL);
     if (ROLE != CBC_ROLE_FUSED) {                            /* the only barrier: the counters start at zero for both waves */
         if (ROLE == CBC_ROLE_MODEL) { W::write_uni(E.ctl, 0u, 0u); W::write_uni(E.ctl, 1u, 0u); W::write_uni(E.ctl, 2u, 0u); W::write_uni(E.ctl, 3u, 0u); }
         W::barrier();
@@ -1961,29 +1939,12 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         for (uint32_t b = 0; b < 512u; b += 64u) W::store32(E.snps_exc, ln + b, W::splat(0u), W::all());   /* snps + indels */
         for (uint32_t b = 0; b < CBC_BLOOM_WORDS; b += 64u) W::store32(E.bloom, ln + b, W::splat(0u), W::all());   /* the p = 0 arrays need no clearing */
     }
-    E.p0cnt = W::splat(0u); E.p0over = 0;
     E.snps_n = L0; E.indels_n = L0;
     E.rn_count = 0; E.rn_cap = CBC_CAP_NAME; E.vtab = nullptr;
     E.pos_card = 1u;                                         /* initialize_stream_model_pos :132-162: the escape */
     E.nev = 0; E.nev1 = 0;
-    E.fkey = W::splat(0u); E.fexc = W::splat(0u); E.fcount = 0;
-    E.hkey = W::splat(0u); E.hexc = W::splat(0u);
-    E.hc0 = E.hc1 = E.hc2 = E.hc3 = 0; E.hn0 = E.hn1 = E.hn2 = E.hn3 = 256u;
-    {   /* lane table: match 1,1 (n=2); same_ref 1,1; chars rows (sam_models.c:372-401) */
-        V32 sm = W::splat(0u);
-        sm = W::select(ln < 10u, W::splat(1u), sm);
-        V32 r = (ln - CBC_LT_CHARS) >> 3, c = (ln - CBC_LT_CHARS) & 7u;
-        Mask inch = (ln >= CBC_LT_CHARS) & (r < 6u) & (c < 5u);
-        V32 cv = W::select(c == 4u, W::splat(1u), W::select(c == r, W::splat(0u), W::splat(8u)));
-        /* +8 on two entries per row: A:{C,G} C:{A,T} G:{A,T} T:{C,G} */
-        Mask bump = ((r == 0u) & ((c == 1u) | (c == 2u))) | ((r == 1u) & ((c == 0u) | (c == 3u))) |
-                    ((r == 2u) & ((c == 0u) | (c == 3u))) | ((r == 3u) & ((c == 1u) | (c == 2u)));
-        cv = W::select(bump, cv + 8u, cv);
-        sm = W::select(inch, cv, sm);
-        E.small = sm;
-    }
-    E.prevPos = 0; E.prevM = 0; E.prevChar = 0; E.win_pos = 0;
-    E.win_clear();
+    E.start_models();
+    E.small = cbc_small_start<W>(10u);                       /* match 1,1 (n = 2) x 4, same_ref 1,1, the chars rows */
 
     const uint4 *recs4 = (const uint4 *)(A.recs + rec_base);
     const uint8_t *seqb = A.seq + seq_base;
@@ -2003,10 +1964,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
     auto gen_header = [&]() {
         for (uint32_t k = 0; k < 34u && E.status == CBC_ST_OK; k++) {
             uint32_t v = (k == 0u) ? L0 : (k == 33u) ? 8u : CBC_WELL_SEED;
-            E.regsparse_code(E.hkey, E.hexc, 0u, 8u, E.hc0, E.hn0, 256u, 1u, v >> 24, CBC_ST_ASSERT);
-            E.regsparse_code(E.hkey, E.hexc, 8u, 8u, E.hc1, E.hn1, 256u, 1u, (v >> 16) & 0xffu, CBC_ST_ASSERT);
-            E.regsparse_code(E.hkey, E.hexc, 16u, 8u, E.hc2, E.hn2, 256u, 1u, (v >> 8) & 0xffu, CBC_ST_ASSERT);
-            E.regsparse_code(E.hkey, E.hexc, 24u, 8u, E.hc3, E.hn3, 256u, 1u, v & 0xffu, CBC_ST_ASSERT);
+            E.code_int(v);
             if ((k & 7u) == 7u) E.drain();
         }
     };
@@ -2078,23 +2036,14 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         if (E.status == CBC_ST_OK) { gen_header(); E.seg_end(); }
         for (uint32_t c0 = 0; c0 < n_reads && E.status == CBC_ST_OK; c0 += 64u) {
             V32 r_pos, r_fl, r_seq, r_tok;
-            const uint32_t cn = n_reads - c0 < 64u ? n_reads - c0 : 64u;
             E.cur_read = c0;
-#ifndef CBC_MATCH_IN_MODEL
             /* the coder wavefront has validated the group and run the match test (post_group); everything this
              * wavefront still holds goes over first -- the coder may need it before it can post the next mask */
-            if (E.q_len) E.publish(0u, 0ull);
+            if (E.q_len) E.publish(0u);
             uint64_t neq;
             if (!E.wait_group(c0 >> 6, neq)) { E.fail(CBC_ST_ASSERT); break; }   /* the coder reports the record */
             load_group(c0, r_pos, r_fl, r_seq, r_tok, false);
-            CBC_TS(0);                                        /* group loads (+ match test) */
-#else
-            if (!load_group(c0, r_pos, r_fl, r_seq, r_tok, true)) break;
-            const uint64_t neq = match_group(cn, r_pos, r_fl, r_seq);
-            CBC_TS(0);                                        /* group loads + match test */
-            if (E.q_len) E.publish(0u, 0ull);                 /* a GROUP batch carries no symbols */
-            E.publish(CBC_BF_GROUP, neq);
-#endif
+            CBC_TS(0);                                        /* group loads */
             if (c0 == 0u) { gen_rname(); E.seg_end(); }
             typename CbcEnc<W>::Prep P;
             E.prep_group(P, neq, r_tok, tokb, n_tok_blk);
@@ -2151,7 +2100,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         if (E.cap_var >= 64u) for (int i = 0; i < 16; i++) {   /* diagnostic build: tail of the event area */
             W::write_uni(E.var_ev + E.cap_var - 32u, 2 * i, (uint32_t)E.t_sum[i]); W::write_uni(E.var_ev + E.cap_var - 32u, 2 * i + 1, (uint32_t)(E.t_sum[i] >> 32)); }
 #endif
-        E.publish(CBC_BF_LAST, 0ull);                         /* carries the status if a check failed */
+        E.publish(CBC_BF_LAST);                         /* carries the status if a check failed */
         return;
     }
 
@@ -2160,7 +2109,6 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
     /* the coder wavefront carries the block's serial chain: it goes first at the SIMD's issue port (s_setprio), the
      * model wavefronts that share the SIMD fill the gaps (cfg2 10.26 -> 9.91 ms, profiles/r02_ab_kernels.log run 9) */
     if (!fused) W::prio(CBC_PRIO_CODER);
-#ifndef CBC_MATCH_IN_MODEL
     /* validate a group and run its match test for both wavefronts; a refused group is posted as such (the model
      * wavefront then winds up) and fails this wavefront through load_group() */
     uint64_t neq_ahead = 0;
@@ -2176,7 +2124,6 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         if (okg) E.cur_read = saved;
     };
     if (!fused && n_reads != 0u && E.status == CBC_ST_OK) look_ahead(0u);
-#endif
     if (E.status == CBC_ST_OK) { if (fused) { gen_header(); E.seg_end(); } else E.seg_consume(); }
     for (uint32_t c0 = 0; c0 < n_reads && E.status == CBC_ST_OK; c0 += 64u) {
         V32 r_pos, r_fl, r_seq, r_tok;
@@ -2191,14 +2138,9 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
             neq = match_group(cn, r_pos, r_fl, r_seq);
             E.prep_group(P, neq, r_tok, tokb, n_tok_blk);
         } else {
-#ifndef CBC_MATCH_IN_MODEL
             neq = neq_ahead;                                  /* posted one group ago */
             if (c0 + 64u < n_reads) look_ahead(c0 + 64u);     /* before anything of this group is waited for */
             if (E.status != CBC_ST_OK) break;
-#else
-            neq = E.pull_group();                             /* the model wave has validated the group */
-            if (E.status != CBC_ST_OK) break;
-#endif
             load_group(c0, r_pos, r_fl, r_seq, r_tok, false);
         }
         typename CbcEnc<W>::Fixed F;
@@ -2218,12 +2160,8 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         const V32 m_hi = F.m_lo + F.m_cnt;
         const V32 m_fl = CBC_FRAC(F.m_lo, F.m_n), m_fh = CBC_FRAC(m_hi, F.m_n);
 
-#ifndef CBC_ENC_NO_PEEL      /* record 0 is its own instantiation of the body: its rare, branchy code stays out of the loop
-                             * (cfg2 encode 10.15 -> 9.06 ms, decode 30.4 -> 29.85 ms: profiles/r02_ab_kernels.log run 13) */
-#define CBC_ENC_FIRST(first, r) (decltype(first)::value)
-#else
-#define CBC_ENC_FIRST(first, r) ((r) == 0u)
-#endif
+        /* record 0 is its own instantiation of the body: its rare, branchy code stays out of the loop
+         * (cfg2 encode 10.15 -> 9.06 ms, decode 30.4 -> 29.85 ms: profiles/r02_ab_kernels.log run 13) */
         /* one record's symbols.  `first` = record 0 of the block (a compile-time flag: the loop body proper has no
          * special case in it, and nothing leaves the loop from inside -- every early exit costs the structurised
          * control flow a flag that is then tested at each join) */
@@ -2235,7 +2173,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
              *    after which only symbol 0 is coded; the name itself is the model wave's segment -- */
             E.room(8u);                                       /* same_ref, rlength x 4, pos, flag, match */
             const uint32_t tn = 255u + 10u * r;
-            if (CBC_ENC_FIRST(first, r)) {
+            if (decltype(first)::value) {
                 E.encode(1u, 1u, 2u); E.drain_q();
                 if (fused) { gen_rname(); E.seg_end(); } else E.seg_consume();
             }
@@ -2243,7 +2181,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
              *    pass; contexts 1..3 only ever code symbol 0, each once per record.  same_ref + rlength[0] and
              *    rlength[1..3] go through the two fused quiet steps, which code them one at a time unless an A/B build
              *    asks for the fused forms; record 0, whose same_ref is not symbol 0, calls the single steps -- */
-            if (CBC_ENC_FIRST(first, r)) {
+            if (decltype(first)::value) {
                 const uint32_t tf = W::readlane(t_fh, j);
                 E.step_fixed_quiet(CBC_LZ(W::readlane(F.rl_lo, j)), CBC_LZ(W::readlane(rl_hi, j)), CBC_LZ(tn), W::readlane(rl_fl, j), W::readlane(rl_fh, j));
                 E.step_known0(CBC_LZ(W::readlane(t_hi, j)), CBC_LZ(tn), tf);
@@ -2287,7 +2225,6 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         /* records up to the first one fixed_group() refused; that one reports its status after the loop */
         uint32_t jn = cn;
         if (F.bad) { const uint32_t fb = W::ctz64(F.bad); if (fb < cn) jn = fb; }
-#ifndef CBC_ENC_NO_PEEL
         /* ... and so is a record whose POS delta is new (escape + four byte symbols + a drain of the symbol queue, one
          * record in ~16): the records between two of them run through a body without that branch */
         typedef std::integral_constant<int, 0> Plain; typedef std::integral_constant<int, 1> Esc; typedef std::integral_constant<int, 2> Look;
@@ -2300,10 +2237,6 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
             for (; j < run_end && E.status == CBC_ST_OK; j++) code_record(j, std::false_type(), Plain());
             if (j < jn && E.status == CBC_ST_OK) { code_record(j, std::false_type(), Esc()); j++; }
         }
-#else
-        for (uint32_t j = 0; j < jn && E.status == CBC_ST_OK; j++) code_record(j, 0, std::integral_constant<int, 2>());
-#endif
-#undef CBC_ENC_FIRST
         if (jn < cn && E.status == CBC_ST_OK) { E.cur_read = c0 + jn; E.fail(W::readlane(F.st, jn)); }
     }
     /* ---- end-of-stream sentinel (compression.c:152): same_ref symbol 1 at counts (1 + 10 (n - 1), 11),
@@ -2318,11 +2251,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
     }
     if (E.status == CBC_ST_OK) { E.flush_recs(); nbytes = E.finish(); }
     if (E.status != CBC_ST_OK) nbytes = 0;
-#ifndef CBC_MATCH_IN_MODEL
-#ifndef CBC_MATCH_NO_ABORT_FOR_TEST
     if (!fused && E.status != CBC_ST_OK) E.abort_groups();
-#endif
-#endif
     if (!fused) E.pull_rest();
 #if defined(CBC_STAMP) && defined(__HIP_DEVICE_COMPILE__)
     if (payload_cap >= 128u) for (int i = 0; i < 16; i++) {   /* diagnostic build: over the payload start */

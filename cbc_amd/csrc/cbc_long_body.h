@@ -138,14 +138,8 @@ CBC_FN void cbc_long_encode(const cbc_long_args &A, uint32_t blk, uint32_t *lds)
     const uint64_t rec_base = bd->rec_base, seq_base = bd->seq_base, tok_base = bd->tok_base, ref_off = bd->ref_off, out_off = bd->out_off;
     const uint32_t out_cap = bd->out_cap, n_reads = bd->n_reads, name_off = bd->name_off, n_tok_blk = bd->n_tok;
 
-    E.status = CBC_ST_OK; E.nsym = 0; E.fail_read = 0; E.cur_read = 0;
-    E.l = W::uv(0u); E.set_l_forms(); E.rng = W::uv(CBC_M26 + 1u); E.scale3 = 0u; E.bitpos = 0; E.flushed = 0;
-    E.ring = lds + CBC_LLDS_RING;
-    E.q_lo = W::splat(0u); E.q_cnt = W::splat(0u); E.q_n = W::splat(0u); E.q_len = 0;
-    E.b_lo = W::splat(0u); E.b_hi = W::splat(0u); E.b_n = W::splat(1u); E.b_fl = W::splat(0u); E.b_fh = W::splat(0u);
-    E.rec_a = W::splat(0u); E.rec_s = W::splat(0u); E.rec_n = 0;
-    E.role = ROLE; E.batch_i = 0; E.batch = lds + CBC_LLDS_BATCH; E.ctl = lds + CBC_LLDS_CTL;
-    E.b_len = 0; E.b_pos = 0; E.b_stop = 64u; E.b_flags = 0; E.seen_last = 0; E.b_neq = 0;
+    E.start_coder(lds + CBC_LLDS_RING, true);
+    E.start_handoff(ROLE, lds + CBC_LLDS_BATCH, lds + CBC_LLDS_CTL);
     if (ROLE != CBC_ROLE_FUSED) {                            /* the only barrier: the hand-off counters start at zero for both */
         if (ROLE == CBC_ROLE_MODEL) for (uint32_t k = 0; k < 8u; k++) W::write_uni(E.ctl, k, 0u);
         W::barrier();
@@ -187,7 +181,6 @@ CBC_FN void cbc_long_encode(const cbc_long_args &A, uint32_t blk, uint32_t *lds)
     E.pos_val = lds + CBC_LLDS_FIXED; E.pos_occ = E.pos_val + A.cap_pos; E.pos_pre = nullptr; E.cap_pos = A.cap_pos;
     E.fsp_key = E.fsp_exc = nullptr; E.fsp_count = 0; E.pos_ov_val = E.pos_ov_occ = nullptr; E.pos_lds_cap = 0xffffffc0u; E.palpha = nullptr;
     E.bloom = nullptr; E.var_ev = nullptr; E.nev = E.nev1 = 0; E.cap_var = 0; E.vtab = nullptr; E.p0ev = nullptr;
-    E.p0cnt = W::splat(0u); E.p0over = 0;
     uint32_t *scr = A.scratch + (uint64_t)blk * CBC_LONG_SCRATCH_WORDS;
     if (ROLE != CBC_ROLE_WALKER) {                            /* the tables are the model wavefront's */
         for (uint32_t b = 0; b < CBC_LLDS_SP; b += 64u) W::store32(lds, ln + b, W::splat(0u), W::all());        /* gap symbols 0..63 */
@@ -196,20 +189,8 @@ CBC_FN void cbc_long_encode(const cbc_long_args &A, uint32_t blk, uint32_t *lds)
         W::write_uni(E.pos_val, 0u, 0xffffffffu); W::write_uni(E.pos_occ, 0u, 1u);
     }
     E.snps_n = 0; E.indels_n = 0; E.pos_card = 1u;
-    E.fkey = W::splat(0u); E.fexc = W::splat(0u); E.fcount = 0;
-    E.hkey = W::splat(0u); E.hexc = W::splat(0u);
-    E.hc0 = E.hc1 = E.hc2 = E.hc3 = 0; E.hn0 = E.hn1 = E.hn2 = E.hn3 = 256u;
-    {   /* lane table: kind contexts (lanes 0-5, 10-15) 1,1,1; same_ref 1,1 (lanes 8, 9); chars rows (16..63) */
-        V32 sm = W::select(ln < 16u, W::splat(1u), W::splat(0u));
-        V32 r = (ln - CBC_LT_CHARS) >> 3, c = (ln - CBC_LT_CHARS) & 7u;
-        Mask inch = (ln >= CBC_LT_CHARS) & (r < 6u) & (c < 5u);
-        V32 cv = W::select(c == 4u, W::splat(1u), W::select(c == r, W::splat(0u), W::splat(8u)));
-        Mask bump = ((r == 0u) & ((c == 1u) | (c == 2u))) | ((r == 1u) & ((c == 0u) | (c == 3u))) |
-                    ((r == 2u) & ((c == 0u) | (c == 3u))) | ((r == 3u) & ((c == 1u) | (c == 2u)));
-        cv = W::select(bump, cv + 8u, cv);
-        E.small = W::select(inch, cv, sm);
-    }
-    E.prevPos = 0; E.prevM = 0; E.prevChar = 0; E.win_pos = 0; E.win_clear();
+    E.start_models();
+    E.small = cbc_small_start<W>(16u);                        /* kind contexts (lanes 0-5, 10-15) 1,1,1; same_ref 1,1 (lanes 8, 9) */
     V32 ntab = W::splat(256u), lsum = W::splat(0u);            /* lane t < 8: total of gap table t, excess held by its symbols 0..63; lanes 8, 9: totals of gx */
     uint32_t flag_n = 65536u, pos_n = 1u;
     V32 spc = W::splat(0u);                                    /* entries of the six sparse lists, lane = list */
@@ -286,7 +267,7 @@ CBC_FN void cbc_long_encode(const cbc_long_args &A, uint32_t blk, uint32_t *lds)
         W::write_uni(tab, idx, (x << 24) | (cnt - 1u + 10u));
         if (!eq) spc = W::select(ln == list, W::splat(count + 1u), spc);
     };
-    auto code_int = [&](uint32_t v) {
+    auto code_int = [&](uint32_t v) {                          /* CbcEnc::code_int; as the member it changes this kernel's code */
         E.regsparse_code(E.hkey, E.hexc, 0u, 8u, E.hc0, E.hn0, 256u, 1u, v >> 24, CBC_ST_ASSERT);
         E.regsparse_code(E.hkey, E.hexc, 8u, 8u, E.hc1, E.hn1, 256u, 1u, (v >> 16) & 0xffu, CBC_ST_ASSERT);
         E.regsparse_code(E.hkey, E.hexc, 16u, 8u, E.hc2, E.hn2, 256u, 1u, (v >> 8) & 0xffu, CBC_ST_ASSERT);
@@ -733,7 +714,7 @@ CBC_FN void cbc_long_encode(const cbc_long_args &A, uint32_t blk, uint32_t *lds)
     if (ROLE == CBC_ROLE_MODEL && out_cap >= 512u) { CBC_TS(3); for (int i = 0; i < 16; i++) {      /* diagnostic build: payload area, second 128 bytes */
         W::write_uni(E.out32 + 32, 2 * i, (uint32_t)E.t_sum[i]); W::write_uni(E.out32 + 32, 2 * i + 1, (uint32_t)(E.t_sum[i] >> 32)); } }
 #endif
-    if (ROLE == CBC_ROLE_MODEL) { E.publish(CBC_BF_LAST, 0ull); return; }   /* with whatever is still queued, and this wavefront's status */
+    if (ROLE == CBC_ROLE_MODEL) { E.publish(CBC_BF_LAST); return; }   /* with whatever is still queued, and this wavefront's status */
     uint32_t nbytes = 0;
     if (E.status == CBC_ST_OK) E.drain_q();
     if (E.status == CBC_ST_OK) { E.flush_recs(); nbytes = E.finish(); }
@@ -758,8 +739,7 @@ CBC_FN void cbc_long_decode(const cbc_dec_args &A, uint32_t blk, uint32_t *lds)
     const uint64_t in_off = bd->in_off, ref_off = bd->ref_off, rec_base = bd->rec_base, seq_base = bd->seq_base;
     const uint32_t in_bytes = bd->in_bytes, n_reads = bd->n_reads, blk_bases = bd->reserved[0];
 
-    D.status = CBC_ST_OK; D.nsym = 0; D.fail_read = 0; D.cur_read = 0;
-    D.l = W::dv(0u); D.rng = W::dv(CBC_M26 + 1u); D.d = W::dv(0u); D.acc = 0; D.navail = 0; D.widx = 0; D.wordv = W::splat(0u);
+    D.start_coder();
     D.inb = A.in + in_off;
     D.lds = lds; D.cap_pos = A.cap_pos; D.cap_var = 0; D.L0 = 256u; D.evp = nullptr; D.vtab = nullptr;
     D.rname_key = lds + CBC_LLDS_RNKEY; D.rname_exc = lds + CBC_LLDS_RNEXC; D.rn_cap = CBC_CAP_NAME; D.histp = nullptr;
@@ -774,25 +754,9 @@ CBC_FN void cbc_long_decode(const cbc_dec_args &A, uint32_t blk, uint32_t *lds)
     for (uint32_t b = 0; b < CBC_LLDS_ROLE; b += 64u) W::store32(lds, ln + b, W::splat(0u), (ln + b) < CBC_LLDS_ROLE);
     if (args_ok) for (uint32_t b = 0; b < CBC_LONG_TABLE_WORDS; b += 64u)
         W::store32_list(A.var_scratch + (uint64_t)blk * CBC_LONG_TABLE_WORDS, ln + b, W::splat(0u), W::all());
-    D.rlen_n = 0; D.rl123_c0 = 0; D.rl123_n = 0; D.snps_n = 0; D.indels_n = 0; D.rn_count = 0;
-    D.pos_card = 1u; D.pos_n = 1u; D.nev = 0; D.nev1 = 0;
-    D.pval = W::splat(0xffffffffu); D.pcnt = W::select(ln == 0u, W::splat(1u), W::splat(0u));
-    D.fkey = W::splat(0u); D.fexc = W::splat(0u); D.fcount = 0; D.fn = 65536u;
-    D.hkey = W::splat(0u); D.hexc = W::splat(0u);
-    D.hc0 = D.hc1 = D.hc2 = D.hc3 = 0; D.hn0 = D.hn1 = D.hn2 = D.hn3 = 256u;
-    {
-        V32 s = W::select(ln < 16u, W::splat(1u), W::splat(0u));
-        V32 r = (ln - CBC_LT_CHARS) >> 3, c = (ln - CBC_LT_CHARS) & 7u;
-        Mask inch = (ln >= CBC_LT_CHARS) & (r < 6u) & (c < 5u);
-        V32 cv = W::select(c == 4u, W::splat(1u), W::select(c == r, W::splat(0u), W::splat(8u)));
-        Mask bump = ((r == 0u) & ((c == 1u) | (c == 2u))) | ((r == 1u) & ((c == 0u) | (c == 3u))) |
-                    ((r == 2u) & ((c == 0u) | (c == 3u))) | ((r == 3u) & ((c == 1u) | (c == 2u)));
-        cv = W::select(bump, cv + 8u, cv);
-        D.small = W::select(inch, cv, s);
-    }
-    D.prevPos = 0; D.prevM = 0; D.prevChar = 0; D.win_clear();
-    D.rl_memo_x = CBC_NOMEMO; D.rl_memo_lo = 0; D.rl_memo_cnt = 0; D.rl_last_x = 0;
-    D.p0cnt = W::splat(0u); D.p0over = 0;
+    D.rlen_n = 0; D.rl123_c0 = 0; D.rl123_n = 0; D.snps_n = 0; D.indels_n = 0;
+    D.start_models();
+    D.small = cbc_small_start<W>(16u);
     V32 ntab = W::splat(256u), lsum = W::splat(0u), spc = W::splat(0u);
     uint32_t *scr = A.var_scratch + (uint64_t)blk * CBC_LONG_TABLE_WORDS;
     /* the symbol of a dense table row in global memory whose cumulative interval holds tg; `first` = cum of the row's entry 0 */
@@ -892,7 +856,7 @@ CBC_FN void cbc_long_decode(const cbc_dec_args &A, uint32_t blk, uint32_t *lds)
         v |= D.regsparse_dec(D.hkey, D.hexc, 24u, 8u, D.hc3, D.hn3, 256u, 1u, CBC_ST_ASSERT);
         return v;
     };
-    if (D.status == CBC_ST_OK) D.d = W::dv(D.take(26u));
+    if (D.status == CBC_ST_OK) D.start_tag();
     if (D.status == CBC_ST_OK && dec_int() != CBC_LONG_MAGIC) D.fail(CBC_ST_UNSUPPORTED);
     if (D.status == CBC_ST_OK && dec_int() != 8u) D.fail(CBC_ST_UNSUPPORTED);
 

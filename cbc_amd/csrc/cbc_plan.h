@@ -23,9 +23,7 @@
 #define CBC_BATCH_SLOTS 2u                         /* encoder hand-off ring depth (power of two; 2 measured as good as 4) */
 #endif
 #define CBC_BATCH_WORDS 200u                       /* 64 lo + 64 cnt + 64 n + {len, flags, status, record, match mask x2} */
-#ifndef CBC_POS_IDX_WORDS
-#define CBC_POS_IDX_WORDS 256u                      /* 0: no index table (A/B) */
-#endif
+#define CBC_POS_IDX_WORDS 256u                     /* alphabet index of the small POS deltas (multiple of 64) */
 #define CBC_RING_WORDS  256u                       /* output bit ring of the coder wave (power of two) */
 #define CBC_RUN_WORDS   16u                        /* scratch of the encoder's SNP run pass: one byte per SNP lane, then the window's 8 words */
 /* encoder: tables, hand-off ring, its two counters (8 words), output ring, run-pass scratch; then 3 x cap_pos */

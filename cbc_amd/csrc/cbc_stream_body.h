@@ -93,13 +93,8 @@ CBC_FN void cbc_encode_whole(const cbc_stream_args &A, uint32_t stream, uint32_t
     const uint64_t out_off = first->out_off;
     const uint32_t out_cap = first->out_cap, L0 = first->read_length;
 
-    E.status = CBC_ST_OK; E.nsym = 0; E.fail_read = 0; E.cur_read = 0;
-    E.l = W::uv(0u); E.set_l_forms(); E.rng = W::uv(CBC_M26 + 1u); E.scale3 = 0u; E.bitpos = 0; E.flushed = 0;
-    E.ring = lds + CBC_SLDS_RING;
-    E.q_lo = W::splat(0u); E.q_cnt = W::splat(0u); E.q_n = W::splat(0u); E.q_len = 0;
-    E.rec_a = W::splat(0u); E.rec_s = W::splat(0u); E.rec_n = 0;
-    E.role = CBC_ROLE_FUSED; E.batch_i = 0; E.batch = nullptr; E.ctl = nullptr;
-    E.b_len = 0; E.b_pos = 0; E.b_stop = 64u; E.b_flags = 0; E.seen_last = 0; E.b_neq = 0;
+    E.start_coder(lds + CBC_SLDS_RING, false);
+    E.start_handoff(CBC_ROLE_FUSED, nullptr, nullptr);       /* one wavefront: no batch is ever published or pulled */
     E.out32 = (uint32_t *)(A.out + out_off);
     E.cap_words = out_cap >> 2;
     bool args_ok = cbc_fits64(out_off, out_cap, A.out_bytes) && ((out_off & 3u) == 0u) && (L0 >= 1u && L0 <= 256u) &&
@@ -124,33 +119,17 @@ CBC_FN void cbc_encode_whole(const cbc_stream_args &A, uint32_t stream, uint32_t
     for (uint32_t b = 0; b < CBC_SLDS_RING + CBC_RING_WORDS; b += 64u) W::store32(lds, ln + b, W::splat(0u), W::all());
     for (uint32_t b = 0; b < 1024u; b += 64u) W::store32(lds + CBC_SLDS_PALPHA, ln + b, W::splat(0u), W::all());
     W::write_uni(E.pos_val, 0u, 0xffffffffu); W::write_uni(E.pos_occ, 0u, 1u);      /* the escape: counts[0] = 1 (sam_models.c:132-162) */
-    E.p0cnt = W::splat(0u); E.p0over = 0; E.p0ev = nullptr;
+    E.p0ev = nullptr;
     E.snps_n = L0; E.indels_n = L0;
     E.pos_card = 1u;
-    E.fkey = W::splat(0u); E.fexc = W::splat(0u); E.fcount = 0;
-    E.hkey = W::splat(0u); E.hexc = W::splat(0u);
-    E.hc0 = E.hc1 = E.hc2 = E.hc3 = 0; E.hn0 = E.hn1 = E.hn2 = E.hn3 = 256u;
-    {   /* lane table: match 1,1; same_ref 1,1; chars rows (sam_models.c:372-401) -- as in cbc_encode_stream */
-        V32 sm = W::select(ln < 10u, W::splat(1u), W::splat(0u));
-        V32 r = (ln - CBC_LT_CHARS) >> 3, c = (ln - CBC_LT_CHARS) & 7u;
-        Mask inch = (ln >= CBC_LT_CHARS) & (r < 6u) & (c < 5u);
-        V32 cv = W::select(c == 4u, W::splat(1u), W::select(c == r, W::splat(0u), W::splat(8u)));
-        Mask bump = ((r == 0u) & ((c == 1u) | (c == 2u))) | ((r == 1u) & ((c == 0u) | (c == 3u))) |
-                    ((r == 2u) & ((c == 0u) | (c == 3u))) | ((r == 3u) & ((c == 1u) | (c == 2u)));
-        cv = W::select(bump, cv + 8u, cv);
-        E.small = W::select(inch, cv, sm);
-    }
-    E.prevPos = 0; E.prevM = 0; E.prevChar = 0; E.win_pos = 0;
-    E.win_clear();
+    E.start_models();
+    E.small = cbc_small_start<W>(10u);
     uint32_t rlen_n = 255u, rl123_c0 = 1u, rl123_n = 255u, flag_n = 65536u, pos_n = 1u;
 
     /* stream header: int(L0), 32 x int(WELL), int(LOSSLESS) */
     for (uint32_t k = 0; k < 34u && E.status == CBC_ST_OK; k++) {
         uint32_t v = (k == 0u) ? L0 : (k == 33u) ? 8u : CBC_WELL_SEED;
-        E.regsparse_code(E.hkey, E.hexc, 0u, 8u, E.hc0, E.hn0, 256u, 1u, v >> 24, CBC_ST_ASSERT);
-        E.regsparse_code(E.hkey, E.hexc, 8u, 8u, E.hc1, E.hn1, 256u, 1u, (v >> 16) & 0xffu, CBC_ST_ASSERT);
-        E.regsparse_code(E.hkey, E.hexc, 16u, 8u, E.hc2, E.hn2, 256u, 1u, (v >> 8) & 0xffu, CBC_ST_ASSERT);
-        E.regsparse_code(E.hkey, E.hexc, 24u, 8u, E.hc3, E.hn3, 256u, 1u, v & 0xffu, CBC_ST_ASSERT);
+        E.code_int(v);
         if ((k & 7u) == 7u) E.drain_q();
     }
     E.drain_q();
@@ -294,13 +273,11 @@ template <class W>
 CBC_FN void cbc_decode_whole(const cbc_dstream_args &A, uint32_t *lds)
 {
     typedef typename W::V32 V32;
-    typedef typename W::Mask Mask;
     const V32 ln = W::lane();
     CbcDec<W, true> D;
     const uint32_t L0 = A.read_length, stride = A.seq_stride;
 
-    D.status = CBC_ST_OK; D.nsym = 0; D.fail_read = 0; D.cur_read = 0;
-    D.l = W::dv(0u); D.rng = W::dv(CBC_M26 + 1u); D.d = W::dv(0u); D.acc = 0; D.navail = 0; D.widx = 0; D.wordv = W::splat(0u);
+    D.start_coder();
     D.inb = A.in;
     D.lds = lds; D.cap_pos = A.cap_pos; D.cap_var = 0; D.L0 = L0; D.evp = nullptr;
     D.rname_key = lds + CBC_SLDS_FIXED; D.rname_exc = D.rname_key + A.cap_name; D.rn_cap = A.cap_name;
@@ -317,34 +294,18 @@ CBC_FN void cbc_decode_whole(const cbc_dstream_args &A, uint32_t *lds)
     D.tail_valid = (uint32_t)A.in_bytes & 3u;
     if (!args_ok) { D.nwords_in = 0; D.fail(CBC_ST_ASSERT); }
     for (uint32_t b = 0; b < CBC_SLDS_FIXED; b += 64u) W::store32(lds, ln + b, W::splat(0u), (ln + b) < CBC_SLDS_FIXED);
-    D.rlen_n = 255u; D.rl123_c0 = 1u; D.rl123_n = 255u; D.snps_n = L0; D.indels_n = L0; D.rn_count = 0;
-    D.pos_card = 1u; D.pos_n = 1u; D.nev = 0; D.nev1 = 0;
-    D.pval = W::splat(0xffffffffu); D.pcnt = W::select(ln == 0u, W::splat(1u), W::splat(0u));
-    D.fkey = W::splat(0u); D.fexc = W::splat(0u); D.fcount = 0; D.fn = 65536u;
-    D.hkey = W::splat(0u); D.hexc = W::splat(0u);
-    D.hc0 = D.hc1 = D.hc2 = D.hc3 = 0; D.hn0 = D.hn1 = D.hn2 = D.hn3 = 256u;
-    {
-        V32 s = W::select(ln < 10u, W::splat(1u), W::splat(0u));
-        V32 r = (ln - CBC_LT_CHARS) >> 3, c = (ln - CBC_LT_CHARS) & 7u;
-        Mask inch = (ln >= CBC_LT_CHARS) & (r < 6u) & (c < 5u);
-        V32 cv = W::select(c == 4u, W::splat(1u), W::select(c == r, W::splat(0u), W::splat(8u)));
-        Mask bump = ((r == 0u) & ((c == 1u) | (c == 2u))) | ((r == 1u) & ((c == 0u) | (c == 3u))) |
-                    ((r == 2u) & ((c == 0u) | (c == 3u))) | ((r == 3u) & ((c == 1u) | (c == 2u)));
-        cv = W::select(bump, cv + 8u, cv);
-        D.small = W::select(inch, cv, s);
-    }
-    D.prevPos = 0; D.prevM = 0; D.prevChar = 0; D.win_clear();
-    D.rl_memo_x = CBC_NOMEMO; D.rl_memo_lo = 0; D.rl_memo_cnt = 0; D.rl_last_x = 0;
-    D.p0cnt = W::splat(0u); D.p0over = 0;
-
-    if (D.status == CBC_ST_OK) D.d = W::dv(D.take(26u));                 /* the tag (alloc_arithmetic_stream :260-263) */
-    for (uint32_t k = 0; k < 34u && D.status == CBC_ST_OK; k++) {  /* header: int(L0), 32 x int(WELL), int(8) */
+    D.rlen_n = 255u; D.rl123_c0 = 1u; D.rl123_n = 255u; D.snps_n = L0; D.indels_n = L0;
+    D.start_models();
+    D.small = cbc_small_start<W>(10u);
+    if (D.status == CBC_ST_OK) D.start_tag();
+    /* stream header: int(L0), 32 x int(WELL), int(8) */
+    for (uint32_t k = 0; k < 34u && D.status == CBC_ST_OK; k++) {
         uint32_t v = D.regsparse_dec(D.hkey, D.hexc, 0u, 8u, D.hc0, D.hn0, 256u, 1u, CBC_ST_ASSERT) << 24;
         v |= D.regsparse_dec(D.hkey, D.hexc, 8u, 8u, D.hc1, D.hn1, 256u, 1u, CBC_ST_ASSERT) << 16;
         v |= D.regsparse_dec(D.hkey, D.hexc, 16u, 8u, D.hc2, D.hn2, 256u, 1u, CBC_ST_ASSERT) << 8;
         v |= D.regsparse_dec(D.hkey, D.hexc, 24u, 8u, D.hc3, D.hn3, 256u, 1u, CBC_ST_ASSERT);
         if (D.status != CBC_ST_OK) break;
-        if (k == 0u && v != L0) D.fail(CBC_ST_ASSERT);
+        if (k == 0u && v != L0) D.fail(CBC_ST_ASSERT);            /* container and stream disagree */
         if (k == 33u && v != 8u) D.fail(CBC_ST_UNSUPPORTED);       /* LOSSY streams are out of scope */
     }
 

@@ -5,7 +5,10 @@
 # run, with --kernel-trace only: MI355X_MICROARCH.md, HBM / rocprofv3 section).  The pmc JSON is stamped with the sha of the
 # kernel sources (bench.py kernel_source_sha): bench.py reports a pass only for the build it was taken from.
 # Copy what should be judged into profiles/ and name it in profiles/CURRENT.json.
-set -e
+# Every step that uses the GPU runs under a time limit of its own (T_BENCH / T_TRACE / T_PMC seconds, a few times what the step
+# takes on a healthy box) and a step that fails or runs out of time ends the script: nothing more is started on the card.
+set -e -o pipefail
+T_BENCH=${T_BENCH:-420}; T_TRACE=${T_TRACE:-300}; T_PMC=${T_PMC:-240}
 tag=$1
 legs=${2:-all}
 [ "$legs" = all ] && legs="encode decode"
@@ -21,15 +24,16 @@ for leg in $legs; do
     *) echo "unknown leg $leg"; exit 2 ;;
   esac
   P=$O/${tag}_${leg}
-  python3 $R/bench.py $args --full --no-e2e > ${P}_bench.log 2>&1; tail -1 ${P}_bench.log > ${P}_bench.json
+  timeout -k 10 $T_BENCH python3 $R/bench.py $args --full --no-e2e > ${P}_bench.log 2>&1 || { echo "bench failed or timed out (see ${P}_bench.log)"; exit 1; }
+  tail -1 ${P}_bench.log > ${P}_bench.json
   rm -rf $O/prof_${tag}_${leg}
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${tag}_${leg} -o p -- python3 $R/bench.py $args --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > ${P}_rp.log 2>&1
-  tail -1 ${P}_rp.log > ${P}_bench_under_rocprof.json
+  timeout -k 10 $T_TRACE rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${tag}_${leg} -o p -- python3 $R/bench.py $args --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > ${P}_rp.log 2>&1 || { echo "kernel trace failed or timed out (see ${P}_rp.log)"; exit 1; }
+  grep '^{"metric"' ${P}_rp.log | tail -1 > ${P}_bench_under_rocprof.json      # rocprofv3 may print its own lines after the bench line
   cp $(find $O/prof_${tag}_${leg} -name '*kernel_stats.csv' | head -1) ${P}_kernel_stats.csv
   for c in FETCH_SIZE WRITE_SIZE "SQ_INSTS_SALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVES" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VALU" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAIT_INST_LDS"; do
     d=$O/pmc_${tag}_${leg}_$(echo $c | tr ' ' '_' | cut -c1-20)
     rm -rf $d
-    rocprofv3 --pmc $c --kernel-trace --output-format csv -d $d -o p -- python3 $R/bench.py $args --steps 2 --warmup 1 --no-cpu-baseline --no-e2e > $d.log 2>&1 || echo "counter pass '$c' failed (see $d.log)"
+    timeout -k 10 $T_PMC rocprofv3 --pmc $c --kernel-trace --output-format csv -d $d -o p -- python3 $R/bench.py $args --steps 2 --warmup 1 --no-cpu-baseline --no-e2e > $d.log 2>&1 || { echo "counter pass '$c' failed or timed out (see $d.log)"; exit 1; }
   done
   python3 - "$tag" "$leg" "$kern" <<'PY'
 import csv, glob, sys, os, json, collections
