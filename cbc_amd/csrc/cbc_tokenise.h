@@ -1,5 +1,5 @@
 /*
- * cbc_tokenise.h -- SAM text -> packed records ON THE DEVICE, included by cbc_gpu.hip.
+ * cbc_tokenise.h -- SAM text -> packed records ON THE DEVICE, included by cbc_gpu_tok.hip.
  *
  * The text goes up once (2.4 bytes per base), the bases and tokens are produced where the encoder reads them, and
  * what comes back to the host is 20 bytes per record for the serial part of packing (block cutting, contig

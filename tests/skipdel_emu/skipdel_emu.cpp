@@ -17,7 +17,7 @@ extern "C" __attribute__((visibility("default")))
 int emu_skipdel_decode(const cbc_dec_device_batch *b, uint32_t smax, uint32_t per_read, uint32_t *side, uint16_t *arena)
 { return emu_decode_blocks<WP, true, true>(b, smax, per_read, side, arena); }
 
-/* the library's bound on the change points (post_sizes_of in cbc_gpu.hip): per_read == 0 is the span depth's */
+/* the library's bound on the change points (post_sizes_of in cbc_gpu_post.hip): per_read == 0 is the span depth's */
 extern "C" __attribute__((visibility("default")))
 uint64_t emu_skipdel_cp_cap(uint64_t d_words, uint64_t n_recs, uint32_t n_iv, uint32_t per_read)
 {

@@ -1,5 +1,6 @@
 # per-section s_memtime sums of the long-read encoder's model and coder wavefronts from a -DCBC_STAMP build (scratch/abl/lib_stamp.so):
-#   hipcc -O3 --offload-arch=gfx950 -fPIC -fvisibility=hidden -ffp-contract=off -DCBC_STAMP -shared -o scratch/abl/lib_stamp.so cbc_amd/csrc/cbc_gpu.hip
+#   hipcc -O3 --offload-arch=gfx950 -fPIC -fvisibility=hidden -ffp-contract=off -DCBC_STAMP -shared -o scratch/abl/lib_stamp.so cbc_amd/csrc/cbc_gpu*.hip -ldl
+#   (every translation unit of the library on one line: cbc_gpu.hip, which holds the stamped kernels, cbc_gpu_post.hip, cbc_gpu_tok.hip)
 import sys, os, ctypes
 R=os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0,R)
 os.environ['CBC_GPU_LIB']=R+'/scratch/abl/'+os.environ.get('STAMP_LIB','lib_stamp.so')
