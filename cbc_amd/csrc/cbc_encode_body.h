@@ -107,6 +107,36 @@ extern "C" void cbc_path_mute(int on);                         /* the cross-chec
 #define CBC_COUNT_MUTE(on) do {} while (0)
 #endif
 
+/* CBC_VAR_COUNTS: host (emulation) build only -- what var_code() did, per block and strand, read through emu_var_counts()
+ * of tests/emu/emu_varpaths.cpp; cbc_var_hot_off() is that build's switch back to the form without the hot table.  The
+ * device code carries no counter and no switch. */
+enum {
+    CBC_VC_CALLS, CBC_VC_P0,                 /* var_code() calls that reach a lookup; those of the p = 0 class (hot ones included) */
+    CBC_VC_HOT,                              /* calls answered by the hot context's count table */
+    CBC_VC_FULL,                             /* p = 0 calls that found their bucket full */
+    CBC_VC_BLOOM,                            /* calls through the Bloom branch */
+    CBC_VC_SCAN, CBC_VC_SCAN_P0,             /* calls that scanned the global event list; the p = 0 calls among them */
+    CBC_VC_N
+};
+#if defined(CBC_VAR_COUNTS) && !defined(__HIP_DEVICE_COMPILE__)
+extern "C" void cbc_var_count(uint32_t what, uint32_t strand);
+extern "C" void cbc_var_block(uint32_t blk);
+extern "C" int cbc_var_hot_off(void);
+#define CBC_VCOUNT(what, strand) cbc_var_count((what), (strand))
+#define CBC_VBLOCK(blk) cbc_var_block(blk)
+#define CBC_VAR_HOT_OFF() (cbc_var_hot_off() != 0)
+#else
+#define CBC_VCOUNT(what, strand) do {} while (0)
+#define CBC_VBLOCK(blk) do {} while (0)
+#define CBC_VAR_HOT_OFF() false
+#endif
+
+/* the hot var context of the block kernels as a count table in registers (CbcEnc::hot_code).  -DCBC_HOT_CTX=0: A/B build,
+ * every context through the buckets and lists. */
+#ifndef CBC_HOT_CTX
+#define CBC_HOT_CTX 1
+#endif
+
 struct cbc_enc_args {
     const cbc_read_rec   *recs;
     const uint8_t        *seq;
@@ -126,15 +156,23 @@ struct cbc_enc_args {
 #define CBC_T0() do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); E.t_last = t_; } while (0)
 #define CBC_TS(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); E.t_sum[k] += t_ - E.t_last; E.t_last = t_; } while (0)
 #define CBC_TSM(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); t_sum[k] += t_ - t_last; t_last = t_; } while (0)
+/* a section inside a stamped section: its own start time, t_last untouched, so the outer sum still holds the whole */
+#define CBC_TN0(v) unsigned long long v; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
+#define CBC_TN(v, k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); t_sum[k] += t_ - v; } while (0)
 #elif defined(CBC_MARKS) && defined(__HIP_DEVICE_COMPILE__)   /* diagnostic: section markers in the ISA listing */
 #define CBC_TSM(k) asm volatile("; ==== CBC_MARK M" #k)
+#define CBC_TN0(v) asm volatile("; ==== CBC_MARK N0")
+#define CBC_TN(v, k) asm volatile("; ==== CBC_MARK N" #k)
 #define CBC_T0() asm volatile("; ==== CBC_MARK start")
 #define CBC_TS(k) asm volatile("; ==== CBC_MARK " #k)
 #else
 #define CBC_T0() do {} while (0)
 #define CBC_TS(k) do {} while (0)
 #define CBC_TSM(k) do {} while (0)
+#define CBC_TN0(v) do {} while (0)
+#define CBC_TN(v, k) do {} while (0)
 #endif
+#define CBC_STAMP_SLOTS 18          /* 0 .. 15: sections of the two wavefronts; 16, 17: inside var_code (tools/stamp.py names them) */
 
 /* bytes readable from offset `off` of a buffer with `total` bytes, clamped to 32 bits */
 /* a <= b for 64-bit values using 32-bit compares only: gfx950's scalar ALU has no ordered 64-bit
@@ -234,8 +272,10 @@ CBC_FN typename W::V32 cbc_small_start(uint32_t ones)
 template <class W, class = void> struct CbcHasLaneN : std::false_type {};
 template <class W> struct CbcHasLaneN<W, std::void_t<decltype(&W::set_lane2_uv), decltype(&W::set_lane3)>> : std::true_type {};
 
-template <class W, bool GEN = false>
+/* HOT (block kernels only, never with GEN): the block's dominant var context as a count table in registers, see hot_code() */
+template <class W, bool GEN = false, bool HOT = false>
 struct CbcEnc {
+    static_assert(!(GEN && HOT), "the hot var context belongs to the block kernels");
     typedef typename W::V32 V32;
     typedef typename W::Mask Mask;
 
@@ -275,7 +315,7 @@ struct CbcEnc {
     uint64_t b_neq;                         /* words 4, 5 of a batch header: the match mask of the retired GROUP batches; nothing sends or reads it */
     V32 rec_a, rec_s; uint32_t rec_n;       /* output of the coder steps not packed yet (see pack())   */
 #ifdef CBC_STAMP
-    unsigned long long t_last, t_sum[16];
+    unsigned long long t_last, t_sum[CBC_STAMP_SLOTS];
 #endif
 
     /* ---- models ---- */
@@ -299,6 +339,10 @@ struct CbcEnc {
     uint32_t nev, nev1, cap_var;             /* var events of strand 0 (from the bottom of the area) / strand 1 (from the top) */
     V32 p0cnt; uint32_t p0over;              /* p = 0 contexts: events held per (strand, d & 7) bucket, lane = strand * 8 + bucket; bit = that bucket spilled to the global list */
     uint32_t L0;
+    /* HOT: the context "first edit of a full-length read, no known SNP ahead" (d = L0 + 2, one per strand) as dense 16-bit
+     * counts: symbol s in lane s & 63, field s >> 6 of the strand's (a: fields 0, 1; b: fields 2, 3); its uses so far;
+     * hot_key = (L0 + 2) << 8, or a value no context has where L0 + 2 reaches the unused-half marker 255 */
+    V32 hot_a0, hot_b0, hot_a1, hot_b1; uint32_t hot_n0, hot_n1, hot_key;
 
     /* ---- cross-read state (T7/T8 of SURVEY.md) ---- */
     uint32_t prevPos, prevM, prevChar, win_pos;
@@ -331,6 +375,10 @@ struct CbcEnc {
         hkey = W::splat(0u); hexc = W::splat(0u);
         hc0 = hc1 = hc2 = hc3 = 0; hn0 = hn1 = hn2 = hn3 = 256u;
         p0cnt = W::splat(0u); p0over = 0;
+        if constexpr (HOT) {
+            hot_a0 = W::splat(0u); hot_b0 = W::splat(0u); hot_a1 = W::splat(0u); hot_b1 = W::splat(0u); hot_n0 = 0; hot_n1 = 0;
+            hot_key = (L0 + 2u <= 254u && !CBC_VAR_HOT_OFF()) ? (L0 + 2u) << 8 : 0xffffffffu;
+        }
         prevPos = 0; prevM = 0; prevChar = 0; win_pos = 0;
         win_clear();
     }
@@ -1448,10 +1496,49 @@ struct CbcEnc {
             }
         }
     }
+    /* HOT: the block's dominant context, d = L0 + 2 -- the first edit of a full-length read with no known SNP ahead, a
+     * fifth of a cfg2 block's var symbols -- never enters a bucket, the filter or a list: its statistics
+     * are the dense count table of the strand (hot_a / hot_b, 16-bit fields) and its number of uses.  n is the use count,
+     * the symbol's own count one readlane and a field extract, the counts below it a masked add of the four fields of each
+     * lane and one wave sum; the update is an add under a one-lane mask.  No LDS, no global memory, no hash.
+     * Bound: a field and every sum of fields is at most the use count n, and a call at n = 0xfffe is refused, so
+     * nothing wraps.  Packed input uses the context at most once per record (p = 0 is a record's first SNP; the other
+     * routes to this context number, p = 128 at d = L0 + 1, need a read of L0 - 1 bases) and a block holds at most
+     * CBC_MAX_BLOCK_READS = 16384 records; only crafted tokens can reach the guard.  The events do not count against cap_var. */
+    CBC_MFN void hot_code(V32 &a, V32 &b, uint32_t &n, uint32_t sym)
+    {
+        if (n >= 0xfffeu) { fail(CBC_ST_ASSERT); return; }
+        const V32 ln = W::lane();
+        const uint32_t q = sym >> 6, r = sym & 63u;             /* sym < L0 <= 256: q <= 3 */
+        const uint32_t w = (q & 2u) ? W::readlane(b, r) : W::readlane(a, r);
+        const uint32_t ceq = (w >> ((q & 1u) * 16u)) & 0xffffu;
+        /* the fields below sym: q of them in every lane, field q as well in the lanes below r */
+        const uint64_t m_all = (1ull << (16u * q)) - 1ull, m_low = (m_all << 16) | 0xffffull;
+        const Mask low = ln < r;
+        const V32 fa = a & W::select(low, W::splat((uint32_t)m_low), W::splat((uint32_t)m_all));
+        const V32 fb = b & W::select(low, W::splat((uint32_t)(m_low >> 32)), W::splat((uint32_t)(m_all >> 32)));
+        const uint32_t clo = W::reduce_add((fa & 0xffffu) + (fa >> 16) + (fb & 0xffffu) + (fb >> 16));
+        W::expect_eq((clo + ceq <= n && n < 0xffffu) ? 1u : 0u, 1u, "hot var context: a count above the use count");
+        encode(sym + 10u * clo, 1u + 10u * ceq, L0 + 10u * n);
+        const uint32_t inc = 1u << ((q & 1u) * 16u);
+        const Mask one = ln == r;
+        a = a + W::select(one, W::splat((q & 2u) ? 0u : inc), W::splat(0u));
+        b = b + W::select(one, W::splat((q & 2u) ? inc : 0u), W::splat(0u));
+        n++;
+    }
     CBC_MFN void var_code(uint32_t ctx, uint32_t sym)
     {
         if (ctx >= CBC_NVARCTX || sym >= L0) { fail(CBC_ST_ASSERT); return; }
         if (GEN) { var_code_dense(ctx, sym); return; }
+        CBC_VCOUNT(CBC_VC_CALLS, ctx & 1u);
+        if constexpr (HOT) {
+            if ((ctx & ~1u) == hot_key) {
+                CBC_VCOUNT(CBC_VC_P0, ctx & 1u); CBC_VCOUNT(CBC_VC_HOT, ctx & 1u);
+                if (ctx & 1u) hot_code(hot_a1, hot_b1, hot_n1, sym);
+                else hot_code(hot_a0, hot_b0, hot_n0, sym);
+                return;
+            }
+        }
         /* Two classes of contexts (the class is a function of the context number alone):
          *  - "p = 0": (ctx >> 1) & 127 == 0 and ctx >> 8 < 255, i.e. ctx = d << 8 | strand -- the FIRST edit of a read, with the
          *    distance d to the first known SNP ahead.  With a few percent of the reference positions marked by
@@ -1471,6 +1558,7 @@ struct CbcEnc {
         const uint32_t bkt = strand1 * 8u + ((ctx >> 8) & 7u);   /* the context's bucket: strand, d & 7 */
         uint32_t have = 0, half_word = 0;                      /* the bucket's last word when its upper half is free */
         if (p0class) {
+            CBC_VCOUNT(CBC_VC_P0, strand1);
             const uint32_t d = ctx >> 8, key16 = (d << 8) | sym;
             const uint32_t *arr = p0ev + bkt * CBC_P0_BUCKET_WORDS;
             have = W::readlane(p0cnt, bkt);
@@ -1485,16 +1573,22 @@ struct CbcEnc {
                                                        W::select(e1 == key16, W::splat(1u << 20), W::splat(0u)), W::splat(0u));
             const uint32_t tot = W::reduce_add(acc);
             cn = tot & 1023u; clo = (tot >> 10) & 1023u; ceq = tot >> 20;
-            if (have >= CBC_P0_CAP) to_global = 1u;
+            if (have >= CBC_P0_CAP) { to_global = 1u; CBC_VCOUNT(CBC_VC_FULL, strand1); }
         }
         uint32_t h1 = 0, h2 = 0, bw1 = 0, bw2 = 0, bb1 = 0, bb2 = 0;
         if ((to_global | ((p0over >> bkt) & 1u)) != 0u) {
+            CBC_VCOUNT(CBC_VC_BLOOM, strand1);
+            CBC_TN0(tb_);
             /* two hash functions, both words fetched by one LDS instruction (lanes 0 and 1) */
             h1 = (ctx * 0x9E3779B1u) >> (32u - CBC_BLOOM_LOG2); h2 = (ctx * 0x85EBCA6Bu + 0x27D4EB2Fu) >> (32u - CBC_BLOOM_LOG2);
             const V32 bwv = W::load32(bloom, W::select(ln == 0u, W::splat(h1 >> 5), W::splat(h2 >> 5)), ln < 2u, 0u);
             bw1 = W::readlane(bwv, 0u); bw2 = W::readlane(bwv, 1u);
             bb1 = 1u << (h1 & 31u); bb2 = 1u << (h2 & 31u);
+            CBC_TN(tb_, 16);                                  /* the Bloom branch up to the filter test */
             if ((bw1 & bb1) && (bw2 & bb2)) {
+                CBC_VCOUNT(CBC_VC_SCAN, strand1);
+                if (p0class) CBC_VCOUNT(CBC_VC_SCAN_P0, strand1);
+                CBC_TN0(ts_);
                 W::list_fence();
                 /* the context's strand bit picks the list: strand 0 grows up from the bottom of the event area,
                  * strand 1 down from its top, so a scan reads half of the block's events and the two share the
@@ -1514,6 +1608,7 @@ struct CbcEnc {
                         }
                     }
                 }
+                CBC_TN(ts_, 17);                              /* the scan of the global list */
             }
         }
         encode(sym + 10u * clo, 1u + 10u * ceq, L0 + 10u * cn);
@@ -1881,7 +1976,8 @@ struct CbcEnc {
  * cbc_encode_stream: code block `blk` completely.  `lds` = this wavefront's table memory
  * (cbc_gpu_lds_bytes() bytes).
  * =========================================================================================== */
-template <class W, uint32_t ROLE>
+/* HOT: CbcEnc's hot var context in registers; the block kernel cut for six wavefronts per SIMD has no register to spare for it */
+template <class W, uint32_t ROLE, bool HOT = (CBC_HOT_CTX != 0)>
 CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds)
 {
     const uint32_t role = ROLE;
@@ -1889,7 +1985,9 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
     typedef typename W::Mask Mask;
     const V32 ln = W::lane();
     const cbc_block_desc *bd = A.blocks + blk;
-    CbcEnc<W> E;
+    typedef CbcEnc<W, false, HOT> Enc;
+    Enc E;
+    CBC_VBLOCK(blk);
 
     /* ---- block descriptor (uniform) ---- */
     const uint64_t rec_base = bd->rec_base, seq_base = bd->seq_base, tok_base = bd->tok_base;
@@ -1954,7 +2052,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
     const uint64_t ref_avail = cbc_le64(ref_off, A.ref_bytes) ? A.ref_bytes - ref_off : 0;
     const uint32_t seq_lim = cbc_avail32(seq_avail, 0u), ref_lim = cbc_avail32(ref_avail, 0u);
 #ifdef CBC_STAMP
-    for (int i = 0; i < 16; i++) E.t_sum[i] = 0;
+    for (int i = 0; i < CBC_STAMP_SLOTS; i++) E.t_sum[i] = 0;
     CBC_T0();
 #endif
 
@@ -2045,7 +2143,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
             load_group(c0, r_pos, r_fl, r_seq, r_tok, false);
             CBC_TS(0);                                        /* group loads */
             if (c0 == 0u) { gen_rname(); E.seg_end(); }
-            typename CbcEnc<W>::Prep P;
+            typename Enc::Prep P;
             E.prep_group(P, neq, r_tok, tokb, n_tok_blk);
             CBC_TS(14);                                       /* group pass */
             /* Runs of ordinary records (P.ord) go through run_pass() and a loop whose body holds no CIGAR walk, no header
@@ -2064,7 +2162,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
             auto prefetch_if_general = [&](uint64_t rest) {
                 if (rest) { const uint32_t jn = W::ctz64(rest); if (!((P.ord >> jn) & 1ull)) prefetch(jn); }
             };
-            typename CbcEnc<W>::Run R;
+            typename Enc::Run R;
             R.pk = W::splat(0u); R.ca = R.pk; R.cb = R.pk; R.rm = 0ull; R.s = 0u; R.counted = 0u;
             while (todo && E.status == CBC_ST_OK) {
                 const uint32_t j = W::ctz64(todo);
@@ -2088,7 +2186,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
                 E.cur_read = c0 + j;
                 const V32 seqv = nx_seq, tokv = nx_tok;
                 prefetch_if_general(todo);
-                const typename CbcEnc<W>::PrepRec pr = { W::readlane(P.lo, j), W::readlane(P.cnt, j) };
+                const typename Enc::PrepRec pr = { W::readlane(P.lo, j), W::readlane(P.cnt, j) };
                 E.edits(W::readlane(r_pos, j), W::readlane(r_fl, j), W::readlane(r_tok, j), seqv, tokv, tokb, n_tok_blk, pr);
                 E.seg_end_fits();
                 CBC_TS(1);
@@ -2097,8 +2195,8 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         }
         if (E.status == CBC_ST_OK) { gen_sentinel(); E.seg_end(); }
 #if defined(CBC_STAMP) && defined(__HIP_DEVICE_COMPILE__)
-        if (E.cap_var >= 64u) for (int i = 0; i < 16; i++) {   /* diagnostic build: tail of the event area */
-            W::write_uni(E.var_ev + E.cap_var - 32u, 2 * i, (uint32_t)E.t_sum[i]); W::write_uni(E.var_ev + E.cap_var - 32u, 2 * i + 1, (uint32_t)(E.t_sum[i] >> 32)); }
+        if (E.cap_var >= 64u) for (int i = 0; i < CBC_STAMP_SLOTS; i++) {   /* diagnostic build: tail of the event area */
+            W::write_uni(E.var_ev + E.cap_var - 2u * CBC_STAMP_SLOTS, 2 * i, (uint32_t)E.t_sum[i]); W::write_uni(E.var_ev + E.cap_var - 2u * CBC_STAMP_SLOTS, 2 * i + 1, (uint32_t)(E.t_sum[i] >> 32)); }
 #endif
         E.publish(CBC_BF_LAST);                         /* carries the status if a check failed */
         return;
@@ -2130,8 +2228,8 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
         const uint32_t cn = n_reads - c0 < 64u ? n_reads - c0 : 64u;
         E.cur_read = c0;
         uint64_t neq;
-        typename CbcEnc<W>::Prep P;                           /* fused role only */
-        typename CbcEnc<W>::Run R;
+        typename Enc::Prep P;                           /* fused role only */
+        typename Enc::Run R;
         R.pk = W::splat(0u); R.ca = R.pk; R.cb = R.pk; R.rm = 0ull; R.s = 0u; R.counted = 0u;
         if (fused) {
             if (!load_group(c0, r_pos, r_fl, r_seq, r_tok, true)) break;
@@ -2143,7 +2241,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
             if (E.status != CBC_ST_OK) break;
             load_group(c0, r_pos, r_fl, r_seq, r_tok, false);
         }
-        typename CbcEnc<W>::Fixed F;
+        typename Enc::Fixed F;
         E.fixed_group(F, c0, cn, r_pos, r_fl, neq);
         /* totals and the scaled fractions of every fixed symbol of the group, one lane per record */
         const V32 rdv = ln + c0;
@@ -2214,7 +2312,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
                         const V32 bo = ln * 4u;
                         const V32 seqv = W::load32_bytes(seqb + so, bo, bo < (flw >> 16));
                         const V32 tokv = W::load32(tokb + to, ln, (ln + to) < n_tok_blk, 0u);
-                        const typename CbcEnc<W>::PrepRec pr = { W::readlane(P.lo, j), W::readlane(P.cnt, j) };
+                        const typename Enc::PrepRec pr = { W::readlane(P.lo, j), W::readlane(P.cnt, j) };
                         E.edits(W::readlane(r_pos, j), flw, to, seqv, tokv, tokb, n_tok_blk, pr);
                     }
                     E.seg_end();
@@ -2254,7 +2352,7 @@ CBC_FN void cbc_encode_stream(const cbc_enc_args &A, uint32_t blk, uint32_t *lds
     if (!fused && E.status != CBC_ST_OK) E.abort_groups();
     if (!fused) E.pull_rest();
 #if defined(CBC_STAMP) && defined(__HIP_DEVICE_COMPILE__)
-    if (payload_cap >= 128u) for (int i = 0; i < 16; i++) {   /* diagnostic build: over the payload start */
+    if (payload_cap >= 8u * CBC_STAMP_SLOTS) for (int i = 0; i < CBC_STAMP_SLOTS; i++) {   /* diagnostic build: over the payload start */
         W::write_uni(E.out32, 2 * i, (uint32_t)E.t_sum[i]); W::write_uni(E.out32, 2 * i + 1, (uint32_t)(E.t_sum[i] >> 32)); }
 #endif
     V32 resv = W::select(ln == 0u, W::splat(nbytes), W::select(ln == 1u, W::splat(E.status),

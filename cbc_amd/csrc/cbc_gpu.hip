@@ -37,24 +37,31 @@ extern __shared__ uint32_t cbc_lds[];
  * Workgroups are dealt round-robin to the 8 XCDs; blocks of one contig are neighbours in the
  * batch and share nothing but read-only reference lines, so the identity map is kept and the
  * per-XCD L2s each see a strided slice of the record stream. */
+template <bool HOT>
 static __device__ __forceinline__ void cbc_encode_block(const cbc_enc_args &A)
 {
     uint32_t blk = blockIdx.x;
     if (blk >= A.n_blocks) return;
     const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (wid == 0u) cbc_encode_stream<WaveGPU, CBC_ROLE_MODEL>(A, blk, cbc_lds);
-    else cbc_encode_stream<WaveGPU, CBC_ROLE_CODER>(A, blk, cbc_lds);
+    if (wid == 0u) cbc_encode_stream<WaveGPU, CBC_ROLE_MODEL, HOT>(A, blk, cbc_lds);
+    else cbc_encode_stream<WaveGPU, CBC_ROLE_CODER, HOT>(A, blk, cbc_lds);
 }
 
 /* Two register budgets of the same code.  Up to ten blocks per CU (cfg2: 9.5) everything is resident at
  * 5 wavefronts per SIMD and the kernel is latency-bound: the 84-register build is the faster one.  With
  * more blocks than that (cfg3-sized input) the CU is throughput-bound and a sixth wavefront per SIMD (80
- * registers, one spilled) gains 6 %; it costs 5 % at cfg2.  One wave fewer than 5 costs 25-30 %. */
+ * registers, one spilled) gains 6 %; it costs 5 % at cfg2.  One wave fewer than 5 costs 25-30 %.
+ * The five-wave build keeps the hot var context in four more registers (CbcEnc::hot_code); the six-wave build has none
+ * to spare (with the table: 28 bytes of scratch per lane) and keeps every context in the buckets and lists
+ * (-DCBC_HOT_CTX_W6=1 to look again). */
+#ifndef CBC_HOT_CTX_W6
+#define CBC_HOT_CTX_W6 0
+#endif
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(5)))
-cbc_encode_blocks_kernel(cbc_enc_args A) { cbc_encode_block(A); }
+cbc_encode_blocks_kernel(cbc_enc_args A) { cbc_encode_block<CBC_HOT_CTX != 0>(A); }
 
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(6)))
-cbc_encode_blocks_kernel_w6(cbc_enc_args A) { cbc_encode_block(A); }
+cbc_encode_blocks_kernel_w6(cbc_enc_args A) { cbc_encode_block<CBC_HOT_CTX_W6 != 0>(A); }
 
 __global__ void __launch_bounds__(64)
 cbc_decode_blocks_kernel(cbc_dec_args A)

@@ -53,7 +53,13 @@ extern "C" {
                                 /* alphabet, unsorted POS, var context >= 65535 ...             */
 #define CBC_ST_CAP_POS      3   /* more distinct POS deltas than lds.cap_pos                    */
 #define CBC_ST_CAP_FLAG     4   /* more than CBC_CAP_FLAG distinct FLAG values                  */
-#define CBC_ST_CAP_VAR      5   /* more var symbols than lds.cap_var                            */
+#define CBC_ST_CAP_VAR      5   /* more var symbols than lds.cap_var.  Counted are the symbols  */
+                                /* that take a list entry: not those held in the LDS buckets,   */
+                                /* and, in the block encode kernel of five wavefronts per SIMD, */
+                                /* not those of the context "first edit of a full-length read,  */
+                                /* no known SNP ahead" (d = read_length + 2), which it keeps as */
+                                /* counts in registers -- with a cap_var below the packer's a    */
+                                /* block may be coded (same bytes) that stopped here before     */
 #define CBC_ST_CAP_NAME     6   /* contig name longer than CBC_CAP_NAME-3                       */
 #define CBC_ST_UNSUPPORTED  7   /* raw leading-S / '*' op in the tokens (the packer emits a leading  */
                                 /* soft clip as an I op after rebuilding MD, quirk Q6); a block    */

@@ -16,11 +16,12 @@ st=ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 for _ in range(2): enc.encode_device(db, st)
 torch.cuda.synchronize(); print('kernel ms', enc.last_kernel_ms())
 out=d_out.cpu().numpy()
-sums=np.zeros(16)
+NS=18   # CBC_STAMP_SLOTS of cbc_encode_body.h
+sums=np.zeros(NS)
 for b in range(pb.n_blocks):
-    o=int(blocks[b]['out_off'])+int(blocks[b]['out_cap'])-128; sums+=out[o:o+128].view(np.uint64).astype(np.float64)
-    o=int(blocks[b]['out_off']); sums+=out[o:o+128].view(np.uint64).astype(np.float64)
-names=['M: grp loads+match','M: seg_end','M: run pass (positions, contexts, chars symbols, window marks one lane per SNP)','M: edits() only: to the first win_first of a record / between SNPs','M: edits() only: win_first','M: until publish','M: at barrier','M: var_code','M: chars (run_record); win_set+chars (edits())','C: coding','C: waiting','M: publish; edits() only: prefetch, window slide, token header','M: edit counts','M: rest of edits()','M: group pass (token headers, SNP counts)','C: look-ahead (group loads, validation, match test, post; before: inside C: coding)']
-tot=sums.sum()
+    o=int(blocks[b]['out_off'])+int(blocks[b]['out_cap'])-8*NS; sums+=out[o:o+8*NS].view(np.uint64).astype(np.float64)
+    o=int(blocks[b]['out_off']); sums+=out[o:o+8*NS].view(np.uint64).astype(np.float64)
+names=['M: grp loads+match','M: seg_end','M: run pass (positions, contexts, chars symbols, window marks one lane per SNP)','M: edits() only: to the first win_first of a record / between SNPs','M: edits() only: win_first','M: until publish','M: at barrier','M: var_code','M: chars (run_record); win_set+chars (edits())','C: coding','C: waiting','M: publish; edits() only: prefetch, window slide, token header','M: edit counts','M: rest of edits()','M: group pass (token headers, SNP counts)','C: look-ahead (group loads, validation, match test, post; before: inside C: coding)','M: inside var_code: the Bloom branch up to the filter test','M: inside var_code: the scan of the global list (list_fence to the loop\'s end)']
+tot=sums[:16].sum()   # slots 16, 17 are parts of slot 7
 for n,v in zip(names,sums): print('%-12s %8.0f cycles/read  %5.1f%%'%(n, v/pb.n_recs, 100*v/tot))
 print('total stamped cycles/read', tot/pb.n_recs)
