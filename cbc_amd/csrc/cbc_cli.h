@@ -23,6 +23,11 @@ int cbc_cli_decompress_depth(const char *in, const char *out, const char *ref, i
 int cbc_cli_decompress_pileup(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,
                               uint32_t min_alt, uint32_t edits_per_read, uint32_t min_alt_ppm, int by_strand, int verbose);
 
+/* --consensus: at most one region (NULL: every contig of the table); min_depth >= 1; call_ppm 1..1000000 (--call-frac);
+ * line_width 1..65535; flags: CBC_CONS_SHOW_DEL | _FILL_REF | _IUPAC; edits_per_read as for --pileup */
+int cbc_cli_decompress_consensus(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,
+                                 uint32_t min_depth, uint32_t call_ppm, uint32_t line_width, uint32_t flags, uint32_t edits_per_read, int verbose);
+
 /* any number of regions and / or a BED file (bed_path NULL: none); output: CBC_TARGETS_READS, _SAM or _DEPTH */
 int cbc_cli_decompress_targets(const char *in, const char *out, const char *ref, int device, const char *const *regions, uint32_t n_regions,
                                const char *bed_path, uint32_t output, uint32_t exclude, int verbose);

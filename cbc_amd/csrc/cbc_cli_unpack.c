@@ -470,6 +470,83 @@ int cbc_cli_decompress_pileup(const char *in, const char *out, const char *ref, 
     return decompress_window(in, out, ref, device, region, exclude, &pu, verbose);
 }
 
+/* `cbc -d|-x ... --consensus [--region NAME[:BEG[-END]]]`: the sequence the reads spell, one FASTA record
+ * per call, called and written on the device (cbc_gpu_decode_consensus): one call for the region's window (`>NAME:BEG-END`), or
+ * one per contig of the table in table order (`>NAME`).  A call's buffer is its record's bound (cbc_unpack_consensus_text_cap), so
+ * no call is repeated.  A selection without blocks, or whose blocks hold no read, is all low depth: its record is written on the
+ * host (cbc_unpack_consensus_empty) and needs no device. */
+int cbc_cli_decompress_consensus(const char *in, const char *out, const char *ref, int device, const char *region, uint32_t exclude,
+                                 uint32_t min_depth, uint32_t call_ppm, uint32_t line_width, uint32_t flags, uint32_t edits_per_read, int verbose)
+{
+    cli_run r;
+    if (cli_open(&r, in, ref, NULL, device, "--consensus", "stores no contig table")) return 1;
+    const cbc_unpack_plan *u = r.u;
+    char err[512];
+    int status = 1;                                     /* every way out but the last goes through `done` */
+    FILE *fo = NULL;
+    char *text = NULL;
+    if (cbc_unpack_sam_header(u, NULL, 0, err, sizeof err) < 0) { fprintf(stderr, "cbc: --consensus: %s\n", err[0] ? err : "the contig table is not usable"); goto done; }
+    const uint32_t n_calls = region ? 1u : u->n_contigs, with_range = region ? 1u : 0u;
+    const cbc_consensus_opts o = { min_depth, call_ppm, line_width, flags };
+    r.t1 = now2();
+    fo = fopen(out, "wb");
+    if (!fo) { cannot_write(out); goto done; }
+    cbc_consensus_counts tot, c;
+    memset(&tot, 0, sizeof tot);
+    uint64_t total = 0, kept = 0, have = 0;
+    uint32_t blocks_used = 0;
+    float ms[4] = { 0, 0, 0, 0 }, m[4];
+    for (uint32_t k = 0; k < n_calls; k++) {
+        cbc_region_sel s;
+        int rc = region ? cbc_unpack_region(u, region, &s, err, sizeof err) : cbc_unpack_contig_blocks(u, k, &s, err, sizeof err);
+        if (rc) { fprintf(stderr, "cbc: %s\n", rc == CBC_E_INPUT ? err : "block selection failed"); goto done; }
+        const uint64_t cap = cbc_unpack_consensus_text_cap(u, s.contig, s.beg, s.end, line_width, with_range);
+        if (!cap) { fprintf(stderr, "cbc: --consensus: the window %llu-%llu is not usable\n", (unsigned long long)s.beg, (unsigned long long)s.end); goto done; }
+        if (cap > have || !text) { free(text); text = (char *)malloc((size_t)cap + 1); have = cap; }
+        if (!text) { fprintf(stderr, "cbc: out of memory\n"); goto done; }
+        uint32_t nb = s.b1 - s.b0;
+        uint64_t reads = 0, tb = 0, nk = 0;
+        for (uint32_t q = s.b0; q < s.b1; q++) reads += u->blocks[q].n_reads;
+        if (!reads) nb = 0;
+        if (!nb) {                                      /* no read can cover the window: all low depth, no device needed */
+            const int64_t n = cbc_unpack_consensus_empty(u, s.contig, s.beg, s.end, &o, with_range, (uint8_t *)text, cap, &c);
+            if (n < 0) { fprintf(stderr, "cbc: --consensus: the record of a window without reads failed (%lld)\n", (long long)n); goto done; }
+            tb = (uint64_t)n;
+        } else {
+            if (cli_device(&r)) goto done;
+            const double b = now2();
+            const char *nm = u->names + u->contig_name_off[s.contig];
+            rc = cbc_gpu_decode_consensus(r.ctx, u->payloads, u->payload_bytes, u->blocks + s.b0, nb, &u->caps, u->window_start + s.b0,
+                                          nm, (uint32_t)strlen(nm), s.beg, s.end, s.smax, exclude, edits_per_read, &o, with_range,
+                                          (uint8_t *)text, cap, &tb, &c, &nk, NULL);
+            if (rc) { fprintf(stderr, "cbc: consensus failed: %s\n", cbc_gpu_last_error(r.ctx)); goto done; }
+            r.t_dev += now2() - b;
+            if (verbose && cbc_gpu_last_consensus_ms(r.ctx, &m[0], &m[1], &m[2], &m[3]) == 0) add_ms(ms, m, 4);
+        }
+        if (tb && fwrite(text, 1, (size_t)tb, fo) != (size_t)tb) { cannot_write(out); goto done; }
+        total += tb; kept += nk; blocks_used += nb;
+        tot.emitted += c.emitted; tot.ref += c.ref; tot.alt += c.alt; tot.del += c.del; tot.ambiguous += c.ambiguous;
+        tot.low_depth += c.low_depth; tot.no_call += c.no_call; tot.ins_skipped += c.ins_skipped;
+    }
+    { FILE *f2 = fo; fo = NULL; if (fclose(f2) != 0) { cannot_write(out); goto done; } }
+    printf("consensus: %llu bases (%llu ref, %llu alt, %llu deleted, %llu ambiguous, %llu low depth, %llu no call; %llu insertions not applied) from %llu reads in %u blocks\n",
+           (unsigned long long)tot.emitted, (unsigned long long)tot.ref, (unsigned long long)tot.alt, (unsigned long long)tot.del,
+           (unsigned long long)tot.ambiguous, (unsigned long long)tot.low_depth, (unsigned long long)tot.no_call,
+           (unsigned long long)tot.ins_skipped, (unsigned long long)kept, blocks_used);
+    if (verbose) {
+        printf("consensus: %llu text bytes, exclude flags 0x%x, min depth %u, call fraction %u ppm, line width %u, flags %u, edits per read %u\n",
+               (unsigned long long)total, exclude, min_depth, call_ppm, line_width, flags, edits_per_read ? edits_per_read : CBC_EDITS_PER_READ);
+        printf("time: read + plan %.3f s, device init + reference upload %.3f s, decode + consensus + write %.3f s\n", r.t1 - r.t0, r.t_init, r.t_dev);
+        if (r.used) printf("kernels: edits decode %.3f ms, mark + events %.3f ms, scans %.3f ms, text %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
+    }
+    status = 0;
+done:
+    if (fo) { fclose(fo); remove(out); }                /* a failed call leaves no partial record file behind */
+    free(text);
+    cli_close(&r);
+    return status;
+}
+
 /* `cbc -d|-x ... --region A --region B ... [--regions-file FILE]`: the union of the loci in one pass.
  * The target set and its blocks come from cbc_unpack_targets; reads and SAM are one call over the selected blocks of all
  * contigs, the depth one call per contig that has intervals and blocks, the texts appended in contig-table order. */

@@ -1331,17 +1331,24 @@ API int cbc_gpu_decode_sam_cigar(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t i
 
 /* coverage: the window's blocks laid out afresh as for a region decode, then span decode + mark + scan + text on the device
  * (cbc_depth_body.h).  pu != NULL: per-position allele counts -- the edits decoder, then mark + events +
- * scans + text (cbc_pileup_body.h), for the blocks of one contig. */
+ * scans + text (cbc_pileup_body.h), for the blocks of one contig.  co != NULL (with pu): the consensus record (DESIGN.md section
+ * 4.25) -- the pileup's passes up to the tile sums' scan, then the call count, its scan and the record (cbc_consensus_body.h). */
 struct pileup_opt { uint32_t min_alt, edits_per_read, min_alt_ppm, by_strand; };
+struct consensus_opt { const cbc_consensus_opts *o; uint32_t with_range; cbc_consensus_counts *counts; };
+/* the decimal digits of a window's bound, at most ten (end <= 2^31 - 1) */
+static uint32_t ndig10(uint64_t x) { uint32_t d = 1; for (; x >= 10u; x /= 10u) d++; return d; }
 static int decode_window_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
                               uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const char *name,
                               uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax, uint32_t exclude_flags, const pileup_opt *pu,
                               uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *n_runs, uint64_t *n_reads_kept,
-                              cbc_block_result *results)
+                              cbc_block_result *results, const consensus_opt *co = NULL)
 {
-    const char *who = pu ? "pileup" : "depth";
+    const char *who = co ? "consensus" : pu ? "pileup" : "depth";
     if (!ctx || !blocks || !caps || !window_start || !name || !text_bytes || !n_runs || !n_reads_kept || (text_cap && !text)) return CBC_E_ARG;
     *text_bytes = 0; *n_runs = 0; *n_reads_kept = 0;
+    if (co && (co->o->min_depth < 1 || co->o->call_ppm < 1 || co->o->call_ppm > 1000000u || co->o->line_width < 1 || co->o->line_width > 65535u ||
+               (co->o->flags & ~(CBC_CONS_SHOW_DEL | CBC_CONS_FILL_REF | CBC_CONS_IUPAC)) || co->with_range > 1u))
+        return set_err(ctx, CBC_E_ARG, "consensus wants min_depth >= 1, call_ppm in 1..1000000, line_width in 1..65535, known flag bits and with_range 0 or 1", hipSuccess);
     int rc = call_ready(ctx, n_blocks, in != NULL);
     if (rc <= 0) return rc;
     if ((rc = check_window(ctx, who, beg, end, smax, true))) return rc;
@@ -1351,14 +1358,14 @@ static int decode_window_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         if (pu->min_alt_ppm > 1000000u || pu->by_strand > 1u)
             return set_err(ctx, CBC_E_ARG, "pileup wants min_alt_ppm in 0..1000000 (0: no fraction rule) and by_strand 0 or 1", hipSuccess);
         edits_per_read = pu->edits_per_read;
-        if ((rc = check_edits(ctx, "pileup wants ", &edits_per_read))) return rc;
+        if ((rc = check_edits(ctx, co ? "consensus wants " : "pileup wants ", &edits_per_read))) return rc;
     }
     const bool skip_del = !pu && ctx->skipdel_edits != 0u;            /* cbc_gpu_set_depth_skip_deletions */
     if ((rc = check_window_name(ctx, who, name, name_bytes))) return rc;
     /* one contig: every block's window lies at the same place of the reference */
     for (uint32_t b = 0; pu && b < n_blocks; b++)
         if (blocks[b].ref_off < window_start[b] || blocks[b].ref_off - window_start[b] != blocks[0].ref_off - window_start[0])
-            return set_err(ctx, CBC_E_ARG, "pileup takes the blocks of one contig", hipSuccess);
+            return set_err(ctx, CBC_E_ARG, co ? "consensus takes the blocks of one contig" : "pileup takes the blocks of one contig", hipSuccess);
     block_layout L;
     rc = relayout_blocks(ctx, who, in_bytes, blocks, n_blocks, NULL, &L);
     if (rc) return rc;
@@ -1367,14 +1374,18 @@ static int decode_window_impl(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_b
         /* depth: K reads give at most 2K - 1 runs; pileup, and the depth under skip_del (cbc_unpack_depth_skipdel_text_cap): a line
          * per position of the window at most, and per reference base a kept read spans (span <= smax) */
         const uint64_t w = end - beg + 1u, by_reads = L.nrec * smax, by_pos = w < by_reads ? w : by_reads;
+        /* consensus: the header, a byte per position at most, their newlines */
+        const uint32_t hdr = co ? name_bytes + 2u + (co->with_range ? 2u + ndig10(beg) + ndig10(end) : 0u) : 0u;
         post_req rg;
-        post_req_init(&rg, pu ? POST_PILEUP : POST_DEPTH, smax, window_start, text, text_cap,
+        post_req_init(&rg, co ? POST_CONSENSUS : pu ? POST_PILEUP : POST_DEPTH, smax, window_start, text, text_cap,
+                      co ? hdr + w + (w + co->o->line_width - 1u) / co->o->line_width :
                       pu ? by_pos * (name_bytes + 102ull + (pu->by_strand ? 77ull : 0ull)) : skip_del ? by_pos * (name_bytes + 34ull) : (2u * L.nrec - 1u) * (name_bytes + 34ull),
                       text_bytes, n_reads_kept);
         rg.beg = beg; rg.end = end;
         rg.names = (const uint8_t *)name; rg.names_bytes = name_bytes; rg.exclude = exclude_flags; rg.n_runs = n_runs;
         if (pu) { rg.edits_per_read = edits_per_read; rg.min_alt = pu->min_alt; rg.ref_c0 = blocks[0].ref_off - window_start[0];
                   rg.min_alt_ppm = pu->min_alt_ppm; rg.by_strand = pu->by_strand != 0u; }
+        if (co) { rg.cons = *co->o; rg.with_range = co->with_range; rg.cons_hdr = hdr; rg.cons_counts = co->counts; }
         if (skip_del) { rg.skip_del = true; rg.edits_per_read = ctx->skipdel_edits; }
         rc = decode_laid_out(ctx, in, &L, n_blocks, caps, results, &rg);
     }
@@ -1413,6 +1424,23 @@ API int cbc_gpu_decode_pileup_ext(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t 
     const pileup_opt pu = { min_alt, edits_per_read, min_alt_ppm, by_strand };
     return decode_window_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, name, name_bytes, beg, end, smax, exclude_flags, &pu,
                               text, text_cap, text_bytes, n_lines, n_reads_kept, results);
+}
+
+/* the consensus record behind the pileup's passes */
+API int cbc_gpu_decode_consensus(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                                 uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start, const char *name,
+                                 uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax, uint32_t exclude_flags,
+                                 uint32_t edits_per_read, const cbc_consensus_opts *opts, uint32_t with_range, uint8_t *text,
+                                 uint64_t text_cap, uint64_t *text_bytes, cbc_consensus_counts *counts, uint64_t *n_reads_kept,
+                                 cbc_block_result *results)
+{
+    if (!opts || !counts) return CBC_E_ARG;
+    memset(counts, 0, sizeof *counts);
+    const pileup_opt pu = { 1u, edits_per_read, 0u, 0u };
+    const consensus_opt co = { opts, with_range, counts };
+    uint64_t n_lines = 0;
+    return decode_window_impl(ctx, in, in_bytes, blocks, n_blocks, caps, window_start, name, name_bytes, beg, end, smax, exclude_flags, &pu,
+                              text, text_cap, text_bytes, &n_lines, n_reads_kept, results, &co);
 }
 
 /* cbc_gpu_decode_blocks_span with the edits reported too: the decoder the pileup runs, with everything it leaves returned */
@@ -1743,6 +1771,8 @@ API int cbc_gpu_last_depth_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *mark_ms
 
 API int cbc_gpu_last_pileup_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *events_ms, float *scan_ms, float *text_ms)
 { LAST_MS(ctx->last_post == POST_PILEUP, decode_ms, events_ms, scan_ms, text_ms); }
+API int cbc_gpu_last_consensus_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *events_ms, float *scan_ms, float *text_ms)
+{ LAST_MS(ctx->last_post == POST_CONSENSUS, decode_ms, events_ms, scan_ms, text_ms); }
 
 /* not after a call with the alignment tables: that one has a third stretch, and an entry point of its own */
 API int cbc_gpu_last_stats_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *stats_ms)

@@ -39,9 +39,9 @@ enum { A_RECS, A_SEQ, A_TOK, A_NAMES, A_BLOCKS, A_OUT, A_RES, A_OFF, A_PACKED, A
 
 /* what decode_blocks_impl runs behind the decode (its post-decode stage): nothing (plain, 2-bit, span, long reads), or the
  * stage of cbc_gpu_decode_region, _sam, _depth, _targets (reads, SAM, depth), _coverage, _depth_hist, _coverage_ext, _stats (whole
- * file, target set), _pileup, _sam_cigar, _stats_aln (whole file, target set) */
+ * file, target set), _pileup, _sam_cigar, _stats_aln (whole file, target set), _consensus */
 enum post_kind { POST_NONE, POST_REGION, POST_SAM, POST_DEPTH, POST_TG_READS, POST_TG_SAM, POST_TG_DEPTH, POST_COV, POST_HIST, POST_COVX,
-                 POST_STATS, POST_TG_STATS, POST_COVQ, POST_PILEUP, POST_SAM_CIGAR, POST_STATS_ALN, POST_TG_STATS_ALN };
+                 POST_STATS, POST_TG_STATS, POST_COVQ, POST_PILEUP, POST_SAM_CIGAR, POST_STATS_ALN, POST_TG_STATS_ALN, POST_CONSENSUS };
 
 struct cbc_gpu_ctx {
     int device;
@@ -89,8 +89,10 @@ void launch_scan_sizes(hipStream_t s, const cbc_block_result *sizes, uint64_t *o
 
 static inline bool post_is_covx(post_kind k) { return k == POST_COVX || k == POST_COVQ; }
 static inline bool post_is_cov(post_kind k) { return k == POST_COV || post_is_covx(k); }
-/* PILEUP shares the depth kinds' arenas, counters and text fetch; it has no change points and its text tiles are the position tiles */
-static inline bool post_is_depth(post_kind k) { return k == POST_DEPTH || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || k == POST_PILEUP; }
+/* PILEUP shares the depth kinds' arenas, counters and text fetch; it has no change points and its text tiles are the position tiles.
+ * CONSENSUS is PILEUP up to the tile sums' scan, with its own call counters and two passes of its own behind */
+static inline bool post_is_pileup(post_kind k) { return k == POST_PILEUP || k == POST_CONSENSUS; }
+static inline bool post_is_depth(post_kind k) { return k == POST_DEPTH || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || post_is_pileup(k); }
 static inline bool post_is_sam(post_kind k) { return k == POST_SAM || k == POST_TG_SAM || k == POST_SAM_CIGAR; }
 static inline bool post_is_targets(post_kind k) { return k == POST_TG_READS || k == POST_TG_SAM || k == POST_TG_DEPTH || post_is_cov(k) || k == POST_HIST || k == POST_TG_STATS || k == POST_TG_STATS_ALN; }
 /* STATS_ALN is STATS behind the edits decoder with one more table and one more kernel */
@@ -137,6 +139,9 @@ struct post_req {
      * none) and whether the line carries the per-strand columns -- then the window holds two difference arrays and 14 planes */
     uint32_t min_alt_ppm; bool by_strand;
     uint32_t *edit_side; uint16_t *edit_arena;
+    /* CONSENSUS (with edits_per_read and ref_c0 as for PILEUP): the rule's options, the header's form and
+     * length, where the counters go.  text_bytes takes header + E + ceil(E / line_width) */
+    cbc_consensus_opts cons; uint32_t with_range, cons_hdr; cbc_consensus_counts *cons_counts;
     /* the depth kinds but PILEUP, under cbc_gpu_set_depth_skip_deletions: deleted bases do not count -- the
      * edits decoder (edits_per_read is set with it) and the unmark stage behind the mark kernel */
     bool skip_del;
@@ -148,7 +153,7 @@ struct post_req {
 struct post_sizes { uint64_t d_words, h_bins; uint32_t n_tiles, cp_cap, n_ttiles, n_sized, n_btiles, h_out_cap, sp_cap; };
 
 /* what post_fetch_sizes brings to the host for post_fetch_output; decode_blocks_impl zeroes it and frees cnt and stats */
-struct post_got { uint32_t dctr[4]; uint64_t total, h_count; cbc_block_result *cnt; /* region / SAM / reads: the filter's per-block counts */
+struct post_got { uint32_t dctr[4], cctr[8]; /* CONSENSUS: the call counters */ uint64_t total, h_count; cbc_block_result *cnt; /* region / SAM / reads: the filter's per-block counts */
                   uint32_t *stats; /* STATS: the device's tables, CBC_STATS_WORDS; STATS_ALN: CBC_SALN_WORDS more behind them */ };
 
 /* cbc_gpu_post.hip: the post-decode stage in the order decode_blocks_impl goes through it -- the sizes, the arenas, the small

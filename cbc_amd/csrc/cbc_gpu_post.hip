@@ -15,6 +15,7 @@
 #include "cbc_hist_body.h"
 #include "cbc_stats_body.h"
 #include "cbc_pileup_body.h"
+#include "cbc_consensus_body.h"
 #include "cbc_skipdel_body.h"
 #include "cbc_cigar_body.h"
 #include "cbc_stats_aln_body.h"
@@ -56,6 +57,12 @@ template <int M> __global__ void __launch_bounds__(64)
 cbc_pileup_count_ext_kernel(cbc_pileup_args A, cbc_pileup_sx X) { cbc_pileup_count<WaveGPU, M>(A, blockIdx.x, &X); }
 template <int M> __global__ void __launch_bounds__(64)
 cbc_pileup_write_ext_kernel(cbc_pileup_args A, cbc_pileup_sx X) { cbc_pileup_write<WaveGPU, M>(A, blockIdx.x, &X); }
+/* cbc_gpu_decode_consensus (cbc_consensus_body.h): behind the plain call's mark, events and tile kernels
+ * above, one wavefront per tile of positions applies the call rule and counts the bytes it emits, and (after the scan) writes them */
+__global__ void __launch_bounds__(64)
+cbc_consensus_count_kernel(cbc_consensus_args A) { cbc_consensus_count<WaveGPU>(A, blockIdx.x); }
+__global__ void __launch_bounds__(64)
+cbc_consensus_write_kernel(cbc_consensus_args A) { cbc_consensus_write<WaveGPU>(A, blockIdx.x); }
 
 /* SAM text with CIGAR, NM and MD (cbc_gpu_decode_sam_cigar, cbc_cigar_body.h): behind the edits decoder CBC_CIGAR_WAVES wavefronts
  * per block measure every kept read's CIGAR, NM and MD; then the count (one wavefront per block) and the text assembly
@@ -247,7 +254,7 @@ post_sizes post_sizes_of(const post_req *rg, uint32_t n_blocks, uint64_t n_recs)
         z.cp_cap = (uint32_t)(by_edits < z.d_words ? by_edits : z.d_words);
     }
     z.n_ttiles = (z.cp_cap + CBC_DEPTH_LINES - 1u) / CBC_DEPTH_LINES;
-    if (rg->kind == POST_PILEUP) { z.cp_cap = 0; z.n_ttiles = z.n_tiles; }
+    if (post_is_pileup(rg->kind)) { z.cp_cap = 0; z.n_ttiles = z.n_tiles; }
     z.n_sized = z.n_ttiles;
     /* start points: a piece starts where its read starts or on an interval's first slot */
     if (post_is_covx(rg->kind)) z.sp_cap = (uint32_t)(n_recs + rg->n_iv);
@@ -295,7 +302,7 @@ int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z, uint3
         NEED(A_DTOFF, ((uint64_t)z.n_tiles + 1) * 2 * 8, "hipMalloc depth tile offsets");
         if (arena_need(ctx, A_DCP, (uint64_t)z.cp_cap * 2 * 4 + 16, "hipMalloc depth change points"))
             return nomem_points(ctx, rg, "no device memory for the depth's change points (8 bytes each)");
-        NEED(A_DCTR, 16, "hipMalloc depth counters");
+        NEED(A_DCTR, k == POST_CONSENSUS ? 16 + 4 * CBC_CONS_CTRS + 4 : 16, "hipMalloc depth counters");   /* CONSENSUS: its call counters behind the four */
         NEED(A_SNAMES, (uint64_t)rg->names_bytes + 16, "hipMalloc contig name");
     }
     if (post_is_sam(k)) {
@@ -341,7 +348,7 @@ int post_arenas(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z, uint3
     }
     if (post_is_stats(k)) NEED(A_STATS, (uint64_t)CBC_STATS_WORDS * 4, "hipMalloc statistics tables");
     if (post_is_stats_aln(k)) NEED(A_SALN, (uint64_t)CBC_SALN_WORDS * 4, "hipMalloc alignment tables");
-    if (k == POST_PILEUP && arena_need(ctx, A_PTAB, pileup_tab_bytes(rg, z), "hipMalloc pileup counters")) {
+    if (post_is_pileup(k) && arena_need(ctx, A_PTAB, pileup_tab_bytes(rg, z), "hipMalloc pileup counters")) {
         (void)hipGetLastError();
         return set_err(ctx, CBC_E_NOMEM, rg->by_strand ? "no device memory for the window's per-strand allele counters and forward difference array (56 + 4 bytes per position)"
                                                        : "no device memory for the window's allele counters (28 bytes per position)", hipSuccess);
@@ -694,6 +701,8 @@ static int launch_hist(cbc_gpu_ctx *ctx, hipStream_t ks, const hist_req *hist, c
 
 /* per-position allele counts: zero, the depth's mark pass and the events; the depth's tile sums and their scan; lines per tile
  * of positions, scan, write */
+static int launch_consensus(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const post_sizes &z, const cbc_pileup_args &pa);
+
 static int launch_pileup(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const post_sizes &z, const cbc_region_args &ra, uint64_t n_recs)
 {
     const uint32_t n_tiles = z.n_tiles;
@@ -737,6 +746,7 @@ static int launch_pileup(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, c
         HIPCHK(hipGetLastError(), "launch cbc_depth_tile_kernel");
         launch_scan_sizes(ks, df.tile_sum, (uint64_t *)df.sum_off, n_tiles);
     }
+    if (rg->kind == POST_CONSENSUS) return launch_consensus(ctx, ks, rg, z, pa);
     if (bs) hipLaunchKernelGGL(cbc_pileup_count_ext_kernel<CBC_PILEUP_STRAND>, dim3(n_tiles), dim3(64), 0, ks, pa, sx);
     else if (ext) hipLaunchKernelGGL(cbc_pileup_count_ext_kernel<CBC_PILEUP_FRAC>, dim3(n_tiles), dim3(64), 0, ks, pa, sx);
     else hipLaunchKernelGGL(cbc_pileup_count_kernel, dim3(n_tiles), dim3(64), 0, ks, pa);
@@ -748,6 +758,26 @@ static int launch_pileup(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, c
     else if (ext) hipLaunchKernelGGL(cbc_pileup_write_ext_kernel<CBC_PILEUP_FRAC>, dim3(n_tiles), dim3(64), 0, ks, pa, sx);
     else hipLaunchKernelGGL(cbc_pileup_write_kernel, dim3(n_tiles), dim3(64), 0, ks, pa);
     HIPCHK(hipGetLastError(), "launch cbc_pileup_write_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[4], ks), "hipEventRecord");
+    return CBC_OK;
+}
+
+/* the consensus behind the pileup's front: its counters zeroed, the call count per tile of positions, its scan, the record */
+static int launch_consensus(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const post_sizes &z, const cbc_pileup_args &pa)
+{
+    cbc_consensus_args ca;
+    memset(&ca, 0, sizeof ca);
+    ca.P = pa; ca.cctr = pa.D.ctr + 4;
+    ca.min_depth = rg->cons.min_depth; ca.ppm = rg->cons.call_ppm; ca.line_width = rg->cons.line_width; ca.flags = rg->cons.flags;
+    ca.with_range = rg->with_range;
+    HIPCHK(hipMemsetAsync(ca.cctr, 0, 4 * CBC_CONS_CTRS, ks), "memset consensus counters");
+    hipLaunchKernelGGL(cbc_consensus_count_kernel, dim3(z.n_tiles), dim3(64), 0, ks, ca);
+    HIPCHK(hipGetLastError(), "launch cbc_consensus_count_kernel");
+    launch_scan_sizes(ks, pa.D.R.counts, (uint64_t *)ctx->arena[A_OFF].p, z.n_tiles);
+    HIPCHK(hipGetLastError(), "launch cbc_scan_sizes_kernel");
+    HIPCHK(hipEventRecord(ctx->ev_rg[3], ks), "hipEventRecord");
+    hipLaunchKernelGGL(cbc_consensus_write_kernel, dim3(z.n_tiles), dim3(64), 0, ks, ca);
+    HIPCHK(hipGetLastError(), "launch cbc_consensus_write_kernel");
     HIPCHK(hipEventRecord(ctx->ev_rg[4], ks), "hipEventRecord");
     return CBC_OK;
 }
@@ -824,7 +854,7 @@ int post_launch(cbc_gpu_ctx *ctx, hipStream_t ks, const post_req *rg, const post
         if (!rc) rc = launch_hist(ctx, ks, &rg->hist, z, da);
         break;
     case POST_STATS: case POST_TG_STATS: case POST_STATS_ALN: case POST_TG_STATS_ALN: rc = launch_stats(ctx, ks, rg, ra); break;
-    case POST_PILEUP: rc = launch_pileup(ctx, ks, rg, z, ra, n_recs); break;
+    case POST_PILEUP: case POST_CONSENSUS: rc = launch_pileup(ctx, ks, rg, z, ra, n_recs); break;
     case POST_SAM_CIGAR: rc = launch_sam_cigar_text(ctx, ks, rg, ra, n_recs); break;
     }
     if (!rc) ctx->last_post = rg->kind;                        /* the events now hold this call's times */
@@ -837,6 +867,8 @@ int post_fetch_sizes(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z, 
 {
     if (post_is_depth(rg->kind)) {
         HIPCHK(hipMemcpyAsync(g->dctr, ctx->arena[A_DCTR].p, 16, hipMemcpyDeviceToHost, sc), "D2H depth counters");
+        if (rg->kind == POST_CONSENSUS)
+            HIPCHK(hipMemcpyAsync(g->cctr, (uint32_t *)ctx->arena[A_DCTR].p + 4, 4 * CBC_CONS_CTRS, hipMemcpyDeviceToHost, sc), "D2H consensus counters");
         if (rg->kind == POST_HIST)
             HIPCHK(hipMemcpyAsync(&g->h_count, (uint64_t *)((cbc_block_result *)ctx->arena[A_HTILE].p + z.n_btiles) + z.n_btiles, 8, hipMemcpyDeviceToHost, sc), "D2H histogram size");
         else if (!post_is_cov(rg->kind))
@@ -887,6 +919,19 @@ int post_fetch_output(cbc_gpu_ctx *ctx, const post_req *rg, const post_sizes &z,
     }
     if (depth) { kept = g->dctr[0]; *rg->n_runs = g->dctr[1]; }
     else for (uint32_t b = 0; b < n_blocks; b++) kept += g->cnt[b].n_symbols;
+    if (rg->kind == POST_CONSENSUS) {                          /* g->total = E, the emitted bytes: the record is the header, they, their newlines */
+        cbc_consensus_counts *c = rg->cons_counts;
+        const uint64_t e = g->total, bytes = rg->cons_hdr + e + (e + rg->cons.line_width - 1u) / rg->cons.line_width;
+        c->emitted = e; c->ref = g->cctr[CBC_CONS_REF]; c->alt = g->cctr[CBC_CONS_ALT]; c->del = g->cctr[CBC_CONS_DEL];
+        c->ambiguous = g->cctr[CBC_CONS_AMB]; c->low_depth = g->cctr[CBC_CONS_LOW]; c->no_call = g->cctr[CBC_CONS_NONE];
+        c->ins_skipped = g->cctr[CBC_CONS_INS];
+        *rg->text_bytes = bytes; *rg->n_selected = kept;
+        if (bytes > rg->text_cap) return set_err(ctx, CBC_E_ARG, "text_cap too small for the consensus record", hipSuccess);
+        HIPCHK(hipMemcpyAsync(rg->text, ctx->arena[A_TEXT].p, bytes, hipMemcpyDeviceToHost, sc), "D2H consensus record");
+        HIPCHK(hipStreamSynchronize(sc), "D2H consensus record");
+        *d2h_bytes = bytes;
+        return CBC_OK;
+    }
     *rg->text_bytes = g->total; *rg->n_selected = kept;
     if (g->total > rg->text_cap)
         return set_err(ctx, CBC_E_ARG, rg->kind == POST_PILEUP ? "text_cap too small for the pileup text" : depth ? "text_cap too small for the depth text" : post_is_sam(rg->kind) ? "text_cap too small for the SAM text" : "text_cap too small for the region's text", hipSuccess);

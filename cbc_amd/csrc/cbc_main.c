@@ -87,7 +87,17 @@ static void usage(const char *p)
             "                  line is decided on the totals)\n"
             "         --min-alt-frac F (with --pileup: only positions whose non-reference observations are at least the fraction F of\n"
             "                  the depth, beside --min-alt; F in (0, 1] with at most six decimals, e.g. 0.02; compared in exact integers)\n"
-            "         --max-edits-per-read N (with --pileup, --sam --cigar, --stats --alignment or --skip-deletions: deleted + inserted bases\n"
+            "         --consensus (the sequence the reads spell, as FASTA: one record per contig of the table, `>NAME`, or with one\n"
+            "                  --region its window, `>NAME:BEG-END`; per position the most frequent of A, C, G, T and deletion is\n"
+            "                  called when it reaches the fraction F of the depth -- ties go to the reference, then in that order --, a\n"
+            "                  called deletion drops the base, anything else is N; insertions are counted, not applied; called on the\n"
+            "                  device; with --depth-exclude-flags and --max-edits-per-read; not with any other output)\n"
+            "         --call-min-depth D (with --consensus: positions with depth < D are N; default 1)\n"
+            "         --call-frac F (with --consensus: F in (0, 1] with at most six decimals; default 0.75)\n"
+            "         --line-width W (with --consensus: bases per line, 1..65535; default 60)\n"
+            "         --show-del (with --consensus: a called deletion writes * )  --fill-ref (low depth writes the reference base in\n"
+            "                  lower case)  --iupac (no single call: the IUPAC code of the smallest top set that reaches F)\n"
+            "         --max-edits-per-read N (with --pileup, --consensus, --sam --cigar, --stats --alignment or --skip-deletions: deleted + inserted bases\n"
             "                  kept per read of a block, 1..510; default 16)\n"
             "         --skip-deletions (with --depth, --bedcov or --depth-hist: the depth at a position is the reads with an aligned base\n"
             "                  there; the bases a read deletes do not count, as in samtools depth without -J, mosdepth and bedtools\n"
@@ -537,6 +547,8 @@ int main(int argc, char **argv)
     uint32_t min_alt = 1, max_edits = 0;
     int by_strand = 0, alt_frac_given = 0;
     uint32_t alt_frac_ppm = 0;
+    int consensus = 0, call_depth_given = 0, call_frac_given = 0, line_width_given = 0, show_del = 0, fill_ref = 0, iupac = 0;
+    uint32_t call_min_depth = 1, call_ppm = 750000, line_width = 60;
     g_main_t0 = now_s();
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
@@ -604,6 +616,13 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--min-alt-frac") && i + 1 < argc) { if (!parse_alt_frac(a, argv[++i], &alt_frac_ppm)) return 1; alt_frac_given = 1; continue; }
         if (!strcmp(a, "--max-edits-per-read") && i + 1 < argc) { if (!parse_count(a, argv[++i], 510, "a number of deleted and inserted bases in 1..510", &n)) return 1; max_edits = (uint32_t)n; max_edits_given = 1; continue; }
         if (!strcmp(a, "--skip-deletions")) { skip_del = 1; continue; }
+        if (!strcmp(a, "--consensus")) { consensus = 1; continue; }
+        if (!strcmp(a, "--call-min-depth") && i + 1 < argc) { if (!parse_count(a, argv[++i], 0xffffffffull, "a depth in 1..4294967295", &n)) return 1; call_min_depth = (uint32_t)n; call_depth_given = 1; continue; }
+        if (!strcmp(a, "--call-frac") && i + 1 < argc) { if (!parse_alt_frac(a, argv[++i], &call_ppm)) return 1; call_frac_given = 1; continue; }
+        if (!strcmp(a, "--line-width") && i + 1 < argc) { if (!parse_count(a, argv[++i], 65535, "a number of bases in 1..65535", &n)) return 1; line_width = (uint32_t)n; line_width_given = 1; continue; }
+        if (!strcmp(a, "--show-del")) { show_del = 1; continue; }
+        if (!strcmp(a, "--fill-ref")) { fill_ref = 1; continue; }
+        if (!strcmp(a, "--iupac")) { iupac = 1; continue; }
         if (!strcmp(a, "--compat")) { compat = 1; continue; }
         if (!strcmp(a, "--long")) { long_reads = 1; continue; }
         if (!strcmp(a, "--device-parse")) { device_parse = 1; continue; }
@@ -656,13 +675,17 @@ int main(int argc, char **argv)
         { "--depth-hist", depth_hist, "--depth-hist, --bedcov, --depth and --sam are different outputs", hist_max_given ? "--hist-max" : NULL },
         { "--stats", stats_out, "--stats, --depth-hist, --bedcov, --depth and --sam are different outputs", stats_excl_given ? "--stats-exclude-flags" : stats_aln ? "--alignment" : NULL },
         { "--pileup", pileup, "--pileup, --stats, --depth-hist, --bedcov, --depth and --sam are different outputs",
-          min_alt_given ? "--min-alt" : max_edits_given && !sam_cigar && !(stats_out && stats_aln) && !skip_del ? "--max-edits-per-read" :
+          min_alt_given ? "--min-alt" : max_edits_given && !sam_cigar && !(stats_out && stats_aln) && !skip_del && !consensus ? "--max-edits-per-read" :
           by_strand ? "--by-strand" : alt_frac_given ? "--min-alt-frac" : NULL },
+        { "--consensus", consensus, "--consensus, --pileup, --stats, --depth-hist, --bedcov, --depth and --sam are different outputs",
+          call_depth_given ? "--call-min-depth" : call_frac_given ? "--call-frac" : line_width_given ? "--line-width" : show_del ? "--show-del" :
+          fill_ref ? "--fill-ref" : iupac ? "--iupac" : NULL },
     };
     /* --skip-deletions changes what the three depth outputs count; anywhere else it means nothing and is refused */
     if (skip_del) {
         if (mode != 2) { fprintf(stderr, "cbc: --skip-deletions applies to decompression (-d / -x)\n"); return 1; }
         if (pileup) { fprintf(stderr, "cbc: --skip-deletions applies to --depth, --bedcov or --depth-hist; the del column of --pileup already says it\n"); return 1; }
+        if (consensus) { fprintf(stderr, "cbc: --skip-deletions applies to --depth, --bedcov or --depth-hist, not to --consensus, which calls deletions itself\n"); return 1; }
         if (!depth_out && !bedcov && !depth_hist) { fprintf(stderr, "cbc: --skip-deletions applies to --depth, --bedcov or --depth-hist\n"); return 1; }
     }
     for (size_t k = 0; k < sizeof opts / sizeof opts[0]; k++) {
@@ -677,12 +700,17 @@ int main(int argc, char **argv)
         if (regions_file || n_regions > 1) { fprintf(stderr, "cbc: --pileup takes at most one --region and no --regions-file\n"); return 1; }
         return cbc_cli_decompress_pileup(files[0], files[1], files[2], device, region, depth_exclude, min_alt, max_edits, alt_frac_ppm, by_strand, verbose);
     }
+    if (consensus) {                                              /* as for --pileup */
+        if (regions_file || n_regions > 1) { fprintf(stderr, "cbc: --consensus takes at most one --region and no --regions-file\n"); return 1; }
+        return cbc_cli_decompress_consensus(files[0], files[1], files[2], device, region, depth_exclude, call_min_depth, call_ppm, line_width,
+                                            (show_del ? 1u : 0u) | (fill_ref ? 2u : 0u) | (iupac ? 4u : 0u), max_edits, verbose);
+    }
     if (sam_cigar && (regions_file || n_regions > 1)) {            /* as for --pileup */
         fprintf(stderr, "cbc: --sam --cigar takes at most one --region and no --regions-file\n"); return 1;
     }
     if (depth_hist)
         return cbc_cli_decompress_hist(files[0], files[1], files[2], device, regions, n_regions, regions_file, hist_max, depth_exclude, verbose);
-    if (depth_excl_given && !depth_out && !bedcov && !pileup) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
+    if (depth_excl_given && !depth_out && !bedcov && !pileup && !consensus) { fprintf(stderr, "cbc: --depth-exclude-flags applies to --depth\n"); return 1; }
     if (stats_out) return cbc_cli_decompress_stats(files[0], files[1], files[2], device, regions, n_regions, regions_file, stats_exclude, stats_aln, max_edits, verbose);
     if (bedcov)                                                   /* no --thresholds, --count-reads, --quantiles: the plain summary */
         return cbc_cli_decompress_bedcov(files[0], files[1], files[2], device, regions, n_regions, regions_file, cov_window, cov_min_depth,

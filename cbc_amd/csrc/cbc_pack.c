@@ -1937,6 +1937,56 @@ API uint64_t cbc_unpack_pileup_ext_text_cap(const cbc_unpack_plan *u, uint32_t b
     return by_strand > 1u ? 0u : pileup_text_cap(u, b0, b1, contig, beg, end, smax, by_strand ? 102u + 7u * 11u : 102u);
 }
 
+/* ---- consensus (include/cbc_host.h) ----
+ * The record of a window holds its header, at most one byte per position (a called deletion drops its byte, or writes '*') and a
+ * newline behind every line_width bytes and behind the last: header + w + ceil(w / line_width) with w = end - beg + 1, exact when
+ * every position writes a byte.  w < 2^31, the header < 2^9: no wrap. */
+static uint32_t cons_ndig(uint64_t x) { uint32_t d = 1; for (; x >= 10u; x /= 10u) d++; return d; }
+
+API uint64_t cbc_unpack_consensus_text_cap(const cbc_unpack_plan *u, uint32_t contig, uint64_t beg, uint64_t end, uint32_t line_width,
+                                           uint32_t with_range)
+{
+    if (!u || u->long_reads || !u->names || !u->contig_name_off || contig >= u->n_contigs || beg < 1 || beg > end || end > 0x7fffffffull ||
+        line_width < 1 || line_width > 65535u || with_range > 1u) return 0;
+    const int64_t nl = sam_name_len(u, contig);
+    if (nl < 0) return 0;
+    const uint64_t w = end - beg + 1u;
+    return (uint64_t)nl + 2u + (with_range ? 2u + cons_ndig(beg) + cons_ndig(end) : 0u) + w + (w + line_width - 1u) / line_width;
+}
+
+/* The record of a window no read covers: every position is low depth (step 1 of the rule), so no device is asked.  The reference
+ * byte of position p of contig c is ref[sum over the contigs in front of c of (length + CBC_REF_PAD) + p - 1], as load_reference
+ * lays the FASTA out (cbc_unpack_plan_create holds table index == FASTA index).  A position past the contig's end is written as
+ * 'N'; cbc_unpack_region and cbc_unpack_contig_blocks clamp a window to its contig, so neither path meets one through them (the
+ * device call, given such a window directly, reads what the uploaded reference holds there: the zero pad, then the next contig). */
+API int64_t cbc_unpack_consensus_empty(const cbc_unpack_plan *u, uint32_t contig, uint64_t beg, uint64_t end, const cbc_consensus_opts *o,
+                                       uint32_t with_range, uint8_t *text, uint64_t text_cap, cbc_consensus_counts *counts)
+{
+    if (!u || !o || !counts || (text_cap && !text) || o->min_depth < 1 || o->call_ppm < 1 || o->call_ppm > 1000000u ||
+        (o->flags & ~(CBC_CONS_SHOW_DEL | CBC_CONS_FILL_REF | CBC_CONS_IUPAC))) return CBC_E_ARG;
+    const uint64_t need = cbc_unpack_consensus_text_cap(u, contig, beg, end, o->line_width, with_range);
+    if (need == 0 || need > text_cap) return CBC_E_ARG;
+    memset(counts, 0, sizeof *counts);
+    const char *nm = u->names + u->contig_name_off[contig];
+    uint64_t ref0 = 0;
+    for (uint32_t c = 0; c < contig; c++) ref0 += u->contig_len[c] + CBC_REF_PAD;
+    uint8_t *p = text;
+    p += with_range ? sprintf((char *)p, ">%s:%llu-%llu\n", nm, (unsigned long long)beg, (unsigned long long)end) : sprintf((char *)p, ">%s\n", nm);
+    const uint64_t w = end - beg + 1u;
+    for (uint64_t i = 0; i < w; i++) {
+        const uint64_t q = beg - 1u + i;
+        uint8_t b = 'N';
+        if (o->flags & CBC_CONS_FILL_REF) {
+            b = q < u->contig_len[contig] && ref0 + q < u->ref_bytes ? u->ref[ref0 + q] : (uint8_t)'N';
+            if ((b & 0xdfu) >= 'A' && (b & 0xdfu) <= 'Z') b |= 0x20u;
+        }
+        *p++ = b;
+        if ((i + 1u) % o->line_width == 0u || i + 1u == w) *p++ = '\n';
+    }
+    counts->emitted = counts->low_depth = w;
+    return (int64_t)(p - text);
+}
+
 /* ---- deletion-aware coverage (include/cbc_host.h) ----
  * Proof of the bound.  Under skip_deletions a read's deletion cuts its cover, so "K reads give at most 2K - 1 runs" no longer
  * holds.  A line stands for a maximal run of equal non-zero depth inside the window [beg, end]; runs are disjoint and each

@@ -305,6 +305,12 @@ def lib():
         L.cbc_gpu_set_depth_skip_deletions.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         L.cbc_gpu_last_pileup_ms.restype = ctypes.c_int
         L.cbc_gpu_last_pileup_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
+        L.cbc_gpu_decode_consensus.restype = ctypes.c_int
+        L.cbc_gpu_decode_consensus.argtypes = L.cbc_gpu_decode_pileup.argtypes[:13] + \
+            [ctypes.c_uint32, ctypes.POINTER(host.ConsensusOpts), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(host.ConsensusCounts), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.cbc_gpu_last_consensus_ms.restype = ctypes.c_int
+        L.cbc_gpu_last_consensus_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         L.cbc_gpu_decode_blocks_edits.restype = ctypes.c_int
         L.cbc_gpu_decode_blocks_edits.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
                                                   ctypes.POINTER(host.LdsCaps), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
@@ -336,7 +342,8 @@ EXPORTS = ["cbc_gpu_abi_version", "cbc_gpu_device_count", "cbc_gpu_init", "cbc_g
            "cbc_gpu_decode_coverage_ext", "cbc_gpu_last_coverage_ext_ms",
            "cbc_gpu_decode_coverage_quant", "cbc_gpu_last_coverage_quant_ms",
            "cbc_gpu_decode_pileup", "cbc_gpu_decode_pileup_ext", "cbc_gpu_last_pileup_ms", "cbc_gpu_decode_blocks_edits",
-           "cbc_gpu_decode_sam_cigar", "cbc_gpu_last_sam_cigar_ms", "cbc_gpu_set_depth_skip_deletions"]
+           "cbc_gpu_decode_sam_cigar", "cbc_gpu_last_sam_cigar_ms", "cbc_gpu_set_depth_skip_deletions",
+           "cbc_gpu_decode_consensus", "cbc_gpu_last_consensus_ms"]
 
 EDITS_PER_READ = 16           # CBC_EDITS_PER_READ: the library's default arena size, entries per read of a block
 
@@ -780,6 +787,69 @@ class Encoder:
     def last_pileup_ms(self):
         """(edits decode, zero + mark + events, scans, text) kernel milliseconds of the last decode_pileup, summed over its calls."""
         return self._summed_ms("_pileup_ms", "decode_pileup")
+
+    def decode_consensus(self, plan: "host.UnpackPlan", region=None, exclude_flags=0, min_depth=1, call_frac="0.75", line_width=60,
+                         show_del=False, fill_ref=False, iupac=False, edits_per_read=None, results=False, text_cap=None):
+        """The sequence the container's reads spell, as FASTA bytes (cbc_gpu_decode_consensus): region=None gives one record
+        `>NAME` per contig of the table, in table order -- contigs without reads included --, otherwise (NAME, NAME:BEG or
+        NAME:BEG-END) the one record `>NAME:BEG-END` of the window.  Per position, over the counts decode_pileup prints under the
+        same exclude_flags: depth < min_depth writes N (fill_ref: the reference base in lower case); else the most frequent of A, C,
+        G, T and deletion -- ties go to the reference's class, then in that order -- is called when count * 10^6 >= call_ppm *
+        depth, call_ppm = alt_frac_ppm(call_frac): a base writes its letter, a deletion drops the base (show_del: `*`); else with
+        iupac the code of the smallest top set of bases, closed under ties, that reaches the fraction; else N.  Insertions are
+        counted, not applied.  Lines hold line_width (1..65535) bytes.  The reference must have been uploaded.  A selection
+        without blocks (or reads) gets its all-low-depth record from the host (plan.consensus_empty) and runs nothing on the
+        device.  Returns (fasta, counts, reads kept) with counts = dict(emitted, ref, alt, del, ambiguous, low_depth, no_call,
+        ins_skipped), summed over the records; ins_skipped = positions with depth >= min_depth whose insertion events reach the
+        fraction (a trailing soft clip shows as one such event).  With results=True a fourth value, the per-block decode results
+        of the blocks used, and a failed block passes (it contributes nothing).  text_cap: size of the buffer of one call
+        (default: plan.consensus_text_cap of its window)."""
+        plan.sam_header()                                     # refuses what the text cannot carry, and long-read containers
+        ppm = alt_frac_ppm(call_frac)
+        if int(min_depth) < 1 or int(min_depth) > 0xffffffff:
+            raise ValueError("min_depth is in 1..4294967295")
+        if not 1 <= int(line_width) <= 65535:
+            raise ValueError("line_width is in 1..65535")
+        epr = EDITS_PER_READ if edits_per_read is None else int(edits_per_read)
+        if not 1 <= epr <= 510:
+            raise ValueError("edits_per_read is in 1..510")
+        opts = host.ConsensusOpts(int(min_depth), ppm, int(line_width), (1 if show_del else 0) | (2 if fill_ref else 0) | (4 if iupac else 0))
+        rng = region is not None
+        sels = [plan.region(region)] if rng else [plan.contig_blocks(c) for c in range(plan.n_contigs)]
+        out, total, n_kept, allres = [], host.ConsensusCounts().as_dict(), 0, []
+        self.last_consensus_text_bytes = 0
+        self._consensus_ms = None
+        caps, pay, _, _ = self._plan_args(plan)
+        for sel in sels:
+            nb = sel.b1 - sel.b0
+            if nb == 0 or int(plan.blocks[sel.b0:sel.b1]["n_reads"].sum()) == 0:
+                text, cnt = plan.consensus_empty(sel.contig, sel.beg, sel.end, opts, rng)
+            else:
+                blocks, ws, _ = self._gather(plan, slice(sel.b0, sel.b1))
+                off = int(plan.contig_name_off[sel.contig])
+                name = plan.names[off:].tobytes().split(b"\0", 1)[0]
+                cap = plan.consensus_text_cap(sel.contig, sel.beg, sel.end, opts.line_width, rng) if text_cap is None else int(text_cap)
+                buf = np.zeros(max(cap, 1), dtype=np.uint8)
+                res = np.zeros(nb, dtype=host.RESULT_DTYPE)
+                nbytes, nk, cc = ctypes.c_uint64(), ctypes.c_uint64(), host.ConsensusCounts()
+                rc = lib().cbc_gpu_decode_consensus(self._ctx, pay.ctypes.data, pay.size, blocks.ctypes.data, nb, ctypes.byref(caps),
+                                                    ws.ctypes.data, name, len(name), sel.beg, sel.end, sel.smax, int(exclude_flags), epr,
+                                                    ctypes.byref(opts), int(rng), buf.ctypes.data, cap, ctypes.byref(nbytes),
+                                                    ctypes.byref(cc), ctypes.byref(nk), res.ctypes.data)
+                self.last_consensus_text_bytes += int(nbytes.value)
+                self._check_blocks(rc, "cbc_gpu_decode_consensus", results)
+                self._add_ms("_consensus_ms", "cbc_gpu_last_consensus_ms", 4, must=True)
+                text, cnt = buf[:int(nbytes.value)].tobytes(), cc.as_dict()
+                n_kept += int(nk.value); allres.append(res)
+            out.append(text)
+            for k, v in cnt.items():
+                total[k] += v
+        text = b"".join(out)
+        return (text, total, n_kept, self._cat(allres)) if results else (text, total, n_kept)
+
+    def last_consensus_ms(self):
+        """(edits decode, zero + mark + events, scans, text) kernel milliseconds of the last decode_consensus, summed over its calls."""
+        return self._summed_ms("_consensus_ms", "decode_consensus")
 
     def decode_blocks_edits(self, plan: "host.UnpackPlan", smax, edits_per_read=None):
         """decode_blocks_span with the alignment of the reads with indels kept as well (cbc_gpu_decode_blocks_edits).  Returns

@@ -50,6 +50,19 @@ class LdsCaps(ctypes.Structure):
     _fields_ = [("cap_pos", ctypes.c_uint32), ("cap_var", ctypes.c_uint32)]
 
 
+class ConsensusOpts(ctypes.Structure):
+    """cbc_consensus_opts: flags = 1 show_del | 2 fill_ref | 4 iupac."""
+    _fields_ = [("min_depth", ctypes.c_uint32), ("call_ppm", ctypes.c_uint32), ("line_width", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class ConsensusCounts(ctypes.Structure):
+    """cbc_consensus_counts."""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("emitted", "ref", "alt", "del", "ambiguous", "low_depth", "no_call", "ins_skipped")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class Packed(ctypes.Structure):
     _fields_ = [
         ("recs", ctypes.POINTER(ReadRec)), ("n_recs", ctypes.c_uint64),
@@ -213,6 +226,13 @@ def lib():
         L.cbc_unpack_pileup_ext_text_cap.restype = ctypes.c_uint64
         L.cbc_unpack_pileup_ext_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                      ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]
+        L.cbc_unpack_consensus_text_cap.restype = ctypes.c_uint64
+        L.cbc_unpack_consensus_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64,
+                                                    ctypes.c_uint32, ctypes.c_uint32]
+        L.cbc_unpack_consensus_empty.restype = ctypes.c_int64
+        L.cbc_unpack_consensus_empty.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64,
+                                                 ctypes.POINTER(ConsensusOpts), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                                 ctypes.POINTER(ConsensusCounts)]
         L.cbc_unpack_depth_skipdel_text_cap.restype = ctypes.c_uint64
         L.cbc_unpack_depth_skipdel_text_cap.argtypes = [ctypes.POINTER(UnpackPlanC), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
@@ -761,6 +781,23 @@ class UnpackPlan:
         if by_strand:
             return int(lib().cbc_unpack_pileup_ext_text_cap(self._ptr, b0, b1, contig, beg, end, smax, 1))
         return int(lib().cbc_unpack_pileup_text_cap(self._ptr, b0, b1, contig, beg, end, smax))
+
+    def consensus_text_cap(self, contig, beg, end, line_width=60, with_range=False) -> int:
+        """The bytes of the consensus record of window [beg, end] of contig `contig` when every position writes a byte
+        (cbc_unpack_consensus_text_cap): exact with show_del, a bound otherwise; 0 for a window or a width it refuses."""
+        return int(lib().cbc_unpack_consensus_text_cap(self._ptr, contig, beg, end, line_width, int(bool(with_range))))
+
+    def consensus_empty(self, contig, beg, end, opts: "ConsensusOpts", with_range=False):
+        """The consensus record of a window no read covers, written on the host (cbc_unpack_consensus_empty): every position low
+        depth.  Returns (fasta bytes, counts dict)."""
+        cap = self.consensus_text_cap(contig, beg, end, opts.line_width, with_range)
+        text = np.zeros(max(cap, 1), dtype=np.uint8)
+        cnt = ConsensusCounts()
+        n = int(lib().cbc_unpack_consensus_empty(self._ptr, contig, beg, end, ctypes.byref(opts), int(bool(with_range)), text.ctypes.data,
+                                                  cap, ctypes.byref(cnt)))
+        if cap == 0 or n < 0:
+            raise ValueError("consensus: a window, a line width or an option the record cannot be written for")
+        return text[:n].tobytes(), cnt.as_dict()
 
     def sam_header(self) -> bytes:
         """@HD and one @SQ line per contig of the container's table (cbc_unpack_sam_header): what precedes the alignment

@@ -448,6 +448,54 @@ int  cbc_gpu_decode_pileup_ext(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_
 /* Kernel times of the most recent cbc_gpu_decode_pileup or _ext (HIP events on its stream): the edits decode; zeroing + mark(s) +
  * events; tile sums, their scan(s), the line count and its scan; the text. */
 int  cbc_gpu_last_pileup_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *events_ms, float *scan_ms, float *text_ms);
+
+/* ---- consensus ------------------------------------------------------------------------------------
+ * The sequence the kept reads spell over the window [beg, end] of contig `name`, as one FASTA record, called and written on the
+ * device behind the passes of cbc_gpu_decode_pileup.  The arguments up to edits_per_read, the kept reads, the alignment and the
+ * failure behaviour are that call's: a block that fails to decode (CBC_ST_EDITS included) contributes nothing and the call returns
+ * CBC_E_BLOCK behind the text of the others.
+ * Per position p, with c[0..3] = the aligned read bases of class A, C, G, T, c[4] = those of any other class, d = the deleted
+ * bases, ins = the insertion events -- the numbers cbc_gpu_decode_pileup prints for p under the same exclude_flags --, depth =
+ * c[0] + ... + c[4] + d, ref = the byte of the uploaded reference, and reaches(x) meaning x * 10^6 >= call_ppm * depth in exact
+ * integers (both products are below 2^52), in this order:
+ *   1  depth < min_depth: 'N'; with CBC_CONS_FILL_REF the reference byte in lower case (ref | 0x20 when ref & 0xDF is in A..Z,
+ *      the byte unchanged otherwise).
+ *   2  of the five candidates A, C, G, T, DEL with the counts c[0..3], d, the highest; among ties the reference's class when it is
+ *      one of them, otherwise the first in the order A, C, G, T, DEL.  When reaches(that count) the position is called: a base
+ *      writes its upper-case letter, DEL writes nothing -- the base is dropped from the sequence -- or '*' with CBC_CONS_SHOW_DEL.
+ *      The other class counts in depth and is never a candidate.
+ *   3  with CBC_CONS_IUPAC, when 2 did not call: for every base count t = c[i] > 0 let S(t) be the bases with c[j] >= t; the
+ *      largest t with reaches(sum of the counts of S(t)) writes the IUPAC letter of S(t) (R Y S W K M B D H V, N for all four);
+ *      none: 'N'.
+ *   4  otherwise 'N'.
+ * Insertions are NOT applied: the planes count insertion events, not their bases.  counts->ins_skipped is the number of positions
+ * with depth >= min_depth and reaches(ins); a trailing soft clip is stored as insertions and shows as one such event at the
+ * read's last aligned base.  ref is read where the window lies in the uploaded reference: a window is expected to end inside its
+ * contig (the selections of cbc_unpack_region and cbc_unpack_contig_blocks do); past it the bytes are the pad's and the next
+ * contig's, and only past the whole reference 'N'.
+ * The text: `>NAME\n` (with_range = 0) or `>NAME:BEG-END\n` (with_range = 1; 1-based, inclusive), then the E emitted bytes in
+ * position order, line_width a line, every line ending in '\n' -- the last too, no empty line, the header alone when E = 0:
+ * header + E + ceil(E / line_width) bytes; cbc_unpack_consensus_text_cap (include/cbc_host.h) gives the bound for E = the window.
+ * counts: emitted = E; ref, alt = called bases of the reference's class and of another; del = called deletions (emitted only with
+ * SHOW_DEL); ambiguous = letters of step 3; low_depth = step 1; no_call = the 'N' of steps 3 and 4: the six sum to the window.
+ * min_depth == 0, call_ppm outside 1..1 000 000, line_width outside 1..65 535, a flag bit beyond the three and with_range > 1 are
+ * CBC_E_ARG.  *text_bytes = bytes of text (also when text_cap is too small: CBC_E_ARG, nothing copied).  Blocks without a single
+ * read are as no blocks: CBC_OK and no text -- the record of such a window is cbc_unpack_consensus_empty's.  The window costs
+ * 4 + 28 bytes of device memory per position: CBC_E_NOMEM when that cannot be had. */
+#define CBC_CONS_SHOW_DEL 1u
+#define CBC_CONS_FILL_REF 2u
+#define CBC_CONS_IUPAC    4u
+typedef struct cbc_consensus_opts   { uint32_t min_depth, call_ppm, line_width, flags; } cbc_consensus_opts;
+typedef struct cbc_consensus_counts { uint64_t emitted, ref, alt, del, ambiguous, low_depth, no_call, ins_skipped; } cbc_consensus_counts;
+int  cbc_gpu_decode_consensus(cbc_gpu_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const cbc_dec_block_desc *blocks,
+                              uint32_t n_blocks, const cbc_lds_caps *caps, const uint64_t *window_start /* n_blocks */,
+                              const char *name, uint32_t name_bytes, uint64_t beg, uint64_t end, uint32_t smax,
+                              uint32_t exclude_flags, uint32_t edits_per_read, const cbc_consensus_opts *opts, uint32_t with_range,
+                              uint8_t *text, uint64_t text_cap, uint64_t *text_bytes, cbc_consensus_counts *counts,
+                              uint64_t *n_reads_kept, cbc_block_result *results /* n_blocks or NULL */);
+/* Kernel times of the most recent cbc_gpu_decode_consensus: the edits decode; zeroing + mark + events; tile sums, their scan, the
+ * call count and its scan; the text. */
+int  cbc_gpu_last_consensus_ms(cbc_gpu_ctx *ctx, float *decode_ms, float *events_ms, float *scan_ms, float *text_ms);
 /* cbc_gpu_decode_blocks_span with the edits reported as well (the decoder the pileup runs, with everything it leaves returned;
  * what the tests check it with): side[2 r] = the first arena entry of record r relative to its block's, side[2 r + 1] =
  * nDel | nIns << 16 (both 0 for a read without indels); block b owns arena entries [rec_base * edits_per_read, (rec_base +

@@ -239,6 +239,20 @@ uint64_t cbc_unpack_pileup_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint3
 uint64_t cbc_unpack_pileup_ext_text_cap(const cbc_unpack_plan *u, uint32_t b0, uint32_t b1, uint32_t contig, uint64_t beg, uint64_t end,
                                         uint32_t smax, uint32_t by_strand);
 
+/* Consensus (the record comes from cbc_gpu_decode_consensus).  cbc_unpack_consensus_text_cap: the bytes
+ * of the record of window [beg, end] of contig `contig` when every position writes a byte -- the header (`>NAME\n`, or
+ * `>NAME:BEG-END\n` with with_range = 1), w = end - beg + 1 bytes, ceil(w / line_width) newlines: exact under CBC_CONS_SHOW_DEL, a
+ * bound otherwise (a called deletion drops its byte).  0 for a plan cbc_unpack_sam_header refuses, a bad contig or window,
+ * line_width outside 1..65535 or with_range > 1.
+ * cbc_unpack_consensus_empty: the record of a window that no block touches (a contig without reads, a region without blocks),
+ * written on the host: every position is low depth, 'N', or with CBC_CONS_FILL_REF the plan's reference byte in lower case; a
+ * position past the contig's end is written as 'N' (the selections of cbc_unpack_region and cbc_unpack_contig_blocks hold none).  Returns the bytes written, and in *counts emitted = low_depth = w; CBC_E_ARG for
+ * the options cbc_gpu_decode_consensus refuses, a window the bound refuses, or text_cap below the bound. */
+uint64_t cbc_unpack_consensus_text_cap(const cbc_unpack_plan *u, uint32_t contig, uint64_t beg, uint64_t end, uint32_t line_width,
+                                       uint32_t with_range);
+int64_t  cbc_unpack_consensus_empty(const cbc_unpack_plan *u, uint32_t contig, uint64_t beg, uint64_t end, const cbc_consensus_opts *opts,
+                                    uint32_t with_range, uint8_t *text, uint64_t text_cap, cbc_consensus_counts *counts);
+
 /* Deletion-aware coverage (the text comes from cbc_gpu_decode_depth after
  * cbc_gpu_set_depth_skip_deletions).  A deletion cuts a read's cover in two, so the 2K - 1 runs of cbc_unpack_depth_text_cap no
  * longer hold.  A text_cap that always holds the bedGraph of blocks [b0, b1) of contig `contig` for the window [beg, end] and the
