@@ -552,7 +552,10 @@ CBC_FN void cbc_long_encode(const cbc_long_args &A, uint32_t blk, uint32_t *lds)
             }
             if (E.status == CBC_ST_OK && i != rl) E.fail(CBC_ST_ASSERT);              /* the CIGAR must consume the read exactly */
             if (second) { if (ROLE != CBC_ROLE_WALKER) flush_edits(strand); return n; }
-            if (!over && ecount) { W::store32_list(ebuf, ln + stored, eb, ln < ecount); stored += ecount; }
+            if (!over && ecount) {                                                  /* the last, partial batch: it too stays inside the half */
+                if (stored + ecount <= CBC_LONG_EDIT_HALF) { W::store32_list(ebuf, ln + stored, eb, ln < ecount); stored += ecount; }
+                else over = 1u;
+            }
             ecount = 0;
             return n;
         };

@@ -151,12 +151,17 @@ extern "C" __attribute__((visibility("default")))
 int emu_long_encode_blocks(const cbc_long_args *A)
 {
     g_emu_errors = 0;
-    std::vector<uint32_t> scratch((size_t)A->n_blocks * CBC_LONG_SCRATCH_WORDS + 64, 0xdeadbeefu);   /* the kernel zeroes what it uses */
-    cbc_long_args B = *A;
-    B.scratch = scratch.data();
-    for (uint32_t blk = 0; blk < B.n_blocks; blk++) {
+    /* every block as a batch of its own, so that its scratch is CBC_LONG_SCRATCH_WORDS and no more: the guard words behind it
+     * must come back untouched (on the GPU they are the next block's tables) */
+    const uint32_t guard = 256u;
+    for (uint32_t blk = 0; blk < A->n_blocks; blk++) {
+        std::vector<uint32_t> scratch((size_t)CBC_LONG_SCRATCH_WORDS + guard, 0xdeadbeefu);           /* the kernel zeroes what it uses */
+        cbc_long_args B = *A;
+        B.blocks = A->blocks + blk; B.results = A->results + blk; B.n_blocks = 1u;
+        B.scratch = scratch.data();
         std::vector<uint32_t> lds(cbc_long_lds_bytes(B.cap_pos) / 4, 0xdeadbeefu);
-        cbc_long_encode<WaveEmu, CBC_ROLE_FUSED>(B, blk, lds.data());
+        cbc_long_encode<WaveEmu, CBC_ROLE_FUSED>(B, 0u, lds.data());
+        for (uint32_t k = 0; k < guard; k++) if (scratch[CBC_LONG_SCRATCH_WORDS + k] != 0xdeadbeefu) { emu_oob("long encoder wrote past its block's scratch"); break; }
     }
     return g_emu_errors ? -100 : 0;
 }
